@@ -4,6 +4,14 @@
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus 2 --cpu-dry      (no GPU: the N > 1 plumbing over gloo, the CPU oracle per rank; a test)
+    python bench.py --gpus 1 ... --full     (the headline, then every other leg of the record: minutes)
+    python bench.py --gpus 1 ... --dump-outputs DIR   (also rank 0's results of the last timed step as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs is given and prints the line:
+the headline (value, ms_per_step), config and the roofline figures of the timed region itself (chain_frac,
+in_timed_region_*).  Everything else in the record below -- roofline's one-block-at-a-time pass (achieved, frac,
+mean_launch_ms), value_at_library_default_slots, real_data, cpu_baseline, the e2e* legs -- is measured after the timed
+steps with --full only; there each --no-* flag still leaves its leg out.
 
 With N > 1 and no launcher around it (WORLD_SIZE unset) the parent -- before any torch / GPU call -- starts
 torch.distributed.run as a child process, relays its stdout and exits with its code.
@@ -675,6 +683,79 @@ def all_devices_leg(line, args, cfg, bg, bv, blocks, sizes, world, release_devic
                 os.unlink(q)
 
 
+DUMP_SEED = 20130502
+DUMP_LINES_PER_BLOCK = 2048  # lines sampled from each block of the last step
+DUMP_CLASS_ROWS_PER_BLOCK = 128  # ... the first records of which also get their per-sample class codes
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(ctx, ptrs, sizes, out_dir):
+    """--dump-outputs: what a caller of the timed path receives for the blocks of the last timed step (every resident
+    block once, in order).  The bench hook leaves its results on the device, so each block goes once more through the
+    same ctx by the library's call for device-resident text (bvcf_submit_device + bvcf_collect: the same kernel chain)
+    and the collected records are written as DIR/<name>.npy.  A fixed, seeded sample of lines per block, with every
+    output record of those lines in order (layout fields such as cmap_off or rec_first are left out: they may differ
+    between builds that compute the same thing), the per-sample class codes of the first records of the sample, every
+    line-level error, and per block the counts over ALL its lines (block_counts: lines, lines that passed, output records,
+    errors).  Integers go as float64 (exact below 2^53), class codes as float32.  An array with nothing in it (no errors,
+    no class maps on sites-only input) is not written: every file holds data."""
+    import numpy as np
+    import bystro_vcf_amd as bv
+    rng = np.random.default_rng(DUMP_SEED)
+    line_cols = ("status", "site_type", "n_rec", "n_fields", "off", "len")
+    rec_cols = ("pos", "alt_idx", "alt_off", "alt_len", "ac", "an", "n_het", "n_hom", "n_miss", "ref", "alt_base", "kind",
+                "site_type", "trtv")
+    out = {"line_block": [], "line_index": [], "record_block": [], "record_line": [], "record_pos_text": [], "classes": [],
+           "classes_record": [], "err_block": [], "err_line": [], "err_alt_no": [], "err_code": [], "block_counts": []}
+    out.update({"line_" + k: [] for k in line_cols})
+    out.update({"record_" + k: [] for k in rec_cols})
+    for b, (p, n) in enumerate(zip(ptrs, sizes)):
+        ctx.submit_device(p, n, seq=b)
+        batch = ctx.collect()
+        n_lines = int(batch.n_lines)
+        out["block_counts"].append([[n_lines, int((batch.lines["status"] == bv.LINE_OK).sum()), int(batch.lines["n_rec"].sum()),
+                                     len(batch.errs)]])
+        pick = np.sort(rng.choice(n_lines, size=min(n_lines, DUMP_LINES_PER_BLOCK), replace=False)) if n_lines else np.zeros(0, np.int64)
+        L = batch.lines[pick]
+        out["line_block"].append(np.full(len(pick), b))
+        out["line_index"].append(pick)
+        for k in line_cols:
+            out["line_" + k].append(L[k])
+        slots = [(int(i), s) for i in pick for s in batch.record_slots(int(i))]
+        line_of = np.array([i for i, _ in slots], dtype=np.int64)
+        R = batch.alleles[np.array([s for _, s in slots], dtype=np.int64)]
+        out["record_block"].append(np.full(len(slots), b))
+        out["record_line"].append(line_of)
+        out["record_pos_text"].append(R["flags"] & 1)
+        for k in rec_cols:
+            out["record_" + k].append(R[k])
+        if batch.n_samples and len(batch.cmap):
+            first = sum(len(x) for x in out["record_block"][:-1])
+            for j, r in enumerate(R[:DUMP_CLASS_ROWS_PER_BLOCK]):
+                if int(r["cmap_off"]) != bv.NO_CMAP:
+                    out["classes"].append(batch.classes(r))
+                    out["classes_record"].append(first + j)
+        e = np.sort(batch.errs, order=["line", "alt_no", "code"])
+        out["err_block"].append(np.full(len(e), b))
+        for k in ("line", "alt_no", "code"):
+            out["err_" + k].append(e[k])
+        del batch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for k, parts in out.items():
+        if k == "classes":
+            if parts:
+                arrays[k] = np.stack(parts).astype(np.float32)
+        else:
+            arrays[k] = np.array(parts, dtype=np.float64) if k == "classes_record" else np.concatenate(parts).astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    for k, a in arrays.items():
+        if a.size:
+            np.save(os.path.join(out_dir, k + ".npy"), a)
+    return total
+
+
 LIBRARY_DEFAULT_SLOTS = 3  # bvcf_params.n_slots == 0 (include/bvcf.h; 2 until round 5)
 LINE_LIMIT = 3072  # bytes: the driver keeps 8 KB of stdout; the verdict asks for <= 3 KB
 
@@ -901,7 +982,16 @@ def main():
     ap.add_argument("--over", default="", help="experiment: row-model knobs of the profile changed, e.g. p_multi=0,p_indel=0")
     ap.add_argument("--all-devices-rows", type=int, default=6_200_000,
                     help="N > 1: rows of rank 0's `bystro-vcf --devices 0,..,N-1` leg after the timed region; 0 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything besides the headline: the one-block-at-a-time roofline pass, the "
+                         "library-default slots rate, the real-data leg, cpu_baseline and the end-to-end CLI legs (each still "
+                         "subject to its --no-* flag); without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write rank 0's results for the blocks of the last step as DIR/<name>.npy "
+                         "(a fixed, seeded sample of lines; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     d_rows, d_blocks = SHAPES[args.profile]
     args.rows = args.rows or d_rows
     args.blocks = args.blocks or d_blocks
@@ -1001,7 +1091,9 @@ def main():
     # outside the timed region (rank 0): the same chain strictly one block after the other, for the dominant
     # kernel's duration when it has the GPU to itself
     alone_ms, alone_chain_ms, default_slots_rate = None, None, None
-    if rank == 0:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(ctx, ptrs, sizes, args.dump_outputs)
+    if rank == 0 and args.full:
         a_chain, alone, _ = ctx.bench_device(ptrs, sizes, max(args.blocks, 8), slots=1)
         alone_ms = sum(alone) / len(alone)
         alone_chain_ms = sum(a_chain) / len(a_chain)
@@ -1063,8 +1155,8 @@ def main():
                 "traffic_source": "profiles/k_gt_hbm_traffic.json (rocprofv3 --pmc passes, tools/derive_traffic.py); not measured in this run" if pmc else None,
                 "algorithmic_bytes_per_launch": alg_bytes,
                 "mean_launch_ms": alone_ms,
-                "how": "HIP events around the kernel on its launch stream, one block at a time (the kernel alone on the GPU), "
-                       "%d launches right after the timed region" % max(args.blocks, 8),
+                "how": ("HIP events around the kernel on its launch stream, one block at a time (the kernel alone on the GPU), "
+                        "%d launches right after the timed region" % max(args.blocks, 8)) if alone_ms else None,
                 # what the whole chain sustains inside the timed region: bytes per block / wall time per block
                 "chain_frac": mean_bytes / (ms_per_block * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                 "chain_GBps": mean_bytes / (ms_per_block * 1e-3) / 1e9,
@@ -1085,17 +1177,17 @@ def main():
         if multi:
             line["ranks_seen"] = ranks_seen
             line["per_rank_variants_per_s"] = per_rank
-        if not multi and streaming and args.profile == "c3" and not args.golden and not args.no_real_data:
+        if args.full and not multi and streaming and args.profile == "c3" and not args.golden and not args.no_real_data:
             try:
                 line["real_data"] = real_data_leg(bv, bg, cfg, local_rank, args, kernel, achieved)
             except Exception as exc:
                 line["real_data"] = {"error": repr(exc)[:300]}
-        want_host_legs = not multi and not args.golden and not (args.no_e2e and args.no_cpu_baseline)
+        want_host_legs = args.full and not multi and not args.golden and not (args.no_e2e and args.no_cpu_baseline)
         if want_host_legs:
             host_legs(line, args, cfg, bg, bv, blocks, sizes, rank, local_rank, ctx.close)
     if multi:
         # every rank lets go of its device (the CLI of rank 0 is about to use all of them), then waits on the host
-        if rank == 0 and args.all_devices_rows > 0 and not args.no_e2e and not args.golden:
+        if rank == 0 and args.full and args.all_devices_rows > 0 and not args.no_e2e and not args.golden:
             all_devices_leg(line, args, cfg, bg, bv, blocks, sizes, world, ctx.close)
         ctx.close()
         blocks.clear()

@@ -96,3 +96,67 @@ def test_gpus_1_cpu_dry_runs_in_process_and_child_failure_is_relayed():
     # a bad flag inside the children: the parent's exit code is not 0 and no line is invented
     rc, out, err = _run_bench(["--gpus", "2", "--cpu-dry", "--profile", "nope"])
     assert rc != 0 and not any(ln.startswith('{"metric"') for ln in out)
+
+
+def test_dump_outputs_samples_the_same_lines_and_keeps_the_limit(tmp_path):
+    """bench.dump_outputs over a stand-in ctx (no GPU): every block of the step is submitted and collected once, the same
+    seeded lines come out of two calls, each record follows its line in order, class codes match the map, errors are sorted"""
+    import numpy as np
+    import bystro_vcf_amd as bv
+
+    ns, n_lines = 10, 5000
+    errs = True
+
+    class Batch(bv.Batch):
+        def __init__(self, seq):
+            self.n_lines, self.n_samples, self.cmap_stride = n_lines, ns, 16
+            self.lines = np.zeros(n_lines, dtype=bv.LINE_DTYPE)
+            self.lines["n_rec"] = 1 + (np.arange(n_lines) % 3 == 0)  # every third line has a second record behind the lines
+            extra = np.nonzero(self.lines["n_rec"] == 2)[0]
+            self.lines["rec_first"][extra] = n_lines + np.arange(len(extra))
+            self.alleles = np.zeros(n_lines + len(extra), dtype=bv.ALLELE_DTYPE)
+            self.alleles["pos"][:n_lines] = 1000 * seq + np.arange(n_lines)
+            self.alleles["line"][n_lines:] = extra
+            self.alleles["alt_idx"][n_lines:] = 1
+            self.alleles["cmap_off"] = np.arange(len(self.alleles)) * 16
+            self.cmap = np.random.default_rng(seq).integers(0, 256, 16 * len(self.alleles), dtype=np.uint8)
+            self.errs = np.zeros(3 if errs else 0, dtype=bv.ERR_DTYPE)
+            if errs:
+                self.errs["line"] = [7, 2, 5]
+
+    class Ctx:
+        def __init__(self):
+            self.seen = []
+
+        def submit_device(self, p, n, seq):
+            self.seen.append((p, n, seq))
+
+        def collect(self):
+            return Batch(self.seen[-1][2])
+
+    outs = []
+    for run in range(2):
+        ctx = Ctx()
+        total = bench.dump_outputs(ctx, [11, 22, 33], [100, 200, 300], str(tmp_path / str(run)))
+        assert ctx.seen == [(11, 100, 0), (22, 200, 1), (33, 300, 2)] and total <= bench.DUMP_LIMIT_BYTES
+        d = tmp_path / str(run)
+        outs.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = outs
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(x.dtype in (np.float32, np.float64) and x.size for x in a.values())
+    assert a["block_counts"].tolist() == [[n_lines, n_lines, n_lines + (np.arange(n_lines) % 3 == 0).sum(), 3]] * 3
+    k = bench.DUMP_LINES_PER_BLOCK
+    assert len(a["line_index"]) == 3 * k and (np.diff(a["line_index"][:k]) > 0).all()
+    lines = a["line_index"]
+    assert len(a["record_line"]) == len(lines) + (lines % 3 == 0).sum()
+    first = a["record_alt_idx"] == 0
+    assert (a["record_pos"][first] == 1000 * a["record_block"][first] + a["record_line"][first]).all()
+    assert (a["record_line"][~first] == a["record_line"][np.nonzero(~first)[0] - 1]).all()  # a line's second record follows its first
+    assert a["classes"].shape == (3 * bench.DUMP_CLASS_ROWS_PER_BLOCK, ns)
+    assert a["err_line"].tolist() == [2, 5, 7] * 3
+    # a step without errors: no err_* file (no empty arrays), the counts say 0
+    errs = False
+    bench.dump_outputs(Ctx(), [11], [100], str(tmp_path / "no_errs"))
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "no_errs"))
+    assert not [f for f in names if f.startswith("err_")] and "classes" in names
+    assert np.load(tmp_path / "no_errs" / "block_counts.npy")[0, 3] == 0

@@ -54,7 +54,7 @@ def test_bench_main_takes_the_multi_rank_path_with_one_rank():
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                BVCF_BENCH_FORCE_MULTI="1")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "2",
-                        "--rows", "12000", "--all-devices-rows", "24000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env,
+                        "--rows", "12000", "--all-devices-rows", "24000", "--full"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env,
                        timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     last = p.stdout.decode().splitlines()[-1]
@@ -63,3 +63,49 @@ def test_bench_main_takes_the_multi_rank_path_with_one_rank():
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and len(line["per_rank_variants_per_s"]) == 1 and line["value"] > 0
     assert line["roofline"]["frac"] > 0 and "cpu_baseline" not in line  # (cpu_baseline: rank 0 at N == 1 only)
     assert line["e2e_all_devices_text"]["sha256_equal"] is True and line["e2e_all_devices_bgzf"]["wall_s"] > 0
+
+
+def test_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: the line has the headline and no leg
+    that --full adds, `steps` is K, and two runs with the same arguments write the same arrays (float32 / float64, at
+    most 64 MB) whose records are the ones the row model makes (configs[2]: biallelic SNPs, an == 2 * samples)"""
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--blocks", "2", "--rows", "12000", "--dump-outputs", str(d)], stdout=subprocess.PIPE,
+                           stderr=subprocess.PIPE, env=env, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        line = json.loads(p.stdout.decode().splitlines()[-1])
+        assert line["metric"] == "variants/sec" and line["unit"] == "variants/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "u8" and line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] - 2 * 12000 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+        for k in ("cpu_baseline", "e2e", "e2e_bgzf", "real_data_frac", "value_at_library_default_slots"):
+            assert k not in line, k
+        assert line["roofline"]["frac"] is None and line["roofline"]["chain_frac"] > 0
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sum(a.nbytes for a in arrays.values()) <= bench.DUMP_LIMIT_BYTES
+        assert all(a.dtype in (np.float32, np.float64) and a.size for a in arrays.values())
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    n = 2 * min(12000, bench.DUMP_LINES_PER_BLOCK)
+    assert len(a["line_index"]) == n and len(a["record_pos"]) == n and (a["line_status"] == 0).all()
+    assert (a["record_an"] == 2 * 2504).all() and (a["record_ac"] == a["record_n_het"] + 2 * a["record_n_hom"]).all()
+    # every row of the step's blocks passes and gives one record; configs[2]'s rows have no errors, so no err_* file
+    assert a["block_counts"].tolist() == [[12000, 12000, 12000, 0]] * 2 and not [k for k in a if k.startswith("err_")]
+    cls = a["classes"]
+    assert cls.shape[1] == 2504 and len(cls) == len(a["classes_record"]) > 0
+    rec = a["classes_record"].astype(int)
+    assert ((cls == 1).sum(axis=1) == a["record_n_het"][rec]).all() and ((cls == 2).sum(axis=1) == a["record_n_hom"][rec]).all()

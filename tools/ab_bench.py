@@ -21,7 +21,7 @@ res = {l: [] for l in libs}
 for r in range(rounds):
     for l in libs:
         env = dict(os.environ, BVCF_LIB=os.path.abspath(l))
-        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1",
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "4", "--warmup", "1",
                                        "--no-cpu-baseline", "--no-e2e", "--slots", "1", "--blocks", "4"] + extra, env=env, stderr=subprocess.DEVNULL)
         d = json.loads(out.decode().strip().splitlines()[-1])
         res[l].append((d["roofline"]["mean_launch_ms"], d["roofline"]["chain_ms_one_block_at_a_time"]))

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 stats() {  # tag, bench args...
   local tag=$1; shift
   rm -rf /tmp/p_$tag
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
   cp "$(find /tmp/p_$tag -name '*kernel_stats.csv' | head -1)" $OUT/${tag}_kernel_stats.csv
   grep '^{' $OUT/$tag.log > $OUT/${tag}_bench_line.json || true
   echo "== $tag"; grep bvcf_dev $OUT/${tag}_kernel_stats.csv | cut -c1-100 | head -6
@@ -21,5 +21,5 @@ stats bench_c5h_haploid_calls_one_block_at_a_time --profile c5h --slots 1
 stats bench_c5_general_stream --profile c5
 stats bench_c5_general_stream_one_block_at_a_time --profile c5 --slots 1
 cd $R
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -c 300 $OUT/bench_default.json

@@ -8,11 +8,11 @@ cd /tmp && export TMPDIR=/tmp
 for rnd in 1 2; do
 for lib in ${LIBS:-libbvcf.so libbvcf_prev.so}; do
   export BVCF_LIB=$R/bystro-vcf_amd/$lib
-  python3 $R/bench.py --profile c2 --no-e2e --no-cpu-baseline 2>> $OUT/err.txt | grep '^{' >> $OUT/bench_c2_$lib.jsonl || exit 1
-  python3 $R/bench.py --profile c2 --no-e2e --no-cpu-baseline --slots 1 2>> $OUT/err.txt | grep '^{' >> $OUT/bench_c2_slots1_$lib.jsonl || exit 1
+  python3 $R/bench.py --full --profile c2 --no-e2e --no-cpu-baseline 2>> $OUT/err.txt | grep '^{' >> $OUT/bench_c2_$lib.jsonl || exit 1
+  python3 $R/bench.py --full --profile c2 --no-e2e --no-cpu-baseline --slots 1 2>> $OUT/err.txt | grep '^{' >> $OUT/bench_c2_slots1_$lib.jsonl || exit 1
   if [ $rnd = 1 ]; then
     rm -rf /tmp/prof_c2
-    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python3 $R/bench.py --profile c2 --no-e2e --no-cpu-baseline --slots 1 > /dev/null 2>> $OUT/err.txt || exit 1
+    rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c2 -- python3 $R/bench.py --full --profile c2 --no-e2e --no-cpu-baseline --slots 1 > /dev/null 2>> $OUT/err.txt || exit 1
     cp $(find /tmp/prof_c2 -name '*kernel_stats.csv' | head -1) $OUT/c2_${lib}_one_block_at_a_time_kernel_stats.csv
     echo "== $lib"; grep "bvcf_dev" $OUT/c2_${lib}_one_block_at_a_time_kernel_stats.csv | cut -d, -f1-4 | cut -c1-110
   fi

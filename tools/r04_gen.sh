@@ -8,7 +8,7 @@ for rnd in 1 2; do
 for lib in ${LIBS:-libbvcf.so libbvcf_prevgen.so}; do
   [ -f $R/bystro-vcf_amd/$lib ] || continue
   for prof in ${PROFILES:-c5 c5h}; do
-    BVCF_LIB=$R/bystro-vcf_amd/$lib python3 $R/bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data >> $OUT/bench_${prof}_$lib.jsonl 2>> $OUT/bench.err || exit 1
+    BVCF_LIB=$R/bystro-vcf_amd/$lib python3 $R/bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data >> $OUT/bench_${prof}_$lib.jsonl 2>> $OUT/bench.err || exit 1
   done
 done
 done

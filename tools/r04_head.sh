@@ -19,7 +19,7 @@ done
 for lib in ${LIBS:-libbvcf.so libbvcf_oldhead.so}; do
   [ -f $R/bystro-vcf_amd/$lib ] || continue
   for prof in c3 c4; do
-    BVCF_LIB=$R/bystro-vcf_amd/$lib python3 $R/bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data > $OUT/bench_${prof}_$lib.json 2>> $OUT/bench.err || exit 1
+    BVCF_LIB=$R/bystro-vcf_amd/$lib python3 $R/bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data > $OUT/bench_${prof}_$lib.json 2>> $OUT/bench.err || exit 1
   done
 done
 echo head done

@@ -7,7 +7,7 @@ mkdir -p $OUT
 for i in 1 2; do
   for t in _r03 .; do
     n=$([ $t = . ] && echo head || echo r03)
-    (cd $R/$t && python3 bench.py --no-e2e --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/${n}_$i.json) || exit 1
+    (cd $R/$t && python3 bench.py --full --no-e2e --no-cpu-baseline 2>/dev/null | grep '^{' > $OUT/${n}_$i.json) || exit 1
     python3 - $OUT/${n}_$i.json $n <<'P'
 import json, sys
 d = json.loads(open(sys.argv[1]).read()); r = d["roofline"]; rd = d.get("real_data", {})

@@ -10,7 +10,7 @@ rot=("${libs[@]:$(( (rep - 1) % ${#libs[@]} ))}" "${libs[@]:0:$(( (rep - 1) % ${
 for prof in $profs; do
 for lib in "${rot[@]}"; do
   name=${prof}_$(basename $(dirname $lib))_$rep
-  BVCF_LIB=$PWD/$lib python3 bench.py --no-e2e --no-cpu-baseline --no-real-data --profile $prof > $O/$name.out 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; continue; }
+  BVCF_LIB=$PWD/$lib python3 bench.py --full --no-e2e --no-cpu-baseline --no-real-data --profile $prof > $O/$name.out 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; continue; }
   python3 - $O/$name.out "$name" <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]) if x.startswith("{")][-1]; d=json.loads(l)

@@ -8,7 +8,7 @@ for rep in 1 2; do
 for lib in "$@"; do
   tag=${prof}_$(basename $(dirname $lib))_s${slots}_$rep
   rm -rf /tmp/p_$tag
-  BVCF_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e --no-real-data --profile $prof --slots $slots > $OUT/$tag.log 2>&1
+  BVCF_LIB=$R/$lib rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-e2e --no-real-data --profile $prof --slots $slots > $OUT/$tag.log 2>&1
   cp "$(find /tmp/p_$tag -name '*kernel_stats.csv' | head -1)" $OUT/${tag}_kernel_stats.csv
   echo "== $tag"
   python3 - $OUT/${tag}_kernel_stats.csv <<'PY'

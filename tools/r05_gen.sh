@@ -11,7 +11,7 @@ for prof in c5 c5h; do
   python tools/ab_bench.py bystro-vcf_amd/libbvcf_base.so bystro-vcf_amd/libbvcf.so 3 -- --profile $prof --no-real-data > $OUT/ab_alone_$prof.txt 2>&1
   cat $OUT/ab_alone_$prof.txt
   for rnd in 1 2; do for lib in libbvcf_base.so libbvcf.so; do
-    BVCF_LIB=$R/bystro-vcf_amd/$lib python bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data | tail -1 > $OUT/line.json
+    BVCF_LIB=$R/bystro-vcf_amd/$lib python bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data | tail -1 > $OUT/line.json
     python -c "import json,sys; d=json.load(open('$OUT/line.json')); print('$prof $lib value %.1f M/s  alone %.4f ms frac %.3f chain_frac %.3f' % (d['value']/1e6, d['roofline']['mean_launch_ms'], d['roofline']['frac'], d['roofline']['chain_frac']))" | tee -a $OUT/inflight.txt
   done; done
 done

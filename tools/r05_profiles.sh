@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 stats() {  # tag, bench args...
   local tag=$1; shift
   rm -rf /tmp/p_$tag
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e --no-real-data "$@" > $OUT/$tag.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-e2e --no-real-data "$@" > $OUT/$tag.log 2>&1
   cp "$(find /tmp/p_$tag -name '*kernel_stats.csv' | head -1)" $OUT/${tag}_kernel_stats.csv
   grep '^{"metric' $OUT/$tag.log | tail -1 > $OUT/${tag}_bench_line.json || true
   echo "== $tag"; cut -d, -f1-4 $OUT/${tag}_kernel_stats.csv | cut -c1-120 | head -8
@@ -19,12 +19,12 @@ stats() {  # tag, bench args...
 pmc() {  # counter, tag, bench args...
   local ctr=$1 tag=$2; shift 2
   rm -rf /tmp/q_$tag
-  rocprofv3 --pmc $ctr --output-format csv -d /tmp/q_$tag -- python3 $R/bench.py --steps 1 --warmup 0 --blocks 3 --no-cpu-baseline --no-e2e --no-real-data "$@" > $OUT/$tag.log 2>&1
+  rocprofv3 --pmc $ctr --output-format csv -d /tmp/q_$tag -- python3 $R/bench.py --full --steps 1 --warmup 0 --blocks 3 --no-cpu-baseline --no-e2e --no-real-data "$@" > $OUT/$tag.log 2>&1
   cp "$(find /tmp/q_$tag -name '*counter_collection.csv' | head -1)" $OUT/$tag.csv
 }
 : > $OUT/bench_unprofiled_lines.json
 for prof in c3 c4 c2 c5 c5h; do
-  python3 $R/bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data 2>/dev/null | grep '^{"metric' | tail -1 >> $OUT/bench_unprofiled_lines.json
+  python3 $R/bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data 2>/dev/null | grep '^{"metric' | tail -1 >> $OUT/bench_unprofiled_lines.json
 done
 echo "unprofiled lines done"
 stats bench_c3_streaming --path 2

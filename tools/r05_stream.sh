@@ -14,7 +14,7 @@ for prof in ${PROFILES:-c3 c4}; do
   python tools/ab_bench.py $(for l in $LIBS; do echo bystro-vcf_amd/$l; done) 3 -- --profile $prof --no-real-data > $OUT/ab_alone_$prof.txt 2>&1
   cat $OUT/ab_alone_$prof.txt
   for rnd in 1 2; do for lib in $LIBS; do
-    BVCF_LIB=$R/bystro-vcf_amd/$lib python bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data | tail -1 > $OUT/line.json
+    BVCF_LIB=$R/bystro-vcf_amd/$lib python bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data | tail -1 > $OUT/line.json
     python -c "import json,sys; d=json.load(open('$OUT/line.json')); print('$prof $lib value %.1f M/s  alone %.4f ms frac %.3f chain_frac %.3f chain alone %.4f' % (d['value']/1e6, d['roofline']['mean_launch_ms'], d['roofline']['frac'], d['roofline']['chain_frac'], d['roofline']['chain_ms_one_block_at_a_time']))" | tee -a $OUT/inflight.txt
   done; done
 done

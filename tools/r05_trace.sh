@@ -3,7 +3,7 @@
 O=gpurun_out/trace; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 for prof in c4 c3; do
-rocprofv3 --kernel-trace --output-format csv -d $R/$O/$prof -- python3 $R/bench.py --profile $prof --no-e2e --no-cpu-baseline --no-real-data --steps 6 --warmup 2 > $R/$O/$prof.out 2> $R/$O/$prof.err || { tail -5 $R/$O/$prof.err; exit 1; }
+rocprofv3 --kernel-trace --output-format csv -d $R/$O/$prof -- python3 $R/bench.py --full --profile $prof --no-e2e --no-cpu-baseline --no-real-data --steps 6 --warmup 2 > $R/$O/$prof.out 2> $R/$O/$prof.err || { tail -5 $R/$O/$prof.err; exit 1; }
 f=$(find $R/$O/$prof -name "*kernel_trace.csv" | head -1)
 python3 - $f $R/$O/${prof}_bvcf_trace.csv <<'PY'
 import csv,sys

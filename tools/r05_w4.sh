@@ -3,7 +3,7 @@
 # without the LDS request that keeps k_stream at two workgroups per CU over all blocks (experiments builds)
 set -o pipefail
 O=gpurun_out/w4; mkdir -p $O
-run() { name=$1; shift; python3 bench.py --no-e2e --no-cpu-baseline --no-real-data "$@" > $O/$name.out 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; return 0; }
+run() { name=$1; shift; python3 bench.py --full --no-e2e --no-cpu-baseline --no-real-data "$@" > $O/$name.out 2> $O/$name.err || { echo "$name failed"; tail -3 $O/$name.err; return 0; }
   python3 - $O/$name.out "$name" <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]) if x.startswith("{")][-1]; d=json.loads(l)

@@ -12,7 +12,7 @@ WHAT=${@:-stats pmc line}
 stats() {  # tag, bench args...
   local tag=$1; shift
   rm -rf /tmp/p_$tag
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_$tag -- python3 $R/bench.py --full --steps 6 --warmup 1 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
   cp "$(find /tmp/p_$tag -name '*kernel_stats.csv' | head -1)" $OUT/${tag}_kernel_stats.csv
   grep '^{' $OUT/$tag.log > $OUT/${tag}_bench_line.json || true
   echo "== $tag"; cat $OUT/${tag}_kernel_stats.csv | cut -d, -f1-4 | head -12
@@ -20,7 +20,7 @@ stats() {  # tag, bench args...
 pmc() {  # counter, tag, bench args...
   local ctr=$1 tag=$2; shift 2
   rm -rf /tmp/q_$tag
-  rocprofv3 --pmc $ctr --output-format csv -d /tmp/q_$tag -- python3 $R/bench.py --steps 1 --warmup 0 --blocks 3 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
+  rocprofv3 --pmc $ctr --output-format csv -d /tmp/q_$tag -- python3 $R/bench.py --full --steps 1 --warmup 0 --blocks 3 --no-cpu-baseline --no-e2e "$@" > $OUT/$tag.log 2>&1
   cp "$(find /tmp/q_$tag -name '*counter_collection.csv' | head -1)" $OUT/$tag.csv
 }
 for w in $WHAT; do
@@ -54,7 +54,7 @@ for w in $WHAT; do
       ;;
     line)
       cd $R
-      python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+      python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
       cat $OUT/bench_default.json
       cd /tmp
       ;;
