@@ -48,7 +48,7 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
 EXPORTS = [
     "bvcf_create", "bvcf_destroy", "bvcf_last_error", "bvcf_version", "bvcf_reserve", "bvcf_set_sample_names", "bvcf_set_row_format", "bvcf_alloc_pinned", "bvcf_alloc_pinned_near", "bvcf_warmup",
     "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_counters", "bvcf_sum_counters",
-    "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_free",
+    "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
 ]
 
@@ -71,7 +71,7 @@ class Config(C.Structure):
         ("keep_pos", C.c_uint8), ("keep_qual", C.c_uint8), ("normalize_header", C.c_uint8),
         ("leave_teardown_to_exit", C.c_uint8), ("reserved", C.c_uint8 * 2), ("device", C.c_int32), ("n_format_threads", C.c_uint32),
         ("max_batch_bytes", C.c_uint64), ("sample_list_path", C.c_char_p),
-        ("dosage_path", C.c_char_p), ("no_out", C.c_uint8), ("reserved3", C.c_uint8 * 3),
+        ("dosage_path", C.c_char_p), ("no_out", C.c_uint8), ("out_bgzf", C.c_uint8), ("reserved3", C.c_uint8 * 2),
         ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)),
     ]
 
@@ -221,6 +221,7 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         keep.append(str(cfg["dosageOutput"]).encode())
         c.dosage_path = keep[-1]
     c.no_out = int(cfg.get("noOut", False))
+    c.out_bgzf = int(cfg.get("compressOutput", "none") == "bgzf")  # bvcf_run_fd only
     if cfg.get("devices"):  # bvcf_run_fd only: the device list the blocks are dealt to
         arr = (C.c_int32 * len(cfg["devices"]))(*cfg["devices"])
         keep.append(arr)
@@ -281,6 +282,29 @@ def bgzf_inflate_device(comp, cap=None, device=0):
     n = C.c_size_t()
     rc = lib.bvcf_bgzf_inflate_device(device, comp, len(comp), buf, cap, C.byref(n))
     return rc, (buf.raw[:n.value] if rc == 0 else b""), n.value
+
+
+lib.bvcf_bgzf_deflate_device.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t,
+                                         C.POINTER(C.c_size_t)]
+PIECE = 65280  # text per BGZF member of bgzf_deflate_device / --compressOutput bgzf
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def bgzf_bound(n):
+    """BVCF_BGZF_BOUND(n): the most bgzf_deflate_device can produce for n bytes of text"""
+    return (n + PIECE - 1) // PIECE * 65311 + 28
+
+
+def bgzf_deflate_device(data, add_eof=True, device=0):
+    """text -> BGZF members (one per 65 280 bytes) through k_deflate / k_crc32 / k_bgzf_pack on the device"""
+    data = bytes(data)
+    cap = bgzf_bound(len(data))
+    buf = C.create_string_buffer(cap)
+    n = C.c_size_t()
+    rc = lib.bvcf_bgzf_deflate_device(device, data, len(data), int(bool(add_eof)), buf, cap, C.byref(n))
+    if rc:
+        raise BvcfError(rc, "bvcf_bgzf_deflate_device")
+    return buf.raw[:n.value]
 
 
 def decompress(data, n_threads=0):

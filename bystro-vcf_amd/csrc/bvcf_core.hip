@@ -6,6 +6,7 @@
 #include "bvcf_device.hip.h"
 #include "../../include/bvcf_bench.h"
 #include "bvcf_bgzf.h"
+#include "bvcf_bgzf_out.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so.1 is dlopen'ed by bvcf_allreduce_counters
@@ -968,6 +969,132 @@ int launch_after_cuts(bvcf_ctx *c, Slot &s, bool wait) {
 }
 
 }  // namespace
+
+// ---- the device compressor (bvcf_bgzf_out.h): k_deflate, k_crc32, k_bgzf_scan, k_bgzf_pack on a stream of its own
+namespace bvcf_bgzf_out {
+
+const uint8_t kEofBlock[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+struct DeflateRun {
+  int device = 0, n_cu = 0, grid = 0;
+  size_t max_text = 0;
+  uint32_t max_pieces = 0;
+  hipStream_t st = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const CrcTabs *crc_tabs = nullptr;
+  uint8_t *d_text = nullptr, *d_slots = nullptr, *d_out = nullptr;
+  uint32_t *d_scratch = nullptr, *d_info = nullptr, *d_crc = nullptr;
+  uint64_t *d_offs = nullptr, *h_total = nullptr;
+  BgzfDesc *d_desc = nullptr;
+};
+
+void deflate_close(DeflateRun *r) {
+  if (!r) return;
+  if (r->st) hipStreamSynchronize(r->st);
+  hipFree(r->d_text);
+  hipFree(r->d_slots);
+  hipFree(r->d_out);
+  hipFree(r->d_scratch);
+  hipFree(r->d_info);
+  hipFree(r->d_crc);
+  hipFree(r->d_offs);
+  hipFree(r->d_desc);
+  if (r->h_total) hipHostFree(r->h_total);
+  if (r->e0) hipEventDestroy(r->e0);
+  if (r->e1) hipEventDestroy(r->e1);
+  if (r->st) hipStreamDestroy(r->st);
+  delete r;
+}
+
+DeflateRun *deflate_open(int device, size_t max_text, std::string *err) {
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) {
+    *err = "no usable HIP device";
+    return nullptr;
+  }
+  DeflateRun *r = new DeflateRun;
+  r->device = device;
+  r->max_pieces = (uint32_t)((max_text + kPiece - 1) / kPiece);
+  r->max_text = (size_t)r->max_pieces * kPiece;
+  hipDeviceProp_t prop;
+  int per_cu = 0;
+  auto fail = [&](const char *what, hipError_t e) {
+    *err = std::string(what) + ": " + hipGetErrorString(e);
+    deflate_close(r);
+    return nullptr;
+  };
+  hipError_t e;
+  if ((e = hipSetDevice(device)) != hipSuccess) return fail("hipSetDevice", e);
+  if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail("hipGetDeviceProperties", e);
+  r->n_cu = prop.multiProcessorCount;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_deflate, kDefThreads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+  // (a workgroup owns a scratch row of a piece's match words: the grid is what is resident, the pieces loop over it)
+  r->grid = (int)std::min<uint64_t>((uint64_t)r->n_cu * (uint64_t)per_cu, r->max_pieces);
+  if ((e = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
+  if ((e = hipEventCreate(&r->e0)) != hipSuccess || (e = hipEventCreate(&r->e1)) != hipSuccess) return fail("hipEventCreate", e);
+  if ((e = hipMalloc(&r->d_text, r->max_text + 64)) != hipSuccess ||
+      (e = hipMalloc(&r->d_slots, (size_t)r->max_pieces * kDefSlot)) != hipSuccess ||
+      (e = hipMalloc(&r->d_out, bound(r->max_text))) != hipSuccess ||
+      (e = hipMalloc(&r->d_scratch, (size_t)r->grid * kDefPiece * sizeof(uint32_t))) != hipSuccess ||
+      (e = hipMalloc(&r->d_info, r->max_pieces * sizeof(uint32_t))) != hipSuccess ||
+      (e = hipMalloc(&r->d_crc, r->max_pieces * sizeof(uint32_t))) != hipSuccess ||
+      (e = hipMalloc(&r->d_offs, (r->max_pieces + 1) * sizeof(uint64_t))) != hipSuccess ||
+      (e = hipMalloc(&r->d_desc, r->max_pieces * sizeof(BgzfDesc))) != hipSuccess ||
+      (e = hipHostMalloc(&r->h_total, sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
+    return fail("device buffers of the compressor", e);
+  r->crc_tabs = crc_tabs_on_device();
+  if (!r->crc_tabs) {
+    *err = "CRC-32 tables: no device memory";
+    deflate_close(r);
+    return nullptr;
+  }
+  return r;
+}
+
+int deflate_run(DeflateRun *r, const uint8_t *text, size_t n, uint8_t *out, size_t cap, size_t *n_out, double *kernel_ms,
+                std::string *err) {
+  *n_out = 0;
+  if (kernel_ms) *kernel_ms = 0;
+  if (n > r->max_text) return BVCF_E_ARG;
+  if (!n) return BVCF_OK;
+  const uint32_t np = (uint32_t)((n + kPiece - 1) / kPiece);
+  hipError_t e;
+  auto hip_fail = [&](const char *what) {
+    *err = std::string(what) + ": " + hipGetErrorString(e);
+    return BVCF_E_HIP;
+  };
+  if ((e = hipSetDevice(r->device)) != hipSuccess) return hip_fail("hipSetDevice");
+  if ((e = hipMemcpyAsync(r->d_text, text, n, hipMemcpyHostToDevice, r->st)) != hipSuccess) return hip_fail("text to the device");
+  hipEventRecord(r->e0, r->st);
+  const uint32_t grid = std::min<uint32_t>(np, (uint32_t)r->grid);
+  hipLaunchKernelGGL(k_deflate, dim3(grid), dim3(kDefThreads), 0, r->st, (const uint8_t *)r->d_text, (uint64_t)n, np, r->d_scratch,
+                     r->d_slots, r->d_info, r->d_desc);
+  hipLaunchKernelGGL(k_crc32, dim3(std::min<uint32_t>(np, (uint32_t)r->n_cu * 16u)), dim3(kWave), 0, r->st, (const uint8_t *)r->d_text,
+                     (const BgzfDesc *)r->d_desc, np, r->crc_tabs, r->d_crc);
+  hipLaunchKernelGGL(k_bgzf_scan, dim3(1), dim3(kDefThreads), 0, r->st, (const uint32_t *)r->d_info, np, r->d_offs);
+  hipLaunchKernelGGL(k_bgzf_pack, dim3(std::min<uint32_t>(np, (uint32_t)r->n_cu * 8u)), dim3(kDefThreads), 0, r->st,
+                     (const uint8_t *)r->d_text, (uint64_t)n, np, (const uint8_t *)r->d_slots, (const uint32_t *)r->d_info,
+                     (const uint32_t *)r->d_crc, (const uint64_t *)r->d_offs, r->d_out);
+  hipEventRecord(r->e1, r->st);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail("compressor kernels");
+  if ((e = hipMemcpyAsync(r->h_total, r->d_offs + np, sizeof(uint64_t), hipMemcpyDeviceToHost, r->st)) != hipSuccess ||
+      (e = hipStreamSynchronize(r->st)) != hipSuccess)
+    return hip_fail("compressor");
+  const uint64_t total = *r->h_total;
+  *n_out = (size_t)total;
+  if (kernel_ms) {
+    float ms = 0;
+    hipEventElapsedTime(&ms, r->e0, r->e1);
+    *kernel_ms = ms;
+  }
+  if (total > cap) return BVCF_E_TOO_BIG;
+  if ((e = hipMemcpyAsync(out, r->d_out, total, hipMemcpyDeviceToHost, r->st)) != hipSuccess ||
+      (e = hipStreamSynchronize(r->st)) != hipSuccess)
+    return hip_fail("members to the host");
+  return BVCF_OK;
+}
+
+}  // namespace bvcf_bgzf_out
 
 extern "C" {
 
@@ -1950,6 +2077,43 @@ int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uin
   for (size_t i = 0; i < nb; i++)
     if (status[i] != kInfOk || crc[i] != blocks[i].crc) return BVCF_E_FATAL;  // corrupt block (inflate or CRC mismatch)
   return BVCF_OK;
+}
+
+int bvcf_bgzf_deflate_device(int device, const uint8_t *text, size_t n, int add_eof, uint8_t *out, size_t cap, size_t *n_out) {
+  if ((!text && n) || !n_out || (!out && cap)) return BVCF_E_ARG;
+  *n_out = 0;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return BVCF_E_NODEV;
+  using namespace bvcf_bgzf_out;
+  // (the text in parts of 1 028 pieces, 64 MiB: the device buffers stay bounded for any n)
+  const size_t part = std::min<size_t>(std::max<size_t>(n, 1), 1028 * kPiece);
+  std::string err;
+  DeflateRun *r = deflate_open(device, part, &err);
+  if (!r) return BVCF_E_HIP;
+  std::vector<uint8_t> tmp;
+  size_t total = 0;
+  int rc = BVCF_OK;
+  for (size_t at = 0; at < n && rc == BVCF_OK; at += part) {
+    const size_t k = std::min(part, n - at);
+    uint8_t *dst = out + total;
+    size_t room = total < cap ? cap - total : 0, got = 0;
+    if (room < bound(k)) {  // may not fit: through a buffer of the worst case
+      tmp.resize(bound(k));
+      dst = tmp.data();
+      room = tmp.size();
+    }
+    rc = deflate_run(r, text + at, k, dst, room, &got, nullptr, &err);
+    if (rc == BVCF_OK && dst == tmp.data() && total + got <= cap) memcpy(out + total, tmp.data(), got);
+    total += got;
+  }
+  deflate_close(r);
+  if (rc) return rc;
+  if (add_eof) {
+    if (total + sizeof kEofBlock <= cap) memcpy(out + total, kEofBlock, sizeof kEofBlock);
+    total += sizeof kEofBlock;
+  }
+  *n_out = total;
+  return total > cap ? BVCF_E_TOO_BIG : BVCF_OK;
 }
 
 int bvcf_device_count(void) {

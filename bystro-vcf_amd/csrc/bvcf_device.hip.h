@@ -49,6 +49,11 @@
 // ... and, on request (bvcf_params.render_sites, bvcf_render.hip.h), behind k_sites2p:
 //   k_render_len / k_render_scan / k_render_rows   the TSV rows of the lines the packed form settles, in input order
 //
+// Compressed output (bvcf_config.out_bgzf, bvcf_bgzf_deflate_device; bvcf_deflate.hip.h), on a stream of its own:
+//   k_deflate      one workgroup per 65 280-byte piece of the TSV: matches, greedy parse, Huffman codes, DEFLATE bits
+//   k_crc32        (bvcf_inflate.hip.h) the pieces' CRC-32
+//   k_bgzf_scan / k_bgzf_pack   the members' offsets, the members packed densely for one copy to the host
+//
 // Everything is byte/integer work over the line bytes; no MFMA.  The genotype scans are bound by
 // VALU issue at 57-70 % of the HBM peak.
 // Loads are 16 B per lane, 1 KiB per wave-instruction, from the dword at or before the byte the
@@ -69,3 +74,4 @@
 #include "bvcf_render.hip.h"
 #include "bvcf_names.hip.h"
 #include "bvcf_inflate.hip.h"
+#include "bvcf_deflate.hip.h"

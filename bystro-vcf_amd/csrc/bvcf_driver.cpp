@@ -135,7 +135,9 @@ void OrderedSink::loop() {
     if (!it.log.empty()) write_all(fd_err_, it.log.data(), it.log.size());
     if (it.parts)
       for (const std::string &s : *it.parts)
-        if (!s.empty() && !write_failed_.load() && write_all(fd_out_, s.data(), s.size())) write_failed_.store(true);
+        if (!s.empty() && !write_failed_.load() &&
+            (bgzf_ ? bgzf_->write(s.data(), s.size()) : write_all(fd_out_, s.data(), s.size())))
+          write_failed_.store(true);
     t_last_write_ = now_s();
     if (it.in_order) it.in_order();
     {
@@ -531,12 +533,25 @@ void Driver::formatter_main(DevWorker *W) {
 
 int Driver::run(uint64_t *n_lines_in) {
   sniff_input();
+  // --compressOutput bgzf: one compressed stream for the header and the rows, on the run's first device
+  if (!dry_ && !c_->no_out && c_->out_bgzf) {
+    if (bvcf_device_count() <= 0) {
+      dprintf(fd_err_, "cannot compress the output: no usable HIP device\n");
+      return BVCF_E_NODEV;
+    }
+    std::string err;
+    bgzf_.reset(new bvcf_bgzf_out::BgzfWriter(fd_out_, dev_list_[0] >= 0 ? dev_list_[0] : c_->device));
+    if (bgzf_->open(&err)) {
+      dprintf(fd_err_, "compressed output: %s\n", err.c_str());
+      return BVCF_E_HIP;
+    }
+  }
   // fmt.Fprintln(writer, stringHeader(config)), main.go:196-200
   if (!dry_ && !c_->no_out) {
     char h[512];
     size_t hn = bvcf_string_header(c_, h, sizeof h);
     h[hn] = '\n';
-    if (write_all(fd_out_, h, hn + 1)) {
+    if (bgzf_ ? bgzf_->write(h, hn + 1) : write_all(fd_out_, h, hn + 1)) {
       dprintf(fd_err_, "write failed\n");
       return BVCF_E_FATAL;
     }
@@ -548,7 +563,7 @@ int Driver::run(uint64_t *n_lines_in) {
   }
   size_t sink_mb = 512;
   if (const char *e = getenv("BVCF_SINK_MB")) sink_mb = (size_t)std::max(1, atoi(e));
-  sink_.reset(new OrderedSink(fd_out_, fd_err_, sink_mb << 20));
+  sink_.reset(new OrderedSink(fd_out_, fd_err_, sink_mb << 20, bgzf_.get()));
 
   // ---- start: the sink, the workers (their devices warm up while the header is read), the reader(s)
   if (!dry_) sink_->start();
@@ -632,6 +647,12 @@ int Driver::run(uint64_t *n_lines_in) {
   sink_->join();
   if (sink_->write_failed()) fail("write failed", BVCF_E_FATAL);
   if (close_dosage(R_)) fail("dosage matrix: write failed", BVCF_E_FATAL);
+  if (bgzf_) {
+    // the last partial piece; the end-of-file block only after a run that succeeded (htslib reports its absence)
+    const double t0 = now_s();
+    if (bgzf_->finish(!failed_.load())) fail(bgzf_->error().empty() ? std::string("write failed") : bgzf_->error(), BVCF_E_FATAL);
+    t_bgzf_finish_ = now_s() - t0;
+  }
   if (!log_.empty()) write_all(fd_err_, log_.data(), log_.size());
   const double t_end0 = now_s();
 
@@ -754,6 +775,12 @@ void Driver::report_timing(double t_end0, const uint64_t totals[8], int used_rcc
     num("system_cpu_s", (double)ru.ru_stime.tv_sec + 1e-6 * (double)ru.ru_stime.tv_usec);
   }
   num("sink_max_held_MB", (double)sink_->max_held_seen() / 1048576.0);
+  if (bgzf_)
+    j.append(tmp, (size_t)snprintf(tmp, sizeof tmp,
+                                   "\"compress\": {\"format\": \"bgzf\", \"text_bytes\": %llu, \"out_bytes\": %llu, \"buffers\": %llu, "
+                                   "\"kernel_ms\": %.3f, \"busy_s\": %.6f, \"sink_wait_s\": %.6f, \"finish_s\": %.6f}, ",
+                                   (unsigned long long)bgzf_->text_bytes, (unsigned long long)bgzf_->out_bytes,
+                                   (unsigned long long)bgzf_->buffers, bgzf_->kernel_ms, bgzf_->busy_s, bgzf_->wait_s, t_bgzf_finish_));
   j.append(tmp, (size_t)snprintf(tmp, sizeof tmp,
                                  "\"threads\": {\"cpus\": %u, \"readers_per_worker\": %u, \"copy_threads_per_reader\": %u, "
                                  "\"format_threads_per_worker\": %u, \"busy_total\": %u}, ",

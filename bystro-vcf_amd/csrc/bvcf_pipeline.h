@@ -16,6 +16,7 @@
 // blocks and the run's thread deals block k to worker k mod N, as the reference's single producer does.  Either way
 // the output is the same bytes in the same order for any device list: blocks are ordered by (range, piece).
 #include "bvcf_host_internal.h"
+#include "bvcf_bgzf_out.h"
 #include "../../include/bvcf_plan.h"
 
 #include <atomic>
@@ -128,7 +129,9 @@ struct OutItem {
 // stop submitting -- as the bounded write queue of the reference's workers does (main.go:524-532).
 class OrderedSink {
  public:
-  OrderedSink(int fd_out, int fd_err, size_t max_held_bytes) : fd_out_(fd_out), fd_err_(fd_err), max_held_(max_held_bytes) {}
+  // out_bgzf: rows go into the run's compressed stream instead of straight to fd_out
+  OrderedSink(int fd_out, int fd_err, size_t max_held_bytes, bvcf_bgzf_out::BgzfWriter *out_bgzf = nullptr)
+      : fd_out_(fd_out), fd_err_(fd_err), max_held_(max_held_bytes), bgzf_(out_bgzf) {}
   ~OrderedSink();
   void start();
   void put(OutItem &&it);
@@ -144,6 +147,7 @@ class OrderedSink {
   void loop();
   int fd_out_, fd_err_;
   size_t max_held_;
+  bvcf_bgzf_out::BgzfWriter *bgzf_;
   std::mutex mu_;
   std::condition_variable cv_, room_;
   std::map<std::pair<uint64_t, uint32_t>, OutItem> held_;
@@ -258,6 +262,8 @@ class Driver {
   unsigned hw_ = 1;
   // first error wins; everything then drains
   std::unique_ptr<OrderedSink> sink_;
+  std::unique_ptr<bvcf_bgzf_out::BgzfWriter> bgzf_;  // bvcf_config.out_bgzf
+  double t_bgzf_finish_ = 0;
   std::mutex fail_mu_;
   int rc_ = BVCF_OK;
   std::string log_;

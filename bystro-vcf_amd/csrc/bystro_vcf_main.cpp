@@ -25,6 +25,8 @@ struct Cli {
   // device: a tool that is dropped into a pipeline on a shared node must not take GPUs it was not given.
   std::string devices = "0";
   unsigned long long batch_mb = 0;
+  // extension: --compressOutput none|bgzf.  bgzf: the TSV (header and rows) leaves as BGZF, compressed on the first device
+  bool out_bgzf = false;
 };
 
 bool parse_bool(const char *v, bool *out) {
@@ -91,8 +93,8 @@ int parse(int argc, char **argv, Cli &c) {
       }
     if (done) continue;
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
-    // counterpart of the reference's NumCPU workers), the block size
-    if (name == "devices" || name == "device" || name == "batchMB") {
+    // counterpart of the reference's NumCPU workers), the block size, the output's compression
+    if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -100,9 +102,15 @@ int parse(int argc, char **argv, Cli &c) {
         }
         val = argv[++i];
       }
-      if (name == "batchMB")
+      if (name == "batchMB") {
         c.batch_mb = strtoull(val.c_str(), nullptr, 10);
-      else
+      } else if (name == "compressOutput") {
+        if (val != "none" && val != "bgzf") {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want none or bgzf\n", val.c_str(), name.c_str());
+          return 2;
+        }
+        c.out_bgzf = val == "bgzf";
+      } else
         c.devices = val;
       continue;
     }
@@ -193,6 +201,7 @@ int main(int argc, char **argv) {
   cfg.sample_list_path = c.sample.c_str();
   cfg.dosage_path = c.dosage.c_str();  // main.go:89
   cfg.no_out = c.no_out;               // main.go:88
+  cfg.out_bgzf = c.out_bgzf;
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

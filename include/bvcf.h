@@ -380,7 +380,11 @@ typedef struct {
   const char *sample_list_path; /* --sample: write the sample names, one per line (main.go:398-445); NULL/"" = no */
   const char *dosage_path;      /* --dosageOutput: Arrow IPC file of the dosage matrix (main.go:306-342); NULL/"" = no */
   uint8_t no_out;               /* --noOut: no TSV rows and no header line (main.go:196-208,502) */
-  uint8_t reserved3[3];
+  uint8_t out_bgzf;             /* --compressOutput bgzf: bvcf_run_fd writes header + rows to fd_out as ONE BGZF stream, cut
+                                   every 65280 bytes of the output (so the bytes depend on the TSV only), compressed on the
+                                   run's first device (bvcf_bgzf_deflate_device), ended by the EOF block -- which a failed
+                                   run leaves out.  0 = plain text (the default) */
+  uint8_t reserved3[2];
   /* bvcf_run_fd: the HIP devices the blocks of the stream are dealt to, round-robin in input order (the
    * counterpart of the reference's NumCPU workers, main.go:345-347).  One ctx and one host thread per entry; an
    * ordinal may repeat (two ctxs sharing a device).  n_devices == 0: the single device `device`.  A device only
@@ -426,6 +430,12 @@ int bvcf_decompress_fd(int fd_in, int fd_out, uint32_t n_threads, char *kind_out
  * BVCF_E_TOO_BIG if out is too small (*n_out then holds the size needed).  This is the building block of
  * bvcf_run_fd's compressed path, exported for tests and for callers that keep compressed data resident. */
 int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uint8_t *out, size_t cap, size_t *n_out);
+/* text -> BGZF, compressed ON THE DEVICE: text is cut every 65280 bytes (bgzip's cut), each piece one BGZF member
+ * (dynamic / fixed / stored DEFLATE, whichever is smallest; CRC32 + ISIZE); add_eof appends the standard 28-byte empty
+ * end-of-file block.  Deterministic: the bytes depend on the text only.  BVCF_E_TOO_BIG if cap is too small (*n_out then
+ * holds the size needed, at most BVCF_BGZF_BOUND(n)). */
+#define BVCF_BGZF_BOUND(n) ((((n) + 65279) / 65280) * 65311 + 28)
+int bvcf_bgzf_deflate_device(int device, const uint8_t *text, size_t n, int add_eof, uint8_t *out, size_t cap, size_t *n_out);
 
 void bvcf_free(void *p);
 
