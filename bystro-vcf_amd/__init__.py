@@ -27,7 +27,7 @@ if not os.path.exists(LIB_PATH):
 
 lib = C.CDLL(LIB_PATH)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 DEVICE_PAD = 64
 NO_CMAP = 0xFFFFFFFF
 
@@ -36,6 +36,9 @@ LINE_OK, LINE_FIELDS, LINE_FILTER, LINE_NOALLELE = 0, 1, 2, 3
 SITE_NAMES = ["SNP", "INS", "DEL", "MNP", "MULTIALLELIC"]
 ALT_BASE, ALT_INS, ALT_DEL = 0, 1, 2
 CLS_NONE, CLS_HET, CLS_HOM, CLS_MISSING = 0, 1, 2, 3
+# the header line of the --sampleStats table (bvcf_config.sample_stats_path)
+SAMPLE_STATS_COLUMNS = ["sample", "het", "hom", "missing", "transitions", "transversions", "heterozygosity", "homozygosity",
+                        "missingness", "trTv"]
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel"]
@@ -47,7 +50,7 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
 # every symbol include/bvcf.h declares
 EXPORTS = [
     "bvcf_create", "bvcf_destroy", "bvcf_last_error", "bvcf_version", "bvcf_reserve", "bvcf_set_sample_names", "bvcf_set_row_format", "bvcf_alloc_pinned", "bvcf_alloc_pinned_near", "bvcf_warmup",
-    "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_counters", "bvcf_sum_counters",
+    "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_sample_stats", "bvcf_counters", "bvcf_sum_counters",
     "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
 ]
@@ -60,7 +63,7 @@ class Params(C.Structure):
         ("want_dosage", C.c_uint8), ("want_name_lists", C.c_uint8), ("allow_filter", C.c_char_p), ("exclude_filter", C.c_char_p),
         ("max_batch_bytes", C.c_uint64), ("max_lines", C.c_uint32), ("max_alleles", C.c_uint32),
         ("cmap_bytes", C.c_uint64), ("n_slots", C.c_uint32), ("path", C.c_uint32),
-        ("packed_sites", C.c_uint32), ("render_sites", C.c_uint32),
+        ("packed_sites", C.c_uint32), ("render_sites", C.c_uint32), ("want_sample_stats", C.c_uint32),
     ]
 
 
@@ -72,7 +75,7 @@ class Config(C.Structure):
         ("leave_teardown_to_exit", C.c_uint8), ("reserved", C.c_uint8 * 2), ("device", C.c_int32), ("n_format_threads", C.c_uint32),
         ("max_batch_bytes", C.c_uint64), ("sample_list_path", C.c_char_p),
         ("dosage_path", C.c_char_p), ("no_out", C.c_uint8), ("out_bgzf", C.c_uint8), ("reserved3", C.c_uint8 * 2),
-        ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)),
+        ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)), ("sample_stats_path", C.c_char_p),
     ]
 
 
@@ -227,6 +230,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         keep.append(arr)
         c.devices = arr
         c.n_devices = len(cfg["devices"])
+    if cfg.get("sampleStats"):  # the per-sample QC table of the run (SAMPLE_STATS_COLUMNS)
+        keep.append(str(cfg["sampleStats"]).encode())
+        c.sample_stats_path = keep[-1]
     c._keep = keep
     return c
 
@@ -493,7 +499,7 @@ class Ctx:
     def __init__(self, n_header_fields, allow="PASS,.", exclude="", device=0, eol_chars=1, eol_byte=b"\n",
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
-                 empty_field="!", keep_pos=False, keep_id=False, keep_info=False):
+                 empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False):
         p = Params()
         p.abi_version = ABI_VERSION
         p.device = device
@@ -513,6 +519,8 @@ class Ctx:
         p.packed_sites = int(packed_sites or render_sites)
         p.render_sites = int(render_sites)
         p.want_name_lists = int(sample_names is not None)
+        p.want_sample_stats = int(sample_stats)
+        self.n_samples = max(n_header_fields - 9, 0)
         self.h = C.c_void_p()
         rc = lib.bvcf_create(C.byref(self.h), C.byref(p))
         if rc:
@@ -591,6 +599,14 @@ class Ctx:
         lib.bvcf_bench_stream_kernel.restype = C.c_int
         k = lib.bvcf_bench_stream_kernel(self.h)
         return None if k < 0 else ("k_stream_gen" if k else "k_stream")
+
+    def sample_stats(self, reset=False):
+        """bvcf_params.want_sample_stats: the per-sample counts over the rows of the batches collected so far ->
+        uint64 array (n_samples, 6): het, hom, missing, transitions, transversions, rows (see include/bvcf.h)"""
+        out = np.zeros(6 * self.n_samples, dtype=np.uint64)
+        lib.bvcf_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._check(lib.bvcf_sample_stats(self.h, out.ctypes.data if self.n_samples else None, int(reset)))
+        return out.reshape(6, self.n_samples).T.copy()
 
     def counters(self):
         out = (C.c_uint64 * 8)()

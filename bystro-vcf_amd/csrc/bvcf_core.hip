@@ -98,6 +98,11 @@ struct Slot {
   bvcf_err *h_errs = nullptr;
   uint8_t *h_cmap = nullptr;
   int8_t *h_dosage = nullptr;
+  // bvcf_params.want_sample_stats (bvcf_samplestats.hip.h): the row lists (follow max_alleles), the batch's counts, the totals
+  uint2 *d_ss_dense = nullptr, *d_ss_sparse = nullptr;
+  uint64_t cap_ss_list = 0;
+  uint32_t *d_ss_ctr = nullptr, *d_ss_part = nullptr, *d_ss_sp = nullptr;
+  unsigned long long *d_ss_acc = nullptr;
   // capacities this slot was allocated with
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
   // in-flight batch
@@ -147,6 +152,9 @@ struct bvcf_ctx {
   uint32_t n_samples = 0;
   uint32_t cmap_stride = 0;
   uint32_t dosage_stride = 0;  // 0 unless want_dosage
+  // bvcf_params.want_sample_stats on a file with samples: the per-sample counts behind every chain (bvcf_samplestats.hip.h)
+  bool ss_on = false;
+  uint32_t ss_ns_pad = 0, ss_max_runs = 0, ss_stripes = 0;
   uint64_t max_lines = 0, max_alleles = 0, max_cmap = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
   FilterTable *d_filters = nullptr;
@@ -262,6 +270,12 @@ void free_slot(Slot &s) {
   hipHostFree(s.h_errs);
   hipHostFree(s.h_cmap);
   hipHostFree(s.h_dosage);
+  hipFree(s.d_ss_dense);
+  hipFree(s.d_ss_sparse);
+  hipFree(s.d_ss_ctr);
+  hipFree(s.d_ss_part);
+  hipFree(s.d_ss_sp);
+  hipFree(s.d_ss_acc);
   if (s.ev_k0) hipEventDestroy(s.ev_k0);
   if (s.ev_k1) hipEventDestroy(s.ev_k1);
   if (s.ev_in) hipEventDestroy(s.ev_in);
@@ -403,6 +417,15 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
     const int rc = alloc_names(c, s, std::max<uint64_t>(s.cap_names, c->p.max_batch_bytes / 2 + (1u << 20)));
     if (rc) return rc;
   }
+  if (c->ss_on) {
+    hipFree(s.d_ss_dense);
+    hipFree(s.d_ss_sparse);
+    s.d_ss_dense = s.d_ss_sparse = nullptr;
+    s.cap_ss_list = 0;
+    HIP_TRY(c, hipMalloc(&s.d_ss_dense, c->max_alleles * sizeof(uint2)));
+    HIP_TRY(c, hipMalloc(&s.d_ss_sparse, c->max_alleles * sizeof(uint2)));
+    s.cap_ss_list = c->max_alleles;
+  }
   s.cap_lines = c->max_lines;
   s.cap_alleles = c->max_alleles;
   s.cap_cmap = c->max_cmap;
@@ -438,6 +461,14 @@ int alloc_slot(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, hipMalloc(&s.d_entries, max_tiles * c->tile_quota * sizeof(StreamEntry)));
     HIP_TRY(c, hipMalloc(&s.d_head_bits, max_tiles * c->tile_quota * 16 * sizeof(uint16_t)));
   }
+  if (c->ss_on) {
+    const size_t table = (size_t)kSsCols * c->ss_ns_pad;
+    HIP_TRY(c, hipMalloc(&s.d_ss_ctr, 4 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&s.d_ss_part, (size_t)c->ss_max_runs * table * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&s.d_ss_sp, table * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&s.d_ss_acc, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(s.d_ss_acc, 0, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
+  }
   return alloc_results(c, s);
 }
 
@@ -450,7 +481,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps;
+  a.want_cmap = c->p.want_class_maps || c->ss_on;  // (the per-sample counts are made from the maps on the device)
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -517,6 +548,34 @@ void adapt_stream_kernel(bvcf_ctx *c, bool was_gen, const BatchCounters &ctr) {
   if ((uint64_t)ctr.n_other_shape * 2u > ctr.n_lines) c->gen_mode = !was_gen;
 }
 
+SampleStatsArgs make_ss_args(bvcf_ctx *c, Slot &s) {
+  SampleStatsArgs sa{};
+  sa.dense = s.d_ss_dense;
+  sa.sparse = s.d_ss_sparse;
+  sa.ctr = s.d_ss_ctr;
+  sa.part = s.d_ss_part;
+  sa.sp = s.d_ss_sp;
+  sa.acc = s.d_ss_acc;
+  sa.list_cap = (uint32_t)s.cap_ss_list;
+  sa.ns_pad = c->ss_ns_pad;
+  sa.max_runs = c->ss_max_runs;
+  sa.n_stripes = c->ss_stripes;
+  return sa;
+}
+
+// bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
+// (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
+void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if (!c->ss_on || !slot || !slot->d_ss_dense) return;
+  const SampleStatsArgs sa = make_ss_args(c, *slot);
+  hipMemsetAsync(sa.ctr, 0, 4 * sizeof(uint32_t), st);
+  hipMemsetAsync(sa.sp, 0, (size_t)kSsCols * sa.ns_pad * sizeof(uint32_t), st);
+  hipLaunchKernelGGL(k_ss_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, sa);
+  const uint32_t waves = c->ss_stripes * c->ss_max_runs;
+  hipLaunchKernelGGL(k_ss_dense, dim3((waves + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, a, sa);
+  hipLaunchKernelGGL(k_ss_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);  // (three dependent loads per list: many in flight)
+}
+
 void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot = nullptr) {
   if (a.fused) {
     // (experiments builds, BVCF_SCAN_STREAM=1: the one-pass kernels of ALL batches through one stream of the ctx, what follows
@@ -564,6 +623,7 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
     if (!(skip & 2)) hipLaunchKernelGGL(k_gt, dim3(gt_wgs), dim3(kWgThreads), 0, st, a);
     if (!(skip & 4)) hipLaunchKernelGGL(k_finish, dim3(fin_wgs), dim3(kWgThreads), 0, st, a);
     if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
+    launch_sample_stats(c, a, st, slot);
     return;
   }
 #ifdef BVCF_EXPERIMENTS
@@ -650,6 +710,7 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
     hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
     if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
     if (a.dosage && c->wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
+    launch_sample_stats(c, a, st, slot);
   } else {
     if (ev_gt0) hipEventRecord(ev_gt0, st);
     if (ev_gt1) hipEventRecord(ev_gt1, st);
@@ -1320,6 +1381,13 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   }
 #endif
   c->sites1_grid = c->n_cu * per_cu;
+  // per-sample counts: a wave per (stripe of 1 024 samples, run of dense rows); the runs' partial tables are held to 16 MiB
+  c->ss_on = p->want_sample_stats != 0 && c->n_samples > 0;
+  if (c->ss_on) {
+    c->ss_ns_pad = 4u * c->cmap_stride;
+    c->ss_stripes = (c->ss_ns_pad + kSsStripeSamples - 1u) / kSsStripeSamples;
+    c->ss_max_runs = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (16ull << 20) / (4ull * kSsCols * c->ss_ns_pad)));
+  }
   // the streaming kernel gives every wave its own range of class-map slots (two of them slack): room for that
   if (!p->cmap_bytes) {
     c->max_cmap += (uint64_t)c->stream_grid * kWavesPerWg * 2u * c->cmap_stride + c->max_lines / 16 * (uint64_t)c->cmap_stride;
@@ -1743,18 +1811,21 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   const uint64_t n_alleles = extras_at + ctr.n_alleles;
   const uint64_t n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
   const uint64_t need_alleles = std::max<uint64_t>(std::max<uint64_t>(n_alleles, ctr.n_errs), n_tasks);
-  const bool maps = c->p.want_class_maps && c->n_samples;
-  const uint64_t cmap_bytes = !maps ? 0 : (c->fused ? (uint64_t)ctr.cmap_maps : n_tasks) * c->cmap_stride;
+  // (the maps are made on the device when the caller wants them or the per-sample counts are made from them; they cross
+  // to the host only in the first case)
+  const bool maps = (c->p.want_class_maps || c->ss_on) && c->n_samples;
+  const uint64_t cmap_need = !maps ? 0 : (c->fused ? (uint64_t)ctr.cmap_maps : n_tasks) * c->cmap_stride;
+  const uint64_t cmap_bytes = c->p.want_class_maps ? cmap_need : 0;
   if (ctr.pad[0]) {
     c->err = "internal error: streaming tile quota or class-map slot range exceeded";
     release();
     return BVCF_E_HIP;
   }
-  if (ctr.n_lines > s.cap_lines || need_alleles > s.cap_alleles || cmap_bytes > s.cap_cmap) {
+  if (ctr.n_lines > s.cap_lines || need_alleles > s.cap_alleles || cmap_need > s.cap_cmap) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
     r->need_alleles = need_alleles;
-    r->need_cmap_bytes = cmap_bytes;
+    r->need_cmap_bytes = cmap_need;
     // (the extras of a packed ctx follow slot cap_lines: once the lines grow, so does where they start -- bvcf_reserve
     // adds them to the NEW line capacity, need_alleles alone is relative to the old one)
     c->need_extras = (c->sites1 || c->packed) ? (uint64_t)ctr.n_alleles : 0;
@@ -1824,6 +1895,13 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
       s.hcap_recs = want_recs;
       s.hcap_errs = want_errs;
     }
+  }
+  if (c->ss_on && s.d_ss_dense) {
+    // the batch is in: its per-sample counts join the slot's totals (ahead of the copies on the slot's stream)
+    const uint32_t n_threads = kSsCols * c->ss_ns_pad;
+    hipLaunchKernelGGL(k_ss_fold, dim3((n_threads + kWgThreads - 1) / kWgThreads), dim3(kWgThreads), 0, s.stream,
+                       make_ss_args(c, s), c->n_samples);
+    HIP_TRY(c, hipGetLastError());
   }
   if (n_first)
     HIP_TRY(c, hipMemcpyAsync(s.h_lines, s.d_lines, (size_t)n_first * sizeof(bvcf_line), hipMemcpyDeviceToHost, s.stream));
@@ -1955,7 +2033,7 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = s.h_cmap;
+  r->cmap = (c->ss_on && !c->p.want_class_maps) ? nullptr : s.h_cmap;  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = was_bgzf ? s.h_text : nullptr;
@@ -2002,6 +2080,35 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   c->totals[6] += r->n_cmap_bytes;
   c->totals[7] += (uint64_t)(ms * 1e6);
   release();
+  return BVCF_OK;
+}
+
+int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->p.want_sample_stats) {
+    c->err = "bvcf_sample_stats: the ctx was created without bvcf_params.want_sample_stats";
+    return BVCF_E_ARG;
+  }
+  const uint32_t ns = c->n_samples;
+  if (out) memset(out, 0, 6ull * ns * sizeof(uint64_t));
+  if (!c->ss_on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<unsigned long long> t((size_t)6 * c->ss_ns_pad);
+  for (auto &s : c->slots) {
+    if (!s.d_ss_acc) continue;
+    HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+    if (out) {
+      HIP_TRY(c, hipMemcpyAsync(t.data(), s.d_ss_acc, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(c, hipStreamSynchronize(s.stream));
+      for (uint32_t col = 0; col < kSsCols; col++)
+        for (uint32_t i = 0; i < ns; i++) out[(size_t)col * ns + i] += t[(size_t)col * c->ss_ns_pad + i];
+      for (uint32_t i = 0; i < ns; i++) out[(size_t)kSsCols * ns + i] += t[(size_t)kSsCols * c->ss_ns_pad];
+    }
+    if (reset) {
+      HIP_TRY(c, hipMemsetAsync(s.d_ss_acc, 0, t.size() * sizeof(unsigned long long), s.stream));
+      HIP_TRY(c, hipStreamSynchronize(s.stream));
+    }
+  }
   return BVCF_OK;
 }
 
@@ -2263,7 +2370,7 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
   const uint64_t b_need = std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctr.n_lines + ctr.n_alleles, ctr.n_errs),
                                              (uint64_t)ctr.n_lines + ctr.n_tasks);
   if ((ctr.n_lines > s.cap_lines || b_need > s.cap_alleles ||
-      (c->p.want_class_maps && c->n_samples &&
+      ((c->p.want_class_maps || c->ss_on) && c->n_samples &&
        (c->fused ? (uint64_t)ctr.cmap_maps : (uint64_t)ctr.n_lines + ctr.n_tasks) * c->cmap_stride > s.cap_cmap))) {
     c->err = "bench block exceeds reserved result capacity: lines " + std::to_string(ctr.n_lines) + " records " +
              std::to_string(b_need) + " maps " + std::to_string(ctr.cmap_maps);

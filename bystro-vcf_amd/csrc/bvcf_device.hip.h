@@ -32,6 +32,9 @@
 // deferred lines and further ALT indices of dense lines; it fills their allele records itself -- and k_finish (lines whose
 // ALT #1 was deferred) run.
 //
+//   (bvcf_params.want_sample_stats, at the end of the chain of a file with samples: k_ss_list / k_ss_dense / k_ss_sparse
+//    count, per sample, the rows whose class maps name it -- bvcf_samplestats.hip.h; k_ss_fold adds a collected batch's
+//    counts to the slot's totals)
 //   (bvcf_params.want_name_lists, after k_finish: k_name_len / k_name_scan / k_name_write render the het / hom / missing
 //    sample-name lists of every output allele as text -- main.go:612-656 -- see bvcf_names.hip.h)
 //
@@ -73,5 +76,6 @@
 #include "bvcf_sites1.hip.h"
 #include "bvcf_render.hip.h"
 #include "bvcf_names.hip.h"
+#include "bvcf_samplestats.hip.h"
 #include "bvcf_inflate.hip.h"
 #include "bvcf_deflate.hip.h"

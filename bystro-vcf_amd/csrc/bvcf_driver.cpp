@@ -390,10 +390,26 @@ void Driver::device_main(DevWorker *W) {
       // grow, resubmit everything still queued on this device
       wait_formatted(n_jobs);
       outstanding.clear();
+      // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
+      const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
+      if (ss) {
+        const size_t n = 6 * (R_.pre.header.size() - 9);
+        std::vector<uint64_t> t(n, 0);
+        W->ss_carry.resize(n, 0);
+        if (bvcf_sample_stats(W->ctx, t.data(), 1) != BVCF_OK) {
+          fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          return;
+        }
+        for (size_t k = 0; k < n; k++) W->ss_carry[k] += t[k];
+      }
       for (size_t k = 1; k < in_flight.size(); k++) {
         bvcf_result tmp;
         bvcf_collect(W->ctx, &tmp);
         n_collects++;
+      }
+      if (ss && bvcf_sample_stats(W->ctx, nullptr, 1) != BVCF_OK) {
+        fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+        return;
       }
       r = bvcf_reserve(W->ctx, res.need_lines + res.need_lines / 4 + 64, res.need_alleles + res.need_alleles / 4 + 64,
                        res.need_cmap_bytes + res.need_cmap_bytes / 4 + 4096);
@@ -532,6 +548,13 @@ void Driver::formatter_main(DevWorker *W) {
 }
 
 int Driver::run(uint64_t *n_lines_in) {
+  if (!dry_) {  // --sampleStats: opened before any device work, as --sample's file is written before it
+    std::string msg;
+    if (open_sample_stats(c_, &ss_fd_, &msg)) {
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return BVCF_E_IO;
+    }
+  }
   sniff_input();
   // --compressOutput bgzf: one compressed stream for the header and the rows, on the run's first device
   if (!dry_ && !c_->no_out && c_->out_bgzf) {
@@ -688,6 +711,27 @@ int Driver::run(uint64_t *n_lines_in) {
       }
     }
     t_gather = now_s() - tg;
+    if (ss_fd_ >= 0) {
+      // --sampleStats: every ctx's table (and what its worker kept across a reservation) summed on the host -- integer sums,
+      // so the table does not depend on how the blocks were dealt
+      if (rc_ == BVCF_OK) {
+        const size_t n = R_.pre.header.size() > 9 ? 6 * (R_.pre.header.size() - 9) : 0;
+        std::vector<uint64_t> sum(n, 0), t(n, 0);
+        for (auto &W : workers_) {
+          if (!W->ctx) continue;
+          if (bvcf_sample_stats(W->ctx, t.data(), 0) != BVCF_OK) {
+            fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+            break;
+          }
+          for (size_t k = 0; k < n; k++) sum[k] += t[k] + (k < W->ss_carry.size() ? W->ss_carry[k] : 0);
+        }
+        std::string msg;
+        if (rc_ == BVCF_OK && write_sample_stats(ss_fd_, c_, R_.pre, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+        if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
+      }
+      if (rc_ != BVCF_OK) close(ss_fd_);  // (write_sample_stats closed it)
+      ss_fd_ = -1;
+    }
     if (!c_->leave_teardown_to_exit)
       for (bvcf_ctx *x : live) bvcf_destroy(x);
   }

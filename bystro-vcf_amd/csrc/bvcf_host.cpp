@@ -83,8 +83,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   R.cfg = c;
   R.max_batch = c->max_batch_bytes ? c->max_batch_bytes : (64ull << 20);
   uint64_t lines_in = 0;
-  int rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg);
-  if (rc < 0) {
+  int ss_fd = -1;
+  int rc = open_sample_stats(c, &ss_fd, &msg);
+  if (rc) {
+    l = msg + "\n";
+  } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
     l = msg + "\n";
     rc = BVCF_E_FATAL;
   } else {
@@ -132,6 +135,22 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (close_dosage(R) && rc == BVCF_OK) {
     l.append("dosage matrix: write failed\n");
     rc = BVCF_E_FATAL;
+  }
+  if (ss_fd >= 0) {  // --sampleStats: the run's table, after a successful run only
+    if (rc == BVCF_OK) {
+      const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+      std::vector<uint64_t> t(6 * ns, 0);
+      if (R.ctx && bvcf_sample_stats(R.ctx, t.data(), 0) != BVCF_OK) {
+        l.append(std::string("bvcf_sample_stats: ") + bvcf_last_error(R.ctx) + "\n");
+        rc = BVCF_E_HIP;
+        close(ss_fd);
+      } else if (write_sample_stats(ss_fd, c, R.pre, t.data(), &msg)) {
+        l.append(msg + "\n");
+        rc = BVCF_E_IO;
+      }
+    } else {
+      close(ss_fd);
+    }
   }
   if (R.ctx) bvcf_destroy(R.ctx);
   if (n_lines_in) *n_lines_in = lines_in;

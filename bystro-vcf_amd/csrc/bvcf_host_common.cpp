@@ -645,6 +645,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
   p.eol_byte = R.pre.eol_byte;
   R.want_rows = !R.cfg->no_out;
   p.want_class_maps = R.want_rows;  // needsLabels, main.go:502
+  p.want_sample_stats = R.cfg->sample_stats_path && *R.cfg->sample_stats_path;  // --sampleStats: counted on the device
   // BVCF_DEVICE_NAMES=1: the sample-name lists of the rows come off the device as text instead of being
   // joined by the formatter from the class maps.  Off by default: measured on the dense profile (every row a common
   // variant, 10 KB of names per row) the text is 16 x the class maps over PCIe and the run gets slower, while the
@@ -826,6 +827,63 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
 
 
 
+
+int open_sample_stats(const bvcf_config *c, int *fd, std::string *msg) {
+  *fd = -1;
+  const char *path = c->sample_stats_path;
+  if (!path || !*path) return BVCF_OK;
+  *fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (*fd < 0) {
+    *msg = std::string("open ") + path + ": " + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+// One line per sample in header order: the counts, then het / (N - missing), hom / (N - missing), missing / N and
+// transitions / transversions with the TSV's "%.3G" (a zero numerator prints 0, as an empty list does; trTv without
+// transversions prints --emptyField)
+void format_sample_stats(const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string &o) {
+  o.append("sample\thet\thom\tmissing\ttransitions\ttransversions\theterozygosity\thomozygosity\tmissingness\ttrTv\n");
+  const size_t ns = pre.header.size() > 9 ? pre.header.size() - 9 : 0;
+  auto ratio = [&](uint64_t num, uint64_t den) {
+    if (num == 0 || den == 0)
+      o.push_back('0');
+    else
+      append_g3(o, (double)num / (double)den);
+  };
+  for (size_t s = 0; s < ns; s++) {
+    const uint64_t het = t[s], hom = t[ns + s], miss = t[2 * ns + s], ts = t[3 * ns + s], tv = t[4 * ns + s], rows = t[5 * ns + s];
+    o.append(pre.header[9 + s]);
+    for (uint64_t v : {het, hom, miss, ts, tv}) {
+      o.push_back('\t');
+      append_ll(o, (long long)v);
+    }
+    const uint64_t called = rows >= miss ? rows - miss : 0;
+    o.push_back('\t');
+    ratio(het, called);
+    o.push_back('\t');
+    ratio(hom, called);
+    o.push_back('\t');
+    ratio(miss, rows);
+    o.push_back('\t');
+    if (tv == 0)
+      o.append(or_default(c->empty_field, "!"));
+    else
+      ratio(ts, tv);
+    o.push_back('\n');
+  }
+}
+
+int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg) {
+  std::string o;
+  format_sample_stats(c, pre, t, o);
+  if (write_all(fd, o.data(), o.size()) || close(fd)) {
+    *msg = std::string("sample stats: write failed: ") + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
 
 int write_all(int fd, const char *p, size_t n) {
   while (n) {

@@ -238,6 +238,11 @@ int open_ctx(Run &R, std::string *msg, const uint8_t *data = nullptr, size_t n_d
 int append_dosage(Run &R, const bvcf_result *r, const uint8_t *block);
 int close_dosage(Run &R);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
+// --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
+// and, at the end of a successful run, the table of the summed per-sample counts t (bvcf_sample_stats layout) written
+int open_sample_stats(const bvcf_config *c, int *fd, std::string *msg);
+void format_sample_stats(const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string &out);
+int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg);
 
 // a bounded FIFO between pipeline stages
 template <class T>

@@ -207,6 +207,9 @@ struct DevWorker {
   // timing
   double t_warm = 0, t_ctx = 0, t_submit = 0, t_gpu = 0, t_fmt_wait = 0, t_first_submit = 0, t_starved = 0, t_fmt = 0, t_read = 0;
   uint64_t n_blocks = 0, n_bytes = 0;
+  // --sampleStats: the counts of batches collected before a reservation grew (the ctx's totals are reset then, because the
+  // batches in flight are collected, dropped and submitted again)
+  std::vector<uint64_t> ss_carry;
 };
 
 enum Mode { kStream = BVCF_MODE_STREAM, kRangeText = BVCF_MODE_TEXT_RANGES, kRangeBgzf = BVCF_MODE_BGZF_RANGES };
@@ -216,6 +219,9 @@ class Driver {
  public:
   Driver(const bvcf_config *c, int fd_in, int fd_out, int fd_err, bool dry = false, unsigned dry_workers = 1,
          int dry_device_inflate = 1);
+  ~Driver() {
+    if (ss_fd_ >= 0) close(ss_fd_);  // (a run that ended before its table was written)
+  }
   int run(uint64_t *n_lines_in);
   // bvcf_plan_fd: the blocks the workers received, in (range, piece) order
   std::vector<bvcf_plan_block> dry_blocks;
@@ -267,6 +273,7 @@ class Driver {
   std::mutex fail_mu_;
   int rc_ = BVCF_OK;
   std::string log_;
+  int ss_fd_ = -1;  // --sampleStats
   std::atomic<bool> failed_{false};
   // what the workers wait for: the header is known, the ctx parameters are set, the ranges are laid out
   struct {

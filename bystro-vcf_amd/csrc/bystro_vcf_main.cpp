@@ -27,6 +27,8 @@ struct Cli {
   unsigned long long batch_mb = 0;
   // extension: --compressOutput none|bgzf.  bgzf: the TSV (header and rows) leaves as BGZF, compressed on the first device
   bool out_bgzf = false;
+  // extension: --sampleStats PATH, the per-sample QC table of the run's rows (counted on the device)
+  std::string sample_stats;
 };
 
 bool parse_bool(const char *v, bool *out) {
@@ -94,7 +96,7 @@ int parse(int argc, char **argv, Cli &c) {
     if (done) continue;
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
-    if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput") {
+    if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -110,6 +112,8 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         c.out_bgzf = val == "bgzf";
+      } else if (name == "sampleStats") {
+        c.sample_stats = val;
       } else
         c.devices = val;
       continue;
@@ -146,7 +150,7 @@ int main(int argc, char **argv) {
     dprintf(fd_err, "Cannot specify --noOut and --out\n");
     return 1;
   }
-  if (c.no_out && c.dosage.empty()) {  // main.go:164-166
+  if (c.no_out && c.dosage.empty() && c.sample_stats.empty()) {  // main.go:164-166 (--sampleStats alone: a QC-only pass)
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -202,6 +206,7 @@ int main(int argc, char **argv) {
   cfg.dosage_path = c.dosage.c_str();  // main.go:89
   cfg.no_out = c.no_out;               // main.go:88
   cfg.out_bgzf = c.out_bgzf;
+  cfg.sample_stats_path = c.sample_stats.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

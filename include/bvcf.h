@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define BVCF_ABI_VERSION 7
+#define BVCF_ABI_VERSION 8
 
 typedef enum {
   BVCF_OK = 0,
@@ -136,6 +136,9 @@ typedef struct {
                                  bvcf_result.rows; the site records then stay on the device (sites == NULL) and the lines
                                  the host still has to format -- the BVCF_SITE_FULL ones -- are listed in row_cuts with the
                                  place of their rows in the stream.  Needs bvcf_set_row_format. */
+  uint32_t want_sample_stats; /* ABI 8: 1 = per-sample counts over the rows of every batch, made on the device from the class
+                                 maps (which the ctx then makes even when want_class_maps is 0, without copying them to the
+                                 host) and read with bvcf_sample_stats.  A file without samples has an empty table */
 } bvcf_params;
 
 /* one input line; 64 bytes */
@@ -342,6 +345,13 @@ int bvcf_submit_bgzf(bvcf_ctx *ctx, const uint8_t *comp, size_t n_comp, size_t n
 int bvcf_collect(bvcf_ctx *ctx, bvcf_result *r);
 /* 1 = census path, 2 = streaming path (see bvcf_params.path) */
 int bvcf_path(const bvcf_ctx *ctx);
+/* bvcf_params.want_sample_stats: the per-sample table over the rows of the batches collected so far -- a row being an
+ * output allele of a line with status OK and ac > 0, as the TSV prints it (main.go:555-560).  out[c * n_samples + s],
+ * column c: 0 het, 1 hom, 2 missing (rows whose heterozygotes / homozygotes / missing list names sample s), 3 ts, 4 tv
+ * (rows with trtv 1 / 2 in which s is het or hom), 5 the number of rows (the same for every s).  A batch counts once it
+ * is collected with BVCF_OK; one that came back BVCF_E_CAPACITY does not.  Waits for the ctx's slots.  reset: zero the
+ * totals after reading them (out may then be NULL).  BVCF_E_ARG on a ctx created without want_sample_stats. */
+int bvcf_sample_stats(bvcf_ctx *ctx, uint64_t *out /* 6 * n_samples, column-major */, int reset);
 
 /* running totals since bvcf_create: {lines_in, lines_ok, alleles_out, alleles_ac0, errs,
  * bytes_in, cmap_bytes, kernel_ns} */
@@ -391,6 +401,9 @@ typedef struct {
    * gets a ctx once a block is dealt to it, so a short stream does not pay for the devices it does not reach. */
   uint32_t n_devices;
   const int32_t *devices;
+  /* ABI 8, --sampleStats: bvcf_run_fd / bvcf_run_buffer write the per-sample QC table of the run's rows here (opened before
+   * any device work, written at the end of a successful run; the format is in README.md).  NULL or "" = no table */
+  const char *sample_stats_path;
 } bvcf_config;
 
 void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
