@@ -564,13 +564,39 @@ class Ctx:
     def reserve(self, lines, alleles, cmap_bytes):
         self._check(lib.bvcf_reserve(self.h, lines, alleles, cmap_bytes))
 
-    def collect(self):
+    def collect(self, tsv=None):
+        """the oldest batch in flight.  tsv = (block, cfg, sample_names): also its TSV rows and log lines through
+        bvcf_format_tsv, made from the raw result before its slot can take another batch -> Batch.tsv (bytes) and
+        Batch.log (text).  block: the host bytes of the submitted block (any buffer; a memoryview slice is not copied),
+        cfg: a make_config dict or Config, sample_names: the normalised header fields 9.."""
         r = Result()
         rc = lib.bvcf_collect(self.h, C.byref(r))
         if rc == E_CAPACITY:
             raise BvcfError(rc, "capacity: need lines=%d alleles=%d cmap=%d" % (r.need_lines, r.need_alleles, r.need_cmap_bytes))
         self._check(rc)
-        return Batch(r)
+        if tsv is None:
+            return Batch(r)
+        block, cfg, names = tsv
+        c = cfg if isinstance(cfg, Config) else make_config(cfg)
+        buf = np.frombuffer(block, dtype=np.uint8)
+        enc = [x.encode() if isinstance(x, str) else x for x in (names or [])]
+        ptrs = (C.c_char_p * max(len(enc), 1))(*enc)
+        lens = (C.c_uint32 * max(len(enc), 1))(*[len(x) for x in enc])
+        out, log = C.c_void_p(), C.c_void_p()
+        n_out, n_log = C.c_size_t(), C.c_size_t()
+        rc = lib.bvcf_format_tsv(C.byref(c), C.byref(r), buf.ctypes.data if len(buf) else None, ptrs, lens, C.byref(out),
+                                 C.byref(n_out), C.byref(log), C.byref(n_log))
+        try:
+            if rc:
+                raise BvcfError(rc, "bvcf_format_tsv")
+            text = C.string_at(out, n_out.value) if out.value else b""
+            log_text = C.string_at(log, n_log.value).decode(errors="replace") if log.value else ""
+        finally:
+            lib.bvcf_free(out)
+            lib.bvcf_free(log)
+        b = Batch(r)
+        b.tsv, b.log = text, log_text
+        return b
 
     def process(self, block):
         self.submit(block)

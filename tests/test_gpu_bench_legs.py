@@ -109,3 +109,33 @@ def test_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
     assert cls.shape[1] == 2504 and len(cls) == len(a["classes_record"]) > 0
     rec = a["classes_record"].astype(int)
     assert ((cls == 1).sum(axis=1) == a["record_n_het"][rec]).all() and ((cls == 2).sum(axis=1) == a["record_n_hom"][rec]).all()
+    # the dumped records and class codes against the oracle on the dumped lines, regenerated on the host from the same
+    # first rows (bench.rank_blocks); configs[2]'s lines give one record each, so the oracle's row j is record j
+    import benchgen as bg
+    import bystro_vcf_amd as bv
+    import oracle_lib as orc
+    cfg = bg.make_cfg("c3")
+    texts = [bg.rows_host(cfg, first, 12000).split(b"\n") for first in bench.rank_blocks(0, 2, 12000)]
+    blk, idx = a["line_block"].astype(int), a["line_index"].astype(int)
+    assert (a["record_block"] == a["line_block"]).all() and (a["record_line"] == a["line_index"]).all()
+    rc, out, log, n_rows = orc.run(bg.header(cfg) + b"".join(texts[k][i] + b"\n" for k, i in zip(blk, idx)), n_threads=16)
+    assert rc == 0 and log == "" and n_rows == n
+    rows = [r.decode().split("\t") for r in out.split(b"\n") if r]
+    assert len(rows) == n
+    hdr = bv.string_header().split("\t")
+    col = {k: hdr.index(k) for k in ("pos", "ref", "alt", "trTv", "heterozygotes", "homozygotes", "missingGenos", "ac", "an")}
+    names = ["HG%05d" % s for s in range(2504)]
+
+    def listed(r, k):
+        return 0 if r[col[k]] == "!" else len(r[col[k]].split(";"))
+    for j, r in enumerate(rows):
+        assert (int(r[col["ac"]]), int(r[col["an"]]), r[col["ref"]], r[col["alt"]], int(r[col["trTv"]])) == (
+            a["record_ac"][j], a["record_an"][j], chr(int(a["record_ref"][j])), chr(int(a["record_alt_base"][j])),
+            a["record_trtv"][j]), (j, r[:6])
+        # (pos: the output position, unless the record says the line's POS text is printed as it is)
+        assert a["record_pos_text"][j] or int(r[col["pos"]]) == a["record_pos"][j], (j, r[:6], a["record_pos"][j])
+        assert (listed(r, "heterozygotes"), listed(r, "homozygotes"), listed(r, "missingGenos")) == (
+            a["record_n_het"][j], a["record_n_hom"][j], a["record_n_miss"][j]), j
+    for c, j in zip(cls, rec):
+        for q, k in ((1, "heterozygotes"), (2, "homozygotes"), (3, "missingGenos")):
+            assert (";".join(names[s] for s in np.flatnonzero(c == q)) or "!") == rows[j][col[k]], (j, k)

@@ -293,14 +293,17 @@ def test_cli_bgzf_edge_files(bv, golden_1kg):
 def test_cli_bgzf_sites_only_rendered_rows_take_only_the_cut_lines_text_back(bv):
     """sites-only BGZF input with the rows rendered on the device (the default): the text stays on the device and only the
     lines left to the host -- here every tenth line, an insertion -- come back, packed (bvcf_row_cut.text_off); a file
-    made of nothing but such lines outgrows that buffer and falls back to the whole text.  Rows and log against the
+    made of nothing but such lines outgrows that buffer and falls back to the whole text, and a file whose batches turn
+    from SNPs to insertions and back makes the collect regrow its host buffers mid-stream.  Rows and log against the
     oracle, for both forms and with the host's rows (BVCF_RENDER_SITES=0)."""
     import oracle_lib as orc
     hdr = "##fileformat=VCFv4.2\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n"
-    for every, n in ((10, 120_000), (1, 250_000)):
+    # (every == 0: SNPs, then a third of nothing but insertions, then SNPs again -- whole 16 MB batches of each kind, so
+    # the buffers grow for the second kind and are reused for the third)
+    for every, n in ((10, 120_000), (1, 250_000), (0, 1_200_000)):
         rows = []
         for i in range(n):
-            alt = "ATT" if i % every == 0 else "G"
+            alt = "ATT" if (i % every == 0 if every else n // 3 <= i < 2 * n // 3) else "G"
             if i % 997 == 5:
                 alt = "<DEL>"  # (a message in the log: its line is read from the cut's text too)
             rows.append("7\t%d\trs%d\tA\t%s\t50\tPASS\tAC=%d;AN=5008" % (100 + 3 * i, i, alt, i % 5000))

@@ -464,10 +464,11 @@ def test_cli_matches_oracle(bv, tmp_path):
     assert p.returncode == 1
 
 
-def test_cli_many_batches_with_capacity_growth(bv):
+def test_cli_many_batches_with_capacity_growth(bv, tmp_path):
     """the pipelined driver over a dozen one-megabyte batches whose line count exceeds the first reservation (short junk
     lines between the records): the formatter runs behind the device, the reservation grows mid-stream, and the
-    rows still come out complete and in input order"""
+    rows still come out complete and in input order -- and with --sampleStats and --dosageOutput on, on one ctx and on
+    two (--devices 0,0), the per-sample table and the dosage rows carry across the growth"""
     import random
     rng = random.Random(77)
     ns = 300
@@ -488,6 +489,18 @@ def test_cli_many_batches_with_capacity_growth(bv):
     assert p.returncode == 0, p.stderr[-500:]
     assert p.stdout == (bv.string_header() + "\n").encode() + out_o
     assert p.stderr.decode() == log_o
+    from test_gpu_sample_stats import table_from_tsv
+    want_table = table_from_tsv(bv, out_o, ["S%05d" % i for i in range(ns)])
+    want_dosage = orc.run_dosage(vcf)
+    assert len(want_dosage) > 1000
+    for tag, extra in (("one", []), ("devices00", ["--devices", "0,0"])):
+        st, dos = tmp_path / (tag + ".stats"), tmp_path / (tag + ".feather")
+        p = _run_cli(["--batchMB", "1", "--sampleStats", str(st), "--dosageOutput", str(dos)] + extra, vcf)
+        assert p.returncode == 0, (tag, p.stderr[-500:])
+        assert p.stdout == (bv.string_header() + "\n").encode() + out_o, tag
+        assert p.stderr.decode() == log_o, tag
+        assert st.read_bytes() == want_table, tag
+        assert _read_matrix(dos)[1] == want_dosage, tag
 
 
 def test_cli_large_stream(bv, golden_1kg):

@@ -3,9 +3,20 @@
 import numpy as np
 import pytest
 
+import blockcheck as bc
 import oracle_lib as orc
 
 pytestmark = pytest.mark.gpu
+
+ORC = bc.Oracle()  # (each full-size block goes through several device paths: one oracle run)
+
+
+def collect_checked(bv, ctx, t, nbytes, hdr, key, cfgd=None):
+    """ctx.collect() of the block in t, with the whole batch's TSV and log compared with the oracle's"""
+    buf, nh = bc.host_copy(t, nbytes, hdr)
+    b = ctx.collect(tsv=(bc.block_view(buf, nh), bv.make_config(cfgd, n_format_threads=bc.THREADS), bc.sample_names(hdr)))
+    ORC.check(key, buf, cfgd, b.tsv, b.log, "block %r" % (key,))
+    return b
 
 
 @pytest.fixture(autouse=True, params=["census", "streaming", "census-wide", "streaming-general"])
@@ -59,8 +70,8 @@ def test_parity_on_bench_shapes(mods, profile, n, cfgd):
 
 
 def test_full_size_properties_c3(mods):
-    """BASELINE-size batch (131 072 rows x 2 504 samples, 1.33 GB) through the device-resident entry:
-    size-independent properties instead of an oracle run: every row is a passing biallelic SNP,
+    """BASELINE-size batch (131 072 rows x 2 504 samples, 1.33 GB) through the device-resident entry: the whole batch's
+    TSV against the oracle, and size-independent properties: every row is a passing biallelic SNP,
     an == 2*ns, ac == n_het + 2*n_hom, ac > 0, and two passes give identical counters."""
     import torch
     bg, bv = mods
@@ -71,7 +82,7 @@ def test_full_size_properties_c3(mods):
     ctx = bv.Ctx(bg.n_header_fields(cfg), max_batch_bytes=nbytes, n_slots=1, max_lines=rows + 16,
                  max_alleles=rows + 1024, cmap_bytes=(rows + 1024 + 16 * 8192) * stride)
     ctx.submit_device(t.data_ptr(), nbytes)
-    b = ctx.collect()
+    b = collect_checked(bv, ctx, t, nbytes, bg.header(cfg), ("c3", 777_000_000, rows))
     assert len(b.lines) == rows and (b.lines["status"] == bv.LINE_OK).all()
     assert (b.lines["n_rec"] == 1).all() and (b.lines["n_fields"] == bg.n_header_fields(cfg)).all()
     al = b.alleles[:rows]
@@ -98,8 +109,8 @@ def test_full_size_properties_c3(mods):
 
 def test_full_size_properties_c4(mods):
     """BASELINE configs[3] at bench size (65 536 rows x 2 504 samples, 20 % multiallelic, 15 % indels,
-    1 % malformed): invariants that hold for every record whatever the data, both device paths agreeing
-    record by record, and oracle spot checks."""
+    1 % malformed): the whole batch's TSV and log against the oracle, invariants that hold for every record whatever the
+    data, and oracle spot checks."""
     import torch
     bg, bv = mods
     cfg = bg.make_cfg("c4")
@@ -110,7 +121,7 @@ def test_full_size_properties_c4(mods):
     ctx = bv.Ctx(bg.n_header_fields(cfg), max_batch_bytes=nbytes, n_slots=1, max_lines=rows + 16,
                  max_alleles=4 * rows, cmap_bytes=(4 * rows + 16 * 8192) * stride)
     ctx.submit_device(t.data_ptr(), nbytes)
-    b = ctx.collect()
+    b = collect_checked(bv, ctx, t, nbytes, bg.header(cfg), ("c4", 42_000_000, rows, "keep"), {"keepId": True, "keepInfo": True})
     ctx.close()
     assert len(b.lines) == rows and b.n_lines_seen == rows
     ok = b.lines["status"] == bv.LINE_OK
@@ -150,8 +161,9 @@ def test_full_size_properties_c4(mods):
 
 def test_block_past_2_gib(mods, bvcf_path):
     """one block of 311 296 rows (3.16 GB, bench.py's block): byte offsets above 2^31 -- the line index, the head
-    windows and the scans compare offsets as unsigned 32-bit values, a signed difference would wrap there.  Size-
-    independent properties over every row, and oracle spot checks on rows from both sides of the 2 GiB mark."""
+    windows and the scans compare offsets as unsigned 32-bit values, a signed difference would wrap there.  The whole
+    batch's TSV against the oracle, size-independent properties over every row, and oracle spot checks on rows from both
+    sides of the 2 GiB mark."""
     if bvcf_path == "census-wide":
         pytest.skip("same kernels as census at this sample count")
     bg, bv = mods
@@ -163,7 +175,7 @@ def test_block_past_2_gib(mods, bvcf_path):
     ctx = bv.Ctx(bg.n_header_fields(cfg), max_batch_bytes=nbytes, n_slots=1, max_lines=rows + 16,
                  max_alleles=rows + 1024, cmap_bytes=(rows + 1024 + 16 * 8192) * stride)
     ctx.submit_device(t.data_ptr(), nbytes)
-    b = ctx.collect()
+    b = collect_checked(bv, ctx, t, nbytes, bg.header(cfg), ("c3", 31_000_000, rows))
     ctx.close()
     assert len(b.lines) == rows and b.n_lines_seen == rows and (b.lines["status"] == bv.LINE_OK).all()
     off = b.lines["off"].astype(np.int64)
