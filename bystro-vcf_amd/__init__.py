@@ -27,7 +27,7 @@ if not os.path.exists(LIB_PATH):
 
 lib = C.CDLL(LIB_PATH)
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 DEVICE_PAD = 64
 NO_CMAP = 0xFFFFFFFF
 
@@ -64,6 +64,7 @@ class Params(C.Structure):
         ("max_batch_bytes", C.c_uint64), ("max_lines", C.c_uint32), ("max_alleles", C.c_uint32),
         ("cmap_bytes", C.c_uint64), ("n_slots", C.c_uint32), ("path", C.c_uint32),
         ("packed_sites", C.c_uint32), ("render_sites", C.c_uint32), ("want_sample_stats", C.c_uint32),
+        ("min_gq", C.c_uint32), ("min_dp", C.c_uint32),
     ]
 
 
@@ -76,6 +77,7 @@ class Config(C.Structure):
         ("max_batch_bytes", C.c_uint64), ("sample_list_path", C.c_char_p),
         ("dosage_path", C.c_char_p), ("no_out", C.c_uint8), ("out_bgzf", C.c_uint8), ("reserved3", C.c_uint8 * 2),
         ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)), ("sample_stats_path", C.c_char_p),
+        ("min_gq", C.c_uint32), ("min_dp", C.c_uint32),
     ]
 
 
@@ -233,6 +235,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     if cfg.get("sampleStats"):  # the per-sample QC table of the run (SAMPLE_STATS_COLUMNS)
         keep.append(str(cfg["sampleStats"]).encode())
         c.sample_stats_path = keep[-1]
+    # --minGQ / --minDP: genotypes whose GQ / DP is a number below the threshold count as missing (0 = off)
+    c.min_gq = int(cfg.get("minGQ", 0))
+    c.min_dp = int(cfg.get("minDP", 0))
     c._keep = keep
     return c
 
@@ -499,7 +504,8 @@ class Ctx:
     def __init__(self, n_header_fields, allow="PASS,.", exclude="", device=0, eol_chars=1, eol_byte=b"\n",
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
-                 empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False):
+                 empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
+                 min_gq=0, min_dp=0):
         p = Params()
         p.abi_version = ABI_VERSION
         p.device = device
@@ -520,6 +526,8 @@ class Ctx:
         p.render_sites = int(render_sites)
         p.want_name_lists = int(sample_names is not None)
         p.want_sample_stats = int(sample_stats)
+        p.min_gq = min_gq  # bvcf_params.min_gq / min_dp: the masked genotype scan (0 = off)
+        p.min_dp = min_dp
         self.n_samples = max(n_header_fields - 9, 0)
         self.h = C.c_void_p()
         rc = lib.bvcf_create(C.byref(self.h), C.byref(p))

@@ -119,6 +119,7 @@ struct bvcf_ctx {
   int device = 0;
   int n_cu = 0;
   int gt_grid = 0, stream_grid = 0;
+  int gt_filter_grid = 0;  // k_gt_filter / k_dosage_filter: what their own registers and LDS window let a CU hold
   hipStream_t scan_stream = nullptr;  // see launch_chain
   uint32_t stream_lds_pad = 0;  // dynamic LDS asked for with k_stream (it uses none): caps the k_stream workgroups of ALL batches per CU
   bool fused = false;
@@ -131,6 +132,9 @@ struct bvcf_ctx {
   int gen_policy = -1;  // -1 adaptive, 0 never, 1 always
   uint32_t gen_grid = 0;
   bool wide = false;  // census path with k_gt_wide in front of k_gt (see kWideSamples)
+  // bvcf_params.min_gq / min_dp on a file with samples: the census chain with k_gt_filter / k_dosage_filter in place of
+  // k_gt / k_dosage, one wave per task at any sample count, whatever the path overrides say (bvcf_gtfilter.hip.h)
+  bool gt_filter = false;
   uint64_t avg_line_bytes = 0;  // of the last collected batch (bvcf_submit_bgzf picks its inflate kernel by it)
   bool names_on = false;  // want_name_lists and bvcf_set_sample_names called: the chain ends with the k_name_* kernels
   uint32_t *d_name_off = nullptr;
@@ -697,6 +701,16 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
     hipLaunchKernelGGL(k_head, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
   if (a.n_samples) {
     if (ev_gt0) hipEventRecord(ev_gt0, st);
+    if (c->gt_filter) {
+      // bvcf_params.min_gq / min_dp: the masked scan and the masked dosage rows; the rest of the chain is the same
+      const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
+      hipLaunchKernelGGL(k_gt_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa);
+      if (ev_gt1) hipEventRecord(ev_gt1, st);
+      hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+      if (a.dosage) hipLaunchKernelGGL(k_dosage_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa);
+      launch_sample_stats(c, a, st, slot);
+      return;
+    }
     if (c->wide) {
       hipMemsetAsync(a.results, 0, (size_t)a.max_tasks * sizeof(GtResult), st);
       hipLaunchKernelGGL(k_gt_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
@@ -1232,6 +1246,10 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
     g_create_err = "bad bvcf_params";
     return BVCF_E_ARG;
   }
+  if (p->min_gq > BVCF_MAX_THRESHOLD || p->min_dp > BVCF_MAX_THRESHOLD) {
+    g_create_err = "bad bvcf_params: min_gq / min_dp above 999999999";
+    return BVCF_E_ARG;
+  }
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || p->device < 0 || p->device >= n_dev) {
     // there is deliberately no CPU fallback
@@ -1270,6 +1288,8 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   }
   uint32_t path = p->path;
   if (const char *e = getenv("BVCF_PATH")) path = (uint32_t)atoi(e);  // test / tuning override
+  c->gt_filter = c->n_samples > 0 && (p->min_gq != 0 || p->min_dp != 0);
+  if (c->gt_filter) path = 1;  // the masked scan lives on the census path only
   // From kWideSamples samples up a line is hundreds of kilobytes and a batch holds too few of them to fill the GPU
   // with one wave per line: the census path then splits the regular scan of a line over several waves, and is
   // what `choose` picks.
@@ -1284,6 +1304,7 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
     c->shape_seen = true;
   }
   if (const char *e = getenv("BVCF_WIDE")) c->wide = !c->fused && c->n_samples > 0 && atoi(e) != 0;  // test / tuning override
+  if (c->gt_filter) c->wide = false;  // k_gt_filter: one wave per (line, ALT index) at any sample count
   if (const char *e = getenv("BVCF_WIDE_WIN")) {  // test / tuning: window of the split general scan, bytes
     const long v = atol(e);
     if (v >= 64 && v <= (64l << 20)) c->win_bytes = (uint32_t)v;
@@ -1308,6 +1329,10 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt, kWgThreads, 0) != hipSuccess || per_cu < 1)
     per_cu = 4;
   c->gt_grid = c->n_cu * per_cu;
+  per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt_filter, kWgThreads, 0) != hipSuccess || per_cu < 1)
+    per_cu = 4;
+  c->gt_filter_grid = c->n_cu * per_cu;
   per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream, kWgThreads, 0) != hipSuccess || per_cu < 1)
     per_cu = 3;

@@ -19,6 +19,12 @@
 //   k_dosage       (bvcf_params.want_dosage) one wave per output allele: the int8 dosage row
 //                  (k_dosage_wide: per share, for the lines k_gt_wide_general scanned)
 //                                                                (main.go:1069-1178)
+//   (bvcf_params.min_gq / min_dp on a file with samples, bvcf_gtfilter.hip.h: the chain above at any sample count and
+//    whatever path was asked for, with
+//    k_gt_filter      in place of k_gt (and of the k_gt_wide* kernels): one wave per task; the wave finds GQ / DP in the
+//                     line's FORMAT column, and every lane that owns a sample field looks its values up in an LDS window
+//                     of the text before it classifies the genotype -- a value below the threshold makes the sample missing
+//    k_dosage_filter  in place of k_dosage: the same scan with the dosage row as output, -1 for a masked sample)
 //
 // Streaming variant for files with samples (KernelArgs.fused): the census, its scans, the scatter
 // and the ALT #1 genotype scan are replaced by ONE pass over the text,
@@ -70,6 +76,7 @@
 #include "bvcf_index.hip.h"
 #include "bvcf_alleles.hip.h"
 #include "bvcf_gtscan.hip.h"
+#include "bvcf_gtfilter.hip.h"
 #include "bvcf_stream.hip.h"
 #include "bvcf_head.hip.h"
 #include "bvcf_sites.hip.h"

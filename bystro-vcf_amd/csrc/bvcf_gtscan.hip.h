@@ -555,6 +555,8 @@ __device__ inline bool gt_scan_fast(const KernelArgs &a, uint32_t s_begin, uint3
 // over waves (k_gt_wide_general).  win->base = TABs of the region before win->lo, i.e. the sample index of the field
 // that holds byte win->lo.  The class map is then zeroed by the caller's predecessor, not here; st and *n_tabs are
 // the share's.
+// (gt_scan_filter, bvcf_gtfilter.hip.h, is this scan with a value lookup per field in front of the classification: the chunk
+// loop, the start masks, the register gate and the empty last field are restated there and have to follow any change here.)
 struct ScanWindow {
   uint32_t lo, hi, base;
 };

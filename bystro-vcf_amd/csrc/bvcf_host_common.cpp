@@ -646,6 +646,13 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
   R.want_rows = !R.cfg->no_out;
   p.want_class_maps = R.want_rows;  // needsLabels, main.go:502
   p.want_sample_stats = R.cfg->sample_stats_path && *R.cfg->sample_stats_path;  // --sampleStats: counted on the device
+  // --minGQ / --minDP: every ctx of the run masks the same way (on the device, inside the genotype scan)
+  if (R.cfg->min_gq > BVCF_MAX_THRESHOLD || R.cfg->min_dp > BVCF_MAX_THRESHOLD) {
+    *msg = "min_gq / min_dp above 999999999";
+    return BVCF_E_ARG;
+  }
+  p.min_gq = R.cfg->min_gq;
+  p.min_dp = R.cfg->min_dp;
   // BVCF_DEVICE_NAMES=1: the sample-name lists of the rows come off the device as text instead of being
   // joined by the formatter from the class maps.  Off by default: measured on the dense profile (every row a common
   // variant, 10 KB of names per row) the text is 16 x the class maps over PCIe and the run gets slower, while the

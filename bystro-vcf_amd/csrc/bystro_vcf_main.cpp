@@ -29,7 +29,21 @@ struct Cli {
   bool out_bgzf = false;
   // extension: --sampleStats PATH, the per-sample QC table of the run's rows (counted on the device)
   std::string sample_stats;
+  // extension: --minGQ N / --minDP N, genotypes whose GQ / DP is a number below N count as missing (masked on the device)
+  uint32_t min_gq = 0, min_dp = 0;
 };
+
+// a decimal integer in 0 .. BVCF_MAX_THRESHOLD, digits only
+bool parse_threshold(const std::string &v, uint32_t *out) {
+  if (v.empty() || v.size() > 9) return false;
+  uint32_t n = 0;
+  for (char ch : v) {
+    if (ch < '0' || ch > '9') return false;
+    n = n * 10u + (uint32_t)(ch - '0');
+  }
+  *out = n;
+  return n <= BVCF_MAX_THRESHOLD;
+}
 
 bool parse_bool(const char *v, bool *out) {
   // strconv.ParseBool
@@ -96,7 +110,8 @@ int parse(int argc, char **argv, Cli &c) {
     if (done) continue;
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
-    if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats") {
+    if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
+        name == "minGQ" || name == "minDP") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -114,6 +129,11 @@ int parse(int argc, char **argv, Cli &c) {
         c.out_bgzf = val == "bgzf";
       } else if (name == "sampleStats") {
         c.sample_stats = val;
+      } else if (name == "minGQ" || name == "minDP") {
+        if (!parse_threshold(val, name == "minGQ" ? &c.min_gq : &c.min_dp)) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
+          return 2;
+        }
       } else
         c.devices = val;
       continue;
@@ -207,6 +227,8 @@ int main(int argc, char **argv) {
   cfg.no_out = c.no_out;               // main.go:88
   cfg.out_bgzf = c.out_bgzf;
   cfg.sample_stats_path = c.sample_stats.c_str();
+  cfg.min_gq = c.min_gq;
+  cfg.min_dp = c.min_dp;
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define BVCF_ABI_VERSION 8
+#define BVCF_ABI_VERSION 9
 
 typedef enum {
   BVCF_OK = 0,
@@ -91,6 +91,7 @@ enum {
 #define BVCF_WIDE_SAMPLES 32768u
 #define BVCF_NO_CMAP 0xFFFFFFFFu
 #define BVCF_DEVICE_PAD 64      /* bytes a device-resident block must own past nbytes */
+#define BVCF_MAX_THRESHOLD 999999999u /* largest bvcf_params.min_gq / min_dp (a value of 10 digits or more is no number) */
 
 typedef struct bvcf_ctx bvcf_ctx;
 
@@ -139,6 +140,21 @@ typedef struct {
   uint32_t want_sample_stats; /* ABI 8: 1 = per-sample counts over the rows of every batch, made on the device from the class
                                  maps (which the ctx then makes even when want_class_maps is 0, without copying them to the
                                  host) and read with bvcf_sample_stats.  A file without samples has an empty table */
+  /* ABI 9, --minGQ / --minDP: genotypes of low quality are masked on the device, inside the genotype scan.  0 = off (the
+   * default; with both off nothing changes), at most BVCF_MAX_THRESHOLD (bvcf_create: BVCF_E_ARG above).  For a data line
+   * with sample columns and a threshold T > 0 on key K ("GQ" for min_gq, "DP" for min_dp):
+   *   - the key's index k is the first position >= 1 of the FORMAT column (the 9th, split at ':') whose text is exactly K
+   *     (position 0 is the genotype); a line whose FORMAT does not name K is not masked by K;
+   *   - a sample's value is subfield k of its field; it is a number iff it exists and is 1..9 ASCII digits;
+   *   - the genotype is masked iff the value is a number below T -- an absent, empty or "." value, one with a sign, a
+   *     decimal point or an exponent, or one of 10 or more digits masks nothing; with both thresholds, either key masks;
+   *   - a masked genotype behaves, for every ALT index of the line, as if its genotype subfield were "./.": class
+   *     missing (BVCF_CLS_MISSING in the class maps, named in missingGenos), nothing added to ac / an, dosage -1.
+   * Field counts, FILTER and allele verdicts and the log read the fixed columns only and do not change; a row whose ac
+   * becomes 0 is dropped like any row no sample carries (main.go:558-560).  A ctx with a threshold and sample columns
+   * runs the census chain (bvcf_path() == 1) with the masked scan, whatever `path` asks for; files without sample
+   * columns accept the thresholds and nothing changes for them. */
+  uint32_t min_gq, min_dp;
 } bvcf_params;
 
 /* one input line; 64 bytes */
@@ -404,6 +420,9 @@ typedef struct {
   /* ABI 8, --sampleStats: bvcf_run_fd / bvcf_run_buffer write the per-sample QC table of the run's rows here (opened before
    * any device work, written at the end of a successful run; the format is in README.md).  NULL or "" = no table */
   const char *sample_stats_path;
+  /* ABI 9, --minGQ / --minDP: bvcf_params.min_gq / min_dp of every ctx of the run (0 = off; bvcf_run_fd / bvcf_run_buffer
+   * fail with BVCF_E_ARG above BVCF_MAX_THRESHOLD).  The output does not depend on devices, batch size or input kind */
+  uint32_t min_gq, min_dp;
 } bvcf_config;
 
 void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
