@@ -41,11 +41,11 @@ SAMPLE_STATS_COLUMNS = ["sample", "het", "hom", "missing", "transitions", "trans
                         "missingness", "trTv"]
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
-BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel"]
+BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
-                "bvcf_plan_threads", "bvcf_plan_fd"]
+                "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -195,6 +195,23 @@ def plan_fd(fd_in, n_workers, max_batch_bytes=0, device_inflate=1, fd_err=2, cap
     rc = lib.bvcf_plan_fd(fd_in, fd_err, n_workers, max_batch_bytes, device_inflate, out, cap, C.byref(n), C.byref(mode), C.byref(plan))
     assert n.value <= cap, "more blocks than room"
     return rc, mode.value, plan, [out[i] for i in range(n.value)]
+
+
+HEAD_FAST_DECLINE, HEAD_FAST_PASS, HEAD_FAST_FILTER = 0, 1, 2
+HAS_HEAD_BITS, NOT_REGULAR, DEFERRED = 0x80000000, 0x40000000, 0xFFFFFFFE
+
+
+def head_fast_line(head, ls, len_flags, counts, cmap_off, tab_bits, line, n_header, allow="PASS,.", exclude=""):
+    """k_order's fast lane on the host (include/bvcf_plan.h) -> (verdict, line record or None, allele record or None)"""
+    # (bound here: BVCF_LIB may name an older build for an A/B run)
+    lib.bvcf_head_fast_line.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32,
+                                        C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
+    L = np.zeros(1, dtype=LINE_DTYPE)
+    A = np.zeros(1, dtype=ALLELE_DTYPE)
+    v = lib.bvcf_head_fast_line(bytes(head), len(head), ls, len_flags, (C.c_uint32 * 5)(*counts), cmap_off,
+                                (C.c_uint32 * 8)(*tab_bits), line, n_header, allow.encode(), exclude.encode(),
+                                L.ctypes.data, A.ctypes.data)
+    return v, (L[0] if v != HEAD_FAST_DECLINE else None), (A[0] if v == HEAD_FAST_PASS else None)
 
 
 class BvcfError(RuntimeError):
@@ -633,6 +650,14 @@ class Ctx:
         lib.bvcf_bench_stream_kernel.restype = C.c_int
         k = lib.bvcf_bench_stream_kernel(self.h)
         return None if k < 0 else ("k_stream_gen" if k else "k_stream")
+
+    def head_left(self):
+        """streaming path: the lines of the last collected batch that k_order left to k_head (None: no batch yet, or not
+        on the streaming path)"""
+        lib.bvcf_bench_head_left.argtypes = [C.c_void_p]
+        lib.bvcf_bench_head_left.restype = C.c_long
+        n = lib.bvcf_bench_head_left(self.h)
+        return None if n < 0 else int(n)
 
     def sample_stats(self, reset=False):
         """bvcf_params.want_sample_stats: the per-sample counts over the rows of the batches collected so far ->

@@ -43,6 +43,7 @@ struct BatchCounters {
   uint32_t n_real;       // streaming path: entries of real_tasks (the task slots that hold a scan, for k_gt)
   uint32_t n_other_shape;  // streaming path: listed lines that were not of the shape the kernel is made for -- k_stream: not the
                            // 4-byte grid (left to k_gt); k_stream_gen: of the 4-byte grid.  The host picks the next batch's kernel by it.
+  uint32_t n_left;       // streaming path: entries of left_lines (the lines k_order did not settle itself: k_head's work list)
 };
 
 // streaming path: what k_stream knows about a line when it has scanned it
@@ -120,6 +121,8 @@ struct KernelArgs {
   uint32_t *line_bits;   // [max_lines][8] the same, in input order (k_order)
   uint32_t *finish_items;// [max_lines] streaming path: the lines k_finish settles (verdict + record counts)
   uint32_t *real_tasks;  // [max_tasks] streaming path: the task slots past n_lines that hold a scan (or kNoTask), see k_head
+  uint32_t *left_lines;  // [max_lines] streaming path: the lines k_order left to k_head, in no particular order (counters->n_left)
+  uint32_t head_fast;    // 1: k_order settles plain SNP lines itself (bvcf_headfast.hip.h); 0: it lists every line for k_head
   // k_sites1: the FILTER gate of the common lines as dwords (see bvcf_sites1.hip.h; 0 = no such table, 1 = keys, 2 = no test)
   uint32_t s1_fmode;
   uint32_t s1_fkey[4], s1_flen[4];

@@ -5,6 +5,7 @@
 // collect = wait, size check, D2H of exactly the used parts of the result arrays.
 #include "bvcf_device.hip.h"
 #include "../../include/bvcf_bench.h"
+#include "../../include/bvcf_plan.h"
 #include "bvcf_bgzf.h"
 #include "bvcf_bgzf_out.h"
 
@@ -62,6 +63,7 @@ struct Slot {
   uint32_t win_tabs_cap = 0;
   StreamEntry *d_entries = nullptr;
   uint32_t *d_line_len = nullptr, *d_line_cmap = nullptr, *d_line_bits = nullptr, *d_finish_items = nullptr;
+  uint32_t *d_left_lines = nullptr;  // streaming path: the lines k_order leaves to k_head
   uint16_t *d_head_bits = nullptr;
   // device-side name lists (want_name_lists)
   bvcf_names *d_name_lists = nullptr, *h_name_lists = nullptr;
@@ -128,6 +130,8 @@ struct bvcf_ctx {
   // kernel's shape switches (the results are the same either way); BVCF_GEN_STREAM=0 / 1 pins it.
   bool gen_mode = false;
   uint32_t last_real = 0xFFFFFFFFu, last_finish = 0xFFFFFFFFu;  // the last collected batch's counters->n_real / n_finish (unknown: full grids)
+  uint32_t last_left = 0xFFFFFFFFu;  // ... and its counters->n_left: the lines k_order left to k_head
+  bool head_fast = true;  // k_order settles plain SNP lines itself (bvcf_headfast.hip.h); BVCF_HEAD_FAST=0: every line goes to k_head
   bool shape_seen = false;  // gen_mode has had its first hint (peek_line_shape) or a batch's counters
   int gen_policy = -1;  // -1 adaptive, 0 never, 1 always
   uint32_t gen_grid = 0;
@@ -247,6 +251,7 @@ void free_slot(Slot &s) {
   hipFree(s.d_line_cmap);
   hipFree(s.d_line_bits);
   hipFree(s.d_finish_items);
+  hipFree(s.d_left_lines);
   hipFree(s.d_head_bits);
   hipFree(s.d_name_lists);
   hipFree(s.d_name_tot);
@@ -354,8 +359,10 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
   hipFree(s.d_line_cmap);
   hipFree(s.d_line_bits);
   hipFree(s.d_finish_items);
+  hipFree(s.d_left_lines);
   s.d_line_bits = nullptr;
   s.d_finish_items = nullptr;
+  s.d_left_lines = nullptr;
   hipHostFree(s.h_lines);
   hipHostFree(s.h_alleles);
   hipHostFree(s.h_errs);
@@ -398,6 +405,7 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
   if (c->fused) {
     HIP_TRY(c, hipMalloc(&s.d_line_bits, c->max_lines * 8 * sizeof(uint32_t)));
     HIP_TRY(c, hipMalloc(&s.d_finish_items, (c->max_lines + c->max_alleles) * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&s.d_left_lines, c->max_lines * sizeof(uint32_t)));
   }
   if (c->packed) {
     s.hcap_recs = std::max<uint64_t>(4096, c->max_lines / 16);
@@ -526,6 +534,8 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.line_bits = s.d_line_bits;
   a.finish_items = s.d_finish_items;
   a.real_tasks = s.d_finish_items ? s.d_finish_items + c->max_lines : nullptr;  // (one allocation: [max_lines] + [max_alleles])
+  a.left_lines = s.d_left_lines;
+  a.head_fast = c->head_fast ? 1u : 0u;
   a.s1_fmode = c->s1_fmode;
   for (int i = 0; i < 4; i++) {
     a.s1_fkey[i] = c->s1_fkey[i];
@@ -547,6 +557,7 @@ void adapt_stream_kernel(bvcf_ctx *c, bool was_gen, const BatchCounters &ctr) {
   // how many scans the last batch left to k_gt, and lines to k_finish: the grids of the next batch's (launch_chain)
   c->last_real = ctr.n_real;
   c->last_finish = ctr.n_finish;
+  c->last_left = ctr.n_left;
   if (c->gen_policy >= 0 || !c->fused || ctr.n_lines < 16) return;
   c->shape_seen = true;
   if ((uint64_t)ctr.n_other_shape * 2u > ctr.n_lines) c->gen_mode = !was_gen;
@@ -610,11 +621,18 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
 #else
     constexpr int skip = 0, head_wgs = 4, gt_div = 1;
 #endif
+    // k_head walks the list of the lines k_order did not settle itself (left_lines), a workgroup step per 256 of them: on a file
+    // of biallelic SNPs those are the first lines of k_stream's runs, a few thousand per block.  As with k_gt and k_finish
+    // below, the grid follows what the last collected batch left; with the fast lane off every line is listed: the full grid.
+    const uint32_t head_full = (uint32_t)c->n_cu * (uint32_t)head_wgs;
+    const uint32_t head_grid = (c->last_left == 0xFFFFFFFFu || !c->head_fast)
+                                   ? head_full
+                                   : std::min<uint32_t>(head_full, std::max<uint32_t>((uint32_t)c->n_cu / 4u, c->last_left / kWgThreads + 1u));
     if (skip & 1) {
     } else if (c->p.n_slots > 1)
-      hipLaunchKernelGGL(k_head_lean, dim3(c->n_cu * head_wgs), dim3(kWgThreads), 0, st, a);
+      hipLaunchKernelGGL(k_head_lean, dim3(head_grid), dim3(kWgThreads), 0, st, a);
     else
-      hipLaunchKernelGGL(k_head, dim3(c->n_cu * head_wgs), dim3(kWgThreads), 0, st, a);
+      hipLaunchKernelGGL(k_head, dim3(head_grid), dim3(kWgThreads), 0, st, a);
     // k_gt and k_finish walk lists (real_tasks, finish_items) with grid strides: any grid is right.  A file of biallelic lines
     // leaves both empty, and a thousand workgroups that start to find that out hold wave slots the next blocks' scans would
     // use; the grids follow what the last collected batch needed (a wave of k_gt per two scans, a thread of k_finish per line).
@@ -1297,6 +1315,7 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   c->fused = c->n_samples > 0 && (path == 2 || path == 3 || (path == 0 && p->n_header_fields >= 256 && !many_samples));
   c->wide = !c->fused && many_samples;
   if (const char *e = getenv("BVCF_GEN_STREAM")) c->gen_policy = atoi(e) != 0 ? 1 : 0;
+  if (const char *e = getenv("BVCF_HEAD_FAST")) c->head_fast = atoi(e) != 0;  // test / tuning override
   if (!c->fused || c->n_samples > 4u * kStageBytes) c->gen_policy = 0;  // (a line's dense class map is staged in LDS)
   c->gen_mode = c->gen_policy == 1;
   if (path == 3 && c->gen_policy < 0) {  // the caller has seen a line: its sample fields carry more than GT
@@ -2139,6 +2158,38 @@ int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
 
 int bvcf_path(const bvcf_ctx *c) { return c ? (c->fused ? 2 : 1) : BVCF_E_ARG; }
 int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && c->fused) ? (c->gen_mode ? 1 : 0) : -1; }
+
+long bvcf_bench_head_left(const bvcf_ctx *c) { return (c && c->fused && c->last_left != 0xFFFFFFFFu) ? (long)c->last_left : -1; }
+
+int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, uint32_t len_flags, const uint32_t counts[5],
+                        uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
+                        const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele) {
+  if (!head || !counts || !tab_bits || !out_line || !out_allele) return -1;
+  FilterTable ft;
+  memset(&ft, 0, sizeof ft);
+  uint32_t used = 0;
+  if (fill_filter(allow_filter, true, &ft.allow_nil, &ft.allow_n, ft.allow_off, ft.allow_len, ft.text, &used) ||
+      fill_filter(exclude_filter, false, &ft.deny_nil, &ft.deny_n, ft.deny_off, ft.deny_len, ft.text, &used))
+    return -1;
+  HeadFastHostBytes hb;
+  memset(&hb, 0, sizeof hb);
+  memcpy(hb.b, head, std::min<size_t>(head_bytes, kHeadFastBytes + 16));
+  StreamEntry en;
+  en.ls = ls;
+  en.len = len_flags;
+  en.ac = counts[0];
+  en.an = counts[1];
+  en.n_het = counts[2];
+  en.n_hom = counts[3];
+  en.n_miss = counts[4];
+  en.cmap_off = cmap_off;
+  HeadFastHostOut out;
+  memset(&out, 0, sizeof out);
+  const int v = head_fast_eval(en, tab_bits, hb, line, n_header, &ft, out);
+  if (v != kHeadFastDecline) memcpy(out_line, out.Lw, sizeof out.Lw);
+  if (v == kHeadFastPass) memcpy(out_allele, out.Aw, sizeof out.Aw);
+  return v;
+}
 
 int bvcf_counters(bvcf_ctx *c, uint64_t out[8]) {
   if (!c || !out) return BVCF_E_ARG;

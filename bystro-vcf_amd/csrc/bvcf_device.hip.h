@@ -32,9 +32,11 @@
 //                  fixed columns and scans ALT #1 straight away (the scan's loads ARE the newline
 //                  search: a regular line ends where 4*ns bytes of "x|y<TAB>" end)
 //   (k_stream_gen  the same for sample fields of any shape -- GT:DP:GQ ... --, bvcf_streamgen.hip.h; chosen per batch)
-//   k_order        tile-local line entries -> input-ordered line_off / line_len / results and the batch's line count
-//                  (a workgroup adds up the one-pass kernel's per-wave line totals and scans its own tiles' counts itself)
-// after which k_head (k_head_lean when blocks are in flight), k_gt -- only the task slots k_head listed as holding a scan:
+//   k_order        tile-local line entries -> input order and the batch's line count (a workgroup adds up the one-pass
+//                  kernel's per-wave line totals and scans its own tiles' counts itself); a plain SNP line -- one-byte REF,
+//                  one-byte ACGT ALT, FILTER decided -- gets its line and allele record here (bvcf_headfast.hip.h), every
+//                  other line its input-ordered line_off / line_len / line_cmap / line_bits and a place in left_lines
+// after which k_head (k_head_lean when blocks are in flight) takes the lines of left_lines, k_gt -- only the task slots k_head listed as holding a scan:
 // deferred lines and further ALT indices of dense lines; it fills their allele records itself -- and k_finish (lines whose
 // ALT #1 was deferred) run.
 //

@@ -179,12 +179,16 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
   const int lane = lane_id();
   const int w = threadIdx.x >> 6;
   const uint32_t n_lines = min(a.counters->n_lines, a.max_lines);
+  // streaming chains: the lines k_order did not settle itself, in the order of its list (any order is right: a line's own
+  // record and task slot are its number, the further ones come from atomics as before); otherwise every line, in input order
+  const uint32_t n_walk = a.fused ? min(a.counters->n_left, n_lines) : n_lines;
+  auto line_at = [&](uint32_t at) -> uint32_t { return a.fused ? a.left_lines[at] : at; };
   const uint32_t stride = gridDim.x * kLinesPerStep;
   const uint32_t need = min(9u, a.n_header - 1u);  // TABs that bound the fixed columns we read
   const uint32_t ns = a.n_samples;
   const bool maps = a.want_cmap && ns > 0;
 
-  for (uint32_t line0 = blockIdx.x * kLinesPerStep; line0 < n_lines; line0 += stride) {
+  for (uint32_t line0 = blockIdx.x * kLinesPerStep; line0 < n_walk; line0 += stride) {
     __syncthreads();  // LDS of the previous step is free (also covers the s_ft copy)
     HSTAMP_A(0);
 
@@ -192,9 +196,11 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
     // lane gl of a group fetches the offsets of the group's round-gl line, so the 16 rounds' offsets
     // are in flight together; the first window of round r + 1 is requested before round r is parsed
     uint32_t my_ls = 0, my_len = 0;
-    uint32_t my_line_ls = 0, my_line_len = 0;  // (streaming chains: of line line0 + threadIdx.x)
+    uint32_t my_line_ls = 0, my_line_len = 0;  // (streaming chains: of the line at line0 + threadIdx.x)
+    // the line this thread takes through phase S
+    const uint32_t my_line = line0 + threadIdx.x < n_walk ? line_at(line0 + threadIdx.x) : n_lines;
     if (!kAllWindows) {
-      const uint32_t l = line0 + threadIdx.x;
+      const uint32_t l = my_line;
       if (l < n_lines) {
         my_line_ls = a.line_off[l];
         if (a.fused) {
@@ -205,7 +211,8 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
         }
       }
     } else {
-      const uint32_t l = line0 + (uint32_t)gl * kGroupsPerWg + g;
+      const uint32_t at = line0 + (uint32_t)gl * kGroupsPerWg + g;
+      const uint32_t l = at < n_walk ? line_at(at) : n_lines;
       if (l < n_lines) {
         my_ls = a.line_off[l];
         if (a.fused) {
@@ -233,8 +240,7 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
     }
     auto tokenise = [&](uint32_t r, uint32_t ls, uint32_t len_flag, const u32x4 &v_first) {
       const uint32_t ll = r * kGroupsPerWg + g;
-      const uint32_t line = line0 + ll;
-      if (line >= n_lines) return;
+      if (line0 + ll >= n_walk) return;
       const uint32_t len = len_flag & ~kHasHeadBits;
       if (len_flag & kHasHeadBits) {
         // k_stream found this line's TABs when it parsed the head window (line_bits): only stage the bytes here
@@ -326,10 +332,10 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
       for (uint32_t r = 0; r < kHeadRounds; r++) {
         const uint32_t ll = r * kLinesPerRound + threadIdx.x / kLanesPerHead;
         hv[r] = u32x4{0u, 0u, 0u, 0u};
-        if (line0 + ll < n_lines && (s_len[ll] & kHasHeadBits)) hv[r] = load16(a.buf, s_ls[ll] + 16u * hq, a.cap);
+        if (line0 + ll < n_walk && (s_len[ll] & kHasHeadBits)) hv[r] = load16(a.buf, s_ls[ll] + 16u * hq, a.cap);
       }
       {
-        const uint32_t line = line0 + threadIdx.x;
+        const uint32_t line = my_line;
         if (line < n_lines && (my_line_len & kHasHeadBits)) {
           const u32x4 *bits = reinterpret_cast<const u32x4 *>(a.line_bits + (size_t)line * 8u);
           pre_b0 = bits[0];
@@ -343,7 +349,7 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
 #pragma unroll
       for (uint32_t r = 0; r < kHeadRounds; r++) {
         const uint32_t ll = r * kLinesPerRound + threadIdx.x / kLanesPerHead;
-        if (line0 + ll < n_lines && (s_len[ll] & kHasHeadBits)) {
+        if (line0 + ll < n_walk && (s_len[ll] & kHasHeadBits)) {
           uint32_t *row = &s_head[ll * kHeadRow + 4u * hq];
           row[0] = hv[r].x;
           row[1] = hv[r].y;
@@ -355,7 +361,7 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
       // the text, 16 lanes a line, the first window of the next round's line requested before this round's is parsed
       auto wants = [&](uint32_t r) -> bool {
         const uint32_t ll = r * kGroupsPerWg + g;
-        return r < kRounds && line0 + ll < n_lines && !(s_len[ll] & kHasHeadBits);
+        return r < kRounds && line0 + ll < n_walk && !(s_len[ll] & kHasHeadBits);
       };
       u32x4 v_next = {0u, 0u, 0u, 0u};
       if (wants(0)) v_next = load16(a.buf, s_ls[g] + 16u * gl, a.cap);
@@ -374,7 +380,7 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
     HSTAMP_A(1);
     // ================= phase S: one lane per line =================
     const uint32_t ll = threadIdx.x;
-    const uint32_t line = line0 + ll;
+    const uint32_t line = my_line;
     const bool active = line < n_lines;
     const uint32_t ls = active ? s_ls[ll] : 0u, len_flag = active ? s_len[ll] : 0u;
     const uint32_t len = len_flag & ~kHasHeadBits;
@@ -647,7 +653,7 @@ __device__ __forceinline__ void k_head_body(const KernelArgs &a) {
         const uint32_t o_mode = o_flags & 3u;
         const bool o_deferred = (o_flags & 4u) != 0, o_fits = (o_flags & 8u) != 0, o_final0 = (o_flags & 16u) != 0;
         // the owner's line: its bytes and fixed columns are in the LDS of this workgroup step
-        const uint32_t oll = (uint32_t)w * kWave + o, o_line = line0 + oll;
+        const uint32_t oll = (uint32_t)w * kWave + o, o_line = from_owner(line);
         const uint32_t o_ls = s_ls[oll], o_cend = o_ls + (s_len[oll] & ~kHasHeadBits);
         const uint32_t *otab = &s_tab[oll * kTabRow];
         AlleleCtx c;

@@ -6,6 +6,7 @@
 
 #include "bvcf_common.hip.h"
 #include "bvcf_gtscan.hip.h"
+#include "bvcf_headfast.hip.h"
 
 namespace bvcf_dev {
 
@@ -13,6 +14,7 @@ namespace bvcf_dev {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 constexpr uint32_t kDeferred = 0xFFFFFFFEu;  // StreamEntry.n_miss / GtResult.n_fields: scan left to k_gt
+static_assert(kDeferred == kHfDeferred, "head_fast_eval's copy");
 
 // first terminator byte at a position in [from, limit), or kNone; 4 KiB in flight per step
 __device__ inline uint32_t find_eol(const KernelArgs &a, uint32_t from, uint32_t limit) {
@@ -486,6 +488,31 @@ namespace bvcf_dev {
 // blocks' k_stream holds.  Workgroup b owns the tiles of a few consecutive waves of the one-pass kernel (their runs are
 // contiguous); the lines before them are the sum of those waves' totals (run_lines: a few thousand words), and an exclusive
 // scan of its own tiles' counts in LDS gives every entry its place.
+// a line's head for head_fast_eval: read where it lies (a byte of REF, a byte of ALT, sixteen bytes from FILTER's start)
+struct HeadFastDeviceBytes {
+  const uint8_t *p;  // the line's first byte
+  uint32_t room;     // bytes that may be read from there
+  __device__ __forceinline__ uint32_t byte(uint32_t rel) const { return rel < room ? p[rel] : 0u; }
+  __device__ __forceinline__ void bytes16(uint32_t rel, uint32_t out[4]) const {
+    const u32x4 v = load16(p, rel, room);
+    out[0] = v.x;
+    out[1] = v.y;
+    out[2] = v.z;
+    out[3] = v.w;
+  }
+};
+
+// ... and its records: 64 bytes each, stored as they are made
+struct HeadFastDeviceOut {
+  u32x4 *lp, *ap;
+  __device__ __forceinline__ static void put(u32x4 *d, const uint32_t w[16]) {
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) d[q] = u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
+  }
+  __device__ __forceinline__ void line(const uint32_t w[16]) { put(lp, w); }
+  __device__ __forceinline__ void allele(const uint32_t w[16]) { put(ap, w); }
+};
+
 __global__ __launch_bounds__(kWgThreads) void k_order(KernelArgs a) {
   __shared__ uint32_t s_part[2][kWavesPerWg];
   __shared__ uint32_t s_first[kWgThreads + 1];
@@ -541,37 +568,81 @@ __global__ __launch_bounds__(kWgThreads) void k_order(KernelArgs a) {
     s_first[threadIdx.x] = wbase + pre;
     if (threadIdx.x == 0) s_first[kWgThreads] = total;
     __syncthreads();
-    const uint32_t pairs = n_here * a.tile_quota;
-    for (uint32_t i = threadIdx.x; i < pairs; i += kWgThreads) {
-      const uint32_t tl = i / a.tile_quota, k = i % a.tile_quota;
-      const uint32_t first = s_first[tl];
-      const uint32_t next = tl + 1u < kWgThreads ? s_first[tl + 1u] : s_first[kWgThreads];
-      if (k >= next - first) continue;
-      const uint32_t g = base + first + k;
-      if (g >= a.max_lines) continue;
-      const size_t ei = (size_t)(c0 + tl) * a.tile_quota + k;
-      const StreamEntry en = a.entries[ei];
-      a.line_off[g] = en.ls;
-      a.line_len[g] = en.len & ~kNotRegular;  // (bit 31: line_bits[g] is valid)
-      a.line_cmap[g] = en.cmap_off;
-      if (en.len & kHasHeadBits) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(a.head_bits + ei * 16u);
-        u32x4 *dst = reinterpret_cast<u32x4 *>(a.line_bits + (size_t)g * 8u);
-        dst[0] = src[0];
-        dst[1] = src[1];
+    // One thread per LINE of the round, not per (tile, slot) pair: a tile's quota is sized for the shortest line that can pass
+    // the field count, so three quarters of the pairs of a cohort file are empty.  Line j of the round belongs to the last
+    // tile whose first line is <= j (eight steps through s_first); consecutive threads then hold consecutive lines, and the
+    // 64-byte records below leave as one contiguous run per wave.
+    const uint32_t n_round = s_first[kWgThreads];
+    for (uint32_t j0 = 0; j0 < n_round; j0 += kWgThreads) {
+      const uint32_t j = j0 + threadIdx.x;
+      const uint32_t g = base + j;
+      const bool live = j < n_round && g < a.max_lines;
+      bool left = false;
+      if (live) {
+        uint32_t lo = 0;  // s_first[lo] <= j < s_first[lo + 2 s]
+#pragma unroll
+        for (uint32_t s = kWgThreads / 2u; s >= 1u; s >>= 1)
+          if (s_first[lo + s] <= j) lo += s;
+        const uint32_t tl = lo, k = j - s_first[lo];
+        const size_t ei = (size_t)(c0 + tl) * a.tile_quota + k;
+        // the entry and -- whether it has one or not: the address does not depend on the entry -- its TAB bitmap, together
+        const u32x4 *ep = reinterpret_cast<const u32x4 *>(a.entries + ei);
+        const u32x4 *bp = reinterpret_cast<const u32x4 *>(a.head_bits + ei * 16u);
+        const u32x4 e0 = ep[0], e1 = ep[1];
+        const u32x4 b0 = bp[0], b1 = bp[1];
+        StreamEntry en;
+        en.ls = e0.x;
+        en.len = e0.y;
+        en.ac = e0.z;
+        en.an = e0.w;
+        en.n_het = e1.x;
+        en.n_hom = e1.y;
+        en.n_miss = e1.z;
+        en.cmap_off = e1.w;
+        if (g < a.max_tasks) {
+          // (k_head reads it for the lines left to it; k_dosage reads `regular` for every record's task)
+          GtResult r;
+          r.ac = en.ac;
+          r.an = en.an;
+          r.n_het = en.n_het;
+          r.n_hom = en.n_hom;
+          r.n_miss = en.n_miss;
+          r.n_fields = en.n_miss == kDeferred ? kDeferred : a.n_header - 9u;
+          // (k_stream only lists counts of lines its regular scan accepted; k_stream_gen marks lines with haploid / odd fields)
+          r.regular = (en.n_miss == kDeferred || (en.len & kNotRegular)) ? 0u : 1u;
+          r.pad = 0;
+          a.results[g] = r;
+        }
+        // ---- the fast lane: a plain SNP line is settled here (bvcf_headfast.hip.h)
+        int verdict = kHeadFastDecline;
+        if (a.head_fast && (en.len & kHasHeadBits) && g < a.max_alleles && g < a.max_tasks) {
+          const uint32_t bits[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+          const HeadFastDeviceBytes head = {a.buf + en.ls, a.cap - min(a.cap, en.ls)};
+          HeadFastDeviceOut out = {reinterpret_cast<u32x4 *>(a.lines + g), reinterpret_cast<u32x4 *>(a.alleles + g)};
+          verdict = head_fast_eval(en, bits, head, g, a.n_header, a.filters, out);
+          if (verdict == kHeadFastFilterFail) a.alleles[g].gt_task = kHfNoTask;  // the slot holds no record
+        }
+        if (verdict == kHeadFastDecline) {
+          // ---- left to k_head: what it reads of the line, in input order
+          left = true;
+          a.line_off[g] = en.ls;
+          a.line_len[g] = en.len & ~kNotRegular;  // (bit 31: line_bits[g] is valid)
+          a.line_cmap[g] = en.cmap_off;
+          if (en.len & kHasHeadBits) {
+            // (read again: a cache hit, and the fast lane above runs without eight registers held for this copy)
+            u32x4 *dst = reinterpret_cast<u32x4 *>(a.line_bits + (size_t)g * 8u);
+            dst[0] = bp[0];
+            dst[1] = bp[1];
+          }
+        }
       }
-      if (g < a.max_tasks) {
-        GtResult r;
-        r.ac = en.ac;
-        r.an = en.an;
-        r.n_het = en.n_het;
-        r.n_hom = en.n_hom;
-        r.n_miss = en.n_miss;
-        r.n_fields = en.n_miss == kDeferred ? kDeferred : a.n_header - 9u;
-        // (k_stream only lists counts of lines its regular scan accepted; k_stream_gen marks lines with haploid / odd fields)
-        r.regular = (en.n_miss == kDeferred || (en.len & kNotRegular)) ? 0u : 1u;
-        r.pad = 0;
-        a.results[g] = r;
+      // k_head's work list: one atomic per wave, in no particular order
+      const unsigned long long lm = __ballot(left);
+      if (lm) {
+        uint32_t at = 0;
+        if (lane == 0) at = atomicAdd(&a.counters->n_left, (uint32_t)__popcll(lm));
+        at = bcast0(at) + __builtin_amdgcn_mbcnt_hi((uint32_t)(lm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)lm, 0u));
+        if (left) a.left_lines[at] = g;  // (g < max_lines, every g once: at most max_lines entries)
       }
     }
     base += s_first[kWgThreads];  // (every thread reads it before the next round's first barrier)

@@ -30,6 +30,10 @@ int bvcf_bench_device_slots(bvcf_ctx *ctx, const void *const *device_blocks, con
  * (-1: the ctx is not on the streaming path) */
 int bvcf_bench_stream_kernel(const bvcf_ctx *ctx);
 
+/* streaming path: how many lines of the last collected batch (bvcf_collect, bvcf_bench_device*) k_order left to k_head --
+ * the ones its fast lane did not settle; -1: no batch yet, or the ctx is not on the streaming path */
+long bvcf_bench_head_left(const bvcf_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

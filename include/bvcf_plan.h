@@ -21,6 +21,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "bvcf.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -100,6 +102,19 @@ typedef struct {
  * Returns BVCF_OK or the status bvcf_run_fd would fail with (message on fd_err). */
 int bvcf_plan_fd(int fd_in, int fd_err, uint32_t n_workers, uint64_t max_batch_bytes, int device_inflate,
                  bvcf_plan_block *out, size_t cap, size_t *n_out, int *mode_out, bvcf_range_plan *plan_out);
+
+/* The fast lane of the streaming path's k_order (csrc/bvcf_headfast.hip.h), run on the host: the same function decides
+ * whether a line is settled without k_head and computes its records.  head = the line's first head_bytes bytes (80 are
+ * looked at, at most); ls = the line's offset in its block (only ls & 3 and the records' `off` depend on it); len_flags =
+ * the content length with bit 31 set when tab_bits is valid (bit 30: counts not from the regular scan); counts = {ac, an,
+ * n_het, n_hom, n_miss} of ALT #1 (n_miss 0xFFFFFFFE: the scan was left to k_gt); cmap_off as k_stream lists it (low bits: the
+ * encoding); tab_bits = the TABs of the 256 bytes from block offset ls & ~3, bit i = byte (ls & ~3) + i; line = the line's
+ * input-order index; the FILTER sets as bvcf_params has them.
+ * Returns 0: declined (k_head takes the line, nothing written); 1: settled, *out_line and *out_allele are the records;
+ * 2: settled as a FILTER failure, *out_line only; -1: bad arguments. */
+int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, uint32_t len_flags, const uint32_t counts[5],
+                        uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
+                        const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele);
 
 #ifdef __cplusplus
 }
