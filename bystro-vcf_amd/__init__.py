@@ -28,6 +28,7 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 ABI_VERSION = 9
+ABI_VERSION_SUBSET = 10  # bvcf_params.abi_version of a ctx that is to read sample_keep (BVCF_ABI_VERSION_SUBSET)
 DEVICE_PAD = 64
 NO_CMAP = 0xFFFFFFFF
 
@@ -64,7 +65,7 @@ class Params(C.Structure):
         ("max_batch_bytes", C.c_uint64), ("max_lines", C.c_uint32), ("max_alleles", C.c_uint32),
         ("cmap_bytes", C.c_uint64), ("n_slots", C.c_uint32), ("path", C.c_uint32),
         ("packed_sites", C.c_uint32), ("render_sites", C.c_uint32), ("want_sample_stats", C.c_uint32),
-        ("min_gq", C.c_uint32), ("min_dp", C.c_uint32),
+        ("min_gq", C.c_uint32), ("min_dp", C.c_uint32), ("sample_keep", C.POINTER(C.c_uint32)),
     ]
 
 
@@ -78,6 +79,7 @@ class Config(C.Structure):
         ("dosage_path", C.c_char_p), ("no_out", C.c_uint8), ("out_bgzf", C.c_uint8), ("reserved3", C.c_uint8 * 2),
         ("n_devices", C.c_uint32), ("devices", C.POINTER(C.c_int32)), ("sample_stats_path", C.c_char_p),
         ("min_gq", C.c_uint32), ("min_dp", C.c_uint32),
+        ("keep_samples_path", C.c_char_p), ("exclude_samples_path", C.c_char_p),
     ]
 
 
@@ -255,6 +257,13 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # --minGQ / --minDP: genotypes whose GQ / DP is a number below the threshold count as missing (0 = off)
     c.min_gq = int(cfg.get("minGQ", 0))
     c.min_dp = int(cfg.get("minDP", 0))
+    # --keepSamples / --excludeSamples: the path of a list of sample names; the run works on those / on all but those
+    if cfg.get("keepSamples"):
+        keep.append(str(cfg["keepSamples"]).encode())
+        c.keep_samples_path = keep[-1]
+    if cfg.get("excludeSamples"):
+        keep.append(str(cfg["excludeSamples"]).encode())
+        c.exclude_samples_path = keep[-1]
     c._keep = keep
     return c
 
@@ -522,7 +531,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0):
+                 min_gq=0, min_dp=0, sample_keep=None):
         p = Params()
         p.abi_version = ABI_VERSION
         p.device = device
@@ -546,6 +555,16 @@ class Ctx:
         p.min_gq = min_gq  # bvcf_params.min_gq / min_dp: the masked genotype scan (0 = off)
         p.min_dp = min_dp
         self.n_samples = max(n_header_fields - 9, 0)
+        if sample_keep is not None:
+            # bvcf_params.sample_keep: the indices of the samples the ctx keeps; everything it returns is then indexed by a
+            # sample's rank among them (n_samples = their number)
+            words = (C.c_uint32 * max((self.n_samples + 31) // 32, 1))()
+            for s in set(int(s) for s in sample_keep):
+                if 0 <= s < 32 * len(words):  # (bits at or beyond n_samples are the library's to ignore)
+                    words[s >> 5] |= 1 << (s & 31)
+            p.abi_version = ABI_VERSION_SUBSET
+            p.sample_keep = words  # (bvcf_create copies it)
+            self.n_samples = len(set(int(s) for s in sample_keep if 0 <= int(s) < self.n_samples))
         self.h = C.c_void_p()
         rc = lib.bvcf_create(C.byref(self.h), C.byref(p))
         if rc:

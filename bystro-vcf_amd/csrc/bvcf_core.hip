@@ -139,6 +139,14 @@ struct bvcf_ctx {
   // bvcf_params.min_gq / min_dp on a file with samples: the census chain with k_gt_filter / k_dosage_filter in place of
   // k_gt / k_dosage, one wave per task at any sample count, whatever the path overrides say (bvcf_gtfilter.hip.h)
   bool gt_filter = false;
+  // bvcf_params.sample_keep on a file with samples: the same chain with k_gt_subset / k_dosage_subset as its scans
+  // (bvcf_gtsubset.hip.h; they apply the thresholds too).  n_samples, cmap_stride and dosage_stride are then those of the
+  // kept samples -- what every kernel behind the scan and the caller see --, n_samples_full is the file's count
+  bool gt_subset = false;
+  uint32_t n_samples_full = 0;
+  uint32_t n_rank_words = 0;
+  uint2 *d_rank = nullptr;  // SubsetArgs.rank
+  int gt_subset_grid = 0;
   uint64_t avg_line_bytes = 0;  // of the last collected batch (bvcf_submit_bgzf picks its inflate kernel by it)
   bool names_on = false;  // want_name_lists and bvcf_set_sample_names called: the chain ends with the k_name_* kernels
   uint32_t *d_name_off = nullptr;
@@ -719,6 +727,18 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
     hipLaunchKernelGGL(k_head, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
   if (a.n_samples) {
     if (ev_gt0) hipEventRecord(ev_gt0, st);
+    if (c->gt_subset) {
+      // bvcf_params.sample_keep: the scan and the dosage rows of the kept samples (masked as well, with a threshold); the
+      // rest of the chain is the same, over n_keep samples
+      const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
+      const SubsetArgs sa = {c->d_rank, c->n_samples_full, c->n_rank_words};
+      hipLaunchKernelGGL(k_gt_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa);
+      if (ev_gt1) hipEventRecord(ev_gt1, st);
+      hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+      if (a.dosage) hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa);
+      launch_sample_stats(c, a, st, slot);
+      return;
+    }
     if (c->gt_filter) {
       // bvcf_params.min_gq / min_dp: the masked scan and the masked dosage rows; the rest of the chain is the same
       const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
@@ -1254,19 +1274,40 @@ void bvcf_destroy(bvcf_ctx *c) {
   hipFree(c->d_row_fmt);
   hipFree(c->d_name_off);
   hipFree(c->d_name_text);
+  hipFree(c->d_rank);
   delete c;
 }
 
 int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   if (!out || !p) return BVCF_E_ARG;
   *out = nullptr;
-  if (p->abi_version != BVCF_ABI_VERSION || p->n_header_fields < 1 || p->eol_chars < 1 || p->eol_chars > 2) {
+  // (abi_version BVCF_ABI_VERSION: the caller's struct ends behind min_dp, and nothing behind it is read)
+  const bool has_keep = p->abi_version == BVCF_ABI_VERSION_SUBSET;
+  if ((p->abi_version != BVCF_ABI_VERSION && !has_keep) || p->n_header_fields < 1 || p->eol_chars < 1 || p->eol_chars > 2) {
     g_create_err = "bad bvcf_params";
     return BVCF_E_ARG;
   }
   if (p->min_gq > BVCF_MAX_THRESHOLD || p->min_dp > BVCF_MAX_THRESHOLD) {
     g_create_err = "bad bvcf_params: min_gq / min_dp above 999999999";
     return BVCF_E_ARG;
+  }
+  // bvcf_params.sample_keep: one {keep bits, kept before} entry per 32 samples; bits from n_samples on are ignored
+  const uint32_t ns_full = p->n_header_fields > 9 ? p->n_header_fields - 9 : 0;
+  std::vector<uint2> rank;
+  uint32_t n_keep = ns_full;
+  if (has_keep && p->sample_keep && ns_full) {
+    n_keep = 0;
+    rank.resize((ns_full + 31u) / 32u);
+    for (uint32_t w = 0; w < rank.size(); w++) {
+      const uint32_t left = ns_full - 32u * w;
+      const uint32_t bits = p->sample_keep[w] & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
+      rank[w] = make_uint2(bits, n_keep);
+      n_keep += (uint32_t)__builtin_popcount(bits);
+    }
+    if (!n_keep) {
+      g_create_err = "bad bvcf_params: sample_keep keeps no sample";
+      return BVCF_E_ARG;
+    }
   }
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || p->device < 0 || p->device >= n_dev) {
@@ -1275,13 +1316,15 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
     return BVCF_E_NODEV;
   }
   bvcf_ctx *c = new bvcf_ctx();
-  c->p = *p;
+  memcpy(&c->p, p, offsetof(bvcf_params, sample_keep));  // (sample_keep, the caller's array, is in the rank table above)
   c->device = p->device;
   if (!c->p.max_batch_bytes) c->p.max_batch_bytes = 64ull << 20;
   if (c->p.max_batch_bytes >= kMaxBlockBytes) c->p.max_batch_bytes = kMaxBlockBytes - 1;
   if (!c->p.n_slots) c->p.n_slots = 3;  // (measured better than 2 or equal on every input shape: profiles/r05_blocks_in_flight_2_vs_3_all_profiles.txt)
   if (!c->p.eol_byte) c->p.eol_byte = '\n';
-  c->n_samples = p->n_header_fields > 9 ? p->n_header_fields - 9 : 0;
+  c->n_samples_full = ns_full;
+  c->n_samples = n_keep;  // (== ns_full without a mask)
+  c->gt_subset = !rank.empty();
   c->cmap_stride = ((c->n_samples + 3) / 4 + 15) & ~15u;
   c->dosage_stride = p->want_dosage && c->n_samples ? ((c->n_samples + 15) & ~15u) : 0u;
   const uint64_t min_line = std::max<uint64_t>(48, 2ull * p->n_header_fields);
@@ -1307,11 +1350,11 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   uint32_t path = p->path;
   if (const char *e = getenv("BVCF_PATH")) path = (uint32_t)atoi(e);  // test / tuning override
   c->gt_filter = c->n_samples > 0 && (p->min_gq != 0 || p->min_dp != 0);
-  if (c->gt_filter) path = 1;  // the masked scan lives on the census path only
+  if (c->gt_filter || c->gt_subset) path = 1;  // the masked scan and the subset scan live on the census path only
   // From kWideSamples samples up a line is hundreds of kilobytes and a batch holds too few of them to fill the GPU
   // with one wave per line: the census path then splits the regular scan of a line over several waves, and is
   // what `choose` picks.
-  const bool many_samples = c->n_samples >= kWideSamples;
+  const bool many_samples = c->n_samples_full >= kWideSamples;
   c->fused = c->n_samples > 0 && (path == 2 || path == 3 || (path == 0 && p->n_header_fields >= 256 && !many_samples));
   c->wide = !c->fused && many_samples;
   if (const char *e = getenv("BVCF_GEN_STREAM")) c->gen_policy = atoi(e) != 0 ? 1 : 0;
@@ -1323,7 +1366,7 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
     c->shape_seen = true;
   }
   if (const char *e = getenv("BVCF_WIDE")) c->wide = !c->fused && c->n_samples > 0 && atoi(e) != 0;  // test / tuning override
-  if (c->gt_filter) c->wide = false;  // k_gt_filter: one wave per (line, ALT index) at any sample count
+  if (c->gt_filter || c->gt_subset) c->wide = false;  // k_gt_filter, k_gt_subset: one wave per (line, ALT index) at any sample count
   if (const char *e = getenv("BVCF_WIDE_WIN")) {  // test / tuning: window of the split general scan, bytes
     const long v = atol(e);
     if (v >= 64 && v <= (64l << 20)) c->win_bytes = (uint32_t)v;
@@ -1352,6 +1395,10 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt_filter, kWgThreads, 0) != hipSuccess || per_cu < 1)
     per_cu = 4;
   c->gt_filter_grid = c->n_cu * per_cu;
+  per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt_subset, kWgThreads, 0) != hipSuccess || per_cu < 1)
+    per_cu = 4;
+  c->gt_subset_grid = c->n_cu * per_cu;
   per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream, kWgThreads, 0) != hipSuccess || per_cu < 1)
     per_cu = 3;
@@ -1472,6 +1519,14 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
       hipMemcpy(c->d_filters, &ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess) {
     c->err = "filter table upload failed";
     return fail(BVCF_E_HIP);
+  }
+  if (c->gt_subset) {
+    c->n_rank_words = (uint32_t)rank.size();
+    if (hipMalloc(&c->d_rank, rank.size() * sizeof(uint2)) != hipSuccess ||
+        hipMemcpy(c->d_rank, rank.data(), rank.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) {
+      c->err = "sample_keep: rank table upload failed";
+      return fail(BVCF_E_HIP);
+    }
   }
   c->slots.resize(c->p.n_slots);
   {

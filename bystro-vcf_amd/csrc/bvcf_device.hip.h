@@ -25,6 +25,14 @@
 //                     line's FORMAT column, and every lane that owns a sample field looks its values up in an LDS window
 //                     of the text before it classifies the genotype -- a value below the threshold makes the sample missing
 //    k_dosage_filter  in place of k_dosage: the same scan with the dosage row as output, -1 for a masked sample)
+//   (bvcf_params.sample_keep on a file with samples, bvcf_gtsubset.hip.h: the same chain, again at any sample count, with
+//    k_gt_subset      in place of k_gt / k_gt_filter: one wave per task walks the whole line -- n_fields is the full
+//                     line's --, skips a field whose sample is not kept before anything is classified, and writes a kept
+//                     sample's class at its rank among the kept samples (a {keep bits, kept before} entry per 32 samples,
+//                     staged in LDS up to 32 768 samples); with a threshold it masks as k_gt_filter does
+//    k_dosage_subset  in place of k_dosage / k_dosage_filter: the same task body, one dosage byte per kept sample
+//    -- KernelArgs.n_samples, cmap_stride and dosage_stride are the kept samples', so every kernel behind the scan runs
+//    as for a file of n_keep samples)
 //
 // Streaming variant for files with samples (KernelArgs.fused): the census, its scans, the scatter
 // and the ALT #1 genotype scan are replaced by ONE pass over the text,
@@ -79,6 +87,7 @@
 #include "bvcf_alleles.hip.h"
 #include "bvcf_gtscan.hip.h"
 #include "bvcf_gtfilter.hip.h"
+#include "bvcf_gtsubset.hip.h"
 #include "bvcf_stream.hip.h"
 #include "bvcf_head.hip.h"
 #include "bvcf_sites.hip.h"

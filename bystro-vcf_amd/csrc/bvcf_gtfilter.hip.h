@@ -64,9 +64,30 @@ __device__ inline void filter_keys(const KernelArgs &a, uint32_t fb, uint32_t fe
 // lists in front of the key) is read from global memory byte by byte.
 //   win: kFiltWin bytes of LDS of this wave.  kq, kd: subfield indices, kNoKey = the key masks nothing on this line; at
 //   least one of them is a key.  tq, td: the thresholds.  dos (optional): the dosage row.
+//
+// The body is written once for the two things a scan of this chain may have to do per field, and compiled per combination:
+//   kKeys    the value lookup above.  Without it (k_gt_subset on a ctx without thresholds, or on a line whose FORMAT names
+//            neither key) nothing is staged in LDS, win is not read and kq / kd / tq / td are ignored.
+//   kSubset  bvcf_params.sample_keep (bvcf_gtsubset.hip.h): ns is the file's sample count; a field whose sample is not
+//            kept is skipped where it is found -- no lookup, no classification --, and a kept one is written at its rank
+//            among the kept samples (sub).  Without it sub is not read, and gt_scan_filter<true, false> is the scan
+//            k_gt_filter has always run.
+//
+// SubsetTab: where the scan reads the rank table of a subset from
+// (the LDS copy is named by an LDS pointer: through a generic one the two sources become one flat load)
+typedef __attribute__((address_space(3))) const uint32_t LdsWord;
+struct SubsetTab {
+  LdsWord *lds;       // the rank table staged in LDS by the workgroup, or null: read it from ...
+  const uint2 *glob;  // ... global memory.  Entry w: {keep bits of samples 32 w .. 32 w + 31, kept samples before 32 w}
+  __device__ __forceinline__ uint2 entry(uint32_t w) const {
+    if (lds) return make_uint2(lds[2u * w], lds[2u * w + 1u]);
+    return glob[w];
+  }
+};
+template <bool kKeys = true, bool kSubset = false>
 __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uint32_t cend, uint32_t ns, uint32_t allele,
                                       uint32_t kq, uint32_t kd, uint32_t tq, uint32_t td, uint8_t *win, uint8_t *cmap,
-                                      GtStats *st, uint32_t *n_tabs, int8_t *dos = nullptr) {
+                                      GtStats *st, uint32_t *n_tabs, int8_t *dos = nullptr, const SubsetTab *sub = nullptr) {
   const int lane = lane_id();
   const uint32_t line_begin = s_begin;
   uint32_t a_nd = 1;
@@ -92,7 +113,7 @@ __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uin
   u32x4 vb[kGenDepth];
 #pragma unroll
   for (int j = 0; j < kGenDepth; j++) vb[j] = fetch(j);
-  if (n_chunks) stage(0u, vb[0]);
+  if (kKeys && n_chunks) stage(0u, vb[0]);
   for (uint32_t c0 = 0; c0 < n_chunks; c0 += kGenDepth) {
 #pragma unroll
     for (int j = 0; j < kGenDepth; j++) {
@@ -101,11 +122,13 @@ __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uin
         const u32x4 v = vb[j];
         // the chunk after this one joins the window (it takes the place of chunk c - 1, whose walks are over: the LDS
         // accesses of a wave complete in order)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        stage(c + 1u, vb[(j + 1) % kGenDepth]);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        if constexpr (kKeys) {
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+          stage(c + 1u, vb[(j + 1) % kGenDepth]);
+          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+          __builtin_amdgcn_wave_barrier();
+        }
         const uint32_t win_end = (c + 2u) * kChunk;  // bytes [lb, lb + win_end) of the text are in the window or were
         // byte g of the text, TAB from the line's end on
         auto getc = [&](uint32_t g) -> uint32_t {
@@ -158,8 +181,16 @@ __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uin
           starts &= starts - 1;
           const uint32_t s = tabs_before + pre + __popc(m & ((1u << k) - 1u));
           if (s >= ns) continue;  // fields past the header's samples are only counted (n_tabs)
+          uint32_t r = s;         // where the sample's class, dosage byte and counts go
+          if constexpr (kSubset) {
+            const uint2 e = sub->entry(s >> 5);
+            if (!((e.x >> (s & 31u)) & 1u)) continue;  // not kept: the field is only a TAB that was counted
+            r = e.y + (uint32_t)__popc(e.x & ((1u << (s & 31u)) - 1u));
+          }
           uint32_t cls = BVCF_CLS_MISSING, altc = 0, gtc = 0;
-          if (!masked_field(off + k)) {
+          bool masked = false;
+          if constexpr (kKeys) masked = masked_field(off + k);
+          if (!masked) {
             // the genotype itself: gt_scan_general's register gate, classify_field otherwise
             const bool in4 = off + k + 4u <= cend;
             const uint32_t i = k >> 2;
@@ -185,8 +216,8 @@ __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uin
           het += cls == BVCF_CLS_HET;
           hom += cls == BVCF_CLS_HOM;
           miss += cls == BVCF_CLS_MISSING;
-          if (dos) dos[s] = cls == BVCF_CLS_MISSING ? (int8_t)-1 : (int8_t)(altc < 127u ? altc : 127u);
-          if (cmap && cls) atomicOr(reinterpret_cast<uint32_t *>(cmap + (s >> 4) * 4u), cls << (2u * (s & 15u)));
+          if (dos) dos[r] = cls == BVCF_CLS_MISSING ? (int8_t)-1 : (int8_t)(altc < 127u ? altc : 127u);
+          if (cmap && cls) atomicOr(reinterpret_cast<uint32_t *>(cmap + (r >> 4) * 4u), cls << (2u * (r & 15u)));
         }
         prev_last_tab = lane_value(m >> 15, kWave - 1) & 1u;
         tabs_before += tot;
@@ -198,8 +229,17 @@ __device__ inline void gt_scan_filter(const KernelArgs &a, uint32_t s_begin, uin
   if (lane == 0) {
     const bool empty_last = (cend == line_begin) || (cend > line_begin && a.buf[cend - 1] == '\t');
     if (empty_last && tabs_before < ns) {
-      an += 1;  // "" is one non-matching allele token
-      if (dos) dos[tabs_before] = 0;
+      uint32_t r = tabs_before;
+      bool kept = true;
+      if constexpr (kSubset) {  // (the last column's field: it counts only if that column is kept)
+        const uint2 e = sub->glob[r >> 5];
+        kept = (e.x >> (r & 31u)) & 1u;
+        r = e.y + (uint32_t)__popc(e.x & ((1u << (r & 31u)) - 1u));
+      }
+      if (kept) {
+        an += 1;  // "" is one non-matching allele token
+        if (dos) dos[r] = 0;
+      }
     }
   }
   st->ac = wave_sum(ac);

@@ -624,6 +624,77 @@ int write_sample_list(const Run &R) {
   return close(fd);
 }
 
+// --keepSamples PATH / --excludeSamples PATH (the rules are in include/bvcf.h): one name per line, a trailing '\r'
+// dropped, empty lines ignored; a name selects every sample column that carries it after normalisation.  From here on
+// R.pre.header is the header of the cut file -- the fixed columns and the kept names in header order --, so the sample
+// list, the formatter's names, the dosage columns, the device name lists and the --sampleStats table are the kept
+// samples' without knowing of the selection; R.n_header_full is what the lines of the file are counted against.
+int select_samples(Run &R, std::string *msg) {
+  R.n_header_full = (uint32_t)R.pre.header.size();
+  R.keep_mask.clear();
+  const char *kp = R.cfg->keep_samples_path, *xp = R.cfg->exclude_samples_path;
+  const bool keep = kp && *kp, excl = xp && *xp;
+  if (!keep && !excl) return BVCF_OK;
+  if (keep && excl) {
+    *msg = "keep_samples_path and exclude_samples_path are both set";
+    return BVCF_E_ARG;
+  }
+  const char *path = keep ? kp : xp;
+  std::string text;
+  {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+      *msg = std::string("open ") + path + ": " + strerror(errno);
+      return BVCF_E_FATAL;
+    }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const int err = ferror(f) ? errno : 0;
+    fclose(f);
+    if (err) {
+      *msg = std::string("read ") + path + ": " + strerror(err);
+      return BVCF_E_FATAL;
+    }
+  }
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+  std::unordered_map<std::string, std::vector<uint32_t>> cols;  // name -> its columns (a header may repeat a name)
+  for (size_t s = 0; s < ns; s++) cols[R.pre.header[9 + s]].push_back((uint32_t)s);
+  std::vector<uint32_t> named((ns + 31) / 32, 0u);
+  for (size_t pos = 0; pos < text.size();) {
+    size_t e = text.find('\n', pos);
+    if (e == std::string::npos) e = text.size();
+    size_t len = e - pos;
+    if (len && text[pos + len - 1] == '\r') len--;
+    if (len) {
+      const std::string name(text, pos, len);
+      const auto it = cols.find(name);
+      if (it == cols.end()) {
+        *msg = std::string(keep ? "keepSamples" : "excludeSamples") + ": no sample column is named \"" + name + "\"";
+        return BVCF_E_FATAL;
+      }
+      for (uint32_t s : it->second) named[s >> 5] |= 1u << (s & 31u);
+    }
+    pos = e + 1;
+  }
+  if (ns == 0) return BVCF_OK;  // (an empty list and no sample columns: nothing to select, the run is the plain one)
+  std::vector<std::string> cut(R.pre.header.begin(), R.pre.header.begin() + 9);
+  R.keep_mask.assign(named.size(), 0u);
+  for (size_t s = 0; s < ns; s++) {
+    const bool in = (named[s >> 5] >> (s & 31u)) & 1u;
+    if (in != keep) continue;
+    R.keep_mask[s >> 5] |= 1u << (s & 31u);
+    cut.push_back(R.pre.header[9 + s]);
+  }
+  if (cut.size() == 9) {
+    *msg = keep ? "keepSamples: the list names no sample, nothing would be left"
+                : "excludeSamples: the list names every sample, nothing would be left";
+    return BVCF_E_FATAL;
+  }
+  R.pre.header.swap(cut);
+  return BVCF_OK;
+}
+
 // What every ctx of the run shares: the sample list file, the ctx parameters (R.params), the name arena, the ratio
 // strings, the formatter's worker pool, the dosage file.  Once per run, after the header is known.
 int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bool make_pool) {
@@ -632,6 +703,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     *msg = "Malformed header: fewer than 8 fields";
     return BVCF_E_FATAL;
   }
+  if (const int rc = select_samples(R, msg)) return rc;
   if (write_sample_list(R)) {  // main.go:298-304
     *msg = "Couldn't write sample list file";
     return BVCF_E_FATAL;
@@ -640,7 +712,11 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
   memset(&p, 0, sizeof p);
   p.abi_version = BVCF_ABI_VERSION;
   p.device = R.cfg->device;
-  p.n_header_fields = (uint32_t)R.pre.header.size();
+  p.n_header_fields = R.n_header_full;  // (the file's: R.pre.header is the kept samples' under --keepSamples / --excludeSamples)
+  if (!R.keep_mask.empty()) {  // (R outlives every bvcf_create of the run)
+    p.abi_version = BVCF_ABI_VERSION_SUBSET;
+    p.sample_keep = R.keep_mask.data();
+  }
   p.eol_chars = R.pre.eol_chars;
   p.eol_byte = R.pre.eol_byte;
   R.want_rows = !R.cfg->no_out;
@@ -688,7 +764,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     for (const uint8_t *q = data, *e = data + look; (q = (const uint8_t *)memchr(q, R.pre.eol_byte, (size_t)(e - q))); q++) n_eol++;
     if (n_eol >= 16) {
       const uint64_t avg = look / n_eol;
-      const uint64_t floor_len = std::max<uint64_t>(48, 2ull * R.pre.header.size());  // the library's own bound
+      const uint64_t floor_len = std::max<uint64_t>(48, 2ull * R.n_header_full);  // the library's own bound
       const uint64_t per_line = std::max<uint64_t>(floor_len, avg / 2);
       // (the slack for short lines between the records, as the library computes it: what 32 MiB of class maps hold)
       const uint64_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;

@@ -27,6 +27,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 namespace bvcf_host {
@@ -225,10 +226,18 @@ struct Run {
   std::unique_ptr<WorkPool> pool;  // TSV assembly workers (n_threads of them, this thread included)
   uint32_t n_slots = 2;            // result slots of the ctx
   bvcf_params params;              // what every ctx of the run is created with (prepare_run), bar the device
+  // --keepSamples / --excludeSamples (select_samples): the header's field count as the file has it -- what the ctxs'
+  // field-count gate compares with --, and bvcf_params.sample_keep of every ctx (empty: no selection).  pre.header is
+  // then the header with the unselected names cut out, which is what every consumer of the names is to see
+  uint32_t n_header_full = 0;
+  std::vector<uint32_t> keep_mask;
 };
 
 uint32_t choose_path(const Run &R, const uint8_t *data, size_t n);
 int write_sample_list(const Run &R);
+// --keepSamples / --excludeSamples: reads the list, matches it against the normalised header, fills R.keep_mask and cuts
+// the unselected names out of R.pre.header (see Run).  BVCF_OK, or BVCF_E_ARG / BVCF_E_FATAL with *msg
+int select_samples(Run &R, std::string *msg);
 // What every ctx of the run shares: the sample list file, the ctx parameters (R.params), the name arena, the ratio
 // strings, the formatter's worker pool, the dosage file.  Once per run, after the header is known.
 int prepare_run(Run &R, std::string *msg, const uint8_t *data = nullptr, size_t n_data = 0, bool make_pool = true);

@@ -31,6 +31,9 @@ struct Cli {
   std::string sample_stats;
   // extension: --minGQ N / --minDP N, genotypes whose GQ / DP is a number below N count as missing (masked on the device)
   uint32_t min_gq = 0, min_dp = 0;
+  // extension: --keepSamples PATH / --excludeSamples PATH, the run works on the named samples only / on all but them
+  // (the unselected sample columns are skipped on the device, inside the genotype scan)
+  std::string keep_samples, exclude_samples;
 };
 
 // a decimal integer in 0 .. BVCF_MAX_THRESHOLD, digits only
@@ -111,7 +114,7 @@ int parse(int argc, char **argv, Cli &c) {
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
-        name == "minGQ" || name == "minDP") {
+        name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -134,11 +137,21 @@ int parse(int argc, char **argv, Cli &c) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
           return 2;
         }
+      } else if (name == "keepSamples" || name == "excludeSamples") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of a list of sample names\n", name.c_str());
+          return 2;
+        }
+        (name == "keepSamples" ? c.keep_samples : c.exclude_samples) = val;
       } else
         c.devices = val;
       continue;
     }
     fprintf(stderr, "flag provided but not defined: -%s\n", name.c_str());
+    return 2;
+  }
+  if (!c.keep_samples.empty() && !c.exclude_samples.empty()) {
+    fprintf(stderr, "-keepSamples and -excludeSamples cannot both be given\n");
     return 2;
   }
   return 0;
@@ -229,6 +242,8 @@ int main(int argc, char **argv) {
   cfg.sample_stats_path = c.sample_stats.c_str();
   cfg.min_gq = c.min_gq;
   cfg.min_dp = c.min_dp;
+  cfg.keep_samples_path = c.keep_samples.c_str();
+  cfg.exclude_samples_path = c.exclude_samples.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -30,6 +30,10 @@ extern "C" {
 #endif
 
 #define BVCF_ABI_VERSION 9
+/* The layout of ABI 9 with bvcf_params.sample_keep behind it.  bvcf_create accepts both versions: a caller that passes
+ * BVCF_ABI_VERSION hands over the ABI-9 fields (up to min_dp; nothing behind them is read, so a program built against the
+ * ABI-9 header keeps working), one that passes BVCF_ABI_VERSION_SUBSET hands over sample_keep as well. */
+#define BVCF_ABI_VERSION_SUBSET 10
 
 typedef enum {
   BVCF_OK = 0,
@@ -97,7 +101,7 @@ typedef struct bvcf_ctx bvcf_ctx;
 
 /* ctx configuration: what processLines closes over (main.go:494-509) */
 typedef struct {
-  uint32_t abi_version;       /* BVCF_ABI_VERSION */
+  uint32_t abi_version;       /* BVCF_ABI_VERSION, or BVCF_ABI_VERSION_SUBSET when sample_keep is to be read */
   int32_t device;             /* HIP device ordinal */
   uint32_t n_header_fields;   /* len(header) incl. the 9 fixed columns (main.go:449,505) */
   uint32_t eol_chars;         /* numChars: 1 for "\n", 2 for "\r\n" (main.go:250,535) */
@@ -155,6 +159,26 @@ typedef struct {
    * runs the census chain (bvcf_path() == 1) with the masked scan, whatever `path` asks for; files without sample
    * columns accept the thresholds and nothing changes for them. */
   uint32_t min_gq, min_dp;
+  /* ABI 10 (read only when abi_version is BVCF_ABI_VERSION_SUBSET; with BVCF_ABI_VERSION the field is ignored),
+   * --keepSamples / --excludeSamples: the ctx works on a subset of the sample columns.  Bit s % 32 of word s / 32
+   * set = keep sample s (header field 9 + s); (n_samples + 31) / 32 words for the n_samples = n_header_fields - 9 sample
+   * columns of the file, bits of samples at or beyond n_samples are ignored.  bvcf_create copies the array.  NULL (the
+   * default) = all samples, and nothing changes.  A mask that keeps no sample of a file with sample columns:
+   * bvcf_create returns BVCF_E_ARG; a file without sample columns ignores the mask.
+   * The one rule: a ctx with a mask produces what a ctx without one produces on the same text with the unselected sample
+   * columns cut out of every data line that has n_header_fields fields; the kept columns stay in header order.  So
+   *   - bvcf_line.n_fields and the BVCF_LINE_FIELDS verdict are those of the full line (n_fields against
+   *     n_header_fields); FILTER and allele verdicts and the log read the fixed columns only and do not change;
+   *   - ac, an, n_het, n_hom, n_miss are over the n_keep kept samples; a row that no kept sample carries has ac == 0 and
+   *     is dropped like any row no sample carries (main.go:558-560);
+   *   - an empty trailing field counts as one non-matching allele token only if the last column is kept;
+   *   - bvcf_result.n_samples is n_keep, and cmap_stride, the class maps, dosage_stride, the dosage rows, the device name
+   *     lists (bvcf_set_sample_names takes the n_keep kept names, in header order) and the bvcf_sample_stats table
+   *     (6 * n_keep) are all indexed by a sample's rank among the kept samples;
+   *   - min_gq / min_dp compose (masking and cutting commute).
+   * A ctx with a mask and sample columns runs the census chain (bvcf_path() == 1) with the subset scan, whatever `path`
+   * asks for. */
+  const uint32_t *sample_keep;
 } bvcf_params;
 
 /* one input line; 64 bytes */
@@ -423,6 +447,23 @@ typedef struct {
   /* ABI 9, --minGQ / --minDP: bvcf_params.min_gq / min_dp of every ctx of the run (0 = off; bvcf_run_fd / bvcf_run_buffer
    * fail with BVCF_E_ARG above BVCF_MAX_THRESHOLD).  The output does not depend on devices, batch size or input kind */
   uint32_t min_gq, min_dp;
+  /* ABI 10 (appended; bvcf_config carries no version: callers rebuild against this header, as after every append),
+   * --keepSamples PATH / --excludeSamples PATH: bvcf_run_fd / bvcf_run_buffer work on a subset of the sample
+   * columns (bvcf_params.sample_keep of every ctx of the run).  keep_samples_path keeps only the named samples,
+   * exclude_samples_path all but the named ones; NULL or "" = not given; both given: BVCF_E_ARG.  The list file: one name
+   * per line, a trailing '\r' is dropped, empty lines are ignored, duplicates are harmless.  A name selects every sample
+   * column whose name as sample_list_path writes it (after header normalisation) equals it byte for byte.
+   * BVCF_E_FATAL with one message when the list cannot be read, when a listed name matches no column (the message names
+   * the first such name; a file without sample columns and a non-empty list fails here), or when the selection leaves no
+   * sample (an empty keep list, or an exclude list naming everyone).  A file without sample columns and an empty list
+   * runs and comes out unchanged.
+   * The run produces, byte for byte, what a run without the flag produces on the same file with the unselected sample
+   * columns cut out of the header line and of every data line that has the header's field count: the TSV, the log, the
+   * sample list, the dosage file (columns, rows, row order), the sample_stats_path table (one line per kept sample) and
+   * the BGZF output.  Rows that no kept sample carries have ac == 0 and disappear.  The output does not depend on devices,
+   * batch size or input kind */
+  const char *keep_samples_path;
+  const char *exclude_samples_path;
 } bvcf_config;
 
 void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
