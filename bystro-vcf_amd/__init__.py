@@ -40,9 +40,13 @@ CLS_NONE, CLS_HET, CLS_HOM, CLS_MISSING = 0, 1, 2, 3
 # the header line of the --sampleStats table (bvcf_config.sample_stats_path)
 SAMPLE_STATS_COLUMNS = ["sample", "het", "hom", "missing", "transitions", "transversions", "heterozygosity", "homozygosity",
                         "missingness", "trTv"]
+# the header line of the --relatedness table (bvcf_config_more.pair_stats_path): one line per unordered pair of samples
+PAIR_STATS_COLUMNS = ["sample1", "sample2", "hetHet", "ibs0", "het1", "het2", "kinship"]
+PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
-BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left"]
+BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
+                 "bvcf_bench_pair_kernels"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -51,8 +55,8 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
 # every symbol include/bvcf.h declares
 EXPORTS = [
     "bvcf_create", "bvcf_destroy", "bvcf_last_error", "bvcf_version", "bvcf_reserve", "bvcf_set_sample_names", "bvcf_set_row_format", "bvcf_alloc_pinned", "bvcf_alloc_pinned_near", "bvcf_warmup",
-    "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_sample_stats", "bvcf_counters", "bvcf_sum_counters",
-    "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
+    "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_sample_stats", "bvcf_enable_pair_stats", "bvcf_pair_stats", "bvcf_counters", "bvcf_sum_counters",
+    "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_config_more_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
 ]
 
@@ -81,6 +85,14 @@ class Config(C.Structure):
         ("min_gq", C.c_uint32), ("min_dp", C.c_uint32),
         ("keep_samples_path", C.c_char_p), ("exclude_samples_path", C.c_char_p),
     ]
+
+
+CONFIG_MORE = 1  # BVCF_CONFIG_MORE in Config.reserved[0]: the struct is the head of a ConfigMore
+
+
+class ConfigMore(C.Structure):
+    """bvcf_config_more: bvcf_config and the fields that came after it stopped growing"""
+    _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p)]
 
 
 class Result(C.Structure):
@@ -226,7 +238,8 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     """cfg uses the key names of tests/golden/known_answers.json (emptyField, keepId, allow, ...).
     The returned object keeps the byte strings alive."""
     cfg = cfg or {}
-    c = Config()
+    more = ConfigMore()
+    c = more.base  # (a view of more's memory, which it keeps alive: what the callers pass on is the head of a bvcf_config_more)
     lib.bvcf_config_defaults(C.byref(c))
     keep = [cfg.get("emptyField", "!").encode(), cfg.get("fieldDelimiter", ";").encode(),
             cfg.get("allow", "PASS,.").encode(), cfg.get("exclude", "").encode()]
@@ -264,6 +277,10 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     if cfg.get("excludeSamples"):
         keep.append(str(cfg["excludeSamples"]).encode())
         c.exclude_samples_path = keep[-1]
+    if cfg.get("relatedness"):  # the pairwise table of the run (PAIR_STATS_COLUMNS)
+        keep.append(str(cfg["relatedness"]).encode())
+        more.pair_stats_path = keep[-1]
+        c.reserved[0] = CONFIG_MORE
     c._keep = keep
     return c
 
@@ -531,7 +548,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False):
         p = Params()
         p.abi_version = ABI_VERSION
         p.device = device
@@ -569,6 +586,13 @@ class Ctx:
         rc = lib.bvcf_create(C.byref(self.h), C.byref(p))
         if rc:
             raise BvcfError(rc, lib.bvcf_last_error(None).decode())
+        if pair_stats:  # bvcf_enable_pair_stats: the pair tables behind every chain (read with pair_stats())
+            lib.bvcf_enable_pair_stats.argtypes = [C.c_void_p]
+            rc = lib.bvcf_enable_pair_stats(self.h)
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
         if render_sites:
             lib.bvcf_set_row_format.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
             self._check(lib.bvcf_set_row_format(self.h, empty_field.encode(), int(keep_pos), int(keep_id), int(keep_info)))
@@ -685,6 +709,22 @@ class Ctx:
         lib.bvcf_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._check(lib.bvcf_sample_stats(self.h, out.ctypes.data if self.n_samples else None, int(reset)))
         return out.reshape(6, self.n_samples).T.copy()
+
+    def bench_pair_kernels(self):
+        """the pair kernels over the first slot's last bench chain -> ms of [k_pr_planes, k_pr_gemm, k_pr_sparse, k_pr_fold]"""
+        ms = (C.c_float * 4)()
+        lib.bvcf_bench_pair_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_pair_kernels(self.h, ms))
+        return list(ms)
+
+    def pair_stats(self, reset=False):
+        """bvcf_enable_pair_stats: the pair tables over the rows of the batches collected so far -> uint64 array
+        (3, n_samples, n_samples): HH, OC, HM (see include/bvcf.h)"""
+        ns = self.n_samples
+        out = np.zeros(3 * ns * ns, dtype=np.uint64)
+        lib.bvcf_pair_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._check(lib.bvcf_pair_stats(self.h, out.ctypes.data if ns else None, int(reset)))
+        return out.reshape(3, ns, ns)
 
     def counters(self):
         out = (C.c_uint64 * 8)()

@@ -105,6 +105,10 @@ struct Slot {
   uint64_t cap_ss_list = 0;
   uint32_t *d_ss_ctr = nullptr, *d_ss_part = nullptr, *d_ss_sp = nullptr;
   unsigned long long *d_ss_acc = nullptr;
+  // bvcf_enable_pair_stats (bvcf_pairstats.hip.h): the bit planes of the dense rows' tiles (follow the row lists), the batch's tables
+  unsigned long long *d_pr_planes = nullptr;
+  uint64_t cap_pr_tiles = 0;
+  uint32_t *d_pr_bt = nullptr;
   // capacities this slot was allocated with
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
   // in-flight batch
@@ -171,6 +175,12 @@ struct bvcf_ctx {
   // bvcf_params.want_sample_stats on a file with samples: the per-sample counts behind every chain (bvcf_samplestats.hip.h)
   bool ss_on = false;
   uint32_t ss_ns_pad = 0, ss_max_runs = 0, ss_stripes = 0;
+  // bvcf_enable_pair_stats on a file with samples: the pair counts behind every chain (bvcf_pairstats.hip.h).  The totals are
+  // the ctx's: the folds of the slots' batches follow one another through ev_pr_fold
+  bool pr_asked = false, pr_on = false, pr_folded = false;
+  uint32_t pr_split = 1;
+  unsigned long long *d_pr_tot = nullptr;
+  hipEvent_t ev_pr_fold = nullptr;
   uint64_t max_lines = 0, max_alleles = 0, max_cmap = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
   FilterTable *d_filters = nullptr;
@@ -293,6 +303,8 @@ void free_slot(Slot &s) {
   hipFree(s.d_ss_part);
   hipFree(s.d_ss_sp);
   hipFree(s.d_ss_acc);
+  hipFree(s.d_pr_planes);
+  hipFree(s.d_pr_bt);
   if (s.ev_k0) hipEventDestroy(s.ev_k0);
   if (s.ev_k1) hipEventDestroy(s.ev_k1);
   if (s.ev_in) hipEventDestroy(s.ev_in);
@@ -344,6 +356,26 @@ NameArgs make_name_args(bvcf_ctx *c, Slot &s) {
   na.cap = s.cap_names;
   na.total = s.d_name_total;
   return na;
+}
+
+// the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
+int alloc_row_lists(bvcf_ctx *c, Slot &s) {
+  if (!c->ss_on && !c->pr_on) return BVCF_OK;
+  hipFree(s.d_ss_dense);
+  hipFree(s.d_ss_sparse);
+  hipFree(s.d_pr_planes);
+  s.d_ss_dense = s.d_ss_sparse = nullptr;
+  s.d_pr_planes = nullptr;
+  s.cap_ss_list = s.cap_pr_tiles = 0;
+  HIP_TRY(c, hipMalloc(&s.d_ss_dense, c->max_alleles * sizeof(uint2)));
+  HIP_TRY(c, hipMalloc(&s.d_ss_sparse, c->max_alleles * sizeof(uint2)));
+  s.cap_ss_list = c->max_alleles;
+  if (c->pr_on) {
+    const uint64_t tiles = (c->max_alleles + kPrTile - 1) / kPrTile;
+    HIP_TRY(c, hipMalloc(&s.d_pr_planes, tiles * kPrTables * 4ull * c->cmap_stride * sizeof(unsigned long long)));
+    s.cap_pr_tiles = tiles;
+  }
+  return BVCF_OK;
 }
 
 // (re)allocate the result arrays of a slot for the ctx's current capacities
@@ -437,14 +469,9 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
     const int rc = alloc_names(c, s, std::max<uint64_t>(s.cap_names, c->p.max_batch_bytes / 2 + (1u << 20)));
     if (rc) return rc;
   }
-  if (c->ss_on) {
-    hipFree(s.d_ss_dense);
-    hipFree(s.d_ss_sparse);
-    s.d_ss_dense = s.d_ss_sparse = nullptr;
-    s.cap_ss_list = 0;
-    HIP_TRY(c, hipMalloc(&s.d_ss_dense, c->max_alleles * sizeof(uint2)));
-    HIP_TRY(c, hipMalloc(&s.d_ss_sparse, c->max_alleles * sizeof(uint2)));
-    s.cap_ss_list = c->max_alleles;
+  {
+    const int rc = alloc_row_lists(c, s);
+    if (rc) return rc;
   }
   s.cap_lines = c->max_lines;
   s.cap_alleles = c->max_alleles;
@@ -501,7 +528,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps || c->ss_on;  // (the per-sample counts are made from the maps on the device)
+  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on;  // (the per-sample and pair counts are made from the maps on the device)
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -586,17 +613,46 @@ SampleStatsArgs make_ss_args(bvcf_ctx *c, Slot &s) {
   return sa;
 }
 
+PairStatsArgs make_pr_args(bvcf_ctx *c, Slot &s) {
+  PairStatsArgs pa{};
+  pa.dense = s.d_ss_dense;
+  pa.sparse = s.d_ss_sparse;
+  pa.ctr = s.d_ss_ctr;
+  pa.planes = s.d_pr_planes;
+  pa.bt = s.d_pr_bt;
+  pa.tot = c->d_pr_tot;
+  pa.list_cap = (uint32_t)s.cap_ss_list;
+  pa.tile_cap = (uint32_t)s.cap_pr_tiles;
+  pa.ns = c->n_samples;
+  pa.ns_pad = 4u * c->cmap_stride;
+  pa.n_split = c->pr_split;
+  return pa;
+}
+
 // bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
 // (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
+// ... and, with bvcf_enable_pair_stats, the batch's pair tables from the same row lists (bvcf_pairstats.hip.h): the list
+// kernel runs once for both, and alone in front of the pair kernels when only they are on
 void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
-  if (!c->ss_on || !slot || !slot->d_ss_dense) return;
+  if ((!c->ss_on && !c->pr_on) || !slot || !slot->d_ss_dense) return;
   const SampleStatsArgs sa = make_ss_args(c, *slot);
   hipMemsetAsync(sa.ctr, 0, 4 * sizeof(uint32_t), st);
-  hipMemsetAsync(sa.sp, 0, (size_t)kSsCols * sa.ns_pad * sizeof(uint32_t), st);
+  if (c->ss_on) hipMemsetAsync(sa.sp, 0, (size_t)kSsCols * sa.ns_pad * sizeof(uint32_t), st);
   hipLaunchKernelGGL(k_ss_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, sa);
-  const uint32_t waves = c->ss_stripes * c->ss_max_runs;
-  hipLaunchKernelGGL(k_ss_dense, dim3((waves + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, a, sa);
-  hipLaunchKernelGGL(k_ss_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);  // (three dependent loads per list: many in flight)
+  if (c->ss_on) {
+    const uint32_t waves = c->ss_stripes * c->ss_max_runs;
+    hipLaunchKernelGGL(k_ss_dense, dim3((waves + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, a, sa);
+    hipLaunchKernelGGL(k_ss_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);  // (three dependent loads per list: many in flight)
+  }
+  if (c->pr_on && slot->d_pr_planes && slot->d_pr_bt) {
+    const PairStatsArgs pa = make_pr_args(c, *slot);
+    const uint32_t nb = pa.ns_pad / kPrBlock;
+    // (tiles dealt among several workgroups per pair block: the tables start from zero and are added to)
+    if (pa.n_split > 1) hipMemsetAsync(pa.bt, 0, (size_t)kPrTables * pa.ns * pa.ns * sizeof(uint32_t), st);
+    hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
+    hipLaunchKernelGGL(k_pr_gemm, dim3(nb, nb, pa.n_split), dim3(kWgThreads), 0, st, pa);
+    hipLaunchKernelGGL(k_pr_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
+  }
 }
 
 void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot = nullptr) {
@@ -1275,6 +1331,8 @@ void bvcf_destroy(bvcf_ctx *c) {
   hipFree(c->d_name_off);
   hipFree(c->d_name_text);
   hipFree(c->d_rank);
+  hipFree(c->d_pr_tot);
+  if (c->ev_pr_fold) hipEventDestroy(c->ev_pr_fold);
   delete c;
 }
 
@@ -1912,7 +1970,7 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   const uint64_t need_alleles = std::max<uint64_t>(std::max<uint64_t>(n_alleles, ctr.n_errs), n_tasks);
   // (the maps are made on the device when the caller wants them or the per-sample counts are made from them; they cross
   // to the host only in the first case)
-  const bool maps = (c->p.want_class_maps || c->ss_on) && c->n_samples;
+  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on) && c->n_samples;
   const uint64_t cmap_need = !maps ? 0 : (c->fused ? (uint64_t)ctr.cmap_maps : n_tasks) * c->cmap_stride;
   const uint64_t cmap_bytes = c->p.want_class_maps ? cmap_need : 0;
   if (ctr.pad[0]) {
@@ -2001,6 +2059,16 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
     hipLaunchKernelGGL(k_ss_fold, dim3((n_threads + kWgThreads - 1) / kWgThreads), dim3(kWgThreads), 0, s.stream,
                        make_ss_args(c, s), c->n_samples);
     HIP_TRY(c, hipGetLastError());
+  }
+  if (c->pr_on && s.d_pr_bt) {
+    // ... and its pair tables the ctx's totals: one fold after the other, whichever slots' streams they run on
+    if (c->pr_folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->ev_pr_fold, 0));
+    const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
+    const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
+    hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, s.stream, make_pr_args(c, s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_pr_fold, s.stream));
+    c->pr_folded = true;
   }
   if (n_first)
     HIP_TRY(c, hipMemcpyAsync(s.h_lines, s.d_lines, (size_t)n_first * sizeof(bvcf_line), hipMemcpyDeviceToHost, s.stream));
@@ -2132,7 +2200,7 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = (c->ss_on && !c->p.want_class_maps) ? nullptr : s.h_cmap;  // (maps kept on the device only: no host copy)
+  r->cmap = ((c->ss_on || c->pr_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap;  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = was_bgzf ? s.h_text : nullptr;
@@ -2208,6 +2276,55 @@ int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
       HIP_TRY(c, hipStreamSynchronize(s.stream));
     }
   }
+  return BVCF_OK;
+}
+
+int bvcf_enable_pair_stats(bvcf_ctx *c) {
+  if (!c) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_enable_pair_stats with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (c->n_samples > BVCF_PAIR_MAX_SAMPLES) {
+    c->err = "bvcf_enable_pair_stats: " + std::to_string(c->n_samples) + " samples, the pair tables hold at most " +
+             std::to_string(BVCF_PAIR_MAX_SAMPLES);
+    return BVCF_E_ARG;
+  }
+  c->pr_asked = true;
+  if (!c->n_samples || c->pr_on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
+  HIP_TRY(c, hipMalloc(&c->d_pr_tot, n * sizeof(unsigned long long)));
+  HIP_TRY(c, hipMemset(c->d_pr_tot, 0, n * sizeof(unsigned long long)));
+  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pr_fold, hipEventDisableTiming));
+  // a cohort of few samples has few pair blocks: the tiles of a block are then dealt to several workgroups
+  const uint64_t nb = 4ull * c->cmap_stride / kPrBlock;
+  c->pr_split = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, 2ull * (uint64_t)c->n_cu / (nb * nb)));
+  c->pr_on = true;
+  for (auto &s : c->slots) {
+    if (!s.d_ss_ctr) HIP_TRY(c, hipMalloc(&s.d_ss_ctr, 4 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&s.d_pr_bt, n * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(s.d_pr_bt, 0, n * sizeof(uint32_t)));
+    const int rc = alloc_row_lists(c, s);
+    if (rc) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->pr_asked) {
+    c->err = "bvcf_pair_stats: bvcf_enable_pair_stats was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (!c->pr_on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+  const size_t bytes = (size_t)kPrTables * c->n_samples * c->n_samples * sizeof(unsigned long long);
+  hipStream_t st = c->slots[0].stream;
+  if (out) HIP_TRY(c, hipMemcpyAsync(out, c->d_pr_tot, bytes, hipMemcpyDeviceToHost, st));
+  if (reset) HIP_TRY(c, hipMemsetAsync(c->d_pr_tot, 0, bytes, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
   return BVCF_OK;
 }
 
@@ -2501,12 +2618,48 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
   const uint64_t b_need = std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctr.n_lines + ctr.n_alleles, ctr.n_errs),
                                              (uint64_t)ctr.n_lines + ctr.n_tasks);
   if ((ctr.n_lines > s.cap_lines || b_need > s.cap_alleles ||
-      ((c->p.want_class_maps || c->ss_on) && c->n_samples &&
+      ((c->p.want_class_maps || c->ss_on || c->pr_on) && c->n_samples &&
        (c->fused ? (uint64_t)ctr.cmap_maps : (uint64_t)ctr.n_lines + ctr.n_tasks) * c->cmap_stride > s.cap_cmap))) {
     c->err = "bench block exceeds reserved result capacity: lines " + std::to_string(ctr.n_lines) + " records " +
              std::to_string(b_need) + " maps " + std::to_string(ctr.cmap_maps);
     return BVCF_E_CAPACITY;
   }
+  return BVCF_OK;
+}
+
+int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_pair_kernels with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  Slot &s = c->slots[0];
+  if (!c->pr_on || !s.d_pr_planes || !s.d_pr_bt) {
+    c->err = "bvcf_bench_pair_kernels: the ctx has no pair tables";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read a.cmap only)
+  const PairStatsArgs pa = make_pr_args(c, s);
+  const uint32_t nb = pa.ns_pad / kPrBlock;
+  const size_t n = (size_t)kPrTables * pa.ns * pa.ns;
+  hipEvent_t ev[5];
+  for (auto &e : ev) HIP_TRY(c, hipEventCreate(&e));
+  if (pa.n_split > 1) HIP_TRY(c, hipMemsetAsync(pa.bt, 0, n * sizeof(uint32_t), s.stream));
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, pa);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  hipLaunchKernelGGL(k_pr_gemm, dim3(nb, nb, pa.n_split), dim3(kWgThreads), 0, s.stream, pa);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  hipLaunchKernelGGL(k_pr_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, pa);
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
+  hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, s.stream, pa);
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  for (auto &e : ev) hipEventDestroy(e);
   return BVCF_OK;
 }
 

@@ -51,6 +51,9 @@
 //   (bvcf_params.want_sample_stats, at the end of the chain of a file with samples: k_ss_list / k_ss_dense / k_ss_sparse
 //    count, per sample, the rows whose class maps name it -- bvcf_samplestats.hip.h; k_ss_fold adds a collected batch's
 //    counts to the slot's totals)
+//   (bvcf_enable_pair_stats, behind them and from the same row lists: k_pr_planes / k_pr_gemm / k_pr_sparse count, per
+//    pair of samples, the rows that name both -- the bit-matrix product behind --relatedness, bvcf_pairstats.hip.h;
+//    k_pr_fold adds a collected batch's tables to the ctx's totals)
 //   (bvcf_params.want_name_lists, after k_finish: k_name_len / k_name_scan / k_name_write render the het / hom / missing
 //    sample-name lists of every output allele as text -- main.go:612-656 -- see bvcf_names.hip.h)
 //
@@ -95,5 +98,6 @@
 #include "bvcf_render.hip.h"
 #include "bvcf_names.hip.h"
 #include "bvcf_samplestats.hip.h"
+#include "bvcf_pairstats.hip.h"
 #include "bvcf_inflate.hip.h"
 #include "bvcf_deflate.hip.h"

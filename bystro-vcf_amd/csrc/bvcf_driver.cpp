@@ -402,10 +402,26 @@ void Driver::device_main(DevWorker *W) {
         }
         for (size_t k = 0; k < n; k++) W->ss_carry[k] += t[k];
       }
+      // (--relatedness: the same for the pair tables)
+      const bool pr = wants_pair_stats(c_) && R_.pre.header.size() > 9;
+      if (pr) {
+        const size_t ns = R_.pre.header.size() - 9, n = 3 * ns * ns;
+        std::vector<uint64_t> t(n, 0);
+        W->pr_carry.resize(n, 0);
+        if (bvcf_pair_stats(W->ctx, t.data(), 1) != BVCF_OK) {
+          fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          return;
+        }
+        for (size_t k = 0; k < n; k++) W->pr_carry[k] += t[k];
+      }
       for (size_t k = 1; k < in_flight.size(); k++) {
         bvcf_result tmp;
         bvcf_collect(W->ctx, &tmp);
         n_collects++;
+      }
+      if (pr && bvcf_pair_stats(W->ctx, nullptr, 1) != BVCF_OK) {
+        fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+        return;
       }
       if (ss && bvcf_sample_stats(W->ctx, nullptr, 1) != BVCF_OK) {
         fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
@@ -551,6 +567,10 @@ int Driver::run(uint64_t *n_lines_in) {
   if (!dry_) {  // --sampleStats: opened before any device work, as --sample's file is written before it
     std::string msg;
     if (open_sample_stats(c_, &ss_fd_, &msg)) {
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return BVCF_E_IO;
+    }
+    if (open_pair_stats(c_, &pr_fd_, &msg)) {  // --relatedness: likewise
       dprintf(fd_err_, "%s\n", msg.c_str());
       return BVCF_E_IO;
     }
@@ -731,6 +751,28 @@ int Driver::run(uint64_t *n_lines_in) {
       }
       if (rc_ != BVCF_OK) close(ss_fd_);  // (write_sample_stats closed it)
       ss_fd_ = -1;
+    }
+    if (pr_fd_ >= 0) {
+      // --relatedness: the workers' pair tables added one after another into one host table
+      if (rc_ == BVCF_OK) {
+        const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0, n = 3 * ns * ns;
+        std::vector<uint64_t> sum(n, 0), t;
+        for (auto &W : workers_) {
+          if (!W->ctx) continue;
+          t.assign(n, 0);
+          if (bvcf_pair_stats(W->ctx, t.data(), 0) != BVCF_OK) {
+            fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+            break;
+          }
+          for (size_t k = 0; k < n; k++) sum[k] += t[k];
+          for (size_t k = 0; k < n && k < W->pr_carry.size(); k++) sum[k] += W->pr_carry[k];
+        }
+        std::string msg;
+        if (rc_ == BVCF_OK && write_pair_stats(pr_fd_, c_, R_.pre, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+        if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
+      }
+      if (rc_ != BVCF_OK) close(pr_fd_);  // (write_pair_stats closed it)
+      pr_fd_ = -1;
     }
     if (!c_->leave_teardown_to_exit)
       for (bvcf_ctx *x : live) bvcf_destroy(x);

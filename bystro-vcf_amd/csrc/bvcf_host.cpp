@@ -19,6 +19,12 @@ void bvcf_config_defaults(bvcf_config *c) {
   c->normalize_header = 1;
 }
 
+void bvcf_config_more_defaults(bvcf_config_more *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_defaults(&c->base);
+  c->base.reserved[0] = BVCF_CONFIG_MORE;
+}
+
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
   std::string h;
   for (int i = 0; i < 15; i++) {
@@ -83,8 +89,9 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   R.cfg = c;
   R.max_batch = c->max_batch_bytes ? c->max_batch_bytes : (64ull << 20);
   uint64_t lines_in = 0;
-  int ss_fd = -1;
+  int ss_fd = -1, pr_fd = -1;
   int rc = open_sample_stats(c, &ss_fd, &msg);
+  if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -150,6 +157,22 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       }
     } else {
       close(ss_fd);
+    }
+  }
+  if (pr_fd >= 0) {  // --relatedness: the run's pairwise table, after a successful run only
+    if (rc == BVCF_OK) {
+      const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+      std::vector<uint64_t> t(3 * ns * ns, 0);
+      if (R.ctx && bvcf_pair_stats(R.ctx, t.data(), 0) != BVCF_OK) {
+        l.append(std::string("bvcf_pair_stats: ") + bvcf_last_error(R.ctx) + "\n");
+        rc = BVCF_E_HIP;
+        close(pr_fd);
+      } else if (write_pair_stats(pr_fd, c, R.pre, t.data(), &msg)) {
+        l.append(msg + "\n");
+        rc = BVCF_E_IO;
+      }
+    } else {
+      close(pr_fd);
     }
   }
   if (R.ctx) bvcf_destroy(R.ctx);

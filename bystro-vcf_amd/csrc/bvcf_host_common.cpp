@@ -704,6 +704,11 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     return BVCF_E_FATAL;
   }
   if (const int rc = select_samples(R, msg)) return rc;
+  if (wants_pair_stats(R.cfg) && R.pre.header.size() > 9 + (size_t)BVCF_PAIR_MAX_SAMPLES) {  // (before any table is allocated)
+    *msg = "relatedness: " + std::to_string(R.pre.header.size() - 9) + " samples, the pairwise table holds at most " +
+           std::to_string(BVCF_PAIR_MAX_SAMPLES) + " (select fewer with --keepSamples / --excludeSamples)";
+    return BVCF_E_ARG;
+  }
   if (write_sample_list(R)) {  // main.go:298-304
     *msg = "Couldn't write sample list file";
     return BVCF_E_FATAL;
@@ -815,6 +820,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
                                or_default(R.cfg->field_delimiter, ";"));
     if (rc) {
       *msg = std::string("bvcf_set_sample_names: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
+  if (rc == BVCF_OK && wants_pair_stats(R.cfg)) {  // --relatedness: the pair tables of every ctx of the run
+    rc = bvcf_enable_pair_stats(*ctx);
+    if (rc) {
+      *msg = std::string("bvcf_enable_pair_stats: ") + bvcf_last_error(*ctx);
       bvcf_destroy(*ctx);
       *ctx = nullptr;
     }
@@ -963,6 +976,64 @@ int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const 
   format_sample_stats(c, pre, t, o);
   if (write_all(fd, o.data(), o.size()) || close(fd)) {
     *msg = std::string("sample stats: write failed: ") + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_pair_stats(const bvcf_config *c, int *fd, std::string *msg) {
+  *fd = -1;
+  if (!wants_pair_stats(c)) return BVCF_OK;
+  *fd = open(pair_stats_path(c), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (*fd < 0) {
+    *msg = std::string("open ") + pair_stats_path(c) + ": " + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+// One line per unordered pair i < j in header order.  hetHet: rows in which both are het; ibs0: rows in which one is hom
+// for the allele and the other is called and does not carry it; het1 / het2: the het rows of i / j in which the other is
+// not missing; kinship: KING-robust, between-family (Manichaikul et al. 2010),
+// 0.5 + (2 hetHet - 4 ibs0 - het1 - het2) / (4 min(het1, het2)), with the TSV's "%.3G"; --emptyField when a sample is
+// never het
+int write_pair_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg) {
+  std::string o = "sample1\tsample2\thetHet\tibs0\thet1\thet2\tkinship\n";
+  const size_t ns = pre.header.size() > 9 ? pre.header.size() - 9 : 0;
+  const uint64_t *hh = t, *oc = t + ns * ns, *hm = t + 2 * ns * ns;
+  const char *empty = or_default(c->empty_field, "!");
+  bool bad = false;
+  for (size_t i = 0; i < ns && !bad; i++) {
+    for (size_t j = i + 1; j < ns; j++) {
+      const uint64_t het_het = hh[i * ns + j];
+      const uint64_t ibs0 = (oc[i * ns + i] - oc[i * ns + j]) + (oc[j * ns + j] - oc[j * ns + i]);
+      const uint64_t het1 = hh[i * ns + i] - hm[i * ns + j], het2 = hh[j * ns + j] - hm[j * ns + i];
+      o.append(pre.header[9 + i]);
+      o.push_back('\t');
+      o.append(pre.header[9 + j]);
+      for (uint64_t v : {het_het, ibs0, het1, het2}) {
+        o.push_back('\t');
+        append_ll(o, (long long)v);
+      }
+      o.push_back('\t');
+      const uint64_t den = 4 * std::min(het1, het2);
+      if (den == 0) {
+        o.append(empty);
+      } else {
+        const int64_t num = 2 * (int64_t)het_het - 4 * (int64_t)ibs0 - (int64_t)het1 - (int64_t)het2;
+        append_g3(o, 0.5 + (double)num / (double)den);
+      }
+      o.push_back('\n');
+    }
+    if (o.size() >= (4u << 20)) {  // (3 M lines for a cohort of 2 504: written as it is made)
+      bad = write_all(fd, o.data(), o.size()) != 0;
+      o.clear();
+    }
+  }
+  if (!bad) bad = write_all(fd, o.data(), o.size()) != 0;
+  const int saved = errno;
+  if (close(fd) || bad) {
+    *msg = std::string("relatedness: write failed: ") + strerror(bad ? saved : errno);
     return BVCF_E_IO;
   }
   return BVCF_OK;

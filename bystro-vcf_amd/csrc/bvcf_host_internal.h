@@ -252,6 +252,19 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
 int open_sample_stats(const bvcf_config *c, int *fd, std::string *msg);
 void format_sample_stats(const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string &out);
 int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg);
+// --relatedness (bvcf_config_more.pair_stats_path): the same for the pairwise table -- t is the sum of the run's bvcf_pair_stats
+// tables, [3][S][S] over the header's samples; one line per unordered pair, i the outer loop
+int open_pair_stats(const bvcf_config *c, int *fd, std::string *msg);
+int write_pair_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg);
+// bvcf_config_more.pair_stats_path of a config that is the head of one; NULL otherwise
+inline const char *pair_stats_path(const bvcf_config *c) {
+  return c->reserved[0] == BVCF_CONFIG_MORE ? reinterpret_cast<const bvcf_config_more *>(c)->pair_stats_path : nullptr;
+}
+// true when the run writes the pairwise table (every ctx of the run then gets bvcf_enable_pair_stats)
+inline bool wants_pair_stats(const bvcf_config *c) {
+  const char *p = pair_stats_path(c);
+  return p && *p;
+}
 
 // a bounded FIFO between pipeline stages
 template <class T>

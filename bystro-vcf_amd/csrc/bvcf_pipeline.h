@@ -210,6 +210,7 @@ struct DevWorker {
   // --sampleStats: the counts of batches collected before a reservation grew (the ctx's totals are reset then, because the
   // batches in flight are collected, dropped and submitted again)
   std::vector<uint64_t> ss_carry;
+  std::vector<uint64_t> pr_carry;  // --relatedness: the same for the pair tables
 };
 
 enum Mode { kStream = BVCF_MODE_STREAM, kRangeText = BVCF_MODE_TEXT_RANGES, kRangeBgzf = BVCF_MODE_BGZF_RANGES };
@@ -221,6 +222,7 @@ class Driver {
          int dry_device_inflate = 1);
   ~Driver() {
     if (ss_fd_ >= 0) close(ss_fd_);  // (a run that ended before its table was written)
+    if (pr_fd_ >= 0) close(pr_fd_);
   }
   int run(uint64_t *n_lines_in);
   // bvcf_plan_fd: the blocks the workers received, in (range, piece) order
@@ -274,6 +276,7 @@ class Driver {
   int rc_ = BVCF_OK;
   std::string log_;
   int ss_fd_ = -1;  // --sampleStats
+  int pr_fd_ = -1;  // --relatedness
   std::atomic<bool> failed_{false};
   // what the workers wait for: the header is known, the ctx parameters are set, the ranges are laid out
   struct {

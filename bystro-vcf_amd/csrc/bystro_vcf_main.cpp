@@ -34,6 +34,9 @@ struct Cli {
   // extension: --keepSamples PATH / --excludeSamples PATH, the run works on the named samples only / on all but them
   // (the unselected sample columns are skipped on the device, inside the genotype scan)
   std::string keep_samples, exclude_samples;
+  // extension: --relatedness PATH, the pairwise table of the run's rows: hetHet, ibs0, het1, het2 and the KING-robust kinship
+  // of every pair of samples (counted on the device)
+  std::string relatedness;
 };
 
 // a decimal integer in 0 .. BVCF_MAX_THRESHOLD, digits only
@@ -114,7 +117,7 @@ int parse(int argc, char **argv, Cli &c) {
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
-        name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples") {
+        name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -132,6 +135,8 @@ int parse(int argc, char **argv, Cli &c) {
         c.out_bgzf = val == "bgzf";
       } else if (name == "sampleStats") {
         c.sample_stats = val;
+      } else if (name == "relatedness") {
+        c.relatedness = val;
       } else if (name == "minGQ" || name == "minDP") {
         if (!parse_threshold(val, name == "minGQ" ? &c.min_gq : &c.min_dp)) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
@@ -183,7 +188,8 @@ int main(int argc, char **argv) {
     dprintf(fd_err, "Cannot specify --noOut and --out\n");
     return 1;
   }
-  if (c.no_out && c.dosage.empty() && c.sample_stats.empty()) {  // main.go:164-166 (--sampleStats alone: a QC-only pass)
+  // main.go:164-166 (--sampleStats or --relatedness alone: a QC-only pass)
+  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -195,8 +201,9 @@ int main(int argc, char **argv) {
     }
   }
 
-  bvcf_config cfg;
-  bvcf_config_defaults(&cfg);
+  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path)
+  bvcf_config_more_defaults(&more);
+  bvcf_config &cfg = more.base;
   cfg.empty_field = c.empty.c_str();
   cfg.field_delimiter = c.delim.c_str();
   cfg.allow_filter = c.allow.c_str();
@@ -244,6 +251,7 @@ int main(int argc, char **argv) {
   cfg.min_dp = c.min_dp;
   cfg.keep_samples_path = c.keep_samples.c_str();
   cfg.exclude_samples_path = c.exclude_samples.c_str();
+  more.pair_stats_path = c.relatedness.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -95,6 +95,7 @@ enum {
 #define BVCF_WIDE_SAMPLES 32768u
 #define BVCF_NO_CMAP 0xFFFFFFFFu
 #define BVCF_DEVICE_PAD 64      /* bytes a device-resident block must own past nbytes */
+#define BVCF_PAIR_MAX_SAMPLES 8192u /* most samples bvcf_enable_pair_stats accepts: the tables grow with their square */
 #define BVCF_MAX_THRESHOLD 999999999u /* largest bvcf_params.min_gq / min_dp (a value of 10 digits or more is no number) */
 
 typedef struct bvcf_ctx bvcf_ctx;
@@ -392,6 +393,22 @@ int bvcf_path(const bvcf_ctx *ctx);
  * is collected with BVCF_OK; one that came back BVCF_E_CAPACITY does not.  Waits for the ctx's slots.  reset: zero the
  * totals after reading them (out may then be NULL).  BVCF_E_ARG on a ctx created without want_sample_stats. */
 int bvcf_sample_stats(bvcf_ctx *ctx, uint64_t *out /* 6 * n_samples, column-major */, int reset);
+/* Per-sample-PAIR counts over the same rows, made on the device from the class maps (which the ctx then makes even when
+ * want_class_maps is 0, without copying them to the host): the input of a relatedness estimate such as KING-robust.  Call
+ * once, before the first submit, as bvcf_set_sample_names is called.  BVCF_E_ARG for a ctx of more than
+ * BVCF_PAIR_MAX_SAMPLES samples (after bvcf_params.sample_keep; the tables take 3 * 8 bytes per ordered pair); a no-op
+ * returning BVCF_OK on a ctx without sample columns.  bvcf_params and the ABI version do not change with it. */
+int bvcf_enable_pair_stats(bvcf_ctx *ctx);
+/* The three S x S tables (S = bvcf_result.n_samples) over the rows of the batches collected so far, out[(t * S + i) * S + j].
+ * With H / O / M = 1 when a row's heterozygotes / homozygotes / missing list names a sample, and C = H + O + M:
+ *   t = 0  HH(i,j) = sum over rows of H_i * H_j   (symmetric; HH(i,i) = het count of i)
+ *   t = 1  OC(i,j) = sum of O_i * C_j             (OC(i,i) = hom count of i)
+ *   t = 2  HM(i,j) = sum of H_i * M_j             (HM(i,i) = 0)
+ * A multiallelic line gives one row per output allele, each "this ALT against the rest".  The contract of
+ * bvcf_sample_stats: a batch counts once it is collected with BVCF_OK, one that came back BVCF_E_CAPACITY does not; waits
+ * for the ctx's slots; reset: zero the totals after reading them (out may then be NULL).  BVCF_E_ARG on a ctx on which
+ * bvcf_enable_pair_stats was not called. */
+int bvcf_pair_stats(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S: [t][i][j] */, int reset);
 
 /* running totals since bvcf_create: {lines_in, lines_ok, alleles_out, alleles_ac0, errs,
  * bytes_in, cmap_bytes, kernel_ns} */
@@ -423,7 +440,7 @@ typedef struct {
   uint8_t normalize_header;     /* parse.NormalizeHeader restatement ('.' -> '_'), default 1 */
   uint8_t leave_teardown_to_exit; /* bvcf_run_fd: the process exits right after the call (the CLI): skip destroying the
                                    ctxs and unpinning the buffers, the OS reclaims them (~0.1 s of a 0.9 s run) */
-  uint8_t reserved[2];
+  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct */
   int32_t device;               /* HIP device ordinal */
   uint32_t n_format_threads;    /* 0 = the CPUs the process may use (affinity, cgroup quota), at most 32 */
   uint64_t max_batch_bytes;     /* 0 = 64 MiB (256 MiB of text for a BGZF file inflated on the device) */
@@ -467,6 +484,24 @@ typedef struct {
 } bvcf_config;
 
 void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
+
+/* bvcf_config with the fields that came after ABI 10 behind it.  bvcf_config carries no version and its size is what
+ * callers built against ABI 10 (and the layout tests) hold on to, so it no longer grows: a caller that wants one of the
+ * fields below fills a bvcf_config_more, sets base.reserved[0] = BVCF_CONFIG_MORE (bvcf_config_more_defaults does) and
+ * hands &more.base to bvcf_run_fd / bvcf_run_buffer.  With reserved[0] == 0 -- what bvcf_config_defaults leaves --
+ * nothing behind the bvcf_config is read. */
+#define BVCF_CONFIG_MORE 1
+typedef struct {
+  bvcf_config base;
+  /* --relatedness: bvcf_run_fd / bvcf_run_buffer write the pairwise table of the run's rows here -- one line per unordered
+   * pair of samples with hetHet, ibs0, het1, het2 and the KING-robust kinship, derived from the bvcf_pair_stats tables of
+   * the run's ctxs (the format is in README.md).  Opened before any device work, written at the end of a successful run;
+   * BVCF_E_ARG with one message when more than BVCF_PAIR_MAX_SAMPLES samples are left after keep_samples_path /
+   * exclude_samples_path.  With a sample selection the table is over the kept samples, with min_gq / min_dp a masked call
+   * is missing.  The bytes do not depend on devices, batch size or input kind.  NULL or "" = no table */
+  const char *pair_stats_path;
+} bvcf_config_more;
+void bvcf_config_more_defaults(bvcf_config_more *c); /* bvcf_config_defaults, the marker, pair_stats_path = NULL */
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -34,6 +34,12 @@ int bvcf_bench_stream_kernel(const bvcf_ctx *ctx);
  * the ones its fast lane did not settle; -1: no batch yet, or the ctx is not on the streaming path */
 long bvcf_bench_head_left(const bvcf_ctx *ctx);
 
+/* bvcf_enable_pair_stats: the pair kernels once more over what the last bvcf_bench_device* chain of the ctx's first slot left
+ * (its row lists and class maps), one after the other with HIP events around each: ms = {k_pr_planes, k_pr_gemm,
+ * k_pr_sparse, k_pr_fold}.  The fold adds the batch to the ctx's totals like a collect would: for a ctx that only measures.
+ * BVCF_E_ARG on a ctx without pair tables */
+int bvcf_bench_pair_kernels(bvcf_ctx *ctx, float ms[4]);
+
 #ifdef __cplusplus
 }
 #endif
