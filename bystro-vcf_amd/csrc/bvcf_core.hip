@@ -8,6 +8,7 @@
 #include "../../include/bvcf_plan.h"
 #include "bvcf_bgzf.h"
 #include "bvcf_bgzf_out.h"
+#include "bvcf_devmem.h"
 
 #include <dlfcn.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so.1 is dlopen'ed by bvcf_allreduce_counters
@@ -22,94 +23,104 @@
 #include <vector>
 
 using namespace bvcf_dev;
+using bvcf_mem::DevBuf;
+using bvcf_mem::Event;
+using bvcf_mem::PinBuf;
+using bvcf_mem::Stream;
 
 namespace {
 
 struct Slot {
-  hipStream_t stream = nullptr;
+  // (the stream and the events first: they go last, behind the buffers)
+  Stream stream;
   bool used_gen = false;  // the batch in flight went through k_stream_gen
-  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr, ev_ctr = nullptr;
-  hipEvent_t ev_in = nullptr, ev_scan = nullptr;  // scan-stream hand-over (launch_chain)
+  Event ev_k0, ev_k1, ev_ctr;
+  Event ev_in, ev_scan;  // scan-stream hand-over (launch_chain)
   // device
-  uint8_t *d_in = nullptr;
-  uint32_t *d_census = nullptr, *d_group = nullptr, *d_line_off = nullptr;
+  DevBuf<uint8_t> d_in;
+  DevBuf<uint32_t> d_census, d_group, d_line_off;
   uint32_t group_words = 0;
-  uint32_t *d_s2_groups = nullptr;  // k_census_tiles: two sets of group totals, used by the slot's batches in turn
-  uint32_t s2_parity = 0;           // ... which one the batch being launched adds to (make_args)
-  bvcf_line *d_lines = nullptr;
-  bvcf_allele *d_alleles = nullptr;
-  bvcf_site *d_sites = nullptr, *h_sites = nullptr;  // packed ctxs only
+  DevBuf<uint32_t> d_s2_groups;  // k_census_tiles: two sets of group totals, used by the slot's batches in turn
+  uint32_t s2_parity = 0;        // ... which one the batch being launched adds to (make_args)
+  DevBuf<bvcf_line> d_lines;
+  DevBuf<bvcf_allele> d_alleles;
+  DevBuf<bvcf_site> d_sites;  // packed ctxs only
+  PinBuf<bvcf_site> h_sites;
   // bvcf_params.render_sites: the stream of rendered rows, the lines left to the host, the scan's group arrays and totals
   // packed ctxs: the pinned copies of the full records are sized for what such files need (a few lines in a hundred
   // leave the fast lanes), not for every line -- pinning costs 0.25 ms per megabyte at ctx set-up; bvcf_collect grows them
   uint64_t hcap_recs = 0, hcap_errs = 0;  // h_lines: hcap_recs; h_alleles: 2 * hcap_recs (first records, then the further ones)
-  uint8_t *d_rows = nullptr, *h_rows = nullptr;
-  uint64_t cap_rows = 0;
-  bvcf_row_cut *d_row_cuts = nullptr, *h_row_cuts = nullptr;
+  DevBuf<uint8_t> d_rows;
+  PinBuf<uint8_t> h_rows;  // (as large as d_rows)
+  DevBuf<bvcf_row_cut> d_row_cuts;
+  PinBuf<bvcf_row_cut> h_row_cuts;
   uint32_t cap_row_cuts = 0, cap_render_groups = 0;
   uint64_t cap_host_cuts = 0;
-  unsigned long long *d_rgroup_bytes = nullptr, *d_rtotals = nullptr, *h_rtotals = nullptr;
-  unsigned long long *d_rgroup_ctext = nullptr;  // BGZF batches: the text of the lines left to the host, packed (k_render_rows)
-  uint8_t *d_cut_text = nullptr;
-  uint64_t cap_cut_text = 0;
+  DevBuf<unsigned long long> d_rgroup_bytes, d_rtotals;
+  PinBuf<unsigned long long> h_rtotals;
+  DevBuf<unsigned long long> d_rgroup_ctext;  // BGZF batches: the text of the lines left to the host, packed (k_render_rows)
+  DevBuf<uint8_t> d_cut_text;
   bool cut_text_on = false;  // the batch in flight was launched with it
-  uint32_t *d_rgroup_full = nullptr;
-  bvcf_err *d_errs = nullptr;
-  uint8_t *d_cmap = nullptr;
-  int8_t *d_dosage = nullptr;
-  GtTask *d_tasks = nullptr;
-  GtResult *d_results = nullptr;
-  uint32_t *d_win_tabs = nullptr;  // wide ctxs only
-  uint32_t win_tabs_cap = 0;
-  StreamEntry *d_entries = nullptr;
-  uint32_t *d_line_len = nullptr, *d_line_cmap = nullptr, *d_line_bits = nullptr, *d_finish_items = nullptr;
-  uint32_t *d_left_lines = nullptr;  // streaming path: the lines k_order leaves to k_head
-  uint16_t *d_head_bits = nullptr;
+  DevBuf<uint32_t> d_rgroup_full;
+  DevBuf<bvcf_err> d_errs;
+  DevBuf<uint8_t> d_cmap;
+  DevBuf<int8_t> d_dosage;
+  DevBuf<GtTask> d_tasks;
+  DevBuf<GtResult> d_results;
+  DevBuf<uint32_t> d_win_tabs;  // wide ctxs only
+  DevBuf<StreamEntry> d_entries;
+  DevBuf<uint32_t> d_line_len, d_line_cmap, d_line_bits, d_finish_items;
+  DevBuf<uint32_t> d_left_lines;  // streaming path: the lines k_order leaves to k_head
+  DevBuf<uint16_t> d_head_bits;
   // device-side name lists (want_name_lists)
-  bvcf_names *d_name_lists = nullptr, *h_name_lists = nullptr;
-  uint32_t *d_name_tot = nullptr;
-  uint8_t *d_names = nullptr;
-  char *h_names = nullptr;
-  unsigned long long *d_name_total = nullptr, *h_name_total = nullptr;
+  DevBuf<bvcf_names> d_name_lists;
+  PinBuf<bvcf_names> h_name_lists;
+  DevBuf<uint32_t> d_name_tot;
+  DevBuf<uint8_t> d_names;  // cap_names bytes and a pad of 64, like h_names
+  PinBuf<char> h_names;
+  DevBuf<unsigned long long> d_name_total;
+  PinBuf<unsigned long long> h_name_total;
   uint64_t cap_names = 0;
-  // bvcf_submit_bgzf: compressed bytes, block descriptors, inflate results, the batch's text on the host
-  uint8_t *d_comp = nullptr;
-  uint64_t cap_comp = 0;
-  uint32_t *d_bgzf = nullptr, *h_bgzf = nullptr;  // per block: BgzfDesc (4 words), expected crc, then status[], crc[]
+  // bvcf_submit_bgzf: compressed bytes (and a pad of 64), block descriptors, inflate results, the batch's text on the host
+  DevBuf<uint8_t> d_comp;
+  DevBuf<uint32_t> d_bgzf;  // per block: BgzfDesc (4 words), expected crc, then status[], crc[]
+  PinBuf<uint32_t> h_bgzf;
   uint64_t cap_bgzf_blocks = 0;
-  uint32_t *d_cuts = nullptr, *h_cuts = nullptr;  // {start, end, flags, first bad block}
-  uint8_t *h_text = nullptr;
-  uint64_t cap_h_text = 0;
+  DevBuf<uint32_t> d_cuts;  // {start, end, flags, first bad block}
+  PinBuf<uint32_t> h_cuts;
+  PinBuf<uint8_t> h_text;
   // ... of which only the line heads come back when there are samples (k_heads_*)
-  uint32_t *d_head_off = nullptr, *h_head_off = nullptr;
-  uint8_t *d_heads = nullptr;
-  unsigned long long *d_head_total = nullptr, *h_head_total = nullptr;
+  DevBuf<uint32_t> d_head_off;
+  PinBuf<uint32_t> h_head_off;
+  DevBuf<uint8_t> d_heads;
+  DevBuf<unsigned long long> d_head_total;
+  PinBuf<unsigned long long> h_head_total;
   uint64_t cap_head_lines = 0;
   bool heads = false;  // the batch in flight returns heads
-  hipEvent_t ev_cut = nullptr;
+  Event ev_cut;
   bool await_cuts = false;  // inflate enqueued, the kernel chain not yet (it needs the cut points)
   bool is_bgzf = false;     // the batch in flight came through bvcf_submit_bgzf
   int bgzf_rc = 0;          // ... and was refused (corrupt block, line past the look-ahead): reported by bvcf_collect
   const char *bgzf_err = nullptr;
   uint32_t text_start = 0, text_total = 0;
-  BatchCounters *d_counters = nullptr;
+  DevBuf<BatchCounters> d_counters;
   // pinned host
-  BatchCounters *h_counters = nullptr;
-  bvcf_line *h_lines = nullptr;
-  bvcf_allele *h_alleles = nullptr;
-  bvcf_err *h_errs = nullptr;
-  uint8_t *h_cmap = nullptr;
-  int8_t *h_dosage = nullptr;
+  PinBuf<BatchCounters> h_counters;
+  PinBuf<bvcf_line> h_lines;
+  PinBuf<bvcf_allele> h_alleles;
+  PinBuf<bvcf_err> h_errs;
+  PinBuf<uint8_t> h_cmap;
+  PinBuf<int8_t> h_dosage;
   // bvcf_params.want_sample_stats (bvcf_samplestats.hip.h): the row lists (follow max_alleles), the batch's counts, the totals
-  uint2 *d_ss_dense = nullptr, *d_ss_sparse = nullptr;
-  uint64_t cap_ss_list = 0;
-  uint32_t *d_ss_ctr = nullptr, *d_ss_part = nullptr, *d_ss_sp = nullptr;
-  unsigned long long *d_ss_acc = nullptr;
+  DevBuf<uint2> d_ss_dense, d_ss_sparse;
+  DevBuf<uint32_t> d_ss_ctr, d_ss_part, d_ss_sp;
+  DevBuf<unsigned long long> d_ss_acc;
   // bvcf_enable_pair_stats (bvcf_pairstats.hip.h): the bit planes of the dense rows' tiles (follow the row lists), the batch's tables
-  unsigned long long *d_pr_planes = nullptr;
+  DevBuf<unsigned long long> d_pr_planes;
   uint64_t cap_pr_tiles = 0;
-  uint32_t *d_pr_bt = nullptr;
-  // capacities this slot was allocated with
+  DevBuf<uint32_t> d_pr_bt;
+  // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
+  // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
   // in-flight batch
   bool busy = false;
@@ -126,7 +137,7 @@ struct bvcf_ctx {
   int n_cu = 0;
   int gt_grid = 0, stream_grid = 0;
   int gt_filter_grid = 0;  // k_gt_filter / k_dosage_filter: what their own registers and LDS window let a CU hold
-  hipStream_t scan_stream = nullptr;  // see launch_chain
+  Stream scan_stream;  // see launch_chain
   uint32_t stream_lds_pad = 0;  // dynamic LDS asked for with k_stream (it uses none): caps the k_stream workgroups of ALL batches per CU
   bool fused = false;
   // streaming path: which kernel walks the next batch -- k_stream (made for the 4-byte sample grid; other lines are
@@ -149,12 +160,12 @@ struct bvcf_ctx {
   bool gt_subset = false;
   uint32_t n_samples_full = 0;
   uint32_t n_rank_words = 0;
-  uint2 *d_rank = nullptr;  // SubsetArgs.rank
+  DevBuf<uint2> d_rank;  // SubsetArgs.rank
   int gt_subset_grid = 0;
   uint64_t avg_line_bytes = 0;  // of the last collected batch (bvcf_submit_bgzf picks its inflate kernel by it)
   bool names_on = false;  // want_name_lists and bvcf_set_sample_names called: the chain ends with the k_name_* kernels
-  uint32_t *d_name_off = nullptr;
-  uint8_t *d_name_text = nullptr;
+  DevBuf<uint32_t> d_name_off;
+  DevBuf<uint8_t> d_name_text;
   NameTable name_table{};
   bool sites = false; // no sample columns: k_sites after the census instead of k_scatter_eol + k_head + k_finish
   bool sites1 = false;  // ... or k_sites1 on its own, no census, the line numbers by look-back (BVCF_SITES=3)
@@ -167,7 +178,7 @@ struct bvcf_ctx {
   uint32_t tile_bytes = 0, tile_quota = 0;
   // bvcf_params.render_sites (packed ctxs): rows made on the device; the format comes with bvcf_set_row_format
   bool render = false, row_fmt_set = false;
-  uint8_t *d_row_fmt = nullptr;  // "chr" | "\tSNP\t" | the constant tail
+  DevBuf<uint8_t> d_row_fmt;  // "chr" | "\tSNP\t" | the constant tail
   uint32_t row_tail_len = 0, row_keep_pos = 0, row_keep_id = 0, row_keep_info = 0;
   uint32_t n_samples = 0;
   uint32_t cmap_stride = 0;
@@ -179,11 +190,11 @@ struct bvcf_ctx {
   // the ctx's: the folds of the slots' batches follow one another through ev_pr_fold
   bool pr_asked = false, pr_on = false, pr_folded = false;
   uint32_t pr_split = 1;
-  unsigned long long *d_pr_tot = nullptr;
-  hipEvent_t ev_pr_fold = nullptr;
+  DevBuf<unsigned long long> d_pr_tot;
+  Event ev_pr_fold;
   uint64_t max_lines = 0, max_alleles = 0, max_cmap = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
-  FilterTable *d_filters = nullptr;
+  DevBuf<FilterTable> d_filters;
   uint32_t s1_fmode = 0, s1_fkey[4] = {0, 0, 0, 0}, s1_flen[4] = {0, 0, 0, 0};  // k_sites1's view of the allow list
   std::vector<Slot> slots;
   size_t head = 0, tail = 0, in_flight = 0;  // ring of busy slots, oldest at tail
@@ -239,91 +250,15 @@ int fill_filter(const char *text, bool star_is_nil, uint32_t *nil, uint32_t *n, 
 
 void free_slot(Slot &s) {
   if (s.stream) hipStreamSynchronize(s.stream);
-  hipFree(s.d_in);
-  hipFree(s.d_census);
-  hipFree(s.d_group);
-  hipFree(s.d_s2_groups);
-  hipFree(s.d_line_off);
-  hipFree(s.d_lines);
-  hipFree(s.d_alleles);
-  hipFree(s.d_sites);
-  hipHostFree(s.h_sites);
-  hipFree(s.d_rows);
-  hipHostFree(s.h_rows);
-  hipFree(s.d_row_cuts);
-  hipHostFree(s.h_row_cuts);
-  hipFree(s.d_rgroup_bytes);
-  hipFree(s.d_rgroup_full);
-  hipFree(s.d_rgroup_ctext);
-  hipFree(s.d_cut_text);
-  hipFree(s.d_rtotals);
-  hipHostFree(s.h_rtotals);
-  hipFree(s.d_errs);
-  hipFree(s.d_cmap);
-  hipFree(s.d_dosage);
-  hipFree(s.d_tasks);
-  hipFree(s.d_results);
-  hipFree(s.d_win_tabs);
-  hipFree(s.d_entries);
-  hipFree(s.d_line_len);
-  hipFree(s.d_line_cmap);
-  hipFree(s.d_line_bits);
-  hipFree(s.d_finish_items);
-  hipFree(s.d_left_lines);
-  hipFree(s.d_head_bits);
-  hipFree(s.d_name_lists);
-  hipFree(s.d_name_tot);
-  hipFree(s.d_names);
-  hipFree(s.d_name_total);
-  hipHostFree(s.h_name_lists);
-  hipHostFree(s.h_names);
-  hipHostFree(s.h_name_total);
-  hipFree(s.d_comp);
-  hipFree(s.d_bgzf);
-  hipHostFree(s.h_bgzf);
-  hipFree(s.d_cuts);
-  hipHostFree(s.h_cuts);
-  hipHostFree(s.h_text);
-  hipFree(s.d_head_off);
-  hipHostFree(s.h_head_off);
-  hipFree(s.d_heads);
-  hipFree(s.d_head_total);
-  hipHostFree(s.h_head_total);
-  if (s.ev_cut) hipEventDestroy(s.ev_cut);
-  hipFree(s.d_counters);
-  hipHostFree(s.h_counters);
-  hipHostFree(s.h_lines);
-  hipHostFree(s.h_alleles);
-  hipHostFree(s.h_errs);
-  hipHostFree(s.h_cmap);
-  hipHostFree(s.h_dosage);
-  hipFree(s.d_ss_dense);
-  hipFree(s.d_ss_sparse);
-  hipFree(s.d_ss_ctr);
-  hipFree(s.d_ss_part);
-  hipFree(s.d_ss_sp);
-  hipFree(s.d_ss_acc);
-  hipFree(s.d_pr_planes);
-  hipFree(s.d_pr_bt);
-  if (s.ev_k0) hipEventDestroy(s.ev_k0);
-  if (s.ev_k1) hipEventDestroy(s.ev_k1);
-  if (s.ev_in) hipEventDestroy(s.ev_in);
-  if (s.ev_scan) hipEventDestroy(s.ev_scan);
-  if (s.ev_ctr) hipEventDestroy(s.ev_ctr);
-  if (s.stream) hipStreamDestroy(s.stream);
   s = Slot{};
 }
 
 // the text arena of a slot's name lists (bvcf_collect grows it when a batch needs more)
 int alloc_name_arena(bvcf_ctx *c, Slot &s, uint64_t want_bytes) {
   if (want_bytes <= s.cap_names) return BVCF_OK;
-  hipFree(s.d_names);
-  hipHostFree(s.h_names);
-  s.d_names = nullptr;
-  s.h_names = nullptr;
   s.cap_names = 0;
-  HIP_TRY(c, hipMalloc(&s.d_names, want_bytes + 64));
-  HIP_TRY(c, hipHostMalloc(&s.h_names, want_bytes + 64, hipHostMallocDefault));
+  HIP_TRY(c, s.d_names.alloc(want_bytes + 64));
+  HIP_TRY(c, s.h_names.alloc(want_bytes + 64));
   s.cap_names = want_bytes;
   return BVCF_OK;
 }
@@ -331,18 +266,12 @@ int alloc_name_arena(bvcf_ctx *c, Slot &s, uint64_t want_bytes) {
 // the name-list buffers of a slot: lists / totals follow max_alleles, the text arena keeps its size
 int alloc_names(bvcf_ctx *c, Slot &s, uint64_t want_bytes) {
   if (!c->names_on) return BVCF_OK;
-  hipFree(s.d_name_lists);
-  hipFree(s.d_name_tot);
-  hipHostFree(s.h_name_lists);
-  s.d_name_lists = nullptr;
-  s.d_name_tot = nullptr;
-  s.h_name_lists = nullptr;
-  HIP_TRY(c, hipMalloc(&s.d_name_lists, c->max_alleles * sizeof(bvcf_names)));
-  HIP_TRY(c, hipMalloc(&s.d_name_tot, (c->max_alleles + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, hipHostMalloc(&s.h_name_lists, c->max_alleles * sizeof(bvcf_names), hipHostMallocDefault));
-  if (!s.d_name_total) {
-    HIP_TRY(c, hipMalloc(&s.d_name_total, sizeof(unsigned long long)));
-    HIP_TRY(c, hipHostMalloc(&s.h_name_total, sizeof(unsigned long long), hipHostMallocDefault));
+  HIP_TRY(c, s.d_name_lists.alloc(c->max_alleles));
+  HIP_TRY(c, s.d_name_tot.alloc(c->max_alleles + 1));
+  HIP_TRY(c, s.h_name_lists.alloc(c->max_alleles));
+  if (!s.h_name_total) {
+    HIP_TRY(c, s.d_name_total.alloc(1));
+    HIP_TRY(c, s.h_name_total.alloc(1));
   }
   return alloc_name_arena(c, s, want_bytes);
 }
@@ -361,18 +290,13 @@ NameArgs make_name_args(bvcf_ctx *c, Slot &s) {
 // the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
 int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (!c->ss_on && !c->pr_on) return BVCF_OK;
-  hipFree(s.d_ss_dense);
-  hipFree(s.d_ss_sparse);
-  hipFree(s.d_pr_planes);
-  s.d_ss_dense = s.d_ss_sparse = nullptr;
-  s.d_pr_planes = nullptr;
-  s.cap_ss_list = s.cap_pr_tiles = 0;
-  HIP_TRY(c, hipMalloc(&s.d_ss_dense, c->max_alleles * sizeof(uint2)));
-  HIP_TRY(c, hipMalloc(&s.d_ss_sparse, c->max_alleles * sizeof(uint2)));
-  s.cap_ss_list = c->max_alleles;
+  s.d_pr_planes.reset();
+  s.cap_pr_tiles = 0;
+  HIP_TRY(c, s.d_ss_dense.alloc(c->max_alleles));
+  HIP_TRY(c, s.d_ss_sparse.alloc(c->max_alleles));
   if (c->pr_on) {
     const uint64_t tiles = (c->max_alleles + kPrTile - 1) / kPrTile;
-    HIP_TRY(c, hipMalloc(&s.d_pr_planes, tiles * kPrTables * 4ull * c->cmap_stride * sizeof(unsigned long long)));
+    HIP_TRY(c, s.d_pr_planes.alloc(tiles * kPrTables * 4ull * c->cmap_stride));
     s.cap_pr_tiles = tiles;
   }
   return BVCF_OK;
@@ -381,89 +305,46 @@ int alloc_row_lists(bvcf_ctx *c, Slot &s) {
 // (re)allocate the result arrays of a slot for the ctx's current capacities
 int alloc_results(bvcf_ctx *c, Slot &s) {
   if (s.cap_lines == c->max_lines && s.cap_alleles == c->max_alleles && s.cap_cmap == c->max_cmap) return BVCF_OK;
-  hipFree(s.d_line_off);
-  hipFree(s.d_lines);
-  hipFree(s.d_alleles);
-  hipFree(s.d_sites);
-  hipHostFree(s.h_sites);
-  s.d_sites = nullptr;
-  s.h_sites = nullptr;
-  hipFree(s.d_errs);
-  hipFree(s.d_cmap);
-  hipFree(s.d_dosage);
-  hipFree(s.d_tasks);
-  hipFree(s.d_results);
-  hipFree(s.d_win_tabs);
-  s.d_win_tabs = nullptr;
-  hipFree(s.d_line_len);
-  hipFree(s.d_line_cmap);
-  hipFree(s.d_line_bits);
-  hipFree(s.d_finish_items);
-  hipFree(s.d_left_lines);
-  s.d_line_bits = nullptr;
-  s.d_finish_items = nullptr;
-  s.d_left_lines = nullptr;
-  hipHostFree(s.h_lines);
-  hipHostFree(s.h_alleles);
-  hipHostFree(s.h_errs);
-  hipHostFree(s.h_cmap);
-  hipHostFree(s.h_dosage);
-  s.d_dosage = nullptr;
-  s.h_dosage = nullptr;
-  s.d_line_off = nullptr;
-  s.d_lines = nullptr;
-  s.d_alleles = nullptr;
-  s.d_errs = nullptr;
-  s.d_cmap = nullptr;
-  s.d_tasks = nullptr;
-  s.d_results = nullptr;
-  s.d_line_len = nullptr;
-  s.d_line_cmap = nullptr;
-  s.h_lines = nullptr;
-  s.h_alleles = nullptr;
-  s.h_errs = nullptr;
-  s.h_cmap = nullptr;
   s.cap_lines = s.cap_alleles = s.cap_cmap = 0;
-  HIP_TRY(c, hipMalloc(&s.d_line_off, (c->max_lines + 1) * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(&s.d_lines, c->max_lines * sizeof(bvcf_line)));
-  HIP_TRY(c, hipMalloc(&s.d_alleles, c->max_alleles * sizeof(bvcf_allele)));
+  s.hcap_recs = s.hcap_errs = 0;
+  // (packed, render, wide, fused and dosage_stride are fixed at bvcf_create: what is not allocated here never was)
+  HIP_TRY(c, s.d_line_off.alloc(c->max_lines + 1));
+  HIP_TRY(c, s.d_lines.alloc(c->max_lines));
+  HIP_TRY(c, s.d_alleles.alloc(c->max_alleles));
   if (c->packed) {
-    HIP_TRY(c, hipMalloc(&s.d_sites, (c->max_lines + 64) * sizeof(bvcf_site)));
+    HIP_TRY(c, s.d_sites.alloc(c->max_lines + 64));
     if (!c->render)  // (rendered rows: the site records never leave the device)
-      HIP_TRY(c, hipHostMalloc(&s.h_sites, (c->max_lines + 64) * sizeof(bvcf_site), hipHostMallocDefault));
+      HIP_TRY(c, s.h_sites.alloc(c->max_lines + 64));
   }
-  HIP_TRY(c, hipMalloc(&s.d_errs, c->max_alleles * sizeof(bvcf_err)));
-  HIP_TRY(c, hipMalloc(&s.d_cmap, c->max_cmap + 64));
-  HIP_TRY(c, hipMalloc(&s.d_tasks, c->max_alleles * sizeof(GtTask)));
-  HIP_TRY(c, hipMalloc(&s.d_results, c->max_alleles * sizeof(GtResult)));
-  if (c->wide) {
-    s.win_tabs_cap = (uint32_t)std::min<uint64_t>(2 * (c->p.max_batch_bytes / c->win_bytes) + c->max_lines + 64, 0x7FFFFFFFu);
-    HIP_TRY(c, hipMalloc(&s.d_win_tabs, (size_t)s.win_tabs_cap * sizeof(uint32_t)));
-  }
-  HIP_TRY(c, hipMalloc(&s.d_line_len, c->max_lines * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(&s.d_line_cmap, c->max_lines * sizeof(uint32_t)));
+  HIP_TRY(c, s.d_errs.alloc(c->max_alleles));
+  HIP_TRY(c, s.d_cmap.alloc(c->max_cmap + 64));
+  HIP_TRY(c, s.d_tasks.alloc(c->max_alleles));
+  HIP_TRY(c, s.d_results.alloc(c->max_alleles));
+  if (c->wide)
+    HIP_TRY(c, s.d_win_tabs.alloc(std::min<uint64_t>(2 * (c->p.max_batch_bytes / c->win_bytes) + c->max_lines + 64, 0x7FFFFFFFu)));
+  HIP_TRY(c, s.d_line_len.alloc(c->max_lines));
+  HIP_TRY(c, s.d_line_cmap.alloc(c->max_lines));
   if (c->fused) {
-    HIP_TRY(c, hipMalloc(&s.d_line_bits, c->max_lines * 8 * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_finish_items, (c->max_lines + c->max_alleles) * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_left_lines, c->max_lines * sizeof(uint32_t)));
+    HIP_TRY(c, s.d_line_bits.alloc(c->max_lines * 8));
+    HIP_TRY(c, s.d_finish_items.alloc(c->max_lines + c->max_alleles));
+    HIP_TRY(c, s.d_left_lines.alloc(c->max_lines));
   }
   if (c->packed) {
-    s.hcap_recs = std::max<uint64_t>(4096, c->max_lines / 16);
-    s.hcap_errs = std::max<uint64_t>(4096, c->max_lines / 16);
-    HIP_TRY(c, hipHostMalloc(&s.h_lines, s.hcap_recs * sizeof(bvcf_line), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_alleles, 2 * s.hcap_recs * sizeof(bvcf_allele), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_errs, s.hcap_errs * sizeof(bvcf_err), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_cmap, 4096, hipHostMallocDefault));  // (no samples: no class maps)
+    const uint64_t recs = std::max<uint64_t>(4096, c->max_lines / 16);
+    HIP_TRY(c, s.h_lines.alloc(recs));
+    HIP_TRY(c, s.h_alleles.alloc(2 * recs));
+    HIP_TRY(c, s.h_errs.alloc(recs));
+    HIP_TRY(c, s.h_cmap.alloc(4096));  // (no samples: no class maps)
+    s.hcap_recs = s.hcap_errs = recs;
   } else {
-    s.hcap_recs = s.hcap_errs = 0;
-    HIP_TRY(c, hipHostMalloc(&s.h_lines, c->max_lines * sizeof(bvcf_line), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_alleles, c->max_alleles * sizeof(bvcf_allele), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_errs, c->max_alleles * sizeof(bvcf_err), hipHostMallocDefault));
-    HIP_TRY(c, hipHostMalloc(&s.h_cmap, c->max_cmap + 64, hipHostMallocDefault));
+    HIP_TRY(c, s.h_lines.alloc(c->max_lines));
+    HIP_TRY(c, s.h_alleles.alloc(c->max_alleles));
+    HIP_TRY(c, s.h_errs.alloc(c->max_alleles));
+    HIP_TRY(c, s.h_cmap.alloc(c->max_cmap + 64));
   }
   if (c->dosage_stride) {
-    HIP_TRY(c, hipMalloc(&s.d_dosage, c->max_alleles * c->dosage_stride + 64));
-    HIP_TRY(c, hipHostMalloc(&s.h_dosage, c->max_alleles * c->dosage_stride + 64, hipHostMallocDefault));
+    HIP_TRY(c, s.d_dosage.alloc(c->max_alleles * c->dosage_stride + 64));
+    HIP_TRY(c, s.h_dosage.alloc(c->max_alleles * c->dosage_stride + 64));
   }
   {
     const int rc = alloc_names(c, s, std::max<uint64_t>(s.cap_names, c->p.max_batch_bytes / 2 + (1u << 20)));
@@ -480,40 +361,39 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
 }
 
 int alloc_slot(bvcf_ctx *c, Slot &s) {
-  HIP_TRY(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  HIP_TRY(c, hipEventCreate(&s.ev_k0));
-  HIP_TRY(c, hipEventCreate(&s.ev_k1));
-  HIP_TRY(c, hipEventCreateWithFlags(&s.ev_in, hipEventDisableTiming));
-  HIP_TRY(c, hipEventCreateWithFlags(&s.ev_scan, hipEventDisableTiming));
-  HIP_TRY(c, hipEventCreate(&s.ev_ctr));
-  const uint64_t in_cap = c->p.max_batch_bytes + BVCF_DEVICE_PAD;
-  HIP_TRY(c, hipMalloc(&s.d_in, in_cap));
+  HIP_TRY(c, s.stream.create(hipStreamNonBlocking));
+  HIP_TRY(c, s.ev_k0.create());
+  HIP_TRY(c, s.ev_k1.create());
+  HIP_TRY(c, s.ev_in.create(hipEventDisableTiming));
+  HIP_TRY(c, s.ev_scan.create(hipEventDisableTiming));
+  HIP_TRY(c, s.ev_ctr.create());
+  HIP_TRY(c, s.d_in.alloc(c->p.max_batch_bytes + BVCF_DEVICE_PAD));
   s.cap_census = std::max<uint64_t>((c->p.max_batch_bytes + kChunk - 1) / kChunk + 1, s1_state_words((uint32_t)c->p.max_batch_bytes));
   {  // (k_census_tiles: a count per tile and, behind them, a total per bundle; two sets of group totals, both zero to begin with)
     const uint32_t nt = s2_n_tiles((uint32_t)c->p.max_batch_bytes) + 1u;
     s.cap_census = std::max<uint64_t>(s.cap_census, (uint64_t)s2_bundle_off(nt) + s2_n_bundles(nt) + 64u);
     c->s2_groups_cap = s2_n_groups(nt) + 2u;
   }
-  HIP_TRY(c, hipMalloc(&s.d_census, s.cap_census * sizeof(uint32_t)));
+  HIP_TRY(c, s.d_census.alloc(s.cap_census));
   // (group totals of the census scan, then -- from a 16-byte boundary -- the lines per producer wave of the streaming path)
   s.group_words = ((uint32_t)(s.cap_census / kScanGroup) + 2u + 3u) & ~3u;
-  HIP_TRY(c, hipMalloc(&s.d_group, ((size_t)s.group_words + kMaxProducerWaves) * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(&s.d_s2_groups, 2ull * c->s2_groups_cap * sizeof(uint32_t)));
+  HIP_TRY(c, s.d_group.alloc((size_t)s.group_words + kMaxProducerWaves));
+  HIP_TRY(c, s.d_s2_groups.alloc(2ull * c->s2_groups_cap));
   HIP_TRY(c, hipMemset(s.d_s2_groups, 0, 2ull * c->s2_groups_cap * sizeof(uint32_t)));
   s.s2_parity = 0;
-  HIP_TRY(c, hipMalloc(&s.d_counters, sizeof(BatchCounters)));
-  HIP_TRY(c, hipHostMalloc(&s.h_counters, sizeof(BatchCounters), hipHostMallocDefault));
+  HIP_TRY(c, s.d_counters.alloc(1));
+  HIP_TRY(c, s.h_counters.alloc(1));
   if (c->fused) {
     const uint64_t max_tiles = (c->p.max_batch_bytes + c->tile_bytes - 1) / c->tile_bytes + 1;
-    HIP_TRY(c, hipMalloc(&s.d_entries, max_tiles * c->tile_quota * sizeof(StreamEntry)));
-    HIP_TRY(c, hipMalloc(&s.d_head_bits, max_tiles * c->tile_quota * 16 * sizeof(uint16_t)));
+    HIP_TRY(c, s.d_entries.alloc(max_tiles * c->tile_quota));
+    HIP_TRY(c, s.d_head_bits.alloc(max_tiles * c->tile_quota * 16));
   }
   if (c->ss_on) {
     const size_t table = (size_t)kSsCols * c->ss_ns_pad;
-    HIP_TRY(c, hipMalloc(&s.d_ss_ctr, 4 * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_ss_part, (size_t)c->ss_max_runs * table * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_ss_sp, table * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_ss_acc, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
+    HIP_TRY(c, s.d_ss_ctr.alloc(4));
+    HIP_TRY(c, s.d_ss_part.alloc((size_t)c->ss_max_runs * table));
+    HIP_TRY(c, s.d_ss_sp.alloc(table));
+    HIP_TRY(c, s.d_ss_acc.alloc(6ull * c->ss_ns_pad));
     HIP_TRY(c, hipMemset(s.d_ss_acc, 0, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
   }
   return alloc_results(c, s);
@@ -558,7 +438,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.wide = c->wide ? 1u : 0u;
   a.win_bytes = c->win_bytes;
   a.win_tabs = s.d_win_tabs;
-  a.win_tabs_cap = s.d_win_tabs ? s.win_tabs_cap : 0u;
+  a.win_tabs_cap = (uint32_t)s.d_win_tabs.size();
   a.tile_bytes = c->tile_bytes;
   a.tile_quota = c->tile_quota;
   a.n_tiles = c->fused ? (uint32_t)((nbytes + c->tile_bytes - 1) / c->tile_bytes) : 0u;
@@ -606,7 +486,7 @@ SampleStatsArgs make_ss_args(bvcf_ctx *c, Slot &s) {
   sa.part = s.d_ss_part;
   sa.sp = s.d_ss_sp;
   sa.acc = s.d_ss_acc;
-  sa.list_cap = (uint32_t)s.cap_ss_list;
+  sa.list_cap = (uint32_t)s.d_ss_sparse.size();  // (the second of the two lists: there when both are)
   sa.ns_pad = c->ss_ns_pad;
   sa.max_runs = c->ss_max_runs;
   sa.n_stripes = c->ss_stripes;
@@ -621,7 +501,7 @@ PairStatsArgs make_pr_args(bvcf_ctx *c, Slot &s) {
   pa.planes = s.d_pr_planes;
   pa.bt = s.d_pr_bt;
   pa.tot = c->d_pr_tot;
-  pa.list_cap = (uint32_t)s.cap_ss_list;
+  pa.list_cap = (uint32_t)s.d_ss_sparse.size();
   pa.tile_cap = (uint32_t)s.cap_pr_tiles;
   pa.ns = c->n_samples;
   pa.ns_pad = 4u * c->cmap_stride;
@@ -829,7 +709,7 @@ void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t e
 // tables moved on by 1 008 zero bytes, x^(8 * 16 * (63 - L)) per lane (zlib's multmodp on the reflected CRC-32 polynomial)
 static const CrcTabs *crc_tabs_on_device() {
   static std::mutex mu;
-  static const CrcTabs *on_dev[64] = {};
+  static DevBuf<CrcTabs> *const on_dev = new DevBuf<CrcTabs>[64];  // (kept for the life of the process, never destroyed)
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
@@ -867,14 +747,9 @@ static const CrcTabs *crc_tabs_on_device() {
   for (int j = 0; j < 4; j++)
     for (uint32_t i = 0; i < 256; i++) t.jump[j][i] = mul(k1008, t.std4[j][i]);
   for (uint32_t L = 0; L < 64; L++) t.lane_k[L] = xpow(8u * 16u * (63u - L));
-  CrcTabs *d = nullptr;
-  if (hipMalloc(&d, sizeof t) != hipSuccess) return nullptr;
-  if (hipMemcpy(d, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
-    hipFree(d);
-    return nullptr;
-  }
-  on_dev[dev] = d;
-  return d;
+  if (on_dev[dev].alloc(1) != hipSuccess) return nullptr;
+  if (hipMemcpy(on_dev[dev], &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) on_dev[dev].reset();
+  return on_dev[dev];
 }
 
 // inflate + CRC of BGZF blocks whose compressed bytes are at d_comp (device): text to d_text.  desc/crc/status are
@@ -936,48 +811,31 @@ int ensure_render_buffers(bvcf_ctx *c, Slot &s, uint64_t need_rows = 0, uint64_t
   const uint32_t want_groups = (uint32_t)((c->max_lines + kRenderGroup - 1) / kRenderGroup + 2);
   // (the stream on its own: when a batch's rows outgrew it, the prefixes k_render_scan left in the group arrays are what
   // the second k_render_rows works from)
-  if (!s.d_rows || s.cap_rows < want_rows) {
+  if (s.h_rows.size() < want_rows) {  // (the pinned copy comes second: there when both are)
     HIP_TRY(c, hipStreamSynchronize(s.stream));
-    hipFree(s.d_rows);
-    hipHostFree(s.h_rows);
-    s.d_rows = s.h_rows = nullptr;
-    s.cap_rows = 0;
-    HIP_TRY(c, hipMalloc(&s.d_rows, want_rows));
-    HIP_TRY(c, hipHostMalloc(&s.h_rows, want_rows, hipHostMallocDefault));
-    s.cap_rows = want_rows;
+    HIP_TRY(c, s.d_rows.alloc(want_rows));
+    HIP_TRY(c, s.h_rows.alloc(want_rows));
   }
   if (!s.h_row_cuts || s.cap_host_cuts < want_host_cuts) {
-    hipHostFree(s.h_row_cuts);
-    s.h_row_cuts = nullptr;
     s.cap_host_cuts = 0;
-    HIP_TRY(c, hipHostMalloc(&s.h_row_cuts, (size_t)want_host_cuts * sizeof(bvcf_row_cut), hipHostMallocDefault));
+    HIP_TRY(c, s.h_row_cuts.alloc(want_host_cuts));
     s.cap_host_cuts = want_host_cuts;
   }
   if (!s.d_row_cuts || s.cap_row_cuts < want_cuts || s.cap_render_groups < want_groups) {
     HIP_TRY(c, hipStreamSynchronize(s.stream));
-    hipFree(s.d_row_cuts);
-    hipFree(s.d_rgroup_bytes);
-    hipFree(s.d_rgroup_full);
-    hipFree(s.d_rgroup_ctext);
-    s.d_row_cuts = nullptr;
-    s.d_rgroup_bytes = nullptr;
-    s.d_rgroup_full = nullptr;
-    s.d_rgroup_ctext = nullptr;
     s.cap_row_cuts = s.cap_render_groups = 0;
-    HIP_TRY(c, hipMalloc(&s.d_row_cuts, (size_t)want_cuts * sizeof(bvcf_row_cut)));
-    HIP_TRY(c, hipMalloc(&s.d_rgroup_bytes, (size_t)want_groups * sizeof(unsigned long long)));
-    HIP_TRY(c, hipMalloc(&s.d_rgroup_full, (size_t)want_groups * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_rgroup_ctext, (size_t)want_groups * sizeof(unsigned long long)));
+    HIP_TRY(c, s.d_row_cuts.alloc(want_cuts));
+    HIP_TRY(c, s.d_rgroup_bytes.alloc(want_groups));
+    HIP_TRY(c, s.d_rgroup_full.alloc(want_groups));
+    HIP_TRY(c, s.d_rgroup_ctext.alloc(want_groups));
     s.cap_row_cuts = want_cuts;
     s.cap_render_groups = want_groups;
   }
-  if (s.is_bgzf && !s.d_cut_text) {  // (a few lines in a hundred: an eighth of the batch and 1 MiB; more falls back to the whole text)
-    s.cap_cut_text = c->p.max_batch_bytes / 8 + (1u << 20);
-    HIP_TRY(c, hipMalloc(&s.d_cut_text, s.cap_cut_text));
-  }
-  if (!s.d_rtotals) {
-    HIP_TRY(c, hipMalloc(&s.d_rtotals, 4 * sizeof(unsigned long long)));
-    HIP_TRY(c, hipHostMalloc(&s.h_rtotals, 4 * sizeof(unsigned long long), hipHostMallocDefault));
+  if (s.is_bgzf && !s.d_cut_text)  // (a few lines in a hundred: an eighth of the batch and 1 MiB; more falls back to the whole text)
+    HIP_TRY(c, s.d_cut_text.alloc(c->p.max_batch_bytes / 8 + (1u << 20)));
+  if (!s.h_rtotals) {
+    HIP_TRY(c, s.d_rtotals.alloc(4));
+    HIP_TRY(c, s.h_rtotals.alloc(4));
   }
   return BVCF_OK;
 }
@@ -988,7 +846,7 @@ RenderArgs make_render_args(bvcf_ctx *c, Slot &s, const KernelArgs &a) {
   ra.sites = a.sites;
   ra.text = a.buf;
   ra.rows = s.d_rows;
-  ra.rows_cap = s.cap_rows;
+  ra.rows_cap = s.d_rows.size();
   ra.cuts = s.d_row_cuts;
   ra.cuts_cap = s.cap_row_cuts;
   ra.n_groups_cap = s.cap_render_groups - 2u;
@@ -1008,7 +866,7 @@ RenderArgs make_render_args(bvcf_ctx *c, Slot &s, const KernelArgs &a) {
     return e && *e == '0';
   }();
   ra.cut_text = (s.is_bgzf && s.d_cut_text && !cut_text_off) ? s.d_cut_text : nullptr;
-  ra.cut_text_cap = s.cap_cut_text;
+  ra.cut_text_cap = s.d_cut_text.size();
   ra.group_ctext = s.d_rgroup_ctext;
   return ra;
 }
@@ -1148,30 +1006,19 @@ struct DeflateRun {
   int device = 0, n_cu = 0, grid = 0;
   size_t max_text = 0;
   uint32_t max_pieces = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  Stream st;  // (first: destroyed last, behind the events and the buffers)
+  Event e0, e1;
   const CrcTabs *crc_tabs = nullptr;
-  uint8_t *d_text = nullptr, *d_slots = nullptr, *d_out = nullptr;
-  uint32_t *d_scratch = nullptr, *d_info = nullptr, *d_crc = nullptr;
-  uint64_t *d_offs = nullptr, *h_total = nullptr;
-  BgzfDesc *d_desc = nullptr;
+  DevBuf<uint8_t> d_text, d_slots, d_out;
+  DevBuf<uint32_t> d_scratch, d_info, d_crc;
+  DevBuf<uint64_t> d_offs;
+  PinBuf<uint64_t> h_total;
+  DevBuf<BgzfDesc> d_desc;
 };
 
 void deflate_close(DeflateRun *r) {
   if (!r) return;
   if (r->st) hipStreamSynchronize(r->st);
-  hipFree(r->d_text);
-  hipFree(r->d_slots);
-  hipFree(r->d_out);
-  hipFree(r->d_scratch);
-  hipFree(r->d_info);
-  hipFree(r->d_crc);
-  hipFree(r->d_offs);
-  hipFree(r->d_desc);
-  if (r->h_total) hipHostFree(r->h_total);
-  if (r->e0) hipEventDestroy(r->e0);
-  if (r->e1) hipEventDestroy(r->e1);
-  if (r->st) hipStreamDestroy(r->st);
   delete r;
 }
 
@@ -1199,17 +1046,17 @@ DeflateRun *deflate_open(int device, size_t max_text, std::string *err) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_deflate, kDefThreads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
   // (a workgroup owns a scratch row of a piece's match words: the grid is what is resident, the pieces loop over it)
   r->grid = (int)std::min<uint64_t>((uint64_t)r->n_cu * (uint64_t)per_cu, r->max_pieces);
-  if ((e = hipStreamCreateWithFlags(&r->st, hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
-  if ((e = hipEventCreate(&r->e0)) != hipSuccess || (e = hipEventCreate(&r->e1)) != hipSuccess) return fail("hipEventCreate", e);
-  if ((e = hipMalloc(&r->d_text, r->max_text + 64)) != hipSuccess ||
-      (e = hipMalloc(&r->d_slots, (size_t)r->max_pieces * kDefSlot)) != hipSuccess ||
-      (e = hipMalloc(&r->d_out, bound(r->max_text))) != hipSuccess ||
-      (e = hipMalloc(&r->d_scratch, (size_t)r->grid * kDefPiece * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMalloc(&r->d_info, r->max_pieces * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMalloc(&r->d_crc, r->max_pieces * sizeof(uint32_t))) != hipSuccess ||
-      (e = hipMalloc(&r->d_offs, (r->max_pieces + 1) * sizeof(uint64_t))) != hipSuccess ||
-      (e = hipMalloc(&r->d_desc, r->max_pieces * sizeof(BgzfDesc))) != hipSuccess ||
-      (e = hipHostMalloc(&r->h_total, sizeof(uint64_t), hipHostMallocDefault)) != hipSuccess)
+  if ((e = r->st.create(hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
+  if ((e = r->e0.create()) != hipSuccess || (e = r->e1.create()) != hipSuccess) return fail("hipEventCreate", e);
+  if ((e = r->d_text.alloc(r->max_text + 64)) != hipSuccess ||
+      (e = r->d_slots.alloc((size_t)r->max_pieces * kDefSlot)) != hipSuccess ||
+      (e = r->d_out.alloc(bound(r->max_text))) != hipSuccess ||
+      (e = r->d_scratch.alloc((size_t)r->grid * kDefPiece)) != hipSuccess ||
+      (e = r->d_info.alloc(r->max_pieces)) != hipSuccess ||
+      (e = r->d_crc.alloc(r->max_pieces)) != hipSuccess ||
+      (e = r->d_offs.alloc(r->max_pieces + 1)) != hipSuccess ||
+      (e = r->d_desc.alloc(r->max_pieces)) != hipSuccess ||
+      (e = r->h_total.alloc(1)) != hipSuccess)
     return fail("device buffers of the compressor", e);
   r->crc_tabs = crc_tabs_on_device();
   if (!r->crc_tabs) {
@@ -1325,15 +1172,7 @@ void bvcf_destroy(bvcf_ctx *c) {
   if (!c) return;
   hipSetDevice(c->device);
   for (auto &s : c->slots) free_slot(s);
-  if (c->scan_stream) hipStreamDestroy(c->scan_stream);
-  hipFree(c->d_filters);
-  hipFree(c->d_row_fmt);
-  hipFree(c->d_name_off);
-  hipFree(c->d_name_text);
-  hipFree(c->d_rank);
-  hipFree(c->d_pr_tot);
-  if (c->ev_pr_fold) hipEventDestroy(c->ev_pr_fold);
-  delete c;
+  delete c;  // (the ctx's own buffers, ev_pr_fold and scan_stream)
 }
 
 int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
@@ -1475,7 +1314,7 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   // (round 5, measured and not adopted: every batch's one-pass kernel on one stream of the ctx; LDS asked for with k_stream
   // to cap its workgroups per CU over all batches -- profiles/r05_c4_in_flight_what_the_ten_percent_are.txt)
   if (c->p.n_slots > 1 && getenv("BVCF_SCAN_STREAM") && atoi(getenv("BVCF_SCAN_STREAM")) == 1 &&
-      hipStreamCreateWithFlags(&c->scan_stream, hipStreamNonBlocking) != hipSuccess) {
+      c->scan_stream.create(hipStreamNonBlocking) != hipSuccess) {
     c->err = "hipStreamCreate failed";
     return fail(BVCF_E_HIP);
   }
@@ -1573,14 +1412,14 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
         for (int i = 0; i < 4; i++) c->s1_flen[i] = 0;
     }
   }
-  if (hipMalloc(&c->d_filters, sizeof ft) != hipSuccess ||
+  if (c->d_filters.alloc(1) != hipSuccess ||
       hipMemcpy(c->d_filters, &ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess) {
     c->err = "filter table upload failed";
     return fail(BVCF_E_HIP);
   }
   if (c->gt_subset) {
     c->n_rank_words = (uint32_t)rank.size();
-    if (hipMalloc(&c->d_rank, rank.size() * sizeof(uint2)) != hipSuccess ||
+    if (c->d_rank.alloc(rank.size()) != hipSuccess ||
         hipMemcpy(c->d_rank, rank.data(), rank.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) {
       c->err = "sample_keep: rank table upload failed";
       return fail(BVCF_E_HIP);
@@ -1636,12 +1475,8 @@ int bvcf_set_sample_names(bvcf_ctx *c, const char *const *names, const uint32_t 
   }
   off[n] = (uint32_t)text.size();
   HIP_TRY(c, hipSetDevice(c->device));
-  hipFree(c->d_name_off);
-  hipFree(c->d_name_text);
-  c->d_name_off = nullptr;
-  c->d_name_text = nullptr;
-  HIP_TRY(c, hipMalloc(&c->d_name_off, off.size() * sizeof(uint32_t)));
-  HIP_TRY(c, hipMalloc(&c->d_name_text, text.size() + 16));
+  HIP_TRY(c, c->d_name_off.alloc(off.size()));
+  HIP_TRY(c, c->d_name_text.alloc(text.size() + 16));
   HIP_TRY(c, hipMemcpy(c->d_name_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   HIP_TRY(c, hipMemcpy(c->d_name_text, text.data(), text.size(), hipMemcpyHostToDevice));
   c->name_table.off = c->d_name_off;
@@ -1679,7 +1514,7 @@ int bvcf_set_row_format(bvcf_ctx *c, const char *empty_field, int keep_pos, int 
   tail += "0\t0\t0";
   fmt += tail;
   HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->d_row_fmt) HIP_TRY(c, hipMalloc(&c->d_row_fmt, 128));
+  if (!c->d_row_fmt) HIP_TRY(c, c->d_row_fmt.alloc(128));
   HIP_TRY(c, hipMemcpy(c->d_row_fmt, fmt.data(), fmt.size(), hipMemcpyHostToDevice));
   c->row_tail_len = (uint32_t)tail.size();
   c->row_keep_pos = keep_pos != 0;
@@ -1805,7 +1640,7 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
   if (rc) return rc;
   // ---- buffers of the compressed path, on first use / growth
   const size_t nb = blocks.size();
-  if (!s.ev_cut) HIP_TRY(c, hipEventCreateWithFlags(&s.ev_cut, hipEventDisableTiming));
+  if (!s.ev_cut) HIP_TRY(c, s.ev_cut.create(hipEventDisableTiming));
   if (!s.h_text) {
     // the host copies of the text, for every slot at once and side by side (pinning 64 MiB takes 13-25 ms).  With
     // samples only the line heads come back, a few percent of the text: a sixteenth of a batch to start with (bvcf_collect
@@ -1819,8 +1654,7 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
       if (!q.h_text)
         th.emplace_back([c, &q, want]() {
           hipSetDevice(c->device);
-          if (hipHostMalloc(&q.h_text, want, hipHostMallocDefault) != hipSuccess) q.h_text = nullptr;
-          q.cap_h_text = q.h_text ? want : 0;
+          (void)q.h_text.alloc(want);  // (checked below, for the slot of this batch)
         });
     for (auto &t : th) t.join();
     if (!s.h_text) {
@@ -1829,45 +1663,31 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
     }
   }
   if (c->n_samples && s.cap_head_lines < c->max_lines) {
-    hipFree(s.d_head_off);
-    hipHostFree(s.h_head_off);
-    s.d_head_off = nullptr;
-    s.h_head_off = nullptr;
     s.cap_head_lines = 0;
-    HIP_TRY(c, hipMalloc(&s.d_head_off, (c->max_lines + 1) * sizeof(uint32_t)));
-    HIP_TRY(c, hipHostMalloc(&s.h_head_off, (c->max_lines + 1) * sizeof(uint32_t), hipHostMallocDefault));
-    if (!s.d_heads) HIP_TRY(c, hipMalloc(&s.d_heads, c->p.max_batch_bytes + 64));
-    if (!s.d_head_total) {
-      HIP_TRY(c, hipMalloc(&s.d_head_total, sizeof(unsigned long long)));
-      HIP_TRY(c, hipHostMalloc(&s.h_head_total, sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(c, s.d_head_off.alloc(c->max_lines + 1));
+    HIP_TRY(c, s.h_head_off.alloc(c->max_lines + 1));
+    if (!s.d_heads) HIP_TRY(c, s.d_heads.alloc(c->p.max_batch_bytes + 64));
+    if (!s.h_head_total) {
+      HIP_TRY(c, s.d_head_total.alloc(1));
+      HIP_TRY(c, s.h_head_total.alloc(1));
     }
     s.cap_head_lines = c->max_lines;
   }
-  if (!s.d_cuts) {
-    HIP_TRY(c, hipMalloc(&s.d_cuts, 4 * sizeof(uint32_t)));
-    HIP_TRY(c, hipHostMalloc(&s.h_cuts, 4 * sizeof(uint32_t), hipHostMallocDefault));
+  if (!s.h_cuts) {
+    HIP_TRY(c, s.d_cuts.alloc(4));
+    HIP_TRY(c, s.h_cuts.alloc(4));
   }
-  if (n_comp > s.cap_comp) {
-    hipFree(s.d_comp);
-    s.d_comp = nullptr;
-    s.cap_comp = 0;
-    const uint64_t want = std::max<uint64_t>(n_comp + n_comp / 4, 1u << 20);
-    HIP_TRY(c, hipMalloc(&s.d_comp, want + 64));
-    s.cap_comp = want;
-  }
+  if (n_comp + 64 > s.d_comp.size())  // (the 64: the pad behind the bytes)
+    HIP_TRY(c, s.d_comp.alloc(std::max<uint64_t>(n_comp + n_comp / 4, 1u << 20) + 64));
   if (nb > s.cap_bgzf_blocks) {
-    hipFree(s.d_bgzf);
-    hipHostFree(s.h_bgzf);
-    s.d_bgzf = nullptr;
-    s.h_bgzf = nullptr;
     s.cap_bgzf_blocks = 0;
     const uint64_t want = std::max<uint64_t>(nb + nb / 4, 4096);
-    HIP_TRY(c, hipMalloc(&s.d_bgzf, want * 7 * sizeof(uint32_t)));
-    HIP_TRY(c, hipHostMalloc(&s.h_bgzf, want * 5 * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(c, s.d_bgzf.alloc(want * 7));
+    HIP_TRY(c, s.h_bgzf.alloc(want * 5));
     s.cap_bgzf_blocks = want;
   }
   // descriptors (4 words per block), then the expected CRCs; status[] and crc[] follow on the device
-  BgzfDesc *h_desc = reinterpret_cast<BgzfDesc *>(s.h_bgzf);
+  BgzfDesc *h_desc = reinterpret_cast<BgzfDesc *>(s.h_bgzf.get());
   uint32_t *h_crc = s.h_bgzf + 4 * nb;
   uint64_t out_off = 0;
   for (size_t i = 0; i < nb; i++) {
@@ -1878,7 +1698,7 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
     h_crc[i] = blocks[i].crc;
     out_off += blocks[i].isize;
   }
-  BgzfDesc *d_desc = reinterpret_cast<BgzfDesc *>(s.d_bgzf);
+  BgzfDesc *d_desc = reinterpret_cast<BgzfDesc *>(s.d_bgzf.get());
   uint32_t *d_want = s.d_bgzf + 4 * nb, *d_status = s.d_bgzf + 5 * nb, *d_crc = s.d_bgzf + 6 * nb;
   HIP_TRY(c, hipMemcpyAsync(s.d_comp, comp, n_comp, hipMemcpyHostToDevice, s.stream));
   HIP_TRY(c, hipMemcpyAsync(s.d_bgzf, s.h_bgzf, 5 * nb * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream));
@@ -2011,7 +1831,7 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
         return rc;
       }
     }
-    if (row_bytes > s.cap_rows) {
+    if (row_bytes > s.d_rows.size()) {
       // the stream was too small and k_render_rows wrote nothing: grow it and write again (the prefixes stand)
       const int rc = ensure_render_buffers(c, s, row_bytes + row_bytes / 4 + (1u << 20));
       if (rc) {
@@ -2034,18 +1854,15 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
     if (need_recs > s.hcap_recs || ctr.n_errs > s.hcap_errs) {
       const uint64_t want_recs = std::max<uint64_t>(s.hcap_recs, need_recs + need_recs / 2 + 64);
       const uint64_t want_errs = std::max<uint64_t>(s.hcap_errs, (uint64_t)ctr.n_errs + ctr.n_errs / 2 + 64);
-      hipHostFree(s.h_lines);
-      hipHostFree(s.h_alleles);
-      hipHostFree(s.h_errs);
-      s.h_lines = nullptr;
-      s.h_alleles = nullptr;
-      s.h_errs = nullptr;
+      // (released together, before the first of them is pinned anew)
+      s.h_lines.reset();
+      s.h_alleles.reset();
+      s.h_errs.reset();
       s.hcap_recs = s.hcap_errs = 0;
-      if (hipHostMalloc(&s.h_lines, want_recs * sizeof(bvcf_line), hipHostMallocDefault) != hipSuccess ||
-          hipHostMalloc(&s.h_alleles, 2 * want_recs * sizeof(bvcf_allele), hipHostMallocDefault) != hipSuccess ||
-          hipHostMalloc(&s.h_errs, want_errs * sizeof(bvcf_err), hipHostMallocDefault) != hipSuccess) {
+      if (s.h_lines.alloc(want_recs) != hipSuccess || s.h_alleles.alloc(2 * want_recs) != hipSuccess ||
+          s.h_errs.alloc(want_errs) != hipSuccess) {
         c->err = "hipHostMalloc failed (full records of a packed batch)";
-        s.cap_lines = 0;  // (alloc_results starts over at the slot's next use)
+        s.cap_lines = 0;  // (alloc_results starts over at the slot's next use: it allocates all three and sets hcap_*)
         release();
         return BVCF_E_NOMEM;
       }
@@ -2102,40 +1919,29 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
       release();
       return BVCF_E_HIP;
     }
-    if (text_bytes > s.cap_h_text) {  // (the caller is done with what this slot returned n_slots collects ago)
-      hipHostFree(s.h_text);
-      s.h_text = nullptr;
-      s.cap_h_text = 0;
+    if (text_bytes > s.h_text.size()) {  // (the caller is done with what this slot returned n_slots collects ago)
       const uint64_t want = std::min<uint64_t>(text_bytes + text_bytes / 2, c->p.max_batch_bytes + BVCF_DEVICE_PAD);
-      if (hipHostMalloc(&s.h_text, want, hipHostMallocDefault) != hipSuccess) {
-        s.h_text = nullptr;
+      if (s.h_text.alloc(want) != hipSuccess) {
         c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
         release();
         return BVCF_E_NOMEM;
       }
-      s.cap_h_text = want;
     }
     if (ctr.n_lines) HIP_TRY(c, hipMemcpyAsync(s.h_head_off, s.d_head_off, ctr.n_lines * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
     if (text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_heads, text_bytes, hipMemcpyDeviceToHost, s.stream));
-  } else if (was_bgzf && c->render && s.cut_text_on && s.h_rtotals[3] <= s.cap_cut_text && s.h_rtotals[3] < 0xFFFFFFFFull) {
+  } else if (was_bgzf && c->render && s.cut_text_on && s.h_rtotals[3] <= s.d_cut_text.size() && s.h_rtotals[3] < 0xFFFFFFFFull) {
     // rendered rows: the host only reads the lines left to it -- their bytes, packed (bvcf_row_cut.text_off), not the
     // batch's whole text
     text_bytes = s.h_rtotals[3];
     if (text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_cut_text, text_bytes, hipMemcpyDeviceToHost, s.stream));
   } else if (was_bgzf && s.nbytes) {
     text_bytes = s.nbytes;
-    if (text_bytes > s.cap_h_text) {  // (a rendered ctx keeps a small copy buffer: see bvcf_submit_bgzf)
-      hipHostFree(s.h_text);
-      s.h_text = nullptr;
-      s.cap_h_text = 0;
-      const uint64_t want = c->p.max_batch_bytes + BVCF_DEVICE_PAD;
-      if (hipHostMalloc(&s.h_text, want, hipHostMallocDefault) != hipSuccess) {
-        s.h_text = nullptr;
+    if (text_bytes > s.h_text.size()) {  // (a rendered ctx keeps a small copy buffer: see bvcf_submit_bgzf)
+      if (s.h_text.alloc(c->p.max_batch_bytes + BVCF_DEVICE_PAD) != hipSuccess) {
         c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
         release();
         return BVCF_E_NOMEM;
       }
-      s.cap_h_text = want;
     }
     HIP_TRY(c, hipMemcpyAsync(s.h_text, s.src, s.nbytes, hipMemcpyDeviceToHost, s.stream));
   }
@@ -2294,16 +2100,16 @@ int bvcf_enable_pair_stats(bvcf_ctx *c) {
   if (!c->n_samples || c->pr_on) return BVCF_OK;  // (no sample columns: an empty table)
   HIP_TRY(c, hipSetDevice(c->device));
   const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
-  HIP_TRY(c, hipMalloc(&c->d_pr_tot, n * sizeof(unsigned long long)));
+  HIP_TRY(c, c->d_pr_tot.alloc(n));
   HIP_TRY(c, hipMemset(c->d_pr_tot, 0, n * sizeof(unsigned long long)));
-  HIP_TRY(c, hipEventCreateWithFlags(&c->ev_pr_fold, hipEventDisableTiming));
+  HIP_TRY(c, c->ev_pr_fold.create(hipEventDisableTiming));
   // a cohort of few samples has few pair blocks: the tiles of a block are then dealt to several workgroups
   const uint64_t nb = 4ull * c->cmap_stride / kPrBlock;
   c->pr_split = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, 2ull * (uint64_t)c->n_cu / (nb * nb)));
   c->pr_on = true;
   for (auto &s : c->slots) {
-    if (!s.d_ss_ctr) HIP_TRY(c, hipMalloc(&s.d_ss_ctr, 4 * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&s.d_pr_bt, n * sizeof(uint32_t)));
+    if (!s.d_ss_ctr) HIP_TRY(c, s.d_ss_ctr.alloc(4));
+    HIP_TRY(c, s.d_pr_bt.alloc(n));
     HIP_TRY(c, hipMemset(s.d_pr_bt, 0, n * sizeof(uint32_t)));
     const int rc = alloc_row_lists(c, s);
     if (rc) return rc;
@@ -2403,15 +2209,14 @@ int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uin
   if (hipSetDevice(device) != hipSuccess) return BVCF_E_HIP;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) return BVCF_E_HIP;
-  uint8_t *d_comp = nullptr, *d_text = nullptr;
-  BgzfDesc *d_desc = nullptr;
-  uint32_t *d_status = nullptr, *d_crc = nullptr;
+  DevBuf<uint8_t> d_comp, d_text;
+  DevBuf<BgzfDesc> d_desc;
+  DevBuf<uint32_t> d_status, d_crc;
   const size_t nb = blocks.size();
   int rc = BVCF_OK;
   std::vector<uint32_t> status(nb), crc(nb);
-  if (hipMalloc(&d_comp, n_comp + 64) != hipSuccess || hipMalloc(&d_text, total + 64) != hipSuccess ||
-      hipMalloc(&d_desc, nb * sizeof(BgzfDesc)) != hipSuccess || hipMalloc(&d_status, nb * 4) != hipSuccess ||
-      hipMalloc(&d_crc, nb * 4) != hipSuccess) {
+  if (d_comp.alloc(n_comp + 64) != hipSuccess || d_text.alloc(total + 64) != hipSuccess || d_desc.alloc(nb) != hipSuccess ||
+      d_status.alloc(nb) != hipSuccess || d_crc.alloc(nb) != hipSuccess) {
     rc = BVCF_E_NOMEM;
   } else if (hipMemcpy(d_comp, comp, n_comp, hipMemcpyHostToDevice) != hipSuccess ||
              hipMemcpy(d_desc, desc.data(), nb * sizeof(BgzfDesc), hipMemcpyHostToDevice) != hipSuccess) {
@@ -2423,11 +2228,6 @@ int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uin
         (total && hipMemcpy(out, d_text, total, hipMemcpyDeviceToHost) != hipSuccess))
       rc = rc ? rc : BVCF_E_HIP;
   }
-  hipFree(d_comp);
-  hipFree(d_text);
-  hipFree(d_desc);
-  hipFree(d_status);
-  hipFree(d_crc);
   if (rc) return rc;
   for (size_t i = 0; i < nb; i++)
     if (status[i] != kInfOk || crc[i] != blocks[i].crc) return BVCF_E_FATAL;  // corrupt block (inflate or CRC mismatch)
@@ -2511,7 +2311,7 @@ int bvcf_allreduce_counters(bvcf_ctx *const *ctxs, int n, uint64_t out[8], int *
   }
   std::vector<int> devs(n);
   std::vector<ncclComm_t> comms(n, nullptr);
-  std::vector<uint64_t *> d_buf(n, nullptr);
+  std::vector<DevBuf<uint64_t>> d_buf(n);
   for (int i = 0; i < n; i++) devs[i] = ctxs[i]->device;
   int rc = BVCF_OK;
   auto nccl_fail = [&](ncclResult_t r, const char *what) {
@@ -2524,7 +2324,7 @@ int bvcf_allreduce_counters(bvcf_ctx *const *ctxs, int n, uint64_t out[8], int *
     return rc;
   }
   for (int i = 0; i < n && rc == BVCF_OK; i++) {
-    if (hipSetDevice(devs[i]) != hipSuccess || hipMalloc(&d_buf[i], 8 * sizeof(uint64_t)) != hipSuccess ||
+    if (hipSetDevice(devs[i]) != hipSuccess || d_buf[i].alloc(8) != hipSuccess ||
         hipMemcpy(d_buf[i], ctxs[i]->totals, 8 * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
       c0->err = "bvcf_allreduce_counters: counter upload failed";
       rc = BVCF_E_HIP;
@@ -2555,7 +2355,7 @@ int bvcf_allreduce_counters(bvcf_ctx *const *ctxs, int n, uint64_t out[8], int *
   }
   for (int i = 0; i < n; i++) {
     hipSetDevice(devs[i]);
-    if (d_buf[i]) hipFree(d_buf[i]);
+    d_buf[i].reset();
     if (comms[i]) p_destroy(comms[i]);
   }
   if (rc == BVCF_OK && used_rccl) *used_rccl = 1;
@@ -2585,8 +2385,8 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
     if (rc) return rc;
   }
   Slot &s = c->slots[(size_t)(iters - 1) % n_use];  // the slot whose counters are reported
-  std::vector<hipEvent_t> ev((size_t)iters * 4);
-  for (auto &e : ev) HIP_TRY(c, hipEventCreate(&e));
+  std::vector<Event> ev((size_t)iters * 4);
+  for (auto &e : ev) HIP_TRY(c, e.create());
   for (int i = 0; i < iters; i++) {
     Slot &si = c->slots[(size_t)i % n_use];
     si.s2_parity ^= 1u;
@@ -2605,7 +2405,6 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
     if (chain_ms) chain_ms[i] = t0;
     if (gt_ms) gt_ms[i] = t1;
   }
-  for (auto &e : ev) hipEventDestroy(e);
   const BatchCounters ctr = *s.h_counters;
   adapt_stream_kernel(c, c->gen_mode, ctr);  // (every launch of this call went through the same kernel)
   if (counts) {
@@ -2643,8 +2442,8 @@ int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
   const PairStatsArgs pa = make_pr_args(c, s);
   const uint32_t nb = pa.ns_pad / kPrBlock;
   const size_t n = (size_t)kPrTables * pa.ns * pa.ns;
-  hipEvent_t ev[5];
-  for (auto &e : ev) HIP_TRY(c, hipEventCreate(&e));
+  Event ev[5];
+  for (auto &e : ev) HIP_TRY(c, e.create());
   if (pa.n_split > 1) HIP_TRY(c, hipMemsetAsync(pa.bt, 0, n * sizeof(uint32_t), s.stream));
   HIP_TRY(c, hipEventRecord(ev[0], s.stream));
   hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, pa);
@@ -2659,7 +2458,6 @@ int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(s.stream));
   for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  for (auto &e : ev) hipEventDestroy(e);
   return BVCF_OK;
 }
 
