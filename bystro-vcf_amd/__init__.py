@@ -50,7 +50,7 @@ BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_str
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
-                "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line"]
+                "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -226,6 +226,69 @@ def head_fast_line(head, ls, len_flags, counts, cmap_off, tab_bits, line, n_head
                                 (C.c_uint32 * 8)(*tab_bits), line, n_header, allow.encode(), exclude.encode(),
                                 L.ctypes.data, A.ctypes.data)
     return v, (L[0] if v != HEAD_FAST_DECLINE else None), (A[0] if v == HEAD_FAST_PASS else None)
+
+
+CHAIN_STREAM, CHAIN_SITES2_TILES, CHAIN_SITES2_CHUNKS, CHAIN_CENSUS, CHAIN_SITES_EXP, CHAIN_SITES1_EXP = range(6)
+SCAN_NONE, SCAN_PLAIN, SCAN_WIDE, SCAN_FILTER, SCAN_SUBSET = range(5)
+WIDE_SAMPLES = 32768  # BVCF_WIDE_SAMPLES
+
+
+class CtxPlan(C.Structure):
+    """bvcf_ctx_plan (include/bvcf_plan.h): what bvcf_create decides before it touches the device"""
+    _fields_ = [("max_batch_bytes", C.c_uint64), ("max_lines", C.c_uint64), ("max_alleles", C.c_uint64), ("max_cmap", C.c_uint64),
+                ("n_slots", C.c_uint32), ("n_samples", C.c_uint32), ("n_samples_full", C.c_uint32), ("cmap_stride", C.c_uint32),
+                ("dosage_stride", C.c_uint32), ("tile_bytes", C.c_uint32), ("tile_quota", C.c_uint32), ("win_bytes", C.c_uint32),
+                ("chain", C.c_uint32), ("scan", C.c_uint32), ("gen_policy", C.c_int32), ("ss_ns_pad", C.c_uint32),
+                ("ss_max_runs", C.c_uint32), ("ss_stripes", C.c_uint32), ("s1_fmode", C.c_uint32), ("s1_fkey", C.c_uint32 * 4),
+                ("s1_flen", C.c_uint32 * 4), ("eol_byte", C.c_uint8), ("packed", C.c_uint8), ("render", C.c_uint8),
+                ("gen_mode", C.c_uint8), ("shape_seen", C.c_uint8), ("head_fast", C.c_uint8), ("ss_on", C.c_uint8),
+                ("reserved", C.c_uint8)]
+
+
+def make_params(n_header_fields, allow="PASS,.", exclude="", device=0, eol_chars=1, eol_byte=b"\n", max_batch_bytes=0,
+                max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True, path=0, want_dosage=False,
+                want_name_lists=False, packed_sites=False, render_sites=False, sample_stats=False, min_gq=0, min_dp=0,
+                sample_keep=None):
+    """bvcf_params as Ctx fills them (sample_keep: the indices of the kept samples); keeps its strings and mask alive"""
+    p = Params()
+    p.abi_version = ABI_VERSION
+    p.device = device
+    p.n_header_fields = n_header_fields
+    p.eol_chars = eol_chars
+    p.eol_byte = eol_byte[0]
+    p.want_class_maps = int(want_class_maps)
+    p.want_dosage = int(want_dosage)
+    p._keep = [allow.encode(), exclude.encode()]
+    p.allow_filter, p.exclude_filter = p._keep
+    p.max_batch_bytes = max_batch_bytes
+    p.max_lines = max_lines
+    p.max_alleles = max_alleles
+    p.cmap_bytes = cmap_bytes
+    p.n_slots = n_slots
+    p.path = path
+    p.packed_sites = int(packed_sites or render_sites)
+    p.render_sites = int(render_sites)
+    p.want_name_lists = int(want_name_lists)
+    p.want_sample_stats = int(sample_stats)
+    p.min_gq = min_gq  # bvcf_params.min_gq / min_dp: the masked genotype scan (0 = off)
+    p.min_dp = min_dp
+    if sample_keep is not None:
+        # bvcf_params.sample_keep: everything the ctx returns is then indexed by a sample's rank among the kept ones
+        words = (C.c_uint32 * max((max(n_header_fields - 9, 0) + 31) // 32, 1))()
+        for s in set(int(s) for s in sample_keep):
+            if 0 <= s < 32 * len(words):  # (bits at or beyond n_samples are the library's to ignore)
+                words[s >> 5] |= 1 << (s & 31)
+        p.abi_version = ABI_VERSION_SUBSET
+        p.sample_keep = words  # (bvcf_create copies it)
+    return p
+
+
+def plan_ctx(n_header_fields, **params):
+    """the plan of a ctx with these make_params arguments, made without a device -> (rc, CtxPlan)"""
+    lib.bvcf_plan_ctx.argtypes = [C.POINTER(Params), C.POINTER(CtxPlan)]  # (bound here: BVCF_LIB may name an older build)
+    p = make_params(n_header_fields, **params)
+    out = CtxPlan()
+    return lib.bvcf_plan_ctx(C.byref(p), C.byref(out)), out
 
 
 class BvcfError(RuntimeError):
@@ -549,38 +612,11 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False):
-        p = Params()
-        p.abi_version = ABI_VERSION
-        p.device = device
-        p.n_header_fields = n_header_fields
-        p.eol_chars = eol_chars
-        p.eol_byte = eol_byte[0]
-        p.want_class_maps = int(want_class_maps)
-        p.want_dosage = int(want_dosage)
-        self._keep = [allow.encode(), exclude.encode()]
-        p.allow_filter, p.exclude_filter = self._keep
-        p.max_batch_bytes = max_batch_bytes
-        p.max_lines = max_lines
-        p.max_alleles = max_alleles
-        p.cmap_bytes = cmap_bytes
-        p.n_slots = n_slots
-        p.path = path
-        p.packed_sites = int(packed_sites or render_sites)
-        p.render_sites = int(render_sites)
-        p.want_name_lists = int(sample_names is not None)
-        p.want_sample_stats = int(sample_stats)
-        p.min_gq = min_gq  # bvcf_params.min_gq / min_dp: the masked genotype scan (0 = off)
-        p.min_dp = min_dp
+        p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
+                        cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
+                        render_sites, sample_stats, min_gq, min_dp, sample_keep)
         self.n_samples = max(n_header_fields - 9, 0)
-        if sample_keep is not None:
-            # bvcf_params.sample_keep: the indices of the samples the ctx keeps; everything it returns is then indexed by a
-            # sample's rank among them (n_samples = their number)
-            words = (C.c_uint32 * max((self.n_samples + 31) // 32, 1))()
-            for s in set(int(s) for s in sample_keep):
-                if 0 <= s < 32 * len(words):  # (bits at or beyond n_samples are the library's to ignore)
-                    words[s >> 5] |= 1 << (s & 31)
-            p.abi_version = ABI_VERSION_SUBSET
-            p.sample_keep = words  # (bvcf_create copies it)
+        if sample_keep is not None:  # (n_samples = the number of kept samples)
             self.n_samples = len(set(int(s) for s in sample_keep if 0 <= int(s) < self.n_samples))
         self.h = C.c_void_p()
         rc = lib.bvcf_create(C.byref(self.h), C.byref(p))

@@ -35,7 +35,7 @@ struct Slot {
   Stream stream;
   bool used_gen = false;  // the batch in flight went through k_stream_gen
   Event ev_k0, ev_k1, ev_ctr;
-  Event ev_in, ev_scan;  // scan-stream hand-over (launch_chain)
+  Event ev_in, ev_scan;  // scan-stream hand-over (launch_stream)
   // device
   DevBuf<uint8_t> d_in;
   DevBuf<uint32_t> d_census, d_group, d_line_off;
@@ -131,71 +131,44 @@ struct Slot {
 
 }  // namespace
 
-struct bvcf_ctx {
+// (the plan first -- include/bvcf_plan.h: the chain, the scan, the result's form, n_samples, the strides, max_* ... --, made
+// once by plan_ctx; what follows is what the device and the batches add)
+struct bvcf_ctx : bvcf_ctx_plan {
   bvcf_params p{};
   int device = 0;
   int n_cu = 0;
   int gt_grid = 0, stream_grid = 0;
   int gt_filter_grid = 0;  // k_gt_filter / k_dosage_filter: what their own registers and LDS window let a CU hold
-  Stream scan_stream;  // see launch_chain
+  int gt_subset_grid = 0;  // k_gt_subset / k_dosage_subset
+  Stream scan_stream;  // see launch_stream
   uint32_t stream_lds_pad = 0;  // dynamic LDS asked for with k_stream (it uses none): caps the k_stream workgroups of ALL batches per CU
-  bool fused = false;
-  // streaming path: which kernel walks the next batch -- k_stream (made for the 4-byte sample grid; other lines are
-  // left to k_gt) or k_stream_gen (any fields, one pass).  Adaptive: a batch whose lines were mostly of the other
+  // streaming path: which kernel walks the next batch (gen_mode) -- k_stream (made for the 4-byte sample grid; other lines
+  // are left to k_gt) or k_stream_gen (any fields, one pass).  Adaptive: a batch whose lines were mostly of the other
   // kernel's shape switches (the results are the same either way); BVCF_GEN_STREAM=0 / 1 pins it.
-  bool gen_mode = false;
   uint32_t last_real = 0xFFFFFFFFu, last_finish = 0xFFFFFFFFu;  // the last collected batch's counters->n_real / n_finish (unknown: full grids)
   uint32_t last_left = 0xFFFFFFFFu;  // ... and its counters->n_left: the lines k_order left to k_head
-  bool head_fast = true;  // k_order settles plain SNP lines itself (bvcf_headfast.hip.h); BVCF_HEAD_FAST=0: every line goes to k_head
-  bool shape_seen = false;  // gen_mode has had its first hint (peek_line_shape) or a batch's counters
-  int gen_policy = -1;  // -1 adaptive, 0 never, 1 always
   uint32_t gen_grid = 0;
-  bool wide = false;  // census path with k_gt_wide in front of k_gt (see kWideSamples)
-  // bvcf_params.min_gq / min_dp on a file with samples: the census chain with k_gt_filter / k_dosage_filter in place of
-  // k_gt / k_dosage, one wave per task at any sample count, whatever the path overrides say (bvcf_gtfilter.hip.h)
-  bool gt_filter = false;
-  // bvcf_params.sample_keep on a file with samples: the same chain with k_gt_subset / k_dosage_subset as its scans
-  // (bvcf_gtsubset.hip.h; they apply the thresholds too).  n_samples, cmap_stride and dosage_stride are then those of the
-  // kept samples -- what every kernel behind the scan and the caller see --, n_samples_full is the file's count
-  bool gt_subset = false;
-  uint32_t n_samples_full = 0;
   uint32_t n_rank_words = 0;
-  DevBuf<uint2> d_rank;  // SubsetArgs.rank
-  int gt_subset_grid = 0;
+  DevBuf<uint2> d_rank;  // SubsetArgs.rank (BVCF_SCAN_SUBSET)
   uint64_t avg_line_bytes = 0;  // of the last collected batch (bvcf_submit_bgzf picks its inflate kernel by it)
   bool names_on = false;  // want_name_lists and bvcf_set_sample_names called: the chain ends with the k_name_* kernels
   DevBuf<uint32_t> d_name_off;
   DevBuf<uint8_t> d_name_text;
   NameTable name_table{};
-  bool sites = false; // no sample columns: k_sites after the census instead of k_scatter_eol + k_head + k_finish
-  bool sites1 = false;  // ... or k_sites1 on its own, no census, the line numbers by look-back (BVCF_SITES=3)
-  bool sites2 = false;  // ... or k_sites2 behind the census: tiles, the common lines on fast lanes (the default for such input)
-  bool packed = false;  // ... and the batch comes back in the packed form (bvcf_params.packed_sites; k_sites2 only)
-  bool sites2_tile_census = true;  // ... its census per tile (k_census_tiles, no scan kernel) instead of per chunk (BVCF_S2_CENSUS=chunk)
-  uint32_t s2_groups_cap = 0;      // entries of one of a slot's two sets of group totals (k_census_tiles)
+  uint32_t s2_groups_cap = 0;  // entries of one of a slot's two sets of group totals (k_census_tiles)
   int sites_grid = 0, sites1_grid = 0;
-  uint32_t win_bytes = 64u << 10;  // wide: bytes of a line's sample region per wave of the split general scan
-  uint32_t tile_bytes = 0, tile_quota = 0;
   // bvcf_params.render_sites (packed ctxs): rows made on the device; the format comes with bvcf_set_row_format
-  bool render = false, row_fmt_set = false;
+  bool row_fmt_set = false;
   DevBuf<uint8_t> d_row_fmt;  // "chr" | "\tSNP\t" | the constant tail
   uint32_t row_tail_len = 0, row_keep_pos = 0, row_keep_id = 0, row_keep_info = 0;
-  uint32_t n_samples = 0;
-  uint32_t cmap_stride = 0;
-  uint32_t dosage_stride = 0;  // 0 unless want_dosage
-  // bvcf_params.want_sample_stats on a file with samples: the per-sample counts behind every chain (bvcf_samplestats.hip.h)
-  bool ss_on = false;
-  uint32_t ss_ns_pad = 0, ss_max_runs = 0, ss_stripes = 0;
   // bvcf_enable_pair_stats on a file with samples: the pair counts behind every chain (bvcf_pairstats.hip.h).  The totals are
   // the ctx's: the folds of the slots' batches follow one another through ev_pr_fold
   bool pr_asked = false, pr_on = false, pr_folded = false;
   uint32_t pr_split = 1;
   DevBuf<unsigned long long> d_pr_tot;
   Event ev_pr_fold;
-  uint64_t max_lines = 0, max_alleles = 0, max_cmap = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
   DevBuf<FilterTable> d_filters;
-  uint32_t s1_fmode = 0, s1_fkey[4] = {0, 0, 0, 0}, s1_flen[4] = {0, 0, 0, 0};  // k_sites1's view of the allow list
   std::vector<Slot> slots;
   size_t head = 0, tail = 0, in_flight = 0;  // ring of busy slots, oldest at tail
   uint64_t totals[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -220,6 +193,14 @@ constexpr uint64_t kMaxBlockBytes = 0xFFF00000ull;
       return BVCF_E_HIP;                                                                 \
     }                                                                                    \
   } while (0)
+
+// workgroups of a kernel a CU holds; `fallback` when the runtime cannot say
+template <class K>
+int wgs_per_cu(K kernel, int threads, size_t lds, int fallback) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, lds) != hipSuccess || n < 1) n = fallback;
+  return n;
+}
 
 bool is_space(char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; }
 
@@ -247,6 +228,180 @@ int fill_filter(const char *text, bool star_is_nil, uint32_t *nil, uint32_t *n, 
   }
   return 0;
 }
+
+// what bvcf_create hands on besides the plan's scalars: the params with their defaults, the two tables it uploads
+struct CtxPlan : bvcf_ctx_plan {
+  bvcf_params p{};
+  std::vector<uint2> rank;  // bvcf_params.sample_keep: one {keep bits, kept before} entry per 32 samples; empty without a subset
+  FilterTable ft;
+};
+
+int env_int(const char *name, int unset) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : unset;
+}
+
+bool fill_filter_table(const char *allow, const char *exclude, FilterTable *ft) {
+  memset(ft, 0, sizeof *ft);
+  uint32_t used = 0;
+  return !fill_filter(allow, true, &ft->allow_nil, &ft->allow_n, ft->allow_off, ft->allow_len, ft->text, &used) &&
+         !fill_filter(exclude, false, &ft->deny_nil, &ft->deny_n, ft->deny_off, ft->deny_len, ft->text, &used);
+}
+
+// k_sites1 / k_sites2 test FILTER values of up to four bytes as dwords: possible when nothing is excluded and the allow list
+// is up to four values of one to four bytes (the default "PASS,." is), or allows everything
+void plan_filter_keys(CtxPlan *o) {
+  const FilterTable &ft = o->ft;
+  if (!ft.deny_nil) return;
+  o->s1_fmode = ft.allow_nil ? 2 : (ft.allow_n <= 4 ? 1 : 0);
+  if (o->s1_fmode != 1) return;
+  for (uint32_t i = 0; i < ft.allow_n; i++) {
+    const uint32_t l = ft.allow_len[i];
+    if (l == 0 || l > 4) {
+      o->s1_fmode = 0;
+      for (int q = 0; q < 4; q++) o->s1_flen[q] = 0;
+      return;
+    }
+    uint32_t k = 0;
+    for (uint32_t q = 0; q < l; q++) k |= (uint32_t)ft.text[ft.allow_off[i] + q] << (8 * q);
+    o->s1_fkey[i] = k;
+    o->s1_flen[i] = l;
+  }
+}
+
+// the defaults of the params, the strides and the capacities of a ctx over o->n_samples kept samples
+void plan_sizes(const bvcf_params *p, CtxPlan *o) {
+  memcpy(&o->p, p, offsetof(bvcf_params, sample_keep));  // (sample_keep, the caller's array, is in the rank table)
+  if (!o->p.max_batch_bytes) o->p.max_batch_bytes = 64ull << 20;
+  if (o->p.max_batch_bytes >= kMaxBlockBytes) o->p.max_batch_bytes = kMaxBlockBytes - 1;
+  if (!o->p.n_slots) o->p.n_slots = 3;  // (measured better than 2 or equal on every input shape: profiles/r05_blocks_in_flight_2_vs_3_all_profiles.txt)
+  if (!o->p.eol_byte) o->p.eol_byte = '\n';
+  o->max_batch_bytes = o->p.max_batch_bytes;
+  o->n_slots = o->p.n_slots;
+  o->eol_byte = o->p.eol_byte;
+  const uint32_t n = o->n_samples;
+  o->cmap_stride = ((n + 3) / 4 + 15) & ~15u;
+  o->dosage_stride = p->want_dosage && n ? ((n + 15) & ~15u) : 0u;
+  const uint64_t min_line = std::max<uint64_t>(48, 2ull * p->n_header_fields);
+  // (the slack is for short lines -- comments, junk -- between the records; every listed line owns a class-map slot
+  // on the census path, so for very wide cohorts the slack is what 32 MiB of maps can hold: a batch that needs more
+  // grows the reservation, BVCF_E_CAPACITY)
+  const uint64_t slack = std::min<uint64_t>(4096, std::max<uint64_t>(64, (32ull << 20) / std::max<uint32_t>(o->cmap_stride, 1u)));
+  o->max_lines = p->max_lines ? p->max_lines : o->max_batch_bytes / min_line + slack;
+  o->max_alleles = p->max_alleles ? p->max_alleles : 2 * o->max_lines + 1024;
+  if (o->max_alleles < o->max_lines + 64) o->max_alleles = o->max_lines + 64;  // slot i belongs to line i
+  o->max_cmap = p->cmap_bytes ? p->cmap_bytes : (o->max_lines + o->max_lines / 2) * (uint64_t)o->cmap_stride + (1ull << 20);
+  if (o->max_cmap > 0xFFFFFF00ull) o->max_cmap = 0xFFFFFF00ull;  // cmap_off is 32-bit
+  if (o->max_cmap < 4096) o->max_cmap = 4096;  // (k_gt's prefetch reads a raw-list area's worth from the start of the arena)
+  o->max_cmap = (o->max_cmap + 63) & ~63ull;
+  // streaming path: lines are found by the genotype scan itself.  Its tile-local entry quota is
+  // bounded because a line that passes the field count is at least n_header - 1 bytes long; for
+  // narrow files the quota would dwarf the text, so they stay on the census path unless asked.
+  o->tile_bytes = 64u << 10;  // (8-64 KiB measure alike now that the runs are balanced)
+  const unsigned tile_kb = (unsigned)env_int("BVCF_TILE_KB", 0);
+  if (tile_kb >= 4 && tile_kb <= 1024) o->tile_bytes = tile_kb << 10;
+  o->tile_quota = o->tile_bytes / (p->n_header_fields - 1 + p->eol_chars) + 2;
+  o->win_bytes = 64u << 10;
+  if (const char *e = getenv("BVCF_WIDE_WIN")) {  // test / tuning: window of the split general scan, bytes
+    const long v = atol(e);
+    if (v >= 64 && v <= (64l << 20)) o->win_bytes = (uint32_t)v;
+  }
+  // per-sample counts: the runs' partial tables are held to 16 MiB
+  o->ss_on = p->want_sample_stats != 0 && n > 0;
+  if (o->ss_on) {
+    o->ss_ns_pad = 4u * o->cmap_stride;
+    o->ss_stripes = (o->ss_ns_pad + kSsStripeSamples - 1u) / kSsStripeSamples;
+    o->ss_max_runs = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (16ull << 20) / (4ull * kSsCols * o->ss_ns_pad)));
+  }
+}
+
+// the chain of a file with samples.  The masked scan and the subset scan live on the census path only, one wave per (line,
+// ALT index) at any sample count, whatever the overrides say.  From kWideSamples samples up a line is hundreds of kilobytes
+// and a batch holds too few of them to fill the GPU with one wave per line: the census path then splits the regular scan
+// of a line over several waves, and is what `choose` picks.
+void plan_sample_chain(const bvcf_params *p, CtxPlan *o) {
+  const uint32_t n = o->n_samples;
+  const bool subset = !o->rank.empty(), filter = p->min_gq != 0 || p->min_dp != 0;
+  const uint32_t path = (filter || subset) ? 1u : (uint32_t)env_int("BVCF_PATH", (int)p->path);  // (the variable: test / tuning override)
+  const bool many = o->n_samples_full >= kWideSamples;
+  const bool fused = path == 2 || path == 3 || (path == 0 && p->n_header_fields >= 256 && !many);
+  bool wide = !fused && many;
+  if (const char *e = getenv("BVCF_WIDE")) wide = !fused && atoi(e) != 0;  // test / tuning override
+  o->chain = fused ? BVCF_CHAIN_STREAM : BVCF_CHAIN_CENSUS;
+  o->scan = subset ? BVCF_SCAN_SUBSET : filter ? BVCF_SCAN_FILTER : wide ? BVCF_SCAN_WIDE : BVCF_SCAN_PLAIN;
+  if (const char *e = getenv("BVCF_GEN_STREAM")) o->gen_policy = atoi(e) != 0 ? 1 : 0;
+  if (!fused || n > 4u * kStageBytes) o->gen_policy = 0;  // (a line's dense class map is staged in LDS)
+  o->gen_mode = o->gen_policy == 1;
+  if (path == 3 && o->gen_policy < 0) o->gen_mode = o->shape_seen = 1;  // the caller has seen a line: its sample fields carry more than GT
+}
+
+// sites-only input takes k_sites2 behind its census (BVCF_SITES=0: the census chain with k_head, for A/B and parity tests;
+// builds with -DBVCF_EXPERIMENTS also know 3: k_sites1, no census, the line numbers by look-back, and any other value
+// but 2: k_sites, round 2's kernel -- both slower, kept out of the product library)
+void plan_sites_chain(const bvcf_params *p, CtxPlan *o) {
+  const int sites = env_int("BVCF_SITES", 2);
+  const char *census = getenv("BVCF_S2_CENSUS");  // (A/B and parity tests)
+  o->chain = (census && strcmp(census, "chunk") == 0) ? BVCF_CHAIN_SITES2_CHUNKS : BVCF_CHAIN_SITES2_TILES;
+  if (sites == 0) o->chain = BVCF_CHAIN_CENSUS;
+#ifdef BVCF_EXPERIMENTS
+  if (sites == 3) o->chain = BVCF_CHAIN_SITES1_EXP;
+  if (sites != 0 && sites != 2 && sites != 3) o->chain = BVCF_CHAIN_SITES_EXP;
+#endif
+  o->gen_policy = 0;
+  o->packed = (o->chain == BVCF_CHAIN_SITES2_TILES || o->chain == BVCF_CHAIN_SITES2_CHUNKS) && p->packed_sites != 0;
+  o->render = o->packed && p->render_sites != 0;
+}
+
+// Everything bvcf_create decides before it needs the device (exported as bvcf_plan_ctx, include/bvcf_plan.h): the
+// argument checks, the sample subset, the defaults and capacities, and which chain a batch of this ctx runs.
+int plan_ctx(const bvcf_params *p, CtxPlan *o, std::string *err) {
+  // (abi_version BVCF_ABI_VERSION: the caller's struct ends behind min_dp, and nothing behind it is read)
+  const bool has_keep = p->abi_version == BVCF_ABI_VERSION_SUBSET;
+  if ((p->abi_version != BVCF_ABI_VERSION && !has_keep) || p->n_header_fields < 1 || p->eol_chars < 1 || p->eol_chars > 2) {
+    *err = "bad bvcf_params";
+    return BVCF_E_ARG;
+  }
+  if (p->min_gq > BVCF_MAX_THRESHOLD || p->min_dp > BVCF_MAX_THRESHOLD) {
+    *err = "bad bvcf_params: min_gq / min_dp above 999999999";
+    return BVCF_E_ARG;
+  }
+  *o = CtxPlan{};
+  if (!fill_filter_table(p->allow_filter, p->exclude_filter, &o->ft)) {
+    *err = "too many / too long FILTER values (32 values, 2048 bytes)";
+    return BVCF_E_ARG;
+  }
+  plan_filter_keys(o);
+  // the sample subset: bits from n_samples_full on are ignored
+  const uint32_t ns_full = o->n_samples = o->n_samples_full = p->n_header_fields > 9 ? p->n_header_fields - 9 : 0;
+  if (has_keep && p->sample_keep && ns_full) {
+    uint32_t n_keep = 0;
+    o->rank.resize((ns_full + 31u) / 32u);
+    for (uint32_t w = 0; w < o->rank.size(); w++) {
+      const uint32_t left = ns_full - 32u * w;
+      const uint32_t bits = p->sample_keep[w] & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
+      o->rank[w] = make_uint2(bits, n_keep);
+      n_keep += (uint32_t)__builtin_popcount(bits);
+    }
+    if (!n_keep) {
+      *err = "bad bvcf_params: sample_keep keeps no sample";
+      return BVCF_E_ARG;
+    }
+    o->n_samples = n_keep;
+  }
+  plan_sizes(p, o);
+  o->gen_policy = -1;
+  o->head_fast = env_int("BVCF_HEAD_FAST", 1) != 0;  // test / tuning override
+  if (o->n_samples)
+    plan_sample_chain(p, o);
+  else
+    plan_sites_chain(p, o);
+  return BVCF_OK;
+}
+
+// the conditions the chain decides that recur: the streaming chain; the extras of alleles[] follow slot cap_lines, not the
+// batch's last line (k_sites1 does not know the number of lines while it runs, the packed form keeps them apart)
+bool is_stream(const bvcf_ctx_plan *c) { return c->chain == BVCF_CHAIN_STREAM; }
+bool extras_at_cap(const bvcf_ctx_plan *c) { return c->chain == BVCF_CHAIN_SITES1_EXP || c->packed; }
 
 void free_slot(Slot &s) {
   if (s.stream) hipStreamSynchronize(s.stream);
@@ -320,11 +475,11 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
   HIP_TRY(c, s.d_cmap.alloc(c->max_cmap + 64));
   HIP_TRY(c, s.d_tasks.alloc(c->max_alleles));
   HIP_TRY(c, s.d_results.alloc(c->max_alleles));
-  if (c->wide)
+  if (c->scan == BVCF_SCAN_WIDE)
     HIP_TRY(c, s.d_win_tabs.alloc(std::min<uint64_t>(2 * (c->p.max_batch_bytes / c->win_bytes) + c->max_lines + 64, 0x7FFFFFFFu)));
   HIP_TRY(c, s.d_line_len.alloc(c->max_lines));
   HIP_TRY(c, s.d_line_cmap.alloc(c->max_lines));
-  if (c->fused) {
+  if (is_stream(c)) {
     HIP_TRY(c, s.d_line_bits.alloc(c->max_lines * 8));
     HIP_TRY(c, s.d_finish_items.alloc(c->max_lines + c->max_alleles));
     HIP_TRY(c, s.d_left_lines.alloc(c->max_lines));
@@ -346,14 +501,9 @@ int alloc_results(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, s.d_dosage.alloc(c->max_alleles * c->dosage_stride + 64));
     HIP_TRY(c, s.h_dosage.alloc(c->max_alleles * c->dosage_stride + 64));
   }
-  {
-    const int rc = alloc_names(c, s, std::max<uint64_t>(s.cap_names, c->p.max_batch_bytes / 2 + (1u << 20)));
-    if (rc) return rc;
-  }
-  {
-    const int rc = alloc_row_lists(c, s);
-    if (rc) return rc;
-  }
+  int rc = alloc_names(c, s, std::max<uint64_t>(s.cap_names, c->p.max_batch_bytes / 2 + (1u << 20)));
+  if (!rc) rc = alloc_row_lists(c, s);
+  if (rc) return rc;
   s.cap_lines = c->max_lines;
   s.cap_alleles = c->max_alleles;
   s.cap_cmap = c->max_cmap;
@@ -383,7 +533,7 @@ int alloc_slot(bvcf_ctx *c, Slot &s) {
   s.s2_parity = 0;
   HIP_TRY(c, s.d_counters.alloc(1));
   HIP_TRY(c, s.h_counters.alloc(1));
-  if (c->fused) {
+  if (is_stream(c)) {
     const uint64_t max_tiles = (c->p.max_batch_bytes + c->tile_bytes - 1) / c->tile_bytes + 1;
     HIP_TRY(c, s.d_entries.alloc(max_tiles * c->tile_quota));
     HIP_TRY(c, s.d_head_bits.alloc(max_tiles * c->tile_quota * 16));
@@ -432,16 +582,16 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.tasks = s.d_tasks;
   a.results = s.d_results;
   a.counters = s.d_counters;
-  a.fused = c->fused ? 1u : 0u;
+  a.fused = is_stream(c) ? 1u : 0u;
   a.gen_stream = c->gen_mode ? 1u : 0u;
   a.prod_waves = (uint32_t)(c->gen_mode ? c->gen_grid : c->stream_grid) * kWavesPerWg;
-  a.wide = c->wide ? 1u : 0u;
+  a.wide = c->scan == BVCF_SCAN_WIDE ? 1u : 0u;
   a.win_bytes = c->win_bytes;
   a.win_tabs = s.d_win_tabs;
   a.win_tabs_cap = (uint32_t)s.d_win_tabs.size();
   a.tile_bytes = c->tile_bytes;
   a.tile_quota = c->tile_quota;
-  a.n_tiles = c->fused ? (uint32_t)((nbytes + c->tile_bytes - 1) / c->tile_bytes) : 0u;
+  a.n_tiles = is_stream(c) ? (uint32_t)((nbytes + c->tile_bytes - 1) / c->tile_bytes) : 0u;
   a.entries = s.d_entries;
   a.line_len = s.d_line_len;
   a.line_cmap = s.d_line_cmap;
@@ -459,8 +609,6 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   return a;
 }
 
-// the kernel chain for one resident block; ev_gt0 / ev_gt1 (optional) bracket the dominant kernel
-// (k_gt on the census path, k_stream on the streaming path)
 void launch_names(bvcf_ctx *c, const KernelArgs &a, const NameArgs &na, hipStream_t st) {
   hipLaunchKernelGGL(k_name_len, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, na);
   hipLaunchKernelGGL(k_name_scan, dim3(1), dim3(1024), 0, st, a, na);
@@ -469,11 +617,11 @@ void launch_names(bvcf_ctx *c, const KernelArgs &a, const NameArgs &na, hipStrea
 
 // a batch's counters are in: should the next one go through the other streaming kernel?
 void adapt_stream_kernel(bvcf_ctx *c, bool was_gen, const BatchCounters &ctr) {
-  // how many scans the last batch left to k_gt, and lines to k_finish: the grids of the next batch's (launch_chain)
+  // how many scans the last batch left to k_gt, and lines to k_finish: the grids of the next batch's (launch_stream)
   c->last_real = ctr.n_real;
   c->last_finish = ctr.n_finish;
   c->last_left = ctr.n_left;
-  if (c->gen_policy >= 0 || !c->fused || ctr.n_lines < 16) return;
+  if (c->gen_policy >= 0 || !is_stream(c) || ctr.n_lines < 16) return;
   c->shape_seen = true;
   if ((uint64_t)ctr.n_other_shape * 2u > ctr.n_lines) c->gen_mode = !was_gen;
 }
@@ -535,173 +683,183 @@ void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot 
   }
 }
 
-void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot = nullptr) {
-  if (a.fused) {
-    // (experiments builds, BVCF_SCAN_STREAM=1: the one-pass kernels of ALL batches through one stream of the ctx, what follows
-    // a batch's pass on the slot's stream behind events -- the chain then runs nearly serially; scan_stream is null otherwise)
-    const bool split = c->scan_stream && slot && slot->ev_in && slot->ev_scan;
-    hipStream_t ss = split ? c->scan_stream : st;
-    if (split) {
-      hipEventRecord(slot->ev_in, st);  // the text is in, and the slot's last batch is through
-      hipStreamWaitEvent(ss, slot->ev_in, 0);
-    }
-    hipMemsetAsync(a.counters, 0, sizeof(BatchCounters), ss);
-    if (ev_gt0) hipEventRecord(ev_gt0, ss);
-    if (a.gen_stream)
-      hipLaunchKernelGGL(k_stream_gen, dim3(c->gen_grid), dim3(kWgThreads), gen_lds_bytes(a.n_samples), ss, a);
-    else
-      hipLaunchKernelGGL(k_stream, dim3(c->stream_grid), dim3(kWgThreads), c->stream_lds_pad, ss, a);
-    if (ev_gt1) hipEventRecord(ev_gt1, ss);
-    if (split) {
-      hipEventRecord(slot->ev_scan, ss);
-      hipStreamWaitEvent(st, slot->ev_scan, 0);
-    }
-    hipLaunchKernelGGL(k_order, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+// a follower grid of the streaming chain.  k_head, k_gt and k_finish walk lists (left_lines, real_tasks, finish_items) with
+// grid strides: any grid is right.  A file of biallelic lines leaves them nearly empty, and a thousand workgroups that start
+// to find that out hold wave slots the next blocks' scans would use; the grids follow what the last collected batch left
+// (`last`, one workgroup per `per_wg` entries; unknown: the full grid).
+uint32_t follower_grid(const bvcf_ctx *c, uint32_t full, uint32_t last, uint32_t per_wg) {
+  if (last == 0xFFFFFFFFu) return full;
+  return std::min<uint32_t>(full, std::max<uint32_t>((uint32_t)c->n_cu / 4u, last / per_wg + 1u));
+}
+
+// (k_head_lean when batches overlap: at 132 registers three of its workgroups fit on a CU beside the kernels of
+// the neighbouring batch; sites-only benchmark with two slots 4.4 -> 4.9 G variants/s, with one slot 3.5 -> 3.4)
+void launch_head(bvcf_ctx *c, const KernelArgs &a, uint32_t grid, hipStream_t st) {
+  if (c->p.n_slots > 1)
+    hipLaunchKernelGGL(k_head_lean, dim3(grid), dim3(kWgThreads), 0, st, a);
+  else
+    hipLaunchKernelGGL(k_head, dim3(grid), dim3(kWgThreads), 0, st, a);
+}
+
+void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot) {
+  // (experiments builds, BVCF_SCAN_STREAM=1: the one-pass kernels of ALL batches through one stream of the ctx, what follows
+  // a batch's pass on the slot's stream behind events -- the chain then runs nearly serially; scan_stream is null otherwise)
+  const bool split = c->scan_stream && slot && slot->ev_in && slot->ev_scan;
+  hipStream_t ss = split ? c->scan_stream : st;
+  if (split) {
+    hipEventRecord(slot->ev_in, st);  // the text is in, and the slot's last batch is through
+    hipStreamWaitEvent(ss, slot->ev_in, 0);
+  }
+  hipMemsetAsync(a.counters, 0, sizeof(BatchCounters), ss);
+  if (ev_gt0) hipEventRecord(ev_gt0, ss);
+  if (a.gen_stream)
+    hipLaunchKernelGGL(k_stream_gen, dim3(c->gen_grid), dim3(kWgThreads), gen_lds_bytes(a.n_samples), ss, a);
+  else
+    hipLaunchKernelGGL(k_stream, dim3(c->stream_grid), dim3(kWgThreads), c->stream_lds_pad, ss, a);
+  if (ev_gt1) hipEventRecord(ev_gt1, ss);
+  if (split) {
+    hipEventRecord(slot->ev_scan, ss);
+    hipStreamWaitEvent(st, slot->ev_scan, 0);
+  }
+  hipLaunchKernelGGL(k_order, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
 #ifdef BVCF_EXPERIMENTS
-    // experiment (results are then wrong): which follower costs what with blocks in flight -- 1: no k_head, 2: no k_gt, 4: no k_finish
-    static const int skip = getenv("BVCF_EXP_SKIP") ? atoi(getenv("BVCF_EXP_SKIP")) : 0;
-    static const int head_wgs = getenv("BVCF_EXP_HEAD_WGS") ? atoi(getenv("BVCF_EXP_HEAD_WGS")) : 4;
-    static const int gt_div = getenv("BVCF_EXP_GT_DIV") ? atoi(getenv("BVCF_EXP_GT_DIV")) : 1;
+  // experiment (results are then wrong): which follower costs what with blocks in flight -- 1: no k_head, 2: no k_gt, 4: no k_finish
+  static const int skip = getenv("BVCF_EXP_SKIP") ? atoi(getenv("BVCF_EXP_SKIP")) : 0;
+  static const int head_wgs = getenv("BVCF_EXP_HEAD_WGS") ? atoi(getenv("BVCF_EXP_HEAD_WGS")) : 4;
+  static const int gt_div = getenv("BVCF_EXP_GT_DIV") ? atoi(getenv("BVCF_EXP_GT_DIV")) : 1;
 #else
-    constexpr int skip = 0, head_wgs = 4, gt_div = 1;
+  constexpr int skip = 0, head_wgs = 4, gt_div = 1;
 #endif
-    // k_head walks the list of the lines k_order did not settle itself (left_lines), a workgroup step per 256 of them: on a file
-    // of biallelic SNPs those are the first lines of k_stream's runs, a few thousand per block.  As with k_gt and k_finish
-    // below, the grid follows what the last collected batch left; with the fast lane off every line is listed: the full grid.
-    const uint32_t head_full = (uint32_t)c->n_cu * (uint32_t)head_wgs;
-    const uint32_t head_grid = (c->last_left == 0xFFFFFFFFu || !c->head_fast)
-                                   ? head_full
-                                   : std::min<uint32_t>(head_full, std::max<uint32_t>((uint32_t)c->n_cu / 4u, c->last_left / kWgThreads + 1u));
-    if (skip & 1) {
-    } else if (c->p.n_slots > 1)
-      hipLaunchKernelGGL(k_head_lean, dim3(head_grid), dim3(kWgThreads), 0, st, a);
-    else
-      hipLaunchKernelGGL(k_head, dim3(head_grid), dim3(kWgThreads), 0, st, a);
-    // k_gt and k_finish walk lists (real_tasks, finish_items) with grid strides: any grid is right.  A file of biallelic lines
-    // leaves both empty, and a thousand workgroups that start to find that out hold wave slots the next blocks' scans would
-    // use; the grids follow what the last collected batch needed (a wave of k_gt per two scans, a thread of k_finish per line).
-    const uint32_t gt_full = (uint32_t)c->gt_grid / (uint32_t)gt_div;
-    const uint32_t gt_wgs = c->last_real == 0xFFFFFFFFu ? gt_full
-                            : std::min<uint32_t>(gt_full, std::max<uint32_t>((uint32_t)c->n_cu / 4u, c->last_real / (2u * kWavesPerWg) + 1u));
-    const uint32_t fin_full = (uint32_t)c->n_cu * 4u;
-    const uint32_t fin_wgs = c->last_finish == 0xFFFFFFFFu ? fin_full
-                             : std::min<uint32_t>(fin_full, std::max<uint32_t>((uint32_t)c->n_cu / 4u, c->last_finish / kWgThreads + 1u));
-    if (!(skip & 2)) hipLaunchKernelGGL(k_gt, dim3(gt_wgs), dim3(kWgThreads), 0, st, a);
-    if (!(skip & 4)) hipLaunchKernelGGL(k_finish, dim3(fin_wgs), dim3(kWgThreads), 0, st, a);
-    if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
-    launch_sample_stats(c, a, st, slot);
-    return;
-  }
-#ifdef BVCF_EXPERIMENTS
-  if (c->sites1) {
-    // sites-only input, one pass: the counters and the tiles' look-back state start from zero
-    const uint32_t n_words = s1_state_words(a.nbytes);
-    hipLaunchKernelGGL(k_s1_zero, dim3(std::min<uint32_t>((n_words + 255u) / 256u, (uint32_t)c->n_cu)), dim3(256), 0, st, a, n_words);
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    const uint32_t n_tiles = s1_n_tiles(a.nbytes);
-    // (the first generation of workgroups starts spread over ~a tile's lifetime, see the kernel; wall_clock64 ticks at 100 MHz)
-    static const uint32_t stagger_us = [] {
-      const char *e = getenv("BVCF_S1_STAGGER_US");
-      return e ? (uint32_t)atoi(e) : 0u;
-    }();
-    if (n_tiles)
-      hipLaunchKernelGGL(k_sites1, dim3(s1_n_wgs(n_tiles)), dim3(kS1Threads), 0, st, a, n_tiles, (uint32_t)c->sites1_grid, stagger_us * 100u);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
-    return;
-  }
-#endif
+  // k_head walks the list of the lines k_order did not settle itself, a workgroup step per 256 of them: on a file of
+  // biallelic SNPs those are the first lines of k_stream's runs, a few thousand per block (with the fast lane off every
+  // line is listed: the full grid); a wave of k_gt per two scans, a thread of k_finish per line
+  const uint32_t n_cu = (uint32_t)c->n_cu;
+  if (!(skip & 1))
+    launch_head(c, a, follower_grid(c, n_cu * (uint32_t)head_wgs, c->head_fast ? c->last_left : 0xFFFFFFFFu, kWgThreads), st);
+  if (!(skip & 2))
+    hipLaunchKernelGGL(k_gt, dim3(follower_grid(c, (uint32_t)c->gt_grid / (uint32_t)gt_div, c->last_real, 2u * kWavesPerWg)),
+                       dim3(kWgThreads), 0, st, a);
+  if (!(skip & 4))
+    hipLaunchKernelGGL(k_finish, dim3(follower_grid(c, n_cu * 4u, c->last_finish, kWgThreads)), dim3(kWgThreads), 0, st, a);
+  if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
+  launch_sample_stats(c, a, st, slot);
+}
+
+uint32_t census_grid(const bvcf_ctx *c, uint32_t n_chunks) {
+  const uint32_t g = (uint32_t)std::min<uint64_t>((n_chunks + kWavesPerWg - 1) / kWavesPerWg, (uint64_t)c->n_cu * 8);
+  return g ? g : 1;
+}
+
+// the newline census per 1 KiB chunk and its two scan levels, in front of the census chain, k_sites and (BVCF_S2_CENSUS=chunk)
+// k_sites2; returns the number of chunks
+uint32_t launch_census(bvcf_ctx *c, const KernelArgs &a, hipStream_t st) {
   const uint32_t n_chunks = (a.nbytes + kChunk - 1) / kChunk;
   const uint32_t n_groups = (n_chunks + kScanGroup - 1) / kScanGroup;
-  const uint32_t stream_grid = (uint32_t)std::min<uint64_t>((n_chunks + kWavesPerWg - 1) / kWavesPerWg,
-                                                            (uint64_t)c->n_cu * 8);
-  if (c->sites2 && c->sites2_tile_census) {
-    // the census per tile, one scan level
-    const uint32_t n_tiles = s2_n_tiles(a.nbytes);
-    if (a.sites) {  // the packed form: no scan kernel, k_sites2p sums the census' three levels itself
-      const uint32_t grid = s2_n_bundles(n_tiles);
-      hipLaunchKernelGGL(k_census_tiles, dim3(grid ? grid : 1), dim3(kWgThreads), 0, st, a, n_tiles, c->s2_groups_cap);
-    } else {
-      const uint32_t grid = (uint32_t)std::min<uint64_t>((n_tiles + kWavesPerWg - 1) / kWavesPerWg, (uint64_t)c->n_cu * 8);
-      hipLaunchKernelGGL(k_count_tiles, dim3(grid ? grid : 1), dim3(kWgThreads), 0, st, a, n_tiles);
-      hipLaunchKernelGGL(k_scan_flat, dim3(1), dim3(1024), 0, st, a, n_tiles);
-    }
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    if (a.sites)
-      hipLaunchKernelGGL(k_sites2p, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, n_tiles, 0u);
-    else
-      hipLaunchKernelGGL(k_sites2, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, n_tiles, 0u);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
-    return;
-  }
-  hipLaunchKernelGGL(k_count_eol, dim3(stream_grid ? stream_grid : 1), dim3(kWgThreads), 0, st, a, n_chunks);
+  hipLaunchKernelGGL(k_count_eol, dim3(census_grid(c, n_chunks)), dim3(kWgThreads), 0, st, a, n_chunks);
   hipLaunchKernelGGL(k_scan_groups, dim3(n_groups ? n_groups : 1), dim3(kWgThreads), 0, st, a, n_chunks);
   hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, st, a, n_groups);
-  if (c->sites2) {
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    if (a.sites)
-      hipLaunchKernelGGL(k_sites2p, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, s2_n_tiles(a.nbytes), n_chunks);
-    else
-      hipLaunchKernelGGL(k_sites2, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, s2_n_tiles(a.nbytes), n_chunks);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
-    return;
+  return n_chunks;
+}
+
+// sites-only input: k_sites2 (full records) or k_sites2p (the packed form) behind the census per tile, one scan level, or
+// behind the census per chunk
+void launch_sites2(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1) {
+  const uint32_t n_tiles = s2_n_tiles(a.nbytes);
+  uint32_t n_chunks = 0;
+  if (c->chain == BVCF_CHAIN_SITES2_CHUNKS) {
+    n_chunks = launch_census(c, a, st);
+  } else if (a.sites) {  // the packed form: no scan kernel, k_sites2p sums the census' three levels itself
+    const uint32_t grid = s2_n_bundles(n_tiles);
+    hipLaunchKernelGGL(k_census_tiles, dim3(grid ? grid : 1), dim3(kWgThreads), 0, st, a, n_tiles, c->s2_groups_cap);
+  } else {
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_tiles + kWavesPerWg - 1) / kWavesPerWg, (uint64_t)c->n_cu * 8);
+    hipLaunchKernelGGL(k_count_tiles, dim3(grid ? grid : 1), dim3(kWgThreads), 0, st, a, n_tiles);
+    hipLaunchKernelGGL(k_scan_flat, dim3(1), dim3(1024), 0, st, a, n_tiles);
   }
-#ifdef BVCF_EXPERIMENTS
-  if (c->sites) {
-    // sites-only input: line records and allele records straight from one pass over the text
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    hipLaunchKernelGGL(k_sites, dim3(c->sites_grid), dim3(kSitesThreads), 0, st, a, n_chunks);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
-    return;
-  }
-#endif
-  hipLaunchKernelGGL(k_scatter_eol, dim3(stream_grid ? stream_grid : 1), dim3(kWgThreads), 0, st, a, n_chunks);
-  // (k_head_lean when batches overlap: at 132 registers three of its workgroups fit on a CU beside the kernels of
-  // the neighbouring batch; sites-only benchmark with two slots 4.4 -> 4.9 G variants/s, with one slot 3.5 -> 3.4)
-  if (c->p.n_slots > 1)
-    hipLaunchKernelGGL(k_head_lean, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+  if (ev_gt0) hipEventRecord(ev_gt0, st);
+  if (a.sites)
+    hipLaunchKernelGGL(k_sites2p, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, n_tiles, n_chunks);
   else
-    hipLaunchKernelGGL(k_head, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
-  if (a.n_samples) {
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    if (c->gt_subset) {
-      // bvcf_params.sample_keep: the scan and the dosage rows of the kept samples (masked as well, with a threshold); the
-      // rest of the chain is the same, over n_keep samples
-      const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
-      const SubsetArgs sa = {c->d_rank, c->n_samples_full, c->n_rank_words};
-      hipLaunchKernelGGL(k_gt_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa);
-      if (ev_gt1) hipEventRecord(ev_gt1, st);
-      hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
-      if (a.dosage) hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa);
-      launch_sample_stats(c, a, st, slot);
-      return;
-    }
-    if (c->gt_filter) {
-      // bvcf_params.min_gq / min_dp: the masked scan and the masked dosage rows; the rest of the chain is the same
-      const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
-      hipLaunchKernelGGL(k_gt_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa);
-      if (ev_gt1) hipEventRecord(ev_gt1, st);
-      hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
-      if (a.dosage) hipLaunchKernelGGL(k_dosage_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa);
-      launch_sample_stats(c, a, st, slot);
-      return;
-    }
-    if (c->wide) {
+    hipLaunchKernelGGL(k_sites2, dim3(c->sites1_grid), dim3(kS1Threads), 0, st, a, n_tiles, n_chunks);
+  if (ev_gt1) hipEventRecord(ev_gt1, st);
+}
+
+#ifdef BVCF_EXPERIMENTS
+// sites-only input: line records and allele records straight from one pass over the text, behind the census (BVCF_SITES=1)
+void launch_sites_exp(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1) {
+  const uint32_t n_chunks = launch_census(c, a, st);
+  if (ev_gt0) hipEventRecord(ev_gt0, st);
+  hipLaunchKernelGGL(k_sites, dim3(c->sites_grid), dim3(kSitesThreads), 0, st, a, n_chunks);
+  if (ev_gt1) hipEventRecord(ev_gt1, st);
+}
+
+// ... or one pass and no census: the counters and the tiles' look-back state start from zero (BVCF_SITES=3)
+void launch_sites1_exp(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1) {
+  const uint32_t n_words = s1_state_words(a.nbytes);
+  hipLaunchKernelGGL(k_s1_zero, dim3(std::min<uint32_t>((n_words + 255u) / 256u, (uint32_t)c->n_cu)), dim3(256), 0, st, a, n_words);
+  if (ev_gt0) hipEventRecord(ev_gt0, st);
+  const uint32_t n_tiles = s1_n_tiles(a.nbytes);
+  // (the first generation of workgroups starts spread over ~a tile's lifetime, see the kernel; wall_clock64 ticks at 100 MHz)
+  static const uint32_t stagger_us = [] {
+    const char *e = getenv("BVCF_S1_STAGGER_US");
+    return e ? (uint32_t)atoi(e) : 0u;
+  }();
+  if (n_tiles)
+    hipLaunchKernelGGL(k_sites1, dim3(s1_n_wgs(n_tiles)), dim3(kS1Threads), 0, st, a, n_tiles, (uint32_t)c->sites1_grid, stagger_us * 100u);
+  if (ev_gt1) hipEventRecord(ev_gt1, st);
+}
+#endif
+
+// the census chain: every line listed and parsed by k_head, then -- with samples -- the scan the plan names, k_finish, the
+// dosage rows of the same scan and the per-sample counts
+void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot) {
+  const uint32_t n_chunks = launch_census(c, a, st);
+  hipLaunchKernelGGL(k_scatter_eol, dim3(census_grid(c, n_chunks)), dim3(kWgThreads), 0, st, a, n_chunks);
+  launch_head(c, a, (uint32_t)c->n_cu * 4u, st);
+  // bvcf_params.min_gq / min_dp: the masked scan and the masked dosage rows; sample_keep: those of the kept samples (masked
+  // as well, with a threshold); the rest of the chain is the same, over n_samples kept samples
+  const GtFilterArgs fa = {c->p.min_gq, c->p.min_dp};
+  const SubsetArgs sa = {c->d_rank, c->n_samples_full, c->n_rank_words};
+  if (ev_gt0) hipEventRecord(ev_gt0, st);
+  switch (c->scan) {
+    case BVCF_SCAN_NONE: break;
+    case BVCF_SCAN_SUBSET: hipLaunchKernelGGL(k_gt_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa); break;
+    case BVCF_SCAN_FILTER: hipLaunchKernelGGL(k_gt_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa); break;
+    case BVCF_SCAN_WIDE:
       hipMemsetAsync(a.results, 0, (size_t)a.max_tasks * sizeof(GtResult), st);
       hipLaunchKernelGGL(k_gt_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
       if (a.win_tabs) {
         hipLaunchKernelGGL(k_tabs_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
         hipLaunchKernelGGL(k_gt_wide_general, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
       }
+      [[fallthrough]];
+    default: hipLaunchKernelGGL(k_gt, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
+  }
+  if (ev_gt1) hipEventRecord(ev_gt1, st);
+  if (c->scan == BVCF_SCAN_NONE) return;
+  hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+  if (a.dosage) switch (c->scan) {
+      case BVCF_SCAN_SUBSET: hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa); break;
+      case BVCF_SCAN_FILTER: hipLaunchKernelGGL(k_dosage_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa); break;
+      default:
+        hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
+        if (a.wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
     }
-    hipLaunchKernelGGL(k_gt, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
-    hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
-    if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
-    if (a.dosage && c->wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
-    launch_sample_stats(c, a, st, slot);
-  } else {
-    if (ev_gt0) hipEventRecord(ev_gt0, st);
-    if (ev_gt1) hipEventRecord(ev_gt1, st);
+  launch_sample_stats(c, a, st, slot);
+}
+
+// the kernel chain for one resident block; ev_gt0 / ev_gt1 (optional) bracket the dominant kernel (k_gt on the census path,
+// k_stream on the streaming path, k_sites* without samples)
+void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot = nullptr) {
+  switch (c->chain) {
+    case BVCF_CHAIN_STREAM: return launch_stream(c, a, st, ev_gt0, ev_gt1, slot);
+    case BVCF_CHAIN_SITES2_TILES:
+    case BVCF_CHAIN_SITES2_CHUNKS: return launch_sites2(c, a, st, ev_gt0, ev_gt1);
+#ifdef BVCF_EXPERIMENTS
+    case BVCF_CHAIN_SITES_EXP: return launch_sites_exp(c, a, st, ev_gt0, ev_gt1);
+    case BVCF_CHAIN_SITES1_EXP: return launch_sites1_exp(c, a, st, ev_gt0, ev_gt1);
+#endif
+    default: return launch_census_chain(c, a, st, ev_gt0, ev_gt1, slot);
   }
 }
 
@@ -752,6 +910,19 @@ static const CrcTabs *crc_tabs_on_device() {
   return on_dev[dev];
 }
 
+// a descriptor per block, the blocks' text one behind the other; returns the bytes of text
+static uint64_t fill_descs(const std::vector<bvcf_bgzf::Block> &blocks, BgzfDesc *desc) {
+  uint64_t total = 0;
+  for (size_t i = 0; i < blocks.size(); i++) {
+    desc[i].in_off = blocks[i].in_off;
+    desc[i].in_len = blocks[i].in_len;
+    desc[i].out_off = (uint32_t)total;
+    desc[i].isize = blocks[i].isize;
+    total += blocks[i].isize;
+  }
+  return total;
+}
+
 // inflate + CRC of BGZF blocks whose compressed bytes are at d_comp (device): text to d_text.  desc/crc/status are
 // device arrays of n_blocks entries.
 // w16: the 16 KiB-window kernel (two batches of blocks resident at once), for text whose lines are well under 16 KB
@@ -760,23 +931,12 @@ static bool launch_inflate(int n_cu, const uint8_t *d_comp, const BgzfDesc *d_de
                            uint32_t *d_status, uint32_t *d_crc, hipStream_t st, bool w16) {
   const CrcTabs *crc_tabs = crc_tabs_on_device();
   if (!crc_tabs) return false;
-  static const int per_cu32 = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate, kInfThreads, 0) != hipSuccess || n < 1) n = 4;
-    return n;
-  }();
-  static const int per_cu16 = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate_w16, kInfThreads, 0) != hipSuccess || n < 1) n = 7;
-    if (getenv("BVCF_DEBUG")) fprintf(stderr, "[bvcf debug] k_inflate_w16: %d workgroups per CU\n", n);
-    return n;
-  }();
-  static const int per_cu4 = [] {
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate_w4, kInfThreads, 0) != hipSuccess || n < 1) n = 12;
-    if (getenv("BVCF_DEBUG")) fprintf(stderr, "[bvcf debug] k_inflate_w4: %d workgroups per CU\n", n);
-    return n;
-  }();
+  static const int per_cu32 = wgs_per_cu(k_inflate, kInfThreads, 0, 4);
+  static const int per_cu16 = wgs_per_cu(k_inflate_w16, kInfThreads, 0, 7);
+  static const int per_cu4 = wgs_per_cu(k_inflate_w4, kInfThreads, 0, 12);
+  static const bool said = getenv("BVCF_DEBUG") && fprintf(stderr, "[bvcf debug] k_inflate_w16: %d workgroups per CU\n"
+                                                           "[bvcf debug] k_inflate_w4: %d workgroups per CU\n", per_cu16, per_cu4);
+  (void)said;
   // The 4 KiB window is the default: the decoder is a serial chain of ~250 instructions per symbol, so what counts is
   // how many blocks a SIMD interleaves -- 15 waves per CU against 7 (16 KiB) and 4 (32 KiB): 117 / 80 / 64 GB/s of text
   // on configs[2] rows, although most of its matches (a line repeats the one before it, 10 KB back) are then read back
@@ -1043,7 +1203,7 @@ DeflateRun *deflate_open(int device, size_t max_text, std::string *err) {
   if ((e = hipSetDevice(device)) != hipSuccess) return fail("hipSetDevice", e);
   if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail("hipGetDeviceProperties", e);
   r->n_cu = prop.multiProcessorCount;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_deflate, kDefThreads, 0) != hipSuccess || per_cu < 1) per_cu = 2;
+  per_cu = wgs_per_cu(k_deflate, kDefThreads, 0, 2);
   // (a workgroup owns a scratch row of a piece's match words: the grid is what is resident, the pieces loop over it)
   r->grid = (int)std::min<uint64_t>((uint64_t)r->n_cu * (uint64_t)per_cu, r->max_pieces);
   if ((e = r->st.create(hipStreamNonBlocking)) != hipSuccess) return fail("hipStreamCreate", e);
@@ -1175,37 +1335,122 @@ void bvcf_destroy(bvcf_ctx *c) {
   delete c;  // (the ctx's own buffers, ev_pr_fold and scan_stream)
 }
 
+}  // extern "C"
+
+namespace {
+
+// fn(slot) for every slot of the ctx, side by side: pinning is most of what creating a ctx costs, and the runtime pins from
+// several threads at once.  HIP_TRY's message of a thread goes to its own string (g_err_sink); the first failure is the ctx's
+template <class F>
+int for_slots_side_by_side(bvcf_ctx *c, F fn) {
+  const size_t n = c->slots.size();
+  std::vector<int> rcs(n, BVCF_OK);
+  std::vector<std::string> errs(n);
+  std::vector<std::thread> th;
+  for (size_t k = 0; k < n; k++)
+    th.emplace_back([&, k]() {
+      g_err_sink = &errs[k];
+      rcs[k] = hipSetDevice(c->device) == hipSuccess ? fn(c->slots[k]) : BVCF_E_HIP;
+      if (rcs[k] && errs[k].empty()) errs[k] = "hipSetDevice failed";
+    });
+  for (auto &t : th) t.join();
+  for (size_t k = 0; k < n; k++)
+    if (rcs[k]) {
+      c->err = errs[k];
+      return rcs[k];
+    }
+  return BVCF_OK;
+}
+
+// stage 2 of bvcf_create: the device, and the grids its occupancy gives the chain's kernels
+int open_device(bvcf_ctx *c) {
+  hipDeviceProp_t prop;
+  if (hipSetDevice(c->device) != hipSuccess) {
+    c->err = "hipSetDevice failed";
+    return BVCF_E_HIP;
+  }
+  if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
+    c->err = "hipGetDeviceProperties failed";
+    return BVCF_E_HIP;
+  }
+  c->n_cu = prop.multiProcessorCount;
+  c->gt_grid = c->n_cu * wgs_per_cu(k_gt, kWgThreads, 0, 4);
+  c->gt_filter_grid = c->n_cu * wgs_per_cu(k_gt_filter, kWgThreads, 0, 4);
+  c->gt_subset_grid = c->n_cu * wgs_per_cu(k_gt_subset, kWgThreads, 0, 4);
+  int per_cu = wgs_per_cu(k_stream, kWgThreads, 0, 3);
+  // Two waves per SIMD run the scan as fast as three (it is bound by VALU issue).  With more than one batch in
+  // flight the third wave's registers are better spent on the previous batch's k_head_lean / k_gt / k_finish, which
+  // then run beside this kernel instead of waiting for its workgroups to finish (+7 % on the two-slot benchmark).
+  if (c->p.n_slots > 1 && per_cu > 2) per_cu = 2;
+#ifdef BVCF_EXPERIMENTS
+  const int stream_wgs = env_int("BVCF_STREAM_WGS", 0);  // experiment: workgroups per CU, up to the occupancy limit
+  if (stream_wgs >= 1 && stream_wgs <= 4) per_cu = stream_wgs;
+  // (round 5, measured and not adopted: every batch's one-pass kernel on one stream of the ctx; LDS asked for with k_stream
+  // to cap its workgroups per CU over all batches -- profiles/r05_c4_in_flight_what_the_ten_percent_are.txt)
+  if (c->p.n_slots > 1 && env_int("BVCF_SCAN_STREAM", 0) == 1 && c->scan_stream.create(hipStreamNonBlocking) != hipSuccess) {
+    c->err = "hipStreamCreate failed";
+    return BVCF_E_HIP;
+  }
+  c->stream_lds_pad = (uint32_t)env_int("BVCF_EXP_STREAM_LDS", 0);
+#endif
+  c->stream_grid = c->n_cu * per_cu;
+  per_cu = std::min(wgs_per_cu(k_stream_gen, kWgThreads, gen_lds_bytes(c->n_samples), 2), 6);  // (7 fit a cohort of a few thousand samples; 6 measured best)
+#ifdef BVCF_EXPERIMENTS
+  const int gen_wgs = env_int("BVCF_GEN_WGS", 0);  // experiment: workgroups per CU
+  if (gen_wgs >= 1 && gen_wgs <= 8) per_cu = std::min(per_cu, gen_wgs);
+#endif
+  c->gen_grid = c->n_cu * per_cu;
+  per_cu = wgs_per_cu(k_sites2, kS1Threads, 0, 2);
+#ifdef BVCF_EXPERIMENTS
+  c->sites_grid = c->n_cu * wgs_per_cu(k_sites, kSitesThreads, 0, 3);
+  const int s1_wgs = env_int("BVCF_SITES1_WGS", 0), s2_wgs = env_int("BVCF_S2_WGS", 0);  // experiments: workgroups per CU
+  if (s1_wgs >= 1 && s1_wgs <= 8) per_cu = std::min(per_cu, s1_wgs);
+  if (s2_wgs >= 1 && s2_wgs <= 4) per_cu = std::min(per_cu, s2_wgs);
+#endif
+  c->sites1_grid = c->n_cu * per_cu;
+  // the streaming kernel gives every wave its own range of class-map slots (two of them slack): room for that
+  if (!c->p.cmap_bytes) {
+    c->max_cmap += (uint64_t)c->stream_grid * kWavesPerWg * 2u * c->cmap_stride + c->max_lines / 16 * (uint64_t)c->cmap_stride;
+    c->max_cmap = std::min<uint64_t>((c->max_cmap + 63) & ~63ull, 0xFFFFFF00ull);
+  }
+  return BVCF_OK;
+}
+
+// stage 3: the FILTER table and the subset's rank table go up, and the slots get their buffers
+int upload_and_allocate(bvcf_ctx *c, const CtxPlan &plan) {
+  if (c->d_filters.alloc(1) != hipSuccess ||
+      hipMemcpy(c->d_filters, &plan.ft, sizeof plan.ft, hipMemcpyHostToDevice) != hipSuccess) {
+    c->err = "filter table upload failed";
+    return BVCF_E_HIP;
+  }
+  c->n_rank_words = (uint32_t)plan.rank.size();
+  if (c->n_rank_words && (c->d_rank.alloc(plan.rank.size()) != hipSuccess ||
+                          hipMemcpy(c->d_rank, plan.rank.data(), plan.rank.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess)) {
+    c->err = "sample_keep: rank table upload failed";
+    return BVCF_E_HIP;
+  }
+  c->slots.resize(c->p.n_slots);
+  return for_slots_side_by_side(c, [c](Slot &s) { return alloc_slot(c, s); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int bvcf_plan_ctx(const bvcf_params *p, bvcf_ctx_plan *out) {
+  if (!p || !out) return BVCF_E_ARG;
+  CtxPlan plan;
+  const int rc = plan_ctx(p, &plan, &g_create_err);
+  if (rc == BVCF_OK) *out = plan;
+  return rc;
+}
+
 int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
   if (!out || !p) return BVCF_E_ARG;
   *out = nullptr;
-  // (abi_version BVCF_ABI_VERSION: the caller's struct ends behind min_dp, and nothing behind it is read)
-  const bool has_keep = p->abi_version == BVCF_ABI_VERSION_SUBSET;
-  if ((p->abi_version != BVCF_ABI_VERSION && !has_keep) || p->n_header_fields < 1 || p->eol_chars < 1 || p->eol_chars > 2) {
-    g_create_err = "bad bvcf_params";
-    return BVCF_E_ARG;
-  }
-  if (p->min_gq > BVCF_MAX_THRESHOLD || p->min_dp > BVCF_MAX_THRESHOLD) {
-    g_create_err = "bad bvcf_params: min_gq / min_dp above 999999999";
-    return BVCF_E_ARG;
-  }
-  // bvcf_params.sample_keep: one {keep bits, kept before} entry per 32 samples; bits from n_samples on are ignored
-  const uint32_t ns_full = p->n_header_fields > 9 ? p->n_header_fields - 9 : 0;
-  std::vector<uint2> rank;
-  uint32_t n_keep = ns_full;
-  if (has_keep && p->sample_keep && ns_full) {
-    n_keep = 0;
-    rank.resize((ns_full + 31u) / 32u);
-    for (uint32_t w = 0; w < rank.size(); w++) {
-      const uint32_t left = ns_full - 32u * w;
-      const uint32_t bits = p->sample_keep[w] & (left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u);
-      rank[w] = make_uint2(bits, n_keep);
-      n_keep += (uint32_t)__builtin_popcount(bits);
-    }
-    if (!n_keep) {
-      g_create_err = "bad bvcf_params: sample_keep keeps no sample";
-      return BVCF_E_ARG;
-    }
-  }
+  CtxPlan plan;
+  int rc = plan_ctx(p, &plan, &g_create_err);
+  if (rc) return rc;
   int n_dev = 0;
   if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || p->device < 0 || p->device >= n_dev) {
     // there is deliberately no CPU fallback
@@ -1213,243 +1458,15 @@ int bvcf_create(bvcf_ctx **out, const bvcf_params *p) {
     return BVCF_E_NODEV;
   }
   bvcf_ctx *c = new bvcf_ctx();
-  memcpy(&c->p, p, offsetof(bvcf_params, sample_keep));  // (sample_keep, the caller's array, is in the rank table above)
+  *static_cast<bvcf_ctx_plan *>(c) = plan;
+  c->p = plan.p;
   c->device = p->device;
-  if (!c->p.max_batch_bytes) c->p.max_batch_bytes = 64ull << 20;
-  if (c->p.max_batch_bytes >= kMaxBlockBytes) c->p.max_batch_bytes = kMaxBlockBytes - 1;
-  if (!c->p.n_slots) c->p.n_slots = 3;  // (measured better than 2 or equal on every input shape: profiles/r05_blocks_in_flight_2_vs_3_all_profiles.txt)
-  if (!c->p.eol_byte) c->p.eol_byte = '\n';
-  c->n_samples_full = ns_full;
-  c->n_samples = n_keep;  // (== ns_full without a mask)
-  c->gt_subset = !rank.empty();
-  c->cmap_stride = ((c->n_samples + 3) / 4 + 15) & ~15u;
-  c->dosage_stride = p->want_dosage && c->n_samples ? ((c->n_samples + 15) & ~15u) : 0u;
-  const uint64_t min_line = std::max<uint64_t>(48, 2ull * p->n_header_fields);
-  // (the slack is for short lines -- comments, junk -- between the records; every listed line owns a class-map slot
-  // on the census path, so for very wide cohorts the slack is what 32 MiB of maps can hold: a batch that needs more
-  // grows the reservation, BVCF_E_CAPACITY)
-  const uint64_t slack = std::min<uint64_t>(4096, std::max<uint64_t>(64, (32ull << 20) / std::max<uint32_t>(c->cmap_stride, 1u)));
-  c->max_lines = p->max_lines ? p->max_lines : c->p.max_batch_bytes / min_line + slack;
-  c->max_alleles = p->max_alleles ? p->max_alleles : 2 * c->max_lines + 1024;
-  if (c->max_alleles < c->max_lines + 64) c->max_alleles = c->max_lines + 64;  // slot i belongs to line i
-  c->max_cmap = p->cmap_bytes ? p->cmap_bytes : (c->max_lines + c->max_lines / 2) * (uint64_t)c->cmap_stride + (1ull << 20);
-  if (c->max_cmap > 0xFFFFFF00ull) c->max_cmap = 0xFFFFFF00ull;  // cmap_off is 32-bit
-  if (c->max_cmap < 4096) c->max_cmap = 4096;  // (k_gt's prefetch reads a raw-list area's worth from the start of the arena)
-  c->max_cmap = (c->max_cmap + 63) & ~63ull;
-  // streaming path: lines are found by the genotype scan itself.  Its tile-local entry quota is
-  // bounded because a line that passes the field count is at least n_header - 1 bytes long; for
-  // narrow files the quota would dwarf the text, so they stay on the census path unless asked.
-  c->tile_bytes = 64u << 10;  // (8-64 KiB measure alike now that the runs are balanced)
-  if (const char *e = getenv("BVCF_TILE_KB")) {
-    const unsigned kb = (unsigned)atoi(e);
-    if (kb >= 4 && kb <= 1024) c->tile_bytes = kb << 10;
-  }
-  uint32_t path = p->path;
-  if (const char *e = getenv("BVCF_PATH")) path = (uint32_t)atoi(e);  // test / tuning override
-  c->gt_filter = c->n_samples > 0 && (p->min_gq != 0 || p->min_dp != 0);
-  if (c->gt_filter || c->gt_subset) path = 1;  // the masked scan and the subset scan live on the census path only
-  // From kWideSamples samples up a line is hundreds of kilobytes and a batch holds too few of them to fill the GPU
-  // with one wave per line: the census path then splits the regular scan of a line over several waves, and is
-  // what `choose` picks.
-  const bool many_samples = c->n_samples_full >= kWideSamples;
-  c->fused = c->n_samples > 0 && (path == 2 || path == 3 || (path == 0 && p->n_header_fields >= 256 && !many_samples));
-  c->wide = !c->fused && many_samples;
-  if (const char *e = getenv("BVCF_GEN_STREAM")) c->gen_policy = atoi(e) != 0 ? 1 : 0;
-  if (const char *e = getenv("BVCF_HEAD_FAST")) c->head_fast = atoi(e) != 0;  // test / tuning override
-  if (!c->fused || c->n_samples > 4u * kStageBytes) c->gen_policy = 0;  // (a line's dense class map is staged in LDS)
-  c->gen_mode = c->gen_policy == 1;
-  if (path == 3 && c->gen_policy < 0) {  // the caller has seen a line: its sample fields carry more than GT
-    c->gen_mode = true;
-    c->shape_seen = true;
-  }
-  if (const char *e = getenv("BVCF_WIDE")) c->wide = !c->fused && c->n_samples > 0 && atoi(e) != 0;  // test / tuning override
-  if (c->gt_filter || c->gt_subset) c->wide = false;  // k_gt_filter, k_gt_subset: one wave per (line, ALT index) at any sample count
-  if (const char *e = getenv("BVCF_WIDE_WIN")) {  // test / tuning: window of the split general scan, bytes
-    const long v = atol(e);
-    if (v >= 64 && v <= (64l << 20)) c->win_bytes = (uint32_t)v;
-  }
-  c->tile_quota = c->tile_bytes / (p->n_header_fields - 1 + p->eol_chars) + 2;
-  auto fail = [&](int rc) {
+  rc = open_device(c);
+  if (rc == BVCF_OK) rc = upload_and_allocate(c, plan);
+  if (rc) {
     g_create_err = c->err;
     bvcf_destroy(c);
     return rc;
-  };
-  if (hipSetDevice(c->device) != hipSuccess) {
-    c->err = "hipSetDevice failed";
-    return fail(BVCF_E_HIP);
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) {
-    c->err = "hipGetDeviceProperties failed";
-    return fail(BVCF_E_HIP);
-  }
-  c->n_cu = prop.multiProcessorCount;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt, kWgThreads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 4;
-  c->gt_grid = c->n_cu * per_cu;
-  per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt_filter, kWgThreads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 4;
-  c->gt_filter_grid = c->n_cu * per_cu;
-  per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gt_subset, kWgThreads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 4;
-  c->gt_subset_grid = c->n_cu * per_cu;
-  per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream, kWgThreads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 3;
-  // Two waves per SIMD run the scan as fast as three (it is bound by VALU issue).  With more than one batch in
-  // flight the third wave's registers are better spent on the previous batch's k_head_lean / k_gt / k_finish, which
-  // then run beside this kernel instead of waiting for its workgroups to finish (+7 % on the two-slot benchmark).
-  if (c->p.n_slots > 1 && per_cu > 2) per_cu = 2;
-#ifdef BVCF_EXPERIMENTS
-  if (const char *e = getenv("BVCF_STREAM_WGS")) {  // experiment: workgroups per CU, up to the occupancy limit
-    const int w = atoi(e);
-    if (w >= 1 && w <= 4) per_cu = w;
-  }
-#endif
-  c->stream_grid = c->n_cu * per_cu;
-#ifdef BVCF_EXPERIMENTS
-  // (round 5, measured and not adopted: every batch's one-pass kernel on one stream of the ctx; LDS asked for with k_stream
-  // to cap its workgroups per CU over all batches -- profiles/r05_c4_in_flight_what_the_ten_percent_are.txt)
-  if (c->p.n_slots > 1 && getenv("BVCF_SCAN_STREAM") && atoi(getenv("BVCF_SCAN_STREAM")) == 1 &&
-      c->scan_stream.create(hipStreamNonBlocking) != hipSuccess) {
-    c->err = "hipStreamCreate failed";
-    return fail(BVCF_E_HIP);
-  }
-  if (const char *e = getenv("BVCF_EXP_STREAM_LDS")) c->stream_lds_pad = (uint32_t)atoi(e);
-#endif
-  per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_stream_gen, kWgThreads, gen_lds_bytes(c->n_samples)) != hipSuccess || per_cu < 1)
-    per_cu = 2;
-  per_cu = std::min(per_cu, 6);  // (7 fit a cohort of a few thousand samples; 6 measured best)
-#ifdef BVCF_EXPERIMENTS
-  if (const char *e = getenv("BVCF_GEN_WGS")) {  // experiment: workgroups per CU
-    const int w = atoi(e);
-    if (w >= 1 && w <= 8) per_cu = std::min(per_cu, w);
-  }
-#endif
-  c->gen_grid = c->n_cu * per_cu;
-  // sites-only input takes k_sites2 behind its census (BVCF_SITES=0: the census chain with k_head, for A/B and parity
-  // tests; builds with -DBVCF_EXPERIMENTS also know 1: k_sites, round 2's kernel, and 3: k_sites1, no census, the line
-  // numbers by look-back -- both slower, kept out of the product library)
-  c->sites = c->n_samples == 0;
-  c->sites2 = c->sites;
-  if (const char *e = getenv("BVCF_SITES")) {
-    const int m = atoi(e);
-#ifdef BVCF_EXPERIMENTS
-    c->sites = c->sites && m != 0;
-    c->sites2 = c->sites && m == 2;
-    c->sites1 = c->sites && m == 3;
-#else
-    c->sites = c->sites2 = c->sites && m != 0;
-#endif
-  }
-  if (const char *e = getenv("BVCF_S2_CENSUS")) c->sites2_tile_census = strcmp(e, "chunk") != 0;  // (A/B and parity tests)
-  c->packed = c->sites2 && p->packed_sites != 0;
-  c->render = c->packed && p->render_sites != 0;
-  per_cu = 0;
-#ifdef BVCF_EXPERIMENTS
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sites, kSitesThreads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 3;
-  c->sites_grid = c->n_cu * per_cu;
-  per_cu = 0;
-#endif
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sites2, kS1Threads, 0) != hipSuccess || per_cu < 1)
-    per_cu = 2;
-#ifdef BVCF_EXPERIMENTS
-  if (const char *e = getenv("BVCF_SITES1_WGS")) {  // experiment: workgroups per CU
-    const int w = atoi(e);
-    if (w >= 1 && w <= 8) per_cu = std::min(per_cu, w);
-  }
-  if (const char *e = getenv("BVCF_S2_WGS")) {  // experiment: workgroups per CU
-    const int w = atoi(e);
-    if (w >= 1 && w <= 4) per_cu = std::min(per_cu, w);
-  }
-#endif
-  c->sites1_grid = c->n_cu * per_cu;
-  // per-sample counts: a wave per (stripe of 1 024 samples, run of dense rows); the runs' partial tables are held to 16 MiB
-  c->ss_on = p->want_sample_stats != 0 && c->n_samples > 0;
-  if (c->ss_on) {
-    c->ss_ns_pad = 4u * c->cmap_stride;
-    c->ss_stripes = (c->ss_ns_pad + kSsStripeSamples - 1u) / kSsStripeSamples;
-    c->ss_max_runs = (uint32_t)std::min<uint64_t>(4096, std::max<uint64_t>(1, (16ull << 20) / (4ull * kSsCols * c->ss_ns_pad)));
-  }
-  // the streaming kernel gives every wave its own range of class-map slots (two of them slack): room for that
-  if (!p->cmap_bytes) {
-    c->max_cmap += (uint64_t)c->stream_grid * kWavesPerWg * 2u * c->cmap_stride + c->max_lines / 16 * (uint64_t)c->cmap_stride;
-    c->max_cmap = std::min<uint64_t>((c->max_cmap + 63) & ~63ull, 0xFFFFFF00ull);
-  }
-
-  FilterTable ft;
-  memset(&ft, 0, sizeof ft);
-  uint32_t used = 0;
-  if (fill_filter(p->allow_filter, true, &ft.allow_nil, &ft.allow_n, ft.allow_off, ft.allow_len, ft.text, &used) ||
-      fill_filter(p->exclude_filter, false, &ft.deny_nil, &ft.deny_n, ft.deny_off, ft.deny_len, ft.text, &used)) {
-    c->err = "too many / too long FILTER values (32 values, 2048 bytes)";
-    return fail(BVCF_E_ARG);
-  }
-  // k_sites1 tests FILTER values of up to four bytes as dwords: possible when nothing is excluded and the allow list is
-  // up to four values of one to four bytes (the default "PASS,." is), or allows everything
-  if (ft.deny_nil) {
-    if (ft.allow_nil) {
-      c->s1_fmode = 2;
-    } else if (ft.allow_n <= 4) {
-      c->s1_fmode = 1;
-      for (uint32_t i = 0; i < ft.allow_n; i++) {
-        const uint32_t l = ft.allow_len[i];
-        if (l == 0 || l > 4) {
-          c->s1_fmode = 0;
-          break;
-        }
-        uint32_t k = 0;
-        for (uint32_t q = 0; q < l; q++) k |= (uint32_t)ft.text[ft.allow_off[i] + q] << (8 * q);
-        c->s1_fkey[i] = k;
-        c->s1_flen[i] = l;
-      }
-      if (!c->s1_fmode)
-        for (int i = 0; i < 4; i++) c->s1_flen[i] = 0;
-    }
-  }
-  if (c->d_filters.alloc(1) != hipSuccess ||
-      hipMemcpy(c->d_filters, &ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess) {
-    c->err = "filter table upload failed";
-    return fail(BVCF_E_HIP);
-  }
-  if (c->gt_subset) {
-    c->n_rank_words = (uint32_t)rank.size();
-    if (c->d_rank.alloc(rank.size()) != hipSuccess ||
-        hipMemcpy(c->d_rank, rank.data(), rank.size() * sizeof(uint2), hipMemcpyHostToDevice) != hipSuccess) {
-      c->err = "sample_keep: rank table upload failed";
-      return fail(BVCF_E_HIP);
-    }
-  }
-  c->slots.resize(c->p.n_slots);
-  {
-    // the slots' buffers side by side: pinning the result arrays is most of what creating a ctx costs
-    std::vector<int> rcs(c->slots.size(), BVCF_OK);
-    std::vector<std::string> errs(c->slots.size());
-    std::vector<std::thread> th;
-    for (size_t i = 1; i < c->slots.size(); i++)
-      th.emplace_back([c, i, &rcs, &errs]() {
-        g_err_sink = &errs[i];
-        if (hipSetDevice(c->device) != hipSuccess) {
-          rcs[i] = BVCF_E_HIP;
-          errs[i] = "hipSetDevice failed";
-          return;
-        }
-        rcs[i] = alloc_slot(c, c->slots[i]);
-      });
-    g_err_sink = &errs[0];
-    rcs[0] = alloc_slot(c, c->slots[0]);
-    g_err_sink = nullptr;
-    for (auto &t : th) t.join();
-    for (size_t i = 0; i < rcs.size(); i++)
-      if (rcs[i]) {
-        c->err = errs[i];
-        return fail(rcs[i]);
-      }
   }
   *out = c;
   return BVCF_OK;
@@ -1521,25 +1538,8 @@ int bvcf_set_row_format(bvcf_ctx *c, const char *empty_field, int keep_pos, int 
   c->row_keep_id = keep_id != 0;
   c->row_keep_info = keep_info != 0;
   c->row_fmt_set = true;
-  // (now, while the caller is still setting up, not inside its first submits; the slots side by side: pinning is what
-  // takes the time, and the runtime pins from several threads at once)
-  std::vector<int> rcs(c->slots.size(), BVCF_OK);
-  std::vector<std::string> errs(c->slots.size());  // (HIP_TRY's message of a thread goes to its own string: g_err_sink)
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < c->slots.size(); k++)
-    th.emplace_back([c, k, &rcs, &errs]() {
-      g_err_sink = &errs[k];
-      hipSetDevice(c->device);
-      rcs[k] = ensure_render_buffers(c, c->slots[k]);
-      g_err_sink = nullptr;
-    });
-  for (auto &t : th) t.join();
-  for (size_t k = 0; k < rcs.size(); k++)
-    if (rcs[k]) {
-      c->err = errs[k];
-      return rcs[k];
-    }
-  return BVCF_OK;
+  // (now, while the caller is still setting up, not inside its first submits)
+  return for_slots_side_by_side(c, [c](Slot &s) { return ensure_render_buffers(c, s); });
 }
 
 int bvcf_reserve(bvcf_ctx *c, uint64_t lines, uint64_t alleles, uint64_t cmap_bytes) {
@@ -1551,7 +1551,7 @@ int bvcf_reserve(bvcf_ctx *c, uint64_t lines, uint64_t alleles, uint64_t cmap_by
   if (lines > 0xFFFFFFF0ull || alleles > 0xFFFFFFF0ull) return BVCF_E_ARG;
   c->max_lines = std::max<uint64_t>(c->max_lines, lines);
   c->max_alleles = std::max<uint64_t>(std::max<uint64_t>(c->max_alleles, alleles), c->max_lines + 64);
-  if (c->sites1 || c->packed)
+  if (extras_at_cap(c))
     c->max_alleles = std::min<uint64_t>(std::max<uint64_t>(c->max_alleles, c->max_lines + c->need_extras + c->need_extras / 4 + 64), 0xFFFFFFF0ull);
   c->max_cmap = std::min<uint64_t>(std::max<uint64_t>(c->max_cmap, (cmap_bytes + 63) & ~63ull), 0xFFFFFF00ull);
   HIP_TRY(c, hipSetDevice(c->device));
@@ -1567,7 +1567,7 @@ int bvcf_reserve(bvcf_ctx *c, uint64_t lines, uint64_t alleles, uint64_t cmap_by
 // k_gt).  Only a hint -- either kernel handles every line.
 static void peek_line_shape(bvcf_ctx *c, const uint8_t *block, size_t nbytes) {
   c->shape_seen = true;
-  if (c->gen_policy >= 0 || !c->fused || !c->n_samples) return;
+  if (c->gen_policy >= 0 || !is_stream(c) || !c->n_samples) return;
   const uint8_t eol = (uint8_t)c->p.eol_byte;
   size_t ls = 0;
   for (int tries = 0; tries < 8 && ls < nbytes; tries++) {
@@ -1598,48 +1598,43 @@ int bvcf_submit_device(bvcf_ctx *c, const void *dblock, size_t nbytes, uint64_t 
   return submit_common(c, nullptr, dblock, nbytes, batch_seq);
 }
 
-int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_own, int flags, uint32_t first_off,
-                     uint64_t batch_seq) {
-  if (!c || !comp || !n_comp || n_own > n_comp) return BVCF_E_ARG;
-  const bool skip_first_line = (flags & BVCF_BGZF_SKIP_FIRST_LINE) != 0;
-  if (c->in_flight == c->slots.size()) {
-    c->err = "all slots in flight";
-    return BVCF_E_BUSY;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  // chains of older bgzf batches whose cut points have arrived go first (keeps the device busy between collects)
-  for (size_t k = 0, i = c->tail; k < c->in_flight; k++, i = (i + 1) % c->slots.size()) {
-    const int rc = launch_after_cuts(c, c->slots[i], false);
-    if (rc) return rc;
-  }
-  std::vector<bvcf_bgzf::Block> blocks;
-  const long used = bvcf_bgzf::scan(comp, n_comp, &blocks);
-  if (used < 0 || (size_t)used != n_comp || blocks.empty()) {
+// the pinned host copy of a BGZF batch's text (whole, its line heads or its cut lines): room for `want` bytes
+static int grow_text(bvcf_ctx *c, Slot &s, uint64_t want) {
+  if (s.h_text.alloc(want) == hipSuccess && s.h_text) return BVCF_OK;
+  c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
+  return BVCF_E_NOMEM;
+}
+
+// the blocks of a compressed batch: whole BGZF blocks, n_own bytes of them the batch's own, their text within a batch's size
+static int check_bgzf_blocks(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_own, std::vector<bvcf_bgzf::Block> *blocks,
+                             uint64_t *total, uint64_t *own) {
+  const long used = bvcf_bgzf::scan(comp, n_comp, blocks);
+  if (used < 0 || (size_t)used != n_comp || blocks->empty()) {
     c->err = "bvcf_submit_bgzf: not whole BGZF blocks";
     return BVCF_E_ARG;
   }
-  uint64_t total = 0, own = 0, own_bytes = 0;
-  for (const auto &b : blocks) {
+  uint64_t own_bytes = 0;
+  *total = *own = 0;
+  for (const auto &b : *blocks) {
     if (own_bytes < n_own) {
       own_bytes += b.total;
-      own += b.isize;
+      *own += b.isize;
     }
-    total += b.isize;
+    *total += b.isize;
   }
   if (own_bytes != n_own) {
     c->err = "bvcf_submit_bgzf: n_own does not fall on a block boundary";
     return BVCF_E_ARG;
   }
-  if (total > c->p.max_batch_bytes || total >= kMaxBlockBytes || n_comp >= kMaxBlockBytes) {
+  if (*total > c->p.max_batch_bytes || *total >= kMaxBlockBytes || n_comp >= kMaxBlockBytes) {
     c->err = "bgzf batch inflates to more than max_batch_bytes";
     return BVCF_E_TOO_BIG;
   }
-  if (!skip_first_line && first_off > total) return BVCF_E_ARG;
-  Slot &s = c->slots[c->head];
-  int rc = alloc_results(c, s);
-  if (rc) return rc;
-  // ---- buffers of the compressed path, on first use / growth
-  const size_t nb = blocks.size();
+  return BVCF_OK;
+}
+
+// the buffers of the compressed path, on first use / growth
+static int ensure_bgzf_buffers(bvcf_ctx *c, Slot &s, size_t n_comp, size_t nb) {
   if (!s.ev_cut) HIP_TRY(c, s.ev_cut.create(hipEventDisableTiming));
   if (!s.h_text) {
     // the host copies of the text, for every slot at once and side by side (pinning 64 MiB takes 13-25 ms).  With
@@ -1651,16 +1646,14 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
                                        : (c->render ? c->p.max_batch_bytes / 8 + (1u << 20) : c->p.max_batch_bytes + BVCF_DEVICE_PAD);
     std::vector<std::thread> th;
     for (auto &q : c->slots)
-      if (!q.h_text)
+      if (&q != &s && !q.h_text)
         th.emplace_back([c, &q, want]() {
           hipSetDevice(c->device);
-          (void)q.h_text.alloc(want);  // (checked below, for the slot of this batch)
+          (void)q.h_text.alloc(want);  // (a slot that went without tries again at its own first batch)
         });
+    const int rc = grow_text(c, s, want);
     for (auto &t : th) t.join();
-    if (!s.h_text) {
-      c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
-      return BVCF_E_NOMEM;
-    }
+    if (rc) return rc;
   }
   if (c->n_samples && s.cap_head_lines < c->max_lines) {
     s.cap_head_lines = 0;
@@ -1686,18 +1679,16 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
     HIP_TRY(c, s.h_bgzf.alloc(want * 5));
     s.cap_bgzf_blocks = want;
   }
+  return BVCF_OK;
+}
+
+// the blocks' descriptors, the inflate and the cut points of the batch's text on their way to the host (ev_cut)
+static int launch_bgzf(bvcf_ctx *c, Slot &s, const uint8_t *comp, size_t n_comp, const std::vector<bvcf_bgzf::Block> &blocks,
+                       uint64_t total, uint64_t own, int flags, uint32_t first_off) {
   // descriptors (4 words per block), then the expected CRCs; status[] and crc[] follow on the device
-  BgzfDesc *h_desc = reinterpret_cast<BgzfDesc *>(s.h_bgzf.get());
-  uint32_t *h_crc = s.h_bgzf + 4 * nb;
-  uint64_t out_off = 0;
-  for (size_t i = 0; i < nb; i++) {
-    h_desc[i].in_off = blocks[i].in_off;
-    h_desc[i].in_len = blocks[i].in_len;
-    h_desc[i].out_off = (uint32_t)out_off;
-    h_desc[i].isize = blocks[i].isize;
-    h_crc[i] = blocks[i].crc;
-    out_off += blocks[i].isize;
-  }
+  const size_t nb = blocks.size();
+  fill_descs(blocks, reinterpret_cast<BgzfDesc *>(s.h_bgzf.get()));
+  for (size_t i = 0; i < nb; i++) s.h_bgzf[4 * nb + i] = blocks[i].crc;
   BgzfDesc *d_desc = reinterpret_cast<BgzfDesc *>(s.d_bgzf.get());
   uint32_t *d_want = s.d_bgzf + 4 * nb, *d_status = s.d_bgzf + 5 * nb, *d_crc = s.d_bgzf + 6 * nb;
   HIP_TRY(c, hipMemcpyAsync(s.d_comp, comp, n_comp, hipMemcpyHostToDevice, s.stream));
@@ -1713,7 +1704,7 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
   ca.text = s.d_in;
   ca.total = (uint32_t)total;
   ca.own = (uint32_t)own;
-  ca.skip_first = skip_first_line ? 1u : 0u;
+  ca.skip_first = (flags & BVCF_BGZF_SKIP_FIRST_LINE) ? 1u : 0u;
   ca.at_eof = (flags & BVCF_BGZF_END_OF_STREAM) ? 1u : 0u;
   ca.first_off = first_off;
   ca.eol_byte = c->p.eol_byte;
@@ -1726,6 +1717,32 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipMemcpyAsync(s.h_cuts, s.d_cuts, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
   HIP_TRY(c, hipEventRecord(s.ev_cut, s.stream));
+  return BVCF_OK;
+}
+
+int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_own, int flags, uint32_t first_off,
+                     uint64_t batch_seq) {
+  if (!c || !comp || !n_comp || n_own > n_comp) return BVCF_E_ARG;
+  if (c->in_flight == c->slots.size()) {
+    c->err = "all slots in flight";
+    return BVCF_E_BUSY;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // chains of older bgzf batches whose cut points have arrived go first (keeps the device busy between collects)
+  for (size_t k = 0, i = c->tail; k < c->in_flight; k++, i = (i + 1) % c->slots.size()) {
+    const int rc = launch_after_cuts(c, c->slots[i], false);
+    if (rc) return rc;
+  }
+  std::vector<bvcf_bgzf::Block> blocks;
+  uint64_t total = 0, own = 0;
+  int rc = check_bgzf_blocks(c, comp, n_comp, n_own, &blocks, &total, &own);
+  if (rc) return rc;
+  if (!(flags & BVCF_BGZF_SKIP_FIRST_LINE) && first_off > total) return BVCF_E_ARG;
+  Slot &s = c->slots[c->head];
+  rc = alloc_results(c, s);
+  if (!rc) rc = ensure_bgzf_buffers(c, s, n_comp, blocks.size());
+  if (!rc) rc = launch_bgzf(c, s, comp, n_comp, blocks, total, own, flags, first_off);
+  if (rc) return rc;
   s.await_cuts = true;
   s.is_bgzf = true;
   s.bgzf_rc = 0;
@@ -1739,146 +1756,103 @@ int bvcf_submit_bgzf(bvcf_ctx *c, const uint8_t *comp, size_t n_comp, size_t n_o
   return BVCF_OK;
 }
 
-int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
-  if (!c || !r) return BVCF_E_ARG;
-  if (!c->in_flight) {
-    c->err = "nothing to collect";
-    return BVCF_E_EMPTY;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  Slot &s = c->slots[c->tail];
-  auto release = [&]() {
-    s.busy = false;
-    c->tail = (c->tail + 1) % c->slots.size();
-    c->in_flight--;
-  };
-  const bool was_bgzf = s.is_bgzf;
-  {
-    const int rc2 = launch_after_cuts(c, s, true);
-    if (rc2) {
-      release();
-      return rc2;
-    }
-  }
-  hipError_t e = hipEventSynchronize(s.ev_ctr);
-  if (e != hipSuccess) {
-    c->err = std::string("kernel chain failed: ") + hipGetErrorString(e);
-    release();
-    return BVCF_E_HIP;
-  }
-  if (s.bgzf_rc) {
-    const int rc2 = s.bgzf_rc;
-    c->err = s.bgzf_err ? s.bgzf_err : "bgzf: batch refused";
-    s.bgzf_rc = 0;
-    release();
-    return rc2;
-  }
-  memset(r, 0, sizeof *r);
-  r->batch_seq = s.seq;
-  r->n_samples = c->n_samples;
-  r->cmap_stride = c->cmap_stride;
-  float ms = 0;
-  hipEventElapsedTime(&ms, s.ev_k0, s.ev_k1);
-  r->kernel_ms = ms;
-  const BatchCounters ctr = *s.h_counters;
-  adapt_stream_kernel(c, s.used_gen, ctr);
-  // slot i of alleles[] / tasks / class maps belongs to line i; the counters count the extras, which follow the lines'
-  // slots (k_sites1 does not know the number of lines while it runs: there they follow slot max_lines)
-  const uint64_t extras_at = (c->sites1 || c->packed) ? (uint64_t)s.cap_lines : (uint64_t)ctr.n_lines;
-  const uint64_t n_alleles = extras_at + ctr.n_alleles;
-  const uint64_t n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
-  const uint64_t need_alleles = std::max<uint64_t>(std::max<uint64_t>(n_alleles, ctr.n_errs), n_tasks);
-  // (the maps are made on the device when the caller wants them or the per-sample counts are made from them; they cross
-  // to the host only in the first case)
+// the class maps a batch's counters count, in bytes: handed out one by one on the streaming path, a slot per task elsewhere
+static uint64_t cmap_bytes_of(const bvcf_ctx *c, const BatchCounters &ctr) {
+  return (is_stream(c) ? (uint64_t)ctr.cmap_maps : (uint64_t)ctr.n_lines + ctr.n_tasks) * c->cmap_stride;
+}
+
+// what a batch's counters ask of its slot.  Slot i of alleles[] / tasks / class maps belongs to line i; the counters count
+// the extras, which follow the lines' slots at extras_at
+struct BatchNeeds {
+  uint64_t extras_at, n_alleles, n_tasks, need_alleles;
+  uint64_t cmap_need;  // (the maps are made on the device when the caller wants them or the per-sample / pair counts are made from them)
+  bool fits;
+};
+static BatchNeeds batch_needs(const bvcf_ctx *c, const Slot &s, const BatchCounters &ctr) {
+  BatchNeeds n;
+  n.extras_at = extras_at_cap(c) ? (uint64_t)s.cap_lines : (uint64_t)ctr.n_lines;
+  n.n_alleles = n.extras_at + ctr.n_alleles;
+  n.n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
+  n.need_alleles = std::max<uint64_t>(std::max<uint64_t>(n.n_alleles, ctr.n_errs), n.n_tasks);
   const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on) && c->n_samples;
-  const uint64_t cmap_need = !maps ? 0 : (c->fused ? (uint64_t)ctr.cmap_maps : n_tasks) * c->cmap_stride;
-  const uint64_t cmap_bytes = c->p.want_class_maps ? cmap_need : 0;
-  if (ctr.pad[0]) {
-    c->err = "internal error: streaming tile quota or class-map slot range exceeded";
-    release();
+  n.cmap_need = maps ? cmap_bytes_of(c, ctr) : 0;
+  n.fits = ctr.n_lines <= s.cap_lines && n.need_alleles <= s.cap_alleles && n.cmap_need <= s.cap_cmap;
+  return n;
+}
+
+// what the steps of collect_slot hand on
+struct Collected {
+  BatchCounters ctr;
+  BatchNeeds need;
+  // the packed form: a site record per line, full records (lines[], their first alleles) only for the n_full lines that asked
+  // for them; every line's otherwise
+  uint32_t n_first = 0;
+  uint64_t row_bytes = 0, n_row_cuts = 0, n_ok_sites = 0;  // rendered rows
+  uint64_t cmap_bytes = 0, text_bytes = 0, name_bytes = 0;  // what crosses to the host
+  bool was_bgzf = false, names = false;
+};
+
+// rendered rows: the site records stay on the device; the stream and the list of the lines left to the host come back
+static int collect_rows(bvcf_ctx *c, Slot &s, Collected &k) {
+  k.row_bytes = s.h_rtotals[0];
+  k.n_row_cuts = s.h_rtotals[1];
+  k.n_ok_sites = s.h_rtotals[2];
+  if (k.n_row_cuts > s.cap_row_cuts) {
+    c->err = "internal error: more lines left to the host than the batch has lines";
     return BVCF_E_HIP;
   }
-  if (ctr.n_lines > s.cap_lines || need_alleles > s.cap_alleles || cmap_need > s.cap_cmap) {
-    r->status = BVCF_E_CAPACITY;
-    r->need_lines = ctr.n_lines;
-    r->need_alleles = need_alleles;
-    r->need_cmap_bytes = cmap_need;
-    // (the extras of a packed ctx follow slot cap_lines: once the lines grow, so does where they start -- bvcf_reserve
-    // adds them to the NEW line capacity, need_alleles alone is relative to the old one)
-    c->need_extras = (c->sites1 || c->packed) ? (uint64_t)ctr.n_alleles : 0;
-    c->err = "batch exceeds reserved result capacity";
-    release();
-    return BVCF_E_CAPACITY;
+  if (k.n_row_cuts > s.cap_host_cuts) {
+    const int rc = ensure_render_buffers(c, s, 0, k.n_row_cuts + k.n_row_cuts / 2 + 64);
+    if (rc) return rc;
   }
-  // the packed form: a site record per line, full records (lines[], their first alleles) only for the n_full lines that
-  // asked for them
-  const uint32_t n_first = c->packed ? std::min<uint32_t>(ctr.n_full, ctr.n_lines) : ctr.n_lines;
-  // (rendered rows: the site records stay on the device; the stream and the list of the lines left to the host come back)
-  uint64_t row_bytes = 0, n_row_cuts = 0, n_ok_sites = 0;
-  if (c->render) {
-    row_bytes = s.h_rtotals[0];
-    n_row_cuts = s.h_rtotals[1];
-    n_ok_sites = s.h_rtotals[2];
-    if (n_row_cuts > s.cap_row_cuts) {
-      c->err = "internal error: more lines left to the host than the batch has lines";
-      release();
-      return BVCF_E_HIP;
-    }
-    if (n_row_cuts > s.cap_host_cuts) {
-      const int rc = ensure_render_buffers(c, s, 0, n_row_cuts + n_row_cuts / 2 + 64);
-      if (rc) {
-        release();
-        return rc;
-      }
-    }
-    if (row_bytes > s.d_rows.size()) {
-      // the stream was too small and k_render_rows wrote nothing: grow it and write again (the prefixes stand)
-      const int rc = ensure_render_buffers(c, s, row_bytes + row_bytes / 4 + (1u << 20));
-      if (rc) {
-        release();
-        return rc;
-      }
-      KernelArgs a = make_args(c, s, s.src, s.nbytes);
-      hipLaunchKernelGGL(k_render_rows, dim3((uint32_t)c->n_cu * 8u), dim3(kWgThreads), 0, s.stream, make_render_args(c, s, a));
-      HIP_TRY(c, hipGetLastError());
-    }
-    if (row_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_rows, s.d_rows, row_bytes, hipMemcpyDeviceToHost, s.stream));
-    if (n_row_cuts)
-      HIP_TRY(c, hipMemcpyAsync(s.h_row_cuts, s.d_row_cuts, n_row_cuts * sizeof(bvcf_row_cut), hipMemcpyDeviceToHost, s.stream));
-  } else if (c->packed && ctr.n_lines)
-    HIP_TRY(c, hipMemcpyAsync(s.h_sites, s.d_sites, ctr.n_lines * sizeof(bvcf_site), hipMemcpyDeviceToHost, s.stream));
-  if (c->packed) {
-    // the host's copies hold the n_first full records and, right behind them, the further alleles (on the device those
-    // follow slot cap_lines: rec_first is moved accordingly once they are here); grown when a batch needs more
-    const uint64_t need_recs = std::max<uint64_t>(n_first, ((uint64_t)n_first + ctr.n_alleles + 1) / 2);  // (h_alleles holds 2 * hcap_recs)
-    if (need_recs > s.hcap_recs || ctr.n_errs > s.hcap_errs) {
-      const uint64_t want_recs = std::max<uint64_t>(s.hcap_recs, need_recs + need_recs / 2 + 64);
-      const uint64_t want_errs = std::max<uint64_t>(s.hcap_errs, (uint64_t)ctr.n_errs + ctr.n_errs / 2 + 64);
-      // (released together, before the first of them is pinned anew)
-      s.h_lines.reset();
-      s.h_alleles.reset();
-      s.h_errs.reset();
-      s.hcap_recs = s.hcap_errs = 0;
-      if (s.h_lines.alloc(want_recs) != hipSuccess || s.h_alleles.alloc(2 * want_recs) != hipSuccess ||
-          s.h_errs.alloc(want_errs) != hipSuccess) {
-        c->err = "hipHostMalloc failed (full records of a packed batch)";
-        s.cap_lines = 0;  // (alloc_results starts over at the slot's next use: it allocates all three and sets hcap_*)
-        release();
-        return BVCF_E_NOMEM;
-      }
-      s.hcap_recs = want_recs;
-      s.hcap_errs = want_errs;
-    }
+  if (k.row_bytes > s.d_rows.size()) {
+    // the stream was too small and k_render_rows wrote nothing: grow it and write again (the prefixes stand)
+    const int rc = ensure_render_buffers(c, s, k.row_bytes + k.row_bytes / 4 + (1u << 20));
+    if (rc) return rc;
+    KernelArgs a = make_args(c, s, s.src, s.nbytes);
+    hipLaunchKernelGGL(k_render_rows, dim3((uint32_t)c->n_cu * 8u), dim3(kWgThreads), 0, s.stream, make_render_args(c, s, a));
+    HIP_TRY(c, hipGetLastError());
   }
+  if (k.row_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_rows, s.d_rows, k.row_bytes, hipMemcpyDeviceToHost, s.stream));
+  if (k.n_row_cuts)
+    HIP_TRY(c, hipMemcpyAsync(s.h_row_cuts, s.d_row_cuts, k.n_row_cuts * sizeof(bvcf_row_cut), hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+// packed ctxs: the host's copies hold the n_first full records and, right behind them, the further alleles (on the device
+// those follow slot cap_lines: rec_first is moved accordingly once they are here); grown when a batch needs more
+static int packed_host_room(bvcf_ctx *c, Slot &s, const Collected &k) {
+  const uint64_t need_recs = std::max<uint64_t>(k.n_first, ((uint64_t)k.n_first + k.ctr.n_alleles + 1) / 2);  // (h_alleles holds 2 * hcap_recs)
+  if (need_recs <= s.hcap_recs && k.ctr.n_errs <= s.hcap_errs) return BVCF_OK;
+  const uint64_t want_recs = std::max<uint64_t>(s.hcap_recs, need_recs + need_recs / 2 + 64);
+  const uint64_t want_errs = std::max<uint64_t>(s.hcap_errs, (uint64_t)k.ctr.n_errs + k.ctr.n_errs / 2 + 64);
+  // (released together, before the first of them is pinned anew)
+  s.h_lines.reset();
+  s.h_alleles.reset();
+  s.h_errs.reset();
+  s.hcap_recs = s.hcap_errs = 0;
+  if (s.h_lines.alloc(want_recs) != hipSuccess || s.h_alleles.alloc(2 * want_recs) != hipSuccess ||
+      s.h_errs.alloc(want_errs) != hipSuccess) {
+    c->err = "hipHostMalloc failed (full records of a packed batch)";
+    s.cap_lines = 0;  // (alloc_results starts over at the slot's next use: it allocates all three and sets hcap_*)
+    return BVCF_E_NOMEM;
+  }
+  s.hcap_recs = want_recs;
+  s.hcap_errs = want_errs;
+  return BVCF_OK;
+}
+
+// the batch is in: its per-sample counts join the slot's totals and its pair tables the ctx's (ahead of the copies on the
+// slot's stream)
+static int launch_folds(bvcf_ctx *c, Slot &s) {
   if (c->ss_on && s.d_ss_dense) {
-    // the batch is in: its per-sample counts join the slot's totals (ahead of the copies on the slot's stream)
     const uint32_t n_threads = kSsCols * c->ss_ns_pad;
     hipLaunchKernelGGL(k_ss_fold, dim3((n_threads + kWgThreads - 1) / kWgThreads), dim3(kWgThreads), 0, s.stream,
                        make_ss_args(c, s), c->n_samples);
     HIP_TRY(c, hipGetLastError());
   }
   if (c->pr_on && s.d_pr_bt) {
-    // ... and its pair tables the ctx's totals: one fold after the other, whichever slots' streams they run on
+    // one fold after the other, whichever slots' streams they run on
     if (c->pr_folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->ev_pr_fold, 0));
     const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
     const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
@@ -1887,155 +1861,158 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
     HIP_TRY(c, hipEventRecord(c->ev_pr_fold, s.stream));
     c->pr_folded = true;
   }
+  return BVCF_OK;
+}
+
+// exactly the used parts of the result arrays
+static int copy_records(bvcf_ctx *c, Slot &s, const Collected &k) {
+  const BatchCounters &ctr = k.ctr;
+  const uint64_t extras_at = k.need.extras_at, n_alleles = k.need.n_alleles;
+  const uint32_t n_first = k.n_first;
   if (n_first)
     HIP_TRY(c, hipMemcpyAsync(s.h_lines, s.d_lines, (size_t)n_first * sizeof(bvcf_line), hipMemcpyDeviceToHost, s.stream));
-  if (c->packed) {
+  if (extras_at_cap(c)) {
+    // (the extras behind the n_first first records in the packed form, where they are on the device for k_sites1)
+    bvcf_allele *extras = s.h_alleles + (c->packed ? (uint64_t)n_first : extras_at);
     if (n_first)
       HIP_TRY(c, hipMemcpyAsync(s.h_alleles, s.d_alleles, (size_t)n_first * sizeof(bvcf_allele), hipMemcpyDeviceToHost, s.stream));
     if (ctr.n_alleles)
-      HIP_TRY(c, hipMemcpyAsync(s.h_alleles + n_first, s.d_alleles + extras_at, (size_t)ctr.n_alleles * sizeof(bvcf_allele),
-                                hipMemcpyDeviceToHost, s.stream));
-  } else if (c->sites1) {
-    if (n_first)
-      HIP_TRY(c, hipMemcpyAsync(s.h_alleles, s.d_alleles, (size_t)n_first * sizeof(bvcf_allele), hipMemcpyDeviceToHost, s.stream));
-    if (ctr.n_alleles)
-      HIP_TRY(c, hipMemcpyAsync(s.h_alleles + extras_at, s.d_alleles + extras_at, (size_t)ctr.n_alleles * sizeof(bvcf_allele),
-                                hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(c, hipMemcpyAsync(extras, s.d_alleles + extras_at, (size_t)ctr.n_alleles * sizeof(bvcf_allele), hipMemcpyDeviceToHost, s.stream));
   } else if (n_alleles)
-    HIP_TRY(c, hipMemcpyAsync(s.h_alleles, s.d_alleles, n_alleles * sizeof(bvcf_allele), hipMemcpyDeviceToHost,
-                              s.stream));
+    HIP_TRY(c, hipMemcpyAsync(s.h_alleles, s.d_alleles, n_alleles * sizeof(bvcf_allele), hipMemcpyDeviceToHost, s.stream));
   if (ctr.n_errs)
     HIP_TRY(c, hipMemcpyAsync(s.h_errs, s.d_errs, ctr.n_errs * sizeof(bvcf_err), hipMemcpyDeviceToHost, s.stream));
-  if (cmap_bytes)
-    HIP_TRY(c, hipMemcpyAsync(s.h_cmap, s.d_cmap, cmap_bytes, hipMemcpyDeviceToHost, s.stream));
+  if (k.cmap_bytes)
+    HIP_TRY(c, hipMemcpyAsync(s.h_cmap, s.d_cmap, k.cmap_bytes, hipMemcpyDeviceToHost, s.stream));
   if (c->dosage_stride && n_alleles)
     HIP_TRY(c, hipMemcpyAsync(s.h_dosage, s.d_dosage, n_alleles * c->dosage_stride, hipMemcpyDeviceToHost, s.stream));
-  uint64_t text_bytes = 0;
-  if (was_bgzf && s.heads) {
+  return BVCF_OK;
+}
+
+// a BGZF batch's text for the caller's TSV assembly: the packed line heads, the cut lines, or all of it
+static int copy_text(bvcf_ctx *c, Slot &s, Collected &k) {
+  if (!k.was_bgzf) return BVCF_OK;
+  if (s.heads) {
     // the packed line heads and where each line's is
-    text_bytes = *s.h_head_total;
-    if (text_bytes > c->p.max_batch_bytes) {
+    k.text_bytes = *s.h_head_total;
+    if (k.text_bytes > c->p.max_batch_bytes) {
       c->err = "internal error: line heads larger than the batch";
-      release();
       return BVCF_E_HIP;
     }
-    if (text_bytes > s.h_text.size()) {  // (the caller is done with what this slot returned n_slots collects ago)
-      const uint64_t want = std::min<uint64_t>(text_bytes + text_bytes / 2, c->p.max_batch_bytes + BVCF_DEVICE_PAD);
-      if (s.h_text.alloc(want) != hipSuccess) {
-        c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
-        release();
-        return BVCF_E_NOMEM;
-      }
+    if (k.text_bytes > s.h_text.size()) {  // (the caller is done with what this slot returned n_slots collects ago)
+      const int rc = grow_text(c, s, std::min<uint64_t>(k.text_bytes + k.text_bytes / 2, c->p.max_batch_bytes + BVCF_DEVICE_PAD));
+      if (rc) return rc;
     }
-    if (ctr.n_lines) HIP_TRY(c, hipMemcpyAsync(s.h_head_off, s.d_head_off, ctr.n_lines * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-    if (text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_heads, text_bytes, hipMemcpyDeviceToHost, s.stream));
-  } else if (was_bgzf && c->render && s.cut_text_on && s.h_rtotals[3] <= s.d_cut_text.size() && s.h_rtotals[3] < 0xFFFFFFFFull) {
+    if (k.ctr.n_lines) HIP_TRY(c, hipMemcpyAsync(s.h_head_off, s.d_head_off, k.ctr.n_lines * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    if (k.text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_heads, k.text_bytes, hipMemcpyDeviceToHost, s.stream));
+  } else if (c->render && s.cut_text_on && s.h_rtotals[3] <= s.d_cut_text.size() && s.h_rtotals[3] < 0xFFFFFFFFull) {
     // rendered rows: the host only reads the lines left to it -- their bytes, packed (bvcf_row_cut.text_off), not the
     // batch's whole text
-    text_bytes = s.h_rtotals[3];
-    if (text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_cut_text, text_bytes, hipMemcpyDeviceToHost, s.stream));
-  } else if (was_bgzf && s.nbytes) {
-    text_bytes = s.nbytes;
-    if (text_bytes > s.h_text.size()) {  // (a rendered ctx keeps a small copy buffer: see bvcf_submit_bgzf)
-      if (s.h_text.alloc(c->p.max_batch_bytes + BVCF_DEVICE_PAD) != hipSuccess) {
-        c->err = "hipHostMalloc failed (text copy of a BGZF batch)";
-        release();
-        return BVCF_E_NOMEM;
-      }
+    k.text_bytes = s.h_rtotals[3];
+    if (k.text_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_text, s.d_cut_text, k.text_bytes, hipMemcpyDeviceToHost, s.stream));
+  } else if (s.nbytes) {
+    k.text_bytes = s.nbytes;
+    if (k.text_bytes > s.h_text.size()) {  // (a rendered ctx keeps a small copy buffer: see ensure_bgzf_buffers)
+      const int rc = grow_text(c, s, c->p.max_batch_bytes + BVCF_DEVICE_PAD);
+      if (rc) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(s.h_text, s.src, s.nbytes, hipMemcpyDeviceToHost, s.stream));
   }
-  const bool names = c->names_on && s.d_name_lists;
-  uint64_t name_bytes = 0;
-  if (names && n_alleles) {
-    name_bytes = *s.h_name_total;
-    if (name_bytes >= 0xFFFFFFF0ull) {
-      c->err = "the sample-name lists of one batch pass 4 GiB: submit smaller blocks";
-      release();
-      return BVCF_E_TOO_BIG;
-    }
-    if (name_bytes > s.cap_names) {
-      // the arena was too small and k_name_write wrote nothing: grow it and write again (the offsets stand)
-      const int rc = alloc_name_arena(c, s, name_bytes + name_bytes / 4 + (1u << 20));
-      if (rc) {
-        release();
-        return rc;
-      }
-      KernelArgs a = make_args(c, s, s.src, s.nbytes);
-      hipLaunchKernelGGL(k_name_write, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, make_name_args(c, s));
-    }
-    HIP_TRY(c, hipMemcpyAsync(s.h_name_lists, s.d_name_lists, n_alleles * sizeof(bvcf_names), hipMemcpyDeviceToHost, s.stream));
-    if (name_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_names, s.d_names, name_bytes, hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+// the device-side name lists and their text arena
+static int copy_names(bvcf_ctx *c, Slot &s, Collected &k) {
+  if (!k.names || !k.need.n_alleles) return BVCF_OK;
+  k.name_bytes = *s.h_name_total;
+  if (k.name_bytes >= 0xFFFFFFF0ull) {
+    c->err = "the sample-name lists of one batch pass 4 GiB: submit smaller blocks";
+    return BVCF_E_TOO_BIG;
   }
-  e = hipStreamSynchronize(s.stream);
-  if (e != hipSuccess) {
-    c->err = std::string("result copy failed: ") + hipGetErrorString(e);
-    release();
-    return BVCF_E_HIP;
+  if (k.name_bytes > s.cap_names) {
+    // the arena was too small and k_name_write wrote nothing: grow it and write again (the offsets stand)
+    const int rc = alloc_name_arena(c, s, k.name_bytes + k.name_bytes / 4 + (1u << 20));
+    if (rc) return rc;
+    KernelArgs a = make_args(c, s, s.src, s.nbytes);
+    hipLaunchKernelGGL(k_name_write, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, make_name_args(c, s));
   }
-  // getAlleles' messages were recorded before the field-count verdict was known: a line that
-  // fails linePasses (main.go:537-539) never reaches getAlleles, so its messages are dropped here
-  // (packed form: the verdict of line i is in its site record, or in the full record that one points at)
-  auto verdict_of = [&](uint32_t i) -> uint32_t {
-    if (!c->packed) return s.h_lines[i].status;
-    if (c->render) {
-      // (only lines with full records log anything: found among the cuts, which are in line order)
-      const bvcf_row_cut *lo = s.h_row_cuts, *hi = s.h_row_cuts + n_row_cuts;
-      const bvcf_row_cut *it = std::lower_bound(lo, hi, i, [](const bvcf_row_cut &q, uint32_t v) { return q.line < v; });
-      if (it == hi || it->line != i || it->slot >= n_first) return (uint32_t)BVCF_LINE_FIELDS;
-      return s.h_lines[it->slot].status;
-    }
-    const bvcf_site &st = s.h_sites[i];
-    if (!(st.status & BVCF_SITE_FULL)) return st.status;
-    return st.full_idx < n_first ? s.h_lines[st.full_idx].status : (uint32_t)BVCF_LINE_FIELDS;
-  };
+  HIP_TRY(c, hipMemcpyAsync(s.h_name_lists, s.d_name_lists, k.need.n_alleles * sizeof(bvcf_names), hipMemcpyDeviceToHost, s.stream));
+  if (k.name_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_names, s.d_names, k.name_bytes, hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+// the field-count verdict of line i (packed form: it is in the line's site record, or in the full record that one points at)
+static uint32_t verdict_of(const bvcf_ctx *c, const Slot &s, const Collected &k, uint32_t i) {
+  if (!c->packed) return s.h_lines[i].status;
+  if (c->render) {
+    // (only lines with full records log anything: found among the cuts, which are in line order)
+    const bvcf_row_cut *lo = s.h_row_cuts, *hi = s.h_row_cuts + k.n_row_cuts;
+    const bvcf_row_cut *it = std::lower_bound(lo, hi, i, [](const bvcf_row_cut &q, uint32_t v) { return q.line < v; });
+    if (it == hi || it->line != i || it->slot >= k.n_first) return (uint32_t)BVCF_LINE_FIELDS;
+    return s.h_lines[it->slot].status;
+  }
+  const bvcf_site &st = s.h_sites[i];
+  if (!(st.status & BVCF_SITE_FULL)) return st.status;
+  return st.full_idx < k.n_first ? s.h_lines[st.full_idx].status : (uint32_t)BVCF_LINE_FIELDS;
+}
+
+// getAlleles' messages were recorded before the field-count verdict was known: a line that
+// fails linePasses (main.go:537-539) never reaches getAlleles, so its messages are dropped here; returns how many stay
+static uint32_t filter_errs(const bvcf_ctx *c, Slot &s, const Collected &k) {
   if (c->packed)  // (the further alleles sit right behind the n_first first records here, behind slot cap_lines on the device)
-    for (uint32_t j = 0; j < n_first; j++)
-      if (s.h_lines[j].rec_first >= extras_at) s.h_lines[j].rec_first = s.h_lines[j].rec_first - (uint32_t)extras_at + n_first;
+    for (uint32_t j = 0; j < k.n_first; j++)
+      if (s.h_lines[j].rec_first >= k.need.extras_at)
+        s.h_lines[j].rec_first = s.h_lines[j].rec_first - (uint32_t)k.need.extras_at + k.n_first;
   uint32_t n_errs = 0;
-  for (uint32_t i = 0; i < ctr.n_errs; i++) {
+  for (uint32_t i = 0; i < k.ctr.n_errs; i++) {
     const bvcf_err &er = s.h_errs[i];
-    if (er.line < ctr.n_lines && verdict_of(er.line) != BVCF_LINE_FIELDS) s.h_errs[n_errs++] = er;
+    if (er.line < k.ctr.n_lines && verdict_of(c, s, k, er.line) != BVCF_LINE_FIELDS) s.h_errs[n_errs++] = er;
   }
+  return n_errs;
+}
+
+static void fill_result(const bvcf_ctx *c, const Slot &s, const Collected &k, uint32_t n_errs, bvcf_result *r) {
   r->status = BVCF_OK;
-  r->n_lines = ctr.n_lines;
-  r->n_alleles = c->packed ? n_first + ctr.n_alleles : (uint32_t)n_alleles;
+  r->n_lines = k.ctr.n_lines;
+  r->n_alleles = c->packed ? k.n_first + k.ctr.n_alleles : (uint32_t)k.need.n_alleles;
   r->n_errs = n_errs;
-  r->n_cmap_bytes = cmap_bytes;
-  r->n_lines_seen = ctr.lines_seen;
+  r->n_cmap_bytes = k.cmap_bytes;
+  r->n_lines_seen = k.ctr.lines_seen;
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = ((c->ss_on || c->pr_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap;  // (maps kept on the device only: no host copy)
-  r->dosage = c->dosage_stride ? s.h_dosage : nullptr;
+  r->cmap = ((c->ss_on || c->pr_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
+  r->dosage = c->dosage_stride ? s.h_dosage.get() : nullptr;
   r->dosage_stride = c->dosage_stride;
-  r->text = was_bgzf ? s.h_text : nullptr;
-  r->n_text_bytes = was_bgzf ? text_bytes : 0;
-  r->head_off = (was_bgzf && s.heads) ? s.h_head_off : nullptr;
-  r->sites = (c->packed && !c->render) ? s.h_sites : nullptr;
-  r->n_full_lines = c->packed ? n_first : 0u;
-  r->rows = c->render ? s.h_rows : nullptr;
-  r->n_row_bytes = row_bytes;
-  r->row_cuts = c->render ? s.h_row_cuts : nullptr;
-  r->n_row_cuts = (uint32_t)n_row_cuts;
-  r->n_ok_sites = n_ok_sites;
-  r->name_lists = names ? s.h_name_lists : nullptr;
-  r->names = names ? s.h_names : nullptr;
-  r->n_name_bytes = name_bytes;
+  r->text = k.was_bgzf ? s.h_text.get() : nullptr;
+  r->n_text_bytes = k.was_bgzf ? k.text_bytes : 0;
+  r->head_off = (k.was_bgzf && s.heads) ? s.h_head_off.get() : nullptr;
+  r->sites = (c->packed && !c->render) ? s.h_sites.get() : nullptr;
+  r->n_full_lines = c->packed ? k.n_first : 0u;
+  r->rows = c->render ? s.h_rows.get() : nullptr;
+  r->n_row_bytes = k.row_bytes;
+  r->row_cuts = c->render ? s.h_row_cuts.get() : nullptr;
+  r->n_row_cuts = (uint32_t)k.n_row_cuts;
+  r->n_ok_sites = k.n_ok_sites;
+  r->name_lists = k.names ? s.h_name_lists.get() : nullptr;
+  r->names = k.names ? s.h_names.get() : nullptr;
+  r->n_name_bytes = k.name_bytes;
+}
 
+static void add_totals(bvcf_ctx *c, const Slot &s, const Collected &k, const bvcf_result *r) {
   uint64_t ok = 0, ac0 = 0, recs = 0;
   if (c->render) {
-    ok += n_ok_sites;
-    recs += n_ok_sites;
+    ok += k.n_ok_sites;
+    recs += k.n_ok_sites;
   } else if (c->packed)
-    for (uint32_t i = 0; i < ctr.n_lines; i++) {
+    for (uint32_t i = 0; i < k.ctr.n_lines; i++) {
       const bvcf_site &st = s.h_sites[i];
       if (!(st.status & BVCF_SITE_FULL)) {
         ok += st.status == BVCF_LINE_OK;
         recs += st.status == BVCF_LINE_OK;
       }
     }
-  for (uint32_t i = 0; i < n_first; i++) {
+  for (uint32_t i = 0; i < k.n_first; i++) {
     const bvcf_line &L = s.h_lines[i];
     if (L.status != BVCF_LINE_OK) continue;
     ok++;
@@ -2043,17 +2020,99 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
     if (c->n_samples)
       for (uint32_t j = 0; j < L.n_rec; j++) ac0 += s.h_alleles[j ? L.rec_first + j - 1 : i].ac == 0;
   }
-  if (ctr.lines_seen) c->avg_line_bytes = s.nbytes / ctr.lines_seen;
-  c->totals[0] += ctr.lines_seen;
+  if (k.ctr.lines_seen) c->avg_line_bytes = s.nbytes / k.ctr.lines_seen;
+  c->totals[0] += k.ctr.lines_seen;
   c->totals[1] += ok;
   c->totals[2] += recs;
   c->totals[3] += ac0;
-  c->totals[4] += n_errs;
+  c->totals[4] += r->n_errs;
   c->totals[5] += s.nbytes;
   c->totals[6] += r->n_cmap_bytes;
-  c->totals[7] += (uint64_t)(ms * 1e6);
-  release();
+  c->totals[7] += (uint64_t)(r->kernel_ms * 1e6);
+}
+
+// the batch in slot s: wait, size check, the folds, D2H of exactly the used parts of the result arrays, *r.  bvcf_collect
+// releases the slot whatever this returns
+static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  Collected k;
+  k.was_bgzf = s.is_bgzf;
+  int rc = launch_after_cuts(c, s, true);
+  if (rc) return rc;
+  hipError_t e = hipEventSynchronize(s.ev_ctr);
+  if (e != hipSuccess) {
+    c->err = std::string("kernel chain failed: ") + hipGetErrorString(e);
+    return BVCF_E_HIP;
+  }
+  if (s.bgzf_rc) {
+    rc = s.bgzf_rc;
+    c->err = s.bgzf_err ? s.bgzf_err : "bgzf: batch refused";
+    s.bgzf_rc = 0;
+    return rc;
+  }
+  memset(r, 0, sizeof *r);
+  r->batch_seq = s.seq;
+  r->n_samples = c->n_samples;
+  r->cmap_stride = c->cmap_stride;
+  hipEventElapsedTime(&r->kernel_ms, s.ev_k0, s.ev_k1);
+  const BatchCounters &ctr = k.ctr = *s.h_counters;
+  adapt_stream_kernel(c, s.used_gen, ctr);
+  k.need = batch_needs(c, s, ctr);
+  if (ctr.pad[0]) {
+    c->err = "internal error: streaming tile quota or class-map slot range exceeded";
+    return BVCF_E_HIP;
+  }
+  if (!k.need.fits) {
+    r->status = BVCF_E_CAPACITY;
+    r->need_lines = ctr.n_lines;
+    r->need_alleles = k.need.need_alleles;
+    r->need_cmap_bytes = k.need.cmap_need;
+    // (the extras of a packed ctx follow slot cap_lines: once the lines grow, so does where they start -- bvcf_reserve
+    // adds them to the NEW line capacity, need_alleles alone is relative to the old one)
+    c->need_extras = extras_at_cap(c) ? (uint64_t)ctr.n_alleles : 0;
+    c->err = "batch exceeds reserved result capacity";
+    return BVCF_E_CAPACITY;
+  }
+  k.n_first = c->packed ? std::min<uint32_t>(ctr.n_full, ctr.n_lines) : ctr.n_lines;
+  k.cmap_bytes = c->p.want_class_maps ? k.need.cmap_need : 0;  // (the maps cross to the host only when the caller wants them)
+  k.names = c->names_on && s.d_name_lists;
+  if (c->render)
+    rc = collect_rows(c, s, k);
+  else if (c->packed && ctr.n_lines)
+    HIP_TRY(c, hipMemcpyAsync(s.h_sites, s.d_sites, ctr.n_lines * sizeof(bvcf_site), hipMemcpyDeviceToHost, s.stream));
+  if (!rc && c->packed) rc = packed_host_room(c, s, k);
+  if (!rc) rc = launch_folds(c, s);
+  if (!rc) rc = copy_records(c, s, k);
+  if (!rc) rc = copy_text(c, s, k);
+  if (!rc) rc = copy_names(c, s, k);
+  if (rc) return rc;
+  e = hipStreamSynchronize(s.stream);
+  if (e != hipSuccess) {
+    c->err = std::string("result copy failed: ") + hipGetErrorString(e);
+    return BVCF_E_HIP;
+  }
+  fill_result(c, s, k, filter_errs(c, s, k), r);
+  add_totals(c, s, k, r);
   return BVCF_OK;
+}
+
+int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
+  if (!c || !r) return BVCF_E_ARG;
+  if (!c->in_flight) {
+    c->err = "nothing to collect";
+    return BVCF_E_EMPTY;
+  }
+  // the oldest batch in flight; its slot is free again whether it came back or failed -- a caller that drains a ctx by
+  // collecting until BVCF_E_EMPTY gets there even when every collect fails
+  Slot &s = c->slots[c->tail];
+  auto release = [&]() {
+    s.busy = false;
+    c->tail = (c->tail + 1) % c->slots.size();
+    c->in_flight--;
+  };
+  const int rc = collect_slot(c, s, r);
+  release();
+  return rc;
 }
 
 int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
@@ -2134,21 +2193,17 @@ int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
   return BVCF_OK;
 }
 
-int bvcf_path(const bvcf_ctx *c) { return c ? (c->fused ? 2 : 1) : BVCF_E_ARG; }
-int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && c->fused) ? (c->gen_mode ? 1 : 0) : -1; }
+int bvcf_path(const bvcf_ctx *c) { return c ? (is_stream(c) ? 2 : 1) : BVCF_E_ARG; }
+int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && is_stream(c)) ? (c->gen_mode ? 1 : 0) : -1; }
 
-long bvcf_bench_head_left(const bvcf_ctx *c) { return (c && c->fused && c->last_left != 0xFFFFFFFFu) ? (long)c->last_left : -1; }
+long bvcf_bench_head_left(const bvcf_ctx *c) { return (c && is_stream(c) && c->last_left != 0xFFFFFFFFu) ? (long)c->last_left : -1; }
 
 int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, uint32_t len_flags, const uint32_t counts[5],
                         uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
                         const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele) {
   if (!head || !counts || !tab_bits || !out_line || !out_allele) return -1;
   FilterTable ft;
-  memset(&ft, 0, sizeof ft);
-  uint32_t used = 0;
-  if (fill_filter(allow_filter, true, &ft.allow_nil, &ft.allow_n, ft.allow_off, ft.allow_len, ft.text, &used) ||
-      fill_filter(exclude_filter, false, &ft.deny_nil, &ft.deny_n, ft.deny_off, ft.deny_len, ft.text, &used))
-    return -1;
+  if (!fill_filter_table(allow_filter, exclude_filter, &ft)) return -1;
   HeadFastHostBytes hb;
   memset(&hb, 0, sizeof hb);
   memcpy(hb.b, head, std::min<size_t>(head_bytes, kHeadFastBytes + 16));
@@ -2195,14 +2250,7 @@ int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uin
   if (used < 0 || (size_t)used != n_comp) return BVCF_E_FATAL;  // not BGZF, or a truncated last block
   if (n_comp >= 0xFFF00000ull) return BVCF_E_TOO_BIG;
   std::vector<BgzfDesc> desc(blocks.size());
-  uint64_t total = 0;
-  for (size_t i = 0; i < blocks.size(); i++) {
-    desc[i].in_off = blocks[i].in_off;
-    desc[i].in_len = blocks[i].in_len;
-    desc[i].out_off = (uint32_t)total;
-    desc[i].isize = blocks[i].isize;
-    total += blocks[i].isize;
-  }
+  const uint64_t total = fill_descs(blocks, desc.data());
   *n_out = (size_t)total;
   if (total > cap || total >= 0xFFF00000ull) return BVCF_E_TOO_BIG;
   if (blocks.empty()) return BVCF_OK;
@@ -2407,20 +2455,17 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
   }
   const BatchCounters ctr = *s.h_counters;
   adapt_stream_kernel(c, c->gen_mode, ctr);  // (every launch of this call went through the same kernel)
+  const BatchNeeds need = batch_needs(c, s, ctr);
   if (counts) {
     counts[0] = ctr.n_lines;
     counts[1] = (uint64_t)ctr.n_lines + ctr.n_alleles;
     counts[2] = ctr.n_errs;
-    counts[3] = (c->fused ? (uint64_t)ctr.cmap_maps : (uint64_t)ctr.n_lines + ctr.n_tasks) * c->cmap_stride;
-    counts[4] = (uint64_t)ctr.n_lines + ctr.n_tasks;
+    counts[3] = cmap_bytes_of(c, ctr);
+    counts[4] = need.n_tasks;
   }
-  const uint64_t b_need = std::max<uint64_t>(std::max<uint64_t>((uint64_t)ctr.n_lines + ctr.n_alleles, ctr.n_errs),
-                                             (uint64_t)ctr.n_lines + ctr.n_tasks);
-  if ((ctr.n_lines > s.cap_lines || b_need > s.cap_alleles ||
-      ((c->p.want_class_maps || c->ss_on || c->pr_on) && c->n_samples &&
-       (c->fused ? (uint64_t)ctr.cmap_maps : (uint64_t)ctr.n_lines + ctr.n_tasks) * c->cmap_stride > s.cap_cmap))) {
+  if (!need.fits) {
     c->err = "bench block exceeds reserved result capacity: lines " + std::to_string(ctr.n_lines) + " records " +
-             std::to_string(b_need) + " maps " + std::to_string(ctr.cmap_maps);
+             std::to_string(need.need_alleles) + " maps " + std::to_string(ctr.cmap_maps);
     return BVCF_E_CAPACITY;
   }
   return BVCF_OK;

@@ -116,6 +116,48 @@ int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, u
                         uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
                         const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele);
 
+/* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
+ * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
+ * moves gen_mode and shape_seen). */
+enum { /* bvcf_ctx_plan.chain: the kernel chain of a batch */
+  BVCF_CHAIN_STREAM = 0,        /* streaming path: lines found by the genotype scan itself (k_stream / k_stream_gen, k_order, ...) */
+  BVCF_CHAIN_SITES2_TILES = 1,  /* no sample columns: k_sites2 / k_sites2p behind a census per tile (the default for such input) */
+  BVCF_CHAIN_SITES2_CHUNKS = 2, /* ... behind the census per chunk (BVCF_S2_CENSUS=chunk) */
+  BVCF_CHAIN_CENSUS = 3,        /* census path: newline census, k_head, then the scan named by bvcf_ctx_plan.scan */
+  BVCF_CHAIN_SITES_EXP = 4,     /* -DBVCF_EXPERIMENTS builds only: k_sites behind the census (BVCF_SITES=1) */
+  BVCF_CHAIN_SITES1_EXP = 5     /* -DBVCF_EXPERIMENTS builds only: k_sites1 on its own, no census (BVCF_SITES=3) */
+};
+enum { /* bvcf_ctx_plan.scan: the genotype scan of the census chain (the streaming chain's own scan counts as plain) */
+  BVCF_SCAN_NONE = 0,   /* no sample columns */
+  BVCF_SCAN_PLAIN = 1,  /* k_gt / k_dosage */
+  BVCF_SCAN_WIDE = 2,   /* k_gt_wide in front of k_gt: a line's regular scan split over waves (from BVCF_WIDE_SAMPLES samples up) */
+  BVCF_SCAN_FILTER = 3, /* min_gq / min_dp: k_gt_filter / k_dosage_filter, one wave per task at any sample count */
+  BVCF_SCAN_SUBSET = 4  /* sample_keep: k_gt_subset / k_dosage_subset (they apply the thresholds too) */
+};
+typedef struct {
+  uint64_t max_batch_bytes;            /* bvcf_params' defaults applied (also n_slots, eol_byte) */
+  uint64_t max_lines, max_alleles;     /* slot i of alleles[] belongs to line i: max_alleles >= max_lines + 64 */
+  uint64_t max_cmap;                   /* before the streaming kernel's per-wave slack, which needs the device's grid */
+  uint32_t n_slots;
+  uint32_t n_samples, n_samples_full;  /* the kept samples -- what every kernel behind the scan and the caller see --, the file's */
+  uint32_t cmap_stride, dosage_stride; /* of the kept samples; dosage_stride 0 unless want_dosage */
+  uint32_t tile_bytes, tile_quota;     /* streaming path: a tile of text and the entries it can list (BVCF_TILE_KB) */
+  uint32_t win_bytes;                  /* wide scan: bytes of a line's sample region per wave (BVCF_WIDE_WIN) */
+  uint32_t chain, scan;                /* BVCF_CHAIN_*, BVCF_SCAN_* */
+  int32_t gen_policy;                  /* k_stream_gen: -1 adaptive, 0 never, 1 always (BVCF_GEN_STREAM) */
+  uint32_t ss_ns_pad, ss_max_runs, ss_stripes; /* want_sample_stats: a wave per (stripe of 1 024 samples, run of dense rows) */
+  uint32_t s1_fmode, s1_fkey[4], s1_flen[4];   /* the allow list as dwords (k_sites1, k_sites2): 0 general, 1 keys, 2 allow all */
+  uint8_t eol_byte;
+  uint8_t packed, render;              /* the result's form: packed_sites / render_sites on a k_sites2 chain */
+  uint8_t gen_mode, shape_seen;        /* the next batch goes through k_stream_gen; that choice has had its first hint */
+  uint8_t head_fast;                   /* k_order settles plain SNP lines itself (BVCF_HEAD_FAST=0: every line goes to k_head) */
+  uint8_t ss_on;                       /* want_sample_stats on a file with samples */
+  uint8_t reserved;
+} bvcf_ctx_plan;
+/* BVCF_OK, or the BVCF_E_ARG bvcf_create would refuse the params with (the message is where a failed create leaves it: the
+ * last error of a null ctx); no device needed */
+int bvcf_plan_ctx(const bvcf_params *p, bvcf_ctx_plan *out);
+
 #ifdef __cplusplus
 }
 #endif
