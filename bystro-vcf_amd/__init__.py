@@ -46,11 +46,12 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels"]
+                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
-                "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx"]
+                "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx",
+                "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -58,6 +59,7 @@ EXPORTS = [
     "bvcf_free_pinned", "bvcf_submit", "bvcf_submit_device", "bvcf_submit_bgzf", "bvcf_collect", "bvcf_sample_stats", "bvcf_enable_pair_stats", "bvcf_pair_stats", "bvcf_counters", "bvcf_sum_counters",
     "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_config_more_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
+    "bvcf_site_gate_defaults", "bvcf_set_site_gate", "bvcf_site_gate_count", "bvcf_config_gate_defaults",
 ]
 
 
@@ -90,9 +92,33 @@ class Config(C.Structure):
 CONFIG_MORE = 1  # BVCF_CONFIG_MORE in Config.reserved[0]: the struct is the head of a ConfigMore
 
 
+CONFIG_MORE_GATE = 1  # BVCF_CONFIG_MORE_GATE in Config.reserved[1]: the ConfigMore reaches up to site_filter_path
+# bvcf_allele.pad[0] of a row the site gate took out: the criteria it fails
+GATE_MIN_MAF, GATE_MAX_MAF, GATE_MIN_MAC, GATE_MAX_MISSING, GATE_HWE = 1, 2, 4, 8, 16
+# the lines of the --siteFilterReport file, and of site_gate_count()
+SITE_GATE_REPORT = ["examined", "kept", "minMaf", "maxMaf", "minMac", "maxMissing", "hwe"]
+
+
+class SiteGate(C.Structure):
+    """bvcf_site_gate"""
+    _fields_ = [("size", C.c_uint32), ("min_mac", C.c_uint32), ("min_maf", C.c_double), ("max_maf", C.c_double),
+                ("max_missing", C.c_double), ("hwe_p", C.c_double)]
+
+
+def make_site_gate(minMaf=0.0, maxMaf=1.0, minMac=0, maxMissing=1.0, hwe=0.0):
+    """a bvcf_site_gate from the CLI's names; the defaults are the neutral values"""
+    g = SiteGate()
+    lib.bvcf_site_gate_defaults(C.byref(g))
+    g.min_maf, g.max_maf, g.min_mac, g.max_missing, g.hwe_p = float(minMaf), float(maxMaf), int(minMac), float(maxMissing), float(hwe)
+    return g
+
+
+GATE_KEYS = ("minMaf", "maxMaf", "minMac", "maxMissing", "hwe")
+
+
 class ConfigMore(C.Structure):
     """bvcf_config_more: bvcf_config and the fields that came after it stopped growing"""
-    _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p)]
+    _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p), ("site_gate", SiteGate), ("site_filter_path", C.c_char_p)]
 
 
 class Result(C.Structure):
@@ -344,8 +370,62 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         keep.append(str(cfg["relatedness"]).encode())
         more.pair_stats_path = keep[-1]
         c.reserved[0] = CONFIG_MORE
+    # --minMaf / --maxMaf / --minMac / --maxMissing / --hwe: the site gate of the run; --siteFilterReport: its counts
+    if any(k in cfg for k in GATE_KEYS) or cfg.get("siteFilterReport"):
+        more.site_gate = make_site_gate(**{k: cfg[k] for k in GATE_KEYS if k in cfg})
+        if cfg.get("siteFilterReport"):
+            keep.append(str(cfg["siteFilterReport"]).encode())
+            more.site_filter_path = keep[-1]
+        c.reserved[0] = CONFIG_MORE
+        c.reserved[1] = CONFIG_MORE_GATE
     c._keep = keep
     return c
+
+
+def hwe_exact(het, hom, other):
+    """bvcf_hwe_exact: the exact Hardy-Weinberg p value as the site gate defines it (host code, no device)"""
+    lib.bvcf_hwe_exact.restype = C.c_double
+    lib.bvcf_hwe_exact.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    return lib.bvcf_hwe_exact(het, hom, other)
+
+
+def hwe_inline_terms():
+    """bvcf_hwe_inline_terms: supports of the exact test up to this many terms are summed by one thread of k_site_gate,
+    longer ones by a wave of k_site_hwe"""
+    lib.bvcf_hwe_inline_terms.restype = C.c_uint32
+    lib.bvcf_hwe_inline_terms.argtypes = []
+    return lib.bvcf_hwe_inline_terms()
+
+
+def site_gate_verdict(gate, n_samples, counts):
+    """bvcf_site_gate_verdict: the GATE_* bits an examined row fails; gate: a SiteGate or make_site_gate's keywords as a
+    dict; counts = (ac, an, n_het, n_hom, n_miss) (host code, no device)"""
+    g = gate if isinstance(gate, SiteGate) else make_site_gate(**gate)
+    arr = (C.c_uint32 * 5)(*[int(x) for x in counts])
+    lib.bvcf_site_gate_verdict.restype = C.c_int
+    lib.bvcf_site_gate_verdict.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+    return lib.bvcf_site_gate_verdict(C.byref(g), n_samples, arr)
+
+
+def site_gate_count(result):
+    """bvcf_site_gate_count over a collected batch (a Result, or a Batch's .r) -> the seven counts of SITE_GATE_REPORT"""
+    out = (C.c_uint64 * 7)()
+    lib.bvcf_site_gate_count.restype = None
+    lib.bvcf_site_gate_count.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bvcf_site_gate_count(C.byref(result), out)
+    return list(out)
+
+
+def bench_hwe(triples, device=0):
+    """bvcf_bench_hwe: the device's exact test on each (het, hom, other) -> float64 array"""
+    t = np.ascontiguousarray(np.asarray(triples, dtype=np.uint32).reshape(-1, 3))
+    p = np.zeros(len(t), dtype=np.float64)
+    lib.bvcf_bench_hwe.restype = C.c_int
+    lib.bvcf_bench_hwe.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
+    rc = lib.bvcf_bench_hwe(device, t.ctypes.data, len(t), p.ctypes.data)
+    if rc:
+        raise BvcfError(rc, "bvcf_bench_hwe")
+    return p
 
 
 def string_header(cfg=None):
@@ -473,6 +553,10 @@ class Batch:
 
     def __init__(self, r):
         self.batch_seq = r.batch_seq
+        # bvcf_site_gate_count, SITE_GATE_REPORT's seven counts of this batch: counted when asked for (gate_counts), from
+        # the record arrays as they are now -- like every view here they belong to the slot, valid until it takes another batch
+        self._result = r
+        self._gate_counts = None
         self.n_samples = r.n_samples
         self.cmap_stride = r.cmap_stride
         self.kernel_ms = r.kernel_ms
@@ -570,6 +654,12 @@ class Batch:
         idx = [i] + [int(L["rec_first"]) + j - 1 for j in range(1, n)]
         return self.alleles[idx]
 
+    @property
+    def gate_counts(self):
+        if self._gate_counts is None:
+            self._gate_counts = site_gate_count(self._result)
+        return self._gate_counts
+
     def record_slots(self, i):
         """indices into alleles[] (and dosage[]) of line i's output alleles, in order"""
         L = self.lines[i]
@@ -611,7 +701,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -629,6 +719,12 @@ class Ctx:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
                 raise BvcfError(rc, msg)
+        if site_gate is not None:  # bvcf_set_site_gate: a SiteGate, or make_site_gate's keywords as a dict
+            try:
+                self.set_site_gate(site_gate)
+            except BvcfError:
+                self.close()
+                raise
         if render_sites:
             lib.bvcf_set_row_format.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int]
             self._check(lib.bvcf_set_row_format(self.h, empty_field.encode(), int(keep_pos), int(keep_id), int(keep_info)))
@@ -745,6 +841,19 @@ class Ctx:
         lib.bvcf_sample_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         self._check(lib.bvcf_sample_stats(self.h, out.ctypes.data if self.n_samples else None, int(reset)))
         return out.reshape(6, self.n_samples).T.copy()
+
+    def set_site_gate(self, gate):
+        """bvcf_set_site_gate, before the first submit: gate is a SiteGate or make_site_gate's keywords as a dict"""
+        g = gate if isinstance(gate, SiteGate) else make_site_gate(**gate)
+        lib.bvcf_set_site_gate.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_set_site_gate(self.h, C.byref(g)))
+
+    def bench_gate_kernels(self):
+        """the gate kernels over the last bench block of the ctx -> ms of [k_site_gate, k_site_hwe]"""
+        ms = (C.c_float * 2)()
+        lib.bvcf_bench_gate_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_gate_kernels(self.h, ms))
+        return list(ms)
 
     def bench_pair_kernels(self):
         """the pair kernels over the first slot's last bench chain -> ms of [k_pr_planes, k_pr_gemm, k_pr_sparse, k_pr_fold]"""

@@ -119,6 +119,8 @@ struct Slot {
   DevBuf<unsigned long long> d_pr_planes;
   uint64_t cap_pr_tiles = 0;
   DevBuf<uint32_t> d_pr_bt;
+  // bvcf_set_site_gate with hwe_p (bvcf_sitegate.hip.h): [0] the number of rows left to k_site_hwe, then their slots (follows max_alleles)
+  DevBuf<uint32_t> d_gate_list;
   // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
   // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
@@ -167,6 +169,11 @@ struct bvcf_ctx : bvcf_ctx_plan {
   uint32_t pr_split = 1;
   DevBuf<unsigned long long> d_pr_tot;
   Event ev_pr_fold;
+  // bvcf_set_site_gate on a file with samples, some criterion not neutral: k_site_gate / k_site_hwe behind k_finish
+  bool gate_on = false;
+  bvcf_site_gate gate{};
+  const void *bench_src = nullptr;  // the last block of the last bvcf_bench_device* call (bvcf_bench_gate_kernels)
+  size_t bench_nbytes = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
   DevBuf<FilterTable> d_filters;
   std::vector<Slot> slots;
@@ -443,7 +450,15 @@ NameArgs make_name_args(bvcf_ctx *c, Slot &s) {
 }
 
 // the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
+// bvcf_set_site_gate with hwe_p: the list of the rows left to k_site_hwe (follows max_alleles) -- for a slot that exists
+// when the gate is set, and again whenever alloc_results sizes the slot anew
+int alloc_gate_list(bvcf_ctx *c, Slot &s) {
+  if (c->gate_on && c->gate.hwe_p > 0.0) HIP_TRY(c, s.d_gate_list.alloc(c->max_alleles + 1));
+  return BVCF_OK;
+}
+
 int alloc_row_lists(bvcf_ctx *c, Slot &s) {
+  if (const int rc = alloc_gate_list(c, s)) return rc;
   if (!c->ss_on && !c->pr_on) return BVCF_OK;
   s.d_pr_planes.reset();
   s.cap_pr_tiles = 0;
@@ -657,6 +672,27 @@ PairStatsArgs make_pr_args(bvcf_ctx *c, Slot &s) {
   return pa;
 }
 
+SiteGateArgs make_gate_args(bvcf_ctx *c, Slot &s) {
+  SiteGateArgs ga{};
+  ga.g = c->gate;
+  if (c->gate.hwe_p > 0.0 && s.d_gate_list) {
+    ga.ctr = s.d_gate_list;
+    ga.list = s.d_gate_list + 1;
+    ga.list_cap = (uint32_t)(s.d_gate_list.size() - 1);
+  }
+  return ga;
+}
+
+// bvcf_set_site_gate: right behind k_finish, in front of every kernel that reads a record's ac -- the rows that fail are
+// taken out (bvcf_sitegate.hip.h); k_site_hwe settles the rows whose exact test is too long for one thread
+void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if (!c->gate_on || !slot) return;
+  const SiteGateArgs ga = make_gate_args(c, *slot);
+  if (ga.list) hipMemsetAsync(ga.ctr, 0, sizeof(uint32_t), st);
+  hipLaunchKernelGGL(k_site_gate, dim3(c->n_cu * kGateListWgs), dim3(kWgThreads), 0, st, a, ga);
+  if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
+}
+
 // bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
 // (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
 // ... and, with bvcf_enable_pair_stats, the batch's pair tables from the same row lists (bvcf_pairstats.hip.h): the list
@@ -741,6 +777,7 @@ void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t 
                        dim3(kWgThreads), 0, st, a);
   if (!(skip & 4))
     hipLaunchKernelGGL(k_finish, dim3(follower_grid(c, n_cu * 4u, c->last_finish, kWgThreads)), dim3(kWgThreads), 0, st, a);
+  launch_site_gate(c, a, st, slot);
   if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
   launch_sample_stats(c, a, st, slot);
 }
@@ -838,6 +875,7 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
   if (ev_gt1) hipEventRecord(ev_gt1, st);
   if (c->scan == BVCF_SCAN_NONE) return;
   hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+  launch_site_gate(c, a, st, slot);
   if (a.dosage) switch (c->scan) {
       case BVCF_SCAN_SUBSET: hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa); break;
       case BVCF_SCAN_FILTER: hipLaunchKernelGGL(k_dosage_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa); break;
@@ -2193,6 +2231,66 @@ int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
   return BVCF_OK;
 }
 
+void bvcf_site_gate_defaults(bvcf_site_gate *g) {
+  if (!g) return;
+  memset(g, 0, sizeof *g);
+  g->size = (uint32_t)sizeof *g;
+  g->max_maf = 1.0;
+  g->max_missing = 1.0;
+}
+
+// the ranges of bvcf_site_gate (a NaN fails every comparison)
+static bool site_gate_in_range(const bvcf_site_gate *g) {
+  return g->size == sizeof *g && g->min_mac <= BVCF_MAX_THRESHOLD && g->min_maf >= 0.0 && g->min_maf <= 0.5 && g->max_maf >= 0.0 &&
+         g->max_maf <= 1.0 && g->max_missing >= 0.0 && g->max_missing <= 1.0 && g->hwe_p >= 0.0 && g->hwe_p <= 1.0;
+}
+
+int bvcf_set_site_gate(bvcf_ctx *c, const bvcf_site_gate *g) {
+  if (!c) return BVCF_E_ARG;
+  if (!g || !site_gate_in_range(g)) {
+    c->err = "bvcf_set_site_gate: want size = sizeof(bvcf_site_gate), min_maf in [0, 0.5], max_maf, max_missing and hwe_p in [0, 1], "
+             "min_mac at most " + std::to_string(BVCF_MAX_THRESHOLD);
+    return BVCF_E_ARG;
+  }
+  if (c->in_flight) {
+    c->err = "bvcf_set_site_gate with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
+  c->gate = *g;
+  c->gate_on = g->min_maf > 0.0 || g->max_maf < 1.0 || g->min_mac > 0u || g->max_missing < 1.0 || g->hwe_p > 0.0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)  // (the slots were sized by bvcf_create, before there was a gate)
+    if (const int rc = alloc_gate_list(c, s)) return rc;
+  return BVCF_OK;
+}
+
+void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]) {
+  if (!out) return;
+  for (int q = 0; q < 7; q++) out[q] = 0;
+  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    for (uint32_t j = 0; j < L.n_rec; j++) {
+      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
+      const uint32_t bits = A.pad[0];
+      if (!bits && !A.ac) continue;  // (a row no sample carries: not examined)
+      out[0]++;
+      if (!bits) out[1]++;
+      for (int q = 0; q < 5; q++) out[2 + q] += (bits >> q) & 1u;
+    }
+  }
+}
+
+int bvcf_site_gate_verdict(const bvcf_site_gate *g, uint32_t S, const uint32_t counts[5]) {
+  if (!g || !counts || !site_gate_in_range(g)) return -1;
+  return (int)site_gate_verdict(*g, S, counts[0], counts[1], counts[2], counts[3], counts[4]);
+}
+
+double bvcf_hwe_exact(uint32_t het, uint32_t hom, uint32_t other) { return hwe_exact_seq(het, hom, other); }
+uint32_t bvcf_hwe_inline_terms(void) { return kHweInlineTerms; }
+
 int bvcf_path(const bvcf_ctx *c) { return c ? (is_stream(c) ? 2 : 1) : BVCF_E_ARG; }
 int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && is_stream(c)) ? (c->gen_mode ? 1 : 0) : -1; }
 
@@ -2435,6 +2533,8 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
   Slot &s = c->slots[(size_t)(iters - 1) % n_use];  // the slot whose counters are reported
   std::vector<Event> ev((size_t)iters * 4);
   for (auto &e : ev) HIP_TRY(c, e.create());
+  c->bench_src = dblocks[(iters - 1) % n_blocks];
+  c->bench_nbytes = nbytes[(iters - 1) % n_blocks];
   for (int i = 0; i < iters; i++) {
     Slot &si = c->slots[(size_t)i % n_use];
     si.s2_parity ^= 1u;
@@ -2503,6 +2603,58 @@ int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(s.stream));
   for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  return BVCF_OK;
+}
+
+int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p) {
+  if (!triples || !p) return BVCF_E_ARG;
+  if (!n) return BVCF_OK;
+  if (hipSetDevice(device) != hipSuccess) return BVCF_E_NODEV;
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) return BVCF_E_HIP;
+  DevBuf<uint32_t> d_t;
+  DevBuf<double> d_p;
+  if (d_t.alloc(3ull * n) != hipSuccess || d_p.alloc(n) != hipSuccess) return BVCF_E_NOMEM;
+  if (hipMemcpy(d_t, triples, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return BVCF_E_HIP;
+  const uint32_t grid = std::min<uint32_t>((n + kWavesPerWg - 1) / kWavesPerWg, (uint32_t)n_cu * kHweWgs);
+  hipLaunchKernelGGL(k_hwe_probe, dim3(grid), dim3(kWgThreads), 0, 0, (const uint32_t *)d_t, n, (double *)d_p);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return BVCF_E_HIP;
+  return hipMemcpy(p, d_p, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
+}
+
+int bvcf_bench_gate_kernels(bvcf_ctx *c, float ms[2]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_gate_kernels with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->gate_on || !c->bench_src) {
+    c->err = "bvcf_bench_gate_kernels: the ctx has no site gate, or no bvcf_bench_device* call went before";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Slot &s = c->slots[0];
+  int rc = alloc_results(c, s);
+  if (rc) return rc;
+  // the chain of the last bench block once more with the gate off: the records as k_finish leaves them
+  s.s2_parity ^= 1u;
+  const KernelArgs a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
+  c->gate_on = false;
+  launch_chain(c, a, s.stream, nullptr, nullptr, &s);
+  c->gate_on = true;
+  const SiteGateArgs ga = make_gate_args(c, s);
+  Event ev[3];
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  if (ga.list) HIP_TRY(c, hipMemsetAsync(ga.ctr, 0, sizeof(uint32_t), s.stream));
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  hipLaunchKernelGGL(k_site_gate, dim3(c->n_cu * kGateListWgs), dim3(kWgThreads), 0, s.stream, a, ga);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, s.stream, a, ga);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < 2; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  if (!ga.list) ms[1] = 0.f;
   return BVCF_OK;
 }
 

@@ -442,6 +442,11 @@ void Driver::device_main(DevWorker *W) {
     }
     in_flight.pop_front();
     lines_in_.fetch_add(res.n_lines_seen);
+    if (sg_fd_ >= 0) {  // --siteFilterReport: exactly the batches of the output -- nothing to reset when a reservation grows
+      uint64_t t[7];
+      bvcf_site_gate_count(&res, t);
+      for (int q = 0; q < 7; q++) W->gate_counts[q] += t[q];
+    }
     FmtJob j;
     j.b = b;
     j.res = res;
@@ -571,6 +576,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return BVCF_E_IO;
     }
     if (open_pair_stats(c_, &pr_fd_, &msg)) {  // --relatedness: likewise
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return BVCF_E_IO;
+    }
+    if (open_site_report(c_, &sg_fd_, &msg)) {  // --siteFilterReport: likewise
       dprintf(fd_err_, "%s\n", msg.c_str());
       return BVCF_E_IO;
     }
@@ -773,6 +782,22 @@ int Driver::run(uint64_t *n_lines_in) {
       }
       if (rc_ != BVCF_OK) close(pr_fd_);  // (write_pair_stats closed it)
       pr_fd_ = -1;
+    }
+    if (sg_fd_ >= 0) {
+      // --siteFilterReport: the workers' counts of the batches they handed on
+      if (rc_ == BVCF_OK) {
+        uint64_t sum[7] = {0, 0, 0, 0, 0, 0, 0};
+        for (auto &W : workers_)
+          for (int q = 0; q < 7; q++) sum[q] += W->gate_counts[q];
+        std::string msg;
+        if (write_site_report(sg_fd_, sum, &msg)) {
+          fail(msg, BVCF_E_IO);
+          write_all(fd_err_, log_.data(), log_.size());
+        }
+      } else {
+        close(sg_fd_);
+      }
+      sg_fd_ = -1;
     }
     if (!c_->leave_teardown_to_exit)
       for (bvcf_ctx *x : live) bvcf_destroy(x);

@@ -20,9 +20,17 @@ void bvcf_config_defaults(bvcf_config *c) {
 }
 
 void bvcf_config_more_defaults(bvcf_config_more *c) {
-  memset(c, 0, sizeof *c);
+  // (up to pair_stats_path: a caller built when that was the last field owns no more)
+  memset(c, 0, offsetof(bvcf_config_more, site_gate));
   bvcf_config_defaults(&c->base);
   c->base.reserved[0] = BVCF_CONFIG_MORE;
+}
+
+void bvcf_config_gate_defaults(bvcf_config_more *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_more_defaults(c);
+  c->base.reserved[1] = BVCF_CONFIG_MORE_GATE;
+  bvcf_site_gate_defaults(&c->site_gate);
 }
 
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
@@ -89,9 +97,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   R.cfg = c;
   R.max_batch = c->max_batch_bytes ? c->max_batch_bytes : (64ull << 20);
   uint64_t lines_in = 0;
-  int ss_fd = -1, pr_fd = -1;
+  int ss_fd = -1, pr_fd = -1, sg_fd = -1;
+  uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};
   int rc = open_sample_stats(c, &ss_fd, &msg);
   if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
+  if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -126,6 +136,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         break;
       }
       lines_in += res.n_lines_seen;
+      if (sg_fd >= 0) {  // --siteFilterReport: what the gate did to the batches of the output
+        uint64_t t[7];
+        bvcf_site_gate_count(&res, t);
+        for (int q = 0; q < 7; q++) gate_counts[q] += t[q];
+      }
       if (R.want_rows) {
         format_batch(c, &res, vcf + pos, nm, R.ratios.get(), R.pool.get(), o, l);
       } else {
@@ -173,6 +188,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       }
     } else {
       close(pr_fd);
+    }
+  }
+  if (sg_fd >= 0) {  // --siteFilterReport: after a successful run only
+    if (rc != BVCF_OK) {
+      close(sg_fd);
+    } else if (write_site_report(sg_fd, gate_counts, &msg)) {
+      l.append(msg + "\n");
+      rc = BVCF_E_IO;
     }
   }
   if (R.ctx) bvcf_destroy(R.ctx);

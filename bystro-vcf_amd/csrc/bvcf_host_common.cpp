@@ -832,6 +832,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (const bvcf_config_more *m = rc == BVCF_OK ? gate_config(R.cfg) : nullptr) {  // the site gate of every ctx of the run
+    rc = bvcf_set_site_gate(*ctx, &m->site_gate);
+    if (rc) {
+      *msg = bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (rc == BVCF_OK && p.render_sites) {
     rc = bvcf_set_row_format(*ctx, or_default(R.cfg->empty_field, "!"), R.cfg->keep_pos, R.cfg->keep_id, R.cfg->keep_info);
     if (rc) {
@@ -976,6 +984,36 @@ int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const 
   format_sample_stats(c, pre, t, o);
   if (write_all(fd, o.data(), o.size()) || close(fd)) {
     *msg = std::string("sample stats: write failed: ") + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_site_report(const bvcf_config *c, int *fd, std::string *msg) {
+  *fd = -1;
+  if (!wants_site_report(c)) return BVCF_OK;
+  const char *path = gate_config(c)->site_filter_path;
+  *fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+  if (*fd < 0) {
+    *msg = std::string("open ") + path + ": " + strerror(errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int write_site_report(int fd, const uint64_t counts[7], std::string *msg) {
+  static const char *const kNames[7] = {"examined", "kept", "minMaf", "maxMaf", "minMac", "maxMissing", "hwe"};
+  std::string o;
+  for (int q = 0; q < 7; q++) {
+    o.append(kNames[q]);
+    o.push_back('\t');
+    append_ll(o, (long long)counts[q]);
+    o.push_back('\n');
+  }
+  const bool bad = write_all(fd, o.data(), o.size()) != 0;
+  const int saved = errno;
+  if (close(fd) || bad) {
+    *msg = std::string("siteFilterReport: write failed: ") + strerror(bad ? saved : errno);
     return BVCF_E_IO;
   }
   return BVCF_OK;

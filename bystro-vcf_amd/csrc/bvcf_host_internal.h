@@ -266,6 +266,20 @@ inline bool wants_pair_stats(const bvcf_config *c) {
   return p && *p;
 }
 
+// --minMaf ... --hwe / --siteFilterReport: the config as a bvcf_config_more that reaches up to site_filter_path (both markers
+// set), or NULL -- nothing behind pair_stats_path is read for a caller built before the fields were there
+inline const bvcf_config_more *gate_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] == BVCF_CONFIG_MORE_GATE) ? reinterpret_cast<const bvcf_config_more *>(c)
+                                                                                       : nullptr;
+}
+inline bool wants_site_report(const bvcf_config *c) {
+  const bvcf_config_more *m = gate_config(c);
+  return m && m->site_filter_path && *m->site_filter_path;
+}
+// the report file: opened before any device work; counts = the sum of bvcf_site_gate_count over the batches of the output
+int open_site_report(const bvcf_config *c, int *fd, std::string *msg);
+int write_site_report(int fd, const uint64_t counts[7], std::string *msg);
+
 // a bounded FIFO between pipeline stages
 template <class T>
 class Channel {

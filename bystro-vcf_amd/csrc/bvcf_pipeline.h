@@ -211,6 +211,7 @@ struct DevWorker {
   // batches in flight are collected, dropped and submitted again)
   std::vector<uint64_t> ss_carry;
   std::vector<uint64_t> pr_carry;  // --relatedness: the same for the pair tables
+  uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};  // --siteFilterReport: bvcf_site_gate_count over the batches handed to the formatter
 };
 
 enum Mode { kStream = BVCF_MODE_STREAM, kRangeText = BVCF_MODE_TEXT_RANGES, kRangeBgzf = BVCF_MODE_BGZF_RANGES };
@@ -223,6 +224,7 @@ class Driver {
   ~Driver() {
     if (ss_fd_ >= 0) close(ss_fd_);  // (a run that ended before its table was written)
     if (pr_fd_ >= 0) close(pr_fd_);
+    if (sg_fd_ >= 0) close(sg_fd_);
   }
   int run(uint64_t *n_lines_in);
   // bvcf_plan_fd: the blocks the workers received, in (range, piece) order
@@ -277,6 +279,7 @@ class Driver {
   std::string log_;
   int ss_fd_ = -1;  // --sampleStats
   int pr_fd_ = -1;  // --relatedness
+  int sg_fd_ = -1;  // --siteFilterReport
   std::atomic<bool> failed_{false};
   // what the workers wait for: the header is known, the ctx parameters are set, the ranges are laid out
   struct {

@@ -10,6 +10,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -37,7 +38,24 @@ struct Cli {
   // extension: --relatedness PATH, the pairwise table of the run's rows: hetHet, ibs0, het1, het2 and the KING-robust kinship
   // of every pair of samples (counted on the device)
   std::string relatedness;
+  // extension: --minMaf F / --maxMaf F / --minMac N / --maxMissing F / --hwe P, the per-site QC gate: rows that fail are taken
+  // out on the device, before anything is made of them; --siteFilterReport PATH, how many rows each criterion failed
+  double min_maf = 0.0, max_maf = 1.0, max_missing = 1.0, hwe = 0.0;
+  uint32_t min_mac = 0;
+  std::string site_report;
 };
+
+// a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
+// finite.  strtod would also read hexadecimal floats ("0x1p-2"): the flags take decimals, those are refused (README.md)
+bool parse_decimal(const std::string &v, double hi, double *out) {
+  if (v.empty() || !((v[0] >= '0' && v[0] <= '9') || v[0] == '.')) return false;
+  if (v.find_first_of("xXpP") != std::string::npos) return false;
+  char *e = nullptr;
+  const double d = strtod(v.c_str(), &e);
+  if (e == v.c_str() || *e || !std::isfinite(d) || !(d >= 0.0 && d <= hi)) return false;
+  *out = d;
+  return true;
+}
 
 // a decimal integer in 0 .. BVCF_MAX_THRESHOLD, digits only
 bool parse_threshold(const std::string &v, uint32_t *out) {
@@ -117,7 +135,8 @@ int parse(int argc, char **argv, Cli &c) {
     // extensions of this build (not in the reference): the devices the blocks are dealt to (the
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
-        name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness") {
+        name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
+        name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -137,6 +156,20 @@ int parse(int argc, char **argv, Cli &c) {
         c.sample_stats = val;
       } else if (name == "relatedness") {
         c.relatedness = val;
+      } else if (name == "siteFilterReport") {
+        c.site_report = val;
+      } else if (name == "minMac") {
+        if (!parse_threshold(val, &c.min_mac)) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
+          return 2;
+        }
+      } else if (name == "minMaf" || name == "maxMaf" || name == "maxMissing" || name == "hwe") {
+        const bool half = name == "minMaf";
+        double *dst = half ? &c.min_maf : name == "maxMaf" ? &c.max_maf : name == "maxMissing" ? &c.max_missing : &c.hwe;
+        if (!parse_decimal(val, half ? 0.5 : 1.0, dst)) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want a decimal from 0 to %s\n", val.c_str(), name.c_str(), half ? "0.5" : "1");
+          return 2;
+        }
       } else if (name == "minGQ" || name == "minDP") {
         if (!parse_threshold(val, name == "minGQ" ? &c.min_gq : &c.min_dp)) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
@@ -188,8 +221,8 @@ int main(int argc, char **argv) {
     dprintf(fd_err, "Cannot specify --noOut and --out\n");
     return 1;
   }
-  // main.go:164-166 (--sampleStats or --relatedness alone: a QC-only pass)
-  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty()) {
+  // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass)
+  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -201,8 +234,8 @@ int main(int argc, char **argv) {
     }
   }
 
-  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path)
-  bvcf_config_more_defaults(&more);
+  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path, the site gate and its report)
+  bvcf_config_gate_defaults(&more);
   bvcf_config &cfg = more.base;
   cfg.empty_field = c.empty.c_str();
   cfg.field_delimiter = c.delim.c_str();
@@ -252,6 +285,12 @@ int main(int argc, char **argv) {
   cfg.keep_samples_path = c.keep_samples.c_str();
   cfg.exclude_samples_path = c.exclude_samples.c_str();
   more.pair_stats_path = c.relatedness.c_str();
+  more.site_gate.min_maf = c.min_maf;
+  more.site_gate.max_maf = c.max_maf;
+  more.site_gate.min_mac = c.min_mac;
+  more.site_gate.max_missing = c.max_missing;
+  more.site_gate.hwe_p = c.hwe;
+  more.site_filter_path = c.site_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

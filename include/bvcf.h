@@ -97,6 +97,12 @@ enum {
 #define BVCF_DEVICE_PAD 64      /* bytes a device-resident block must own past nbytes */
 #define BVCF_PAIR_MAX_SAMPLES 8192u /* most samples bvcf_enable_pair_stats accepts: the tables grow with their square */
 #define BVCF_MAX_THRESHOLD 999999999u /* largest bvcf_params.min_gq / min_dp (a value of 10 digits or more is no number) */
+/* bvcf_set_site_gate: the fail bits of a gated record, in bvcf_allele.pad[0] */
+#define BVCF_GATE_MIN_MAF 1u
+#define BVCF_GATE_MAX_MAF 2u
+#define BVCF_GATE_MIN_MAC 4u
+#define BVCF_GATE_MAX_MISSING 8u
+#define BVCF_GATE_HWE 16u
 
 typedef struct bvcf_ctx bvcf_ctx;
 
@@ -217,7 +223,7 @@ typedef struct {
   uint8_t site_type;   /* BVCF_SITE_* */
   uint8_t trtv;        /* 0 / 1 / 2 (main.go:602-606) */
   uint8_t flags;
-  uint8_t pad[2];
+  uint8_t pad[2];      /* [0]: bvcf_set_site_gate, the BVCF_GATE_* bits of a row the gate took out (its ac is then 0); else 0 */
   uint32_t gt_task;    /* internal: genotype-scan task that produced ac..n_miss */
   uint32_t pad2;
 } bvcf_allele;
@@ -410,8 +416,44 @@ int bvcf_enable_pair_stats(bvcf_ctx *ctx);
  * bvcf_enable_pair_stats was not called. */
 int bvcf_pair_stats(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S: [t][i][j] */, int reset);
 
+/* The per-site QC gate (--minMaf / --maxMaf / --minMac / --maxMissing / --hwe).  size = sizeof(bvcf_site_gate).  A criterion
+ * at its neutral value is off; with all of them neutral the ctx allocates and launches nothing for the gate.
+ * The gate examines every output allele of a line with status OK, in a file with sample columns, whose ac > 0 -- after
+ * min_gq / min_dp masking and after sample_keep --, on the device, right behind the kernel that settles the counts.  With
+ * S = bvcf_result.n_samples (the kept samples), mac = min(ac, an - ac) and the record's own counts (the ones the TSV row
+ * prints; a multiallelic line is gated per emitted row, "this ALT against the rest"), a row FAILS
+ *   BVCF_GATE_MIN_MAF      when (double)mac / (double)an < min_maf        [0, 0.5], 0 = off
+ *   BVCF_GATE_MAX_MAF      when (double)mac / (double)an > max_maf        [0, 1],   1 = off
+ *   BVCF_GATE_MIN_MAC      when mac < min_mac                             0 .. BVCF_MAX_THRESHOLD, 0 = off
+ *   BVCF_GATE_MAX_MISSING  when (double)n_miss / (double)S > max_missing  [0, 1],   1 = off
+ *   BVCF_GATE_HWE          when p_hwe < hwe_p                             [0, 1],   0 = off
+ * (IEEE double divisions).  p_hwe is the exact test of Wigginton et al. 2005 on the row's three counts, without mid-p
+ * correction: n = S - n_miss, a = n_het, b = n_hom, c = n - a - b, r = a + 2 min(b, c); over the support
+ * h in {0 <= h <= r, h = r (mod 2)} with w(h) = n! 2^h / (((r-h)/2)! h! (n - h - (r-h)/2)!),
+ *   p_hwe = sum{w(h) : w(h) <= w(a) (1 + 1e-7)} / sum w(h)
+ * -- the factor 1 + 1e-7 is part of the definition: mathematically tied terms land on the same side everywhere.  Samples
+ * are counted by the list that names them, whatever their ploidy: a haploid call counts as hom, as in the TSV.
+ * The contract: a gated record has ac == 0 and a non-zero gate byte (bvcf_allele.pad[0], every criterion the row fails --
+ * the exact test is evaluated even when a cheaper criterion already failed the row); an, n_het, n_hom and n_miss stay as
+ * they were; every consumer written against this ABI drops it as it drops any row no sample carries (main.go:558-560):
+ * bvcf_format_tsv, the dosage rows, the name lists, bvcf_sample_stats and bvcf_pair_stats count the surviving rows only.
+ * Line verdicts, the error list and bvcf_line do not change; bvcf_counters' alleles_ac0 includes the gated rows.
+ * Call once, before the first submit, like bvcf_enable_pair_stats.  BVCF_E_ARG for a value out of range or NaN; a no-op
+ * returning BVCF_OK on a ctx without sample columns.  bvcf_params and the ABI version do not change with it. */
+typedef struct {
+  uint32_t size;
+  uint32_t min_mac;
+  double min_maf, max_maf, max_missing, hwe_p;
+} bvcf_site_gate;
+void bvcf_site_gate_defaults(bvcf_site_gate *g); /* size set, every criterion neutral */
+int bvcf_set_site_gate(bvcf_ctx *ctx, const bvcf_site_gate *g);
+/* what the gate did to a collected batch, from its records alone (host only; no ctx): out = {examined, kept, failed
+ * minMaf, maxMaf, minMac, maxMissing, hwe} -- a row counts under every criterion it fails.  All zero for a batch without
+ * sample columns. */
+void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]);
+
 /* running totals since bvcf_create: {lines_in, lines_ok, alleles_out, alleles_ac0, errs,
- * bytes_in, cmap_bytes, kernel_ns} */
+ * bytes_in, cmap_bytes, kernel_ns}; alleles_ac0 includes the rows bvcf_set_site_gate took out */
 int bvcf_counters(bvcf_ctx *ctx, uint64_t out[8]);
 /* the run summary over several ctxs driven by one process: element-wise sum of their counters, on the host */
 int bvcf_sum_counters(bvcf_ctx *const *ctxs, int n, uint64_t out[8]);
@@ -440,7 +482,7 @@ typedef struct {
   uint8_t normalize_header;     /* parse.NormalizeHeader restatement ('.' -> '_'), default 1 */
   uint8_t leave_teardown_to_exit; /* bvcf_run_fd: the process exits right after the call (the CLI): skip destroying the
                                    ctxs and unpinning the buffers, the OS reclaims them (~0.1 s of a 0.9 s run) */
-  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct */
+  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct; [1]: BVCF_CONFIG_MORE_GATE */
   int32_t device;               /* HIP device ordinal */
   uint32_t n_format_threads;    /* 0 = the CPUs the process may use (affinity, cgroup quota), at most 32 */
   uint64_t max_batch_bytes;     /* 0 = 64 MiB (256 MiB of text for a BGZF file inflated on the device) */
@@ -491,6 +533,10 @@ void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
  * hands &more.base to bvcf_run_fd / bvcf_run_buffer.  With reserved[0] == 0 -- what bvcf_config_defaults leaves --
  * nothing behind the bvcf_config is read. */
 #define BVCF_CONFIG_MORE 1
+/* ... and a second marker, in base.reserved[1]: the struct reaches up to site_filter_path.  Without it -- a caller built
+ * when pair_stats_path was the last field -- nothing behind pair_stats_path is read (or written by
+ * bvcf_config_more_defaults). */
+#define BVCF_CONFIG_MORE_GATE 1
 typedef struct {
   bvcf_config base;
   /* --relatedness: bvcf_run_fd / bvcf_run_buffer write the pairwise table of the run's rows here -- one line per unordered
@@ -500,8 +546,21 @@ typedef struct {
    * exclude_samples_path.  With a sample selection the table is over the kept samples, with min_gq / min_dp a masked call
    * is missing.  The bytes do not depend on devices, batch size or input kind.  NULL or "" = no table */
   const char *pair_stats_path;
+  /* base.reserved[1] == BVCF_CONFIG_MORE_GATE only (bvcf_config_gate_defaults sets it).  --minMaf / --maxMaf / --minMac / --maxMissing / --hwe: the
+   * bvcf_set_site_gate of every ctx of the run (bvcf_run_fd / bvcf_run_buffer fail with BVCF_E_ARG for a value out of range).
+   * The one rule: a run with a gate produces, byte for byte, what the run without it produces with the failing rows taken
+   * out -- the TSV and its BGZF form, the dosage file (rows and their order); sample_stats_path and pair_stats_path count the
+   * surviving rows.  The log, the sample list and the line verdicts do not change.  Files without sample columns come out
+   * unchanged.  The output does not depend on devices, batch size or input kind */
+  bvcf_site_gate site_gate;
+  /* --siteFilterReport: seven lines "name\tcount" -- examined, kept, minMaf, maxMaf, minMac, maxMissing, hwe -- summed with
+   * bvcf_site_gate_count over the batches of the output.  Opened before any device work, written at the end of a
+   * successful run.  NULL or "" = no report */
+  const char *site_filter_path;
 } bvcf_config_more;
 void bvcf_config_more_defaults(bvcf_config_more *c); /* bvcf_config_defaults, the marker, pair_stats_path = NULL */
+/* the whole struct: bvcf_config_more_defaults, base.reserved[1] = BVCF_CONFIG_MORE_GATE, a neutral gate, no report */
+void bvcf_config_gate_defaults(bvcf_config_more *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

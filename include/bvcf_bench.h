@@ -40,6 +40,20 @@ long bvcf_bench_head_left(const bvcf_ctx *ctx);
  * BVCF_E_ARG on a ctx without pair tables */
 int bvcf_bench_pair_kernels(bvcf_ctx *ctx, float ms[4]);
 
+/* The exact Hardy-Weinberg test as the site gate runs it on the device: triples = n x {het, hom, other}, p[j] the p value of
+ * triple j -- by the thread-per-row recurrence or by a wave (k_site_hwe's code), chosen by the length of the support as
+ * k_site_gate chooses.  Needs no ctx */
+int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p);
+
+/* bvcf_set_site_gate: the two gate kernels on their own.  The chain of the LAST block of the ctx's last bvcf_bench_device*
+ * call runs once more on the first slot with the gate switched off, so that the records are as k_finish leaves them; then
+ * k_site_gate and k_site_hwe run over them with HIP events around each: ms = {k_site_gate, k_site_hwe} (0 for k_site_hwe
+ * when the gate has no hwe_p) -- the times of a gate that does all its work.  For this the ctx KEEPS the device pointer
+ * and size of that block past the bvcf_bench_device* call: the caller must leave the block resident until it has made its
+ * last bvcf_bench_gate_kernels call (or the next bvcf_bench_device* call, which replaces the pointer).  BVCF_E_ARG on a
+ * ctx without a gate, or when no bvcf_bench_device* call went before */
+int bvcf_bench_gate_kernels(bvcf_ctx *ctx, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,17 @@ int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, u
                         uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
                         const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele);
 
+/* The per-row code of the site gate (csrc/bvcf_sitegate.hip.h; bvcf_set_site_gate in include/bvcf.h), run on the host: the
+ * same functions the device runs per alleles[] slot.  counts = {ac, an, n_het, n_hom, n_miss} of an examined row, S the
+ * ctx's sample count; returns the BVCF_GATE_* bits the row fails (0: it stays), the exact test by the sequential
+ * recurrence whatever the length of its support; -1: bad arguments. */
+int bvcf_site_gate_verdict(const bvcf_site_gate *g, uint32_t S, const uint32_t counts[5]);
+/* the exact Hardy-Weinberg p value of {het, hom, other} called samples, as bvcf_set_site_gate defines it */
+double bvcf_hwe_exact(uint32_t het, uint32_t hom, uint32_t other);
+/* the bound between the device's two forms of the test: a row whose support has at most this many terms
+ * (het + 2 min(hom, other) <= 2 * terms - 1) is summed by the thread that examines it, a longer one by a wave (k_site_hwe) */
+uint32_t bvcf_hwe_inline_terms(void);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
