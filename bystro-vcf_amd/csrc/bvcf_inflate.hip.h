@@ -12,6 +12,13 @@
 // and the write-out.  Per wave in LDS: a 32 KiB window of the output (the most a match may reach back), written to
 // memory in 16 KiB segments as it fills; a 2 KiB ring of compressed input; a 10-bit literal/length table and a 9-bit
 // distance table with canonical-code fallbacks for longer codes.
+//
+// What is refused: an over-subscribed code is (inf_build), an INCOMPLETE one is not -- no completeness check is built.
+// zlib refuses thirty 5-bit distance codes, a literal/length code whose Kraft sum is below 1 over two or more codes and
+// an incomplete code-length code; this decoder accepts all three (all three windows, rc 0) and, as long as none of the
+// unused codes occurs, gives the text the used codes spell (tests/test_gpu_inflate_craft.py::test_lenient_members).  An
+// unused code that does occur finds an empty table entry and no code in the canonical walk: kInfBadSymbol /
+// kInfBadDistance / kInfBadCodeLengths.  The block's CRC-32 (k_crc32, compared by the caller) guards the text either way.
 #pragma once
 
 #include "bvcf_common.hip.h"
