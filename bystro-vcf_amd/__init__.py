@@ -46,12 +46,12 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels"]
+                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
                 "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx",
-                "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms"]
+                "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms", "bvcf_bed_row"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -60,6 +60,7 @@ EXPORTS = [
     "bvcf_allreduce_counters", "bvcf_device_count", "bvcf_device_pci_bus_id", "bvcf_path", "bvcf_config_defaults", "bvcf_config_more_defaults", "bvcf_string_header", "bvcf_format_tsv", "bvcf_run_buffer", "bvcf_run_fd", "bvcf_decompress_fd", "bvcf_bgzf_inflate_device", "bvcf_bgzf_deflate_device", "bvcf_free",
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
     "bvcf_site_gate_defaults", "bvcf_set_site_gate", "bvcf_site_gate_count", "bvcf_config_gate_defaults",
+    "bvcf_enable_bed_rows", "bvcf_reserve_bed_rows", "bvcf_bed_rows", "bvcf_config_plink_defaults",
 ]
 
 
@@ -116,9 +117,22 @@ def make_site_gate(minMaf=0.0, maxMaf=1.0, minMac=0, maxMissing=1.0, hwe=0.0):
 GATE_KEYS = ("minMaf", "maxMaf", "minMac", "maxMissing", "hwe")
 
 
+CONFIG_MORE_PLINK = 2  # BVCF_CONFIG_MORE_PLINK in Config.reserved[1]: ... up to plink_prefix (and so the gate fields too)
+BED_MAGIC = b"\x6c\x1b\x01"  # a variant-major PLINK 1 .bed
+# class -> .bed code with A1 = the row's ALT: none 3 (hom A2), het 2, hom 0 (hom A1), missing 1
+BED_CODE = (3, 2, 0, 1)
+
+
+class BedRowsInfo(C.Structure):
+    """bvcf_bed_rows_info"""
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_uint64), ("row_bytes", C.c_uint32), ("reserved", C.c_uint32),
+                ("need_bytes", C.c_uint64)]
+
+
 class ConfigMore(C.Structure):
     """bvcf_config_more: bvcf_config and the fields that came after it stopped growing"""
-    _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p), ("site_gate", SiteGate), ("site_filter_path", C.c_char_p)]
+    _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p), ("site_gate", SiteGate), ("site_filter_path", C.c_char_p),
+                ("plink_prefix", C.c_char_p)]
 
 
 class Result(C.Structure):
@@ -378,8 +392,31 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
             more.site_filter_path = keep[-1]
         c.reserved[0] = CONFIG_MORE
         c.reserved[1] = CONFIG_MORE_GATE
+    if cfg.get("plinkOutput"):  # PREFIX.bed / .bim / .fam of the run's rows (the third marker implies the gate fields)
+        if not c.reserved[1]:
+            more.site_gate = make_site_gate()
+        keep.append(str(cfg["plinkOutput"]).encode())
+        more.plink_prefix = keep[-1]
+        c.reserved[0] = CONFIG_MORE
+        c.reserved[1] = CONFIG_MORE_PLINK
     c._keep = keep
     return c
+
+
+def bed_row(cmap, n_samples, sparse=False, out=None):
+    """bvcf_bed_row: one class map -- dense, padded to 16 bytes as the library lays it out, or a short list (uint32 n, then
+    n entries) -- into the ceil(S / 4) bytes of its .bed row (host code, no device).  out: a uint8 array to write into at
+    offset 0 (the return value is then the length); otherwise the row is returned as bytes.  cmap None: a record without a
+    map"""
+    rb = (n_samples + 3) // 4
+    buf = out if out is not None else np.zeros(rb, dtype=np.uint8)
+    src = None if cmap is None else np.ascontiguousarray(np.frombuffer(bytes(cmap), dtype=np.uint8))
+    lib.bvcf_bed_row.restype = C.c_int
+    lib.bvcf_bed_row.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+    n = lib.bvcf_bed_row(None if src is None else src.ctypes.data, int(sparse), n_samples, buf.ctypes.data)
+    if n != rb:
+        raise BvcfError(E_ARG, "bvcf_bed_row")
+    return n if out is not None else buf.tobytes()
 
 
 def hwe_exact(het, hom, other):
@@ -438,7 +475,8 @@ def string_header(cfg=None):
 def run_buffer(vcf_bytes, cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     """readVcf on an in-memory VCF through the HIP path.
     -> (rc, TSV body bytes (no header line), log text, n data lines)"""
-    c = make_config(cfg, device, max_batch_bytes, n_format_threads)
+    # (a Config -- make_config's, or the head of a ConfigMore filled by hand -- is passed on as it is)
+    c = cfg if isinstance(cfg, Config) else make_config(cfg, device, max_batch_bytes, n_format_threads)
     out, log = C.c_void_p(), C.c_void_p()
     n_out, n_log, n_lines = C.c_size_t(), C.c_size_t(), C.c_uint64()
     rc = lib.bvcf_run_buffer(C.byref(c), vcf_bytes, len(vcf_bytes), C.byref(out), C.byref(n_out), C.byref(log),
@@ -701,7 +739,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -715,6 +753,13 @@ class Ctx:
         if pair_stats:  # bvcf_enable_pair_stats: the pair tables behind every chain (read with pair_stats())
             lib.bvcf_enable_pair_stats.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_pair_stats(self.h)
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+        if bed_rows:  # bvcf_enable_bed_rows: the .bed rows behind every chain (read with bed_rows() after each collect)
+            lib.bvcf_enable_bed_rows.argtypes = [C.c_void_p]
+            rc = lib.bvcf_enable_bed_rows(self.h)
             if rc:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
@@ -847,6 +892,35 @@ class Ctx:
         g = gate if isinstance(gate, SiteGate) else make_site_gate(**gate)
         lib.bvcf_set_site_gate.argtypes = [C.c_void_p, C.c_void_p]
         self._check(lib.bvcf_set_site_gate(self.h, C.byref(g)))
+
+    def bed_rows_info(self):
+        """bvcf_bed_rows: the BedRowsInfo of the batch collected last (need_bytes is set after BVCF_E_CAPACITY too)"""
+        info = BedRowsInfo()
+        lib.bvcf_bed_rows.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_bed_rows(self.h, C.byref(info)))
+        return info
+
+    def bed_rows(self):
+        """the .bed rows of the batch collected last -> a uint8 array (n_rows, row_bytes), copied out of the slot"""
+        info = self.bed_rows_info()
+        n = int(info.n_rows) * int(info.row_bytes)
+        if not n:
+            return np.zeros((0, int(info.row_bytes)), dtype=np.uint8)
+        buf = (C.c_uint8 * n).from_address(info.rows)
+        return np.frombuffer(buf, dtype=np.uint8).reshape(int(info.n_rows), int(info.row_bytes)).copy()
+
+    def reserve_bed_rows(self, nbytes):
+        """bvcf_reserve_bed_rows: grow the arena of the .bed rows (no batch in flight)"""
+        lib.bvcf_reserve_bed_rows.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(lib.bvcf_reserve_bed_rows(self.h, int(nbytes)))
+
+    def bench_bed_kernels(self):
+        """the .bed kernels over the first slot's last bench chain -> (ms of [k_bed_count + k_bed_scan + k_bed_index, k_bed_rows], rows, bytes)"""
+        ms = (C.c_float * 2)()
+        out = (C.c_uint64 * 2)()
+        lib.bvcf_bench_bed_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(lib.bvcf_bench_bed_kernels(self.h, ms, out))
+        return list(ms), int(out[0]), int(out[1])
 
     def bench_gate_kernels(self):
         """the gate kernels over the last bench block of the ctx -> ms of [k_site_gate, k_site_hwe]"""

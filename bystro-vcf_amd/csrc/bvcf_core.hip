@@ -121,6 +121,15 @@ struct Slot {
   DevBuf<uint32_t> d_pr_bt;
   // bvcf_set_site_gate with hwe_p (bvcf_sitegate.hip.h): [0] the number of rows left to k_site_hwe, then their slots (follows max_alleles)
   DevBuf<uint32_t> d_gate_list;
+  // bvcf_enable_bed_rows (bvcf_bedrows.hip.h): the first row of every line (follows max_lines), the batch's row count, and
+  // the arena of the packed rows with its pinned copy -- an arena with a bound of its own (bvcf_ctx.bed_cap)
+  DevBuf<uint32_t> d_bed_base, d_bed_tile;
+  DevBuf<uint2> d_bed_src;  // a row's map (follows max_alleles)
+  DevBuf<unsigned long long> d_bed_total;
+  PinBuf<unsigned long long> h_bed_total;
+  DevBuf<uint8_t> d_bed;
+  PinBuf<uint8_t> h_bed;
+  uint64_t cap_bed = 0;
   // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
   // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
@@ -172,6 +181,11 @@ struct bvcf_ctx : bvcf_ctx_plan {
   // bvcf_set_site_gate on a file with samples, some criterion not neutral: k_site_gate / k_site_hwe behind k_finish
   bool gate_on = false;
   bvcf_site_gate gate{};
+  // bvcf_enable_bed_rows on a file with samples: k_bed_count / k_bed_scan / k_bed_index / k_bed_rows at the end of every chain; bed_cap is
+  // what a slot's arena holds (bvcf_reserve_bed_rows grows it), bed_last the batch collected last (bvcf_bed_rows)
+  bool bed_asked = false, bed_on = false;
+  uint64_t bed_cap = 0;
+  bvcf_bed_rows_info bed_last{};
   const void *bench_src = nullptr;  // the last block of the last bvcf_bench_device* call (bvcf_bench_gate_kernels)
   size_t bench_nbytes = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
@@ -457,8 +471,31 @@ int alloc_gate_list(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
+// bvcf_enable_bed_rows: the lines' first rows (follow max_lines) and the counter; the arena and its pinned copy when the
+// ctx's bound has grown past what the slot holds
+int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
+  if (!c->bed_on) return BVCF_OK;
+  if (s.d_bed_base.size() < c->max_lines) {
+    HIP_TRY(c, s.d_bed_base.alloc(c->max_lines));
+    HIP_TRY(c, s.d_bed_tile.alloc(c->max_lines / kBedTile + 2));
+  }
+  if (s.d_bed_src.size() < c->max_alleles) HIP_TRY(c, s.d_bed_src.alloc(c->max_alleles));
+  if (!s.d_bed_total) {
+    HIP_TRY(c, s.d_bed_total.alloc(1));
+    HIP_TRY(c, s.h_bed_total.alloc(1));
+  }
+  if (s.cap_bed < c->bed_cap) {
+    s.cap_bed = 0;
+    HIP_TRY(c, s.d_bed.alloc(c->bed_cap + 16));
+    HIP_TRY(c, s.h_bed.alloc(c->bed_cap + 16));
+    s.cap_bed = c->bed_cap;
+  }
+  return BVCF_OK;
+}
+
 int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_gate_list(c, s)) return rc;
+  if (const int rc = alloc_bed_rows(c, s)) return rc;
   if (!c->ss_on && !c->pr_on) return BVCF_OK;
   s.d_pr_planes.reset();
   s.cap_pr_tiles = 0;
@@ -573,7 +610,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on;  // (the per-sample and pair counts are made from the maps on the device)
+  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on;  // (the per-sample and pair counts and the .bed rows are made from the maps on the device)
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -693,6 +730,34 @@ void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *sl
   if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
 }
 
+// the slot holds everything the .bed kernels write, sized for the ctx's current capacities
+bool bed_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.d_bed && s.d_bed_total && s.d_bed_base.size() >= c->max_lines && s.d_bed_src.size() >= c->max_alleles;
+}
+
+BedArgs make_bed_args(bvcf_ctx *c, Slot &s) {
+  BedArgs ba{};
+  ba.line_base = s.d_bed_base;
+  ba.tile_base = s.d_bed_tile;
+  ba.row_src = s.d_bed_src;
+  ba.row_cap = (uint32_t)s.d_bed_src.size();
+  ba.total = s.d_bed_total;
+  ba.out = s.d_bed;
+  ba.cap = s.cap_bed;
+  return ba;
+}
+
+// bvcf_enable_bed_rows: the end of a chain with samples -- every row's place in output order, then the rows themselves
+// into the slot's arena (bvcf_bedrows.hip.h; bvcf_collect copies the used part)
+void launch_bed_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if (!c->bed_on || !slot || !bed_ready(c, *slot)) return;
+  const BedArgs ba = make_bed_args(c, *slot);
+  hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
+  hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, st, a, ba);
+  hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
+  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ba);
+}
+
 // bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
 // (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
 // ... and, with bvcf_enable_pair_stats, the batch's pair tables from the same row lists (bvcf_pairstats.hip.h): the list
@@ -780,6 +845,7 @@ void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t 
   launch_site_gate(c, a, st, slot);
   if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
   launch_sample_stats(c, a, st, slot);
+  launch_bed_rows(c, a, st, slot);
 }
 
 uint32_t census_grid(const bvcf_ctx *c, uint32_t n_chunks) {
@@ -884,6 +950,7 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
         if (a.wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
     }
   launch_sample_stats(c, a, st, slot);
+  launch_bed_rows(c, a, st, slot);
 }
 
 // the kernel chain for one resident block; ev_gt0 / ev_gt1 (optional) bracket the dominant kernel (k_gt on the census path,
@@ -1107,6 +1174,8 @@ int launch_batch(bvcf_ctx *c, Slot &s, const uint8_t *src, size_t nbytes) {
   }
   HIP_TRY(c, hipEventRecord(s.ev_k1, s.stream));
   HIP_TRY(c, hipMemcpyAsync(s.h_counters, s.d_counters, sizeof(BatchCounters), hipMemcpyDeviceToHost, s.stream));
+  if (c->bed_on && s.d_bed_total)
+    HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   if (c->render) {
     HIP_TRY(c, hipMemcpyAsync(s.h_rtotals, s.d_rtotals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
     // (Tried: as much of the stream as the last batch's rows-per-text ratio predicts copied to the host right here,
@@ -1812,7 +1881,7 @@ static BatchNeeds batch_needs(const bvcf_ctx *c, const Slot &s, const BatchCount
   n.n_alleles = n.extras_at + ctr.n_alleles;
   n.n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
   n.need_alleles = std::max<uint64_t>(std::max<uint64_t>(n.n_alleles, ctr.n_errs), n.n_tasks);
-  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on) && c->n_samples;
+  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on) && c->n_samples;
   n.cmap_need = maps ? cmap_bytes_of(c, ctr) : 0;
   n.fits = ctr.n_lines <= s.cap_lines && n.need_alleles <= s.cap_alleles && n.cmap_need <= s.cap_cmap;
   return n;
@@ -2019,7 +2088,7 @@ static void fill_result(const bvcf_ctx *c, const Slot &s, const Collected &k, ui
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = ((c->ss_on || c->pr_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
+  r->cmap = ((c->ss_on || c->pr_on || c->bed_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage.get() : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = k.was_bgzf ? s.h_text.get() : nullptr;
@@ -2100,7 +2169,14 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     c->err = "internal error: streaming tile quota or class-map slot range exceeded";
     return BVCF_E_HIP;
   }
-  if (!k.need.fits) {
+  // bvcf_enable_bed_rows: the rows the batch packs, against the slot's arena (a batch that does not fit otherwise may
+  // count too few: it asks again)
+  c->bed_last = bvcf_bed_rows_info{};
+  c->bed_last.row_bytes = c->bed_on ? (c->n_samples + 3u) / 4u : 0u;
+  const bool bed = c->bed_on && bed_ready(c, s);
+  const uint64_t bed_rows = bed ? *s.h_bed_total : 0, bed_bytes = bed_rows * c->bed_last.row_bytes;
+  c->bed_last.need_bytes = bed_bytes;
+  if (!k.need.fits || bed_bytes > s.cap_bed) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
     r->need_alleles = k.need.need_alleles;
@@ -2123,6 +2199,7 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   if (!rc) rc = copy_records(c, s, k);
   if (!rc) rc = copy_text(c, s, k);
   if (!rc) rc = copy_names(c, s, k);
+  if (!rc && bed_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_bed, s.d_bed, bed_bytes, hipMemcpyDeviceToHost, s.stream));
   if (rc) return rc;
   e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) {
@@ -2130,6 +2207,10 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     return BVCF_E_HIP;
   }
   fill_result(c, s, k, filter_errs(c, s, k), r);
+  if (bed) {
+    c->bed_last.rows = s.h_bed;
+    c->bed_last.n_rows = bed_rows;
+  }
   add_totals(c, s, k, r);
   return BVCF_OK;
 }
@@ -2229,6 +2310,56 @@ int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
   if (reset) HIP_TRY(c, hipMemsetAsync(c->d_pr_tot, 0, bytes, st));
   HIP_TRY(c, hipStreamSynchronize(st));
   return BVCF_OK;
+}
+
+int bvcf_enable_bed_rows(bvcf_ctx *c) {
+  if (!c) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_enable_bed_rows with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  c->bed_asked = true;
+  if (!c->n_samples || c->bed_on) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  // a biallelic line has at least two text bytes per sample and gives a quarter byte per sample; lines with many ALTs at
+  // few samples outrun this and grow the arena (BVCF_E_CAPACITY, bvcf_reserve_bed_rows)
+  c->bed_cap = std::max<uint64_t>(c->bed_cap, c->p.max_batch_bytes / 4);
+  c->bed_on = true;
+  c->bed_last = bvcf_bed_rows_info{};
+  c->bed_last.row_bytes = (c->n_samples + 3u) / 4u;
+  for (auto &s : c->slots)
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_reserve_bed_rows(bvcf_ctx *c, uint64_t bytes) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->bed_asked) {
+    c->err = "bvcf_reserve_bed_rows: bvcf_enable_bed_rows was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (c->in_flight) {
+    c->err = "bvcf_reserve_bed_rows with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->bed_on) return BVCF_OK;
+  c->bed_cap = std::max<uint64_t>(c->bed_cap, (bytes + 63) & ~63ull);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_bed_rows(const bvcf_ctx *c, bvcf_bed_rows_info *out) {
+  if (!c || !out || !c->bed_asked) return BVCF_E_ARG;
+  *out = c->bed_last;
+  return BVCF_OK;
+}
+
+int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out) {
+  if (!out || !S) return -1;
+  bed_row_host(cmap_or_list, sparse != 0, S, out);
+  return (int)((S + 3u) / 4u);
 }
 
 void bvcf_site_gate_defaults(bvcf_site_gate *g) {
@@ -2603,6 +2734,42 @@ int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(s.stream));
   for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  return BVCF_OK;
+}
+
+int bvcf_bench_bed_kernels(bvcf_ctx *c, float ms[2], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_bed_kernels with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  Slot &s = c->slots[0];
+  if (!c->bed_on || !bed_ready(c, s)) {
+    c->err = "bvcf_bench_bed_kernels: the ctx has no bed rows";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
+  const BedArgs ba = make_bed_args(c, s);
+  Event ev[3];
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba);
+  hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, s.stream, a, ba);
+  hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, ba);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < 2; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  out[0] = *s.h_bed_total;
+  out[1] = out[0] * ((c->n_samples + 3u) / 4u);
+  if (out[1] > s.cap_bed) {
+    c->err = "bvcf_bench_bed_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[1]) + " bytes";
+    return BVCF_E_CAPACITY;
+  }
   return BVCF_OK;
 }
 

@@ -57,6 +57,9 @@
 //   (bvcf_set_site_gate, right behind k_finish and in front of everything that reads a record's ac: k_site_gate takes the
 //    rows out that fail --minMaf / --maxMaf / --minMac / --maxMissing / --hwe, k_site_hwe runs the exact test of the rows
 //    whose support is too long for one thread, a wave per row -- bvcf_sitegate.hip.h)
+//   (bvcf_enable_bed_rows, at the end of the chain of a file with samples: k_bed_count / k_bed_scan / k_bed_index give every row its
+//    place in output order, k_bed_rows recodes its class map -- dense or short list -- into the unpadded row of a PLINK
+//    .bed file, the rows back to back in an arena of their own -- bvcf_bedrows.hip.h)
 //   (bvcf_params.want_name_lists, after k_finish: k_name_len / k_name_scan / k_name_write render the het / hom / missing
 //    sample-name lists of every output allele as text -- main.go:612-656 -- see bvcf_names.hip.h)
 //
@@ -103,5 +106,6 @@
 #include "bvcf_sitegate.hip.h"
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
+#include "bvcf_bedrows.hip.h"
 #include "bvcf_inflate.hip.h"
 #include "bvcf_deflate.hip.h"

@@ -390,6 +390,11 @@ void Driver::device_main(DevWorker *W) {
       // grow, resubmit everything still queued on this device
       wait_formatted(n_jobs);
       outstanding.clear();
+      uint64_t bed_need = 0;
+      if (wants_plink(c_)) {
+        bvcf_bed_rows_info bi;
+        if (bvcf_bed_rows(W->ctx, &bi) == BVCF_OK) bed_need = bi.need_bytes;
+      }
       // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
       const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
       if (ss) {
@@ -427,8 +432,10 @@ void Driver::device_main(DevWorker *W) {
         fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
         return;
       }
+      // (--plinkOutput: what the batch that asked reported for its .bed rows, read before the collects above replace it)
       r = bvcf_reserve(W->ctx, res.need_lines + res.need_lines / 4 + 64, res.need_alleles + res.need_alleles / 4 + 64,
                        res.need_cmap_bytes + res.need_cmap_bytes / 4 + 4096);
+      if (r == BVCF_OK && bed_need) r = bvcf_reserve_bed_rows(W->ctx, bed_need + bed_need / 4 + 4096);
       for (size_t k = 0; k < in_flight.size() && r == BVCF_OK; k++) r = submit(in_flight[k]);
       if (r == BVCF_OK) {
         r = bvcf_collect(W->ctx, &res);
@@ -451,6 +458,10 @@ void Driver::device_main(DevWorker *W) {
     j.b = b;
     j.res = res;
     j.has_res = true;
+    if (wants_plink(c_) && bvcf_bed_rows(W->ctx, &j.bed) != BVCF_OK) {  // --plinkOutput: the rows collected with this batch
+      fail(std::string("bvcf_bed_rows: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      return;
+    }
     j.job = n_jobs;
     outstanding.emplace_back(n_jobs, n_collects - 1);
     n_jobs++;
@@ -545,14 +556,19 @@ void Driver::formatter_main(DevWorker *W) {
         format_parts(c_, &j.res, text, *R_.names, R_.ratios.get(), W->fmt_pool.get(), *it.parts);
       else
         for (auto &q : *it.parts) q.clear();
-      if (R_.arrow && j.res.dosage) {
+      const bool plink = R_.bed_fd >= 0;
+      if ((R_.arrow && j.res.dosage) || plink) {
         // the dosage rows go into the file in input order (main.go:576-584): the sink runs this when it is the block's
-        // turn; the result slot and the text stay on loan until then
+        // turn; the result slot and the text stay on loan until then -- and so do the batch's .bed rows and .bim lines
         auto keep = std::make_shared<FmtJob>(std::move(j));
-        it.in_order = [this, keep, text, release]() {
+        it.in_order = [this, keep, text, release, plink]() {
           if (!dosage_failed_.load() && append_dosage(R_, &keep->res, text)) {
             dosage_failed_.store(true);
             fail("dosage matrix: write failed", BVCF_E_FATAL);
+          }
+          if (plink && !plink_failed_.load() && append_plink(R_, &keep->res, text, keep->bed)) {
+            plink_failed_.store(true);
+            fail("plinkOutput: write failed", BVCF_E_FATAL);
           }
           release();
         };
@@ -580,6 +596,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return BVCF_E_IO;
     }
     if (open_site_report(c_, &sg_fd_, &msg)) {  // --siteFilterReport: likewise
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return BVCF_E_IO;
+    }
+    if (open_plink(R_, &msg)) {  // --plinkOutput: likewise, all three files
       dprintf(fd_err_, "%s\n", msg.c_str());
       return BVCF_E_IO;
     }
@@ -699,6 +719,7 @@ int Driver::run(uint64_t *n_lines_in) {
   sink_->join();
   if (sink_->write_failed()) fail("write failed", BVCF_E_FATAL);
   if (close_dosage(R_)) fail("dosage matrix: write failed", BVCF_E_FATAL);
+  if (close_plink(R_)) fail("plinkOutput: write failed", BVCF_E_FATAL);
   if (bgzf_) {
     // the last partial piece; the end-of-file block only after a run that succeeded (htslib reports its absence)
     const double t0 = now_s();

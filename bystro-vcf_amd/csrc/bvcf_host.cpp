@@ -27,10 +27,17 @@ void bvcf_config_more_defaults(bvcf_config_more *c) {
 }
 
 void bvcf_config_gate_defaults(bvcf_config_more *c) {
-  memset(c, 0, sizeof *c);
+  // (up to site_filter_path: a caller built when that was the last field owns no more)
+  memset(c, 0, offsetof(bvcf_config_more, plink_prefix));
   bvcf_config_more_defaults(c);
   c->base.reserved[1] = BVCF_CONFIG_MORE_GATE;
   bvcf_site_gate_defaults(&c->site_gate);
+}
+
+void bvcf_config_plink_defaults(bvcf_config_more *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_gate_defaults(c);
+  c->base.reserved[1] = BVCF_CONFIG_MORE_PLINK;
 }
 
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
@@ -102,6 +109,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   int rc = open_sample_stats(c, &ss_fd, &msg);
   if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
   if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
+  if (rc == BVCF_OK) rc = open_plink(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -151,11 +159,23 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         rc = BVCF_E_FATAL;
         break;
       }
+      if (wants_plink(c)) {  // --plinkOutput: the batch's .bed rows and .bim lines
+        bvcf_bed_rows_info bed;
+        if (bvcf_bed_rows(R.ctx, &bed) != BVCF_OK || append_plink(R, &res, vcf + pos, bed)) {
+          l.append("plinkOutput: write failed\n");
+          rc = BVCF_E_FATAL;
+          break;
+        }
+      }
       pos += nb;
     }
   }
   if (close_dosage(R) && rc == BVCF_OK) {
     l.append("dosage matrix: write failed\n");
+    rc = BVCF_E_FATAL;
+  }
+  if (close_plink(R) && rc == BVCF_OK) {
+    l.append("plinkOutput: write failed\n");
     rc = BVCF_E_FATAL;
   }
   if (ss_fd >= 0) {  // --sampleStats: the run's table, after a successful run only

@@ -713,6 +713,10 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     *msg = "Couldn't write sample list file";
     return BVCF_E_FATAL;
   }
+  if (write_plink_heads(R)) {  // --plinkOutput: the .fam and the .bed magic, once the (kept) names are known
+    *msg = std::string("plinkOutput: write failed: ") + strerror(errno);
+    return BVCF_E_IO;
+  }
   bvcf_params &p = R.params;
   memset(&p, 0, sizeof p);
   p.abi_version = BVCF_ABI_VERSION;
@@ -832,6 +836,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && wants_plink(R.cfg)) {  // --plinkOutput: the .bed rows of every ctx of the run
+    rc = bvcf_enable_bed_rows(*ctx);
+    if (rc) {
+      *msg = std::string("bvcf_enable_bed_rows: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (const bvcf_config_more *m = rc == BVCF_OK ? gate_config(R.cfg) : nullptr) {  // the site gate of every ctx of the run
     rc = bvcf_set_site_gate(*ctx, &m->site_gate);
     if (rc) {
@@ -857,10 +869,41 @@ int open_ctx(Run &R, std::string *msg, const uint8_t *data, size_t n_data) {
   return rc;
 }
 
+// The four columns a row is known by -- chrom, pos, ref, alt as the TSV prints them (main.go:570-601) -- appended to o with
+// `sep` between them: "chrom:pos:ref:alt" is the locus string of a dosage row.  at[0..3]: where each column starts in o,
+// at[4]: the end
+static void append_locus(std::string &o, const bvcf_line &L, const bvcf_allele &A, const char *row, char sep, size_t at[5]) {
+  at[0] = o.size();
+  if (L.fend[0] < 4 || row[0] != 'c') o.append("chr");
+  o.append(row, L.fend[0]);
+  o.push_back(sep);
+  at[1] = o.size();
+  if (A.flags & BVCF_ALLELE_POS_TEXT)
+    o.append(row + L.fend[0] + 1, L.fend[1] - L.fend[0] - 1);
+  else
+    append_ll(o, A.pos);
+  o.push_back(sep);
+  at[2] = o.size();
+  o.push_back((char)A.ref);
+  o.push_back(sep);
+  at[3] = o.size();
+  if (A.kind == BVCF_ALT_BASE) {
+    o.push_back((char)A.alt_base);
+  } else if (A.kind == BVCF_ALT_INS) {
+    o.push_back('+');
+    o.append(row + (A.alt_off - L.off), A.alt_len);
+  } else {
+    o.push_back('-');
+    append_ll(o, A.alt_len);
+  }
+  at[4] = o.size();
+}
+
 // the Arrow rows of one collected batch, in input order (main.go:576-584): "chrom:pos:ref:alt" + one int8 per sample
 int append_dosage(Run &R, const bvcf_result *r, const uint8_t *block) {
   if (!R.arrow || !r->dosage) return BVCF_OK;
   std::string locus;
+  size_t at[5];
   for (uint32_t li = 0; li < r->n_lines; li++) {  // (a dosage matrix needs samples: never the packed form)
     const bvcf_line &L = r->lines[li];
     if (L.status != BVCF_LINE_OK) continue;
@@ -870,25 +913,7 @@ int append_dosage(Run &R, const bvcf_result *r, const uint8_t *block) {
       const bvcf_allele &A = r->alleles[slot];
       if (A.ac == 0) continue;  // main.go:558-560
       locus.clear();
-      if (L.fend[0] < 4 || row[0] != 'c') locus.append("chr");
-      locus.append(row, L.fend[0]);
-      locus.push_back(':');
-      if (A.flags & BVCF_ALLELE_POS_TEXT)
-        locus.append(row + L.fend[0] + 1, L.fend[1] - L.fend[0] - 1);
-      else
-        append_ll(locus, A.pos);
-      locus.push_back(':');
-      locus.push_back((char)A.ref);
-      locus.push_back(':');
-      if (A.kind == BVCF_ALT_BASE) {
-        locus.push_back((char)A.alt_base);
-      } else if (A.kind == BVCF_ALT_INS) {
-        locus.push_back('+');
-        locus.append(row + (A.alt_off - L.off), A.alt_len);
-      } else {
-        locus.push_back('-');
-        append_ll(locus, A.alt_len);
-      }
+      append_locus(locus, L, A, row, ':', at);
       if (bvcf_arrow_append(R.arrow, locus.data(), (uint32_t)locus.size(), r->dosage + (size_t)slot * r->dosage_stride))
         return BVCF_E_FATAL;
     }
@@ -896,11 +921,96 @@ int append_dosage(Run &R, const bvcf_result *r, const uint8_t *block) {
   return BVCF_OK;
 }
 
+int open_plink(Run &R, std::string *msg) {
+  if (!wants_plink(R.cfg)) return BVCF_OK;
+  const std::string prefix = plink_prefix(R.cfg);
+  struct {
+    const char *ext;
+    int *fd;
+  } files[3] = {{".bed", &R.bed_fd}, {".bim", &R.bim_fd}, {".fam", &R.fam_fd}};
+  for (auto &f : files) {
+    const std::string path = prefix + f.ext;
+    *f.fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.fd < 0) {
+      *msg = "open " + path + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  return BVCF_OK;
+}
+
+// .fam: a line per (kept) sample in header order, the name as --sample writes it for family and individual, no parents, no
+// sex, no phenotype; .bed: the magic of the variant-major form
+int write_plink_heads(Run &R) {
+  if (R.bed_fd < 0) return BVCF_OK;
+  std::string fam;
+  for (size_t i = 9; i < R.pre.header.size(); i++) {
+    fam.append(R.pre.header[i]);
+    fam.push_back('\t');
+    fam.append(R.pre.header[i]);
+    fam.append("\t0\t0\t0\t-9\n");
+  }
+  static const char kMagic[3] = {0x6C, 0x1B, 0x01};
+  return (write_all(R.fam_fd, fam.data(), fam.size()) || write_all(R.bed_fd, kMagic, sizeof kMagic)) ? BVCF_E_IO : BVCF_OK;
+}
+
+// the rows of one collected batch: their bytes as the device packed them, one write; a .bim line per row -- the rows
+// bvcf_bed_rows counts are the rows this loop visits, in this order
+int append_plink(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_bed_rows_info &bed) {
+  if (R.bed_fd < 0 || !r->n_samples) return BVCF_OK;
+  std::string bim, locus;
+  size_t at[5];
+  uint64_t n_rows = 0;
+  for (uint32_t li = 0; li < r->n_lines; li++) {
+    const bvcf_line &L = r->lines[li];
+    if (L.status != BVCF_LINE_OK) continue;
+    const char *row = row_of(r, block, li, L);
+    for (uint32_t k = 0; k < L.n_rec; k++) {
+      const bvcf_allele &A = r->alleles[k ? L.rec_first + k - 1 : li];
+      if (A.ac == 0) continue;  // main.go:558-560
+      locus.clear();
+      append_locus(locus, L, A, row, ':', at);
+      // chrom, locus, 0 cM, pos, A1 = the ALT, A2 = the REF
+      bim.append(locus, at[0], at[1] - 1 - at[0]);
+      bim.push_back('\t');
+      bim.append(locus);
+      bim.append("\t0\t");
+      bim.append(locus, at[1], at[2] - 1 - at[1]);
+      bim.push_back('\t');
+      bim.append(locus, at[3], at[4] - at[3]);
+      bim.push_back('\t');
+      bim.append(locus, at[2], at[3] - 1 - at[2]);
+      bim.push_back('\n');
+      n_rows++;
+    }
+  }
+  if (n_rows != bed.n_rows || (n_rows && !bed.rows)) return BVCF_E_FATAL;  // (.bed and .bim never disagree in length)
+  if (write_all(R.bed_fd, (const char *)bed.rows, (size_t)(bed.n_rows * bed.row_bytes))) return BVCF_E_IO;
+  return write_all(R.bim_fd, bim.data(), bim.size()) ? BVCF_E_IO : BVCF_OK;
+}
+
+int close_plink(Run &R) {
+  int rc = BVCF_OK;
+  for (int *fd : {&R.bed_fd, &R.bim_fd, &R.fam_fd}) {
+    if (*fd >= 0 && close(*fd)) rc = BVCF_E_IO;
+    *fd = -1;
+  }
+  return rc;
+}
+
 int close_dosage(Run &R) {
   if (!R.arrow) return BVCF_OK;
   const int rc = bvcf_arrow_close(R.arrow);
   R.arrow = nullptr;
   return rc;
+}
+
+// --plinkOutput, after a BVCF_E_CAPACITY: the arena of the .bed rows grown to what the batch reported, like need_cmap_bytes
+int reserve_bed_need(bvcf_ctx *ctx, const bvcf_config *c) {
+  if (!wants_plink(c)) return BVCF_OK;
+  bvcf_bed_rows_info b;
+  if (bvcf_bed_rows(ctx, &b) != BVCF_OK) return BVCF_OK;
+  return bvcf_reserve_bed_rows(ctx, b.need_bytes + b.need_bytes / 4 + 4096);
 }
 
 // submit one block and collect it, growing the result reservation when the batch asks for it
@@ -919,6 +1029,7 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
     }
     rc = bvcf_reserve(R.ctx, res->need_lines + res->need_lines / 4 + 64, res->need_alleles + res->need_alleles / 4 + 64,
                       res->need_cmap_bytes + res->need_cmap_bytes / 4 + 4096);
+    if (rc == BVCF_OK) rc = reserve_bed_need(R.ctx, R.cfg);
     if (rc) {
       *msg = std::string("bvcf_reserve: ") + bvcf_last_error(R.ctx);
       return rc;

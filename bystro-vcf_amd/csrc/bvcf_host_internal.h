@@ -231,6 +231,13 @@ struct Run {
   // then the header with the unselected names cut out, which is what every consumer of the names is to see
   uint32_t n_header_full = 0;
   std::vector<uint32_t> keep_mask;
+  // --plinkOutput: PREFIX.bed / .bim / .fam, opened by open_plink before any device work; prepare_run writes the .fam and
+  // the .bed magic, append_plink a batch's rows and .bim lines in input order, close_plink closes what is open
+  int bed_fd = -1, bim_fd = -1, fam_fd = -1;
+  ~Run() {
+    for (int fd : {bed_fd, bim_fd, fam_fd})
+      if (fd >= 0) close(fd);
+  }
 };
 
 uint32_t choose_path(const Run &R, const uint8_t *data, size_t n);
@@ -245,6 +252,14 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data = nullptr, size_t 
 int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg);
 int open_ctx(Run &R, std::string *msg, const uint8_t *data = nullptr, size_t n_data = 0);
 int append_dosage(Run &R, const bvcf_result *r, const uint8_t *block);
+// --plinkOutput: the three files opened (truncated) -- BVCF_E_IO with one message in *msg; the rows of one collected batch
+// (bed = what bvcf_bed_rows gave for it) behind the .bed as one write, and their .bim lines; the files closed (BVCF_E_IO when
+// a close fails)
+int open_plink(Run &R, std::string *msg);
+int append_plink(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_bed_rows_info &bed);
+int close_plink(Run &R);
+int write_plink_heads(Run &R);  // (prepare_run: the .fam and the .bed magic)
+int reserve_bed_need(bvcf_ctx *ctx, const bvcf_config *c);
 int close_dosage(Run &R);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
 // --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
@@ -269,8 +284,18 @@ inline bool wants_pair_stats(const bvcf_config *c) {
 // --minMaf ... --hwe / --siteFilterReport: the config as a bvcf_config_more that reaches up to site_filter_path (both markers
 // set), or NULL -- nothing behind pair_stats_path is read for a caller built before the fields were there
 inline const bvcf_config_more *gate_config(const bvcf_config *c) {
-  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] == BVCF_CONFIG_MORE_GATE) ? reinterpret_cast<const bvcf_config_more *>(c)
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_GATE) ? reinterpret_cast<const bvcf_config_more *>(c)
                                                                                        : nullptr;
+}
+// --plinkOutput: bvcf_config_more.plink_prefix of a config that reaches up to it (the third marker); NULL otherwise
+inline const char *plink_prefix(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_PLINK)
+             ? reinterpret_cast<const bvcf_config_more *>(c)->plink_prefix
+             : nullptr;
+}
+inline bool wants_plink(const bvcf_config *c) {
+  const char *p = plink_prefix(c);
+  return p && *p;
 }
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);

@@ -181,6 +181,7 @@ struct FmtJob {
   Block b;
   bvcf_result res;
   bool has_res = false;
+  bvcf_bed_rows_info bed{};  // --plinkOutput: bvcf_bed_rows of the batch (valid as long as res)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };
@@ -295,6 +296,7 @@ class Driver {
   std::atomic<bool> input_is_bgzf_device_{false};
   std::atomic<uint8_t> eol_byte_{'\n'};
   std::atomic<bool> dosage_failed_{false};
+  std::atomic<bool> plink_failed_{false};  // --plinkOutput: likewise
   // stream mode
   std::string source_err_;
   std::unique_ptr<Channel<Block>> ready_q_;

@@ -43,6 +43,8 @@ struct Cli {
   double min_maf = 0.0, max_maf = 1.0, max_missing = 1.0, hwe = 0.0;
   uint32_t min_mac = 0;
   std::string site_report;
+  // extension: --plinkOutput PREFIX, the run's rows as PREFIX.bed / .bim / .fam (the .bed rows packed on the device)
+  std::string plink;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -136,7 +138,8 @@ int parse(int argc, char **argv, Cli &c) {
     // counterpart of the reference's NumCPU workers), the block size, the output's compression
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
         name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
-        name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport") {
+        name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
+        name == "plinkOutput") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -158,6 +161,8 @@ int parse(int argc, char **argv, Cli &c) {
         c.relatedness = val;
       } else if (name == "siteFilterReport") {
         c.site_report = val;
+      } else if (name == "plinkOutput") {
+        c.plink = val;
       } else if (name == "minMac") {
         if (!parse_threshold(val, &c.min_mac)) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
@@ -221,8 +226,9 @@ int main(int argc, char **argv) {
     dprintf(fd_err, "Cannot specify --noOut and --out\n");
     return 1;
   }
-  // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass)
-  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty()) {
+  // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
+  // conversion-only pass)
+  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -234,8 +240,8 @@ int main(int argc, char **argv) {
     }
   }
 
-  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path, the site gate and its report)
-  bvcf_config_gate_defaults(&more);
+  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix)
+  bvcf_config_plink_defaults(&more);
   bvcf_config &cfg = more.base;
   cfg.empty_field = c.empty.c_str();
   cfg.field_delimiter = c.delim.c_str();
@@ -291,6 +297,7 @@ int main(int argc, char **argv) {
   more.site_gate.max_missing = c.max_missing;
   more.site_gate.hwe_p = c.hwe;
   more.site_filter_path = c.site_report.c_str();
+  more.plink_prefix = c.plink.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

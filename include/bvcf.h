@@ -415,6 +415,31 @@ int bvcf_enable_pair_stats(bvcf_ctx *ctx);
  * for the ctx's slots; reset: zero the totals after reading them (out may then be NULL).  BVCF_E_ARG on a ctx on which
  * bvcf_enable_pair_stats was not called. */
 int bvcf_pair_stats(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S: [t][i][j] */, int reset);
+/* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
+ * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
+ * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
+ *   00  the homozygotes list names the sample (a haploid call counts as hom, as in the TSV and the gate)
+ *   01  the missingGenos list names it          10  the heterozygotes list names it          11  no list names it
+ * i.e. class -> code NONE 3, HET 2, HOM 0, MISSING 1; the unused high bits of a row's last byte are 0.  The rows of a batch
+ * lie back to back, without padding, in the order bvcf_format_tsv prints them; a multiallelic line gives one row per output
+ * allele, "this ALT against the rest".  Call bvcf_enable_bed_rows once, before the first submit, like
+ * bvcf_enable_pair_stats; a no-op returning BVCF_OK on a ctx without sample columns (such a ctx has no rows: n_rows 0,
+ * rows NULL).  bvcf_params and the ABI version do not change with it.
+ * The rows go into an arena of the slot with a bound of its own: max_batch_bytes / 4 to begin with (a biallelic line has
+ * two text bytes per sample and gives a quarter byte).  A batch whose rows outrun it comes back BVCF_E_CAPACITY like one
+ * that outruns the class-map arena; bvcf_bed_rows then reports need_bytes, bvcf_reserve_bed_rows(ctx, bytes) -- with no
+ * batch in flight, like bvcf_reserve -- grows the arena, and the batch is submitted again. */
+typedef struct {
+  const uint8_t *rows; /* n_rows * row_bytes bytes; valid as long as the pointers of the bvcf_result collected with them */
+  uint64_t n_rows;
+  uint32_t row_bytes;
+  uint32_t reserved;
+  uint64_t need_bytes; /* what the batch's rows take (also after BVCF_E_CAPACITY, when rows is NULL and n_rows 0) */
+} bvcf_bed_rows_info;
+int bvcf_enable_bed_rows(bvcf_ctx *ctx);
+int bvcf_reserve_bed_rows(bvcf_ctx *ctx, uint64_t bytes);
+/* the rows of the batch bvcf_collect returned last on ctx.  BVCF_E_ARG on a ctx without bvcf_enable_bed_rows */
+int bvcf_bed_rows(const bvcf_ctx *ctx, bvcf_bed_rows_info *out);
 
 /* The per-site QC gate (--minMaf / --maxMaf / --minMac / --maxMissing / --hwe).  size = sizeof(bvcf_site_gate).  A criterion
  * at its neutral value is off; with all of them neutral the ctx allocates and launches nothing for the gate.
@@ -537,6 +562,10 @@ void bvcf_config_defaults(bvcf_config *c); /* setup() defaults, main.go:84-99 */
  * when pair_stats_path was the last field -- nothing behind pair_stats_path is read (or written by
  * bvcf_config_more_defaults). */
 #define BVCF_CONFIG_MORE_GATE 1
+/* ... and a third, a larger value in base.reserved[1]: the struct reaches up to plink_prefix (and so holds the gate
+ * fields: code that asks for BVCF_CONFIG_MORE_GATE asks for "at least").  bvcf_config_plink_defaults sets it; the two
+ * older *_defaults write what they always wrote. */
+#define BVCF_CONFIG_MORE_PLINK 2
 typedef struct {
   bvcf_config base;
   /* --relatedness: bvcf_run_fd / bvcf_run_buffer write the pairwise table of the run's rows here -- one line per unordered
@@ -557,10 +586,19 @@ typedef struct {
    * bvcf_site_gate_count over the batches of the output.  Opened before any device work, written at the end of a
    * successful run.  NULL or "" = no report */
   const char *site_filter_path;
+  /* base.reserved[1] >= BVCF_CONFIG_MORE_PLINK only.  --plinkOutput PREFIX: the run's rows as a PLINK 1 binary fileset,
+   * PREFIX.bed / .bim / .fam.  .bed: 6C 1B 01, then the rows of bvcf_bed_rows in TSV order.  .bim: one line per row,
+   * "chrom \t locus \t 0 \t pos \t alt \t ref \n" with the row's TSV columns and the locus string of its dosage row.  .fam: one
+   * line per (kept) sample in header order, "name \t name \t 0 \t 0 \t 0 \t -9 \n".  All three are opened before any device
+   * work; their bytes do not depend on devices, batch size or input kind, and no other output changes with them.  A file
+   * without sample columns gives a 3-byte .bed and empty .bim / .fam.  NULL or "" = no fileset */
+  const char *plink_prefix;
 } bvcf_config_more;
 void bvcf_config_more_defaults(bvcf_config_more *c); /* bvcf_config_defaults, the marker, pair_stats_path = NULL */
 /* the whole struct: bvcf_config_more_defaults, base.reserved[1] = BVCF_CONFIG_MORE_GATE, a neutral gate, no report */
 void bvcf_config_gate_defaults(bvcf_config_more *c);
+/* the whole struct: bvcf_config_gate_defaults, base.reserved[1] = BVCF_CONFIG_MORE_PLINK, no fileset */
+void bvcf_config_plink_defaults(bvcf_config_more *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -54,6 +54,11 @@ int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p);
  * ctx without a gate, or when no bvcf_bench_device* call went before */
 int bvcf_bench_gate_kernels(bvcf_ctx *ctx, float ms[2]);
 
+/* bvcf_enable_bed_rows: the .bed kernels over the records and class maps the first slot's last bench chain left, with HIP
+ * events around them: ms = {k_bed_count + k_bed_scan + k_bed_index (the row index), k_bed_rows}; out[0] = the rows, out[1] = the bytes
+ * k_bed_rows wrote (rows * row_bytes).  BVCF_E_ARG on a ctx without bed rows, BVCF_E_CAPACITY when the rows outrun the arena */
+int bvcf_bench_bed_kernels(bvcf_ctx *ctx, float ms[2], uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

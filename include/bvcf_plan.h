@@ -127,6 +127,14 @@ double bvcf_hwe_exact(uint32_t het, uint32_t hom, uint32_t other);
  * (het + 2 min(hom, other) <= 2 * terms - 1) is summed by the thread that examines it, a longer one by a wave (k_site_hwe) */
 uint32_t bvcf_hwe_inline_terms(void);
 
+/* The per-row code of the .bed rows (csrc/bvcf_bedrows.hip.h; bvcf_enable_bed_rows in include/bvcf.h), run on the host: the function the device makes every
+ * 16 bytes of a row with, over one row.  cmap_or_list: the row's class map as the library lays it out -- the dense form
+ * (4 * ceil(ceil(S / 4) / 4) bytes are read: a map is padded to 16) or, with sparse != 0, the short list of
+ * BVCF_ALLELE_CMAP_SPARSE (n, then n entries; n is clamped to BVCF_CMAP_SPARSE_MAX, entries past the row ignored); NULL: a
+ * record without a map, every sample missing.  Writes out[0, ceil(S / 4)) and nothing else; returns that length, -1 for
+ * bad arguments. */
+int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
