@@ -46,7 +46,8 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels"]
+                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_deflate_codes"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -463,6 +464,24 @@ def bench_hwe(triples, device=0):
     if rc:
         raise BvcfError(rc, "bvcf_bench_hwe")
     return p
+
+
+def bench_deflate_codes(cases, device=0):
+    """bvcf_bench_deflate_codes: step 4 of k_deflate on each (hll[286], hd[30], text bytes) ->
+    (lens uint8 [n, 335] = 286 + 30 + 19 code lengths, rle uint16 [n, 316] = symbol | extra << 8,
+     out uint32 [n, 8] = kind, header bits, hlit, hdist, hclen, entries, dyn_bytes, fix_bytes)"""
+    hist = np.zeros((len(cases), 317), dtype=np.uint32)
+    for i, (hll, hd, n) in enumerate(cases):
+        hist[i, :286], hist[i, 286:316], hist[i, 316] = hll, hd, n
+    lens = np.zeros((len(cases), 335), dtype=np.uint8)
+    rle = np.zeros((len(cases), 316), dtype=np.uint16)
+    out = np.zeros((len(cases), 8), dtype=np.uint32)
+    lib.bvcf_bench_deflate_codes.restype = C.c_int
+    lib.bvcf_bench_deflate_codes.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = lib.bvcf_bench_deflate_codes(device, hist.ctypes.data, len(cases), lens.ctypes.data, rle.ctypes.data, out.ctypes.data)
+    if rc:
+        raise BvcfError(rc, "bvcf_bench_deflate_codes")
+    return lens, rle, out
 
 
 def string_header(cfg=None):

@@ -2789,6 +2789,38 @@ int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p) {
   return hipMemcpy(p, d_p, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
 }
 
+int bvcf_bench_deflate_codes(int device, const uint32_t *hist, uint32_t n, uint8_t *lens, uint16_t *rle, uint32_t *out) {
+  if (!hist || !lens || !rle || !out) return BVCF_E_ARG;
+  if (!n) return BVCF_OK;
+  for (uint32_t c = 0; c < n; c++) {  // what a piece can give: its end-of-block code, and no more tokens than bytes
+    const uint32_t *h = hist + (size_t)c * kDefCodesIn;
+    uint64_t sum = 0, sum_d = 0;
+    for (uint32_t i = 0; i < kDefLL; i++) sum += h[i];
+    for (uint32_t i = 0; i < kDefDist; i++) sum_d += h[kDefLL + i];
+    if (!h[256] || sum > kDefPiece + 1u || sum_d > kDefPiece || h[kDefLL + kDefDist] > kDefPiece) return BVCF_E_ARG;
+  }
+  if (hipSetDevice(device) != hipSuccess) return BVCF_E_NODEV;
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) return BVCF_E_HIP;
+  const size_t n_rle = kDefLL + kDefDist;
+  DevBuf<uint32_t> d_in, d_out;
+  DevBuf<uint8_t> d_lens;
+  DevBuf<uint16_t> d_rle;
+  if (d_in.alloc((size_t)n * kDefCodesIn) != hipSuccess || d_out.alloc((size_t)n * 8) != hipSuccess ||
+      d_lens.alloc((size_t)n * kDefCodesLens) != hipSuccess || d_rle.alloc((size_t)n * n_rle) != hipSuccess)
+    return BVCF_E_NOMEM;
+  if (hipMemcpy(d_in, hist, (size_t)n * kDefCodesIn * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return BVCF_E_HIP;
+  const uint32_t grid = std::min<uint32_t>(n, (uint32_t)n_cu * 8u);
+  hipLaunchKernelGGL(k_deflate_codes, dim3(grid), dim3(kDefThreads), 0, 0, (const uint32_t *)d_in, n, (uint8_t *)d_lens,
+                     (uint16_t *)d_rle, (uint32_t *)d_out);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return BVCF_E_HIP;
+  if (hipMemcpy(lens, d_lens, (size_t)n * kDefCodesLens, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(rle, d_rle, (size_t)n * n_rle * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(out, d_out, (size_t)n * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return BVCF_E_HIP;
+  return BVCF_OK;
+}
+
 int bvcf_bench_gate_kernels(bvcf_ctx *c, float ms[2]) {
   if (!c || !ms) return BVCF_E_ARG;
   if (c->in_flight) {

@@ -196,6 +196,148 @@ struct DefBits {
   }
 };
 
+// The LDS arrays of step 4 of k_deflate.  hll / hd: the histograms (read only).  All, Ad, sll, sd: the used symbols
+// sorted, scratch.  lll, ld, lcl: the code lengths of the dynamic form.  ccl: the canonical code of the code-length code.
+// rle: the run-length entries of the header (symbol | extra value << 8).  m[2]: used symbols.  hdr[8]: kind, bits of the
+// dynamic header, hlit, hdist, hclen, rle entries, bytes of the dynamic form, bytes of the fixed form.
+struct DefCodeBufs {
+  const uint32_t *hll, *hd;
+  uint32_t *All, *Ad;
+  uint16_t *sll, *sd;
+  uint8_t *lll, *ld, *lcl;
+  uint16_t *ccl, *rle;
+  uint32_t *m, *hdr;
+};
+
+// Step 4 of k_deflate, by the whole workgroup of kDefThreads: code lengths from the histograms of a piece of n bytes, the
+// block header, the sizes of the three forms and the choice.  Lane 0 writes b.hdr last; the caller's barrier publishes
+// what b points to.
+__device__ __forceinline__ void def_codes(const DefCodeBufs &b, int tid, uint32_t n) {
+  // rank sort of the used symbols (by frequency, then symbol)
+  for (uint32_t i = tid; i < kDefLL + kDefDist; i += kDefThreads) {
+    const bool is_d = i >= kDefLL;
+    const uint32_t s = is_d ? i - kDefLL : i, ns = is_d ? kDefDist : kDefLL;
+    const uint32_t *f = is_d ? b.hd : b.hll;
+    const uint32_t fs = f[s];
+    if (is_d) b.ld[s] = 0; else b.lll[s] = 0;
+    if (!fs) continue;
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < ns; j++) r += (f[j] && (f[j] < fs || (f[j] == fs && j < s))) ? 1u : 0u;
+    if (is_d) {
+      b.sd[r] = (uint16_t)s;
+      b.Ad[r] = fs;
+    } else {
+      b.sll[r] = (uint16_t)s;
+      b.All[r] = fs;
+    }
+  }
+  if (tid == 0 || tid == kWave) {
+    const bool is_d = tid != 0;
+    const uint32_t *f = is_d ? b.hd : b.hll;
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < (is_d ? kDefDist : kDefLL); j++) m += f[j] ? 1u : 0u;
+    b.m[is_d ? 1 : 0] = m;
+  }
+  __syncthreads();
+  if (tid == 0) def_huff_lengths(b.sll, b.All, (int)b.m[0], 15u, b.lll);
+  if (tid == kWave) def_huff_lengths(b.sd, b.Ad, (int)b.m[1], 15u, b.ld);
+  __syncthreads();
+
+  // block header, sizes of the three forms, the choice (one lane)
+  if (tid == 0) {
+    uint32_t hlit = kDefLL, hdist = kDefDist;
+    while (hlit > 257u && !b.lll[hlit - 1]) hlit--;
+    while (hdist > 1u && !b.ld[hdist - 1]) hdist--;
+    // run-length code of the code lengths (16: repeat the previous 3..6 times, 17: 3..10 zeros, 18: 11..138 zeros)
+    uint32_t nr = 0;
+    const uint32_t n_all = hlit + hdist;
+    for (uint32_t i = 0; i < n_all;) {
+      const uint32_t v = i < hlit ? b.lll[i] : b.ld[i - hlit];
+      uint32_t run = 1;
+      while (i + run < n_all && (i + run < hlit ? b.lll[i + run] : b.ld[i + run - hlit]) == v) run++;
+      i += run;
+      if (v == 0) {
+        while (run >= 11u) {
+          const uint32_t r = run < 138u ? run : 138u;
+          b.rle[nr++] = (uint16_t)(18u | (r - 11u) << 8);
+          run -= r;
+        }
+        if (run >= 3u) {
+          b.rle[nr++] = (uint16_t)(17u | (run - 3u) << 8);
+          run = 0;
+        }
+      } else {
+        b.rle[nr++] = (uint16_t)v;
+        run--;
+        while (run >= 3u) {
+          const uint32_t r = run < 6u ? run : 6u;
+          b.rle[nr++] = (uint16_t)(16u | (r - 3u) << 8);
+          run -= r;
+        }
+      }
+      for (; run; run--) b.rle[nr++] = (uint16_t)v;
+    }
+    // the code-length code: 19 symbols, sorted here, lengths <= 7
+    uint32_t fcl[kDefCL];
+    for (uint32_t i = 0; i < kDefCL; i++) fcl[i] = 0, b.lcl[i] = 0;
+    for (uint32_t i = 0; i < nr; i++) fcl[b.rle[i] & 0xFFu]++;
+    uint16_t scl[kDefCL];
+    uint32_t Acl[kDefCL];
+    int mcl = 0;
+    for (uint32_t s = 0; s < kDefCL; s++) {
+      if (!fcl[s]) continue;
+      int k = mcl++;
+      while (k > 0 && Acl[k - 1] > fcl[s]) {
+        Acl[k] = Acl[k - 1];
+        scl[k] = scl[k - 1];
+        k--;
+      }
+      Acl[k] = fcl[s];
+      scl[k] = (uint16_t)s;
+    }
+    def_huff_lengths(scl, Acl, mcl, 7u, b.lcl);
+    def_canonical(b.lcl, kDefCL, b.ccl);
+    const uint8_t order[kDefCL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+    uint32_t hclen = kDefCL;
+    while (hclen > 4u && !b.lcl[order[hclen - 1]]) hclen--;
+    uint32_t hdr = 3u + 14u + 3u * hclen;
+    for (uint32_t i = 0; i < nr; i++) {
+      const uint32_t s = b.rle[i] & 0xFFu;
+      hdr += b.lcl[s] + (s == 16u ? 2u : s == 17u ? 3u : s == 18u ? 7u : 0u);
+    }
+    // body bits under the dynamic and the fixed codes
+    uint64_t dyn = hdr, fix = 3;
+    for (uint32_t s = 0; s < kDefLL; s++) {
+      const uint32_t f = b.hll[s];
+      if (!f) continue;
+      const uint32_t x = s >= 257u ? def_ll_extra(s) : 0u;
+      const uint32_t fl = s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : 8u;
+      dyn += (uint64_t)f * (b.lll[s] + x);
+      fix += (uint64_t)f * (fl + x);
+    }
+    for (uint32_t s = 0; s < kDefDist; s++) {
+      const uint32_t f = b.hd[s];
+      if (!f) continue;
+      dyn += (uint64_t)f * (b.ld[s] + def_dist_extra(s));
+      fix += (uint64_t)f * (5u + def_dist_extra(s));
+    }
+    const uint64_t dyn_b = (dyn + 7u) >> 3, fix_b = (fix + 7u) >> 3, sto_b = (uint64_t)n + 5u;
+    uint32_t kind = kDefDynamic;
+    if (sto_b <= dyn_b && sto_b <= fix_b)
+      kind = kDefStored;
+    else if (fix_b <= dyn_b)
+      kind = kDefFixed;
+    b.hdr[0] = kind;
+    b.hdr[1] = hdr;
+    b.hdr[2] = hlit;
+    b.hdr[3] = hdist;
+    b.hdr[4] = hclen;
+    b.hdr[5] = nr;
+    b.hdr[6] = (uint32_t)dyn_b;
+    b.hdr[7] = (uint32_t)fix_b;
+  }
+}
+
 // (two workgroups per CU: 71 KiB of LDS each; the bound keeps the registers within two waves per SIMD)
 // text[0, n_text) in pieces of kDefPiece; piece i -> slots + i * kDefSlot (raw DEFLATE, unless stored), info[i] =
 // payload bytes | block type << 24, desc[i] for k_crc32.  scratch: kDefPiece words per workgroup of the grid.
@@ -210,7 +352,7 @@ __global__ __launch_bounds__(kDefThreads, 2) void k_deflate(const uint8_t *text,
   __shared__ uint16_t s_rle[kDefLL + kDefDist + 4];
   __shared__ uint32_t s_entry[kDefThreads + 1], s_off[kDefThreads + 1];
   __shared__ uint32_t s_m[2];  // used symbols: literal/length, distance
-  __shared__ uint32_t s_hdr[6];  // kind, header bits, hlit, hdist, hclen, rle entries
+  __shared__ uint32_t s_hdr[8];  // def_codes': kind, dynamic header bits, hlit, hdist, hclen, rle entries, dyn_b, fix_b
 
   const int tid = threadIdx.x;
   uint32_t *mt = scratch + (size_t)blockIdx.x * kDefPiece;
@@ -308,135 +450,24 @@ __global__ __launch_bounds__(kDefThreads, 2) void k_deflate(const uint8_t *text,
     }
     __syncthreads();
 
-    // ---- 4: code lengths.  Rank sort of the used symbols (by frequency, then symbol)
-    for (uint32_t i = tid; i < kDefLL + kDefDist; i += kDefThreads) {
-      const bool is_d = i >= kDefLL;
-      const uint32_t s = is_d ? i - kDefLL : i, ns = is_d ? kDefDist : kDefLL;
-      const uint32_t *f = is_d ? s_hd : s_hll;
-      const uint32_t fs = f[s];
-      if (is_d) s_ld[s] = 0; else s_lll[s] = 0;
-      if (!fs) continue;
-      uint32_t r = 0;
-      for (uint32_t j = 0; j < ns; j++) r += (f[j] && (f[j] < fs || (f[j] == fs && j < s))) ? 1u : 0u;
-      if (is_d) {
-        s_sd[r] = (uint16_t)s;
-        s_Ad[r] = fs;
-      } else {
-        s_sll[r] = (uint16_t)s;
-        s_All[r] = fs;
-      }
+    // ---- 4: code lengths, block header, sizes of the three forms, the choice
+    {
+      const DefCodeBufs cb = {s_hll, s_hd, s_All, s_Ad, s_sll, s_sd, s_lll, s_ld, s_lcl, s_ccl, s_rle, s_m, s_hdr};
+      def_codes(cb, tid, n);
     }
-    if (tid == 0 || tid == kWave) {
-      const bool is_d = tid != 0;
-      const uint32_t *f = is_d ? s_hd : s_hll;
-      uint32_t m = 0;
-      for (uint32_t j = 0; j < (is_d ? kDefDist : kDefLL); j++) m += f[j] ? 1u : 0u;
-      s_m[is_d ? 1 : 0] = m;
-    }
-    __syncthreads();
-    if (tid == 0) def_huff_lengths(s_sll, s_All, (int)s_m[0], 15u, s_lll);
-    if (tid == kWave) def_huff_lengths(s_sd, s_Ad, (int)s_m[1], 15u, s_ld);
-    __syncthreads();
-
-    // block header, sizes of the three forms, the choice (one lane)
-    if (tid == 0) {
-      uint32_t hlit = kDefLL, hdist = kDefDist;
-      while (hlit > 257u && !s_lll[hlit - 1]) hlit--;
-      while (hdist > 1u && !s_ld[hdist - 1]) hdist--;
-      // run-length code of the code lengths (16: repeat the previous 3..6 times, 17: 3..10 zeros, 18: 11..138 zeros)
-      uint32_t nr = 0;
-      const uint32_t n_all = hlit + hdist;
-      for (uint32_t i = 0; i < n_all;) {
-        const uint32_t v = i < hlit ? s_lll[i] : s_ld[i - hlit];
-        uint32_t run = 1;
-        while (i + run < n_all && (i + run < hlit ? s_lll[i + run] : s_ld[i + run - hlit]) == v) run++;
-        i += run;
-        if (v == 0) {
-          while (run >= 11u) {
-            const uint32_t r = run < 138u ? run : 138u;
-            s_rle[nr++] = (uint16_t)(18u | (r - 11u) << 8);
-            run -= r;
-          }
-          if (run >= 3u) {
-            s_rle[nr++] = (uint16_t)(17u | (run - 3u) << 8);
-            run = 0;
-          }
-        } else {
-          s_rle[nr++] = (uint16_t)v;
-          run--;
-          while (run >= 3u) {
-            const uint32_t r = run < 6u ? run : 6u;
-            s_rle[nr++] = (uint16_t)(16u | (r - 3u) << 8);
-            run -= r;
-          }
-        }
-        for (; run; run--) s_rle[nr++] = (uint16_t)v;
-      }
-      // the code-length code: 19 symbols, sorted here, lengths <= 7
-      uint32_t fcl[kDefCL];
-      for (uint32_t i = 0; i < kDefCL; i++) fcl[i] = 0, s_lcl[i] = 0;
-      for (uint32_t i = 0; i < nr; i++) fcl[s_rle[i] & 0xFFu]++;
-      uint16_t scl[kDefCL];
-      uint32_t Acl[kDefCL];
-      int mcl = 0;
-      for (uint32_t s = 0; s < kDefCL; s++) {
-        if (!fcl[s]) continue;
-        int k = mcl++;
-        while (k > 0 && Acl[k - 1] > fcl[s]) {
-          Acl[k] = Acl[k - 1];
-          scl[k] = scl[k - 1];
-          k--;
-        }
-        Acl[k] = fcl[s];
-        scl[k] = (uint16_t)s;
-      }
-      def_huff_lengths(scl, Acl, mcl, 7u, s_lcl);
-      def_canonical(s_lcl, kDefCL, s_ccl);
-      const uint8_t order[kDefCL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-      uint32_t hclen = kDefCL;
-      while (hclen > 4u && !s_lcl[order[hclen - 1]]) hclen--;
-      uint32_t hdr = 3u + 14u + 3u * hclen;
-      for (uint32_t i = 0; i < nr; i++) {
-        const uint32_t s = s_rle[i] & 0xFFu;
-        hdr += s_lcl[s] + (s == 16u ? 2u : s == 17u ? 3u : s == 18u ? 7u : 0u);
-      }
-      // body bits under the dynamic and the fixed codes
-      uint64_t dyn = hdr, fix = 3;
-      for (uint32_t s = 0; s < kDefLL; s++) {
-        const uint32_t f = s_hll[s];
-        if (!f) continue;
-        const uint32_t x = s >= 257u ? def_ll_extra(s) : 0u;
-        const uint32_t fl = s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : 8u;
-        dyn += (uint64_t)f * (s_lll[s] + x);
-        fix += (uint64_t)f * (fl + x);
-      }
-      for (uint32_t s = 0; s < kDefDist; s++) {
-        const uint32_t f = s_hd[s];
-        if (!f) continue;
-        dyn += (uint64_t)f * (s_ld[s] + def_dist_extra(s));
-        fix += (uint64_t)f * (5u + def_dist_extra(s));
-      }
-      const uint64_t dyn_b = (dyn + 7u) >> 3, fix_b = (fix + 7u) >> 3, sto_b = (uint64_t)n + 5u;
-      uint32_t kind = kDefDynamic;
-      if (sto_b <= dyn_b && sto_b <= fix_b)
-        kind = kDefStored;
-      else if (fix_b <= dyn_b)
-        kind = kDefFixed;
+    if (tid == 0) {  // the codes of the form that won
+      const uint32_t kind = s_hdr[0];
       if (kind == kDefFixed) {
-        for (uint32_t s = 0; s < kDefLL; s++) s_lll[s] = (uint8_t)(s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : 8u);
+        // (all 288 lengths: the fixed code counts the two symbols that never occur, 286 and 287, among its 8-bit codes,
+        // and the 9-bit codes of the literals from 144 on start behind them)
+        for (uint32_t s = 0; s < kDefLL + 2u; s++) s_lll[s] = (uint8_t)(s < 144u ? 8u : s < 256u ? 9u : s < 280u ? 7u : 8u);
         for (uint32_t s = 0; s < kDefDist; s++) s_ld[s] = 5;
       }
       if (kind != kDefStored) {
-        def_canonical(s_lll, kDefLL, s_cll);
+        def_canonical(s_lll, kind == kDefFixed ? kDefLL + 2u : kDefLL, s_cll);
         def_canonical(s_ld, kDefDist, s_cd);
       }
-      s_hdr[0] = kind;
-      s_hdr[1] = kind == kDefDynamic ? hdr : 3u;
-      s_hdr[2] = hlit;
-      s_hdr[3] = hdist;
-      s_hdr[4] = hclen;
-      s_hdr[5] = nr;
-      info[piece] = (kind == kDefStored ? n + 5u : (uint32_t)(kind == kDefDynamic ? dyn_b : fix_b)) | kind << 24;
+      info[piece] = (kind == kDefStored ? n + 5u : s_hdr[kind == kDefDynamic ? 6 : 7]) | kind << 24;
     }
     __syncthreads();
     const uint32_t kind = s_hdr[0];
@@ -470,7 +501,7 @@ __global__ __launch_bounds__(kDefThreads, 2) void k_deflate(const uint8_t *text,
     for (uint32_t i = tid; i < n_words; i += kDefThreads) s_tab[i] = 0;
     __syncthreads();
     if (tid == 0) {
-      uint32_t acc = s_hdr[1];
+      uint32_t acc = kind == kDefDynamic ? s_hdr[1] : 3u;
       for (int i = 0; i < kDefThreads; i++) {
         const uint32_t v = s_off[i];
         s_off[i] = acc;
@@ -508,6 +539,39 @@ __global__ __launch_bounds__(kDefThreads, 2) void k_deflate(const uint8_t *text,
     __syncthreads();
     uint32_t *slot = reinterpret_cast<uint32_t *>(slots + (size_t)piece * kDefSlot);
     for (uint32_t i = tid; i < n_words; i += kDefThreads) slot[i] = s_tab[i];
+  }
+}
+
+// bvcf_bench_deflate_codes: step 4 of k_deflate on given histograms, one workgroup per case.  in: kDefCodesIn words per
+// case = hll[286], hd[30], n.  lens: the 286 + 30 + 19 code lengths of the dynamic form, whatever the choice.  rle: the
+// run-length entries, kDefLL + kDefDist per case.  out: the 8 words of DefCodeBufs' hdr
+constexpr uint32_t kDefCodesIn = kDefLL + kDefDist + 1u, kDefCodesLens = kDefLL + kDefDist + kDefCL;
+__global__ __launch_bounds__(kDefThreads) void k_deflate_codes(const uint32_t *in, uint32_t n_cases, uint8_t *lens, uint16_t *rle,
+                                                              uint32_t *out) {
+  __shared__ uint32_t s_hll[kDefLL + 2], s_hd[kDefDist + 2];
+  __shared__ uint32_t s_All[kDefLL + 2], s_Ad[kDefDist + 2];
+  __shared__ uint16_t s_sll[kDefLL + 2], s_sd[kDefDist + 2];
+  __shared__ uint8_t s_lll[kDefLL + 2], s_ld[kDefDist + 2], s_lcl[kDefCL + 1];
+  __shared__ uint16_t s_ccl[kDefCL + 1];
+  __shared__ uint16_t s_rle[kDefLL + kDefDist + 4];
+  __shared__ uint32_t s_m[2];
+  __shared__ uint32_t s_hdr[8];
+  const int tid = threadIdx.x;
+  for (uint32_t c = blockIdx.x; c < n_cases; c += gridDim.x) {
+    const uint32_t *ci = in + (size_t)c * kDefCodesIn;
+    __syncthreads();  // the previous case is out of LDS
+    for (uint32_t i = tid; i < kDefLL + 2; i += kDefThreads) s_hll[i] = i < kDefLL ? ci[i] : 0u;
+    if (tid < (int)kDefDist + 2) s_hd[tid] = tid < (int)kDefDist ? ci[kDefLL + tid] : 0u;
+    for (uint32_t i = tid; i < kDefLL + kDefDist + 4; i += kDefThreads) s_rle[i] = 0;
+    __syncthreads();
+    const DefCodeBufs cb = {s_hll, s_hd, s_All, s_Ad, s_sll, s_sd, s_lll, s_ld, s_lcl, s_ccl, s_rle, s_m, s_hdr};
+    def_codes(cb, tid, ci[kDefLL + kDefDist]);
+    __syncthreads();
+    for (uint32_t i = tid; i < kDefCodesLens; i += kDefThreads)
+      lens[(size_t)c * kDefCodesLens + i] =
+          i < kDefLL ? s_lll[i] : i < kDefLL + kDefDist ? s_ld[i - kDefLL] : s_lcl[i - kDefLL - kDefDist];
+    for (uint32_t i = tid; i < kDefLL + kDefDist; i += kDefThreads) rle[(size_t)c * (kDefLL + kDefDist) + i] = s_rle[i];
+    if (tid < 8) out[(size_t)c * 8u + tid] = s_hdr[tid];
   }
 }
 

@@ -45,6 +45,14 @@ int bvcf_bench_pair_kernels(bvcf_ctx *ctx, float ms[4]);
  * k_site_gate chooses.  Needs no ctx */
 int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p);
 
+/* The code builder of the device compressor (step 4 of k_deflate) on given histograms, one workgroup per case, as k_deflate
+ * runs it on a piece's own.  hist = n x {hll[286], hd[30], text bytes}: literal/length and distance frequencies with
+ * hll[256] >= 1, at most 65 281 resp. 65 280 in sum, at most 65 280 text bytes (else BVCF_E_ARG).  lens = n x 335 bytes: the
+ * 286 + 30 + 19 code lengths of the dynamic form, whatever form wins.  rle = n x 316: the run-length entries of the header
+ * as sent, symbol | extra value << 8.  out = n x {kind (0 stored, 1 fixed, 2 dynamic), bits of the dynamic header, hlit,
+ * hdist, hclen, entries, bytes of the dynamic form, bytes of the fixed form}.  Needs no ctx */
+int bvcf_bench_deflate_codes(int device, const uint32_t *hist, uint32_t n, uint8_t *lens, uint16_t *rle, uint32_t *out);
+
 /* bvcf_set_site_gate: the two gate kernels on their own.  The chain of the LAST block of the ctx's last bvcf_bench_device*
  * call runs once more on the first slot with the gate switched off, so that the records are as k_finish leaves them; then
  * k_site_gate and k_site_hwe run over them with HIP events around each: ms = {k_site_gate, k_site_hwe} (0 for k_site_hwe
