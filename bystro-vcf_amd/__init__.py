@@ -47,12 +47,13 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
                  "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
-                 "bvcf_bench_deflate_codes"]
+                 "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
                 "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx",
-                "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms", "bvcf_bed_row"]
+                "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms", "bvcf_bed_row",
+                "bvcf_trio_verdict", "bvcf_parse_fam"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -62,6 +63,7 @@ EXPORTS = [
     "bvcf_arrow_open", "bvcf_arrow_append", "bvcf_arrow_close",
     "bvcf_site_gate_defaults", "bvcf_set_site_gate", "bvcf_site_gate_count", "bvcf_config_gate_defaults",
     "bvcf_enable_bed_rows", "bvcf_reserve_bed_rows", "bvcf_bed_rows", "bvcf_config_plink_defaults",
+    "bvcf_enable_trios", "bvcf_reserve_trio_events", "bvcf_trio_stats", "bvcf_config_trios_defaults",
 ]
 
 
@@ -134,6 +136,27 @@ class ConfigMore(C.Structure):
     """bvcf_config_more: bvcf_config and the fields that came after it stopped growing"""
     _fields_ = [("base", Config), ("pair_stats_path", C.c_char_p), ("site_gate", SiteGate), ("site_filter_path", C.c_char_p),
                 ("plink_prefix", C.c_char_p)]
+
+
+CONFIG_MORE_TRIOS = 3  # BVCF_CONFIG_MORE_TRIOS in Config.reserved[1]: the ConfigMore is the head of a ConfigTrios
+# bvcf_trio_verdict / BVCF_TRIO_*; the classes it takes are the class maps': none 0, het 1, hom 2, missing 3
+TRIO_UNINFORMATIVE, TRIO_CONSISTENT, TRIO_DENOVO, TRIO_ERROR = 0, 1, 2, 3
+# bvcf_parse_fam / BVCF_FAM_*
+FAM_OK, FAM_SHORT_LINE, FAM_DUP_IID, FAM_AMBIGUOUS, FAM_SAME_SAMPLE = 0, 1, 2, 3, 4
+MENDEL_COLUMNS = ["child", "father", "mother", "informative", "errors", "denovo", "errorRate"]
+MENDEL_ERRORS_COLUMNS = ["chrom", "pos", "ref", "alt", "child", "father", "mother", "childClass", "fatherClass", "motherClass",
+                         "kind"]
+
+
+class ConfigTrios(C.Structure):
+    """bvcf_config_trios: a bvcf_config_more and the paths that came after it stopped growing"""
+    _fields_ = [("more", ConfigMore), ("fam_path", C.c_char_p), ("mendel_path", C.c_char_p), ("mendel_errors_path", C.c_char_p)]
+
+
+class TrioInfo(C.Structure):
+    """bvcf_trio_info"""
+    _fields_ = [("counts", C.c_void_p), ("events", C.c_void_p), ("n_events", C.c_uint64), ("need_events", C.c_uint64),
+                ("n_trios", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -342,7 +365,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     """cfg uses the key names of tests/golden/known_answers.json (emptyField, keepId, allow, ...).
     The returned object keeps the byte strings alive."""
     cfg = cfg or {}
-    more = ConfigMore()
+    # (--mendel / --mendelErrors: the larger struct and its marker, only then; every other config is a ConfigMore as before)
+    trios = ConfigTrios() if cfg.get("mendel") or cfg.get("mendelErrors") else None
+    more = trios.more if trios is not None else ConfigMore()
     c = more.base  # (a view of more's memory, which it keeps alive: what the callers pass on is the head of a bvcf_config_more)
     lib.bvcf_config_defaults(C.byref(c))
     keep = [cfg.get("emptyField", "!").encode(), cfg.get("fieldDelimiter", ";").encode(),
@@ -400,8 +425,43 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         more.plink_prefix = keep[-1]
         c.reserved[0] = CONFIG_MORE
         c.reserved[1] = CONFIG_MORE_PLINK
+    if trios is not None:  # the pedigree and the two tables (the fourth marker implies the gate fields and the prefix)
+        if not c.reserved[1]:
+            more.site_gate = make_site_gate()
+        for key, field in (("fam", "fam_path"), ("mendel", "mendel_path"), ("mendelErrors", "mendel_errors_path")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(trios, field, keep[-1])
+        c.reserved[0] = CONFIG_MORE
+        c.reserved[1] = CONFIG_MORE_TRIOS
     c._keep = keep
     return c
+
+
+def trio_verdict(child, father, mother):
+    """bvcf_trio_verdict: TRIO_* for the classes (none 0, het 1, hom 2, missing 3) of a trio in a row (host code, no device)"""
+    lib.bvcf_trio_verdict.restype = C.c_int
+    lib.bvcf_trio_verdict.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    return lib.bvcf_trio_verdict(child, father, mother)
+
+
+def parse_fam(text, names):
+    """bvcf_parse_fam: a PLINK .fam (bytes) against the sample names (list of bytes, header order) -> (FAM_OK, [(child,
+    father, mother), ...] by child) or (FAM_* reason, 1-based line, the line's IID or None)  (host code, no device)"""
+    n = len(names)
+    arr = (C.c_char_p * max(n, 1))(*names)
+    lens = (C.c_uint32 * max(n, 1))(*[len(x) for x in names])
+    out = (C.c_uint32 * (3 * max(n, 1)))()
+    n_trios, bad_line, iid, iid_len = C.c_size_t(), C.c_uint64(), C.c_void_p(), C.c_size_t()
+    buf = C.create_string_buffer(bytes(text), len(text) + 1)
+    lib.bvcf_parse_fam.restype = C.c_int
+    lib.bvcf_parse_fam.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    why = lib.bvcf_parse_fam(buf, len(text), arr, lens, n, out, n, C.byref(n_trios), C.byref(bad_line), C.byref(iid),
+                             C.byref(iid_len))
+    if why:
+        return why, int(bad_line.value), (C.string_at(iid.value, iid_len.value) if iid.value else None)
+    return FAM_OK, [tuple(out[3 * t:3 * t + 3]) for t in range(n_trios.value)]
 
 
 def bed_row(cmap, n_samples, sparse=False, out=None):
@@ -758,7 +818,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -779,6 +839,14 @@ class Ctx:
         if bed_rows:  # bvcf_enable_bed_rows: the .bed rows behind every chain (read with bed_rows() after each collect)
             lib.bvcf_enable_bed_rows.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_bed_rows(self.h)
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+        if trios is not None:  # bvcf_enable_trios: (child, father, mother) kept-sample indices (read with trio_stats() after each collect)
+            t = np.ascontiguousarray(np.asarray(trios, dtype=np.uint32).reshape(-1, 3))
+            lib.bvcf_enable_trios.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+            rc = lib.bvcf_enable_trios(self.h, t.ctypes.data if len(t) else None, len(t))
             if rc:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
@@ -932,6 +1000,42 @@ class Ctx:
         """bvcf_reserve_bed_rows: grow the arena of the .bed rows (no batch in flight)"""
         lib.bvcf_reserve_bed_rows.argtypes = [C.c_void_p, C.c_uint64]
         self._check(lib.bvcf_reserve_bed_rows(self.h, int(nbytes)))
+
+    def trio_info(self):
+        """bvcf_trio_stats: the TrioInfo of the batch collected last (need_events is set after BVCF_E_CAPACITY too)"""
+        info = TrioInfo()
+        lib.bvcf_trio_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_trio_stats(self.h, C.byref(info)))
+        return info
+
+    def trio_stats(self):
+        """the batch collected last -> (counts uint32 (n_trios, 3): informative, errors, denovo; events uint32 (n_events, 5):
+        row, trio, then the classes of child, father and mother), copied out of the slot"""
+        info = self.trio_info()
+        nt, ne = int(info.n_trios), int(info.n_events)
+        counts = np.zeros((nt, 3), dtype=np.uint32)
+        if nt and info.counts:
+            counts = np.frombuffer((C.c_uint32 * (3 * nt)).from_address(info.counts), dtype=np.uint32).reshape(nt, 3).copy()
+        ev = np.zeros((ne, 5), dtype=np.uint32)
+        if ne:
+            raw = np.frombuffer((C.c_uint32 * (2 * ne)).from_address(info.events), dtype=np.uint32).reshape(ne, 2)
+            w = raw[:, 1]
+            ev = np.stack([raw[:, 0], w & 0xFFFFFF, (w >> 24) & 3, (w >> 26) & 3, (w >> 28) & 3], axis=1).astype(np.uint32)
+        return counts, ev
+
+    def reserve_trio_events(self, n):
+        """bvcf_reserve_trio_events: grow the arena of the events (no batch in flight)"""
+        lib.bvcf_reserve_trio_events.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(lib.bvcf_reserve_trio_events(self.h, int(n)))
+
+    def bench_trio_kernels(self):
+        """the trio kernels over the first slot's last bench chain -> (ms of [row index + memsets, k_trio_count, k_trio_scan,
+        k_trio_fill], rows, events)"""
+        ms = (C.c_float * 4)()
+        out = (C.c_uint64 * 2)()
+        lib.bvcf_bench_trio_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(lib.bvcf_bench_trio_kernels(self.h, ms, out))
+        return list(ms), int(out[0]), int(out[1])
 
     def bench_bed_kernels(self):
         """the .bed kernels over the first slot's last bench chain -> (ms of [k_bed_count + k_bed_scan + k_bed_index, k_bed_rows], rows, bytes)"""

@@ -130,6 +130,16 @@ struct Slot {
   DevBuf<uint8_t> d_bed;
   PinBuf<uint8_t> h_bed;
   uint64_t cap_bed = 0;
+  // bvcf_enable_trios (bvcf_mendel.hip.h): the batch's [T][3] counts with their pinned copy, the events per row (follow
+  // max_alleles), the batch's event count, and the arena of the events with its pinned copy -- a bound of its own
+  // (bvcf_ctx.trio_cap, in events)
+  DevBuf<uint32_t> d_trio_counts, d_trio_rowev;
+  PinBuf<uint32_t> h_trio_counts;
+  DevBuf<unsigned long long> d_trio_total;
+  PinBuf<unsigned long long> h_trio_total;
+  DevBuf<uint2> d_trio_ev;
+  PinBuf<uint2> h_trio_ev;
+  uint64_t cap_trio = 0;
   // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
   // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
@@ -186,6 +196,14 @@ struct bvcf_ctx : bvcf_ctx_plan {
   bool bed_asked = false, bed_on = false;
   uint64_t bed_cap = 0;
   bvcf_bed_rows_info bed_last{};
+  // bvcf_enable_trios on a file with samples and at least one trio: k_trio_count / k_trio_scan / k_trio_fill at the end of
+  // every chain, behind the row index they share with the .bed rows (built once when either is on); trio_cap is what a
+  // slot's events arena holds (bvcf_reserve_trio_events grows it), trio_last the batch collected last (bvcf_trio_stats)
+  bool trio_asked = false, trio_on = false;
+  uint32_t n_trios = 0;
+  DevBuf<uint32_t> d_trios;
+  uint64_t trio_cap = 0;
+  bvcf_trio_info trio_last{};
   const void *bench_src = nullptr;  // the last block of the last bvcf_bench_device* call (bvcf_bench_gate_kernels)
   size_t bench_nbytes = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
@@ -471,10 +489,11 @@ int alloc_gate_list(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
-// bvcf_enable_bed_rows: the lines' first rows (follow max_lines) and the counter; the arena and its pinned copy when the
-// ctx's bound has grown past what the slot holds
+// bvcf_enable_bed_rows / bvcf_enable_trios: the row index both read -- the lines' first rows (follow max_lines), a row's map
+// (follows max_alleles) and the counter; the .bed arena and its pinned copy when the ctx's bound has grown past what the
+// slot holds
 int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
-  if (!c->bed_on) return BVCF_OK;
+  if (!c->bed_on && !c->trio_on) return BVCF_OK;
   if (s.d_bed_base.size() < c->max_lines) {
     HIP_TRY(c, s.d_bed_base.alloc(c->max_lines));
     HIP_TRY(c, s.d_bed_tile.alloc(c->max_lines / kBedTile + 2));
@@ -484,7 +503,7 @@ int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, s.d_bed_total.alloc(1));
     HIP_TRY(c, s.h_bed_total.alloc(1));
   }
-  if (s.cap_bed < c->bed_cap) {
+  if (c->bed_on && s.cap_bed < c->bed_cap) {
     s.cap_bed = 0;
     HIP_TRY(c, s.d_bed.alloc(c->bed_cap + 16));
     HIP_TRY(c, s.h_bed.alloc(c->bed_cap + 16));
@@ -493,9 +512,33 @@ int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
+// the events of max_alleles rows and, behind them, of their tiles of kTrioTile rows
+size_t trio_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kTrioTile + 2; }
+
+// bvcf_enable_trios: the counts, the events per row and per tile (follow max_alleles) and the counter; the events arena and its pinned
+// copy when the ctx's bound has grown past what the slot holds
+int alloc_trios(bvcf_ctx *c, Slot &s) {
+  if (!c->trio_on) return BVCF_OK;
+  if (!s.d_trio_counts) {
+    HIP_TRY(c, s.d_trio_counts.alloc(3ull * c->n_trios));
+    HIP_TRY(c, s.h_trio_counts.alloc(3ull * c->n_trios));
+    HIP_TRY(c, s.d_trio_total.alloc(1));
+    HIP_TRY(c, s.h_trio_total.alloc(1));
+  }
+  if (s.d_trio_rowev.size() < trio_rowev_words(c->max_alleles)) HIP_TRY(c, s.d_trio_rowev.alloc(trio_rowev_words(c->max_alleles)));
+  if (s.cap_trio < c->trio_cap) {
+    s.cap_trio = 0;
+    HIP_TRY(c, s.d_trio_ev.alloc(c->trio_cap));
+    HIP_TRY(c, s.h_trio_ev.alloc(c->trio_cap));
+    s.cap_trio = c->trio_cap;
+  }
+  return BVCF_OK;
+}
+
 int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_gate_list(c, s)) return rc;
   if (const int rc = alloc_bed_rows(c, s)) return rc;
+  if (const int rc = alloc_trios(c, s)) return rc;
   if (!c->ss_on && !c->pr_on) return BVCF_OK;
   s.d_pr_planes.reset();
   s.cap_pr_tiles = 0;
@@ -610,7 +653,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on;  // (the per-sample and pair counts and the .bed rows are made from the maps on the device)
+  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on;  // (the per-sample, pair and trio counts and the .bed rows are made from the maps on the device)
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -730,9 +773,17 @@ void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *sl
   if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
 }
 
-// the slot holds everything the .bed kernels write, sized for the ctx's current capacities
-bool bed_ready(const bvcf_ctx *c, const Slot &s) {
-  return s.d_bed && s.d_bed_total && s.d_bed_base.size() >= c->max_lines && s.d_bed_src.size() >= c->max_alleles;
+// the slot holds everything the kernels of the row index write, sized for the ctx's current capacities
+bool index_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.d_bed_total && s.d_bed_base.size() >= c->max_lines && s.d_bed_src.size() >= c->max_alleles;
+}
+
+// ... and the arena k_bed_rows writes
+bool bed_ready(const bvcf_ctx *c, const Slot &s) { return s.d_bed && index_ready(c, s); }
+
+// ... and everything the trio kernels write
+bool trios_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.d_trio_ev && s.d_trio_counts && s.d_trio_total && s.d_trio_rowev.size() >= trio_rowev_words(c->max_alleles) && index_ready(c, s);
 }
 
 BedArgs make_bed_args(bvcf_ctx *c, Slot &s) {
@@ -749,13 +800,52 @@ BedArgs make_bed_args(bvcf_ctx *c, Slot &s) {
 
 // bvcf_enable_bed_rows: the end of a chain with samples -- every row's place in output order, then the rows themselves
 // into the slot's arena (bvcf_bedrows.hip.h; bvcf_collect copies the used part)
-void launch_bed_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
-  if (!c->bed_on || !slot || !bed_ready(c, *slot)) return;
-  const BedArgs ba = make_bed_args(c, *slot);
+void launch_bed_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
+  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ba);
+}
+
+void launch_row_index(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
   hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
   hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, st, a, ba);
   hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
-  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ba);
+}
+
+TrioArgs make_trio_args(bvcf_ctx *c, Slot &s) {
+  TrioArgs ta{};
+  ta.trios = c->d_trios;
+  ta.n_trios = c->n_trios;
+  ta.ev_rows = (uint32_t)c->max_alleles;
+  ta.counts = s.d_trio_counts;
+  ta.row_events = s.d_trio_rowev;
+  ta.total = s.d_trio_total;
+  ta.events = s.d_trio_ev;
+  ta.cap = s.cap_trio;
+  return ta;
+}
+
+constexpr int kTrioCountWgs = 5, kTrioFillWgs = 4;  // (k_trio_count: 5 waves per SIMD is what its registers allow)  // workgroups per CU
+
+// bvcf_enable_trios: the batch's counts and the events per row from zero, then the three kernels (bvcf_mendel.hip.h;
+// bvcf_collect copies the counts and the used part of the events)
+int launch_trio_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const TrioArgs &ta) {
+  HIP_TRY(c, hipMemsetAsync(ta.counts, 0, 3ull * ta.n_trios * sizeof(uint32_t), st));
+  HIP_TRY(c, hipMemsetAsync(ta.row_events, 0, trio_rowev_words(ta.ev_rows) * sizeof(uint32_t), st));
+  hipLaunchKernelGGL(k_trio_count, dim3(c->n_cu * kTrioCountWgs), dim3(kWgThreads), 0, st, a, ba, ta);
+  hipLaunchKernelGGL(k_trio_scan, dim3(1), dim3(1024), 0, st, a, ba, ta);
+  hipLaunchKernelGGL(k_trio_fill, dim3(c->n_cu * kTrioFillWgs), dim3(kWgThreads), 0, st, a, ba, ta);
+  return BVCF_OK;
+}
+
+// the end of a chain with samples, with bvcf_enable_bed_rows and / or bvcf_enable_trios: every row's place in output order
+// -- once --, then the .bed rows into the slot's arena and the trios' counts and events into theirs
+void launch_trios(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if (!slot) return;
+  const bool bed = c->bed_on && bed_ready(c, *slot), trios = c->trio_on && trios_ready(c, *slot);
+  if (!bed && !trios) return;
+  const BedArgs ba = make_bed_args(c, *slot);
+  launch_row_index(c, a, st, ba);
+  if (bed) launch_bed_rows(c, a, st, ba);
+  if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)
 }
 
 // bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
@@ -845,7 +935,7 @@ void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t 
   launch_site_gate(c, a, st, slot);
   if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
   launch_sample_stats(c, a, st, slot);
-  launch_bed_rows(c, a, st, slot);
+  launch_trios(c, a, st, slot);
 }
 
 uint32_t census_grid(const bvcf_ctx *c, uint32_t n_chunks) {
@@ -950,7 +1040,7 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
         if (a.wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
     }
   launch_sample_stats(c, a, st, slot);
-  launch_bed_rows(c, a, st, slot);
+  launch_trios(c, a, st, slot);
 }
 
 // the kernel chain for one resident block; ev_gt0 / ev_gt1 (optional) bracket the dominant kernel (k_gt on the census path,
@@ -1174,8 +1264,10 @@ int launch_batch(bvcf_ctx *c, Slot &s, const uint8_t *src, size_t nbytes) {
   }
   HIP_TRY(c, hipEventRecord(s.ev_k1, s.stream));
   HIP_TRY(c, hipMemcpyAsync(s.h_counters, s.d_counters, sizeof(BatchCounters), hipMemcpyDeviceToHost, s.stream));
-  if (c->bed_on && s.d_bed_total)
+  if ((c->bed_on || c->trio_on) && s.d_bed_total)
     HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (c->trio_on && trios_ready(c, s))
+    HIP_TRY(c, hipMemcpyAsync(s.h_trio_total, s.d_trio_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   if (c->render) {
     HIP_TRY(c, hipMemcpyAsync(s.h_rtotals, s.d_rtotals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
     // (Tried: as much of the stream as the last batch's rows-per-text ratio predicts copied to the host right here,
@@ -1881,7 +1973,7 @@ static BatchNeeds batch_needs(const bvcf_ctx *c, const Slot &s, const BatchCount
   n.n_alleles = n.extras_at + ctr.n_alleles;
   n.n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
   n.need_alleles = std::max<uint64_t>(std::max<uint64_t>(n.n_alleles, ctr.n_errs), n.n_tasks);
-  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on) && c->n_samples;
+  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on) && c->n_samples;
   n.cmap_need = maps ? cmap_bytes_of(c, ctr) : 0;
   n.fits = ctr.n_lines <= s.cap_lines && n.need_alleles <= s.cap_alleles && n.cmap_need <= s.cap_cmap;
   return n;
@@ -2088,7 +2180,7 @@ static void fill_result(const bvcf_ctx *c, const Slot &s, const Collected &k, ui
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = ((c->ss_on || c->pr_on || c->bed_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
+  r->cmap = ((c->ss_on || c->pr_on || c->bed_on || c->trio_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage.get() : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = k.was_bgzf ? s.h_text.get() : nullptr;
@@ -2176,7 +2268,13 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   const bool bed = c->bed_on && bed_ready(c, s);
   const uint64_t bed_rows = bed ? *s.h_bed_total : 0, bed_bytes = bed_rows * c->bed_last.row_bytes;
   c->bed_last.need_bytes = bed_bytes;
-  if (!k.need.fits || bed_bytes > s.cap_bed) {
+  // bvcf_enable_trios: likewise the batch's events against the slot's arena
+  c->trio_last = bvcf_trio_info{};
+  c->trio_last.n_trios = c->n_trios;
+  const bool trios = c->trio_on && trios_ready(c, s);
+  const uint64_t trio_events = trios ? *s.h_trio_total : 0;
+  c->trio_last.need_events = trio_events;
+  if (!k.need.fits || bed_bytes > s.cap_bed || trio_events > s.cap_trio) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
     r->need_alleles = k.need.need_alleles;
@@ -2200,6 +2298,11 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   if (!rc) rc = copy_text(c, s, k);
   if (!rc) rc = copy_names(c, s, k);
   if (!rc && bed_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_bed, s.d_bed, bed_bytes, hipMemcpyDeviceToHost, s.stream));
+  // (the table too comes over only now: until this collect the slot's pinned copy is the caller's, from the slot's last batch)
+  if (!rc && trios)
+    HIP_TRY(c, hipMemcpyAsync(s.h_trio_counts, s.d_trio_counts, 3ull * c->n_trios * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+  if (!rc && trio_events)
+    HIP_TRY(c, hipMemcpyAsync(s.h_trio_ev, s.d_trio_ev, trio_events * sizeof(uint2), hipMemcpyDeviceToHost, s.stream));
   if (rc) return rc;
   e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) {
@@ -2210,6 +2313,11 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   if (bed) {
     c->bed_last.rows = s.h_bed;
     c->bed_last.n_rows = bed_rows;
+  }
+  if (trios) {
+    c->trio_last.counts = s.h_trio_counts;
+    c->trio_last.events = reinterpret_cast<const uint32_t *>(s.h_trio_ev.get());
+    c->trio_last.n_events = trio_events;
   }
   add_totals(c, s, k, r);
   return BVCF_OK;
@@ -2354,6 +2462,81 @@ int bvcf_bed_rows(const bvcf_ctx *c, bvcf_bed_rows_info *out) {
   if (!c || !out || !c->bed_asked) return BVCF_E_ARG;
   *out = c->bed_last;
   return BVCF_OK;
+}
+
+int bvcf_enable_trios(bvcf_ctx *c, const uint32_t *trios, uint32_t n) {
+  if (!c || (n && !trios)) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_enable_trios with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (c->trio_asked) {
+    c->err = "bvcf_enable_trios: called twice on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (n >= kTrioMax) {
+    c->err = "bvcf_enable_trios: more than " + std::to_string(kTrioMax - 1) + " trios";
+    return BVCF_E_ARG;
+  }
+  for (uint32_t t = 0; t < n; t++) {
+    const uint32_t *x = trios + 3ull * t;
+    if (x[0] >= c->n_samples || x[1] >= c->n_samples || x[2] >= c->n_samples || x[0] == x[1] || x[0] == x[2] || x[1] == x[2]) {
+      c->err = "bvcf_enable_trios: trio " + std::to_string(t) + " names a sample index past the ctx's samples, or one sample twice";
+      return BVCF_E_ARG;
+    }
+  }
+  c->trio_asked = true;
+  c->trio_last = bvcf_trio_info{};
+  if (!n) return BVCF_OK;  // (no trios -- or no sample columns, which gives none: nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_trios.alloc(3ull * n + 16));  // (16 words at least: what trio_row reads for a row that is no short list)
+  HIP_TRY(c, hipMemset(c->d_trios, 0, (3ull * n + 16) * sizeof(uint32_t)));
+  HIP_TRY(c, hipMemcpy(c->d_trios, trios, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->n_trios = n;
+  // an event needs a call that contradicts the pedigree; real cohorts show a few per thousand (row, trio) pairs, and a
+  // line of text gives a row.  One event (8 bytes) per 64 bytes of text holds that with room; a wrong pedigree or a
+  // crafted file outruns it and grows the arena (BVCF_E_CAPACITY, bvcf_reserve_trio_events)
+  c->trio_cap = std::max<uint64_t>(c->trio_cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
+  c->trio_on = true;
+  c->trio_last.n_trios = n;
+  for (auto &s : c->slots) {
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+    if (const int rc = alloc_trios(c, s)) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_reserve_trio_events(bvcf_ctx *c, uint64_t n) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->trio_asked) {
+    c->err = "bvcf_reserve_trio_events: bvcf_enable_trios was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (c->in_flight) {
+    c->err = "bvcf_reserve_trio_events with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->trio_on) return BVCF_OK;
+  if (n > kTrioEventsMax) {
+    c->err = "bvcf_reserve_trio_events: a batch holds fewer than 2^32 events (smaller batches: max_batch_bytes)";
+    return BVCF_E_ARG;
+  }
+  c->trio_cap = std::max<uint64_t>(c->trio_cap, (n + 63) & ~63ull);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)
+    if (const int rc = alloc_trios(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_trio_stats(const bvcf_ctx *c, bvcf_trio_info *out) {
+  if (!c || !out || !c->trio_asked) return BVCF_E_ARG;
+  *out = c->trio_last;
+  return BVCF_OK;
+}
+
+int bvcf_trio_verdict(uint32_t child, uint32_t father, uint32_t mother) {
+  if (child > 3u || father > 3u || mother > 3u) return -1;
+  return (int)trio_verdict(child, father, mother);
 }
 
 int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out) {
@@ -2768,6 +2951,48 @@ int bvcf_bench_bed_kernels(bvcf_ctx *c, float ms[2], uint64_t out[2]) {
   out[1] = out[0] * ((c->n_samples + 3u) / 4u);
   if (out[1] > s.cap_bed) {
     c->err = "bvcf_bench_bed_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[1]) + " bytes";
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_bench_trio_kernels(bvcf_ctx *c, float ms[4], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_trio_kernels with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  Slot &s = c->slots[0];
+  if (!c->trio_on || !trios_ready(c, s)) {
+    c->err = "bvcf_bench_trio_kernels: the ctx has no trios";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
+  const BedArgs ba = make_bed_args(c, s);
+  const TrioArgs ta = make_trio_args(c, s);
+  Event ev[5];
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_row_index(c, a, s.stream, ba);
+  HIP_TRY(c, hipMemsetAsync(ta.counts, 0, 3ull * ta.n_trios * sizeof(uint32_t), s.stream));
+  HIP_TRY(c, hipMemsetAsync(ta.row_events, 0, trio_rowev_words(ta.ev_rows) * sizeof(uint32_t), s.stream));
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  hipLaunchKernelGGL(k_trio_count, dim3(c->n_cu * kTrioCountWgs), dim3(kWgThreads), 0, s.stream, a, ba, ta);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  hipLaunchKernelGGL(k_trio_scan, dim3(1), dim3(1024), 0, s.stream, a, ba, ta);
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  hipLaunchKernelGGL(k_trio_fill, dim3(c->n_cu * kTrioFillWgs), dim3(kWgThreads), 0, s.stream, a, ba, ta);
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(c, hipMemcpyAsync(s.h_trio_total, s.d_trio_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  out[0] = *s.h_bed_total;
+  out[1] = *s.h_trio_total;
+  if (out[1] > s.cap_trio) {
+    c->err = "bvcf_bench_trio_kernels: the events outrun the arena (bvcf_reserve_trio_events): " + std::to_string(out[1]);
     return BVCF_E_CAPACITY;
   }
   return BVCF_OK;

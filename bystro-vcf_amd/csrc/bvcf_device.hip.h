@@ -60,6 +60,9 @@
 //   (bvcf_enable_bed_rows, at the end of the chain of a file with samples: k_bed_count / k_bed_scan / k_bed_index give every row its
 //    place in output order, k_bed_rows recodes its class map -- dense or short list -- into the unpadded row of a PLINK
 //    .bed file, the rows back to back in an arena of their own -- bvcf_bedrows.hip.h)
+//   (bvcf_enable_trios, behind the same row index -- built once when either is on: k_trio_count / k_trio_scan / k_trio_fill
+//    give, per trio, the rows that are informative, Mendelian errors and de novo calls, and the batch's events in
+//    (row, trio) order -- bvcf_mendel.hip.h)
 //   (bvcf_params.want_name_lists, after k_finish: k_name_len / k_name_scan / k_name_write render the het / hom / missing
 //    sample-name lists of every output allele as text -- main.go:612-656 -- see bvcf_names.hip.h)
 //
@@ -107,5 +110,6 @@
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_bedrows.hip.h"
+#include "bvcf_mendel.hip.h"
 #include "bvcf_inflate.hip.h"
 #include "bvcf_deflate.hip.h"

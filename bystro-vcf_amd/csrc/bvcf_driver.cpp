@@ -395,6 +395,11 @@ void Driver::device_main(DevWorker *W) {
         bvcf_bed_rows_info bi;
         if (bvcf_bed_rows(W->ctx, &bi) == BVCF_OK) bed_need = bi.need_bytes;
       }
+      uint64_t trio_need = 0;  // (--mendel / --mendelErrors: likewise the events)
+      if (R_.mendel_on) {
+        bvcf_trio_info ti;
+        if (bvcf_trio_stats(W->ctx, &ti) == BVCF_OK) trio_need = ti.need_events;
+      }
       // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
       const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
       if (ss) {
@@ -436,6 +441,7 @@ void Driver::device_main(DevWorker *W) {
       r = bvcf_reserve(W->ctx, res.need_lines + res.need_lines / 4 + 64, res.need_alleles + res.need_alleles / 4 + 64,
                        res.need_cmap_bytes + res.need_cmap_bytes / 4 + 4096);
       if (r == BVCF_OK && bed_need) r = bvcf_reserve_bed_rows(W->ctx, bed_need + bed_need / 4 + 4096);
+      if (r == BVCF_OK && trio_need) r = bvcf_reserve_trio_events(W->ctx, trio_need + trio_need / 4 + 1024);
       for (size_t k = 0; k < in_flight.size() && r == BVCF_OK; k++) r = submit(in_flight[k]);
       if (r == BVCF_OK) {
         r = bvcf_collect(W->ctx, &res);
@@ -460,6 +466,10 @@ void Driver::device_main(DevWorker *W) {
     j.has_res = true;
     if (wants_plink(c_) && bvcf_bed_rows(W->ctx, &j.bed) != BVCF_OK) {  // --plinkOutput: the rows collected with this batch
       fail(std::string("bvcf_bed_rows: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      return;
+    }
+    if (R_.mendel_on && bvcf_trio_stats(W->ctx, &j.trio) != BVCF_OK) {  // --mendel / --mendelErrors: likewise
+      fail(std::string("bvcf_trio_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
       return;
     }
     j.job = n_jobs;
@@ -557,11 +567,12 @@ void Driver::formatter_main(DevWorker *W) {
       else
         for (auto &q : *it.parts) q.clear();
       const bool plink = R_.bed_fd >= 0;
-      if ((R_.arrow && j.res.dosage) || plink) {
+      const bool mendel = R_.mendel_on && !R_.trios.empty();  // (the tables are summed in input order too: one thread)
+      if ((R_.arrow && j.res.dosage) || plink || mendel) {
         // the dosage rows go into the file in input order (main.go:576-584): the sink runs this when it is the block's
         // turn; the result slot and the text stay on loan until then -- and so do the batch's .bed rows and .bim lines
         auto keep = std::make_shared<FmtJob>(std::move(j));
-        it.in_order = [this, keep, text, release, plink]() {
+        it.in_order = [this, keep, text, release, plink, mendel]() {
           if (!dosage_failed_.load() && append_dosage(R_, &keep->res, text)) {
             dosage_failed_.store(true);
             fail("dosage matrix: write failed", BVCF_E_FATAL);
@@ -569,6 +580,10 @@ void Driver::formatter_main(DevWorker *W) {
           if (plink && !plink_failed_.load() && append_plink(R_, &keep->res, text, keep->bed)) {
             plink_failed_.store(true);
             fail("plinkOutput: write failed", BVCF_E_FATAL);
+          }
+          if (mendel && !mendel_failed_.load() && append_mendel(R_, &keep->res, text, keep->trio)) {
+            mendel_failed_.store(true);
+            fail("mendel: the device's events do not match the batch's rows", BVCF_E_FATAL);
           }
           release();
         };
@@ -602,6 +617,10 @@ int Driver::run(uint64_t *n_lines_in) {
     if (open_plink(R_, &msg)) {  // --plinkOutput: likewise, all three files
       dprintf(fd_err_, "%s\n", msg.c_str());
       return BVCF_E_IO;
+    }
+    if (const int rc = open_mendel(R_, &msg)) {  // --mendel / --mendelErrors: likewise
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
     }
   }
   sniff_input();
@@ -819,6 +838,16 @@ int Driver::run(uint64_t *n_lines_in) {
         close(sg_fd_);
       }
       sg_fd_ = -1;
+    }
+    if (R_.mendel_fd >= 0 || R_.mendel_errors_fd >= 0) {
+      // --mendel / --mendelErrors: the sink added up the batches it was handed, in input order
+      std::string msg;
+      if (rc_ != BVCF_OK) {
+        close_mendel(R_);
+      } else if (write_mendel(R_, &msg)) {
+        fail(msg, BVCF_E_IO);
+        write_all(fd_err_, log_.data(), log_.size());
+      }
     }
     if (!c_->leave_teardown_to_exit)
       for (bvcf_ctx *x : live) bvcf_destroy(x);

@@ -40,6 +40,12 @@ void bvcf_config_plink_defaults(bvcf_config_more *c) {
   c->base.reserved[1] = BVCF_CONFIG_MORE_PLINK;
 }
 
+void bvcf_config_trios_defaults(bvcf_config_trios *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_plink_defaults(&c->more);
+  c->more.base.reserved[1] = BVCF_CONFIG_MORE_TRIOS;
+}
+
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
   std::string h;
   for (int i = 0; i < 15; i++) {
@@ -110,6 +116,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
   if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
   if (rc == BVCF_OK) rc = open_plink(R, &msg);
+  if (rc == BVCF_OK) rc = open_mendel(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -167,6 +174,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
           break;
         }
       }
+      if (R.mendel_on) {  // --mendel / --mendelErrors: the batch's counts and events
+        bvcf_trio_info ti;
+        if (bvcf_trio_stats(R.ctx, &ti) != BVCF_OK || append_mendel(R, &res, vcf + pos, ti)) {
+          l.append("mendel: the device's events do not match the batch's rows\n");
+          rc = BVCF_E_FATAL;
+          break;
+        }
+      }
       pos += nb;
     }
   }
@@ -177,6 +192,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (close_plink(R) && rc == BVCF_OK) {
     l.append("plinkOutput: write failed\n");
     rc = BVCF_E_FATAL;
+  }
+  if (R.mendel_fd >= 0 || R.mendel_errors_fd >= 0) {  // --mendel / --mendelErrors: after a successful run only
+    if (rc != BVCF_OK) {
+      close_mendel(R);
+    } else if (write_mendel(R, &msg)) {
+      l.append(msg + "\n");
+      rc = BVCF_E_IO;
+    }
   }
   if (ss_fd >= 0) {  // --sampleStats: the run's table, after a successful run only
     if (rc == BVCF_OK) {

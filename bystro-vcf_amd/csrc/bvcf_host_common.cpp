@@ -4,6 +4,7 @@
 //
 // Nothing here computes what the kernels compute: rows are assembled from bvcf_result only.
 #include "bvcf_host_internal.h"
+#include "../../include/bvcf_plan.h"
 
 #include <sched.h>
 
@@ -717,6 +718,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     *msg = std::string("plinkOutput: write failed: ") + strerror(errno);
     return BVCF_E_IO;
   }
+  if (const int rc = load_pedigree(R, msg)) return rc;  // --mendel / --mendelErrors: the trios among the (kept) names
   bvcf_params &p = R.params;
   memset(&p, 0, sizeof p);
   p.abi_version = BVCF_ABI_VERSION;
@@ -840,6 +842,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
     rc = bvcf_enable_bed_rows(*ctx);
     if (rc) {
       *msg = std::string("bvcf_enable_bed_rows: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
+  if (rc == BVCF_OK && R.mendel_on) {  // --mendel / --mendelErrors: the trio counts of every ctx of the run
+    rc = bvcf_enable_trios(*ctx, R.trios.data(), (uint32_t)(R.trios.size() / 3));
+    if (rc) {
+      *msg = std::string("bvcf_enable_trios: ") + bvcf_last_error(*ctx);
       bvcf_destroy(*ctx);
       *ctx = nullptr;
     }
@@ -998,6 +1008,175 @@ int close_plink(Run &R) {
   return rc;
 }
 
+int open_mendel(Run &R, std::string *msg) {
+  R.mendel_on = wants_mendel(R.cfg);
+  if (!R.mendel_on) return BVCF_OK;
+  const bvcf_config_trios *t = trios_config(R.cfg);
+  if (!t->fam_path || !*t->fam_path) {
+    *msg = "mendel: no pedigree (fam_path)";
+    return BVCF_E_ARG;
+  }
+  struct {
+    const char *path;
+    int *fd;
+  } files[2] = {{t->mendel_path, &R.mendel_fd}, {t->mendel_errors_path, &R.mendel_errors_fd}};
+  for (auto &f : files) {
+    if (!f.path || !*f.path) continue;
+    *f.fd = open(f.path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.fd < 0) {
+      *msg = std::string("open ") + f.path + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  return BVCF_OK;
+}
+
+int load_pedigree(Run &R, std::string *msg) {
+  if (!R.mendel_on) return BVCF_OK;
+  const char *path = trios_config(R.cfg)->fam_path;
+  std::string text;
+  {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+      *msg = std::string("open ") + path + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const int err = ferror(f) ? errno : 0;
+    fclose(f);
+    if (err) {
+      *msg = std::string("read ") + path + ": " + strerror(err);
+      return BVCF_E_IO;
+    }
+  }
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+  std::vector<const char *> names(ns);
+  std::vector<uint32_t> lens(ns);
+  for (size_t s = 0; s < ns; s++) {
+    names[s] = R.pre.header[9 + s].data();
+    lens[s] = (uint32_t)R.pre.header[9 + s].size();
+  }
+  R.trios.assign(3 * ns, 0u);  // (a sample is the child of one trio at most)
+  size_t n_trios = 0, iid_len = 0;
+  uint64_t line = 0;
+  const char *iid = nullptr;
+  const int why = bvcf_parse_fam(text.data(), text.size(), names.data(), lens.data(), (uint32_t)ns, R.trios.data(), ns, &n_trios,
+                                 &line, &iid, &iid_len);
+  if (why) {
+    const std::string who = iid ? std::string(iid, iid_len) : std::string();
+    *msg = std::string("fam ") + path + ": line " + std::to_string(line) + ": ";
+    switch (why) {
+      case BVCF_FAM_SHORT_LINE: msg->append("fewer than four fields (FID IID PAT MAT)"); break;
+      case BVCF_FAM_DUP_IID: msg->append("individual \"" + who + "\" is on two lines"); break;
+      case BVCF_FAM_AMBIGUOUS: msg->append("individual \"" + who + "\": a name of the line matches more than one sample column"); break;
+      case BVCF_FAM_SAME_SAMPLE: msg->append("individual \"" + who + "\": two of child, father and mother are the same sample"); break;
+      default: msg->append("cannot be read"); break;
+    }
+    return BVCF_E_IO;
+  }
+  R.trios.resize(3 * n_trios);
+  R.trio_counts.assign(3 * n_trios, 0);
+  return BVCF_OK;
+}
+
+// the batch's table into the run's; a line per event: the row's TSV columns from append_locus' inputs -- the rows
+// bvcf_trio_stats numbers are the rows this loop visits, in this order, as for append_plink
+int append_mendel(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_trio_info &ti) {
+  if (!R.mendel_on || R.trios.empty() || !r->n_samples) return BVCF_OK;
+  const size_t T = R.trios.size() / 3;
+  if (ti.n_trios != T || !ti.counts || (ti.n_events && !ti.events)) return BVCF_E_FATAL;
+  for (size_t k = 0; k < 3 * T; k++) R.trio_counts[k] += ti.counts[k];
+  if (R.mendel_errors_fd < 0 || !ti.n_events) return BVCF_OK;
+  static const char *const kClass[4] = {"ref", "het", "hom", "missing"};
+  std::string &o = R.mendel_events;
+  size_t at[5];
+  uint64_t row_i = 0, e = 0;
+  for (uint32_t li = 0; li < r->n_lines && e < ti.n_events; li++) {
+    const bvcf_line &L = r->lines[li];
+    if (L.status != BVCF_LINE_OK) continue;
+    const char *row = row_of(r, block, li, L);
+    for (uint32_t k = 0; k < L.n_rec && e < ti.n_events; k++) {
+      const bvcf_allele &A = r->alleles[k ? L.rec_first + k - 1 : li];
+      if (A.ac == 0) continue;  // main.go:558-560
+      for (; e < ti.n_events && ti.events[2 * e] == row_i; e++) {
+        const uint32_t w = ti.events[2 * e + 1], t = w & 0xFFFFFFu, c = (w >> 24) & 3u, f = (w >> 26) & 3u, m = (w >> 28) & 3u;
+        if (t >= T) return BVCF_E_FATAL;
+        append_locus(o, L, A, row, '\t', at);
+        for (int q = 0; q < 3; q++) {
+          o.push_back('\t');
+          o.append(R.pre.header[9 + R.trios[3 * t + q]]);
+        }
+        for (uint32_t cls : {c, f, m}) {
+          o.push_back('\t');
+          o.append(kClass[cls]);
+        }
+        o.append(f == 0 && m == 0 ? "\tdenovo\n" : "\terror\n");
+      }
+      row_i++;
+    }
+  }
+  return e == ti.n_events ? BVCF_OK : BVCF_E_FATAL;  // (an event names a row the batch has)
+}
+
+void close_mendel(Run &R) {
+  for (int *fd : {&R.mendel_fd, &R.mendel_errors_fd}) {
+    if (*fd >= 0) close(*fd);
+    *fd = -1;
+  }
+}
+
+int write_mendel(Run &R, std::string *msg) {
+  bool bad = false;
+  int saved = 0;
+  if (R.mendel_fd >= 0) {
+    std::string o = "child\tfather\tmother\tinformative\terrors\tdenovo\terrorRate\n";
+    for (size_t t = 0; t < R.trios.size() / 3; t++) {
+      for (int q = 0; q < 3; q++) {
+        o.append(R.pre.header[9 + R.trios[3 * t + q]]);
+        o.push_back('\t');
+      }
+      const uint64_t inf = R.trio_counts[3 * t], err = R.trio_counts[3 * t + 1], dn = R.trio_counts[3 * t + 2];
+      for (uint64_t v : {inf, err, dn}) {
+        append_ll(o, (long long)v);
+        o.push_back('\t');
+      }
+      if (inf == 0)
+        o.append(or_default(R.cfg->empty_field, "!"));
+      else if (err == 0)
+        o.push_back('0');
+      else
+        append_g3(o, (double)err / (double)inf);
+      o.push_back('\n');
+    }
+    if (write_all(R.mendel_fd, o.data(), o.size())) bad = true, saved = errno;
+    if (close(R.mendel_fd) && !bad) bad = true, saved = errno;
+    R.mendel_fd = -1;
+  }
+  if (R.mendel_errors_fd >= 0) {
+    static const char kHead[] = "chrom\tpos\tref\talt\tchild\tfather\tmother\tchildClass\tfatherClass\tmotherClass\tkind\n";
+    if (!bad && (write_all(R.mendel_errors_fd, kHead, sizeof kHead - 1) ||
+                 write_all(R.mendel_errors_fd, R.mendel_events.data(), R.mendel_events.size())))
+      bad = true, saved = errno;
+    if (close(R.mendel_errors_fd) && !bad) bad = true, saved = errno;
+    R.mendel_errors_fd = -1;
+  }
+  if (bad) {
+    *msg = std::string("mendel: write failed: ") + strerror(saved);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+// --mendel / --mendelErrors, after a BVCF_E_CAPACITY: the events arena grown to what the batch reported
+int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c) {
+  if (!wants_mendel(c)) return BVCF_OK;
+  bvcf_trio_info t;
+  if (bvcf_trio_stats(ctx, &t) != BVCF_OK) return BVCF_OK;
+  return bvcf_reserve_trio_events(ctx, t.need_events + t.need_events / 4 + 1024);
+}
+
 int close_dosage(Run &R) {
   if (!R.arrow) return BVCF_OK;
   const int rc = bvcf_arrow_close(R.arrow);
@@ -1030,6 +1209,7 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
     rc = bvcf_reserve(R.ctx, res->need_lines + res->need_lines / 4 + 64, res->need_alleles + res->need_alleles / 4 + 64,
                       res->need_cmap_bytes + res->need_cmap_bytes / 4 + 4096);
     if (rc == BVCF_OK) rc = reserve_bed_need(R.ctx, R.cfg);
+    if (rc == BVCF_OK) rc = reserve_trio_need(R.ctx, R.cfg);
     if (rc) {
       *msg = std::string("bvcf_reserve: ") + bvcf_last_error(R.ctx);
       return rc;

@@ -234,8 +234,16 @@ struct Run {
   // --plinkOutput: PREFIX.bed / .bim / .fam, opened by open_plink before any device work; prepare_run writes the .fam and
   // the .bed magic, append_plink a batch's rows and .bim lines in input order, close_plink closes what is open
   int bed_fd = -1, bim_fd = -1, fam_fd = -1;
+  // --mendel / --mendelErrors: both files opened by open_mendel before any device work; prepare_run reads --fam into
+  // trios ({child, father, mother} as kept-sample indices, by child); append_mendel adds a batch's [T][3] table to
+  // trio_counts and its events' lines to mendel_events, in input order; write_mendel writes both at the end
+  bool mendel_on = false;
+  int mendel_fd = -1, mendel_errors_fd = -1;
+  std::vector<uint32_t> trios;
+  std::vector<uint64_t> trio_counts;
+  std::string mendel_events;
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd})
+    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd})
       if (fd >= 0) close(fd);
   }
 };
@@ -260,6 +268,16 @@ int append_plink(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_
 int close_plink(Run &R);
 int write_plink_heads(Run &R);  // (prepare_run: the .fam and the .bed magic)
 int reserve_bed_need(bvcf_ctx *ctx, const bvcf_config *c);
+// --mendel / --mendelErrors: the files opened (truncated) -- BVCF_E_IO with one message in *msg; the pedigree read and
+// matched against the (kept) names (prepare_run) -- BVCF_E_IO with one message; the counts and events of one collected batch
+// (ti = what bvcf_trio_stats gave for it) added to the run's -- BVCF_E_FATAL when the events name a row the batch does not
+// have; both files written and closed at the end of a successful run; closed without writing otherwise
+int open_mendel(Run &R, std::string *msg);
+int load_pedigree(Run &R, std::string *msg);
+int append_mendel(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_trio_info &ti);
+int write_mendel(Run &R, std::string *msg);
+void close_mendel(Run &R);
+int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c);
 int close_dosage(Run &R);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
 // --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
@@ -296,6 +314,16 @@ inline const char *plink_prefix(const bvcf_config *c) {
 inline bool wants_plink(const bvcf_config *c) {
   const char *p = plink_prefix(c);
   return p && *p;
+}
+// --fam / --mendel / --mendelErrors: the config as a bvcf_config_trios (the fourth marker), or NULL
+inline const bvcf_config_trios *trios_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_TRIOS) ? reinterpret_cast<const bvcf_config_trios *>(c)
+                                                                                          : nullptr;
+}
+// true when the run counts trios (every ctx of the run then gets bvcf_enable_trios): one of the two outputs is asked for
+inline bool wants_mendel(const bvcf_config *c) {
+  const bvcf_config_trios *t = trios_config(c);
+  return t && ((t->mendel_path && *t->mendel_path) || (t->mendel_errors_path && *t->mendel_errors_path));
 }
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);

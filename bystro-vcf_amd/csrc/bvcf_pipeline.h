@@ -182,6 +182,7 @@ struct FmtJob {
   bvcf_result res;
   bool has_res = false;
   bvcf_bed_rows_info bed{};  // --plinkOutput: bvcf_bed_rows of the batch (valid as long as res)
+  bvcf_trio_info trio{};     // --mendel / --mendelErrors: bvcf_trio_stats of the batch (likewise)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };
@@ -297,6 +298,7 @@ class Driver {
   std::atomic<uint8_t> eol_byte_{'\n'};
   std::atomic<bool> dosage_failed_{false};
   std::atomic<bool> plink_failed_{false};  // --plinkOutput: likewise
+  std::atomic<bool> mendel_failed_{false};  // --mendel / --mendelErrors: likewise
   // stream mode
   std::string source_err_;
   std::unique_ptr<Channel<Block>> ready_q_;

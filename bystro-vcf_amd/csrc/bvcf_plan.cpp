@@ -4,6 +4,9 @@
 // work items (main.go:345-380).
 #include "bvcf_pipeline.h"
 
+#include <array>
+#include <unordered_map>
+
 namespace bvcf_host {
 
 // The byte ranges of a text file.  A reader reads range + spare straight into one pinned buffer of `cap` bytes.
@@ -256,5 +259,91 @@ int bvcf_plan_threads(uint32_t cpus, uint32_t n_workers, int mode, bvcf_thread_b
   *out = plan_threads(cpus, n_workers, mode);
   return BVCF_OK;
 }
+
+// A PLINK .fam against the sample names (the rules: bvcf_config_trios.fam_path in include/bvcf.h).  Per line, in this order:
+// the field count; the IID among the names (none: the line is ignored; two columns: ambiguous); the IID on an earlier
+// line; PAT and MAT ("0", or no such sample: none; two columns: ambiguous); then, with all three found, the same sample twice.
+int bvcf_parse_fam(const char *text, size_t len, const char *const *names, const uint32_t *name_lens, uint32_t n_names,
+                   uint32_t *trios_out, size_t cap, size_t *n_trios, uint64_t *bad_line, const char **bad_iid,
+                   size_t *bad_iid_len) {
+  if ((!text && len) || (n_names && (!names || !name_lens)) || !n_trios) return BVCF_FAM_ARG;
+  *n_trios = 0;
+  if (bad_line) *bad_line = 0;
+  if (bad_iid) *bad_iid = nullptr;
+  if (bad_iid_len) *bad_iid_len = 0;
+  std::unordered_map<std::string, std::pair<uint32_t, uint32_t>> cols;  // name -> {its first column, its columns}
+  for (uint32_t s = 0; s < n_names; s++) {
+    auto &e = cols[std::string(names[s], name_lens[s])];
+    if (!e.second++) e.first = s;
+  }
+  constexpr uint32_t kNone = 0xFFFFFFFFu, kTwo = 0xFFFFFFFEu;
+  auto find = [&](const char *p, size_t n) -> uint32_t {
+    const auto it = cols.find(std::string(p, n));
+    return it == cols.end() ? kNone : it->second.second > 1 ? kTwo : it->second.first;
+  };
+  std::vector<uint8_t> seen(n_names, 0);
+  std::vector<std::array<uint32_t, 3>> found;
+  uint64_t line = 0;
+  for (size_t pos = 0; pos < len;) {
+    const char *nl = (const char *)memchr(text + pos, '\n', len - pos);
+    const size_t e = nl ? (size_t)(nl - text) : len;
+    size_t n = e - pos;
+    line++;
+    if (n && text[pos + n - 1] == '\r') n--;
+    const char *f[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t fl[4] = {0, 0, 0, 0};
+    int nf = 0;
+    for (size_t i = 0; i < n && nf < 4;) {
+      while (i < n && (text[pos + i] == ' ' || text[pos + i] == '\t')) i++;
+      if (i == n) break;
+      const size_t b = i;
+      while (i < n && text[pos + i] != ' ' && text[pos + i] != '\t') i++;
+      f[nf] = text + pos + b;
+      fl[nf++] = i - b;
+    }
+    pos = e + 1;
+    if (!nf) continue;  // (an empty line, or one of blanks)
+    int why = BVCF_FAM_OK;
+    uint32_t who[3] = {kNone, kNone, kNone};
+    if (nf < 4) {
+      why = BVCF_FAM_SHORT_LINE;
+    } else {
+      who[0] = find(f[1], fl[1]);
+      if (who[0] == kNone) continue;  // (not a sample of this run: a .fam may describe a larger cohort)
+      if (who[0] == kTwo) {
+        why = BVCF_FAM_AMBIGUOUS;
+      } else if (seen[who[0]]) {
+        why = BVCF_FAM_DUP_IID;
+      } else {
+        seen[who[0]] = 1;
+        for (int q = 1; q < 3 && !why; q++) {
+          const bool none = fl[1 + q] == 1 && f[1 + q][0] == '0';
+          who[q] = none ? kNone : find(f[1 + q], fl[1 + q]);
+          if (who[q] == kTwo) why = BVCF_FAM_AMBIGUOUS;
+        }
+        if (!why && who[1] != kNone && who[2] != kNone) {
+          if (who[0] == who[1] || who[0] == who[2] || who[1] == who[2])
+            why = BVCF_FAM_SAME_SAMPLE;
+          else
+            found.push_back({who[0], who[1], who[2]});
+        }
+      }
+    }
+    if (why) {
+      if (bad_line) *bad_line = line;
+      if (nf >= 2 && why != BVCF_FAM_SHORT_LINE) {
+        if (bad_iid) *bad_iid = f[1];
+        if (bad_iid_len) *bad_iid_len = fl[1];
+      }
+      return why;
+    }
+  }
+  std::sort(found.begin(), found.end());  // (by child: a sample is the child of one line)
+  *n_trios = found.size();
+  for (size_t t = 0; t < found.size() && t < cap && trios_out; t++)
+    for (int q = 0; q < 3; q++) trios_out[3 * t + q] = found[t][q];
+  return BVCF_FAM_OK;
+}
+
 
 }  // extern "C"

@@ -45,6 +45,9 @@ struct Cli {
   std::string site_report;
   // extension: --plinkOutput PREFIX, the run's rows as PREFIX.bed / .bim / .fam (the .bed rows packed on the device)
   std::string plink;
+  // extension: --mendel PATH / --mendelErrors PATH, per trio of --fam's pedigree the rows that are Mendelian errors and
+  // de novo calls, and the list of them (counted on the device); --fam alone stays accepted and ignored
+  std::string mendel, mendel_errors;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -139,7 +142,7 @@ int parse(int argc, char **argv, Cli &c) {
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
         name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
         name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
-        name == "plinkOutput") {
+        name == "plinkOutput" || name == "mendel" || name == "mendelErrors") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -163,6 +166,12 @@ int parse(int argc, char **argv, Cli &c) {
         c.site_report = val;
       } else if (name == "plinkOutput") {
         c.plink = val;
+      } else if (name == "mendel" || name == "mendelErrors") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to write\n", name.c_str());
+          return 2;
+        }
+        (name == "mendel" ? c.mendel : c.mendel_errors) = val;
       } else if (name == "minMac") {
         if (!parse_threshold(val, &c.min_mac)) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
@@ -197,6 +206,10 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-keepSamples and -excludeSamples cannot both be given\n");
     return 2;
   }
+  if ((!c.mendel.empty() || !c.mendel_errors.empty()) && c.fam.empty()) {
+    fprintf(stderr, "-mendel and -mendelErrors need the pedigree: -fam PATH\n");
+    return 2;
+  }
   return 0;
 }
 
@@ -227,8 +240,9 @@ int main(int argc, char **argv) {
     return 1;
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
-  // conversion-only pass)
-  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty()) {
+  // conversion-only pass; --mendel / --mendelErrors alone: QC-only again)
+  if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
+      c.mendel.empty() && c.mendel_errors.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -240,8 +254,11 @@ int main(int argc, char **argv) {
     }
   }
 
-  bvcf_config_more more;  // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix)
-  bvcf_config_plink_defaults(&more);
+  // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
+  // pedigree and the two --mendel paths)
+  bvcf_config_trios trios;
+  bvcf_config_trios_defaults(&trios);
+  bvcf_config_more &more = trios.more;
   bvcf_config &cfg = more.base;
   cfg.empty_field = c.empty.c_str();
   cfg.field_delimiter = c.delim.c_str();
@@ -298,6 +315,9 @@ int main(int argc, char **argv) {
   more.site_gate.hwe_p = c.hwe;
   more.site_filter_path = c.site_report.c_str();
   more.plink_prefix = c.plink.c_str();
+  trios.fam_path = c.fam.c_str();
+  trios.mendel_path = c.mendel.c_str();
+  trios.mendel_errors_path = c.mendel_errors.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -440,6 +440,44 @@ int bvcf_enable_bed_rows(bvcf_ctx *ctx);
 int bvcf_reserve_bed_rows(bvcf_ctx *ctx, uint64_t bytes);
 /* the rows of the batch bvcf_collect returned last on ctx.  BVCF_E_ARG on a ctx without bvcf_enable_bed_rows */
 int bvcf_bed_rows(const bvcf_ctx *ctx, bvcf_bed_rows_info *out);
+/* Per-trio Mendelian error and de novo counts over the same rows, counted on the device from the class maps (which the
+ * ctx then makes even when want_class_maps is 0, without copying them to the host).  trios: n triples {child, father,
+ * mother} of sample indices as bvcf_result sees them (the kept samples), copied.  Per (row, trio), with the classes c, f, m
+ * of the three samples in the row (none / het / hom / missing by the list that names the sample; a masked call is
+ * missing, a haploid call hom; a record without a usable map is all missing):
+ *   uninformative  one of the three is missing
+ *   consistent     the child's ALT count (0 / 1 / 2) is a + b for some a the father can transmit and some b the mother can
+ *                  (none {0}, het {0, 1}, hom {1})
+ *   de novo        otherwise, with both parents none
+ *   error          otherwise
+ * A multiallelic line gives one row per output allele, "this ALT against the rest", which maps consistent trios to
+ * consistent ones.  There is no sex or chrX handling.  Everything is integer work and no atomic places an event, so the
+ * table and the events are a property of the data.
+ * Call bvcf_enable_trios once, before the first submit, like bvcf_enable_pair_stats: BVCF_E_ARG for an index >= S, two
+ * equal indices in a trio, 2^24 trios or more, or a second call; with n = 0 (the only n a ctx without sample columns
+ * accepts) nothing is allocated or launched and every batch reports no counts and no events.  bvcf_params and the ABI
+ * version do not change with it.
+ * The events go into an arena of the slot with a bound of its own, in events: max_batch_bytes / 64 to begin with (at
+ * least 1 024).  A row costs a line of text -- hundreds of bytes and more once there are trios in it -- and real pedigrees
+ * contradict a few calls per thousand (row, trio) pairs, so one event per 64 bytes of text is room enough for cohorts of
+ * thousands of trios; a wrong pedigree file, which is what the counts are there to show, outruns it and is then handled like
+ * every other capacity: the batch comes back BVCF_E_CAPACITY, bvcf_trio_stats reports need_events,
+ * bvcf_reserve_trio_events(ctx, n) -- with no batch in flight, like bvcf_reserve -- grows the arena, and the batch is
+ * submitted again.  A batch holds fewer than 2^32 events. */
+typedef struct {
+  const uint32_t *counts; /* [n_trios][3]: informative rows, errors (de novo included), de novo -- of this batch alone */
+  const uint32_t *events; /* [n_events][2]: {row of the batch in output order, trio | c << 24 | f << 26 | m << 28}, every
+                           * de novo or error verdict, by row, then by trio */
+  uint64_t n_events;
+  uint64_t need_events; /* what the batch's events take (also after BVCF_E_CAPACITY, when counts and events are NULL) */
+  uint32_t n_trios;
+  uint32_t reserved;
+} bvcf_trio_info;
+int bvcf_enable_trios(bvcf_ctx *ctx, const uint32_t *trios /* [n][3]: child, father, mother as kept-sample indices */, uint32_t n);
+int bvcf_reserve_trio_events(bvcf_ctx *ctx, uint64_t n);
+/* the counts and events of the batch bvcf_collect returned last on ctx; the pointers are valid as long as those of the
+ * bvcf_result collected with them.  BVCF_E_ARG on a ctx without bvcf_enable_trios */
+int bvcf_trio_stats(const bvcf_ctx *ctx, bvcf_trio_info *out);
 
 /* The per-site QC gate (--minMaf / --maxMaf / --minMac / --maxMissing / --hwe).  size = sizeof(bvcf_site_gate).  A criterion
  * at its neutral value is off; with all of them neutral the ctx allocates and launches nothing for the gate.
@@ -599,6 +637,33 @@ void bvcf_config_more_defaults(bvcf_config_more *c); /* bvcf_config_defaults, th
 void bvcf_config_gate_defaults(bvcf_config_more *c);
 /* the whole struct: bvcf_config_gate_defaults, base.reserved[1] = BVCF_CONFIG_MORE_PLINK, no fileset */
 void bvcf_config_plink_defaults(bvcf_config_more *c);
+/* bvcf_config_more keeps its size: what came after it lives in a struct that begins with one.  Read only when
+ * more.base.reserved[0] = BVCF_CONFIG_MORE and more.base.reserved[1] >= BVCF_CONFIG_MORE_TRIOS (which, as before, means "at
+ * least" for the older fields).  bvcf_config_trios_defaults sets that; the three older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_TRIOS 3
+typedef struct {
+  bvcf_config_more more;
+  /* --fam: a PLINK .fam -- FID IID PAT MAT [SEX [PHENO]] per line, fields separated by runs of spaces or TABs, a trailing
+   * \r dropped, empty lines ignored; PAT / MAT "0" = none.  Names are compared byte for byte with the (kept) sample names as
+   * the sample list file has them.  A line whose IID is no (kept) sample is ignored; a line whose IID, PAT and MAT are all
+   * (kept) samples is a trio; trios are ordered by the child's position in the header.  Read only when mendel_path or
+   * mendel_errors_path is set -- alone it is accepted and ignored -- and then required.  Errors (BVCF_E_IO, one message):
+   * an unreadable file, a line of one to three fields, an IID that is a (kept) sample on two lines, a name that matches
+   * two sample columns, a trio with one sample twice. */
+  const char *fam_path;
+  /* --mendel: "child father mother informative errors denovo errorRate", then a tab-separated line per trio -- the sums
+   * of bvcf_trio_stats' counts over the batches of the output; errorRate = errors / informative printed as the TSV's ratios
+   * are, empty_field without informative rows.  Opened before any device work, written at the end of a successful run;
+   * the bytes do not depend on devices, batch size or input kind.  NULL or "" = no table */
+  const char *mendel_path;
+  /* --mendelErrors: "chrom pos ref alt child father mother childClass fatherClass motherClass kind", then a
+   * tab-separated line per event in TSV order (trios in trio order within a row): the row's TSV columns, the three
+   * names, the classes as ref / het / hom, kind = denovo or error.  Likewise opened first and written at the end (it is
+   * kept in memory until then).  NULL or "" = no list */
+  const char *mendel_errors_path;
+} bvcf_config_trios;
+/* the whole struct: bvcf_config_plink_defaults, more.base.reserved[1] = BVCF_CONFIG_MORE_TRIOS, no paths */
+void bvcf_config_trios_defaults(bvcf_config_trios *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

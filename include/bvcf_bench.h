@@ -67,6 +67,11 @@ int bvcf_bench_gate_kernels(bvcf_ctx *ctx, float ms[2]);
  * k_bed_rows wrote (rows * row_bytes).  BVCF_E_ARG on a ctx without bed rows, BVCF_E_CAPACITY when the rows outrun the arena */
 int bvcf_bench_bed_kernels(bvcf_ctx *ctx, float ms[2], uint64_t out[2]);
 
+/* bvcf_enable_trios: the trio kernels over the records and class maps the first slot's last bench chain left, with HIP
+ * events around them: ms = {the row index and the two memsets, k_trio_count, k_trio_scan, k_trio_fill}; out[0] = the rows,
+ * out[1] = the events.  BVCF_E_ARG on a ctx without trios, BVCF_E_CAPACITY when the events outrun the arena */
+int bvcf_bench_trio_kernels(bvcf_ctx *ctx, float ms[4], uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,28 @@ uint32_t bvcf_hwe_inline_terms(void);
  * bad arguments. */
 int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out);
 
+/* The per-(row, trio) code of the trio counts (csrc/bvcf_mendel.hip.h; bvcf_enable_trios in include/bvcf.h), run on the
+ * host: the same function the kernels run.  Classes: 0 none, 1 het, 2 hom, 3 missing.  Returns BVCF_TRIO_*; -1 for a
+ * class above 3. */
+enum { BVCF_TRIO_UNINFORMATIVE = 0, BVCF_TRIO_CONSISTENT = 1, BVCF_TRIO_DENOVO = 2, BVCF_TRIO_ERROR = 3 };
+int bvcf_trio_verdict(uint32_t child, uint32_t father, uint32_t mother);
+/* A PLINK .fam against the (kept) sample names, by the rules of bvcf_config_trios.fam_path: text[0, len) is the file,
+ * names / name_lens the n_names sample names in header order.  trios_out (may be NULL) receives up to cap triples
+ * {child, father, mother} of name indices, ordered by child; *n_trios the number of trios found (may exceed cap).
+ * Returns 0, or a BVCF_FAM_* reason with *bad_line = the 1-based line it was found on and, for the reasons that name an
+ * individual, bad_iid[0, *bad_iid_len) = its IID inside text. */
+enum {
+  BVCF_FAM_OK = 0,
+  BVCF_FAM_SHORT_LINE = 1,    /* one to three fields */
+  BVCF_FAM_DUP_IID = 2,       /* an IID that is a sample, on two lines */
+  BVCF_FAM_AMBIGUOUS = 3,     /* a name of the line (bad_iid: the line's IID) matches more than one sample column */
+  BVCF_FAM_SAME_SAMPLE = 4,   /* two of a trio's three names are the same sample */
+  BVCF_FAM_ARG = -1
+};
+int bvcf_parse_fam(const char *text, size_t len, const char *const *names, const uint32_t *name_lens, uint32_t n_names,
+                   uint32_t *trios_out, size_t cap, size_t *n_trios, uint64_t *bad_line, const char **bad_iid,
+                   size_t *bad_iid_len);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
