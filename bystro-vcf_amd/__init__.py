@@ -47,13 +47,15 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
                  "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
-                 "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels"]
+                 "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
                 "bvcf_plan_threads", "bvcf_plan_fd", "bvcf_head_fast_line", "bvcf_plan_ctx",
                 "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms", "bvcf_bed_row",
-                "bvcf_trio_verdict", "bvcf_parse_fam"]
+                "bvcf_trio_verdict", "bvcf_parse_fam",
+                "bvcf_ld_counts", "bvcf_ld_in_ld", "bvcf_parse_ld_r2", "bvcf_ld_seam_create", "bvcf_ld_seam_push",
+                "bvcf_ld_seam_read", "bvcf_ld_seam_rows", "bvcf_ld_seam_pairs", "bvcf_ld_seam_destroy"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -64,6 +66,7 @@ EXPORTS = [
     "bvcf_site_gate_defaults", "bvcf_set_site_gate", "bvcf_site_gate_count", "bvcf_config_gate_defaults",
     "bvcf_enable_bed_rows", "bvcf_reserve_bed_rows", "bvcf_bed_rows", "bvcf_config_plink_defaults",
     "bvcf_enable_trios", "bvcf_reserve_trio_events", "bvcf_trio_stats", "bvcf_config_trios_defaults",
+    "bvcf_enable_ld", "bvcf_reserve_ld_events", "bvcf_ld_stats", "bvcf_config_ld_defaults",
 ]
 
 
@@ -157,6 +160,24 @@ class TrioInfo(C.Structure):
     """bvcf_trio_info"""
     _fields_ = [("counts", C.c_void_p), ("events", C.c_void_p), ("n_events", C.c_uint64), ("need_events", C.c_uint64),
                 ("n_trios", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONFIG_MORE_LD = 4  # BVCF_CONFIG_MORE_LD in Config.reserved[1]: the ConfigTrios is the head of a ConfigLd
+LD_COLUMNS = ["chrom", "pos1", "ref1", "alt1", "pos2", "ref2", "alt2", "n", "r2", "dir"]
+LD_MAX_WINDOW = 512
+
+
+class ConfigLd(C.Structure):
+    """bvcf_config_ld: a bvcf_config_trios and what came after it"""
+    _fields_ = [("trios", ConfigTrios), ("ld_path", C.c_char_p), ("ld_prune_prefix", C.c_char_p), ("ld_window", C.c_uint32),
+                ("ld_t6", C.c_uint32), ("ld_t6_set", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LdInfo(C.Structure):
+    """bvcf_ld_info"""
+    _fields_ = [("events", C.c_void_p), ("n_events", C.c_uint64), ("need_events", C.c_uint64), ("need_row_bytes", C.c_uint64),
+                ("head_rows", C.c_void_p), ("tail_rows", C.c_void_p), ("n_rows", C.c_uint64), ("n_edge", C.c_uint32),
+                ("row_bytes", C.c_uint32), ("window", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Result(C.Structure):
@@ -366,7 +387,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     The returned object keeps the byte strings alive."""
     cfg = cfg or {}
     # (--mendel / --mendelErrors: the larger struct and its marker, only then; every other config is a ConfigMore as before)
-    trios = ConfigTrios() if cfg.get("mendel") or cfg.get("mendelErrors") else None
+    # (--ld / --ldPrune: the still larger struct and its marker, only then)
+    ldc = ConfigLd() if cfg.get("ld") or cfg.get("ldPrune") else None
+    trios = ldc.trios if ldc is not None else ConfigTrios() if cfg.get("mendel") or cfg.get("mendelErrors") else None
     more = trios.more if trios is not None else ConfigMore()
     c = more.base  # (a view of more's memory, which it keeps alive: what the callers pass on is the head of a bvcf_config_more)
     lib.bvcf_config_defaults(C.byref(c))
@@ -434,8 +457,111 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 setattr(trios, field, keep[-1])
         c.reserved[0] = CONFIG_MORE
         c.reserved[1] = CONFIG_MORE_TRIOS
+    if ldc is not None:  # the table, the prune prefix, the window and the threshold (ldR2: the flag's text)
+        for key, field in (("ld", "ld_path"), ("ldPrune", "ld_prune_prefix")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(ldc, field, keep[-1])
+        ldc.ld_window = int(cfg.get("ldWindow", 50))
+        ldc.ld_t6 = parse_ld_r2(str(cfg.get("ldR2", "0.2")))
+        ldc.ld_t6_set = 1
+        c.reserved[1] = CONFIG_MORE_LD
     c._keep = keep
     return c
+
+
+def ld_counts(row_a, row_b, n_samples):
+    """bvcf_ld_counts: two rows in .bed code (bytes-like, ceil(S / 4) bytes) -> [n, sa, sb, saa, sbb, sab]  (host code, no device)"""
+    rb = (n_samples + 3) // 4
+    a = (C.c_uint8 * rb).from_buffer_copy(bytes(row_a)[:rb])
+    b = (C.c_uint8 * rb).from_buffer_copy(bytes(row_b)[:rb])
+    out = (C.c_uint32 * 6)()
+    lib.bvcf_ld_counts.restype = C.c_int
+    lib.bvcf_ld_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    if lib.bvcf_ld_counts(a, b, n_samples, out):
+        raise ValueError("bvcf_ld_counts: bad arguments")
+    return [int(x) for x in out]
+
+
+def ld_in_ld(counts, t6):
+    """bvcf_ld_in_ld: the exact 128-bit predicate on [n, sa, sb, saa, sbb, sab] at t6 millionths -> bool  (host code)"""
+    k = (C.c_uint32 * 6)(*[int(x) for x in counts])
+    lib.bvcf_ld_in_ld.restype = C.c_int
+    lib.bvcf_ld_in_ld.argtypes = [C.c_void_p, C.c_uint32]
+    r = lib.bvcf_ld_in_ld(k, t6)
+    if r < 0:
+        raise ValueError("bvcf_ld_in_ld: bad arguments")
+    return bool(r)
+
+
+def parse_ld_r2(text):
+    """bvcf_parse_ld_r2: the text of --ldR2 -> millionths; ValueError for a text outside the flag's rules"""
+    t6 = C.c_uint32()
+    lib.bvcf_parse_ld_r2.restype = C.c_int
+    lib.bvcf_parse_ld_r2.argtypes = [C.c_char_p, C.c_void_p]
+    if lib.bvcf_parse_ld_r2(text.encode() if isinstance(text, str) else bytes(text), C.byref(t6)):
+        raise ValueError("ldR2: %r" % (text,))
+    return int(t6.value)
+
+
+class LdSeam:
+    """bvcf_ld_seam_*: the state machine behind --ld / --ldPrune, fed batches cut anywhere (host code, no device)"""
+
+    def __init__(self, n_samples, window, t6):
+        lib.bvcf_ld_seam_create.restype = C.c_void_p
+        lib.bvcf_ld_seam_create.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+        self.h = lib.bvcf_ld_seam_create(n_samples, window, t6)
+        if not self.h:
+            raise ValueError("bvcf_ld_seam_create: bad arguments")
+        self.window, self.rb = window, (n_samples + 3) // 4
+
+    def push(self, rows, events, loci):
+        """rows: uint8 (n_rows, row_bytes) in .bed code -- only the first and last min(window, n_rows) are handed on, as a
+        ctx gives them; events: uint32 (n, 8), rows local to the batch; loci: list of bytes "chrom\tpos\tref\talt" """
+        rows = np.ascontiguousarray(rows, dtype=np.uint8).reshape(len(loci), self.rb)
+        n = len(loci)
+        k = min(self.window, n)
+        head, tail = np.ascontiguousarray(rows[:k]), np.ascontiguousarray(rows[n - k:])
+        return self.push_edges(n, head, tail, events, loci)
+
+    def push_edges(self, n_rows, head, tail, events, loci):
+        ev = np.ascontiguousarray(events, dtype=np.uint32).reshape(-1, 8)
+        text = b"".join(loci)
+        off = np.zeros(n_rows + 1, dtype=np.uint64)
+        if n_rows:
+            off[1:] = np.cumsum([len(x) for x in loci])
+        head = np.ascontiguousarray(head, dtype=np.uint8)
+        tail = np.ascontiguousarray(tail, dtype=np.uint8)
+        buf = C.create_string_buffer(text, len(text) + 1)
+        lib.bvcf_ld_seam_push.restype = C.c_int
+        lib.bvcf_ld_seam_push.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.c_void_p, C.c_void_p]
+        rc = lib.bvcf_ld_seam_push(self.h, n_rows, min(self.window, n_rows), head.ctypes.data if head.size else None,
+                                   tail.ctypes.data if tail.size else None, ev.ctypes.data if len(ev) else None, len(ev), buf,
+                                   off.ctypes.data)
+        if rc:
+            raise ValueError("bvcf_ld_seam_push: the batch contradicts itself")
+
+    def read(self, which):
+        """0: the table's lines (no header), 1: .prune.in, 2: .prune.out -> bytes"""
+        p, n = C.c_void_p(), C.c_size_t()
+        lib.bvcf_ld_seam_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if lib.bvcf_ld_seam_read(self.h, which, C.byref(p), C.byref(n)):
+            raise ValueError("bvcf_ld_seam_read")
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def counts(self):
+        lib.bvcf_ld_seam_rows.restype = lib.bvcf_ld_seam_pairs.restype = C.c_uint64
+        lib.bvcf_ld_seam_rows.argtypes = lib.bvcf_ld_seam_pairs.argtypes = [C.c_void_p]
+        return int(lib.bvcf_ld_seam_rows(self.h)), int(lib.bvcf_ld_seam_pairs(self.h))
+
+    def close(self):
+        if self.h:
+            lib.bvcf_ld_seam_destroy.argtypes = [C.c_void_p]
+            lib.bvcf_ld_seam_destroy(self.h)
+            self.h = None
+
+    __del__ = close
 
 
 def trio_verdict(child, father, mother):
@@ -818,7 +944,7 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -847,6 +973,13 @@ class Ctx:
             t = np.ascontiguousarray(np.asarray(trios, dtype=np.uint32).reshape(-1, 3))
             lib.bvcf_enable_trios.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
             rc = lib.bvcf_enable_trios(self.h, t.ctypes.data if len(t) else None, len(t))
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+        if ld is not None:  # bvcf_enable_ld: (window, t6) (read with ld_stats() after each collect)
+            lib.bvcf_enable_ld.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+            rc = lib.bvcf_enable_ld(self.h, int(ld[0]), int(ld[1]))
             if rc:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
@@ -1027,6 +1160,41 @@ class Ctx:
         """bvcf_reserve_trio_events: grow the arena of the events (no batch in flight)"""
         lib.bvcf_reserve_trio_events.argtypes = [C.c_void_p, C.c_uint64]
         self._check(lib.bvcf_reserve_trio_events(self.h, int(n)))
+
+    def ld_info(self):
+        """bvcf_ld_stats: the LdInfo of the batch collected last (need_events is set after BVCF_E_CAPACITY too)"""
+        info = LdInfo()
+        lib.bvcf_ld_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_ld_stats(self.h, C.byref(info)))
+        return info
+
+    def ld_stats(self):
+        """the batch collected last -> (events uint32 (n_events, 8): b, d, n, sa, sb, saa, sbb, sab; head rows and tail rows
+        uint8 (n_edge, row_bytes) in .bed code; rows of the batch), copied out of the slot"""
+        info = self.ld_info()
+        ne, k, rb = int(info.n_events), int(info.n_edge), int(info.row_bytes)
+        ev = np.zeros((ne, 8), dtype=np.uint32)
+        if ne:
+            ev = np.frombuffer((C.c_uint32 * (8 * ne)).from_address(info.events), dtype=np.uint32).reshape(ne, 8).copy()
+        head = tail = np.zeros((0, rb), dtype=np.uint8)
+        if k and rb:
+            head = np.frombuffer((C.c_uint8 * (k * rb)).from_address(info.head_rows), dtype=np.uint8).reshape(k, rb).copy()
+            tail = np.frombuffer((C.c_uint8 * (k * rb)).from_address(info.tail_rows), dtype=np.uint8).reshape(k, rb).copy()
+        return ev, head, tail, int(info.n_rows)
+
+    def reserve_ld_events(self, n):
+        """bvcf_reserve_ld_events: grow the arena of the events (no batch in flight)"""
+        lib.bvcf_reserve_ld_events.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(lib.bvcf_reserve_ld_events(self.h, int(n)))
+
+    def bench_ld_kernels(self):
+        """the LD kernels over the first slot's last bench chain -> (ms of [row index, k_bed_rows, k_ld_keys, k_ld_pairs
+        counting, k_ld_scan, k_ld_pairs filling], rows, events)"""
+        ms = (C.c_float * 6)()
+        out = (C.c_uint64 * 2)()
+        lib.bvcf_bench_ld_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(lib.bvcf_bench_ld_kernels(self.h, ms, out))
+        return list(ms), int(out[0]), int(out[1])
 
     def bench_trio_kernels(self):
         """the trio kernels over the first slot's last bench chain -> (ms of [row index + memsets, k_trio_count, k_trio_scan,

@@ -140,6 +140,17 @@ struct Slot {
   DevBuf<uint2> d_trio_ev;
   PinBuf<uint2> h_trio_ev;
   uint64_t cap_trio = 0;
+  // bvcf_enable_ld (bvcf_ld.hip.h): a row's chrom key and its events (follow max_alleles), the batch's event count, the
+  // arena of the events with its pinned copy -- a bound of its own (bvcf_ctx.ld_cap, in events) -- and the pinned copy of
+  // the batch's first and last `window` rows
+  DevBuf<uint4> d_ld_key;
+  DevBuf<uint32_t> d_ld_rowev;
+  DevBuf<unsigned long long> d_ld_total;
+  PinBuf<unsigned long long> h_ld_total;
+  DevBuf<uint32_t> d_ld_ev;
+  PinBuf<uint32_t> h_ld_ev;
+  PinBuf<uint8_t> h_ld_edge;
+  uint64_t cap_ld = 0;
   // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
   // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
@@ -204,6 +215,13 @@ struct bvcf_ctx : bvcf_ctx_plan {
   DevBuf<uint32_t> d_trios;
   uint64_t trio_cap = 0;
   bvcf_trio_info trio_last{};
+  // bvcf_enable_ld on a file with samples: k_bed_rows (once, shared with the fileset), k_ld_keys, k_ld_pairs / k_ld_scan /
+  // k_ld_pairs at the end of every chain, behind the same row index; ld_cap is what a slot's events arena holds
+  // (bvcf_reserve_ld_events grows it), ld_last the batch collected last (bvcf_ld_stats)
+  bool ld_asked = false, ld_on = false;
+  uint32_t ld_window = 0, ld_t6 = 0;
+  uint64_t ld_cap = 0;
+  bvcf_ld_info ld_last{};
   const void *bench_src = nullptr;  // the last block of the last bvcf_bench_device* call (bvcf_bench_gate_kernels)
   size_t bench_nbytes = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
@@ -493,7 +511,7 @@ int alloc_gate_list(bvcf_ctx *c, Slot &s) {
 // (follows max_alleles) and the counter; the .bed arena and its pinned copy when the ctx's bound has grown past what the
 // slot holds
 int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
-  if (!c->bed_on && !c->trio_on) return BVCF_OK;
+  if (!c->bed_on && !c->trio_on && !c->ld_on) return BVCF_OK;
   if (s.d_bed_base.size() < c->max_lines) {
     HIP_TRY(c, s.d_bed_base.alloc(c->max_lines));
     HIP_TRY(c, s.d_bed_tile.alloc(c->max_lines / kBedTile + 2));
@@ -503,10 +521,11 @@ int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, s.d_bed_total.alloc(1));
     HIP_TRY(c, s.h_bed_total.alloc(1));
   }
-  if (c->bed_on && s.cap_bed < c->bed_cap) {
+  // (the pairs read the arena on the device: only the fileset has a pinned copy of it)
+  if ((c->bed_on || c->ld_on) && (s.cap_bed < c->bed_cap || (c->bed_on && !s.h_bed))) {
     s.cap_bed = 0;
     HIP_TRY(c, s.d_bed.alloc(c->bed_cap + 16));
-    HIP_TRY(c, s.h_bed.alloc(c->bed_cap + 16));
+    if (c->bed_on) HIP_TRY(c, s.h_bed.alloc(c->bed_cap + 16));
     s.cap_bed = c->bed_cap;
   }
   return BVCF_OK;
@@ -535,10 +554,34 @@ int alloc_trios(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
+// the events of max_alleles rows and, behind them, of their tiles of kLdTile rows
+size_t ld_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kLdTile + 2; }
+
+// bvcf_enable_ld: the keys and the events per row and per tile (follow max_alleles), the counter and the edge rows; the
+// events arena and its pinned copy when the ctx's bound has grown past what the slot holds
+int alloc_ld(bvcf_ctx *c, Slot &s) {
+  if (!c->ld_on) return BVCF_OK;
+  if (!s.d_ld_total) {
+    HIP_TRY(c, s.d_ld_total.alloc(1));
+    HIP_TRY(c, s.h_ld_total.alloc(1));
+    HIP_TRY(c, s.h_ld_edge.alloc(2ull * c->ld_window * ((c->n_samples + 3u) / 4u) + 16));
+  }
+  if (s.d_ld_key.size() < c->max_alleles) HIP_TRY(c, s.d_ld_key.alloc(c->max_alleles));
+  if (s.d_ld_rowev.size() < ld_rowev_words(c->max_alleles)) HIP_TRY(c, s.d_ld_rowev.alloc(ld_rowev_words(c->max_alleles)));
+  if (s.cap_ld < c->ld_cap) {
+    s.cap_ld = 0;
+    HIP_TRY(c, s.d_ld_ev.alloc(8ull * c->ld_cap));
+    HIP_TRY(c, s.h_ld_ev.alloc(8ull * c->ld_cap));
+    s.cap_ld = c->ld_cap;
+  }
+  return BVCF_OK;
+}
+
 int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_gate_list(c, s)) return rc;
   if (const int rc = alloc_bed_rows(c, s)) return rc;
   if (const int rc = alloc_trios(c, s)) return rc;
+  if (const int rc = alloc_ld(c, s)) return rc;
   if (!c->ss_on && !c->pr_on) return BVCF_OK;
   s.d_pr_planes.reset();
   s.cap_pr_tiles = 0;
@@ -653,7 +696,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on;  // (the per-sample, pair and trio counts and the .bed rows are made from the maps on the device)
+  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on;  // (the per-sample, pair and trio counts and the .bed rows are made from the maps on the device)
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -810,6 +853,36 @@ void launch_row_index(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const Be
   hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
 }
 
+// ... and everything the LD kernels write (the arena of the rows among it)
+bool ld_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.d_ld_ev && s.d_ld_total && s.d_ld_key.size() >= c->max_alleles && s.d_ld_rowev.size() >= ld_rowev_words(c->max_alleles) &&
+         bed_ready(c, s);
+}
+
+LdArgs make_ld_args(bvcf_ctx *c, Slot &s) {
+  LdArgs la{};
+  la.window = c->ld_window;
+  la.t6 = c->ld_t6;
+  la.ev_rows = (uint32_t)c->max_alleles;
+  la.row_key = s.d_ld_key;
+  la.row_events = s.d_ld_rowev;
+  la.total = s.d_ld_total;
+  la.events = s.d_ld_ev;
+  la.cap = s.cap_ld;
+  return la;
+}
+
+constexpr int kLdPairWgs = 8;  // workgroups per CU (13 KB of LDS each)
+
+// bvcf_enable_ld: the rows' chrom keys, then count, scan and fill (bvcf_ld.hip.h; bvcf_collect copies the used part of the
+// events and the edge rows)
+void launch_ld_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const LdArgs &la) {
+  hipLaunchKernelGGL(k_ld_keys, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba, la);
+  hipLaunchKernelGGL(k_ld_pairs<false>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
+  hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(1024), 0, st, a, ba, la);
+  hipLaunchKernelGGL(k_ld_pairs<true>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
+}
+
 TrioArgs make_trio_args(bvcf_ctx *c, Slot &s) {
   TrioArgs ta{};
   ta.trios = c->d_trios;
@@ -840,11 +913,13 @@ int launch_trio_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const 
 // -- once --, then the .bed rows into the slot's arena and the trios' counts and events into theirs
 void launch_trios(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
   if (!slot) return;
-  const bool bed = c->bed_on && bed_ready(c, *slot), trios = c->trio_on && trios_ready(c, *slot);
+  const bool ld = c->ld_on && ld_ready(c, *slot);
+  const bool bed = (c->bed_on && bed_ready(c, *slot)) || ld, trios = c->trio_on && trios_ready(c, *slot);
   if (!bed && !trios) return;
   const BedArgs ba = make_bed_args(c, *slot);
   launch_row_index(c, a, st, ba);
   if (bed) launch_bed_rows(c, a, st, ba);
+  if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
   if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)
 }
 
@@ -1264,8 +1339,10 @@ int launch_batch(bvcf_ctx *c, Slot &s, const uint8_t *src, size_t nbytes) {
   }
   HIP_TRY(c, hipEventRecord(s.ev_k1, s.stream));
   HIP_TRY(c, hipMemcpyAsync(s.h_counters, s.d_counters, sizeof(BatchCounters), hipMemcpyDeviceToHost, s.stream));
-  if ((c->bed_on || c->trio_on) && s.d_bed_total)
+  if ((c->bed_on || c->trio_on || c->ld_on) && s.d_bed_total)
     HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (c->ld_on && ld_ready(c, s))
+    HIP_TRY(c, hipMemcpyAsync(s.h_ld_total, s.d_ld_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   if (c->trio_on && trios_ready(c, s))
     HIP_TRY(c, hipMemcpyAsync(s.h_trio_total, s.d_trio_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   if (c->render) {
@@ -1973,7 +2050,7 @@ static BatchNeeds batch_needs(const bvcf_ctx *c, const Slot &s, const BatchCount
   n.n_alleles = n.extras_at + ctr.n_alleles;
   n.n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
   n.need_alleles = std::max<uint64_t>(std::max<uint64_t>(n.n_alleles, ctr.n_errs), n.n_tasks);
-  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on) && c->n_samples;
+  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on) && c->n_samples;
   n.cmap_need = maps ? cmap_bytes_of(c, ctr) : 0;
   n.fits = ctr.n_lines <= s.cap_lines && n.need_alleles <= s.cap_alleles && n.cmap_need <= s.cap_cmap;
   return n;
@@ -2180,7 +2257,7 @@ static void fill_result(const bvcf_ctx *c, const Slot &s, const Collected &k, ui
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = ((c->ss_on || c->pr_on || c->bed_on || c->trio_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
+  r->cmap = ((c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage.get() : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = k.was_bgzf ? s.h_text.get() : nullptr;
@@ -2268,13 +2345,22 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   const bool bed = c->bed_on && bed_ready(c, s);
   const uint64_t bed_rows = bed ? *s.h_bed_total : 0, bed_bytes = bed_rows * c->bed_last.row_bytes;
   c->bed_last.need_bytes = bed_bytes;
+  // bvcf_enable_ld: the rows again -- the pairs read the same arena --, and the batch's events against theirs
+  c->ld_last = bvcf_ld_info{};
+  const bool ld = c->ld_on && ld_ready(c, s);
+  const uint32_t ld_rb = (c->n_samples + 3u) / 4u;
+  const uint64_t ld_rows = ld ? *s.h_bed_total : 0, ld_events = ld ? *s.h_ld_total : 0;
+  c->ld_last.row_bytes = c->ld_on ? ld_rb : 0u;
+  c->ld_last.window = c->ld_window;
+  c->ld_last.need_events = ld_events;
+  c->ld_last.need_row_bytes = ld_rows * ld_rb;
   // bvcf_enable_trios: likewise the batch's events against the slot's arena
   c->trio_last = bvcf_trio_info{};
   c->trio_last.n_trios = c->n_trios;
   const bool trios = c->trio_on && trios_ready(c, s);
   const uint64_t trio_events = trios ? *s.h_trio_total : 0;
   c->trio_last.need_events = trio_events;
-  if (!k.need.fits || bed_bytes > s.cap_bed || trio_events > s.cap_trio) {
+  if (!k.need.fits || bed_bytes > s.cap_bed || trio_events > s.cap_trio || ld_rows * ld_rb > s.cap_bed || ld_events > s.cap_ld) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
     r->need_alleles = k.need.need_alleles;
@@ -2303,6 +2389,15 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     HIP_TRY(c, hipMemcpyAsync(s.h_trio_counts, s.d_trio_counts, 3ull * c->n_trios * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
   if (!rc && trio_events)
     HIP_TRY(c, hipMemcpyAsync(s.h_trio_ev, s.d_trio_ev, trio_events * sizeof(uint2), hipMemcpyDeviceToHost, s.stream));
+  // (likewise the events and the batch's first and last rows, which the seam pairs with its neighbours')
+  const uint64_t ld_edge = std::min<uint64_t>(c->ld_window, ld_rows);
+  if (!rc && ld_events)
+    HIP_TRY(c, hipMemcpyAsync(s.h_ld_ev, s.d_ld_ev, ld_events * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+  if (!rc && ld_edge) {
+    HIP_TRY(c, hipMemcpyAsync(s.h_ld_edge, s.d_bed, ld_edge * ld_rb, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(c, hipMemcpyAsync(s.h_ld_edge + ld_edge * ld_rb, s.d_bed + (ld_rows - ld_edge) * ld_rb, ld_edge * ld_rb, hipMemcpyDeviceToHost,
+                              s.stream));
+  }
   if (rc) return rc;
   e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) {
@@ -2318,6 +2413,14 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     c->trio_last.counts = s.h_trio_counts;
     c->trio_last.events = reinterpret_cast<const uint32_t *>(s.h_trio_ev.get());
     c->trio_last.n_events = trio_events;
+  }
+  if (ld) {
+    c->ld_last.events = s.h_ld_ev;
+    c->ld_last.n_events = ld_events;
+    c->ld_last.n_rows = ld_rows;
+    c->ld_last.n_edge = (uint32_t)ld_edge;
+    c->ld_last.head_rows = s.h_ld_edge;
+    c->ld_last.tail_rows = s.h_ld_edge + ld_edge * ld_rb;
   }
   add_totals(c, s, k, r);
   return BVCF_OK;
@@ -2442,7 +2545,7 @@ int bvcf_enable_bed_rows(bvcf_ctx *c) {
 
 int bvcf_reserve_bed_rows(bvcf_ctx *c, uint64_t bytes) {
   if (!c) return BVCF_E_ARG;
-  if (!c->bed_asked) {
+  if (!c->bed_asked && !c->ld_asked) {
     c->err = "bvcf_reserve_bed_rows: bvcf_enable_bed_rows was not called on the ctx";
     return BVCF_E_ARG;
   }
@@ -2450,7 +2553,7 @@ int bvcf_reserve_bed_rows(bvcf_ctx *c, uint64_t bytes) {
     c->err = "bvcf_reserve_bed_rows with batches in flight";
     return BVCF_E_BUSY;
   }
-  if (!c->bed_on) return BVCF_OK;
+  if (!c->bed_on && !c->ld_on) return BVCF_OK;
   c->bed_cap = std::max<uint64_t>(c->bed_cap, (bytes + 63) & ~63ull);
   HIP_TRY(c, hipSetDevice(c->device));
   for (auto &s : c->slots)
@@ -2532,6 +2635,85 @@ int bvcf_trio_stats(const bvcf_ctx *c, bvcf_trio_info *out) {
   if (!c || !out || !c->trio_asked) return BVCF_E_ARG;
   *out = c->trio_last;
   return BVCF_OK;
+}
+
+int bvcf_enable_ld(bvcf_ctx *c, uint32_t window, uint32_t t6) {
+  if (!c) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_enable_ld with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (c->ld_asked) {
+    c->err = "bvcf_enable_ld: called twice on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (window < 1 || window > bvcf_ld::kMaxWindow || t6 > bvcf_ld::kT6One) {
+    c->err = "bvcf_enable_ld: window must be 1 to 512 and t6 at most 1000000";
+    return BVCF_E_ARG;
+  }
+  if (c->n_samples >= bvcf_ld::kMaxSamples) {
+    c->err = "bvcf_enable_ld: " + std::to_string(c->n_samples) + " samples, the exact comparison holds below 2^24";
+    return BVCF_E_ARG;
+  }
+  c->ld_asked = true;
+  c->ld_window = window;
+  c->ld_t6 = t6;
+  c->ld_last = bvcf_ld_info{};
+  c->ld_last.window = window;
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  // the rows' arena as bvcf_enable_bed_rows bounds it; an event (32 bytes) per 64 bytes of text to begin with: a line of
+  // text gives a row, and at the usual thresholds a row of a real cohort is in LD with a few of its 50 neighbours at
+  // most.  A threshold of 0, a long window or a file of copies of one line outruns that and grows the arena
+  // (BVCF_E_CAPACITY, bvcf_reserve_ld_events)
+  c->bed_cap = std::max<uint64_t>(c->bed_cap, c->p.max_batch_bytes / 4);
+  c->ld_cap = std::max<uint64_t>(c->ld_cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
+  c->ld_on = true;
+  c->ld_last.row_bytes = (c->n_samples + 3u) / 4u;
+  for (auto &s : c->slots) {
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+    if (const int rc = alloc_ld(c, s)) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_reserve_ld_events(bvcf_ctx *c, uint64_t n) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->ld_asked) {
+    c->err = "bvcf_reserve_ld_events: bvcf_enable_ld was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (c->in_flight) {
+    c->err = "bvcf_reserve_ld_events with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->ld_on) return BVCF_OK;
+  if (n > kLdEventsMax / 8) {
+    c->err = "bvcf_reserve_ld_events: a batch holds fewer than 2^29 events (smaller batches: max_batch_bytes)";
+    return BVCF_E_ARG;
+  }
+  c->ld_cap = std::max<uint64_t>(c->ld_cap, (n + 63) & ~63ull);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)
+    if (const int rc = alloc_ld(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_ld_stats(const bvcf_ctx *c, bvcf_ld_info *out) {
+  if (!c || !out || !c->ld_asked) return BVCF_E_ARG;
+  *out = c->ld_last;
+  return BVCF_OK;
+}
+
+int bvcf_ld_counts(const uint8_t *row_a, const uint8_t *row_b, uint32_t S, uint32_t out[6]) {
+  if (!row_a || !row_b || !out || !S) return -1;
+  bvcf_ld::counts_host(row_a, row_b, S, out);
+  return 0;
+}
+
+int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
+  if (!counts || t6 > bvcf_ld::kT6One || counts[0] >= bvcf_ld::kMaxSamples) return -1;
+  return bvcf_ld::in_ld(counts, t6) ? 1 : 0;
 }
 
 int bvcf_trio_verdict(uint32_t child, uint32_t father, uint32_t mother) {
@@ -2993,6 +3175,55 @@ int bvcf_bench_trio_kernels(bvcf_ctx *c, float ms[4], uint64_t out[2]) {
   out[1] = *s.h_trio_total;
   if (out[1] > s.cap_trio) {
     c->err = "bvcf_bench_trio_kernels: the events outrun the arena (bvcf_reserve_trio_events): " + std::to_string(out[1]);
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_bench_ld_kernels(bvcf_ctx *c, float ms[6], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_ld_kernels with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  Slot &s = c->slots[0];
+  if (!c->ld_on || !ld_ready(c, s)) {
+    c->err = "bvcf_bench_ld_kernels: bvcf_enable_ld was not called on the ctx, or it has no samples";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  // (k_ld_keys reads the lines' first fields: the block of the last bench call, which is still on the device)
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  const BedArgs ba = make_bed_args(c, s);
+  const LdArgs la = make_ld_args(c, s);
+  Event ev[7];
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_row_index(c, a, s.stream, ba);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  launch_bed_rows(c, a, s.stream, ba);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  hipLaunchKernelGGL(k_ld_keys, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba, la);
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  hipLaunchKernelGGL(k_ld_pairs<false>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, s.stream, a, ba, la);
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(1024), 0, s.stream, a, ba, la);
+  HIP_TRY(c, hipEventRecord(ev[5], s.stream));
+  hipLaunchKernelGGL(k_ld_pairs<true>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, s.stream, a, ba, la);
+  HIP_TRY(c, hipEventRecord(ev[6], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(c, hipMemcpyAsync(s.h_ld_total, s.d_ld_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < 6; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  out[0] = *s.h_bed_total;
+  out[1] = *s.h_ld_total;
+  if (out[0] * ((c->n_samples + 3u) / 4u) > s.cap_bed) {
+    c->err = "bvcf_bench_ld_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[0]) + " rows";
+    return BVCF_E_CAPACITY;
+  }
+  if (out[1] > s.cap_ld) {
+    c->err = "bvcf_bench_ld_kernels: the events outrun the arena (bvcf_reserve_ld_events): " + std::to_string(out[1]);
     return BVCF_E_CAPACITY;
   }
   return BVCF_OK;

@@ -63,6 +63,9 @@
 //   (bvcf_enable_trios, behind the same row index -- built once when either is on: k_trio_count / k_trio_scan / k_trio_fill
 //    give, per trio, the rows that are informative, Mendelian errors and de novo calls, and the batch's events in
 //    (row, trio) order -- bvcf_mendel.hip.h)
+//   (bvcf_enable_ld, behind the same row index and on the .bed arena, made once: k_ld_keys, then k_ld_pairs<false> /
+//    k_ld_scan / k_ld_pairs<true> give the pairs of rows at most `window` apart whose r² reaches the threshold, as
+//    events in (b, a) order -- bvcf_ld.hip.h)
 //   (bvcf_params.want_name_lists, after k_finish: k_name_len / k_name_scan / k_name_write render the het / hom / missing
 //    sample-name lists of every output allele as text -- main.go:612-656 -- see bvcf_names.hip.h)
 //
@@ -111,5 +114,6 @@
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
+#include "bvcf_ld.hip.h"
 #include "bvcf_inflate.hip.h"
 #include "bvcf_deflate.hip.h"

@@ -400,6 +400,11 @@ void Driver::device_main(DevWorker *W) {
         bvcf_trio_info ti;
         if (bvcf_trio_stats(W->ctx, &ti) == BVCF_OK) trio_need = ti.need_events;
       }
+      uint64_t ld_need = 0, ld_rows_need = 0;  // (--ld / --ldPrune: likewise the events, and the rows the pairs read)
+      if (R_.ld_on) {
+        bvcf_ld_info li;
+        if (bvcf_ld_stats(W->ctx, &li) == BVCF_OK) ld_need = li.need_events, ld_rows_need = li.need_row_bytes;
+      }
       // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
       const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
       if (ss) {
@@ -442,6 +447,8 @@ void Driver::device_main(DevWorker *W) {
                        res.need_cmap_bytes + res.need_cmap_bytes / 4 + 4096);
       if (r == BVCF_OK && bed_need) r = bvcf_reserve_bed_rows(W->ctx, bed_need + bed_need / 4 + 4096);
       if (r == BVCF_OK && trio_need) r = bvcf_reserve_trio_events(W->ctx, trio_need + trio_need / 4 + 1024);
+      if (r == BVCF_OK && ld_need) r = bvcf_reserve_ld_events(W->ctx, ld_need + ld_need / 4 + 1024);
+      if (r == BVCF_OK && ld_rows_need) r = bvcf_reserve_bed_rows(W->ctx, ld_rows_need + ld_rows_need / 4 + 4096);
       for (size_t k = 0; k < in_flight.size() && r == BVCF_OK; k++) r = submit(in_flight[k]);
       if (r == BVCF_OK) {
         r = bvcf_collect(W->ctx, &res);
@@ -470,6 +477,10 @@ void Driver::device_main(DevWorker *W) {
     }
     if (R_.mendel_on && bvcf_trio_stats(W->ctx, &j.trio) != BVCF_OK) {  // --mendel / --mendelErrors: likewise
       fail(std::string("bvcf_trio_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      return;
+    }
+    if (R_.ld_on && bvcf_ld_stats(W->ctx, &j.ld) != BVCF_OK) {  // --ld / --ldPrune: likewise
+      fail(std::string("bvcf_ld_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
       return;
     }
     j.job = n_jobs;
@@ -568,11 +579,12 @@ void Driver::formatter_main(DevWorker *W) {
         for (auto &q : *it.parts) q.clear();
       const bool plink = R_.bed_fd >= 0;
       const bool mendel = R_.mendel_on && !R_.trios.empty();  // (the tables are summed in input order too: one thread)
-      if ((R_.arrow && j.res.dosage) || plink || mendel) {
+      const bool ld = R_.ld_on;  // (the seam is a state machine over the batches in input order: one thread)
+      if ((R_.arrow && j.res.dosage) || plink || mendel || ld) {
         // the dosage rows go into the file in input order (main.go:576-584): the sink runs this when it is the block's
         // turn; the result slot and the text stay on loan until then -- and so do the batch's .bed rows and .bim lines
         auto keep = std::make_shared<FmtJob>(std::move(j));
-        it.in_order = [this, keep, text, release, plink, mendel]() {
+        it.in_order = [this, keep, text, release, plink, mendel, ld]() {
           if (!dosage_failed_.load() && append_dosage(R_, &keep->res, text)) {
             dosage_failed_.store(true);
             fail("dosage matrix: write failed", BVCF_E_FATAL);
@@ -584,6 +596,10 @@ void Driver::formatter_main(DevWorker *W) {
           if (mendel && !mendel_failed_.load() && append_mendel(R_, &keep->res, text, keep->trio)) {
             mendel_failed_.store(true);
             fail("mendel: the device's events do not match the batch's rows", BVCF_E_FATAL);
+          }
+          if (ld && !ld_failed_.load() && append_ld(R_, &keep->res, text, keep->ld)) {
+            ld_failed_.store(true);
+            fail("ld: the device's events do not match the batch's rows", BVCF_E_FATAL);
           }
           release();
         };
@@ -619,6 +635,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return BVCF_E_IO;
     }
     if (const int rc = open_mendel(R_, &msg)) {  // --mendel / --mendelErrors: likewise
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
+    if (const int rc = open_ld(R_, &msg)) {  // --ld / --ldPrune: likewise
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
@@ -845,6 +865,16 @@ int Driver::run(uint64_t *n_lines_in) {
       if (rc_ != BVCF_OK) {
         close_mendel(R_);
       } else if (write_mendel(R_, &msg)) {
+        fail(msg, BVCF_E_IO);
+        write_all(fd_err_, log_.data(), log_.size());
+      }
+    }
+    if (R_.ld_fd >= 0 || R_.ld_in_fd >= 0 || R_.ld_out_fd >= 0) {
+      // --ld / --ldPrune: the seam saw the batches the sink was handed, in input order
+      std::string msg;
+      if (rc_ != BVCF_OK) {
+        close_ld(R_);
+      } else if (write_ld(R_, &msg)) {
         fail(msg, BVCF_E_IO);
         write_all(fd_err_, log_.data(), log_.size());
       }

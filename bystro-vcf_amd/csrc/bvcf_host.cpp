@@ -46,6 +46,15 @@ void bvcf_config_trios_defaults(bvcf_config_trios *c) {
   c->more.base.reserved[1] = BVCF_CONFIG_MORE_TRIOS;
 }
 
+void bvcf_config_ld_defaults(bvcf_config_ld *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_trios_defaults(&c->trios);
+  c->trios.more.base.reserved[1] = BVCF_CONFIG_MORE_LD;
+  c->ld_window = 50;
+  c->ld_t6 = 200000;
+  c->ld_t6_set = 1;
+}
+
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
   std::string h;
   for (int i = 0; i < 15; i++) {
@@ -117,6 +126,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
   if (rc == BVCF_OK) rc = open_plink(R, &msg);
   if (rc == BVCF_OK) rc = open_mendel(R, &msg);
+  if (rc == BVCF_OK) rc = open_ld(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -182,6 +192,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
           break;
         }
       }
+      if (R.ld_on) {  // --ld / --ldPrune: the batch's events and edge rows
+        bvcf_ld_info li;
+        if (bvcf_ld_stats(R.ctx, &li) != BVCF_OK || append_ld(R, &res, vcf + pos, li)) {
+          l.append("ld: the device's events do not match the batch's rows\n");
+          rc = BVCF_E_FATAL;
+          break;
+        }
+      }
       pos += nb;
     }
   }
@@ -197,6 +215,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
     if (rc != BVCF_OK) {
       close_mendel(R);
     } else if (write_mendel(R, &msg)) {
+      l.append(msg + "\n");
+      rc = BVCF_E_IO;
+    }
+  }
+  if (R.ld_fd >= 0 || R.ld_in_fd >= 0 || R.ld_out_fd >= 0) {  // --ld / --ldPrune: after a successful run only
+    if (rc != BVCF_OK) {
+      close_ld(R);
+    } else if (write_ld(R, &msg)) {
       l.append(msg + "\n");
       rc = BVCF_E_IO;
     }

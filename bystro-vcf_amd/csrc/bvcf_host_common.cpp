@@ -854,6 +854,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.ld_on) {  // --ld / --ldPrune: the pairs of every ctx of the run
+    rc = bvcf_enable_ld(*ctx, R.ld_window, R.ld_t6);
+    if (rc) {
+      *msg = std::string("bvcf_enable_ld: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (const bvcf_config_more *m = rc == BVCF_OK ? gate_config(R.cfg) : nullptr) {  // the site gate of every ctx of the run
     rc = bvcf_set_site_gate(*ctx, &m->site_gate);
     if (rc) {
@@ -1177,6 +1185,98 @@ int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c) {
   return bvcf_reserve_trio_events(ctx, t.need_events + t.need_events / 4 + 1024);
 }
 
+int open_ld(Run &R, std::string *msg) {
+  R.ld_on = wants_ld(R.cfg);
+  if (!R.ld_on) return BVCF_OK;
+  const bvcf_config_ld *l = ld_config(R.cfg);
+  R.ld_window = l->ld_window ? l->ld_window : 50u;
+  R.ld_t6 = l->ld_t6_set ? l->ld_t6 : 200000u;
+  if (R.ld_window > 512u || R.ld_t6 > 1000000u) {
+    *msg = "ld: the window must be 1 to 512 rows and the threshold 0 to 1";
+    return BVCF_E_ARG;
+  }
+  const std::string prefix = (l->ld_prune_prefix && *l->ld_prune_prefix) ? l->ld_prune_prefix : "";
+  struct {
+    std::string path;
+    int *fd;
+  } files[3] = {{(l->ld_path && *l->ld_path) ? l->ld_path : "", &R.ld_fd},
+                {prefix.empty() ? "" : prefix + ".prune.in", &R.ld_in_fd},
+                {prefix.empty() ? "" : prefix + ".prune.out", &R.ld_out_fd}};
+  for (auto &f : files) {
+    if (f.path.empty()) continue;
+    *f.fd = open(f.path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.fd < 0) {
+      *msg = "open " + f.path + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  return BVCF_OK;
+}
+
+// the batch into the seam: the rows bvcf_ld_stats numbers are the rows this loop visits, in this order, as for append_plink
+int append_ld(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_ld_info &li) {
+  if (!R.ld_on || !r->n_samples) return BVCF_OK;
+  if (!R.ld_seam && !(R.ld_seam = bvcf_ld_seam_create(r->n_samples, R.ld_window, R.ld_t6))) return BVCF_E_FATAL;
+  std::string loci;
+  std::vector<uint64_t> off;
+  size_t at[5];
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    const char *row = row_of(r, block, i, L);
+    for (uint32_t k = 0; k < L.n_rec; k++) {
+      const bvcf_allele &A = r->alleles[k ? L.rec_first + k - 1 : i];
+      if (A.ac == 0) continue;  // main.go:558-560
+      off.push_back(loci.size());
+      append_locus(loci, L, A, row, '\t', at);
+    }
+  }
+  const uint64_t n_rows = off.size();
+  off.push_back(loci.size());
+  if (n_rows != li.n_rows) return BVCF_E_FATAL;
+  return bvcf_ld_seam_push(R.ld_seam, n_rows, li.n_edge, li.head_rows, li.tail_rows, li.events, li.n_events, loci.data(), off.data())
+             ? BVCF_E_FATAL
+             : BVCF_OK;
+}
+
+void close_ld(Run &R) {
+  for (int *fd : {&R.ld_fd, &R.ld_in_fd, &R.ld_out_fd}) {
+    if (*fd >= 0) close(*fd);
+    *fd = -1;
+  }
+}
+
+int write_ld(Run &R, std::string *msg) {
+  static const char kHead[] = "chrom\tpos1\tref1\talt1\tpos2\tref2\talt2\tn\tr2\tdir\n";
+  bool bad = false;
+  int saved = 0;
+  int *fds[3] = {&R.ld_fd, &R.ld_in_fd, &R.ld_out_fd};
+  for (int which = 0; which < 3; which++) {
+    if (*fds[which] < 0) continue;
+    const char *text = nullptr;
+    size_t len = 0;
+    if (R.ld_seam) bvcf_ld_seam_read(R.ld_seam, which, &text, &len);
+    if (!bad && which == 0 && write_all(*fds[which], kHead, sizeof kHead - 1)) bad = true, saved = errno;
+    if (!bad && len && write_all(*fds[which], text, len)) bad = true, saved = errno;
+    if (close(*fds[which]) && !bad) bad = true, saved = errno;
+    *fds[which] = -1;
+  }
+  if (bad) {
+    *msg = std::string("ld: write failed: ") + strerror(saved);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+// --ld / --ldPrune, after a BVCF_E_CAPACITY: the events arena and the rows' arena grown to what the batch reported
+int reserve_ld_need(bvcf_ctx *ctx, const bvcf_config *c) {
+  if (!wants_ld(c)) return BVCF_OK;
+  bvcf_ld_info t;
+  if (bvcf_ld_stats(ctx, &t) != BVCF_OK) return BVCF_OK;
+  const int rc = bvcf_reserve_ld_events(ctx, t.need_events + t.need_events / 4 + 1024);
+  return rc ? rc : bvcf_reserve_bed_rows(ctx, t.need_row_bytes + t.need_row_bytes / 4 + 4096);
+}
+
 int close_dosage(Run &R) {
   if (!R.arrow) return BVCF_OK;
   const int rc = bvcf_arrow_close(R.arrow);
@@ -1210,6 +1310,7 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
                       res->need_cmap_bytes + res->need_cmap_bytes / 4 + 4096);
     if (rc == BVCF_OK) rc = reserve_bed_need(R.ctx, R.cfg);
     if (rc == BVCF_OK) rc = reserve_trio_need(R.ctx, R.cfg);
+    if (rc == BVCF_OK) rc = reserve_ld_need(R.ctx, R.cfg);
     if (rc) {
       *msg = std::string("bvcf_reserve: ") + bvcf_last_error(R.ctx);
       return rc;

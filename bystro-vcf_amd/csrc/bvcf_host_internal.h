@@ -5,6 +5,7 @@
 //
 // Nothing here computes what the kernels compute: rows are assembled from bvcf_result only.
 #include "../../include/bvcf.h"
+#include "../../include/bvcf_plan.h"
 #include "bvcf_input.h"
 #include "bvcf_bgzf.h"
 
@@ -242,9 +243,16 @@ struct Run {
   std::vector<uint32_t> trios;
   std::vector<uint64_t> trio_counts;
   std::string mendel_events;
+  // --ld / --ldPrune: the three files opened by open_ld before any device work; append_ld hands a batch's events, edge
+  // rows and loci to the seam (bvcf_ld_seam_* of include/bvcf_plan.h) in input order; write_ld writes them at the end
+  bool ld_on = false;
+  uint32_t ld_window = 0, ld_t6 = 0;
+  int ld_fd = -1, ld_in_fd = -1, ld_out_fd = -1;
+  bvcf_ld_seam *ld_seam = nullptr;
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd})
+    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd})
       if (fd >= 0) close(fd);
+    bvcf_ld_seam_destroy(ld_seam);
   }
 };
 
@@ -278,6 +286,15 @@ int append_mendel(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf
 int write_mendel(Run &R, std::string *msg);
 void close_mendel(Run &R);
 int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c);
+// --ld / --ldPrune: the files opened (truncated) and the window and threshold checked -- BVCF_E_IO / BVCF_E_ARG with one
+// message in *msg; the events, edge rows and loci of one collected batch (li = what bvcf_ld_stats gave for it) pushed into
+// the run's seam -- BVCF_E_FATAL when they contradict the batch's rows; the files written and closed at the end of a
+// successful run; closed without writing otherwise
+int open_ld(Run &R, std::string *msg);
+int append_ld(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_ld_info &li);
+int write_ld(Run &R, std::string *msg);
+void close_ld(Run &R);
+int reserve_ld_need(bvcf_ctx *ctx, const bvcf_config *c);
 int close_dosage(Run &R);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
 // --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
@@ -324,6 +341,15 @@ inline const bvcf_config_trios *trios_config(const bvcf_config *c) {
 inline bool wants_mendel(const bvcf_config *c) {
   const bvcf_config_trios *t = trios_config(c);
   return t && ((t->mendel_path && *t->mendel_path) || (t->mendel_errors_path && *t->mendel_errors_path));
+}
+// --ld / --ldPrune / --ldWindow / --ldR2: the config as a bvcf_config_ld (the fifth marker), or NULL
+inline const bvcf_config_ld *ld_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_LD) ? reinterpret_cast<const bvcf_config_ld *>(c) : nullptr;
+}
+// true when the run counts pairs (every ctx of the run then gets bvcf_enable_ld): one of the two outputs is asked for
+inline bool wants_ld(const bvcf_config *c) {
+  const bvcf_config_ld *l = ld_config(c);
+  return l && ((l->ld_path && *l->ld_path) || (l->ld_prune_prefix && *l->ld_prune_prefix));
 }
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);

@@ -3,8 +3,11 @@
 // these through the C entries of include/bvcf_plan.h.  Counterpart of the reference's single producer cutting 64-line
 // work items (main.go:345-380).
 #include "bvcf_pipeline.h"
+#include "bvcf_ld_counts.h"
 
+#include <algorithm>
 #include <array>
+#include <deque>
 #include <unordered_map>
 
 namespace bvcf_host {
@@ -345,5 +348,156 @@ int bvcf_parse_fam(const char *text, size_t len, const char *const *names, const
   return BVCF_FAM_OK;
 }
 
+// --ldR2: "0", "1", "0.d{1,6}" or "1.0{1,6}" -> the digits as millionths
+int bvcf_parse_ld_r2(const char *text, uint32_t *t6) {
+  if (!text || !t6) return -1;
+  const size_t n = strlen(text);
+  if (n < 1 || (text[0] != '0' && text[0] != '1')) return -1;
+  uint32_t v = text[0] == '1' ? bvcf_ld::kT6One : 0u;
+  if (n > 1) {
+    if (text[1] != '.' || n < 3 || n > 8) return -1;
+    uint32_t frac = 0, scale = 100000u;
+    for (size_t i = 2; i < n; i++, scale /= 10u) {
+      if (text[i] < '0' || text[i] > '9') return -1;
+      frac += (uint32_t)(text[i] - '0') * scale;
+    }
+    if (v && frac) return -1;
+    v += frac;
+  }
+  *t6 = v;
+  return 0;
+}
+
+}  // extern "C"
+
+// The seam of --ld / --ldPrune (include/bvcf_plan.h).  One thread, output order.
+struct bvcf_ld_seam {
+  struct Row {
+    std::string bed;    // the row in .bed code
+    std::string locus;  // "chrom\tpos\tref\talt"
+    size_t chrom_len;
+    bool kept;
+  };
+  uint32_t S, rb, window, t6;
+  uint64_t n_rows = 0, n_pairs = 0;
+  std::deque<Row> carry;        // the run's last rows, the newest at the back: `window` of them at most
+  std::vector<uint8_t> kept;    // the kept flags of the batch being walked
+  std::string table, in, out;
+
+  static bool same_chrom(const char *a, size_t na, const char *b, size_t nb) { return na == nb && !memcmp(a, b, na); }
+
+  void line(const char *la, const char *lb, size_t chrom_len, const uint32_t k[6]) {
+    // la, lb: the loci "chrom\tpos\tref\talt" of the earlier and the later row
+    table.append(la, strlen(la));
+    table.push_back('\t');
+    table.append(lb + chrom_len + 1);
+    table.push_back('\t');
+    append_ll(table, k[0]);
+    table.push_back('\t');
+    const bvcf_ld::Moments m = bvcf_ld::moments(k);
+    const double r2 = ((double)m.c * (double)m.c) / ((double)m.va * (double)m.vb);
+    if (r2 == 0.0)
+      table.push_back('0');
+    else
+      append_g3(table, r2);
+    table.append(m.c > 0 ? "\t+\n" : m.c < 0 ? "\t-\n" : "\t0\n");
+  }
+};
+
+extern "C" {
+
+bvcf_ld_seam *bvcf_ld_seam_create(uint32_t n_samples, uint32_t window, uint32_t t6) {
+  if (window < 1 || window > bvcf_ld::kMaxWindow || t6 > bvcf_ld::kT6One || n_samples >= bvcf_ld::kMaxSamples) return nullptr;
+  bvcf_ld_seam *s = new bvcf_ld_seam();
+  s->S = n_samples;
+  s->rb = (n_samples + 3u) / 4u;
+  s->window = window;
+  s->t6 = t6;
+  return s;
+}
+
+void bvcf_ld_seam_destroy(bvcf_ld_seam *s) { delete s; }
+uint64_t bvcf_ld_seam_rows(const bvcf_ld_seam *s) { return s ? s->n_rows : 0; }
+uint64_t bvcf_ld_seam_pairs(const bvcf_ld_seam *s) { return s ? s->n_pairs : 0; }
+
+int bvcf_ld_seam_read(const bvcf_ld_seam *s, int which, const char **text, size_t *len) {
+  if (!s || !text || !len || which < 0 || which > 2) return -1;
+  const std::string &o = which == 0 ? s->table : which == 1 ? s->in : s->out;
+  *text = o.data();
+  *len = o.size();
+  return 0;
+}
+
+int bvcf_ld_seam_push(bvcf_ld_seam *s, uint64_t n_rows, uint32_t n_edge, const uint8_t *head, const uint8_t *tail,
+                      const uint32_t *events, uint64_t n_events, const char *loci, const uint64_t *loci_off) {
+  if (!s || (n_events && !events)) return -1;
+  if (!n_rows) return n_events ? -1 : 0;
+  if (!loci || !loci_off || n_edge != std::min<uint64_t>(s->window, n_rows) || (s->S && (!head || !tail))) return -1;
+  const uint32_t N = s->window, rb = s->rb;
+  // a locus as a C string with its chrom's length
+  std::vector<size_t> chrom_len(n_rows);
+  std::string text;  // the batch's loci, each ended by a NUL
+  std::vector<size_t> at(n_rows);
+  for (uint64_t i = 0; i < n_rows; i++) {
+    const char *p = loci + loci_off[i];
+    const size_t n = (size_t)(loci_off[i + 1] - loci_off[i]);
+    const char *tab = (const char *)memchr(p, '\t', n);
+    if (!tab || std::count(p, p + n, '\t') != 3) return -1;
+    chrom_len[i] = (size_t)(tab - p);
+    at[i] = text.size();
+    text.append(p, n);
+    text.push_back('\0');
+  }
+  s->kept.assign(n_rows, 1);
+  const size_t n_carry = s->carry.size();
+  uint64_t e = 0;
+  uint32_t k[6];
+  for (uint64_t b = 0; b < n_rows; b++) {
+    const char *lb = text.data() + at[b];
+    bool pruned = false;
+    // the carry's partners first: row j of the carry is n_carry - j + b rows in front of b
+    if (b < N && s->S) {
+      for (size_t j = 0; j < n_carry; j++) {
+        if (n_carry - j + b > N) continue;
+        const bvcf_ld_seam::Row &A = s->carry[j];
+        if (!bvcf_ld_seam::same_chrom(A.locus.data(), A.chrom_len, lb, chrom_len[b])) continue;
+        bvcf_ld::counts_host((const uint8_t *)A.bed.data(), head + b * rb, s->S, k);
+        if (!bvcf_ld::in_ld(k, s->t6)) continue;
+        s->line(A.locus.c_str(), lb, chrom_len[b], k);
+        s->n_pairs++;
+        pruned |= A.kept;
+      }
+    }
+    // then the device's: by b, then by a ascending = d descending
+    uint32_t last_d = 0xFFFFFFFFu;
+    for (; e < n_events && events[8 * e] == b; e++) {
+      const uint32_t d = events[8 * e + 1];
+      if (d < 1 || d > b || d > N || d >= last_d) return -1;
+      last_d = d;
+      const uint64_t a = b - d;
+      s->line(text.data() + at[a], lb, chrom_len[b], events + 8 * e + 2);
+      s->n_pairs++;
+      pruned |= s->kept[a] != 0;
+    }
+    if (e < n_events && events[8 * e] < b) return -1;
+    s->kept[b] = !pruned;
+    std::string &list = pruned ? s->out : s->in;
+    for (const char *p = lb; *p; p++) list.push_back(*p == '\t' ? ':' : *p);
+    list.push_back('\n');
+  }
+  if (e != n_events) return -1;
+  // the batch's tail is the new carry, behind what is left of the old one
+  for (uint64_t i = n_rows - n_edge; i < n_rows; i++) {
+    bvcf_ld_seam::Row r;
+    if (s->S) r.bed.assign((const char *)tail + (i - (n_rows - n_edge)) * rb, rb);
+    r.locus.assign(text.data() + at[i]);
+    r.chrom_len = chrom_len[i];
+    r.kept = s->kept[i] != 0;
+    s->carry.push_back(std::move(r));
+  }
+  while (s->carry.size() > N) s->carry.pop_front();
+  s->n_rows += n_rows;
+  return 0;
+}
 
 }  // extern "C"

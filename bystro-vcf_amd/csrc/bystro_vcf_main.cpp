@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bvcf.h"
+#include "../../include/bvcf_plan.h"
 
 namespace {
 
@@ -48,6 +49,10 @@ struct Cli {
   // extension: --mendel PATH / --mendelErrors PATH, per trio of --fam's pedigree the rows that are Mendelian errors and
   // de novo calls, and the list of them (counted on the device); --fam alone stays accepted and ignored
   std::string mendel, mendel_errors;
+  // extension: --ld PATH / --ldPrune PREFIX, the pairs of rows at most --ldWindow rows apart whose r² reaches --ldR2, and
+  // the greedy prune lists made of them (counted on the device); --ldWindow / --ldR2 alone are accepted and do nothing
+  std::string ld, ld_prune;
+  uint32_t ld_window = 50, ld_t6 = 200000;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -142,7 +147,8 @@ int parse(int argc, char **argv, Cli &c) {
     if (name == "devices" || name == "device" || name == "batchMB" || name == "compressOutput" || name == "sampleStats" ||
         name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
         name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
-        name == "plinkOutput" || name == "mendel" || name == "mendelErrors") {
+        name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
+        name == "ldR2") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -172,6 +178,22 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         (name == "mendel" ? c.mendel : c.mendel_errors) = val;
+      } else if (name == "ld" || name == "ldPrune") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the %s to write\n", name.c_str(), name == "ld" ? "path of the file" : "prefix of the two lists");
+          return 2;
+        }
+        (name == "ld" ? c.ld : c.ld_prune) = val;
+      } else if (name == "ldWindow") {
+        if (!parse_threshold(val, &c.ld_window) || c.ld_window < 1 || c.ld_window > 512) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 1 to 512\n", val.c_str(), name.c_str());
+          return 2;
+        }
+      } else if (name == "ldR2") {
+        if (bvcf_parse_ld_r2(val.c_str(), &c.ld_t6)) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want a decimal from 0 to 1 with at most six places\n", val.c_str(), name.c_str());
+          return 2;
+        }
       } else if (name == "minMac") {
         if (!parse_threshold(val, &c.min_mac)) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
@@ -242,7 +264,7 @@ int main(int argc, char **argv) {
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
   // conversion-only pass; --mendel / --mendelErrors alone: QC-only again)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
-      c.mendel.empty() && c.mendel_errors.empty()) {
+      c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -256,8 +278,10 @@ int main(int argc, char **argv) {
 
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
-  bvcf_config_trios trios;
-  bvcf_config_trios_defaults(&trios);
+  // (... and behind those the --ld paths, window and threshold)
+  bvcf_config_ld ldc;
+  bvcf_config_ld_defaults(&ldc);
+  bvcf_config_trios &trios = ldc.trios;
   bvcf_config_more &more = trios.more;
   bvcf_config &cfg = more.base;
   cfg.empty_field = c.empty.c_str();
@@ -318,6 +342,11 @@ int main(int argc, char **argv) {
   trios.fam_path = c.fam.c_str();
   trios.mendel_path = c.mendel.c_str();
   trios.mendel_errors_path = c.mendel_errors.c_str();
+  ldc.ld_path = c.ld.c_str();
+  ldc.ld_prune_prefix = c.ld_prune.c_str();
+  ldc.ld_window = c.ld_window;
+  ldc.ld_t6 = c.ld_t6;
+  ldc.ld_t6_set = 1;
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

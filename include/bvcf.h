@@ -478,6 +478,49 @@ int bvcf_reserve_trio_events(bvcf_ctx *ctx, uint64_t n);
 /* the counts and events of the batch bvcf_collect returned last on ctx; the pointers are valid as long as those of the
  * bvcf_result collected with them.  BVCF_E_ARG on a ctx without bvcf_enable_trios */
 int bvcf_trio_stats(const bvcf_ctx *ctx, bvcf_trio_info *out);
+/* Windowed pairwise r² between the same rows, counted on the device from their .bed form (which the ctx then packs even
+ * without bvcf_enable_bed_rows, and packs once with it; the class maps are made without being copied to the host).  Rows
+ * are numbered in output order.  A pair of rows a < b is EXAMINED when b - a <= window and the rows' TSV chrom columns
+ * are byte-equal (after the reference's "chr" rule, main.go:570-574: raw "1" and "chr1" are one chromosome).  A sample's
+ * genotype in a row is 0 (no list names it), 1 (het), 2 (hom; a haploid call counts as hom) or missing (a masked call; a
+ * record without a usable map is all missing).  Over the samples called in both rows:
+ *   n, sa = sum g_a, sb = sum g_b, saa = sum g_a^2, sbb = sum g_b^2, sab = sum g_a g_b
+ *   c = n sab - sa sb, va = n saa - sa^2, vb = n sbb - sb^2
+ * and the pair is IN LD iff va > 0, vb > 0 and c^2 * 10^6 >= t6 * va * vb, compared exactly in 128-bit integers (nothing
+ * is divided, no floating point decides anything; with S < 2^24 samples c^2 * 10^6 < 2^120).  So the set of pairs is a
+ * property of the data.  A batch reports the pairs in LD BOTH of whose rows are its own, as events of eight uint32
+ * {b, d, n, sa, sb, saa, sbb, sab} -- b the later row's number within the batch, the earlier row a = b - d -- ordered by b,
+ * then by a ascending; no atomic places an event.  The pairs across a batch boundary are the caller's: the batch's first
+ * and last min(window, n_rows) rows come back in .bed code for that (bvcf_ld_seam_* of include/bvcf_plan.h pairs them with
+ * the shared functions bvcf_ld_counts / bvcf_ld_in_ld and merges everything into run order).
+ * Call bvcf_enable_ld once, before the first submit: BVCF_E_ARG for a window outside 1 .. 512, t6 > 10^6, 2^24 samples or
+ * more, or a second call; a no-op returning BVCF_OK on a ctx without sample columns.  bvcf_params and the ABI version do
+ * not change with it.
+ * The events go into an arena of the slot with a bound of its own, in events of 32 bytes: max_batch_bytes / 64 to begin
+ * with (at least 1 024).  A line of text gives a row, a cohort's line is thousands of bytes, and at the usual
+ * thresholds (0.2, 0.5) a row of a real cohort is in LD with a few of its 50 neighbours at most; so one event per 64
+ * bytes of text is room for tens of events per row.  A threshold of 0, a window of hundreds over few samples or a file
+ * that repeats one line outruns it and is handled like every other capacity: the batch comes back BVCF_E_CAPACITY,
+ * bvcf_ld_stats reports need_events (and need_row_bytes, for bvcf_reserve_bed_rows: the rows' arena is the fileset's),
+ * bvcf_reserve_ld_events(ctx, n) -- with no batch in flight -- grows the arena, and the batch is submitted again. */
+typedef struct {
+  const uint32_t *events;   /* [n_events][8] */
+  uint64_t n_events;
+  uint64_t need_events;     /* what the batch's events take (also after BVCF_E_CAPACITY, when the pointers are NULL) */
+  uint64_t need_row_bytes;  /* what the batch's rows take in the arena bvcf_reserve_bed_rows grows (likewise) */
+  const uint8_t *head_rows; /* the batch's first n_edge rows in .bed code, row_bytes apart */
+  const uint8_t *tail_rows; /* its last n_edge rows */
+  uint64_t n_rows;          /* rows of the batch */
+  uint32_t n_edge;          /* min(window, n_rows) */
+  uint32_t row_bytes;       /* ceil(S / 4) */
+  uint32_t window;
+  uint32_t reserved;
+} bvcf_ld_info;
+int bvcf_enable_ld(bvcf_ctx *ctx, uint32_t window, uint32_t t6);
+int bvcf_reserve_ld_events(bvcf_ctx *ctx, uint64_t n);
+/* the events and edge rows of the batch bvcf_collect returned last on ctx; the pointers are valid as long as those of the
+ * bvcf_result collected with them.  BVCF_E_ARG on a ctx without bvcf_enable_ld */
+int bvcf_ld_stats(const bvcf_ctx *ctx, bvcf_ld_info *out);
 
 /* The per-site QC gate (--minMaf / --maxMaf / --minMac / --maxMissing / --hwe).  size = sizeof(bvcf_site_gate).  A criterion
  * at its neutral value is off; with all of them neutral the ctx allocates and launches nothing for the gate.
@@ -664,6 +707,29 @@ typedef struct {
 } bvcf_config_trios;
 /* the whole struct: bvcf_config_plink_defaults, more.base.reserved[1] = BVCF_CONFIG_MORE_TRIOS, no paths */
 void bvcf_config_trios_defaults(bvcf_config_trios *c);
+/* Likewise what came after bvcf_config_trios: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_LD.  bvcf_config_ld_defaults sets that; the four older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_LD 4
+typedef struct {
+  bvcf_config_trios trios;
+  /* --ld: "chrom pos1 ref1 alt1 pos2 ref2 alt2 n r2 dir", then a tab-separated line per pair of rows in LD (bvcf_enable_ld)
+   * ordered by the later row b, then by the earlier row a: the rows' TSV columns byte for byte, n, r2 =
+   * ((double)c * (double)c) / ((double)va * (double)vb) in that order of IEEE double operations, printed as the TSV's ratios are
+   * (%.3G; zero prints 0), dir = + / - / 0 by the sign of c.  Opened before any device work, written at the end of a
+   * successful run; the bytes do not depend on devices, batch size or input kind.  NULL or "" = no table */
+  const char *ld_path;
+  /* --ldPrune: PREFIX.prune.in / PREFIX.prune.out, the rows' locus strings "chrom:pos:ref:alt" (the second .bim column)
+   * one per line in TSV order.  Walking the rows in that order, row b is pruned iff some pair (a, b) in LD has an a that
+   * was kept: greedy in file order, NOT PLINK's --indep-pairwise set.  Every row is in exactly one file.  Likewise opened
+   * first and written at the end.  NULL or "" = no lists */
+  const char *ld_prune_prefix;
+  uint32_t ld_window; /* --ldWindow: 1 .. 512; 0 = the default, 50 */
+  uint32_t ld_t6;     /* --ldR2 * 10^6, 0 .. 10^6, read when ld_t6_set is not 0; otherwise the default, 200 000 */
+  uint32_t ld_t6_set;
+  uint32_t reserved;
+} bvcf_config_ld;
+/* the whole struct: bvcf_config_trios_defaults, base.reserved[1] = BVCF_CONFIG_MORE_LD, no paths, window 50, t6 200 000 */
+void bvcf_config_ld_defaults(bvcf_config_ld *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

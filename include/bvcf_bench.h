@@ -72,6 +72,12 @@ int bvcf_bench_bed_kernels(bvcf_ctx *ctx, float ms[2], uint64_t out[2]);
  * out[1] = the events.  BVCF_E_ARG on a ctx without trios, BVCF_E_CAPACITY when the events outrun the arena */
 int bvcf_bench_trio_kernels(bvcf_ctx *ctx, float ms[4], uint64_t out[2]);
 
+/* bvcf_enable_ld: the LD kernels over the records, class maps and text the first slot's last bench chain left, with HIP
+ * events around them: ms = {the row index, k_bed_rows, k_ld_keys, k_ld_pairs counting, k_ld_scan, k_ld_pairs filling};
+ * out[0] = the rows, out[1] = the events.  BVCF_E_ARG on a ctx without bvcf_enable_ld, BVCF_E_CAPACITY when the rows or
+ * the events outrun their arena */
+int bvcf_bench_ld_kernels(bvcf_ctx *ctx, float ms[6], uint64_t out[2]);
+
 #ifdef __cplusplus
 }
 #endif

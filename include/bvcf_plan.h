@@ -157,6 +157,36 @@ int bvcf_parse_fam(const char *text, size_t len, const char *const *names, const
                    uint32_t *trios_out, size_t cap, size_t *n_trios, uint64_t *bad_line, const char **bad_iid,
                    size_t *bad_iid_len);
 
+/* The pair code behind bvcf_enable_ld -- csrc/bvcf_ld_counts.h -- run on the host: the same functions the kernels run.
+ * bvcf_ld_counts: two rows in .bed code (ceil(S / 4) bytes each, pad bits ignored) -> out = {n, sa, sb, saa, sbb, sab};
+ * -1 for bad arguments.  bvcf_ld_in_ld: 1 when the counts are in LD at t6, 0 when not, -1 for t6 > 10^6 or n >= 2^24.
+ * bvcf_parse_ld_r2: the text of --ldR2 ("0", "1", "0.d{1,6}", "1.0{1,6}": no sign, no exponent, no spaces) -> *t6 = its
+ * value times 10^6 from the digits; 0, or -1 for any other text. */
+int bvcf_ld_counts(const uint8_t *row_a, const uint8_t *row_b, uint32_t S, uint32_t out[6]);
+int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6);
+int bvcf_parse_ld_r2(const char *text, uint32_t *t6);
+/* The seam of --ld / --ldPrune: a state machine that is handed the batches of a run in output order -- cut anywhere -- and
+ * gives the run's table and prune lists.  It keeps the last `window` rows of the run so far (.bed code, chrom, locus
+ * text; several batches' worth when batches are shorter than the window).  For a new batch it counts the pairs (a in the
+ * carry, b among the batch's first rows, b - a <= window, equal chrom) with bvcf_ld_counts / bvcf_ld_in_ld, puts them in
+ * front of the device's events of the same b, turns batch-local rows into the run's numbering, writes the table lines,
+ * walks the prune rule (which needs the kept flags of the last `window` rows only) and takes the batch's tail over as
+ * the new carry.
+ *   push: n_rows rows; head / tail: the first and last n_edge = min(window, n_rows) rows in .bed code, row_bytes apart;
+ *   events [n_events][8] as bvcf_ld_info has them; the rows' TSV columns "chrom\tpos\tref\talt" back to back in `loci`, row
+ *   i at loci[loci_off[i], loci_off[i + 1]).  Returns 0, or -1 when the arguments contradict each other (an event that
+ *   names a row the batch does not have, events out of order, n_edge not min(window, n_rows), a locus without three TABs).
+ *   read: which = 0 the table's lines (no header), 1 the .prune.in lines, 2 the .prune.out lines: everything pushed so
+ *   far; the pointer holds until the next push or destroy.  rows / pairs: the run's rows and pairs in LD so far. */
+typedef struct bvcf_ld_seam bvcf_ld_seam;
+bvcf_ld_seam *bvcf_ld_seam_create(uint32_t n_samples, uint32_t window, uint32_t t6);
+int bvcf_ld_seam_push(bvcf_ld_seam *s, uint64_t n_rows, uint32_t n_edge, const uint8_t *head, const uint8_t *tail,
+                      const uint32_t *events, uint64_t n_events, const char *loci, const uint64_t *loci_off);
+int bvcf_ld_seam_read(const bvcf_ld_seam *s, int which, const char **text, size_t *len);
+uint64_t bvcf_ld_seam_rows(const bvcf_ld_seam *s);
+uint64_t bvcf_ld_seam_pairs(const bvcf_ld_seam *s);
+void bvcf_ld_seam_destroy(bvcf_ld_seam *s);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
