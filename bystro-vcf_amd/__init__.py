@@ -47,7 +47,8 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
                  "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
-                 "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels"]
+                 "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
+                 "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -67,6 +68,9 @@ EXPORTS = [
     "bvcf_enable_bed_rows", "bvcf_reserve_bed_rows", "bvcf_bed_rows", "bvcf_config_plink_defaults",
     "bvcf_enable_trios", "bvcf_reserve_trio_events", "bvcf_trio_stats", "bvcf_config_trios_defaults",
     "bvcf_enable_ld", "bvcf_reserve_ld_events", "bvcf_ld_stats", "bvcf_config_ld_defaults",
+    "bvcf_locus_hash", "bvcf_variant_table_capacity", "bvcf_variant_table_build", "bvcf_variant_table_parse",
+    "bvcf_variant_table_free", "bvcf_variant_table_has", "bvcf_set_variant_table", "bvcf_set_variant_list",
+    "bvcf_variant_gate_count", "bvcf_config_variants_defaults",
 ]
 
 
@@ -171,6 +175,107 @@ class ConfigLd(C.Structure):
     """bvcf_config_ld: a bvcf_config_trios and what came after it"""
     _fields_ = [("trios", ConfigTrios), ("ld_path", C.c_char_p), ("ld_prune_prefix", C.c_char_p), ("ld_window", C.c_uint32),
                 ("ld_t6", C.c_uint32), ("ld_t6_set", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+CONFIG_MORE_VARIANTS = 5  # BVCF_CONFIG_MORE_VARIANTS in Config.reserved[1]: the ConfigLd is the head of a ConfigVariants
+VARIANT_MAX_ENTRIES = 1 << 27  # BVCF_VARIANT_MAX_ENTRIES
+# the lines of the --variantFilterReport file; variant_gate_count() gives the last three
+VARIANT_REPORT = ["listed", "examined", "kept", "dropped"]
+VARIANT_ENTRY_DTYPE = np.dtype([("tag", "<u4"), ("off", "<u4"), ("len", "<u4"), ("zero", "<u4")])
+
+
+class ConfigVariants(C.Structure):
+    """bvcf_config_variants: a bvcf_config_ld and what came after it"""
+    _fields_ = [("ld", ConfigLd), ("keep_variants_path", C.c_char_p), ("exclude_variants_path", C.c_char_p),
+                ("variant_filter_path", C.c_char_p)]
+
+
+class VariantTableStruct(C.Structure):
+    """bvcf_variant_table"""
+    _fields_ = [("entries", C.c_void_p), ("capacity", C.c_uint64), ("blob", C.c_void_p), ("blob_bytes", C.c_uint64),
+                ("n", C.c_uint64)]
+
+
+def locus_hash(s):
+    """bvcf_locus_hash: the 64-bit hash of a locus string (bytes) that places it in the table  (host code, no device)"""
+    lib.bvcf_locus_hash.restype = C.c_uint64
+    lib.bvcf_locus_hash.argtypes = [C.c_char_p, C.c_size_t]
+    return int(lib.bvcf_locus_hash(bytes(s), len(s)))
+
+
+def variant_table_capacity(n):
+    """bvcf_variant_table_capacity: the slots of a table of n distinct entries (0 above VARIANT_MAX_ENTRIES)"""
+    lib.bvcf_variant_table_capacity.restype = C.c_uint64
+    lib.bvcf_variant_table_capacity.argtypes = [C.c_uint64]
+    return int(lib.bvcf_variant_table_capacity(n))
+
+
+class VariantTable:
+    """a host table of locus strings: bvcf_variant_table_build over a list of bytes, or -- text= -- bvcf_variant_table_parse
+    over the bytes of a list file  (host code, no device)"""
+
+    def __init__(self, loci=None, text=None):
+        self.t = VariantTableStruct()
+        if text is not None:
+            lib.bvcf_variant_table_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+            rc = lib.bvcf_variant_table_parse(bytes(text), len(text), C.byref(self.t))
+        else:
+            loci = [bytes(x) for x in loci]
+            blob = b"".join(loci)
+            lens = np.array([len(x) for x in loci], dtype=np.uint32)
+            offs = np.zeros(len(loci), dtype=np.uint64)
+            if len(loci) > 1:
+                offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+            lib.bvcf_variant_table_build.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            rc = lib.bvcf_variant_table_build(blob, offs.ctypes.data if len(loci) else None,
+                                              lens.ctypes.data if len(loci) else None, len(loci), C.byref(self.t))
+        if rc:
+            raise BvcfError(rc, "bvcf_variant_table_build")
+
+    @property
+    def n(self):
+        return int(self.t.n)
+
+    @property
+    def capacity(self):
+        return int(self.t.capacity)
+
+    @property
+    def blob(self):
+        return C.string_at(self.t.blob, self.t.blob_bytes) if self.t.blob_bytes else b""
+
+    @property
+    def entries(self):
+        """the slots as a VARIANT_ENTRY_DTYPE array (copied)"""
+        n = self.capacity * VARIANT_ENTRY_DTYPE.itemsize
+        return np.frombuffer(C.string_at(self.t.entries, n), dtype=VARIANT_ENTRY_DTYPE).copy()
+
+    def has(self, s):
+        """bvcf_variant_table_has: the probe the device runs"""
+        lib.bvcf_variant_table_has.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        r = lib.bvcf_variant_table_has(C.byref(self.t), bytes(s), len(s))
+        if r < 0:
+            raise ValueError("bvcf_variant_table_has: bad arguments")
+        return bool(r)
+
+    def close(self):
+        lib.bvcf_variant_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_variant_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def variant_gate_count(result):
+    """bvcf_variant_gate_count over a collected batch (a Result) -> [examined, kept, dropped]"""
+    out = (C.c_uint64 * 3)()
+    lib.bvcf_variant_gate_count.restype = None
+    lib.bvcf_variant_gate_count.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bvcf_variant_gate_count(C.byref(result), out)
+    return [int(x) for x in out]
 
 
 class LdInfo(C.Structure):
@@ -388,7 +493,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     cfg = cfg or {}
     # (--mendel / --mendelErrors: the larger struct and its marker, only then; every other config is a ConfigMore as before)
     # (--ld / --ldPrune: the still larger struct and its marker, only then)
-    ldc = ConfigLd() if cfg.get("ld") or cfg.get("ldPrune") else None
+    # (--keepVariants / --excludeVariants / --variantFilterReport: the largest struct and its marker, only then)
+    vc = ConfigVariants() if any(cfg.get(k) for k in ("keepVariants", "excludeVariants", "variantFilterReport")) else None
+    ldc = vc.ld if vc is not None else ConfigLd() if cfg.get("ld") or cfg.get("ldPrune") else None
     trios = ldc.trios if ldc is not None else ConfigTrios() if cfg.get("mendel") or cfg.get("mendelErrors") else None
     more = trios.more if trios is not None else ConfigMore()
     c = more.base  # (a view of more's memory, which it keeps alive: what the callers pass on is the head of a bvcf_config_more)
@@ -466,6 +573,13 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         ldc.ld_t6 = parse_ld_r2(str(cfg.get("ldR2", "0.2")))
         ldc.ld_t6_set = 1
         c.reserved[1] = CONFIG_MORE_LD
+    if vc is not None:  # the list of locus strings and its report
+        for key, field in (("keepVariants", "keep_variants_path"), ("excludeVariants", "exclude_variants_path"),
+                           ("variantFilterReport", "variant_filter_path")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(vc, field, keep[-1])
+        c.reserved[1] = CONFIG_MORE_VARIANTS
     c._keep = keep
     return c
 
@@ -800,6 +914,7 @@ class Batch:
         # the record arrays as they are now -- like every view here they belong to the slot, valid until it takes another batch
         self._result = r
         self._gate_counts = None
+        self._variant_counts = None  # bvcf_variant_gate_count, likewise
         self.n_samples = r.n_samples
         self.cmap_stride = r.cmap_stride
         self.kernel_ms = r.kernel_ms
@@ -903,6 +1018,12 @@ class Batch:
             self._gate_counts = site_gate_count(self._result)
         return self._gate_counts
 
+    @property
+    def variant_counts(self):
+        if self._variant_counts is None:
+            self._variant_counts = variant_gate_count(self._result)
+        return self._variant_counts
+
     def record_slots(self, i):
         """indices into alleles[] (and dosage[]) of line i's output alleles, in order"""
         L = self.lines[i]
@@ -944,7 +1065,8 @@ class Ctx:
                  max_batch_bytes=0, max_lines=0, max_alleles=0, cmap_bytes=0, n_slots=0, want_class_maps=True,
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
-                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None):
+                 min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
+                 variants=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -984,6 +1106,12 @@ class Ctx:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
                 raise BvcfError(rc, msg)
+        if variants is not None:  # bvcf_set_variant_list / bvcf_set_variant_table: (loci or a VariantTable, exclude)
+            try:
+                self.set_variant_list(*variants)
+            except BvcfError:
+                self.close()
+                raise
         if site_gate is not None:  # bvcf_set_site_gate: a SiteGate, or make_site_gate's keywords as a dict
             try:
                 self.set_site_gate(site_gate)
@@ -1112,6 +1240,36 @@ class Ctx:
         g = gate if isinstance(gate, SiteGate) else make_site_gate(**gate)
         lib.bvcf_set_site_gate.argtypes = [C.c_void_p, C.c_void_p]
         self._check(lib.bvcf_set_site_gate(self.h, C.byref(g)))
+
+    def set_variant_list(self, loci, exclude=False):
+        """before the first submit: loci is a list of locus strings (bytes; bvcf_set_variant_list) or a built VariantTable
+        (bvcf_set_variant_table); exclude: the listed rows go instead of staying"""
+        if isinstance(loci, VariantTable):
+            lib.bvcf_set_variant_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            self._check(lib.bvcf_set_variant_table(self.h, C.byref(loci.t), int(bool(exclude))))
+            return
+        loci = [bytes(x) for x in loci]
+        blob = b"".join(loci)
+        lens = np.array([len(x) for x in loci], dtype=np.uint32)
+        offs = np.zeros(len(loci), dtype=np.uint64)
+        if len(loci) > 1:
+            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        lib.bvcf_set_variant_list.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        self._check(lib.bvcf_set_variant_list(self.h, blob, offs.ctypes.data if len(loci) else None,
+                                              lens.ctypes.data if len(loci) else None, len(loci), int(bool(exclude))))
+
+    def variant_gate_stride(self):
+        """the alleles[] slots k_variant_gate's grid covers in one step"""
+        lib.bvcf_bench_variant_gate_stride.restype = C.c_uint32
+        lib.bvcf_bench_variant_gate_stride.argtypes = [C.c_void_p]
+        return int(lib.bvcf_bench_variant_gate_stride(self.h))
+
+    def bench_variant_kernel(self):
+        """k_variant_gate over the last bench block of the ctx -> ms"""
+        ms = C.c_float()
+        lib.bvcf_bench_variant_kernel.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_bench_variant_kernel(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def bed_rows_info(self):
         """bvcf_bed_rows: the BedRowsInfo of the batch collected last (need_bytes is set after BVCF_E_CAPACITY too)"""

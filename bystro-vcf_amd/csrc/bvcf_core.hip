@@ -19,7 +19,9 @@
 #include <algorithm>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <thread>
+#include <unordered_set>
 #include <vector>
 
 using namespace bvcf_dev;
@@ -202,6 +204,12 @@ struct bvcf_ctx : bvcf_ctx_plan {
   // bvcf_set_site_gate on a file with samples, some criterion not neutral: k_site_gate / k_site_hwe behind k_finish
   bool gate_on = false;
   bvcf_site_gate gate{};
+  // bvcf_set_variant_list / bvcf_set_variant_table on a file with samples: k_variant_gate behind k_finish, in front of the
+  // site gate; the hash set (bvcf_variantlist.hip.h) is the ctx's, read by the batches of every slot
+  bool variants_on = false;
+  uint32_t variants_exclude = 0, variants_mask = 0;
+  DevBuf<VariantEntry> d_variant_entries;
+  DevBuf<uint8_t> d_variant_blob;
   // bvcf_enable_bed_rows on a file with samples: k_bed_count / k_bed_scan / k_bed_index / k_bed_rows at the end of every chain; bed_cap is
   // what a slot's arena holds (bvcf_reserve_bed_rows grows it), bed_last the batch collected last (bvcf_bed_rows)
   bool bed_asked = false, bed_on = false;
@@ -816,6 +824,24 @@ void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *sl
   if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
 }
 
+VariantGateArgs make_variant_args(const bvcf_ctx *c) {
+  VariantGateArgs va{};
+  va.entries = c->d_variant_entries;
+  va.blob = c->d_variant_blob;
+  va.mask = c->variants_mask;
+  va.exclude = c->variants_exclude;
+  return va;
+}
+
+uint32_t variant_gate_grid(const bvcf_ctx *c) { return (uint32_t)c->n_cu * kVariantGateWgs; }
+
+// bvcf_set_variant_list: right behind k_finish and in front of the site gate -- the rows the list does not select are
+// taken out (bvcf_variantlist.hip.h) before anything examines them
+void launch_variant_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st) {
+  if (!c->variants_on) return;
+  hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, st, a, make_variant_args(c));
+}
+
 // the slot holds everything the kernels of the row index write, sized for the ctx's current capacities
 bool index_ready(const bvcf_ctx *c, const Slot &s) {
   return s.d_bed_total && s.d_bed_base.size() >= c->max_lines && s.d_bed_src.size() >= c->max_alleles;
@@ -1007,6 +1033,7 @@ void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t 
                        dim3(kWgThreads), 0, st, a);
   if (!(skip & 4))
     hipLaunchKernelGGL(k_finish, dim3(follower_grid(c, n_cu * 4u, c->last_finish, kWgThreads)), dim3(kWgThreads), 0, st, a);
+  launch_variant_gate(c, a, st);
   launch_site_gate(c, a, st, slot);
   if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
   launch_sample_stats(c, a, st, slot);
@@ -1106,6 +1133,7 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
   if (ev_gt1) hipEventRecord(ev_gt1, st);
   if (c->scan == BVCF_SCAN_NONE) return;
   hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
+  launch_variant_gate(c, a, st);
   launch_site_gate(c, a, st, slot);
   if (a.dosage) switch (c->scan) {
       case BVCF_SCAN_SUBSET: hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa); break;
@@ -2779,6 +2807,149 @@ void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]) {
   }
 }
 
+uint64_t bvcf_locus_hash(const char *s, size_t n) { return s ? fnv1a((const uint8_t *)s, n) : kFnvBasis; }
+
+uint64_t bvcf_variant_table_capacity(uint64_t n) { return n <= BVCF_VARIANT_MAX_ENTRIES ? variant_capacity(n) : 0; }
+
+// is the string s[0, n) an entry?  (the probe the device runs, on the host's table)
+static bool table_has(const VariantEntry *entries, const uint8_t *blob, uint32_t mask, const uint8_t *s, uint32_t n) {
+  return variant_find(entries, blob, mask, fnv1a(s, n), n, [&](LocusComparer &cmp) {
+    for (uint32_t i = 0; i < n; i++)
+      if (!cmp(s[i])) return false;
+    return true;
+  });
+}
+
+void bvcf_variant_table_free(bvcf_variant_table *t) {
+  if (!t) return;
+  free((void *)t->entries);
+  free((void *)t->blob);
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_variant_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, bvcf_variant_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (n && (!bytes || !off || !len)) return BVCF_E_ARG;
+  // the distinct entries first: the capacity follows their number
+  std::unordered_set<std::string_view> seen;
+  std::vector<uint64_t> first;
+  uint64_t blob_bytes = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (!len[i]) return BVCF_E_ARG;  // (len == 0 marks an empty slot)
+    if (!seen.emplace(bytes + off[i], len[i]).second) continue;
+    first.push_back(i);
+    blob_bytes += len[i];
+    if (first.size() > BVCF_VARIANT_MAX_ENTRIES || blob_bytes >= (1ull << 32)) return BVCF_E_TOO_BIG;
+  }
+  const uint64_t cap = variant_capacity(first.size());
+  VariantEntry *entries = (VariantEntry *)calloc((size_t)cap, sizeof(VariantEntry));
+  uint8_t *blob = (uint8_t *)malloc((size_t)blob_bytes + 1);
+  if (!entries || !blob) {
+    free(entries);
+    free(blob);
+    return BVCF_E_NOMEM;
+  }
+  const uint32_t mask = (uint32_t)(cap - 1);
+  uint64_t at = 0;
+  for (const uint64_t i : first) {
+    const uint8_t *s = (const uint8_t *)bytes + off[i];
+    const unsigned long long h = fnv1a(s, len[i]);
+    uint32_t slot = (uint32_t)h & mask;
+    while (entries[slot].len) slot = (slot + 1u) & mask;
+    entries[slot] = VariantEntry{(uint32_t)(h >> 32), (uint32_t)at, len[i], 0u};
+    memcpy(blob + at, s, len[i]);
+    at += len[i];
+  }
+  out->entries = (const uint32_t *)entries;
+  out->capacity = cap;
+  out->blob = (const char *)blob;
+  out->blob_bytes = blob_bytes;
+  out->n = first.size();
+  return BVCF_OK;
+}
+
+int bvcf_variant_table_has(const bvcf_variant_table *t, const char *s, size_t n) {
+  if (!t || !t->entries || !t->capacity || (t->capacity & (t->capacity - 1)) || (!s && n) || n > 0xFFFFFFFFull) return -1;
+  return table_has((const VariantEntry *)t->entries, (const uint8_t *)t->blob, (uint32_t)(t->capacity - 1), (const uint8_t *)s, (uint32_t)n) ? 1 : 0;
+}
+
+// every entry lies in the blob, nothing is stored in the fourth word, the capacity is a power of two with an empty slot
+static bool variant_table_sound(const bvcf_variant_table *t) {
+  if (!t || !t->entries || t->capacity < 16 || t->capacity > (1ull << 31) || (t->capacity & (t->capacity - 1)) ||
+      t->blob_bytes >= (1ull << 32) || (t->blob_bytes && !t->blob))
+    return false;
+  const VariantEntry *e = (const VariantEntry *)t->entries;
+  uint64_t used = 0;
+  for (uint64_t i = 0; i < t->capacity; i++) {
+    if (!e[i].len) continue;
+    used++;
+    if ((uint64_t)e[i].off + e[i].len > t->blob_bytes) return false;
+  }
+  return used == t->n && 2 * used <= t->capacity;
+}
+
+int bvcf_set_variant_table(bvcf_ctx *c, const bvcf_variant_table *t, int exclude) {
+  if (!c) return BVCF_E_ARG;
+  if (!variant_table_sound(t)) {
+    c->err = "bvcf_set_variant_table: want a table as bvcf_variant_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (c->in_flight) {
+    c->err = "bvcf_set_variant_table with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
+  c->variants_on = false;
+  c->d_variant_entries.reset();
+  c->d_variant_blob.reset();
+  if (exclude && !t->n) return BVCF_OK;  // (nothing to take out: nothing is allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->d_variant_entries.alloc((size_t)t->capacity));
+  HIP_TRY(c, c->d_variant_blob.alloc((size_t)t->blob_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->d_variant_entries, t->entries, (size_t)t->capacity * sizeof(VariantEntry), hipMemcpyHostToDevice));
+  if (t->blob_bytes) HIP_TRY(c, hipMemcpy(c->d_variant_blob, t->blob, (size_t)t->blob_bytes, hipMemcpyHostToDevice));
+  c->variants_mask = (uint32_t)(t->capacity - 1);
+  c->variants_exclude = exclude ? 1u : 0u;
+  c->variants_on = true;
+  return BVCF_OK;
+}
+
+int bvcf_set_variant_list(bvcf_ctx *c, const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int exclude) {
+  if (!c) return BVCF_E_ARG;
+  bvcf_variant_table t;
+  const int rc = bvcf_variant_table_build(bytes, off, len, n, &t);
+  if (rc) {
+    c->err = rc == BVCF_E_TOO_BIG ? "bvcf_set_variant_list: more than 2^27 distinct entries, or 4 GiB of them"
+                                  : "bvcf_set_variant_list: bad arguments (an entry of length 0?) or no memory";
+    return rc;
+  }
+  const int rc2 = bvcf_set_variant_table(c, &t, exclude);
+  bvcf_variant_table_free(&t);
+  return rc2;
+}
+
+void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]) {
+  if (!out) return;
+  out[0] = out[1] = out[2] = 0;
+  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    for (uint32_t j = 0; j < L.n_rec; j++) {
+      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
+      if (A.pad[1]) {
+        out[2]++;
+      } else if (A.ac || A.pad[0]) {  // (a row the site gate took out afterwards was kept here)
+        out[1]++;
+      }
+    }
+  }
+  out[0] = out[1] + out[2];
+}
+
+uint32_t bvcf_bench_variant_gate_stride(const bvcf_ctx *c) { return c ? variant_gate_grid(c) * kWgThreads : 0u; }
+
 int bvcf_site_gate_verdict(const bvcf_site_gate *g, uint32_t S, const uint32_t counts[5]) {
   if (!g || !counts || !site_gate_in_range(g)) return -1;
   return (int)site_gate_verdict(*g, S, counts[0], counts[1], counts[2], counts[3], counts[4]);
@@ -3310,6 +3481,39 @@ int bvcf_bench_gate_kernels(bvcf_ctx *c, float ms[2]) {
   HIP_TRY(c, hipStreamSynchronize(s.stream));
   for (int k = 0; k < 2; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
   if (!ga.list) ms[1] = 0.f;
+  return BVCF_OK;
+}
+
+int bvcf_bench_variant_kernel(bvcf_ctx *c, float *ms) {
+  if (!c || !ms) return BVCF_E_ARG;
+  if (c->in_flight) {
+    c->err = "bvcf_bench_variant_kernel with batches in flight";
+    return BVCF_E_BUSY;
+  }
+  if (!c->variants_on || !c->bench_src) {
+    c->err = "bvcf_bench_variant_kernel: the ctx has no variant list, or no bvcf_bench_device* call went before";
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  Slot &s = c->slots[0];
+  int rc = alloc_results(c, s);
+  if (rc) return rc;
+  // the chain of the last bench block once more with both gates off: the records as k_finish leaves them
+  s.s2_parity ^= 1u;
+  const KernelArgs a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
+  const bool gate_on = c->gate_on;
+  c->variants_on = c->gate_on = false;
+  launch_chain(c, a, s.stream, nullptr, nullptr, &s);
+  c->variants_on = true;
+  c->gate_on = gate_on;
+  Event ev[2];
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, s.stream, a, make_variant_args(c));
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  hipEventElapsedTime(ms, ev[0], ev[1]);
   return BVCF_OK;
 }
 

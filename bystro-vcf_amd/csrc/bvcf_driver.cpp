@@ -467,6 +467,11 @@ void Driver::device_main(DevWorker *W) {
       bvcf_site_gate_count(&res, t);
       for (int q = 0; q < 7; q++) W->gate_counts[q] += t[q];
     }
+    if (R_.variant_fd >= 0) {  // --variantFilterReport: likewise
+      uint64_t t[3];
+      bvcf_variant_gate_count(&res, t);
+      for (int q = 0; q < 3; q++) W->variant_counts[q] += t[q];
+    }
     FmtJob j;
     j.b = b;
     j.res = res;
@@ -639,6 +644,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return rc;
     }
     if (const int rc = open_ld(R_, &msg)) {  // --ld / --ldPrune: likewise
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
+    if (const int rc = open_variants(R_, &msg)) {  // --keepVariants / --excludeVariants / --variantFilterReport: the list read, the report opened
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
@@ -858,6 +867,17 @@ int Driver::run(uint64_t *n_lines_in) {
         close(sg_fd_);
       }
       sg_fd_ = -1;
+    }
+    if (R_.variant_fd >= 0 && rc_ == BVCF_OK) {
+      // --variantFilterReport: the workers' counts of the batches they handed on (a failed run leaves the file empty)
+      uint64_t sum[3] = {0, 0, 0};
+      for (auto &W : workers_)
+        for (int q = 0; q < 3; q++) sum[q] += W->variant_counts[q];
+      std::string msg;
+      if (write_variant_report(R_, sum, &msg)) {
+        fail(msg, BVCF_E_IO);
+        write_all(fd_err_, log_.data(), log_.size());
+      }
     }
     if (R_.mendel_fd >= 0 || R_.mendel_errors_fd >= 0) {
       // --mendel / --mendelErrors: the sink added up the batches it was handed, in input order

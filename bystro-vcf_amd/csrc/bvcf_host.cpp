@@ -55,6 +55,31 @@ void bvcf_config_ld_defaults(bvcf_config_ld *c) {
   c->ld_t6_set = 1;
 }
 
+void bvcf_config_variants_defaults(bvcf_config_variants *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_ld_defaults(&c->ld);
+  c->ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_VARIANTS;
+}
+
+int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out) {
+  if (!out || (!text && n)) return BVCF_E_ARG;
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  for (size_t pos = 0; pos < n;) {
+    const char *nl = (const char *)memchr(text + pos, '\n', n - pos);
+    const size_t e = nl ? (size_t)(nl - text) : n;
+    size_t l = e - pos;
+    if (l && text[pos + l - 1] == '\r') l--;
+    if (l > 0xFFFFFFFFull) return BVCF_E_TOO_BIG;
+    if (l) {
+      off.push_back(pos);
+      len.push_back((uint32_t)l);
+    }
+    pos = e + 1;
+  }
+  return bvcf_variant_table_build(text, off.data(), len.data(), off.size(), out);
+}
+
 size_t bvcf_string_header(const bvcf_config *c, char *out, size_t cap) {
   std::string h;
   for (int i = 0; i < 15; i++) {
@@ -121,12 +146,14 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   uint64_t lines_in = 0;
   int ss_fd = -1, pr_fd = -1, sg_fd = -1;
   uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint64_t variant_counts[3] = {0, 0, 0};
   int rc = open_sample_stats(c, &ss_fd, &msg);
   if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
   if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
   if (rc == BVCF_OK) rc = open_plink(R, &msg);
   if (rc == BVCF_OK) rc = open_mendel(R, &msg);
   if (rc == BVCF_OK) rc = open_ld(R, &msg);
+  if (rc == BVCF_OK) rc = open_variants(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -165,6 +192,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         uint64_t t[7];
         bvcf_site_gate_count(&res, t);
         for (int q = 0; q < 7; q++) gate_counts[q] += t[q];
+      }
+      if (R.variant_fd >= 0) {  // --variantFilterReport: likewise
+        uint64_t t[3];
+        bvcf_variant_gate_count(&res, t);
+        for (int q = 0; q < 3; q++) variant_counts[q] += t[q];
       }
       if (R.want_rows) {
         format_batch(c, &res, vcf + pos, nm, R.ratios.get(), R.pool.get(), o, l);
@@ -266,6 +298,10 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       l.append(msg + "\n");
       rc = BVCF_E_IO;
     }
+  }
+  if (R.variant_fd >= 0 && rc == BVCF_OK && write_variant_report(R, variant_counts, &msg)) {  // --variantFilterReport: likewise
+    l.append(msg + "\n");
+    rc = BVCF_E_IO;
   }
   if (R.ctx) bvcf_destroy(R.ctx);
   if (n_lines_in) *n_lines_in = lines_in;

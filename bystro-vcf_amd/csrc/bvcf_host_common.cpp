@@ -862,6 +862,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.variants_on) {  // --keepVariants / --excludeVariants: the run's table on every ctx of the run
+    rc = bvcf_set_variant_table(*ctx, &R.variant_table, R.variants_exclude);
+    if (rc) {
+      *msg = std::string("bvcf_set_variant_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (const bvcf_config_more *m = rc == BVCF_OK ? gate_config(R.cfg) : nullptr) {  // the site gate of every ctx of the run
     rc = bvcf_set_site_gate(*ctx, &m->site_gate);
     if (rc) {
@@ -1406,6 +1414,74 @@ int write_site_report(int fd, const uint64_t counts[7], std::string *msg) {
   const int saved = errno;
   if (close(fd) || bad) {
     *msg = std::string("siteFilterReport: write failed: ") + strerror(bad ? saved : errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_variants(Run &R, std::string *msg) {
+  const bvcf_config_variants *v = variants_config(R.cfg);
+  if (!v) return BVCF_OK;
+  const char *kp = v->keep_variants_path, *xp = v->exclude_variants_path, *rp = v->variant_filter_path;
+  const bool keep = kp && *kp, excl = xp && *xp;
+  if (keep && excl) {
+    *msg = "keep_variants_path and exclude_variants_path are both set";
+    return BVCF_E_ARG;
+  }
+  if (rp && *rp) {
+    R.variant_fd = open(rp, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (R.variant_fd < 0) {
+      *msg = std::string("open ") + rp + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  if (!keep && !excl) return BVCF_OK;
+  const char *path = keep ? kp : xp;
+  std::string text;
+  {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+      *msg = std::string("open ") + path + ": " + strerror(errno);
+      return BVCF_E_FATAL;
+    }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const int err = ferror(f) ? errno : 0;
+    fclose(f);
+    if (err) {
+      *msg = std::string("read ") + path + ": " + strerror(err);
+      return BVCF_E_FATAL;
+    }
+  }
+  const int rc = bvcf_variant_table_parse(text.data(), text.size(), &R.variant_table);
+  if (rc) {
+    *msg = std::string(keep ? "keepVariants: " : "excludeVariants: ") + path +
+           (rc == BVCF_E_TOO_BIG ? ": more than 134217728 distinct entries, or 4 GiB of them" : ": out of memory");
+    return BVCF_E_FATAL;
+  }
+  R.variants_on = true;
+  R.variants_exclude = excl;
+  return BVCF_OK;
+}
+
+int write_variant_report(Run &R, const uint64_t counts[3], std::string *msg) {
+  if (R.variant_fd < 0) return BVCF_OK;
+  static const char *const kNames[4] = {"listed", "examined", "kept", "dropped"};
+  const uint64_t v[4] = {R.variant_table.n, counts[0], counts[1], counts[2]};
+  std::string o;
+  for (int q = 0; q < 4; q++) {
+    o.append(kNames[q]);
+    o.push_back('\t');
+    append_ll(o, (long long)v[q]);
+    o.push_back('\n');
+  }
+  const bool bad = write_all(R.variant_fd, o.data(), o.size()) != 0;
+  const int saved = errno;
+  const bool bad_close = close(R.variant_fd) != 0;
+  R.variant_fd = -1;
+  if (bad || bad_close) {
+    *msg = std::string("variantFilterReport: write failed: ") + strerror(bad ? saved : errno);
     return BVCF_E_IO;
   }
   return BVCF_OK;

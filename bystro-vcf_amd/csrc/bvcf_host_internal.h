@@ -249,10 +249,17 @@ struct Run {
   uint32_t ld_window = 0, ld_t6 = 0;
   int ld_fd = -1, ld_in_fd = -1, ld_out_fd = -1;
   bvcf_ld_seam *ld_seam = nullptr;
+  // --keepVariants / --excludeVariants / --variantFilterReport: open_variants opens the report and reads the list into the
+  // run's one table before any device work; create_ctx uploads it to every ctx; write_variant_report writes `listed` and
+  // the sum of bvcf_variant_gate_count over the batches of the output at the end
+  bool variants_on = false, variants_exclude = false;
+  bvcf_variant_table variant_table{};
+  int variant_fd = -1;
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd})
+    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
+    bvcf_variant_table_free(&variant_table);
   }
 };
 
@@ -351,6 +358,16 @@ inline bool wants_ld(const bvcf_config *c) {
   const bvcf_config_ld *l = ld_config(c);
   return l && ((l->ld_path && *l->ld_path) || (l->ld_prune_prefix && *l->ld_prune_prefix));
 }
+// --keepVariants / --excludeVariants / --variantFilterReport: the config as a bvcf_config_variants (the sixth marker), or NULL
+inline const bvcf_config_variants *variants_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_VARIANTS) ? reinterpret_cast<const bvcf_config_variants *>(c)
+                                                                                             : nullptr;
+}
+// the report opened (truncated) and the list read into R.variant_table -- BVCF_E_ARG when both lists are given, BVCF_E_IO for
+// the report, BVCF_E_FATAL for a list that cannot be read or is over the bound, one message in *msg; the four lines written
+// (counts = the sum of bvcf_variant_gate_count over the batches of the output) and the file closed
+int open_variants(Run &R, std::string *msg);
+int write_variant_report(Run &R, const uint64_t counts[3], std::string *msg);
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

@@ -53,6 +53,10 @@ struct Cli {
   // the greedy prune lists made of them (counted on the device); --ldWindow / --ldR2 alone are accepted and do nothing
   std::string ld, ld_prune;
   uint32_t ld_window = 50, ld_t6 = 200000;
+  // extension: --keepVariants PATH / --excludeVariants PATH, the run keeps only the rows whose locus string "chrom:pos:ref:alt"
+  // is in the list / all the others (looked up on the device, in front of the site gate); --variantFilterReport PATH, how
+  // many rows the list examined, kept and dropped
+  std::string keep_variants, exclude_variants, variant_report;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -148,7 +152,7 @@ int parse(int argc, char **argv, Cli &c) {
         name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
         name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
         name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
-        name == "ldR2") {
+        name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -211,6 +215,14 @@ int parse(int argc, char **argv, Cli &c) {
           fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 0 to 999999999\n", val.c_str(), name.c_str());
           return 2;
         }
+      } else if (name == "keepVariants" || name == "excludeVariants") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of a list of locus strings\n", name.c_str());
+          return 2;
+        }
+        (name == "keepVariants" ? c.keep_variants : c.exclude_variants) = val;
+      } else if (name == "variantFilterReport") {
+        c.variant_report = val;
       } else if (name == "keepSamples" || name == "excludeSamples") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of a list of sample names\n", name.c_str());
@@ -226,6 +238,10 @@ int parse(int argc, char **argv, Cli &c) {
   }
   if (!c.keep_samples.empty() && !c.exclude_samples.empty()) {
     fprintf(stderr, "-keepSamples and -excludeSamples cannot both be given\n");
+    return 2;
+  }
+  if (!c.keep_variants.empty() && !c.exclude_variants.empty()) {
+    fprintf(stderr, "-keepVariants and -excludeVariants cannot both be given\n");
     return 2;
   }
   if ((!c.mendel.empty() || !c.mendel_errors.empty()) && c.fam.empty()) {
@@ -262,9 +278,10 @@ int main(int argc, char **argv) {
     return 1;
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
-  // conversion-only pass; --mendel / --mendelErrors alone: QC-only again)
+  // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so is --variantFilterReport alone)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
-      c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty()) {
+      c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
+      c.variant_report.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -278,9 +295,10 @@ int main(int argc, char **argv) {
 
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
-  // (... and behind those the --ld paths, window and threshold)
-  bvcf_config_ld ldc;
-  bvcf_config_ld_defaults(&ldc);
+  // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report)
+  bvcf_config_variants vc;
+  bvcf_config_variants_defaults(&vc);
+  bvcf_config_ld &ldc = vc.ld;
   bvcf_config_trios &trios = ldc.trios;
   bvcf_config_more &more = trios.more;
   bvcf_config &cfg = more.base;
@@ -347,6 +365,9 @@ int main(int argc, char **argv) {
   ldc.ld_window = c.ld_window;
   ldc.ld_t6 = c.ld_t6;
   ldc.ld_t6_set = 1;
+  vc.keep_variants_path = c.keep_variants.c_str();
+  vc.exclude_variants_path = c.exclude_variants.c_str();
+  vc.variant_filter_path = c.variant_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -223,7 +223,9 @@ typedef struct {
   uint8_t site_type;   /* BVCF_SITE_* */
   uint8_t trtv;        /* 0 / 1 / 2 (main.go:602-606) */
   uint8_t flags;
-  uint8_t pad[2];      /* [0]: bvcf_set_site_gate, the BVCF_GATE_* bits of a row the gate took out (its ac is then 0); else 0 */
+  uint8_t pad[2];      /* [0]: bvcf_set_site_gate, the BVCF_GATE_* bits of a row the gate took out (its ac is then 0); else 0
+                          [1]: bvcf_set_variant_list, 1 for a row the list took out (its ac is then 0, and [0] is 0: the
+                          site gate never saw it); else 0 -- every kernel that writes a record writes 0 here */
   uint32_t gt_task;    /* internal: genotype-scan task that produced ac..n_miss */
   uint32_t pad2;
 } bvcf_allele;
@@ -558,6 +560,57 @@ int bvcf_set_site_gate(bvcf_ctx *ctx, const bvcf_site_gate *g);
  * sample columns. */
 void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]);
 
+/* Row selection by a list of locus strings (--keepVariants / --excludeVariants).  The locus string of a row is
+ * "chrom:pos:ref:alt", the row's four TSV columns joined by ':' -- the second .bim column, the dosage file's locus, a line
+ * of the --ldPrune lists: chrom with the TSV's "chr" rule (put in front unless CHROM has four bytes or more and starts with
+ * 'c'), pos as the TSV prints it (the POS bytes of a BVCF_ALLELE_POS_TEXT row), ref, and the base / "+ACG" / "-3".
+ * A row MATCHES iff its locus string equals an entry byte for byte: "1:100:A:T" does not match the row of "chr1" -- the
+ * list is in TSV form.  A multiallelic or MNP line is matched per emitted row; two lines with the same locus both match.
+ * With exclude == 0 the matching rows stay, otherwise the others.  The rows examined are the rows the site gate examines: an
+ * output allele of a line with status OK, in a file with sample columns, with ac > 0 after min_gq / min_dp masking and after
+ * sample_keep.  On the device, right behind the kernel that settles the counts and IN FRONT OF the site gate: a row the
+ * list takes out is not examined by the gate and is in none of bvcf_site_gate_count's counts, like a row no sample carries.
+ * The contract: a row the list took out has ac == 0, bvcf_allele.pad[1] == 1 and pad[0] == 0; an, n_het, n_hom and n_miss
+ * stay as they were; every consumer written against this ABI drops it as it drops any row no sample carries
+ * (main.go:558-560) -- bvcf_format_tsv, the dosage rows, the name lists, bvcf_sample_stats, bvcf_pair_stats, bvcf_bed_rows,
+ * bvcf_trio_stats and bvcf_ld_stats see the surviving rows only (the LD window is over the rows that remain).  Line
+ * verdicts, the error list and bvcf_line do not change; bvcf_counters' alleles_ac0 includes the rows taken out.
+ * The decision is exact: the hash places an entry, the row's bytes are compared with the entry's before it counts as found.
+ * The table: entries[4 * i ..] = {tag, off, len, 0} for slot i < capacity, len == 0 = empty; capacity =
+ * bvcf_variant_table_capacity(n) = the smallest power of two >= 2 n, at least 16 (0 for n above BVCF_VARIANT_MAX_ENTRIES);
+ * with h = bvcf_locus_hash(s, len) -- FNV-1a 64, offset basis 0xcbf29ce484222325, prime 0x100000001b3 -- an entry's home
+ * slot is h & (capacity - 1), its tag h >> 32, collisions go to the next free slot (wrapping); its bytes are
+ * blob[off, off + len).  At most BVCF_VARIANT_MAX_ENTRIES distinct entries and less than 4 GiB of them.
+ * bvcf_variant_table_build makes the table on the host from n strings bytes[off[i], off[i] + len[i]) -- duplicates are
+ * stored once, an entry of length 0 is BVCF_E_ARG, a list over the bound BVCF_E_TOO_BIG -- and bvcf_variant_table_free
+ * releases it; bvcf_variant_table_has looks a string up in it with the probe the device runs (1 / 0; -1 for bad arguments).
+ * bvcf_set_variant_table uploads a built table to a ctx (one table serves every ctx of a run); bvcf_set_variant_list is
+ * build + set + free.  Call once, before the first submit, like bvcf_set_site_gate; BVCF_E_BUSY with batches in flight.  A
+ * no-op returning BVCF_OK on a ctx without sample columns.  An empty list with exclude != 0 selects every row: the ctx
+ * then allocates and launches nothing for it, as a ctx on which neither is called; an empty list with exclude == 0 leaves
+ * no row.  bvcf_params and the ABI version do not change with it. */
+#define BVCF_VARIANT_MAX_ENTRIES (1ull << 27)
+typedef struct {
+  const uint32_t *entries; /* [4 * capacity] */
+  uint64_t capacity;
+  const char *blob;
+  uint64_t blob_bytes;
+  uint64_t n;              /* distinct entries */
+} bvcf_variant_table;
+uint64_t bvcf_locus_hash(const char *s, size_t n);
+uint64_t bvcf_variant_table_capacity(uint64_t n);
+int bvcf_variant_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, bvcf_variant_table *out);
+void bvcf_variant_table_free(bvcf_variant_table *t);
+/* the table of a list file's text[0, n) by the file's rules (bvcf_config_variants): one entry per line, a trailing '\r'
+ * dropped, empty lines ignored, a line taken whole otherwise; BVCF_E_TOO_BIG for a line of 4 GiB or a list over the bound */
+int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out);
+int bvcf_variant_table_has(const bvcf_variant_table *t, const char *s, size_t n);
+int bvcf_set_variant_table(bvcf_ctx *ctx, const bvcf_variant_table *t, int exclude);
+int bvcf_set_variant_list(bvcf_ctx *ctx, const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int exclude);
+/* what the list did to a collected batch, from its records alone (host only; no ctx): out = {examined, kept, dropped}.  A
+ * row the site gate took out afterwards counts as kept here.  All zero for a batch without sample columns. */
+void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]);
+
 /* running totals since bvcf_create: {lines_in, lines_ok, alleles_out, alleles_ac0, errs,
  * bytes_in, cmap_bytes, kernel_ns}; alleles_ac0 includes the rows bvcf_set_site_gate took out */
 int bvcf_counters(bvcf_ctx *ctx, uint64_t out[8]);
@@ -588,7 +641,7 @@ typedef struct {
   uint8_t normalize_header;     /* parse.NormalizeHeader restatement ('.' -> '_'), default 1 */
   uint8_t leave_teardown_to_exit; /* bvcf_run_fd: the process exits right after the call (the CLI): skip destroying the
                                    ctxs and unpinning the buffers, the OS reclaims them (~0.1 s of a 0.9 s run) */
-  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct; [1]: BVCF_CONFIG_MORE_GATE */
+  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct; [1]: BVCF_CONFIG_MORE_GATE .. BVCF_CONFIG_MORE_VARIANTS */
   int32_t device;               /* HIP device ordinal */
   uint32_t n_format_threads;    /* 0 = the CPUs the process may use (affinity, cgroup quota), at most 32 */
   uint64_t max_batch_bytes;     /* 0 = 64 MiB (256 MiB of text for a BGZF file inflated on the device) */
@@ -730,6 +783,35 @@ typedef struct {
 } bvcf_config_ld;
 /* the whole struct: bvcf_config_trios_defaults, base.reserved[1] = BVCF_CONFIG_MORE_LD, no paths, window 50, t6 200 000 */
 void bvcf_config_ld_defaults(bvcf_config_ld *c);
+/* Likewise what came after bvcf_config_ld: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_VARIANTS.  bvcf_config_variants_defaults sets that; the five older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_VARIANTS 5
+typedef struct {
+  bvcf_config_ld ld;
+  /* --keepVariants PATH / --excludeVariants PATH: the bvcf_set_variant_table of every ctx of the run.  keep_variants_path
+   * keeps only the rows whose locus string is in the list, exclude_variants_path all the others; NULL or "" = not given;
+   * both given: BVCF_E_ARG.  The list file: one locus string per line, a trailing '\r' is dropped, empty lines are ignored,
+   * duplicates are harmless; a line is taken whole -- no trimming, no columns --, so a .prune.in, a .prune.out or the
+   * second column of a .bim can be fed as they are.  At most BVCF_VARIANT_MAX_ENTRIES distinct entries and less than 4 GiB
+   * of them.  An unreadable file or a list over the bound: BVCF_E_FATAL with one message, before any device work.  An
+   * entry that matches no row is no error (a list may describe more than the file); an empty keep list leaves no rows, an
+   * empty exclude list changes nothing.
+   * The one rule: a run with a list produces, byte for byte, what the run without it produces with the unselected rows
+   * taken out -- the TSV and its BGZF form, the dosage file, plink_prefix's .bed / .bim, sample_stats_path (its counts),
+   * pair_stats_path, mendel_path / mendel_errors_path, and ld_path / ld_prune_prefix, which number the rows that remain
+   * (the window is over the thinned rows).  The log, the sample list and the field-count / FILTER / allele verdicts do not
+   * change.  The list acts before the site gate: a row it takes out is not examined by the gate and not in
+   * site_filter_path's counts.  **Files without sample columns accept the paths and come out unchanged.**  The output
+   * does not depend on devices, batch size or input kind, and the chain a file runs on does not change with a list. */
+  const char *keep_variants_path;
+  const char *exclude_variants_path;
+  /* --variantFilterReport: four lines "name\tcount" -- listed (the distinct entries of the list), then examined, kept,
+   * dropped summed with bvcf_variant_gate_count over the batches of the output.  Opened before any device work, written
+   * at the end of a successful run.  NULL or "" = no report */
+  const char *variant_filter_path;
+} bvcf_config_variants;
+/* the whole struct: bvcf_config_ld_defaults, base.reserved[1] = BVCF_CONFIG_MORE_VARIANTS, no paths */
+void bvcf_config_variants_defaults(bvcf_config_variants *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -62,6 +62,14 @@ int bvcf_bench_deflate_codes(int device, const uint32_t *hist, uint32_t n, uint8
  * ctx without a gate, or when no bvcf_bench_device* call went before */
 int bvcf_bench_gate_kernels(bvcf_ctx *ctx, float ms[2]);
 
+/* bvcf_set_variant_list: k_variant_gate on its own, as bvcf_bench_gate_kernels times the site gate -- the chain of the last
+ * bench block once more on the first slot with both gates off, then the kernel over those records between two HIP events:
+ * *ms.  The same rule for the block's residency.  BVCF_E_ARG on a ctx without a list, or when no bvcf_bench_device* call
+ * went before */
+int bvcf_bench_variant_kernel(bvcf_ctx *ctx, float *ms);
+/* the alleles[] slots k_variant_gate's grid covers in one step (its threads): a batch with more rows takes a second step */
+uint32_t bvcf_bench_variant_gate_stride(const bvcf_ctx *ctx);
+
 /* bvcf_enable_bed_rows: the .bed kernels over the records and class maps the first slot's last bench chain left, with HIP
  * events around them: ms = {k_bed_count + k_bed_scan + k_bed_index (the row index), k_bed_rows}; out[0] = the rows, out[1] = the bytes
  * k_bed_rows wrote (rows * row_bytes).  BVCF_E_ARG on a ctx without bed rows, BVCF_E_CAPACITY when the rows outrun the arena */
