@@ -1682,7 +1682,8 @@ int open_device(bvcf_ctx *c) {
   c->gt_filter_grid = c->n_cu * wgs_per_cu(k_gt_filter, kWgThreads, 0, 4);
   c->gt_subset_grid = c->n_cu * wgs_per_cu(k_gt_subset, kWgThreads, 0, 4);
   int per_cu = wgs_per_cu(k_stream, kWgThreads, 0, 3);
-  // Two waves per SIMD run the scan as fast as three (it is bound by VALU issue).  With more than one batch in
+  // Two waves per SIMD run the scan as fast as three (it is bound by the memory system: its waves wait for their chunk
+  // loads, and a third wave's loads only queue behind the others').  With more than one batch in
   // flight the third wave's registers are better spent on the previous batch's k_head_lean / k_gt / k_finish, which
   // then run beside this kernel instead of waiting for its workgroups to finish (+7 % on the two-slot benchmark).
   if (c->p.n_slots > 1 && per_cu > 2) per_cu = 2;

@@ -187,6 +187,52 @@ __device__ __forceinline__ void flush_stage(const uint8_t *stage, uint8_t *cmap,
   __builtin_amdgcn_wave_barrier();
 }
 
+// ---- k_stream's pending-store log (the pipelined path, bvcf_stream.hip.h)
+// A pipelined line leaves four kinds of result stores: its entry, its head TAB bitmap, ALT #1's class list or dense map.
+// They are not issued per line: they are appended, as 16-byte pieces with a 4-byte tag each (destination array and the
+// offset in it, in pieces), to a log in the part of the wave's stage that lines of <= 16 chunks never touch (zero_stage
+// and flush_stage stay within its first 1 KiB), and k_stream stores the whole log at once (pend_flush, see there).
+constexpr uint32_t kPendBase = 1024u;   // the log's pieces: stage bytes [1024, 3424)
+constexpr uint32_t kPendPieces = 150u;  // an average cohort line leaves 18, a dense-map line of 2 504 samples 44
+constexpr uint32_t kPendTags = kPendBase + 16u * kPendPieces;  // their tags: [3424, 4024)
+constexpr uint32_t kPendEntries = 0u << 30, kPendHeadBits = 1u << 30, kPendCmap = 2u << 30;  // tag: array | piece offset
+constexpr uint32_t kPendOffMask = (1u << 30) - 1u;
+static_assert(kPendTags + 4u * kPendPieces <= kStageBytes, "the log lives in the stage");
+struct PendLog {
+  u32x4 *data;     // the pieces
+  uint32_t *tag;   // ... and their tags
+  uint32_t n;      // pieces waiting (wave-uniform); the caller keeps room for a whole line
+  uint32_t cm16;   // the class-map slot of the line being scanned: its offset in the arena, in pieces
+};
+// The lane index for the log's appends and its flush, as a value the compiler takes for new at every use: k_stream's
+// pipeline is instantiated ten times, and every mask and address derived from a lane index that is known not to change
+// is computed once, ahead of the kernel's outer loop, and kept -- in scalar registers spilled to vector lanes and in
+// vector registers -- through all ten (k_stream went from 145 vector registers to 256 and 126 accumulation registers).
+__device__ __forceinline__ uint32_t pend_lane() {
+  uint32_t l = (uint32_t)lane_id();
+  asm volatile("" : "+v"(l));
+  return l;
+}
+// a finished map of n_bytes (a multiple of 16, 1 KiB at most) from the start of the stage
+__device__ __forceinline__ void pend_map(PendLog &pl, const uint8_t *stage, uint32_t n_bytes) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const uint32_t lane = pend_lane(), np = n_bytes / 16u;
+  if (lane < np) {
+    pl.data[pl.n + lane] = *reinterpret_cast<const u32x4 *>(stage + 16u * lane);
+    pl.tag[pl.n + lane] = kPendCmap | (pl.cm16 + lane);
+  }
+  pl.n = bcast0(pl.n + np);
+}
+// a class list: `word` is the lane's dword of it, n_words of them count; zeros fill the last piece (the slot is the
+// line's own, and the bytes behind a list mean nothing)
+__device__ __forceinline__ void pend_list(PendLog &pl, uint32_t word, uint32_t n_words) {
+  const uint32_t lane = pend_lane(), np = (n_words + 3u) / 4u;
+  if (lane < 4u * np) reinterpret_cast<uint32_t *>(pl.data + pl.n)[lane] = lane < n_words ? word : 0u;
+  if (lane < np) pl.tag[pl.n + lane] = kPendCmap | (pl.cm16 + lane);
+  pl.n = bcast0(pl.n + np);
+}
+
 // The lane's four fields at once, one byte lane per field.  t[q] = field word ^ "0<sep>0<TAB>" with the frame bytes
 // already checked: byte 0 / byte 2 are the allele characters ^ '0' (0..9 for digits, 0x1E for '.'; below 32 whenever
 // the frame test passes, which makes the carry-free zero-byte test ~((x + 0x7F..) | x) & 0x80.. exact).
@@ -262,9 +308,10 @@ __device__ __forceinline__ void list_to_stage(RawList *sp, uint32_t n, uint32_t 
 
 // one 1 KiB chunk (this lane's 4 fields) of a regular region
 // sp (optional, lines of <= kStageChunks chunks only): the line is in list mode while acc.n_sp < kDenseMode
+// pl (optional, lines of <= 16 chunks only): the finished map goes to the pending-store log instead of the class-map arena
 __device__ __forceinline__ void fast_chunk(u32x4 v, uint32_t c, uint32_t n_chunks, uint32_t ns, uint32_t kref,
                                            uint32_t table, uint8_t *cmap, uint8_t *stage, uint32_t stride,
-                                           uint32_t term_xor, FastAcc &acc, RawList *sp = nullptr) {
+                                           uint32_t term_xor, FastAcc &acc, RawList *sp = nullptr, PendLog *pl = nullptr) {
   const int lane = lane_id();
   const uint32_t f0 = c * 256u + 4u * lane;  // sample index of the lane's first dword
   uint32_t t[4] = {v.x ^ kref, v.y ^ kref, v.z ^ kref, v.w ^ kref};
@@ -337,7 +384,10 @@ __device__ __forceinline__ void fast_chunk(u32x4 v, uint32_t c, uint32_t n_chunk
     }
   }
   if (cmap && !(sp && acc.n_sp < kDenseMode) && ((c % kStageChunks) == kStageChunks - 1u || c + 1 == n_chunks)) {
-    flush_stage(stage, cmap, c - (c % kStageChunks), ((c % kStageChunks) + 1u) * 64u, stride);
+    if (pl)
+      pend_map(*pl, stage, min(((c % kStageChunks) + 1u) * 64u, stride));
+    else
+      flush_stage(stage, cmap, c - (c % kStageChunks), ((c % kStageChunks) + 1u) * 64u, stride);
     if (c + 1 != n_chunks) zero_stage(stage, n_chunks - (c + 1u));
   }
 }
@@ -402,7 +452,12 @@ __device__ __forceinline__ void write_further_lists(const Alleles4 &g, uint32_t 
 // 0 and 1 (fast_chunk, list_to_stage), in scan order.  Returns 1 << 1 when the entries are dots only (nobody carries a
 // further allele), kRawEnc when they were saved for k_gt (raw_area: the slots behind the line's own, null when the
 // wave has none to spare), 0 otherwise (k_gt reads the line).
-__device__ __forceinline__ uint32_t finish_dense(const RawList *sp, uint32_t n, uint8_t *raw_area) {
+// before_direct(): called ahead of the stores made here (k_stream's pipelined path empties its pending-store log first)
+struct NoPendingStores {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <class F = NoPendingStores>
+__device__ __forceinline__ uint32_t finish_dense(const RawList *sp, uint32_t n, uint8_t *raw_area, F before_direct = F()) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   u32x4 e = {0u, 0u, 0u, 0u};
@@ -414,6 +469,7 @@ __device__ __forceinline__ uint32_t finish_dense(const RawList *sp, uint32_t n, 
   const Alleles4 g = gather4(e.x, e.y, e.z, e.w);
   if (highest_allele(g, e.x | e.y | e.z | e.w) == 1u) return 1u << 1;
   if (!raw_area) return 0u;
+  before_direct();
   raw_save(raw_area, n, e, idx);
   return kRawEnc;
 }
@@ -430,8 +486,12 @@ __device__ __forceinline__ uint32_t finish_dense(const RawList *sp, uint32_t n, 
 //                                    no spare slots
 // Either way a multiallelic line whose non-reference samples fit the raw list is read once (the reference rescans the
 // line once per allele, main.go:549-556).
+// pl (optional, k_stream's pipelined path): ALT #1's list or map goes to the pending-store log; before_direct() runs ahead
+// of the stores that are still made here (further alleles' lists, raw_save).
+template <class F = NoPendingStores>
 __device__ __forceinline__ uint32_t finish_list(const RawList *sp, FastAcc &acc, uint8_t *cmap, uint32_t max_k,
-                                                uint8_t *stage, uint32_t n_chunks, uint32_t stride, uint8_t *raw_area) {
+                                                uint8_t *stage, uint32_t n_chunks, uint32_t stride, uint8_t *raw_area,
+                                                PendLog *pl = nullptr, F before_direct = F()) {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int lane = lane_id();
@@ -456,21 +516,29 @@ __device__ __forceinline__ uint32_t finish_list(const RawList *sp, FastAcc &acc,
     // a dense map of ALT #1 after all
     zero_stage(stage, n_chunks);
     if ((uint32_t)lane < n) stage[idx % kStageBytes] = (uint8_t)byte1;
-    flush_stage(stage, cmap, 0u, n_chunks * 64u, stride);
+    if (pl)
+      pend_map(*pl, stage, min(n_chunks * 64u, stride));
+    else
+      flush_stage(stage, cmap, 0u, n_chunks * 64u, stride);
     acc.n_sp = bcast0(kDenseMode);
     if (kmax == 1u) return 1u << 1;  // nobody carries a further allele
     // (Tried: dense maps of ALT #2..#4 grown beside ALT #1's in the stage during the scan -- no rescans at all, but
-    // k_stream, which is bound by instruction issue, took 23 % longer on configs[3] and 1-5 % on biallelic files, more
+    // k_stream took 23 % longer on configs[3] and 1-5 % on biallelic files, more
     // than k_gt's rescans cost; class lists and maps of the further alleles built here from the entries: +1.4 %.)
     if (!raw_area) return 0u;
+    before_direct();
     raw_save(raw_area, n, e, idx);
     return kRawEnc;
   }
+  if (kmax > 1u) before_direct();
   write_further_lists(g, idx, kmax, cmap);  // (the list of ALT #k at cmap + 64 * (k - 1))
   // the list of ALT #1: count, then the entries (an entry may carry a zero byte: a lane whose fields only hold other
   // alleles)
   const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)((idx << 8) | byte1), 0x138, 0xF, 0xF, false);  // wave_shr:1
-  if ((uint32_t)lane <= n) __builtin_nontemporal_store(lane == 0 ? n : prev, reinterpret_cast<uint32_t *>(cmap) + lane);
+  if (pl)
+    pend_list(*pl, lane == 0 ? n : prev, n + 1u);
+  else if ((uint32_t)lane <= n)
+    __builtin_nontemporal_store(lane == 0 ? n : prev, reinterpret_cast<uint32_t *>(cmap) + lane);
   return 1u | ((kmax - 1u) << 1);
 }
 

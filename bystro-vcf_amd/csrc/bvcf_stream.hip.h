@@ -117,6 +117,25 @@ __device__ __forceinline__ uint32_t head_window16(const KernelArgs &a, u32x4 v, 
 
 constexpr int kPipeChunks = 10;  // chunk registers of the cross-line pipeline: lines of <= 2560 samples
 
+// ---- when the pending-store log (PendLog, bvcf_gtscan.hip.h) of the pipelined path is stored: pend_flush
+//   * at the end of a line after which the largest line of the geometry would no longer fit,
+//   * on every exit from the pipeline, and ahead of every store the pipeline still makes directly (further alleles'
+//     lists, raw_save), so that the log never outlives the order the stores had,
+//   * when the 100 MHz wall clock, which all waves of the chip read alike, has crossed a multiple of the epoch since
+//     the wave last looked: all waves then write within the same few microseconds, and between epochs the memory
+//     controllers see reads only.
+// Off the per-line path the stores also leave the vmcnt queue the chunk loads wait on.
+constexpr uint32_t kPendRounds = (kPendPieces + kWave - 1u) / kWave;
+static_assert(kPipeChunks <= 16, "pipelined lines keep to the stage's first 1 KiB");
+static_assert(sizeof(StreamEntry) == 32, "an entry is two pieces");
+// epoch in ticks of the wall clock (100 MHz); 0 = no clock: flush when full and at exits only.  Measured at 8, 16 and 32 us
+// and without the clock (profiles/k_stream_pending_stores.txt); experiment builds choose with -DBVCF_EXP_PEND_EPOCH_US=n
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_EPOCH_US)
+constexpr uint32_t kPendEpochTicks = 100u * (BVCF_EXP_PEND_EPOCH_US);
+#else
+constexpr uint32_t kPendEpochTicks = 1600u;
+#endif
+
 // -DBVCF_EXP_TIMES: per-wave start/end wall clock, hardware placement and time per pipeline phase
 // (s_memtime stamps), read back through bvcf_debug_* by tools/wave_times.py.  Not part of the product.
 #ifdef BVCF_EXP_TIMES
@@ -173,10 +192,10 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
   // a search for its first line start (those bytes are the previous wave's last line).  Entries
   // stay per tile: the quota argument is about bytes, not about who scans them.
   // (Claiming smaller runs from a counter instead evens out the waves' finish times but costs more
-  // than it returns: every run start is a chain of dependent loads.  The kernel is bound by VALU
-  // issue, not by the slowest wave: a SIMD arbitrates by age, so with equal runs the waves of the three
-  // dispatch rounds finish at 161 / 196 / 216 us of a 240 us kernel, but runs weighted by those speeds
-  // changed nothing -- two waves keep a SIMD as busy as three.)
+  // than it returns: every run start is a chain of dependent loads.  The kernel is bound by the memory
+  // system -- its waves wait for their chunk loads, DESIGN.md section 3.4 --, not by the slowest wave: a SIMD
+  // arbitrates by age, so with equal runs the waves of the three dispatch rounds finish at 161 / 196 / 216 us
+  // of a 240 us kernel, but runs weighted by those speeds changed nothing.)
   // Balanced: the first n_tiles % n_waves waves walk one tile more than the others (a plain ceil() split left 5 %
   // of the waves without work on the benchmark's 20 332 tiles).
   const uint32_t q_tiles = a.n_tiles / n_waves, r_tiles = a.n_tiles % n_waves;
@@ -216,10 +235,36 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
     }
     return cmap_of(a, cm_next, true);
   };
+  // the pending-store log
+  PendLog pl = {reinterpret_cast<u32x4 *>(stage + kPendBase), reinterpret_cast<uint32_t *>(stage + kPendTags), 0u, 0u};
+  uint32_t pend_epoch = 0;
+  // pieces of the largest line of the pipeline: entry, bitmap, and a map (a list is four pieces at most)
+  const uint32_t pend_line_max = 4u + max(4u, min(n_chunks * 64u, a.cmap_stride) / 16u);
+  // Lane i stores pieces i, i + 64 and i + 128.  A fixed number of masked rounds, not a loop over the count: the stores of a
+  // flush are then a count hipcc's s_waitcnt insertion knows (see run_pipeline on the unconditional chunk loads).
+  auto pend_flush = [&]() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (uint32_t r = 0; r < kPendRounds; r++) {
+      const uint32_t i = pend_lane() + r * kWave;
+      if (i < pl.n) {
+        const u32x4 v = pl.data[i];
+        const uint32_t tag = pl.tag[i];
+        uint8_t *dst = tag >= kPendCmap ? a.cmap
+                                        : (tag >= kPendHeadBits ? reinterpret_cast<uint8_t *>(a.head_bits) : reinterpret_cast<uint8_t *>(a.entries));
+        __builtin_nontemporal_store(v, reinterpret_cast<u32x4 *>(dst + (size_t)(tag & kPendOffMask) * 16u));
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    pl.n = 0;
+  };
   // list a line (in input order) in the tile it starts in
   // bits_ok: `bits` is the TAB mask of the line's head window (head_window16), one 16-bit piece per lane 0..15
+  // pend: entry and bitmap go to the pending-store log, which has room for their four pieces
   auto commit = [&](uint32_t ls, uint32_t cend, const GtStats &st, bool deferred, uint32_t cm_off, bool bits_ok = false,
-                    uint32_t bits = 0u, uint32_t n_slots = 1u) {
+                    uint32_t bits = 0u, uint32_t n_slots = 1u, bool pend = false) {
     // (a deferred line gets its class map with its k_gt task, not here)
     while (ls >= (tile + 1) * T) {  // ls moved into a later tile of the run
       if (lane == 0) a.census[tile] = n_local;
@@ -231,19 +276,34 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
       if (lane == 0) a.counters->pad[0] = 1;  // cannot happen: see tile_quota
       return;
     }
-    if (lane == 0) {
-      StreamEntry en;
-      en.ls = ls;
-      en.len = (cend - ls) | (bits_ok ? kHasHeadBits : 0u);
-      en.ac = st.ac;
-      en.an = st.an;
-      en.n_het = st.n_het;
-      en.n_hom = st.n_hom;
-      en.n_miss = deferred ? kDeferred : st.n_miss;
-      en.cmap_off = cm_off;
-      a.entries[(size_t)tile * a.tile_quota + n_local] = en;
+    const size_t ei = (size_t)tile * a.tile_quota + n_local;
+    StreamEntry en;
+    en.ls = ls;
+    en.len = (cend - ls) | (bits_ok ? kHasHeadBits : 0u);
+    en.ac = st.ac;
+    en.an = st.an;
+    en.n_het = st.n_het;
+    en.n_hom = st.n_hom;
+    en.n_miss = deferred ? kDeferred : st.n_miss;
+    en.cmap_off = cm_off;
+    if (pend && 2u * ei + 1u <= kPendOffMask) {  // (an entry the tag cannot address is stored directly)
+      u32x4 *pd = pl.data + pl.n;
+      const uint32_t pln = pend_lane();
+      if (pln == 0) {
+        pd[0] = u32x4{en.ls, en.len, en.ac, en.an};
+        pd[1] = u32x4{en.n_het, en.n_hom, en.n_miss, en.cmap_off};
+      }
+      if (pln < 2) pl.tag[pl.n + pln] = kPendEntries | (2u * (uint32_t)ei + pln);
+      pl.n += 2u;
+      if (bits_ok) {
+        if (pln < 16) reinterpret_cast<uint16_t *>(pd + 2)[pln] = (uint16_t)bits;
+        if (pln < 2) pl.tag[pl.n + pln] = kPendHeadBits | (2u * (uint32_t)ei + pln);
+        pl.n += 2u;
+      }
+    } else {
+      if (lane == 0) a.entries[ei] = en;
+      if (bits_ok && lane < 16) a.head_bits[ei * 16u + (uint32_t)lane] = (uint16_t)bits;
     }
-    if (bits_ok && lane < 16) a.head_bits[((size_t)tile * a.tile_quota + n_local) * 16u + (uint32_t)lane] = (uint16_t)bits;
     n_local++;
     if (maps && !deferred) cm_next += n_slots;
   };
@@ -328,6 +388,7 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
           STAMP(1);
           // ---- scan A, re-issuing each register for B
           const uint32_t cmA = bcast0(map_slot());  // (wave-uniform by construction; tell the compiler)
+          pl.cm16 = cmA / 16u;
           uint8_t *cm = cmA != BVCF_NO_CMAP ? a.cmap + cmA : nullptr;
           // the line starts in list mode (nothing to zero, nothing classified per chunk) when a list fits the map's slot
 #ifdef BVCF_EXP_NO_SPARSE
@@ -351,7 +412,8 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
             if ((uint32_t)g < nc) {
               const uint32_t nx = (uint32_t)g + 1u < nc
                                       ? (uint32_t)__builtin_amdgcn_readfirstlane(va[g + 1 < kPipeChunks ? g + 1 : g].x) : 0u;
-              fast_chunk(realign(va[g], nx, rA), g, nc, ns, kref, table1, cm, stage, a.cmap_stride, term_xor, acc, sparse_ok ? sparse : nullptr);
+              fast_chunk(realign(va[g], nx, rA), g, nc, ns, kref, table1, cm, stage, a.cmap_stride, term_xor, acc, sparse_ok ? sparse : nullptr,
+                         &pl);
             }
             va[g] = chunk_at(s_next, g);
           }
@@ -369,14 +431,15 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
             if (cm_next + 1u + raw_slots + reserve > cm_end || cmap_of(a, cm_next + raw_slots, true) == BVCF_NO_CMAP) return nullptr;
             return cm + a.cmap_stride;
           };
+          auto before_direct = [&]() { pend_flush(); };
           if (sparse_ok && acc.n_sp < kDenseMode) {
             enc = finish_list(sparse, acc, cm, min(kListAlleles, a.cmap_stride / (4u * kSparseWords)), stage, nc, a.cmap_stride,
-                              acc.n_sp > BVCF_CMAP_SPARSE_MAX ? raw_area() : nullptr);
+                              acc.n_sp > BVCF_CMAP_SPARSE_MAX ? raw_area() : nullptr, &pl, before_direct);
           } else if (sparse_ok && acc.n_oth == 0u) {
             enc = 1u << 1;
           } else if (sparse_ok && acc.n_oth < kDenseMode) {
             // the lanes that saw a digit >= 2 or a dot were listed on the way: k_gt settles the further alleles from them
-            enc = finish_dense(sparse, acc.n_oth, raw_area());
+            enc = finish_dense(sparse, acc.n_oth, raw_area(), before_direct);
           }
           if (enc == kRawEnc) n_slots += raw_slots;
           if (__any(acc.bad != 0)) {
@@ -389,7 +452,15 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
           finish_stats(acc, &st);
           seen++;
           // (offsets are multiples of 16: the low bits tell k_head what finish_list left in the slot, see there)
-          commit(pA, peA, st, false, cmA == BVCF_NO_CMAP ? cmA : cmA | enc, bitsA, mtA, n_slots);
+          commit(pA, peA, st, false, cmA == BVCF_NO_CMAP ? cmA : cmA | enc, bitsA, mtA, n_slots, true);
+          // the log leaves at the epoch, or when the largest line there can be would not fit behind this one
+          bool leave = pl.n + pend_line_max > kPendPieces;
+          if constexpr (kPendEpochTicks != 0u) {
+            const uint32_t ep = (uint32_t)wall_clock64() / kPendEpochTicks;
+            leave |= ep != pend_epoch;
+            pend_epoch = ep;
+          }
+          if (leave) pend_flush();
           p = peA + 1u;
           if (!b_ok) {
             s_begin = kNone;  // nothing pending: rediscover from p
@@ -421,6 +492,7 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
         default: run_pipeline(std::integral_constant<int, 10>{}); break;
       }
       static_assert(kPipeChunks == 10, "the dispatch above covers 1..10 chunks");
+      pend_flush();  // every exit: a line that was not regular after all, no B, the run's end
       if (s_begin == kNone) continue;
       // fall through with (p, s_begin) of the line that failed the regular scan
     } else if (pred + a.eol_chars <= nb) {
