@@ -1,0 +1,1242 @@
+// bvcf_analyses.hip.h — the host half of the analyses behind k_finish: the site gate and the variant gate, the row index with
+// the .bed rows, the trios and the LD pairs on it, the per-sample and the pair counts.  Per analysis one struct of what a slot
+// owns and one of what the ctx owns, then its functions next to each other: allocate for the ctx's current capacities,
+// ready, kernel args, launch, its part of collect, its entries of the C-ABI, its bench hook.  The kernels are in the
+// analyses' own headers.
+// Part of bvcf_core.hip's one translation unit, which includes it twice: in front of Slot and bvcf_ctx for the state -- they
+// hold a member per analysis --, and behind them for the functions, which read both.
+#ifndef BVCF_ANALYSES_STATE
+#define BVCF_ANALYSES_STATE
+
+namespace {
+
+// An arena with a bound of its own: a device counter of what a batch put (or would have put) into it with its pinned copy,
+// the arena with -- optionally -- its pinned copy, and the capacity both were allocated with, in units of kPer elements.
+// The bound is the ctx's.  A batch that outruns the arena comes back BVCF_E_CAPACITY with the need reported, bvcf_reserve_*
+// grows the bound with nothing in flight, and the batch is submitted again.
+template <class T, unsigned kPer = 1, unsigned kPad = 0>
+struct Arena {
+  DevBuf<unsigned long long> d_total;
+  PinBuf<unsigned long long> h_total;
+  DevBuf<T> d;
+  PinBuf<T> h;
+  uint64_t cap = 0;
+  hipError_t alloc_total() {
+    if (d_total) return hipSuccess;
+    const hipError_t e = d_total.alloc(1);
+    return e != hipSuccess ? e : h_total.alloc(1);
+  }
+  // room for `bound` units: the capacity is zeroed before anything is allocated and set once everything is there, so a slot
+  // whose allocation failed starts over at its next use
+  hipError_t grow_to(uint64_t bound, bool pinned = true) {
+    if (cap >= bound && (h || !pinned)) return hipSuccess;
+    cap = 0;
+    hipError_t e = d.alloc((size_t)kPer * bound + kPad);
+    if (e == hipSuccess && pinned) e = h.alloc((size_t)kPer * bound + kPad);
+    if (e == hipSuccess) cap = bound;
+    return e;
+  }
+  bool fits(uint64_t need) const { return need <= cap; }
+  hipError_t copy_total(hipStream_t st) { return hipMemcpyAsync(h_total, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, st); }
+};
+
+// bvcf_set_site_gate on a file with samples, some criterion not neutral: k_site_gate / k_site_hwe behind k_finish
+// (bvcf_sitegate.hip.h).  With hwe_p a slot holds [0] the number of rows left to k_site_hwe, then their slots (follows max_alleles)
+struct SiteGateSlot {
+  DevBuf<uint32_t> list;
+};
+struct SiteGateCtx {
+  bool on = false;
+  bvcf_site_gate g{};
+};
+
+// bvcf_set_variant_list / bvcf_set_variant_table on a file with samples: k_variant_gate behind k_finish, in front of the
+// site gate; the hash set (bvcf_variantlist.hip.h) is the ctx's, read by the batches of every slot
+struct VariantGateCtx {
+  bool on = false;
+  uint32_t exclude = 0, mask = 0;
+  DevBuf<VariantEntry> entries;
+  DevBuf<uint8_t> blob;
+};
+
+// the row index the .bed rows, the trios and the LD pairs share (bvcf_bedrows.hip.h), built once when any of them is on:
+// the first row of every line (follows max_lines) and a row's map (follows max_alleles); the batch's row count is the
+// counter of the .bed arena
+struct RowIndexSlot {
+  DevBuf<uint32_t> base, tile;
+  DevBuf<uint2> src;
+};
+
+// bvcf_enable_bed_rows on a file with samples (bvcf_bedrows.hip.h): k_bed_count / k_bed_scan / k_bed_index / k_bed_rows at the
+// end of every chain.  A slot holds the batch's row count and the arena of the packed rows with its pinned copy, a pad of
+// 16 bytes behind the bound.  The arena is shared: the LD pairs read the fileset's rows on the
+// device, and only the fileset has a pinned copy of it.  cap is what a slot's arena holds (bvcf_reserve_bed_rows grows it),
+// last the batch collected last (bvcf_bed_rows)
+struct BedSlot {
+  Arena<uint8_t, 1, 16> rows;
+};
+struct BedCtx {
+  bool asked = false, on = false;
+  uint64_t cap = 0;
+  bvcf_bed_rows_info last{};
+};
+
+// bvcf_enable_trios on a file with samples and at least one trio (bvcf_mendel.hip.h): k_trio_count / k_trio_scan / k_trio_fill
+// at the end of every chain, behind the row index.  A slot holds the batch's [T][3] counts with their pinned copy, the events
+// per row (follow max_alleles), the batch's event count and the arena of the events with its pinned copy.  cap is what a
+// slot's arena holds, in events (bvcf_reserve_trio_events grows it), last the batch collected last (bvcf_trio_stats)
+struct TrioSlot {
+  DevBuf<uint32_t> counts, rowev;
+  PinBuf<uint32_t> h_counts;
+  Arena<uint2> ev;
+};
+struct TrioCtx {
+  bool asked = false, on = false;
+  uint32_t n = 0;
+  DevBuf<uint32_t> trios;
+  uint64_t cap = 0;
+  bvcf_trio_info last{};
+};
+
+// bvcf_enable_ld on a file with samples (bvcf_ld.hip.h): k_bed_rows (once, shared with the fileset), k_ld_keys, k_ld_pairs /
+// k_ld_scan / k_ld_pairs at the end of every chain, behind the same row index.  A slot holds a row's chrom key and its events
+// (follow max_alleles), the batch's event count, the arena of the events (8 words each) with its pinned copy, and the pinned
+// copy of the batch's first and last `window` rows.  cap is what a slot's arena holds, in events (bvcf_reserve_ld_events
+// grows it), last the batch collected last (bvcf_ld_stats)
+struct LdSlot {
+  DevBuf<uint4> key;
+  DevBuf<uint32_t> rowev;
+  Arena<uint32_t, 8> ev;
+  PinBuf<uint8_t> h_edge;
+};
+struct LdCtx {
+  bool asked = false, on = false;
+  uint32_t window = 0, t6 = 0;
+  uint64_t cap = 0;
+  bvcf_ld_info last{};
+};
+
+// bvcf_params.want_sample_stats (bvcf_samplestats.hip.h): the row lists (follow max_alleles; the pair counts read them too),
+// the batch's counts, the totals
+struct SampleStatsSlot {
+  DevBuf<uint2> dense, sparse;
+  DevBuf<uint32_t> ctr, part, sp;
+  DevBuf<unsigned long long> acc;
+};
+
+// bvcf_enable_pair_stats on a file with samples (bvcf_pairstats.hip.h): the pair counts behind every chain.  A slot holds the
+// bit planes of the dense rows' tiles (follow the row lists) and the batch's tables.  The totals are the ctx's: the folds of
+// the slots' batches follow one another through ev_fold
+struct PairStatsSlot {
+  DevBuf<unsigned long long> planes;
+  uint64_t cap_tiles = 0;
+  DevBuf<uint32_t> bt;
+};
+struct PairStatsCtx {
+  bool asked = false, on = false, folded = false;
+  uint32_t split = 1;
+  DevBuf<unsigned long long> tot;
+  Event ev_fold;
+};
+
+}  // namespace
+
+#else  // ---- the functions, behind Slot, bvcf_ctx and HIP_TRY
+
+namespace {
+
+KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes);
+int alloc_results(bvcf_ctx *c, Slot &s);
+void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot);
+
+// the per-sample, pair and trio counts, the .bed rows and the LD pairs are made from the class maps on the device: the
+// maps are made whether or not the caller wants them on the host
+bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->bed.on || c->trio.on || c->ld.on; }
+
+// "<what> with batches in flight": what every call that changes what the slots hold says when it comes too early
+int refuse_in_flight(bvcf_ctx *c, const char *what) {
+  if (!c->in_flight) return BVCF_OK;
+  c->err = std::string(what) + " with batches in flight";
+  return BVCF_E_BUSY;
+}
+
+// A launch list takes an optional array of events and records one where a step ends and the next begins: the bench hooks
+// time the lists the product runs.  A hook starts with nothing in flight and its analysis there (`missing`: what to say
+// when it is not), and ends with the launches gone through and the stream drained: ms[k] is from event k to event k + 1
+void mark(const Event *&ev, hipStream_t st) {
+  if (ev) hipEventRecord(*ev++, st);
+}
+template <size_t N>
+int start_hook(bvcf_ctx *c, const char *what, bool there, const char *missing, Event (&ev)[N]) {
+  if (const int rc = refuse_in_flight(c, what)) return rc;
+  if (!there) {
+    c->err = std::string(what) + ": " + missing;
+    return BVCF_E_ARG;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &e : ev) HIP_TRY(c, e.create());
+  return BVCF_OK;
+}
+template <size_t N>
+int finish_hook(bvcf_ctx *c, Event (&ev)[N], hipStream_t st, float *ms) {
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(st));
+  for (size_t k = 0; k + 1 < N; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  return BVCF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- the gates
+
+// bvcf_set_site_gate with hwe_p: the list of the rows left to k_site_hwe (follows max_alleles) -- for a slot that exists
+// when the gate is set, and again whenever alloc_results sizes the slot anew
+static int alloc_gate_list(bvcf_ctx *c, Slot &s) {
+  if (c->gate.on && c->gate.g.hwe_p > 0.0) HIP_TRY(c, s.gate.list.alloc(c->max_alleles + 1));
+  return BVCF_OK;
+}
+
+static SiteGateArgs make_gate_args(bvcf_ctx *c, Slot &s) {
+  SiteGateArgs ga{};
+  ga.g = c->gate.g;
+  if (c->gate.g.hwe_p > 0.0 && s.gate.list) {
+    ga.ctr = s.gate.list;
+    ga.list = s.gate.list + 1;
+    ga.list_cap = (uint32_t)(s.gate.list.size() - 1);
+  }
+  return ga;
+}
+
+// bvcf_set_site_gate: right behind k_finish, in front of every kernel that reads a record's ac -- the rows that fail are
+// taken out (bvcf_sitegate.hip.h); k_site_hwe settles the rows whose exact test is too long for one thread
+static void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot, const Event *ev = nullptr) {
+  if (!c->gate.on || !slot) return;
+  const SiteGateArgs ga = make_gate_args(c, *slot);
+  if (ga.list) hipMemsetAsync(ga.ctr, 0, sizeof(uint32_t), st);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_site_gate, dim3(c->n_cu * kGateListWgs), dim3(kWgThreads), 0, st, a, ga);
+  mark(ev, st);
+  if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
+}
+
+void bvcf_site_gate_defaults(bvcf_site_gate *g) {
+  if (!g) return;
+  memset(g, 0, sizeof *g);
+  g->size = (uint32_t)sizeof *g;
+  g->max_maf = 1.0;
+  g->max_missing = 1.0;
+}
+
+// the ranges of bvcf_site_gate (a NaN fails every comparison)
+static bool site_gate_in_range(const bvcf_site_gate *g) {
+  return g->size == sizeof *g && g->min_mac <= BVCF_MAX_THRESHOLD && g->min_maf >= 0.0 && g->min_maf <= 0.5 && g->max_maf >= 0.0 &&
+         g->max_maf <= 1.0 && g->max_missing >= 0.0 && g->max_missing <= 1.0 && g->hwe_p >= 0.0 && g->hwe_p <= 1.0;
+}
+
+int bvcf_set_site_gate(bvcf_ctx *c, const bvcf_site_gate *g) {
+  if (!c) return BVCF_E_ARG;
+  if (!g || !site_gate_in_range(g)) {
+    c->err = "bvcf_set_site_gate: want size = sizeof(bvcf_site_gate), min_maf in [0, 0.5], max_maf, max_missing and hwe_p in [0, 1], "
+             "min_mac at most " + std::to_string(BVCF_MAX_THRESHOLD);
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_site_gate")) return rc;
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
+  c->gate.g = *g;
+  c->gate.on = g->min_maf > 0.0 || g->max_maf < 1.0 || g->min_mac > 0u || g->max_missing < 1.0 || g->hwe_p > 0.0;
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)  // (the slots were sized by bvcf_create, before there was a gate)
+    if (const int rc = alloc_gate_list(c, s)) return rc;
+  return BVCF_OK;
+}
+
+void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]) {
+  if (!out) return;
+  for (int q = 0; q < 7; q++) out[q] = 0;
+  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    for (uint32_t j = 0; j < L.n_rec; j++) {
+      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
+      const uint32_t bits = A.pad[0];
+      if (!bits && !A.ac) continue;  // (a row no sample carries: not examined)
+      out[0]++;
+      if (!bits) out[1]++;
+      for (int q = 0; q < 5; q++) out[2 + q] += (bits >> q) & 1u;
+    }
+  }
+}
+
+int bvcf_site_gate_verdict(const bvcf_site_gate *g, uint32_t S, const uint32_t counts[5]) {
+  if (!g || !counts || !site_gate_in_range(g)) return -1;
+  return (int)site_gate_verdict(*g, S, counts[0], counts[1], counts[2], counts[3], counts[4]);
+}
+
+double bvcf_hwe_exact(uint32_t het, uint32_t hom, uint32_t other) { return hwe_exact_seq(het, hom, other); }
+uint32_t bvcf_hwe_inline_terms(void) { return kHweInlineTerms; }
+
+// the chain of the last bench block once more with the variant gate (and the site gate) off: the records as k_finish
+// leaves them, for the gates' hooks
+static int launch_ungated(bvcf_ctx *c, Slot &s, KernelArgs *a, bool variants_too) {
+  if (const int rc = alloc_results(c, s)) return rc;
+  s.s2_parity ^= 1u;
+  *a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
+  const bool gate_on = c->gate.on, variants_on = c->variants.on;
+  c->gate.on = false;
+  if (variants_too) c->variants.on = false;
+  launch_chain(c, *a, s.stream, nullptr, nullptr, &s);
+  c->gate.on = gate_on;
+  c->variants.on = variants_on;
+  return BVCF_OK;
+}
+
+int bvcf_bench_gate_kernels(bvcf_ctx *c, float ms[2]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Event ev[3];
+  if (const int rc = start_hook(c, "bvcf_bench_gate_kernels", c->gate.on && c->bench_src,
+                                "the ctx has no site gate, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  Slot &s = c->slots[0];
+  KernelArgs a;
+  if (const int rc = launch_ungated(c, s, &a, false)) return rc;
+  launch_site_gate(c, a, s.stream, &s, ev);  // (ev[0] behind the memset, ev[1] behind k_site_gate)
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  const int rc = finish_hook(c, ev, s.stream, ms);
+  if (!rc && !make_gate_args(c, s).list) ms[1] = 0.f;
+  return rc;
+}
+
+int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p) {
+  if (!triples || !p) return BVCF_E_ARG;
+  if (!n) return BVCF_OK;
+  if (hipSetDevice(device) != hipSuccess) return BVCF_E_NODEV;
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) return BVCF_E_HIP;
+  DevBuf<uint32_t> d_t;
+  DevBuf<double> d_p;
+  if (d_t.alloc(3ull * n) != hipSuccess || d_p.alloc(n) != hipSuccess) return BVCF_E_NOMEM;
+  if (hipMemcpy(d_t, triples, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return BVCF_E_HIP;
+  const uint32_t grid = std::min<uint32_t>((n + kWavesPerWg - 1) / kWavesPerWg, (uint32_t)n_cu * kHweWgs);
+  hipLaunchKernelGGL(k_hwe_probe, dim3(grid), dim3(kWgThreads), 0, 0, (const uint32_t *)d_t, n, (double *)d_p);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return BVCF_E_HIP;
+  return hipMemcpy(p, d_p, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
+}
+
+static VariantGateArgs make_variant_args(const bvcf_ctx *c) {
+  VariantGateArgs va{};
+  va.entries = c->variants.entries;
+  va.blob = c->variants.blob;
+  va.mask = c->variants.mask;
+  va.exclude = c->variants.exclude;
+  return va;
+}
+
+static uint32_t variant_gate_grid(const bvcf_ctx *c) { return (uint32_t)c->n_cu * kVariantGateWgs; }
+
+// bvcf_set_variant_list: right behind k_finish and in front of the site gate -- the rows the list does not select are
+// taken out (bvcf_variantlist.hip.h) before anything examines them
+static void launch_variant_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st) {
+  if (!c->variants.on) return;
+  hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, st, a, make_variant_args(c));
+}
+
+// right behind k_finish: the gates, in front of every kernel that reads a record's ac
+static void launch_gates(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  launch_variant_gate(c, a, st);
+  launch_site_gate(c, a, st, slot);
+}
+
+uint64_t bvcf_locus_hash(const char *s, size_t n) { return s ? fnv1a((const uint8_t *)s, n) : kFnvBasis; }
+uint64_t bvcf_variant_table_capacity(uint64_t n) { return n <= BVCF_VARIANT_MAX_ENTRIES ? variant_capacity(n) : 0; }
+
+// is the string s[0, n) an entry?  (the probe the device runs, on the host's table)
+static bool table_has(const VariantEntry *entries, const uint8_t *blob, uint32_t mask, const uint8_t *s, uint32_t n) {
+  return variant_find(entries, blob, mask, fnv1a(s, n), n, [&](LocusComparer &cmp) {
+    for (uint32_t i = 0; i < n; i++)
+      if (!cmp(s[i])) return false;
+    return true;
+  });
+}
+
+void bvcf_variant_table_free(bvcf_variant_table *t) {
+  if (!t) return;
+  free((void *)t->entries);
+  free((void *)t->blob);
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_variant_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, bvcf_variant_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (n && (!bytes || !off || !len)) return BVCF_E_ARG;
+  // the distinct entries first: the capacity follows their number
+  std::unordered_set<std::string_view> seen;
+  std::vector<uint64_t> first;
+  uint64_t blob_bytes = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    if (!len[i]) return BVCF_E_ARG;  // (len == 0 marks an empty slot)
+    if (!seen.emplace(bytes + off[i], len[i]).second) continue;
+    first.push_back(i);
+    blob_bytes += len[i];
+    if (first.size() > BVCF_VARIANT_MAX_ENTRIES || blob_bytes >= (1ull << 32)) return BVCF_E_TOO_BIG;
+  }
+  const uint64_t cap = variant_capacity(first.size());
+  VariantEntry *entries = (VariantEntry *)calloc((size_t)cap, sizeof(VariantEntry));
+  uint8_t *blob = (uint8_t *)malloc((size_t)blob_bytes + 1);
+  if (!entries || !blob) {
+    free(entries);
+    free(blob);
+    return BVCF_E_NOMEM;
+  }
+  const uint32_t mask = (uint32_t)(cap - 1);
+  uint64_t at = 0;
+  for (const uint64_t i : first) {
+    const uint8_t *s = (const uint8_t *)bytes + off[i];
+    const unsigned long long h = fnv1a(s, len[i]);
+    uint32_t slot = (uint32_t)h & mask;
+    while (entries[slot].len) slot = (slot + 1u) & mask;
+    entries[slot] = VariantEntry{(uint32_t)(h >> 32), (uint32_t)at, len[i], 0u};
+    memcpy(blob + at, s, len[i]);
+    at += len[i];
+  }
+  out->entries = (const uint32_t *)entries;
+  out->capacity = cap;
+  out->blob = (const char *)blob;
+  out->blob_bytes = blob_bytes;
+  out->n = first.size();
+  return BVCF_OK;
+}
+
+int bvcf_variant_table_has(const bvcf_variant_table *t, const char *s, size_t n) {
+  if (!t || !t->entries || !t->capacity || (t->capacity & (t->capacity - 1)) || (!s && n) || n > 0xFFFFFFFFull) return -1;
+  return table_has((const VariantEntry *)t->entries, (const uint8_t *)t->blob, (uint32_t)(t->capacity - 1), (const uint8_t *)s, (uint32_t)n) ? 1 : 0;
+}
+
+// every entry lies in the blob, nothing is stored in the fourth word, the capacity is a power of two with an empty slot
+static bool variant_table_sound(const bvcf_variant_table *t) {
+  if (!t || !t->entries || t->capacity < 16 || t->capacity > (1ull << 31) || (t->capacity & (t->capacity - 1)) ||
+      t->blob_bytes >= (1ull << 32) || (t->blob_bytes && !t->blob))
+    return false;
+  const VariantEntry *e = (const VariantEntry *)t->entries;
+  uint64_t used = 0;
+  for (uint64_t i = 0; i < t->capacity; i++) {
+    if (!e[i].len) continue;
+    used++;
+    if ((uint64_t)e[i].off + e[i].len > t->blob_bytes) return false;
+  }
+  return used == t->n && 2 * used <= t->capacity;
+}
+
+int bvcf_set_variant_table(bvcf_ctx *c, const bvcf_variant_table *t, int exclude) {
+  if (!c) return BVCF_E_ARG;
+  if (!variant_table_sound(t)) {
+    c->err = "bvcf_set_variant_table: want a table as bvcf_variant_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_variant_table")) return rc;
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
+  c->variants.on = false;
+  c->variants.entries.reset();
+  c->variants.blob.reset();
+  if (exclude && !t->n) return BVCF_OK;  // (nothing to take out: nothing is allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->variants.entries.alloc((size_t)t->capacity));
+  HIP_TRY(c, c->variants.blob.alloc((size_t)t->blob_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->variants.entries, t->entries, (size_t)t->capacity * sizeof(VariantEntry), hipMemcpyHostToDevice));
+  if (t->blob_bytes) HIP_TRY(c, hipMemcpy(c->variants.blob, t->blob, (size_t)t->blob_bytes, hipMemcpyHostToDevice));
+  c->variants.mask = (uint32_t)(t->capacity - 1);
+  c->variants.exclude = exclude ? 1u : 0u;
+  c->variants.on = true;
+  return BVCF_OK;
+}
+
+int bvcf_set_variant_list(bvcf_ctx *c, const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int exclude) {
+  if (!c) return BVCF_E_ARG;
+  bvcf_variant_table t;
+  const int rc = bvcf_variant_table_build(bytes, off, len, n, &t);
+  if (rc) {
+    c->err = rc == BVCF_E_TOO_BIG ? "bvcf_set_variant_list: more than 2^27 distinct entries, or 4 GiB of them"
+                                  : "bvcf_set_variant_list: bad arguments (an entry of length 0?) or no memory";
+    return rc;
+  }
+  const int rc2 = bvcf_set_variant_table(c, &t, exclude);
+  bvcf_variant_table_free(&t);
+  return rc2;
+}
+
+void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]) {
+  if (!out) return;
+  out[0] = out[1] = out[2] = 0;
+  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    for (uint32_t j = 0; j < L.n_rec; j++) {
+      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
+      if (A.pad[1]) {
+        out[2]++;
+      } else if (A.ac || A.pad[0]) {  // (a row the site gate took out afterwards was kept here)
+        out[1]++;
+      }
+    }
+  }
+  out[0] = out[1] + out[2];
+}
+
+uint32_t bvcf_bench_variant_gate_stride(const bvcf_ctx *c) { return c ? variant_gate_grid(c) * kWgThreads : 0u; }
+
+int bvcf_bench_variant_kernel(bvcf_ctx *c, float *ms) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Event ev[2];
+  if (const int rc = start_hook(c, "bvcf_bench_variant_kernel", c->variants.on && c->bench_src,
+                                "the ctx has no variant list, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  Slot &s = c->slots[0];
+  KernelArgs a;
+  if (const int rc = launch_ungated(c, s, &a, true)) return rc;
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_variant_gate(c, a, s.stream);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  return finish_hook(c, ev, s.stream, ms);
+}
+
+// ---- the arenas of the rows: what the .bed rows, the trios and the LD pairs share
+
+// the body of bvcf_reserve_bed_rows / _trio_events / _ld_events (`what` and `enable`: their names in the messages): the
+// bound grown to n units, in whole 64s, with nothing in flight, and every slot's arena with it
+static int reserve_arena(bvcf_ctx *c, const char *what, const char *enable, bool asked, bool on, uint64_t n, uint64_t n_max,
+                         const char *too_many, uint64_t *cap, int (*alloc)(bvcf_ctx *, Slot &)) {
+  if (!asked) {
+    c->err = std::string(what) + ": " + enable + " was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, what)) return rc;
+  if (!on) return BVCF_OK;
+  if (n > n_max) {
+    c->err = std::string(what) + too_many;
+    return BVCF_E_ARG;
+  }
+  *cap = std::max<uint64_t>(*cap, (n + 63) & ~63ull);
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots)
+    if (const int rc = alloc(c, s)) return rc;
+  return BVCF_OK;
+}
+
+// ---- the row index and the .bed rows
+
+// bvcf_enable_bed_rows / bvcf_enable_trios / bvcf_enable_ld: the row index all three read -- the lines' first rows (follow
+// max_lines), a row's map (follows max_alleles) and the counter; the .bed arena and its pinned copy when the ctx's bound
+// has grown past what the slot holds
+static int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
+  if (!c->bed.on && !c->trio.on && !c->ld.on) return BVCF_OK;
+  if (s.idx.base.size() < c->max_lines) {
+    HIP_TRY(c, s.idx.base.alloc(c->max_lines));
+    HIP_TRY(c, s.idx.tile.alloc(c->max_lines / kBedTile + 2));
+  }
+  if (s.idx.src.size() < c->max_alleles) HIP_TRY(c, s.idx.src.alloc(c->max_alleles));
+  HIP_TRY(c, s.bed.rows.alloc_total());
+  // (the pairs read the arena on the device: only the fileset has a pinned copy of it)
+  if (c->bed.on || c->ld.on) HIP_TRY(c, s.bed.rows.grow_to(c->bed.cap, c->bed.on));
+  return BVCF_OK;
+}
+
+// the slot holds everything the kernels of the row index write, sized for the ctx's current capacities
+static bool index_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.bed.rows.d_total && s.idx.base.size() >= c->max_lines && s.idx.src.size() >= c->max_alleles;
+}
+
+// ... and the arena k_bed_rows writes
+static bool bed_ready(const bvcf_ctx *c, const Slot &s) { return s.bed.rows.d && index_ready(c, s); }
+
+static BedArgs make_bed_args(bvcf_ctx *c, Slot &s) {
+  BedArgs ba{};
+  ba.line_base = s.idx.base;
+  ba.tile_base = s.idx.tile;
+  ba.row_src = s.idx.src;
+  ba.row_cap = (uint32_t)s.idx.src.size();
+  ba.total = s.bed.rows.d_total;
+  ba.out = s.bed.rows.d;
+  ba.cap = s.bed.rows.cap;
+  return ba;
+}
+
+// every row's place in output order
+static void launch_row_index(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
+  hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
+  hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, st, a, ba);
+  hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
+}
+
+// bvcf_enable_bed_rows: behind the row index, the rows themselves into the slot's arena (bvcf_bedrows.hip.h; bvcf_collect
+// copies the used part)
+static void launch_bed_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
+  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ba);
+}
+
+// collect in three steps.  The need, before the capacity verdict: what bvcf_bed_rows reports once the batch is in -- the
+// rows the batch packs, against the slot's arena (a batch that does not fit otherwise may count too few: it asks again) --
+// and, in c->bed.last until then and after BVCF_E_CAPACITY, the need alone.  The copy, on the slot's stream.  And, behind
+// the stream's sync, collect_slot publishes the report
+static bvcf_bed_rows_info bed_need(bvcf_ctx *c, const Slot &s) {
+  bvcf_bed_rows_info b{};
+  b.row_bytes = c->bed.on ? (c->n_samples + 3u) / 4u : 0u;
+  if (c->bed.on && bed_ready(c, s)) {
+    b.rows = s.bed.rows.h;
+    b.n_rows = *s.bed.rows.h_total;
+  }
+  b.need_bytes = b.n_rows * b.row_bytes;
+  c->bed.last = bvcf_bed_rows_info{};
+  c->bed.last.row_bytes = b.row_bytes;
+  c->bed.last.need_bytes = b.need_bytes;
+  return b;
+}
+static int bed_copy(bvcf_ctx *c, Slot &s, const bvcf_bed_rows_info &b) {
+  if (b.need_bytes) HIP_TRY(c, hipMemcpyAsync(s.bed.rows.h, s.bed.rows.d, b.need_bytes, hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+int bvcf_enable_bed_rows(bvcf_ctx *c) {
+  if (!c) return BVCF_E_ARG;
+  if (const int rc = refuse_in_flight(c, "bvcf_enable_bed_rows")) return rc;
+  c->bed.asked = true;
+  if (!c->n_samples || c->bed.on) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  // a biallelic line has at least two text bytes per sample and gives a quarter byte per sample; lines with many ALTs at
+  // few samples outrun this and grow the arena (BVCF_E_CAPACITY, bvcf_reserve_bed_rows)
+  c->bed.cap = std::max<uint64_t>(c->bed.cap, c->p.max_batch_bytes / 4);
+  c->bed.on = true;
+  c->bed.last = bvcf_bed_rows_info{};
+  c->bed.last.row_bytes = (c->n_samples + 3u) / 4u;
+  for (auto &s : c->slots)
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_reserve_bed_rows(bvcf_ctx *c, uint64_t bytes) {
+  if (!c) return BVCF_E_ARG;
+  return reserve_arena(c, "bvcf_reserve_bed_rows", "bvcf_enable_bed_rows", c->bed.asked || c->ld.asked, c->bed.on || c->ld.on, bytes,
+                       ~0ull, "", &c->bed.cap, alloc_bed_rows);
+}
+
+int bvcf_bed_rows(const bvcf_ctx *c, bvcf_bed_rows_info *out) {
+  if (!c || !out || !c->bed.asked) return BVCF_E_ARG;
+  *out = c->bed.last;
+  return BVCF_OK;
+}
+
+int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out) {
+  if (!out || !S) return -1;
+  bed_row_host(cmap_or_list, sparse != 0, S, out);
+  return (int)((S + 3u) / 4u);
+}
+
+// ---- the trios
+
+// the events of max_alleles rows and, behind them, of their tiles of kTrioTile rows
+static size_t trio_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kTrioTile + 2; }
+
+// bvcf_enable_trios: the counts, the events per row and per tile (follow max_alleles) and the counter; the events arena and its pinned
+// copy when the ctx's bound has grown past what the slot holds
+static int alloc_trios(bvcf_ctx *c, Slot &s) {
+  if (!c->trio.on) return BVCF_OK;
+  if (!s.trio.counts) {
+    HIP_TRY(c, s.trio.counts.alloc(3ull * c->trio.n));
+    HIP_TRY(c, s.trio.h_counts.alloc(3ull * c->trio.n));
+    HIP_TRY(c, s.trio.ev.alloc_total());
+  }
+  if (s.trio.rowev.size() < trio_rowev_words(c->max_alleles)) HIP_TRY(c, s.trio.rowev.alloc(trio_rowev_words(c->max_alleles)));
+  HIP_TRY(c, s.trio.ev.grow_to(c->trio.cap));
+  return BVCF_OK;
+}
+
+// the slot holds the row index and everything the trio kernels write
+static bool trios_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.trio.ev.d && s.trio.counts && s.trio.ev.d_total && s.trio.rowev.size() >= trio_rowev_words(c->max_alleles) && index_ready(c, s);
+}
+
+static TrioArgs make_trio_args(bvcf_ctx *c, Slot &s) {
+  TrioArgs ta{};
+  ta.trios = c->trio.trios;
+  ta.n_trios = c->trio.n;
+  ta.ev_rows = (uint32_t)c->max_alleles;
+  ta.counts = s.trio.counts;
+  ta.row_events = s.trio.rowev;
+  ta.total = s.trio.ev.d_total;
+  ta.events = s.trio.ev.d;
+  ta.cap = s.trio.ev.cap;
+  return ta;
+}
+
+constexpr int kTrioCountWgs = 5, kTrioFillWgs = 4;  // (k_trio_count: 5 waves per SIMD is what its registers allow)  // workgroups per CU
+
+// bvcf_enable_trios: the batch's counts and the events per row from zero, then the three kernels (bvcf_mendel.hip.h;
+// bvcf_collect copies the counts and the used part of the events)
+static int launch_trio_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const TrioArgs &ta,
+                               const Event *ev = nullptr) {
+  HIP_TRY(c, hipMemsetAsync(ta.counts, 0, 3ull * ta.n_trios * sizeof(uint32_t), st));
+  HIP_TRY(c, hipMemsetAsync(ta.row_events, 0, trio_rowev_words(ta.ev_rows) * sizeof(uint32_t), st));
+  mark(ev, st);
+  hipLaunchKernelGGL(k_trio_count, dim3(c->n_cu * kTrioCountWgs), dim3(kWgThreads), 0, st, a, ba, ta);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_trio_scan, dim3(1), dim3(1024), 0, st, a, ba, ta);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_trio_fill, dim3(c->n_cu * kTrioFillWgs), dim3(kWgThreads), 0, st, a, ba, ta);
+  return BVCF_OK;
+}
+
+// collect, as for the .bed rows: likewise the batch's events against the slot's arena
+static bvcf_trio_info trio_need(bvcf_ctx *c, const Slot &s) {
+  bvcf_trio_info t{};
+  t.n_trios = c->trio.n;
+  if (c->trio.on && trios_ready(c, s)) {
+    t.counts = s.trio.h_counts;
+    t.events = reinterpret_cast<const uint32_t *>(s.trio.ev.h.get());
+    t.n_events = *s.trio.ev.h_total;
+  }
+  t.need_events = t.n_events;
+  c->trio.last = bvcf_trio_info{};
+  c->trio.last.n_trios = t.n_trios;
+  c->trio.last.need_events = t.need_events;
+  return t;
+}
+// (the table too comes over only now: until this collect the slot's pinned copy is the caller's, from the slot's last batch)
+static int trio_copy(bvcf_ctx *c, Slot &s, const bvcf_trio_info &t) {
+  if (t.counts)
+    HIP_TRY(c, hipMemcpyAsync(s.trio.h_counts, s.trio.counts, 3ull * c->trio.n * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+  if (t.n_events) HIP_TRY(c, hipMemcpyAsync(s.trio.ev.h, s.trio.ev.d, t.n_events * sizeof(uint2), hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+int bvcf_enable_trios(bvcf_ctx *c, const uint32_t *trios, uint32_t n) {
+  if (!c || (n && !trios)) return BVCF_E_ARG;
+  if (const int rc = refuse_in_flight(c, "bvcf_enable_trios")) return rc;
+  if (c->trio.asked) {
+    c->err = "bvcf_enable_trios: called twice on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (n >= kTrioMax) {
+    c->err = "bvcf_enable_trios: more than " + std::to_string(kTrioMax - 1) + " trios";
+    return BVCF_E_ARG;
+  }
+  for (uint32_t t = 0; t < n; t++) {
+    const uint32_t *x = trios + 3ull * t;
+    if (x[0] >= c->n_samples || x[1] >= c->n_samples || x[2] >= c->n_samples || x[0] == x[1] || x[0] == x[2] || x[1] == x[2]) {
+      c->err = "bvcf_enable_trios: trio " + std::to_string(t) + " names a sample index past the ctx's samples, or one sample twice";
+      return BVCF_E_ARG;
+    }
+  }
+  c->trio.asked = true;
+  c->trio.last = bvcf_trio_info{};
+  if (!n) return BVCF_OK;  // (no trios -- or no sample columns, which gives none: nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->trio.trios.alloc(3ull * n + 16));  // (16 words at least: what trio_row reads for a row that is no short list)
+  HIP_TRY(c, hipMemset(c->trio.trios, 0, (3ull * n + 16) * sizeof(uint32_t)));
+  HIP_TRY(c, hipMemcpy(c->trio.trios, trios, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  c->trio.n = n;
+  // an event needs a call that contradicts the pedigree; real cohorts show a few per thousand (row, trio) pairs, and a
+  // line of text gives a row.  One event (8 bytes) per 64 bytes of text holds that with room; a wrong pedigree or a
+  // crafted file outruns it and grows the arena (BVCF_E_CAPACITY, bvcf_reserve_trio_events)
+  c->trio.cap = std::max<uint64_t>(c->trio.cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
+  c->trio.on = true;
+  c->trio.last.n_trios = n;
+  for (auto &s : c->slots) {
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+    if (const int rc = alloc_trios(c, s)) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_reserve_trio_events(bvcf_ctx *c, uint64_t n) {
+  if (!c) return BVCF_E_ARG;
+  return reserve_arena(c, "bvcf_reserve_trio_events", "bvcf_enable_trios", c->trio.asked, c->trio.on, n, kTrioEventsMax,
+                       ": a batch holds fewer than 2^32 events (smaller batches: max_batch_bytes)", &c->trio.cap, alloc_trios);
+}
+
+int bvcf_trio_stats(const bvcf_ctx *c, bvcf_trio_info *out) {
+  if (!c || !out || !c->trio.asked) return BVCF_E_ARG;
+  *out = c->trio.last;
+  return BVCF_OK;
+}
+
+int bvcf_trio_verdict(uint32_t child, uint32_t father, uint32_t mother) {
+  if (child > 3u || father > 3u || mother > 3u) return -1;
+  return (int)trio_verdict(child, father, mother);
+}
+
+// ---- the LD pairs
+
+// the events of max_alleles rows and, behind them, of their tiles of kLdTile rows
+static size_t ld_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kLdTile + 2; }
+
+// bvcf_enable_ld: the keys and the events per row and per tile (follow max_alleles), the counter and the edge rows; the
+// events arena and its pinned copy when the ctx's bound has grown past what the slot holds
+static int alloc_ld(bvcf_ctx *c, Slot &s) {
+  if (!c->ld.on) return BVCF_OK;
+  if (!s.ld.ev.d_total) {
+    HIP_TRY(c, s.ld.ev.alloc_total());
+    HIP_TRY(c, s.ld.h_edge.alloc(2ull * c->ld.window * ((c->n_samples + 3u) / 4u) + 16));
+  }
+  if (s.ld.key.size() < c->max_alleles) HIP_TRY(c, s.ld.key.alloc(c->max_alleles));
+  if (s.ld.rowev.size() < ld_rowev_words(c->max_alleles)) HIP_TRY(c, s.ld.rowev.alloc(ld_rowev_words(c->max_alleles)));
+  HIP_TRY(c, s.ld.ev.grow_to(c->ld.cap));
+  return BVCF_OK;
+}
+
+// the slot holds the row index, the arena of the rows and everything the LD kernels write
+static bool ld_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.ld.ev.d && s.ld.ev.d_total && s.ld.key.size() >= c->max_alleles && s.ld.rowev.size() >= ld_rowev_words(c->max_alleles) &&
+         bed_ready(c, s);
+}
+
+static LdArgs make_ld_args(bvcf_ctx *c, Slot &s) {
+  LdArgs la{};
+  la.window = c->ld.window;
+  la.t6 = c->ld.t6;
+  la.ev_rows = (uint32_t)c->max_alleles;
+  la.row_key = s.ld.key;
+  la.row_events = s.ld.rowev;
+  la.total = s.ld.ev.d_total;
+  la.events = s.ld.ev.d;
+  la.cap = s.ld.ev.cap;
+  return la;
+}
+
+constexpr int kLdPairWgs = 8;  // workgroups per CU (13 KB of LDS each)
+
+// bvcf_enable_ld: the rows' chrom keys, then count, scan and fill (bvcf_ld.hip.h; bvcf_collect copies the used part of the
+// events and the edge rows)
+static void launch_ld_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const LdArgs &la,
+                              const Event *ev = nullptr) {
+  hipLaunchKernelGGL(k_ld_keys, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba, la);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_ld_pairs<false>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(1024), 0, st, a, ba, la);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_ld_pairs<true>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
+}
+
+// collect, as for the .bed rows: the rows again -- the pairs read the same arena --, and the batch's events against theirs
+static bvcf_ld_info ld_need(bvcf_ctx *c, const Slot &s) {
+  const uint32_t rb = (c->n_samples + 3u) / 4u;
+  bvcf_ld_info l{};
+  l.row_bytes = c->ld.on ? rb : 0u;
+  l.window = c->ld.window;
+  if (c->ld.on && ld_ready(c, s)) {
+    l.events = s.ld.ev.h;
+    l.n_events = *s.ld.ev.h_total;
+    l.n_rows = *s.bed.rows.h_total;
+    l.n_edge = (uint32_t)std::min<uint64_t>(c->ld.window, l.n_rows);
+    l.head_rows = s.ld.h_edge;
+    l.tail_rows = s.ld.h_edge + (uint64_t)l.n_edge * rb;
+  }
+  l.need_events = l.n_events;
+  l.need_row_bytes = l.n_rows * rb;
+  c->ld.last = bvcf_ld_info{};
+  c->ld.last.row_bytes = l.row_bytes;
+  c->ld.last.window = l.window;
+  c->ld.last.need_events = l.need_events;
+  c->ld.last.need_row_bytes = l.need_row_bytes;
+  return l;
+}
+// (likewise the events and the batch's first and last rows, which the seam pairs with its neighbours')
+static int ld_copy(bvcf_ctx *c, Slot &s, const bvcf_ld_info &l) {
+  const uint64_t edge_bytes = (uint64_t)l.n_edge * l.row_bytes;
+  if (l.n_events) HIP_TRY(c, hipMemcpyAsync(s.ld.ev.h, s.ld.ev.d, l.n_events * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+  if (l.n_edge) {
+    HIP_TRY(c, hipMemcpyAsync(s.ld.h_edge, s.bed.rows.d, edge_bytes, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(c, hipMemcpyAsync(s.ld.h_edge + edge_bytes, s.bed.rows.d + (l.n_rows - l.n_edge) * l.row_bytes, edge_bytes, hipMemcpyDeviceToHost,
+                              s.stream));
+  }
+  return BVCF_OK;
+}
+
+int bvcf_enable_ld(bvcf_ctx *c, uint32_t window, uint32_t t6) {
+  if (!c) return BVCF_E_ARG;
+  if (const int rc = refuse_in_flight(c, "bvcf_enable_ld")) return rc;
+  if (c->ld.asked) {
+    c->err = "bvcf_enable_ld: called twice on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (window < 1 || window > bvcf_ld::kMaxWindow || t6 > bvcf_ld::kT6One) {
+    c->err = "bvcf_enable_ld: window must be 1 to 512 and t6 at most 1000000";
+    return BVCF_E_ARG;
+  }
+  if (c->n_samples >= bvcf_ld::kMaxSamples) {
+    c->err = "bvcf_enable_ld: " + std::to_string(c->n_samples) + " samples, the exact comparison holds below 2^24";
+    return BVCF_E_ARG;
+  }
+  c->ld.asked = true;
+  c->ld.window = window;
+  c->ld.t6 = t6;
+  c->ld.last = bvcf_ld_info{};
+  c->ld.last.window = window;
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  // the rows' arena as bvcf_enable_bed_rows bounds it; an event (32 bytes) per 64 bytes of text to begin with: a line of
+  // text gives a row, and at the usual thresholds a row of a real cohort is in LD with a few of its 50 neighbours at
+  // most.  A threshold of 0, a long window or a file of copies of one line outruns that and grows the arena
+  // (BVCF_E_CAPACITY, bvcf_reserve_ld_events)
+  c->bed.cap = std::max<uint64_t>(c->bed.cap, c->p.max_batch_bytes / 4);
+  c->ld.cap = std::max<uint64_t>(c->ld.cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
+  c->ld.on = true;
+  c->ld.last.row_bytes = (c->n_samples + 3u) / 4u;
+  for (auto &s : c->slots) {
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+    if (const int rc = alloc_ld(c, s)) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_reserve_ld_events(bvcf_ctx *c, uint64_t n) {
+  if (!c) return BVCF_E_ARG;
+  return reserve_arena(c, "bvcf_reserve_ld_events", "bvcf_enable_ld", c->ld.asked, c->ld.on, n, kLdEventsMax / 8,
+                       ": a batch holds fewer than 2^29 events (smaller batches: max_batch_bytes)", &c->ld.cap, alloc_ld);
+}
+
+int bvcf_ld_stats(const bvcf_ctx *c, bvcf_ld_info *out) {
+  if (!c || !out || !c->ld.asked) return BVCF_E_ARG;
+  *out = c->ld.last;
+  return BVCF_OK;
+}
+
+int bvcf_ld_counts(const uint8_t *row_a, const uint8_t *row_b, uint32_t S, uint32_t out[6]) {
+  if (!row_a || !row_b || !out || !S) return -1;
+  bvcf_ld::counts_host(row_a, row_b, S, out);
+  return 0;
+}
+
+int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
+  if (!counts || t6 > bvcf_ld::kT6One || counts[0] >= bvcf_ld::kMaxSamples) return -1;
+  return bvcf_ld::in_ld(counts, t6) ? 1 : 0;
+}
+
+// ---- the rows' kernels together: the end of a chain, the counters' way to the host, the bench hooks
+
+// the end of a chain with samples, with bvcf_enable_bed_rows, bvcf_enable_ld and / or bvcf_enable_trios: every row's place
+// in output order -- once --, then the .bed rows into the slot's arena, the pairs' events and the trios' counts and events
+// into theirs
+static void launch_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if (!slot) return;
+  const bool ld = c->ld.on && ld_ready(c, *slot);
+  const bool bed = (c->bed.on && bed_ready(c, *slot)) || ld, trios = c->trio.on && trios_ready(c, *slot);
+  if (!bed && !trios) return;
+  const BedArgs ba = make_bed_args(c, *slot);
+  launch_row_index(c, a, st, ba);
+  if (bed) launch_bed_rows(c, a, st, ba);
+  if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
+  if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)
+}
+
+// the arenas' counters on their way to the host, behind the batch's own (launch_batch)
+static int copy_arena_totals(bvcf_ctx *c, Slot &s) {
+  if ((c->bed.on || c->trio.on || c->ld.on) && s.bed.rows.d_total) HIP_TRY(c, s.bed.rows.copy_total(s.stream));
+  if (c->ld.on && ld_ready(c, s)) HIP_TRY(c, s.ld.ev.copy_total(s.stream));
+  if (c->trio.on && trios_ready(c, s)) HIP_TRY(c, s.trio.ev.copy_total(s.stream));
+  return BVCF_OK;
+}
+
+// how a hook of the rows' kernels ends: out[0] the batch's rows
+static int finish_rows_hook(bvcf_ctx *c, Slot &s, Event *ev, size_t n_ev, float *ms, uint64_t *out) {
+  HIP_TRY(c, hipEventRecord(ev[n_ev - 1], s.stream));
+  HIP_TRY(c, hipGetLastError());
+  if (const int rc = copy_arena_totals(c, s)) return rc;
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  for (size_t k = 0; k + 1 < n_ev; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  out[0] = *s.bed.rows.h_total;
+  return BVCF_OK;
+}
+
+int bvcf_bench_bed_kernels(bvcf_ctx *c, float ms[2], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[3];
+  if (const int rc = start_hook(c, "bvcf_bench_bed_kernels", c->bed.on && bed_ready(c, s), "the ctx has no bed rows", ev)) return rc;
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
+  const BedArgs ba = make_bed_args(c, s);
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_row_index(c, a, s.stream, ba);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  launch_bed_rows(c, a, s.stream, ba);
+  if (const int rc = finish_rows_hook(c, s, ev, 3, ms, out)) return rc;
+  out[1] = out[0] * ((c->n_samples + 3u) / 4u);
+  if (!s.bed.rows.fits(out[1])) {
+    c->err = "bvcf_bench_bed_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[1]) + " bytes";
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_bench_trio_kernels(bvcf_ctx *c, float ms[4], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[5];
+  if (const int rc = start_hook(c, "bvcf_bench_trio_kernels", c->trio.on && trios_ready(c, s), "the ctx has no trios", ev)) return rc;
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
+  const BedArgs ba = make_bed_args(c, s);
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_row_index(c, a, s.stream, ba);
+  if (const int rc = launch_trio_kernels(c, a, s.stream, ba, make_trio_args(c, s), ev + 1)) return rc;  // (ev[1] to ev[3])
+  if (const int rc = finish_rows_hook(c, s, ev, 5, ms, out)) return rc;
+  out[1] = *s.trio.ev.h_total;
+  if (!s.trio.ev.fits(out[1])) {
+    c->err = "bvcf_bench_trio_kernels: the events outrun the arena (bvcf_reserve_trio_events): " + std::to_string(out[1]);
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_bench_ld_kernels(bvcf_ctx *c, float ms[6], uint64_t out[2]) {
+  if (!c || !ms || !out) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[7];
+  if (const int rc = start_hook(c, "bvcf_bench_ld_kernels", c->ld.on && ld_ready(c, s),
+                                "bvcf_enable_ld was not called on the ctx, or it has no samples", ev))
+    return rc;
+  // (k_ld_keys reads the lines' first fields: the block of the last bench call, which is still on the device)
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  const BedArgs ba = make_bed_args(c, s);
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_row_index(c, a, s.stream, ba);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  launch_bed_rows(c, a, s.stream, ba);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  launch_ld_kernels(c, a, s.stream, ba, make_ld_args(c, s), ev + 3);  // (ev[3] to ev[5])
+  if (const int rc = finish_rows_hook(c, s, ev, 7, ms, out)) return rc;
+  out[1] = *s.ld.ev.h_total;
+  if (!s.bed.rows.fits(out[0] * ((c->n_samples + 3u) / 4u))) {
+    c->err = "bvcf_bench_ld_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[0]) + " rows";
+    return BVCF_E_CAPACITY;
+  }
+  if (!s.ld.ev.fits(out[1])) {
+    c->err = "bvcf_bench_ld_kernels: the events outrun the arena (bvcf_reserve_ld_events): " + std::to_string(out[1]);
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
+// ---- per-sample counts and pair counts
+
+// bvcf_params.want_sample_stats: the tables of a slot, once (alloc_slot); the totals start from zero
+static int alloc_ss_tables(bvcf_ctx *c, Slot &s) {
+  if (!c->ss_on) return BVCF_OK;
+  const size_t table = (size_t)kSsCols * c->ss_ns_pad;
+  HIP_TRY(c, s.ss.ctr.alloc(4));
+  HIP_TRY(c, s.ss.part.alloc((size_t)c->ss_max_runs * table));
+  HIP_TRY(c, s.ss.sp.alloc(table));
+  HIP_TRY(c, s.ss.acc.alloc(6ull * c->ss_ns_pad));
+  HIP_TRY(c, hipMemset(s.ss.acc, 0, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
+  return BVCF_OK;
+}
+
+// what follows max_lines / max_alleles or a bound of the ctx's, for the ctx's current capacities: the analyses' above, then
+// the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
+static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
+  if (const int rc = alloc_gate_list(c, s)) return rc;
+  if (const int rc = alloc_bed_rows(c, s)) return rc;
+  if (const int rc = alloc_trios(c, s)) return rc;
+  if (const int rc = alloc_ld(c, s)) return rc;
+  if (!c->ss_on && !c->pr.on) return BVCF_OK;
+  s.pr.planes.reset();
+  s.pr.cap_tiles = 0;
+  HIP_TRY(c, s.ss.dense.alloc(c->max_alleles));
+  HIP_TRY(c, s.ss.sparse.alloc(c->max_alleles));
+  if (c->pr.on) {
+    const uint64_t tiles = (c->max_alleles + kPrTile - 1) / kPrTile;
+    HIP_TRY(c, s.pr.planes.alloc(tiles * kPrTables * 4ull * c->cmap_stride));
+    s.pr.cap_tiles = tiles;
+  }
+  return BVCF_OK;
+}
+
+static SampleStatsArgs make_ss_args(bvcf_ctx *c, Slot &s) {
+  SampleStatsArgs sa{};
+  sa.dense = s.ss.dense;
+  sa.sparse = s.ss.sparse;
+  sa.ctr = s.ss.ctr;
+  sa.part = s.ss.part;
+  sa.sp = s.ss.sp;
+  sa.acc = s.ss.acc;
+  sa.list_cap = (uint32_t)s.ss.sparse.size();  // (the second of the two lists: there when both are)
+  sa.ns_pad = c->ss_ns_pad;
+  sa.max_runs = c->ss_max_runs;
+  sa.n_stripes = c->ss_stripes;
+  return sa;
+}
+
+static PairStatsArgs make_pr_args(bvcf_ctx *c, Slot &s) {
+  PairStatsArgs pa{};
+  pa.dense = s.ss.dense;
+  pa.sparse = s.ss.sparse;
+  pa.ctr = s.ss.ctr;
+  pa.planes = s.pr.planes;
+  pa.bt = s.pr.bt;
+  pa.tot = c->pr.tot;
+  pa.list_cap = (uint32_t)s.ss.sparse.size();
+  pa.tile_cap = (uint32_t)s.pr.cap_tiles;
+  pa.ns = c->n_samples;
+  pa.ns_pad = 4u * c->cmap_stride;
+  pa.n_split = c->pr.split;
+  return pa;
+}
+
+// the batch's pair tables from the row lists k_ss_list left: the tables from zero, the planes, the product, the short lists
+static void launch_pair_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const PairStatsArgs &pa, const Event *ev = nullptr) {
+  const uint32_t nb = pa.ns_pad / kPrBlock;
+  // (tiles dealt among several workgroups per pair block: the tables start from zero and are added to)
+  if (pa.n_split > 1) hipMemsetAsync(pa.bt, 0, (size_t)kPrTables * pa.ns * pa.ns * sizeof(uint32_t), st);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_pr_gemm, dim3(nb, nb, pa.n_split), dim3(kWgThreads), 0, st, pa);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_pr_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
+}
+
+// bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
+// (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
+// ... and, with bvcf_enable_pair_stats, the batch's pair tables from the same row lists (bvcf_pairstats.hip.h): the list
+// kernel runs once for both, and alone in front of the pair kernels when only they are on
+static void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  if ((!c->ss_on && !c->pr.on) || !slot || !slot->ss.dense) return;
+  const SampleStatsArgs sa = make_ss_args(c, *slot);
+  hipMemsetAsync(sa.ctr, 0, 4 * sizeof(uint32_t), st);
+  if (c->ss_on) hipMemsetAsync(sa.sp, 0, (size_t)kSsCols * sa.ns_pad * sizeof(uint32_t), st);
+  hipLaunchKernelGGL(k_ss_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, sa);
+  if (c->ss_on) {
+    const uint32_t waves = c->ss_stripes * c->ss_max_runs;
+    hipLaunchKernelGGL(k_ss_dense, dim3((waves + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, a, sa);
+    hipLaunchKernelGGL(k_ss_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);  // (three dependent loads per list: many in flight)
+  }
+  if (c->pr.on && slot->pr.planes && slot->pr.bt) launch_pair_kernels(c, a, st, make_pr_args(c, *slot));
+}
+
+// the end of a chain with samples, behind the dosage rows: the counts, then the rows
+static void launch_analyses(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  launch_sample_stats(c, a, st, slot);
+  launch_rows(c, a, st, slot);
+}
+
+static void launch_pr_fold(bvcf_ctx *c, hipStream_t st, const PairStatsArgs &pa) {
+  const size_t n = (size_t)kPrTables * pa.ns * pa.ns;
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
+  hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, st, pa);
+}
+
+// the batch is in: its per-sample counts join the slot's totals and its pair tables the ctx's (ahead of the copies on the
+// slot's stream)
+static int launch_folds(bvcf_ctx *c, Slot &s) {
+  if (c->ss_on && s.ss.dense) {
+    const uint32_t n_threads = kSsCols * c->ss_ns_pad;
+    hipLaunchKernelGGL(k_ss_fold, dim3((n_threads + kWgThreads - 1) / kWgThreads), dim3(kWgThreads), 0, s.stream,
+                       make_ss_args(c, s), c->n_samples);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (c->pr.on && s.pr.bt) {
+    // one fold after the other, whichever slots' streams they run on
+    if (c->pr.folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->pr.ev_fold, 0));
+    launch_pr_fold(c, s.stream, make_pr_args(c, s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->pr.ev_fold, s.stream));
+    c->pr.folded = true;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->p.want_sample_stats) {
+    c->err = "bvcf_sample_stats: the ctx was created without bvcf_params.want_sample_stats";
+    return BVCF_E_ARG;
+  }
+  const uint32_t ns = c->n_samples;
+  if (out) memset(out, 0, 6ull * ns * sizeof(uint64_t));
+  if (!c->ss_on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  std::vector<unsigned long long> t((size_t)6 * c->ss_ns_pad);
+  for (auto &s : c->slots) {
+    if (!s.ss.acc) continue;
+    HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+    if (out) {
+      HIP_TRY(c, hipMemcpyAsync(t.data(), s.ss.acc, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+      HIP_TRY(c, hipStreamSynchronize(s.stream));
+      for (uint32_t col = 0; col < kSsCols; col++)
+        for (uint32_t i = 0; i < ns; i++) out[(size_t)col * ns + i] += t[(size_t)col * c->ss_ns_pad + i];
+      for (uint32_t i = 0; i < ns; i++) out[(size_t)kSsCols * ns + i] += t[(size_t)kSsCols * c->ss_ns_pad];
+    }
+    if (reset) {
+      HIP_TRY(c, hipMemsetAsync(s.ss.acc, 0, t.size() * sizeof(unsigned long long), s.stream));
+      HIP_TRY(c, hipStreamSynchronize(s.stream));
+    }
+  }
+  return BVCF_OK;
+}
+
+int bvcf_enable_pair_stats(bvcf_ctx *c) {
+  if (!c) return BVCF_E_ARG;
+  if (const int rc = refuse_in_flight(c, "bvcf_enable_pair_stats")) return rc;
+  if (c->n_samples > BVCF_PAIR_MAX_SAMPLES) {
+    c->err = "bvcf_enable_pair_stats: " + std::to_string(c->n_samples) + " samples, the pair tables hold at most " +
+             std::to_string(BVCF_PAIR_MAX_SAMPLES);
+    return BVCF_E_ARG;
+  }
+  c->pr.asked = true;
+  if (!c->n_samples || c->pr.on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
+  HIP_TRY(c, c->pr.tot.alloc(n));
+  HIP_TRY(c, hipMemset(c->pr.tot, 0, n * sizeof(unsigned long long)));
+  HIP_TRY(c, c->pr.ev_fold.create(hipEventDisableTiming));
+  // a cohort of few samples has few pair blocks: the tiles of a block are then dealt to several workgroups
+  const uint64_t nb = 4ull * c->cmap_stride / kPrBlock;
+  c->pr.split = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, 2ull * (uint64_t)c->n_cu / (nb * nb)));
+  c->pr.on = true;
+  for (auto &s : c->slots) {
+    if (!s.ss.ctr) HIP_TRY(c, s.ss.ctr.alloc(4));
+    HIP_TRY(c, s.pr.bt.alloc(n));
+    HIP_TRY(c, hipMemset(s.pr.bt, 0, n * sizeof(uint32_t)));
+    const int rc = alloc_row_lists(c, s);
+    if (rc) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->pr.asked) {
+    c->err = "bvcf_pair_stats: bvcf_enable_pair_stats was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (!c->pr.on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+  const size_t bytes = (size_t)kPrTables * c->n_samples * c->n_samples * sizeof(unsigned long long);
+  hipStream_t st = c->slots[0].stream;
+  if (out) HIP_TRY(c, hipMemcpyAsync(out, c->pr.tot, bytes, hipMemcpyDeviceToHost, st));
+  if (reset) HIP_TRY(c, hipMemsetAsync(c->pr.tot, 0, bytes, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BVCF_OK;
+}
+
+// (the last interval is k_pr_fold, which the product runs at collect -- launch_folds --: the hook's own step)
+int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[5];
+  if (const int rc = start_hook(c, "bvcf_bench_pair_kernels", c->pr.on && s.pr.planes && s.pr.bt, "the ctx has no pair tables", ev)) return rc;
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read a.cmap only)
+  const PairStatsArgs pa = make_pr_args(c, s);
+  launch_pair_kernels(c, a, s.stream, pa, ev);  // (ev[0] behind the memset, ev[1], ev[2])
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  launch_pr_fold(c, s.stream, pa);
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  return finish_hook(c, ev, s.stream, ms);
+}
+
+}  // extern "C"
+
+#endif

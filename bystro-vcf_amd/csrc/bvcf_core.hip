@@ -30,6 +30,8 @@ using bvcf_mem::Event;
 using bvcf_mem::PinBuf;
 using bvcf_mem::Stream;
 
+#include "bvcf_analyses.hip.h"  // (the state; the functions follow behind bvcf_ctx)
+
 namespace {
 
 struct Slot {
@@ -113,46 +115,14 @@ struct Slot {
   PinBuf<bvcf_err> h_errs;
   PinBuf<uint8_t> h_cmap;
   PinBuf<int8_t> h_dosage;
-  // bvcf_params.want_sample_stats (bvcf_samplestats.hip.h): the row lists (follow max_alleles), the batch's counts, the totals
-  DevBuf<uint2> d_ss_dense, d_ss_sparse;
-  DevBuf<uint32_t> d_ss_ctr, d_ss_part, d_ss_sp;
-  DevBuf<unsigned long long> d_ss_acc;
-  // bvcf_enable_pair_stats (bvcf_pairstats.hip.h): the bit planes of the dense rows' tiles (follow the row lists), the batch's tables
-  DevBuf<unsigned long long> d_pr_planes;
-  uint64_t cap_pr_tiles = 0;
-  DevBuf<uint32_t> d_pr_bt;
-  // bvcf_set_site_gate with hwe_p (bvcf_sitegate.hip.h): [0] the number of rows left to k_site_hwe, then their slots (follows max_alleles)
-  DevBuf<uint32_t> d_gate_list;
-  // bvcf_enable_bed_rows (bvcf_bedrows.hip.h): the first row of every line (follows max_lines), the batch's row count, and
-  // the arena of the packed rows with its pinned copy -- an arena with a bound of its own (bvcf_ctx.bed_cap)
-  DevBuf<uint32_t> d_bed_base, d_bed_tile;
-  DevBuf<uint2> d_bed_src;  // a row's map (follows max_alleles)
-  DevBuf<unsigned long long> d_bed_total;
-  PinBuf<unsigned long long> h_bed_total;
-  DevBuf<uint8_t> d_bed;
-  PinBuf<uint8_t> h_bed;
-  uint64_t cap_bed = 0;
-  // bvcf_enable_trios (bvcf_mendel.hip.h): the batch's [T][3] counts with their pinned copy, the events per row (follow
-  // max_alleles), the batch's event count, and the arena of the events with its pinned copy -- a bound of its own
-  // (bvcf_ctx.trio_cap, in events)
-  DevBuf<uint32_t> d_trio_counts, d_trio_rowev;
-  PinBuf<uint32_t> h_trio_counts;
-  DevBuf<unsigned long long> d_trio_total;
-  PinBuf<unsigned long long> h_trio_total;
-  DevBuf<uint2> d_trio_ev;
-  PinBuf<uint2> h_trio_ev;
-  uint64_t cap_trio = 0;
-  // bvcf_enable_ld (bvcf_ld.hip.h): a row's chrom key and its events (follow max_alleles), the batch's event count, the
-  // arena of the events with its pinned copy -- a bound of its own (bvcf_ctx.ld_cap, in events) -- and the pinned copy of
-  // the batch's first and last `window` rows
-  DevBuf<uint4> d_ld_key;
-  DevBuf<uint32_t> d_ld_rowev;
-  DevBuf<unsigned long long> d_ld_total;
-  PinBuf<unsigned long long> h_ld_total;
-  DevBuf<uint32_t> d_ld_ev;
-  PinBuf<uint32_t> h_ld_ev;
-  PinBuf<uint8_t> h_ld_edge;
-  uint64_t cap_ld = 0;
+  // the analyses behind k_finish (bvcf_analyses.hip.h)
+  SampleStatsSlot ss;
+  PairStatsSlot pr;
+  SiteGateSlot gate;
+  RowIndexSlot idx;
+  BedSlot bed;
+  TrioSlot trio;
+  LdSlot ld;
   // capacities this slot was allocated with: alloc_results zeroes them before it allocates and sets them once everything
   // is there, so a slot whose allocation failed starts over at its next use
   uint64_t cap_lines = 0, cap_alleles = 0, cap_cmap = 0, cap_census = 0;
@@ -195,41 +165,13 @@ struct bvcf_ctx : bvcf_ctx_plan {
   bool row_fmt_set = false;
   DevBuf<uint8_t> d_row_fmt;  // "chr" | "\tSNP\t" | the constant tail
   uint32_t row_tail_len = 0, row_keep_pos = 0, row_keep_id = 0, row_keep_info = 0;
-  // bvcf_enable_pair_stats on a file with samples: the pair counts behind every chain (bvcf_pairstats.hip.h).  The totals are
-  // the ctx's: the folds of the slots' batches follow one another through ev_pr_fold
-  bool pr_asked = false, pr_on = false, pr_folded = false;
-  uint32_t pr_split = 1;
-  DevBuf<unsigned long long> d_pr_tot;
-  Event ev_pr_fold;
-  // bvcf_set_site_gate on a file with samples, some criterion not neutral: k_site_gate / k_site_hwe behind k_finish
-  bool gate_on = false;
-  bvcf_site_gate gate{};
-  // bvcf_set_variant_list / bvcf_set_variant_table on a file with samples: k_variant_gate behind k_finish, in front of the
-  // site gate; the hash set (bvcf_variantlist.hip.h) is the ctx's, read by the batches of every slot
-  bool variants_on = false;
-  uint32_t variants_exclude = 0, variants_mask = 0;
-  DevBuf<VariantEntry> d_variant_entries;
-  DevBuf<uint8_t> d_variant_blob;
-  // bvcf_enable_bed_rows on a file with samples: k_bed_count / k_bed_scan / k_bed_index / k_bed_rows at the end of every chain; bed_cap is
-  // what a slot's arena holds (bvcf_reserve_bed_rows grows it), bed_last the batch collected last (bvcf_bed_rows)
-  bool bed_asked = false, bed_on = false;
-  uint64_t bed_cap = 0;
-  bvcf_bed_rows_info bed_last{};
-  // bvcf_enable_trios on a file with samples and at least one trio: k_trio_count / k_trio_scan / k_trio_fill at the end of
-  // every chain, behind the row index they share with the .bed rows (built once when either is on); trio_cap is what a
-  // slot's events arena holds (bvcf_reserve_trio_events grows it), trio_last the batch collected last (bvcf_trio_stats)
-  bool trio_asked = false, trio_on = false;
-  uint32_t n_trios = 0;
-  DevBuf<uint32_t> d_trios;
-  uint64_t trio_cap = 0;
-  bvcf_trio_info trio_last{};
-  // bvcf_enable_ld on a file with samples: k_bed_rows (once, shared with the fileset), k_ld_keys, k_ld_pairs / k_ld_scan /
-  // k_ld_pairs at the end of every chain, behind the same row index; ld_cap is what a slot's events arena holds
-  // (bvcf_reserve_ld_events grows it), ld_last the batch collected last (bvcf_ld_stats)
-  bool ld_asked = false, ld_on = false;
-  uint32_t ld_window = 0, ld_t6 = 0;
-  uint64_t ld_cap = 0;
-  bvcf_ld_info ld_last{};
+  // the analyses behind k_finish (bvcf_analyses.hip.h)
+  PairStatsCtx pr;
+  SiteGateCtx gate;
+  VariantGateCtx variants;
+  BedCtx bed;
+  TrioCtx trio;
+  LdCtx ld;
   const void *bench_src = nullptr;  // the last block of the last bvcf_bench_device* call (bvcf_bench_gate_kernels)
   size_t bench_nbytes = 0;
   uint64_t need_extras = 0;  // packed / k_sites1 ctxs: extra ALT records of the last batch that did not fit (they sit behind slot max_lines)
@@ -507,101 +449,11 @@ NameArgs make_name_args(bvcf_ctx *c, Slot &s) {
   return na;
 }
 
-// the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
-// bvcf_set_site_gate with hwe_p: the list of the rows left to k_site_hwe (follows max_alleles) -- for a slot that exists
-// when the gate is set, and again whenever alloc_results sizes the slot anew
-int alloc_gate_list(bvcf_ctx *c, Slot &s) {
-  if (c->gate_on && c->gate.hwe_p > 0.0) HIP_TRY(c, s.d_gate_list.alloc(c->max_alleles + 1));
-  return BVCF_OK;
-}
+}  // namespace
 
-// bvcf_enable_bed_rows / bvcf_enable_trios: the row index both read -- the lines' first rows (follow max_lines), a row's map
-// (follows max_alleles) and the counter; the .bed arena and its pinned copy when the ctx's bound has grown past what the
-// slot holds
-int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
-  if (!c->bed_on && !c->trio_on && !c->ld_on) return BVCF_OK;
-  if (s.d_bed_base.size() < c->max_lines) {
-    HIP_TRY(c, s.d_bed_base.alloc(c->max_lines));
-    HIP_TRY(c, s.d_bed_tile.alloc(c->max_lines / kBedTile + 2));
-  }
-  if (s.d_bed_src.size() < c->max_alleles) HIP_TRY(c, s.d_bed_src.alloc(c->max_alleles));
-  if (!s.d_bed_total) {
-    HIP_TRY(c, s.d_bed_total.alloc(1));
-    HIP_TRY(c, s.h_bed_total.alloc(1));
-  }
-  // (the pairs read the arena on the device: only the fileset has a pinned copy of it)
-  if ((c->bed_on || c->ld_on) && (s.cap_bed < c->bed_cap || (c->bed_on && !s.h_bed))) {
-    s.cap_bed = 0;
-    HIP_TRY(c, s.d_bed.alloc(c->bed_cap + 16));
-    if (c->bed_on) HIP_TRY(c, s.h_bed.alloc(c->bed_cap + 16));
-    s.cap_bed = c->bed_cap;
-  }
-  return BVCF_OK;
-}
+#include "bvcf_analyses.hip.h"  // (the functions)
 
-// the events of max_alleles rows and, behind them, of their tiles of kTrioTile rows
-size_t trio_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kTrioTile + 2; }
-
-// bvcf_enable_trios: the counts, the events per row and per tile (follow max_alleles) and the counter; the events arena and its pinned
-// copy when the ctx's bound has grown past what the slot holds
-int alloc_trios(bvcf_ctx *c, Slot &s) {
-  if (!c->trio_on) return BVCF_OK;
-  if (!s.d_trio_counts) {
-    HIP_TRY(c, s.d_trio_counts.alloc(3ull * c->n_trios));
-    HIP_TRY(c, s.h_trio_counts.alloc(3ull * c->n_trios));
-    HIP_TRY(c, s.d_trio_total.alloc(1));
-    HIP_TRY(c, s.h_trio_total.alloc(1));
-  }
-  if (s.d_trio_rowev.size() < trio_rowev_words(c->max_alleles)) HIP_TRY(c, s.d_trio_rowev.alloc(trio_rowev_words(c->max_alleles)));
-  if (s.cap_trio < c->trio_cap) {
-    s.cap_trio = 0;
-    HIP_TRY(c, s.d_trio_ev.alloc(c->trio_cap));
-    HIP_TRY(c, s.h_trio_ev.alloc(c->trio_cap));
-    s.cap_trio = c->trio_cap;
-  }
-  return BVCF_OK;
-}
-
-// the events of max_alleles rows and, behind them, of their tiles of kLdTile rows
-size_t ld_rowev_words(uint64_t max_alleles) { return max_alleles + max_alleles / kLdTile + 2; }
-
-// bvcf_enable_ld: the keys and the events per row and per tile (follow max_alleles), the counter and the edge rows; the
-// events arena and its pinned copy when the ctx's bound has grown past what the slot holds
-int alloc_ld(bvcf_ctx *c, Slot &s) {
-  if (!c->ld_on) return BVCF_OK;
-  if (!s.d_ld_total) {
-    HIP_TRY(c, s.d_ld_total.alloc(1));
-    HIP_TRY(c, s.h_ld_total.alloc(1));
-    HIP_TRY(c, s.h_ld_edge.alloc(2ull * c->ld_window * ((c->n_samples + 3u) / 4u) + 16));
-  }
-  if (s.d_ld_key.size() < c->max_alleles) HIP_TRY(c, s.d_ld_key.alloc(c->max_alleles));
-  if (s.d_ld_rowev.size() < ld_rowev_words(c->max_alleles)) HIP_TRY(c, s.d_ld_rowev.alloc(ld_rowev_words(c->max_alleles)));
-  if (s.cap_ld < c->ld_cap) {
-    s.cap_ld = 0;
-    HIP_TRY(c, s.d_ld_ev.alloc(8ull * c->ld_cap));
-    HIP_TRY(c, s.h_ld_ev.alloc(8ull * c->ld_cap));
-    s.cap_ld = c->ld_cap;
-  }
-  return BVCF_OK;
-}
-
-int alloc_row_lists(bvcf_ctx *c, Slot &s) {
-  if (const int rc = alloc_gate_list(c, s)) return rc;
-  if (const int rc = alloc_bed_rows(c, s)) return rc;
-  if (const int rc = alloc_trios(c, s)) return rc;
-  if (const int rc = alloc_ld(c, s)) return rc;
-  if (!c->ss_on && !c->pr_on) return BVCF_OK;
-  s.d_pr_planes.reset();
-  s.cap_pr_tiles = 0;
-  HIP_TRY(c, s.d_ss_dense.alloc(c->max_alleles));
-  HIP_TRY(c, s.d_ss_sparse.alloc(c->max_alleles));
-  if (c->pr_on) {
-    const uint64_t tiles = (c->max_alleles + kPrTile - 1) / kPrTile;
-    HIP_TRY(c, s.d_pr_planes.alloc(tiles * kPrTables * 4ull * c->cmap_stride));
-    s.cap_pr_tiles = tiles;
-  }
-  return BVCF_OK;
-}
+namespace {
 
 // (re)allocate the result arrays of a slot for the ctx's current capacities
 int alloc_results(bvcf_ctx *c, Slot &s) {
@@ -684,14 +536,7 @@ int alloc_slot(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, s.d_entries.alloc(max_tiles * c->tile_quota));
     HIP_TRY(c, s.d_head_bits.alloc(max_tiles * c->tile_quota * 16));
   }
-  if (c->ss_on) {
-    const size_t table = (size_t)kSsCols * c->ss_ns_pad;
-    HIP_TRY(c, s.d_ss_ctr.alloc(4));
-    HIP_TRY(c, s.d_ss_part.alloc((size_t)c->ss_max_runs * table));
-    HIP_TRY(c, s.d_ss_sp.alloc(table));
-    HIP_TRY(c, s.d_ss_acc.alloc(6ull * c->ss_ns_pad));
-    HIP_TRY(c, hipMemset(s.d_ss_acc, 0, 6ull * c->ss_ns_pad * sizeof(unsigned long long)));
-  }
+  if (const int rc = alloc_ss_tables(c, s)) return rc;
   return alloc_results(c, s);
 }
 
@@ -704,7 +549,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.n_samples = c->n_samples;
   a.eol_chars = c->p.eol_chars;
   a.eol_byte = c->p.eol_byte;
-  a.want_cmap = c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on;  // (the per-sample, pair and trio counts and the .bed rows are made from the maps on the device)
+  a.want_cmap = c->p.want_class_maps || analyses_read_maps(c);
   a.cmap_stride = c->cmap_stride;
   a.max_lines = (uint32_t)c->max_lines;
   a.max_alleles = (uint32_t)c->max_alleles;
@@ -772,209 +617,6 @@ void adapt_stream_kernel(bvcf_ctx *c, bool was_gen, const BatchCounters &ctr) {
   if ((uint64_t)ctr.n_other_shape * 2u > ctr.n_lines) c->gen_mode = !was_gen;
 }
 
-SampleStatsArgs make_ss_args(bvcf_ctx *c, Slot &s) {
-  SampleStatsArgs sa{};
-  sa.dense = s.d_ss_dense;
-  sa.sparse = s.d_ss_sparse;
-  sa.ctr = s.d_ss_ctr;
-  sa.part = s.d_ss_part;
-  sa.sp = s.d_ss_sp;
-  sa.acc = s.d_ss_acc;
-  sa.list_cap = (uint32_t)s.d_ss_sparse.size();  // (the second of the two lists: there when both are)
-  sa.ns_pad = c->ss_ns_pad;
-  sa.max_runs = c->ss_max_runs;
-  sa.n_stripes = c->ss_stripes;
-  return sa;
-}
-
-PairStatsArgs make_pr_args(bvcf_ctx *c, Slot &s) {
-  PairStatsArgs pa{};
-  pa.dense = s.d_ss_dense;
-  pa.sparse = s.d_ss_sparse;
-  pa.ctr = s.d_ss_ctr;
-  pa.planes = s.d_pr_planes;
-  pa.bt = s.d_pr_bt;
-  pa.tot = c->d_pr_tot;
-  pa.list_cap = (uint32_t)s.d_ss_sparse.size();
-  pa.tile_cap = (uint32_t)s.cap_pr_tiles;
-  pa.ns = c->n_samples;
-  pa.ns_pad = 4u * c->cmap_stride;
-  pa.n_split = c->pr_split;
-  return pa;
-}
-
-SiteGateArgs make_gate_args(bvcf_ctx *c, Slot &s) {
-  SiteGateArgs ga{};
-  ga.g = c->gate;
-  if (c->gate.hwe_p > 0.0 && s.d_gate_list) {
-    ga.ctr = s.d_gate_list;
-    ga.list = s.d_gate_list + 1;
-    ga.list_cap = (uint32_t)(s.d_gate_list.size() - 1);
-  }
-  return ga;
-}
-
-// bvcf_set_site_gate: right behind k_finish, in front of every kernel that reads a record's ac -- the rows that fail are
-// taken out (bvcf_sitegate.hip.h); k_site_hwe settles the rows whose exact test is too long for one thread
-void launch_site_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
-  if (!c->gate_on || !slot) return;
-  const SiteGateArgs ga = make_gate_args(c, *slot);
-  if (ga.list) hipMemsetAsync(ga.ctr, 0, sizeof(uint32_t), st);
-  hipLaunchKernelGGL(k_site_gate, dim3(c->n_cu * kGateListWgs), dim3(kWgThreads), 0, st, a, ga);
-  if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, st, a, ga);
-}
-
-VariantGateArgs make_variant_args(const bvcf_ctx *c) {
-  VariantGateArgs va{};
-  va.entries = c->d_variant_entries;
-  va.blob = c->d_variant_blob;
-  va.mask = c->variants_mask;
-  va.exclude = c->variants_exclude;
-  return va;
-}
-
-uint32_t variant_gate_grid(const bvcf_ctx *c) { return (uint32_t)c->n_cu * kVariantGateWgs; }
-
-// bvcf_set_variant_list: right behind k_finish and in front of the site gate -- the rows the list does not select are
-// taken out (bvcf_variantlist.hip.h) before anything examines them
-void launch_variant_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st) {
-  if (!c->variants_on) return;
-  hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, st, a, make_variant_args(c));
-}
-
-// the slot holds everything the kernels of the row index write, sized for the ctx's current capacities
-bool index_ready(const bvcf_ctx *c, const Slot &s) {
-  return s.d_bed_total && s.d_bed_base.size() >= c->max_lines && s.d_bed_src.size() >= c->max_alleles;
-}
-
-// ... and the arena k_bed_rows writes
-bool bed_ready(const bvcf_ctx *c, const Slot &s) { return s.d_bed && index_ready(c, s); }
-
-// ... and everything the trio kernels write
-bool trios_ready(const bvcf_ctx *c, const Slot &s) {
-  return s.d_trio_ev && s.d_trio_counts && s.d_trio_total && s.d_trio_rowev.size() >= trio_rowev_words(c->max_alleles) && index_ready(c, s);
-}
-
-BedArgs make_bed_args(bvcf_ctx *c, Slot &s) {
-  BedArgs ba{};
-  ba.line_base = s.d_bed_base;
-  ba.tile_base = s.d_bed_tile;
-  ba.row_src = s.d_bed_src;
-  ba.row_cap = (uint32_t)s.d_bed_src.size();
-  ba.total = s.d_bed_total;
-  ba.out = s.d_bed;
-  ba.cap = s.cap_bed;
-  return ba;
-}
-
-// bvcf_enable_bed_rows: the end of a chain with samples -- every row's place in output order, then the rows themselves
-// into the slot's arena (bvcf_bedrows.hip.h; bvcf_collect copies the used part)
-void launch_bed_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
-  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ba);
-}
-
-void launch_row_index(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba) {
-  hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
-  hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, st, a, ba);
-  hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba);
-}
-
-// ... and everything the LD kernels write (the arena of the rows among it)
-bool ld_ready(const bvcf_ctx *c, const Slot &s) {
-  return s.d_ld_ev && s.d_ld_total && s.d_ld_key.size() >= c->max_alleles && s.d_ld_rowev.size() >= ld_rowev_words(c->max_alleles) &&
-         bed_ready(c, s);
-}
-
-LdArgs make_ld_args(bvcf_ctx *c, Slot &s) {
-  LdArgs la{};
-  la.window = c->ld_window;
-  la.t6 = c->ld_t6;
-  la.ev_rows = (uint32_t)c->max_alleles;
-  la.row_key = s.d_ld_key;
-  la.row_events = s.d_ld_rowev;
-  la.total = s.d_ld_total;
-  la.events = s.d_ld_ev;
-  la.cap = s.cap_ld;
-  return la;
-}
-
-constexpr int kLdPairWgs = 8;  // workgroups per CU (13 KB of LDS each)
-
-// bvcf_enable_ld: the rows' chrom keys, then count, scan and fill (bvcf_ld.hip.h; bvcf_collect copies the used part of the
-// events and the edge rows)
-void launch_ld_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const LdArgs &la) {
-  hipLaunchKernelGGL(k_ld_keys, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ba, la);
-  hipLaunchKernelGGL(k_ld_pairs<false>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
-  hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(1024), 0, st, a, ba, la);
-  hipLaunchKernelGGL(k_ld_pairs<true>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, st, a, ba, la);
-}
-
-TrioArgs make_trio_args(bvcf_ctx *c, Slot &s) {
-  TrioArgs ta{};
-  ta.trios = c->d_trios;
-  ta.n_trios = c->n_trios;
-  ta.ev_rows = (uint32_t)c->max_alleles;
-  ta.counts = s.d_trio_counts;
-  ta.row_events = s.d_trio_rowev;
-  ta.total = s.d_trio_total;
-  ta.events = s.d_trio_ev;
-  ta.cap = s.cap_trio;
-  return ta;
-}
-
-constexpr int kTrioCountWgs = 5, kTrioFillWgs = 4;  // (k_trio_count: 5 waves per SIMD is what its registers allow)  // workgroups per CU
-
-// bvcf_enable_trios: the batch's counts and the events per row from zero, then the three kernels (bvcf_mendel.hip.h;
-// bvcf_collect copies the counts and the used part of the events)
-int launch_trio_kernels(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const BedArgs &ba, const TrioArgs &ta) {
-  HIP_TRY(c, hipMemsetAsync(ta.counts, 0, 3ull * ta.n_trios * sizeof(uint32_t), st));
-  HIP_TRY(c, hipMemsetAsync(ta.row_events, 0, trio_rowev_words(ta.ev_rows) * sizeof(uint32_t), st));
-  hipLaunchKernelGGL(k_trio_count, dim3(c->n_cu * kTrioCountWgs), dim3(kWgThreads), 0, st, a, ba, ta);
-  hipLaunchKernelGGL(k_trio_scan, dim3(1), dim3(1024), 0, st, a, ba, ta);
-  hipLaunchKernelGGL(k_trio_fill, dim3(c->n_cu * kTrioFillWgs), dim3(kWgThreads), 0, st, a, ba, ta);
-  return BVCF_OK;
-}
-
-// the end of a chain with samples, with bvcf_enable_bed_rows and / or bvcf_enable_trios: every row's place in output order
-// -- once --, then the .bed rows into the slot's arena and the trios' counts and events into theirs
-void launch_trios(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
-  if (!slot) return;
-  const bool ld = c->ld_on && ld_ready(c, *slot);
-  const bool bed = (c->bed_on && bed_ready(c, *slot)) || ld, trios = c->trio_on && trios_ready(c, *slot);
-  if (!bed && !trios) return;
-  const BedArgs ba = make_bed_args(c, *slot);
-  launch_row_index(c, a, st, ba);
-  if (bed) launch_bed_rows(c, a, st, ba);
-  if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
-  if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)
-}
-
-// bvcf_params.want_sample_stats: the end of a chain with samples -- the batch's per-sample counts into the slot's tables
-// (bvcf_samplestats.hip.h; bvcf_collect folds them into the totals)
-// ... and, with bvcf_enable_pair_stats, the batch's pair tables from the same row lists (bvcf_pairstats.hip.h): the list
-// kernel runs once for both, and alone in front of the pair kernels when only they are on
-void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
-  if ((!c->ss_on && !c->pr_on) || !slot || !slot->d_ss_dense) return;
-  const SampleStatsArgs sa = make_ss_args(c, *slot);
-  hipMemsetAsync(sa.ctr, 0, 4 * sizeof(uint32_t), st);
-  if (c->ss_on) hipMemsetAsync(sa.sp, 0, (size_t)kSsCols * sa.ns_pad * sizeof(uint32_t), st);
-  hipLaunchKernelGGL(k_ss_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, sa);
-  if (c->ss_on) {
-    const uint32_t waves = c->ss_stripes * c->ss_max_runs;
-    hipLaunchKernelGGL(k_ss_dense, dim3((waves + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, a, sa);
-    hipLaunchKernelGGL(k_ss_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);  // (three dependent loads per list: many in flight)
-  }
-  if (c->pr_on && slot->d_pr_planes && slot->d_pr_bt) {
-    const PairStatsArgs pa = make_pr_args(c, *slot);
-    const uint32_t nb = pa.ns_pad / kPrBlock;
-    // (tiles dealt among several workgroups per pair block: the tables start from zero and are added to)
-    if (pa.n_split > 1) hipMemsetAsync(pa.bt, 0, (size_t)kPrTables * pa.ns * pa.ns * sizeof(uint32_t), st);
-    hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
-    hipLaunchKernelGGL(k_pr_gemm, dim3(nb, nb, pa.n_split), dim3(kWgThreads), 0, st, pa);
-    hipLaunchKernelGGL(k_pr_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, pa);
-  }
-}
-
 // a follower grid of the streaming chain.  k_head, k_gt and k_finish walk lists (left_lines, real_tasks, finish_items) with
 // grid strides: any grid is right.  A file of biallelic lines leaves them nearly empty, and a thousand workgroups that start
 // to find that out hold wave slots the next blocks' scans would use; the grids follow what the last collected batch left
@@ -1033,11 +675,9 @@ void launch_stream(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t 
                        dim3(kWgThreads), 0, st, a);
   if (!(skip & 4))
     hipLaunchKernelGGL(k_finish, dim3(follower_grid(c, n_cu * 4u, c->last_finish, kWgThreads)), dim3(kWgThreads), 0, st, a);
-  launch_variant_gate(c, a, st);
-  launch_site_gate(c, a, st, slot);
+  launch_gates(c, a, st, slot);
   if (a.dosage) hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
-  launch_sample_stats(c, a, st, slot);
-  launch_trios(c, a, st, slot);
+  launch_analyses(c, a, st, slot);
 }
 
 uint32_t census_grid(const bvcf_ctx *c, uint32_t n_chunks) {
@@ -1133,8 +773,7 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
   if (ev_gt1) hipEventRecord(ev_gt1, st);
   if (c->scan == BVCF_SCAN_NONE) return;
   hipLaunchKernelGGL(k_finish, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a);
-  launch_variant_gate(c, a, st);
-  launch_site_gate(c, a, st, slot);
+  launch_gates(c, a, st, slot);
   if (a.dosage) switch (c->scan) {
       case BVCF_SCAN_SUBSET: hipLaunchKernelGGL(k_dosage_subset, dim3(c->gt_subset_grid), dim3(kWgThreads), 0, st, a, fa, sa); break;
       case BVCF_SCAN_FILTER: hipLaunchKernelGGL(k_dosage_filter, dim3(c->gt_filter_grid), dim3(kWgThreads), 0, st, a, fa); break;
@@ -1142,13 +781,12 @@ void launch_census_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEv
         hipLaunchKernelGGL(k_dosage, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
         if (a.wide && a.win_tabs) hipLaunchKernelGGL(k_dosage_wide, dim3(c->gt_grid), dim3(kWgThreads), 0, st, a);
     }
-  launch_sample_stats(c, a, st, slot);
-  launch_trios(c, a, st, slot);
+  launch_analyses(c, a, st, slot);
 }
 
 // the kernel chain for one resident block; ev_gt0 / ev_gt1 (optional) bracket the dominant kernel (k_gt on the census path,
 // k_stream on the streaming path, k_sites* without samples)
-void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot = nullptr) {
+void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot) {
   switch (c->chain) {
     case BVCF_CHAIN_STREAM: return launch_stream(c, a, st, ev_gt0, ev_gt1, slot);
     case BVCF_CHAIN_SITES2_TILES:
@@ -1367,12 +1005,7 @@ int launch_batch(bvcf_ctx *c, Slot &s, const uint8_t *src, size_t nbytes) {
   }
   HIP_TRY(c, hipEventRecord(s.ev_k1, s.stream));
   HIP_TRY(c, hipMemcpyAsync(s.h_counters, s.d_counters, sizeof(BatchCounters), hipMemcpyDeviceToHost, s.stream));
-  if ((c->bed_on || c->trio_on || c->ld_on) && s.d_bed_total)
-    HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  if (c->ld_on && ld_ready(c, s))
-    HIP_TRY(c, hipMemcpyAsync(s.h_ld_total, s.d_ld_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  if (c->trio_on && trios_ready(c, s))
-    HIP_TRY(c, hipMemcpyAsync(s.h_trio_total, s.d_trio_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (const int rc = copy_arena_totals(c, s)) return rc;
   if (c->render) {
     HIP_TRY(c, hipMemcpyAsync(s.h_rtotals, s.d_rtotals, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
     // (Tried: as much of the stream as the last batch's rows-per-text ratio predicts copied to the host right here,
@@ -1849,10 +1482,7 @@ int bvcf_set_row_format(bvcf_ctx *c, const char *empty_field, int keep_pos, int 
 
 int bvcf_reserve(bvcf_ctx *c, uint64_t lines, uint64_t alleles, uint64_t cmap_bytes) {
   if (!c) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_reserve with batches in flight";
-    return BVCF_E_BUSY;
-  }
+  if (const int rc = refuse_in_flight(c, "bvcf_reserve")) return rc;
   if (lines > 0xFFFFFFF0ull || alleles > 0xFFFFFFF0ull) return BVCF_E_ARG;
   c->max_lines = std::max<uint64_t>(c->max_lines, lines);
   c->max_alleles = std::max<uint64_t>(std::max<uint64_t>(c->max_alleles, alleles), c->max_lines + 64);
@@ -2079,7 +1709,7 @@ static BatchNeeds batch_needs(const bvcf_ctx *c, const Slot &s, const BatchCount
   n.n_alleles = n.extras_at + ctr.n_alleles;
   n.n_tasks = (uint64_t)ctr.n_lines + ctr.n_tasks;
   n.need_alleles = std::max<uint64_t>(std::max<uint64_t>(n.n_alleles, ctr.n_errs), n.n_tasks);
-  const bool maps = (c->p.want_class_maps || c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on) && c->n_samples;
+  const bool maps = (c->p.want_class_maps || analyses_read_maps(c)) && c->n_samples;
   n.cmap_need = maps ? cmap_bytes_of(c, ctr) : 0;
   n.fits = ctr.n_lines <= s.cap_lines && n.need_alleles <= s.cap_alleles && n.cmap_need <= s.cap_cmap;
   return n;
@@ -2144,28 +1774,6 @@ static int packed_host_room(bvcf_ctx *c, Slot &s, const Collected &k) {
   }
   s.hcap_recs = want_recs;
   s.hcap_errs = want_errs;
-  return BVCF_OK;
-}
-
-// the batch is in: its per-sample counts join the slot's totals and its pair tables the ctx's (ahead of the copies on the
-// slot's stream)
-static int launch_folds(bvcf_ctx *c, Slot &s) {
-  if (c->ss_on && s.d_ss_dense) {
-    const uint32_t n_threads = kSsCols * c->ss_ns_pad;
-    hipLaunchKernelGGL(k_ss_fold, dim3((n_threads + kWgThreads - 1) / kWgThreads), dim3(kWgThreads), 0, s.stream,
-                       make_ss_args(c, s), c->n_samples);
-    HIP_TRY(c, hipGetLastError());
-  }
-  if (c->pr_on && s.d_pr_bt) {
-    // one fold after the other, whichever slots' streams they run on
-    if (c->pr_folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->ev_pr_fold, 0));
-    const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
-    const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
-    hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, s.stream, make_pr_args(c, s));
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_pr_fold, s.stream));
-    c->pr_folded = true;
-  }
   return BVCF_OK;
 }
 
@@ -2286,7 +1894,7 @@ static void fill_result(const bvcf_ctx *c, const Slot &s, const Collected &k, ui
   r->lines = s.h_lines;
   r->alleles = s.h_alleles;
   r->errs = s.h_errs;
-  r->cmap = ((c->ss_on || c->pr_on || c->bed_on || c->trio_on || c->ld_on) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
+  r->cmap = (analyses_read_maps(c) && !c->p.want_class_maps) ? nullptr : s.h_cmap.get();  // (maps kept on the device only: no host copy)
   r->dosage = c->dosage_stride ? s.h_dosage.get() : nullptr;
   r->dosage_stride = c->dosage_stride;
   r->text = k.was_bgzf ? s.h_text.get() : nullptr;
@@ -2367,29 +1975,12 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     c->err = "internal error: streaming tile quota or class-map slot range exceeded";
     return BVCF_E_HIP;
   }
-  // bvcf_enable_bed_rows: the rows the batch packs, against the slot's arena (a batch that does not fit otherwise may
-  // count too few: it asks again)
-  c->bed_last = bvcf_bed_rows_info{};
-  c->bed_last.row_bytes = c->bed_on ? (c->n_samples + 3u) / 4u : 0u;
-  const bool bed = c->bed_on && bed_ready(c, s);
-  const uint64_t bed_rows = bed ? *s.h_bed_total : 0, bed_bytes = bed_rows * c->bed_last.row_bytes;
-  c->bed_last.need_bytes = bed_bytes;
-  // bvcf_enable_ld: the rows again -- the pairs read the same arena --, and the batch's events against theirs
-  c->ld_last = bvcf_ld_info{};
-  const bool ld = c->ld_on && ld_ready(c, s);
-  const uint32_t ld_rb = (c->n_samples + 3u) / 4u;
-  const uint64_t ld_rows = ld ? *s.h_bed_total : 0, ld_events = ld ? *s.h_ld_total : 0;
-  c->ld_last.row_bytes = c->ld_on ? ld_rb : 0u;
-  c->ld_last.window = c->ld_window;
-  c->ld_last.need_events = ld_events;
-  c->ld_last.need_row_bytes = ld_rows * ld_rb;
-  // bvcf_enable_trios: likewise the batch's events against the slot's arena
-  c->trio_last = bvcf_trio_info{};
-  c->trio_last.n_trios = c->n_trios;
-  const bool trios = c->trio_on && trios_ready(c, s);
-  const uint64_t trio_events = trios ? *s.h_trio_total : 0;
-  c->trio_last.need_events = trio_events;
-  if (!k.need.fits || bed_bytes > s.cap_bed || trio_events > s.cap_trio || ld_rows * ld_rb > s.cap_bed || ld_events > s.cap_ld) {
+  // the arenas: what the batch asks of each, before the verdict
+  const bvcf_bed_rows_info bed = bed_need(c, s);
+  const bvcf_ld_info ld = ld_need(c, s);
+  const bvcf_trio_info trio = trio_need(c, s);
+  if (!k.need.fits || !s.bed.rows.fits(bed.need_bytes) || !s.trio.ev.fits(trio.need_events) || !s.bed.rows.fits(ld.need_row_bytes) ||
+      !s.ld.ev.fits(ld.need_events)) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
     r->need_alleles = k.need.need_alleles;
@@ -2412,21 +2003,9 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   if (!rc) rc = copy_records(c, s, k);
   if (!rc) rc = copy_text(c, s, k);
   if (!rc) rc = copy_names(c, s, k);
-  if (!rc && bed_bytes) HIP_TRY(c, hipMemcpyAsync(s.h_bed, s.d_bed, bed_bytes, hipMemcpyDeviceToHost, s.stream));
-  // (the table too comes over only now: until this collect the slot's pinned copy is the caller's, from the slot's last batch)
-  if (!rc && trios)
-    HIP_TRY(c, hipMemcpyAsync(s.h_trio_counts, s.d_trio_counts, 3ull * c->n_trios * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-  if (!rc && trio_events)
-    HIP_TRY(c, hipMemcpyAsync(s.h_trio_ev, s.d_trio_ev, trio_events * sizeof(uint2), hipMemcpyDeviceToHost, s.stream));
-  // (likewise the events and the batch's first and last rows, which the seam pairs with its neighbours')
-  const uint64_t ld_edge = std::min<uint64_t>(c->ld_window, ld_rows);
-  if (!rc && ld_events)
-    HIP_TRY(c, hipMemcpyAsync(s.h_ld_ev, s.d_ld_ev, ld_events * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
-  if (!rc && ld_edge) {
-    HIP_TRY(c, hipMemcpyAsync(s.h_ld_edge, s.d_bed, ld_edge * ld_rb, hipMemcpyDeviceToHost, s.stream));
-    HIP_TRY(c, hipMemcpyAsync(s.h_ld_edge + ld_edge * ld_rb, s.d_bed + (ld_rows - ld_edge) * ld_rb, ld_edge * ld_rb, hipMemcpyDeviceToHost,
-                              s.stream));
-  }
+  if (!rc) rc = bed_copy(c, s, bed);
+  if (!rc) rc = trio_copy(c, s, trio);
+  if (!rc) rc = ld_copy(c, s, ld);
   if (rc) return rc;
   e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) {
@@ -2434,23 +2013,9 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
     return BVCF_E_HIP;
   }
   fill_result(c, s, k, filter_errs(c, s, k), r);
-  if (bed) {
-    c->bed_last.rows = s.h_bed;
-    c->bed_last.n_rows = bed_rows;
-  }
-  if (trios) {
-    c->trio_last.counts = s.h_trio_counts;
-    c->trio_last.events = reinterpret_cast<const uint32_t *>(s.h_trio_ev.get());
-    c->trio_last.n_events = trio_events;
-  }
-  if (ld) {
-    c->ld_last.events = s.h_ld_ev;
-    c->ld_last.n_events = ld_events;
-    c->ld_last.n_rows = ld_rows;
-    c->ld_last.n_edge = (uint32_t)ld_edge;
-    c->ld_last.head_rows = s.h_ld_edge;
-    c->ld_last.tail_rows = s.h_ld_edge + ld_edge * ld_rb;
-  }
+  c->bed.last = bed;  // (published: until here the reports held the needs alone)
+  c->trio.last = trio;
+  c->ld.last = ld;
   add_totals(c, s, k, r);
   return BVCF_OK;
 }
@@ -2473,491 +2038,6 @@ int bvcf_collect(bvcf_ctx *c, bvcf_result *r) {
   release();
   return rc;
 }
-
-int bvcf_sample_stats(bvcf_ctx *c, uint64_t *out, int reset) {
-  if (!c) return BVCF_E_ARG;
-  if (!c->p.want_sample_stats) {
-    c->err = "bvcf_sample_stats: the ctx was created without bvcf_params.want_sample_stats";
-    return BVCF_E_ARG;
-  }
-  const uint32_t ns = c->n_samples;
-  if (out) memset(out, 0, 6ull * ns * sizeof(uint64_t));
-  if (!c->ss_on) return BVCF_OK;  // (no sample columns: an empty table)
-  HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<unsigned long long> t((size_t)6 * c->ss_ns_pad);
-  for (auto &s : c->slots) {
-    if (!s.d_ss_acc) continue;
-    HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
-    if (out) {
-      HIP_TRY(c, hipMemcpyAsync(t.data(), s.d_ss_acc, t.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-      HIP_TRY(c, hipStreamSynchronize(s.stream));
-      for (uint32_t col = 0; col < kSsCols; col++)
-        for (uint32_t i = 0; i < ns; i++) out[(size_t)col * ns + i] += t[(size_t)col * c->ss_ns_pad + i];
-      for (uint32_t i = 0; i < ns; i++) out[(size_t)kSsCols * ns + i] += t[(size_t)kSsCols * c->ss_ns_pad];
-    }
-    if (reset) {
-      HIP_TRY(c, hipMemsetAsync(s.d_ss_acc, 0, t.size() * sizeof(unsigned long long), s.stream));
-      HIP_TRY(c, hipStreamSynchronize(s.stream));
-    }
-  }
-  return BVCF_OK;
-}
-
-int bvcf_enable_pair_stats(bvcf_ctx *c) {
-  if (!c) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_enable_pair_stats with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (c->n_samples > BVCF_PAIR_MAX_SAMPLES) {
-    c->err = "bvcf_enable_pair_stats: " + std::to_string(c->n_samples) + " samples, the pair tables hold at most " +
-             std::to_string(BVCF_PAIR_MAX_SAMPLES);
-    return BVCF_E_ARG;
-  }
-  c->pr_asked = true;
-  if (!c->n_samples || c->pr_on) return BVCF_OK;  // (no sample columns: an empty table)
-  HIP_TRY(c, hipSetDevice(c->device));
-  const size_t n = (size_t)kPrTables * c->n_samples * c->n_samples;
-  HIP_TRY(c, c->d_pr_tot.alloc(n));
-  HIP_TRY(c, hipMemset(c->d_pr_tot, 0, n * sizeof(unsigned long long)));
-  HIP_TRY(c, c->ev_pr_fold.create(hipEventDisableTiming));
-  // a cohort of few samples has few pair blocks: the tiles of a block are then dealt to several workgroups
-  const uint64_t nb = 4ull * c->cmap_stride / kPrBlock;
-  c->pr_split = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, 2ull * (uint64_t)c->n_cu / (nb * nb)));
-  c->pr_on = true;
-  for (auto &s : c->slots) {
-    if (!s.d_ss_ctr) HIP_TRY(c, s.d_ss_ctr.alloc(4));
-    HIP_TRY(c, s.d_pr_bt.alloc(n));
-    HIP_TRY(c, hipMemset(s.d_pr_bt, 0, n * sizeof(uint32_t)));
-    const int rc = alloc_row_lists(c, s);
-    if (rc) return rc;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_pair_stats(bvcf_ctx *c, uint64_t *out, int reset) {
-  if (!c) return BVCF_E_ARG;
-  if (!c->pr_asked) {
-    c->err = "bvcf_pair_stats: bvcf_enable_pair_stats was not called on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (!c->pr_on) return BVCF_OK;  // (no sample columns: an empty table)
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (auto &s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
-  const size_t bytes = (size_t)kPrTables * c->n_samples * c->n_samples * sizeof(unsigned long long);
-  hipStream_t st = c->slots[0].stream;
-  if (out) HIP_TRY(c, hipMemcpyAsync(out, c->d_pr_tot, bytes, hipMemcpyDeviceToHost, st));
-  if (reset) HIP_TRY(c, hipMemsetAsync(c->d_pr_tot, 0, bytes, st));
-  HIP_TRY(c, hipStreamSynchronize(st));
-  return BVCF_OK;
-}
-
-int bvcf_enable_bed_rows(bvcf_ctx *c) {
-  if (!c) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_enable_bed_rows with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  c->bed_asked = true;
-  if (!c->n_samples || c->bed_on) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
-  HIP_TRY(c, hipSetDevice(c->device));
-  // a biallelic line has at least two text bytes per sample and gives a quarter byte per sample; lines with many ALTs at
-  // few samples outrun this and grow the arena (BVCF_E_CAPACITY, bvcf_reserve_bed_rows)
-  c->bed_cap = std::max<uint64_t>(c->bed_cap, c->p.max_batch_bytes / 4);
-  c->bed_on = true;
-  c->bed_last = bvcf_bed_rows_info{};
-  c->bed_last.row_bytes = (c->n_samples + 3u) / 4u;
-  for (auto &s : c->slots)
-    if (const int rc = alloc_bed_rows(c, s)) return rc;
-  return BVCF_OK;
-}
-
-int bvcf_reserve_bed_rows(bvcf_ctx *c, uint64_t bytes) {
-  if (!c) return BVCF_E_ARG;
-  if (!c->bed_asked && !c->ld_asked) {
-    c->err = "bvcf_reserve_bed_rows: bvcf_enable_bed_rows was not called on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (c->in_flight) {
-    c->err = "bvcf_reserve_bed_rows with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->bed_on && !c->ld_on) return BVCF_OK;
-  c->bed_cap = std::max<uint64_t>(c->bed_cap, (bytes + 63) & ~63ull);
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (auto &s : c->slots)
-    if (const int rc = alloc_bed_rows(c, s)) return rc;
-  return BVCF_OK;
-}
-
-int bvcf_bed_rows(const bvcf_ctx *c, bvcf_bed_rows_info *out) {
-  if (!c || !out || !c->bed_asked) return BVCF_E_ARG;
-  *out = c->bed_last;
-  return BVCF_OK;
-}
-
-int bvcf_enable_trios(bvcf_ctx *c, const uint32_t *trios, uint32_t n) {
-  if (!c || (n && !trios)) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_enable_trios with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (c->trio_asked) {
-    c->err = "bvcf_enable_trios: called twice on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (n >= kTrioMax) {
-    c->err = "bvcf_enable_trios: more than " + std::to_string(kTrioMax - 1) + " trios";
-    return BVCF_E_ARG;
-  }
-  for (uint32_t t = 0; t < n; t++) {
-    const uint32_t *x = trios + 3ull * t;
-    if (x[0] >= c->n_samples || x[1] >= c->n_samples || x[2] >= c->n_samples || x[0] == x[1] || x[0] == x[2] || x[1] == x[2]) {
-      c->err = "bvcf_enable_trios: trio " + std::to_string(t) + " names a sample index past the ctx's samples, or one sample twice";
-      return BVCF_E_ARG;
-    }
-  }
-  c->trio_asked = true;
-  c->trio_last = bvcf_trio_info{};
-  if (!n) return BVCF_OK;  // (no trios -- or no sample columns, which gives none: nothing allocated or launched)
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_trios.alloc(3ull * n + 16));  // (16 words at least: what trio_row reads for a row that is no short list)
-  HIP_TRY(c, hipMemset(c->d_trios, 0, (3ull * n + 16) * sizeof(uint32_t)));
-  HIP_TRY(c, hipMemcpy(c->d_trios, trios, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  c->n_trios = n;
-  // an event needs a call that contradicts the pedigree; real cohorts show a few per thousand (row, trio) pairs, and a
-  // line of text gives a row.  One event (8 bytes) per 64 bytes of text holds that with room; a wrong pedigree or a
-  // crafted file outruns it and grows the arena (BVCF_E_CAPACITY, bvcf_reserve_trio_events)
-  c->trio_cap = std::max<uint64_t>(c->trio_cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
-  c->trio_on = true;
-  c->trio_last.n_trios = n;
-  for (auto &s : c->slots) {
-    if (const int rc = alloc_bed_rows(c, s)) return rc;
-    if (const int rc = alloc_trios(c, s)) return rc;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_reserve_trio_events(bvcf_ctx *c, uint64_t n) {
-  if (!c) return BVCF_E_ARG;
-  if (!c->trio_asked) {
-    c->err = "bvcf_reserve_trio_events: bvcf_enable_trios was not called on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (c->in_flight) {
-    c->err = "bvcf_reserve_trio_events with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->trio_on) return BVCF_OK;
-  if (n > kTrioEventsMax) {
-    c->err = "bvcf_reserve_trio_events: a batch holds fewer than 2^32 events (smaller batches: max_batch_bytes)";
-    return BVCF_E_ARG;
-  }
-  c->trio_cap = std::max<uint64_t>(c->trio_cap, (n + 63) & ~63ull);
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (auto &s : c->slots)
-    if (const int rc = alloc_trios(c, s)) return rc;
-  return BVCF_OK;
-}
-
-int bvcf_trio_stats(const bvcf_ctx *c, bvcf_trio_info *out) {
-  if (!c || !out || !c->trio_asked) return BVCF_E_ARG;
-  *out = c->trio_last;
-  return BVCF_OK;
-}
-
-int bvcf_enable_ld(bvcf_ctx *c, uint32_t window, uint32_t t6) {
-  if (!c) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_enable_ld with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (c->ld_asked) {
-    c->err = "bvcf_enable_ld: called twice on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (window < 1 || window > bvcf_ld::kMaxWindow || t6 > bvcf_ld::kT6One) {
-    c->err = "bvcf_enable_ld: window must be 1 to 512 and t6 at most 1000000";
-    return BVCF_E_ARG;
-  }
-  if (c->n_samples >= bvcf_ld::kMaxSamples) {
-    c->err = "bvcf_enable_ld: " + std::to_string(c->n_samples) + " samples, the exact comparison holds below 2^24";
-    return BVCF_E_ARG;
-  }
-  c->ld_asked = true;
-  c->ld_window = window;
-  c->ld_t6 = t6;
-  c->ld_last = bvcf_ld_info{};
-  c->ld_last.window = window;
-  if (!c->n_samples) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
-  HIP_TRY(c, hipSetDevice(c->device));
-  // the rows' arena as bvcf_enable_bed_rows bounds it; an event (32 bytes) per 64 bytes of text to begin with: a line of
-  // text gives a row, and at the usual thresholds a row of a real cohort is in LD with a few of its 50 neighbours at
-  // most.  A threshold of 0, a long window or a file of copies of one line outruns that and grows the arena
-  // (BVCF_E_CAPACITY, bvcf_reserve_ld_events)
-  c->bed_cap = std::max<uint64_t>(c->bed_cap, c->p.max_batch_bytes / 4);
-  c->ld_cap = std::max<uint64_t>(c->ld_cap, std::max<uint64_t>(c->p.max_batch_bytes / 64, 1024));
-  c->ld_on = true;
-  c->ld_last.row_bytes = (c->n_samples + 3u) / 4u;
-  for (auto &s : c->slots) {
-    if (const int rc = alloc_bed_rows(c, s)) return rc;
-    if (const int rc = alloc_ld(c, s)) return rc;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_reserve_ld_events(bvcf_ctx *c, uint64_t n) {
-  if (!c) return BVCF_E_ARG;
-  if (!c->ld_asked) {
-    c->err = "bvcf_reserve_ld_events: bvcf_enable_ld was not called on the ctx";
-    return BVCF_E_ARG;
-  }
-  if (c->in_flight) {
-    c->err = "bvcf_reserve_ld_events with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->ld_on) return BVCF_OK;
-  if (n > kLdEventsMax / 8) {
-    c->err = "bvcf_reserve_ld_events: a batch holds fewer than 2^29 events (smaller batches: max_batch_bytes)";
-    return BVCF_E_ARG;
-  }
-  c->ld_cap = std::max<uint64_t>(c->ld_cap, (n + 63) & ~63ull);
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (auto &s : c->slots)
-    if (const int rc = alloc_ld(c, s)) return rc;
-  return BVCF_OK;
-}
-
-int bvcf_ld_stats(const bvcf_ctx *c, bvcf_ld_info *out) {
-  if (!c || !out || !c->ld_asked) return BVCF_E_ARG;
-  *out = c->ld_last;
-  return BVCF_OK;
-}
-
-int bvcf_ld_counts(const uint8_t *row_a, const uint8_t *row_b, uint32_t S, uint32_t out[6]) {
-  if (!row_a || !row_b || !out || !S) return -1;
-  bvcf_ld::counts_host(row_a, row_b, S, out);
-  return 0;
-}
-
-int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
-  if (!counts || t6 > bvcf_ld::kT6One || counts[0] >= bvcf_ld::kMaxSamples) return -1;
-  return bvcf_ld::in_ld(counts, t6) ? 1 : 0;
-}
-
-int bvcf_trio_verdict(uint32_t child, uint32_t father, uint32_t mother) {
-  if (child > 3u || father > 3u || mother > 3u) return -1;
-  return (int)trio_verdict(child, father, mother);
-}
-
-int bvcf_bed_row(const uint8_t *cmap_or_list, int sparse, uint32_t S, uint8_t *out) {
-  if (!out || !S) return -1;
-  bed_row_host(cmap_or_list, sparse != 0, S, out);
-  return (int)((S + 3u) / 4u);
-}
-
-void bvcf_site_gate_defaults(bvcf_site_gate *g) {
-  if (!g) return;
-  memset(g, 0, sizeof *g);
-  g->size = (uint32_t)sizeof *g;
-  g->max_maf = 1.0;
-  g->max_missing = 1.0;
-}
-
-// the ranges of bvcf_site_gate (a NaN fails every comparison)
-static bool site_gate_in_range(const bvcf_site_gate *g) {
-  return g->size == sizeof *g && g->min_mac <= BVCF_MAX_THRESHOLD && g->min_maf >= 0.0 && g->min_maf <= 0.5 && g->max_maf >= 0.0 &&
-         g->max_maf <= 1.0 && g->max_missing >= 0.0 && g->max_missing <= 1.0 && g->hwe_p >= 0.0 && g->hwe_p <= 1.0;
-}
-
-int bvcf_set_site_gate(bvcf_ctx *c, const bvcf_site_gate *g) {
-  if (!c) return BVCF_E_ARG;
-  if (!g || !site_gate_in_range(g)) {
-    c->err = "bvcf_set_site_gate: want size = sizeof(bvcf_site_gate), min_maf in [0, 0.5], max_maf, max_missing and hwe_p in [0, 1], "
-             "min_mac at most " + std::to_string(BVCF_MAX_THRESHOLD);
-    return BVCF_E_ARG;
-  }
-  if (c->in_flight) {
-    c->err = "bvcf_set_site_gate with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
-  c->gate = *g;
-  c->gate_on = g->min_maf > 0.0 || g->max_maf < 1.0 || g->min_mac > 0u || g->max_missing < 1.0 || g->hwe_p > 0.0;
-  HIP_TRY(c, hipSetDevice(c->device));
-  for (auto &s : c->slots)  // (the slots were sized by bvcf_create, before there was a gate)
-    if (const int rc = alloc_gate_list(c, s)) return rc;
-  return BVCF_OK;
-}
-
-void bvcf_site_gate_count(const bvcf_result *r, uint64_t out[7]) {
-  if (!out) return;
-  for (int q = 0; q < 7; q++) out[q] = 0;
-  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
-  for (uint32_t i = 0; i < r->n_lines; i++) {
-    const bvcf_line &L = r->lines[i];
-    if (L.status != BVCF_LINE_OK) continue;
-    for (uint32_t j = 0; j < L.n_rec; j++) {
-      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
-      const uint32_t bits = A.pad[0];
-      if (!bits && !A.ac) continue;  // (a row no sample carries: not examined)
-      out[0]++;
-      if (!bits) out[1]++;
-      for (int q = 0; q < 5; q++) out[2 + q] += (bits >> q) & 1u;
-    }
-  }
-}
-
-uint64_t bvcf_locus_hash(const char *s, size_t n) { return s ? fnv1a((const uint8_t *)s, n) : kFnvBasis; }
-
-uint64_t bvcf_variant_table_capacity(uint64_t n) { return n <= BVCF_VARIANT_MAX_ENTRIES ? variant_capacity(n) : 0; }
-
-// is the string s[0, n) an entry?  (the probe the device runs, on the host's table)
-static bool table_has(const VariantEntry *entries, const uint8_t *blob, uint32_t mask, const uint8_t *s, uint32_t n) {
-  return variant_find(entries, blob, mask, fnv1a(s, n), n, [&](LocusComparer &cmp) {
-    for (uint32_t i = 0; i < n; i++)
-      if (!cmp(s[i])) return false;
-    return true;
-  });
-}
-
-void bvcf_variant_table_free(bvcf_variant_table *t) {
-  if (!t) return;
-  free((void *)t->entries);
-  free((void *)t->blob);
-  memset(t, 0, sizeof *t);
-}
-
-int bvcf_variant_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, bvcf_variant_table *out) {
-  if (!out) return BVCF_E_ARG;
-  memset(out, 0, sizeof *out);
-  if (n && (!bytes || !off || !len)) return BVCF_E_ARG;
-  // the distinct entries first: the capacity follows their number
-  std::unordered_set<std::string_view> seen;
-  std::vector<uint64_t> first;
-  uint64_t blob_bytes = 0;
-  for (uint64_t i = 0; i < n; i++) {
-    if (!len[i]) return BVCF_E_ARG;  // (len == 0 marks an empty slot)
-    if (!seen.emplace(bytes + off[i], len[i]).second) continue;
-    first.push_back(i);
-    blob_bytes += len[i];
-    if (first.size() > BVCF_VARIANT_MAX_ENTRIES || blob_bytes >= (1ull << 32)) return BVCF_E_TOO_BIG;
-  }
-  const uint64_t cap = variant_capacity(first.size());
-  VariantEntry *entries = (VariantEntry *)calloc((size_t)cap, sizeof(VariantEntry));
-  uint8_t *blob = (uint8_t *)malloc((size_t)blob_bytes + 1);
-  if (!entries || !blob) {
-    free(entries);
-    free(blob);
-    return BVCF_E_NOMEM;
-  }
-  const uint32_t mask = (uint32_t)(cap - 1);
-  uint64_t at = 0;
-  for (const uint64_t i : first) {
-    const uint8_t *s = (const uint8_t *)bytes + off[i];
-    const unsigned long long h = fnv1a(s, len[i]);
-    uint32_t slot = (uint32_t)h & mask;
-    while (entries[slot].len) slot = (slot + 1u) & mask;
-    entries[slot] = VariantEntry{(uint32_t)(h >> 32), (uint32_t)at, len[i], 0u};
-    memcpy(blob + at, s, len[i]);
-    at += len[i];
-  }
-  out->entries = (const uint32_t *)entries;
-  out->capacity = cap;
-  out->blob = (const char *)blob;
-  out->blob_bytes = blob_bytes;
-  out->n = first.size();
-  return BVCF_OK;
-}
-
-int bvcf_variant_table_has(const bvcf_variant_table *t, const char *s, size_t n) {
-  if (!t || !t->entries || !t->capacity || (t->capacity & (t->capacity - 1)) || (!s && n) || n > 0xFFFFFFFFull) return -1;
-  return table_has((const VariantEntry *)t->entries, (const uint8_t *)t->blob, (uint32_t)(t->capacity - 1), (const uint8_t *)s, (uint32_t)n) ? 1 : 0;
-}
-
-// every entry lies in the blob, nothing is stored in the fourth word, the capacity is a power of two with an empty slot
-static bool variant_table_sound(const bvcf_variant_table *t) {
-  if (!t || !t->entries || t->capacity < 16 || t->capacity > (1ull << 31) || (t->capacity & (t->capacity - 1)) ||
-      t->blob_bytes >= (1ull << 32) || (t->blob_bytes && !t->blob))
-    return false;
-  const VariantEntry *e = (const VariantEntry *)t->entries;
-  uint64_t used = 0;
-  for (uint64_t i = 0; i < t->capacity; i++) {
-    if (!e[i].len) continue;
-    used++;
-    if ((uint64_t)e[i].off + e[i].len > t->blob_bytes) return false;
-  }
-  return used == t->n && 2 * used <= t->capacity;
-}
-
-int bvcf_set_variant_table(bvcf_ctx *c, const bvcf_variant_table *t, int exclude) {
-  if (!c) return BVCF_E_ARG;
-  if (!variant_table_sound(t)) {
-    c->err = "bvcf_set_variant_table: want a table as bvcf_variant_table_build makes it";
-    return BVCF_E_ARG;
-  }
-  if (c->in_flight) {
-    c->err = "bvcf_set_variant_table with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
-  c->variants_on = false;
-  c->d_variant_entries.reset();
-  c->d_variant_blob.reset();
-  if (exclude && !t->n) return BVCF_OK;  // (nothing to take out: nothing is allocated or launched)
-  HIP_TRY(c, hipSetDevice(c->device));
-  HIP_TRY(c, c->d_variant_entries.alloc((size_t)t->capacity));
-  HIP_TRY(c, c->d_variant_blob.alloc((size_t)t->blob_bytes + BVCF_DEVICE_PAD));
-  HIP_TRY(c, hipMemcpy(c->d_variant_entries, t->entries, (size_t)t->capacity * sizeof(VariantEntry), hipMemcpyHostToDevice));
-  if (t->blob_bytes) HIP_TRY(c, hipMemcpy(c->d_variant_blob, t->blob, (size_t)t->blob_bytes, hipMemcpyHostToDevice));
-  c->variants_mask = (uint32_t)(t->capacity - 1);
-  c->variants_exclude = exclude ? 1u : 0u;
-  c->variants_on = true;
-  return BVCF_OK;
-}
-
-int bvcf_set_variant_list(bvcf_ctx *c, const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int exclude) {
-  if (!c) return BVCF_E_ARG;
-  bvcf_variant_table t;
-  const int rc = bvcf_variant_table_build(bytes, off, len, n, &t);
-  if (rc) {
-    c->err = rc == BVCF_E_TOO_BIG ? "bvcf_set_variant_list: more than 2^27 distinct entries, or 4 GiB of them"
-                                  : "bvcf_set_variant_list: bad arguments (an entry of length 0?) or no memory";
-    return rc;
-  }
-  const int rc2 = bvcf_set_variant_table(c, &t, exclude);
-  bvcf_variant_table_free(&t);
-  return rc2;
-}
-
-void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]) {
-  if (!out) return;
-  out[0] = out[1] = out[2] = 0;
-  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
-  for (uint32_t i = 0; i < r->n_lines; i++) {
-    const bvcf_line &L = r->lines[i];
-    if (L.status != BVCF_LINE_OK) continue;
-    for (uint32_t j = 0; j < L.n_rec; j++) {
-      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
-      if (A.pad[1]) {
-        out[2]++;
-      } else if (A.ac || A.pad[0]) {  // (a row the site gate took out afterwards was kept here)
-        out[1]++;
-      }
-    }
-  }
-  out[0] = out[1] + out[2];
-}
-
-uint32_t bvcf_bench_variant_gate_stride(const bvcf_ctx *c) { return c ? variant_gate_grid(c) * kWgThreads : 0u; }
-
-int bvcf_site_gate_verdict(const bvcf_site_gate *g, uint32_t S, const uint32_t counts[5]) {
-  if (!g || !counts || !site_gate_in_range(g)) return -1;
-  return (int)site_gate_verdict(*g, S, counts[0], counts[1], counts[2], counts[3], counts[4]);
-}
-
-double bvcf_hwe_exact(uint32_t het, uint32_t hom, uint32_t other) { return hwe_exact_seq(het, hom, other); }
-uint32_t bvcf_hwe_inline_terms(void) { return kHweInlineTerms; }
 
 int bvcf_path(const bvcf_ctx *c) { return c ? (is_stream(c) ? 2 : 1) : BVCF_E_ARG; }
 int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && is_stream(c)) ? (c->gen_mode ? 1 : 0) : -1; }
@@ -3184,10 +2264,7 @@ int bvcf_bench_device(bvcf_ctx *c, const void *const *dblocks, const size_t *nby
 int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_t *nbytes, int n_blocks, int iters,
                             uint32_t slots_in_use, float *chain_ms, float *gt_ms, uint64_t counts[5]) {
   if (!c || !dblocks || !nbytes || n_blocks < 1 || iters < 1) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_device with batches in flight";
-    return BVCF_E_BUSY;
-  }
+  if (const int rc = refuse_in_flight(c, "bvcf_bench_device")) return rc;
   for (int b = 0; b < n_blocks; b++)
     if (!dblocks[b] || nbytes[b] > c->p.max_batch_bytes || nbytes[b] >= kMaxBlockBytes) return BVCF_E_TOO_BIG;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -3239,184 +2316,6 @@ int bvcf_bench_device_slots(bvcf_ctx *c, const void *const *dblocks, const size_
   return BVCF_OK;
 }
 
-int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
-  if (!c || !ms) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_pair_kernels with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  Slot &s = c->slots[0];
-  if (!c->pr_on || !s.d_pr_planes || !s.d_pr_bt) {
-    c->err = "bvcf_bench_pair_kernels: the ctx has no pair tables";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read a.cmap only)
-  const PairStatsArgs pa = make_pr_args(c, s);
-  const uint32_t nb = pa.ns_pad / kPrBlock;
-  const size_t n = (size_t)kPrTables * pa.ns * pa.ns;
-  Event ev[5];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  if (pa.n_split > 1) HIP_TRY(c, hipMemsetAsync(pa.bt, 0, n * sizeof(uint32_t), s.stream));
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  hipLaunchKernelGGL(k_pr_planes, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, pa);
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  hipLaunchKernelGGL(k_pr_gemm, dim3(nb, nb, pa.n_split), dim3(kWgThreads), 0, s.stream, pa);
-  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
-  hipLaunchKernelGGL(k_pr_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, pa);
-  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
-  const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
-  hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, s.stream, pa);
-  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  return BVCF_OK;
-}
-
-int bvcf_bench_bed_kernels(bvcf_ctx *c, float ms[2], uint64_t out[2]) {
-  if (!c || !ms || !out) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_bed_kernels with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  Slot &s = c->slots[0];
-  if (!c->bed_on || !bed_ready(c, s)) {
-    c->err = "bvcf_bench_bed_kernels: the ctx has no bed rows";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
-  const BedArgs ba = make_bed_args(c, s);
-  Event ev[3];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  hipLaunchKernelGGL(k_bed_count, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba);
-  hipLaunchKernelGGL(k_bed_scan, dim3(1), dim3(1024), 0, s.stream, a, ba);
-  hipLaunchKernelGGL(k_bed_index, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba);
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  hipLaunchKernelGGL(k_bed_rows, dim3(c->n_cu * 8), dim3(kWgThreads), 0, s.stream, a, ba);
-  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  for (int k = 0; k < 2; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  out[0] = *s.h_bed_total;
-  out[1] = out[0] * ((c->n_samples + 3u) / 4u);
-  if (out[1] > s.cap_bed) {
-    c->err = "bvcf_bench_bed_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[1]) + " bytes";
-    return BVCF_E_CAPACITY;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_bench_trio_kernels(bvcf_ctx *c, float ms[4], uint64_t out[2]) {
-  if (!c || !ms || !out) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_trio_kernels with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  Slot &s = c->slots[0];
-  if (!c->trio_on || !trios_ready(c, s)) {
-    c->err = "bvcf_bench_trio_kernels: the ctx has no trios";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records and a.cmap only)
-  const BedArgs ba = make_bed_args(c, s);
-  const TrioArgs ta = make_trio_args(c, s);
-  Event ev[5];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  launch_row_index(c, a, s.stream, ba);
-  HIP_TRY(c, hipMemsetAsync(ta.counts, 0, 3ull * ta.n_trios * sizeof(uint32_t), s.stream));
-  HIP_TRY(c, hipMemsetAsync(ta.row_events, 0, trio_rowev_words(ta.ev_rows) * sizeof(uint32_t), s.stream));
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  hipLaunchKernelGGL(k_trio_count, dim3(c->n_cu * kTrioCountWgs), dim3(kWgThreads), 0, s.stream, a, ba, ta);
-  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
-  hipLaunchKernelGGL(k_trio_scan, dim3(1), dim3(1024), 0, s.stream, a, ba, ta);
-  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
-  hipLaunchKernelGGL(k_trio_fill, dim3(c->n_cu * kTrioFillWgs), dim3(kWgThreads), 0, s.stream, a, ba, ta);
-  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(c, hipMemcpyAsync(s.h_trio_total, s.d_trio_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  for (int k = 0; k < 4; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  out[0] = *s.h_bed_total;
-  out[1] = *s.h_trio_total;
-  if (out[1] > s.cap_trio) {
-    c->err = "bvcf_bench_trio_kernels: the events outrun the arena (bvcf_reserve_trio_events): " + std::to_string(out[1]);
-    return BVCF_E_CAPACITY;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_bench_ld_kernels(bvcf_ctx *c, float ms[6], uint64_t out[2]) {
-  if (!c || !ms || !out) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_ld_kernels with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  Slot &s = c->slots[0];
-  if (!c->ld_on || !ld_ready(c, s)) {
-    c->err = "bvcf_bench_ld_kernels: bvcf_enable_ld was not called on the ctx, or it has no samples";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  // (k_ld_keys reads the lines' first fields: the block of the last bench call, which is still on the device)
-  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
-  const BedArgs ba = make_bed_args(c, s);
-  const LdArgs la = make_ld_args(c, s);
-  Event ev[7];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  launch_row_index(c, a, s.stream, ba);
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  launch_bed_rows(c, a, s.stream, ba);
-  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
-  hipLaunchKernelGGL(k_ld_keys, dim3(c->n_cu * 4), dim3(kWgThreads), 0, s.stream, a, ba, la);
-  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
-  hipLaunchKernelGGL(k_ld_pairs<false>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, s.stream, a, ba, la);
-  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
-  hipLaunchKernelGGL(k_ld_scan, dim3(1), dim3(1024), 0, s.stream, a, ba, la);
-  HIP_TRY(c, hipEventRecord(ev[5], s.stream));
-  hipLaunchKernelGGL(k_ld_pairs<true>, dim3(c->n_cu * kLdPairWgs), dim3(kWgThreads), 0, s.stream, a, ba, la);
-  HIP_TRY(c, hipEventRecord(ev[6], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipMemcpyAsync(s.h_bed_total, s.d_bed_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(c, hipMemcpyAsync(s.h_ld_total, s.d_ld_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  for (int k = 0; k < 6; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  out[0] = *s.h_bed_total;
-  out[1] = *s.h_ld_total;
-  if (out[0] * ((c->n_samples + 3u) / 4u) > s.cap_bed) {
-    c->err = "bvcf_bench_ld_kernels: the rows outrun the arena (bvcf_reserve_bed_rows): " + std::to_string(out[0]) + " rows";
-    return BVCF_E_CAPACITY;
-  }
-  if (out[1] > s.cap_ld) {
-    c->err = "bvcf_bench_ld_kernels: the events outrun the arena (bvcf_reserve_ld_events): " + std::to_string(out[1]);
-    return BVCF_E_CAPACITY;
-  }
-  return BVCF_OK;
-}
-
-int bvcf_bench_hwe(int device, const uint32_t *triples, uint32_t n, double *p) {
-  if (!triples || !p) return BVCF_E_ARG;
-  if (!n) return BVCF_OK;
-  if (hipSetDevice(device) != hipSuccess) return BVCF_E_NODEV;
-  int n_cu = 0;
-  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) return BVCF_E_HIP;
-  DevBuf<uint32_t> d_t;
-  DevBuf<double> d_p;
-  if (d_t.alloc(3ull * n) != hipSuccess || d_p.alloc(n) != hipSuccess) return BVCF_E_NOMEM;
-  if (hipMemcpy(d_t, triples, 3ull * n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) return BVCF_E_HIP;
-  const uint32_t grid = std::min<uint32_t>((n + kWavesPerWg - 1) / kWavesPerWg, (uint32_t)n_cu * kHweWgs);
-  hipLaunchKernelGGL(k_hwe_probe, dim3(grid), dim3(kWgThreads), 0, 0, (const uint32_t *)d_t, n, (double *)d_p);
-  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return BVCF_E_HIP;
-  return hipMemcpy(p, d_p, n * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
-}
-
 int bvcf_bench_deflate_codes(int device, const uint32_t *hist, uint32_t n, uint8_t *lens, uint16_t *rle, uint32_t *out) {
   if (!hist || !lens || !rle || !out) return BVCF_E_ARG;
   if (!n) return BVCF_OK;
@@ -3446,75 +2345,6 @@ int bvcf_bench_deflate_codes(int device, const uint32_t *hist, uint32_t n, uint8
       hipMemcpy(rle, d_rle, (size_t)n * n_rle * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(out, d_out, (size_t)n * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
     return BVCF_E_HIP;
-  return BVCF_OK;
-}
-
-int bvcf_bench_gate_kernels(bvcf_ctx *c, float ms[2]) {
-  if (!c || !ms) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_gate_kernels with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->gate_on || !c->bench_src) {
-    c->err = "bvcf_bench_gate_kernels: the ctx has no site gate, or no bvcf_bench_device* call went before";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  Slot &s = c->slots[0];
-  int rc = alloc_results(c, s);
-  if (rc) return rc;
-  // the chain of the last bench block once more with the gate off: the records as k_finish leaves them
-  s.s2_parity ^= 1u;
-  const KernelArgs a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
-  c->gate_on = false;
-  launch_chain(c, a, s.stream, nullptr, nullptr, &s);
-  c->gate_on = true;
-  const SiteGateArgs ga = make_gate_args(c, s);
-  Event ev[3];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  if (ga.list) HIP_TRY(c, hipMemsetAsync(ga.ctr, 0, sizeof(uint32_t), s.stream));
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  hipLaunchKernelGGL(k_site_gate, dim3(c->n_cu * kGateListWgs), dim3(kWgThreads), 0, s.stream, a, ga);
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  if (ga.list) hipLaunchKernelGGL(k_site_hwe, dim3(c->n_cu * kHweWgs), dim3(kWgThreads), 0, s.stream, a, ga);
-  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  for (int k = 0; k < 2; k++) hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-  if (!ga.list) ms[1] = 0.f;
-  return BVCF_OK;
-}
-
-int bvcf_bench_variant_kernel(bvcf_ctx *c, float *ms) {
-  if (!c || !ms) return BVCF_E_ARG;
-  if (c->in_flight) {
-    c->err = "bvcf_bench_variant_kernel with batches in flight";
-    return BVCF_E_BUSY;
-  }
-  if (!c->variants_on || !c->bench_src) {
-    c->err = "bvcf_bench_variant_kernel: the ctx has no variant list, or no bvcf_bench_device* call went before";
-    return BVCF_E_ARG;
-  }
-  HIP_TRY(c, hipSetDevice(c->device));
-  Slot &s = c->slots[0];
-  int rc = alloc_results(c, s);
-  if (rc) return rc;
-  // the chain of the last bench block once more with both gates off: the records as k_finish leaves them
-  s.s2_parity ^= 1u;
-  const KernelArgs a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
-  const bool gate_on = c->gate_on;
-  c->variants_on = c->gate_on = false;
-  launch_chain(c, a, s.stream, nullptr, nullptr, &s);
-  c->variants_on = true;
-  c->gate_on = gate_on;
-  Event ev[2];
-  for (auto &e : ev) HIP_TRY(c, e.create());
-  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
-  hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, s.stream, a, make_variant_args(c));
-  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
-  HIP_TRY(c, hipGetLastError());
-  HIP_TRY(c, hipStreamSynchronize(s.stream));
-  hipEventElapsedTime(ms, ev[0], ev[1]);
   return BVCF_OK;
 }
 

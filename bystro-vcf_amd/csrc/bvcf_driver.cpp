@@ -390,21 +390,9 @@ void Driver::device_main(DevWorker *W) {
       // grow, resubmit everything still queued on this device
       wait_formatted(n_jobs);
       outstanding.clear();
-      uint64_t bed_need = 0;
-      if (wants_plink(c_)) {
-        bvcf_bed_rows_info bi;
-        if (bvcf_bed_rows(W->ctx, &bi) == BVCF_OK) bed_need = bi.need_bytes;
-      }
-      uint64_t trio_need = 0;  // (--mendel / --mendelErrors: likewise the events)
-      if (R_.mendel_on) {
-        bvcf_trio_info ti;
-        if (bvcf_trio_stats(W->ctx, &ti) == BVCF_OK) trio_need = ti.need_events;
-      }
-      uint64_t ld_need = 0, ld_rows_need = 0;  // (--ld / --ldPrune: likewise the events, and the rows the pairs read)
-      if (R_.ld_on) {
-        bvcf_ld_info li;
-        if (bvcf_ld_stats(W->ctx, &li) == BVCF_OK) ld_need = li.need_events, ld_rows_need = li.need_row_bytes;
-      }
+      // (what the batch that asked reported, for its result arrays and for the analyses' arenas: read before the collects
+      // below replace the ctx's reports)
+      const BatchNeed need = read_batch_need(W->ctx, c_, res);
       // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
       const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
       if (ss) {
@@ -442,13 +430,8 @@ void Driver::device_main(DevWorker *W) {
         fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
         return;
       }
-      // (--plinkOutput: what the batch that asked reported for its .bed rows, read before the collects above replace it)
-      r = bvcf_reserve(W->ctx, res.need_lines + res.need_lines / 4 + 64, res.need_alleles + res.need_alleles / 4 + 64,
-                       res.need_cmap_bytes + res.need_cmap_bytes / 4 + 4096);
-      if (r == BVCF_OK && bed_need) r = bvcf_reserve_bed_rows(W->ctx, bed_need + bed_need / 4 + 4096);
-      if (r == BVCF_OK && trio_need) r = bvcf_reserve_trio_events(W->ctx, trio_need + trio_need / 4 + 1024);
-      if (r == BVCF_OK && ld_need) r = bvcf_reserve_ld_events(W->ctx, ld_need + ld_need / 4 + 1024);
-      if (r == BVCF_OK && ld_rows_need) r = bvcf_reserve_bed_rows(W->ctx, ld_rows_need + ld_rows_need / 4 + 4096);
+      // (grown with nothing in flight, before the batches are submitted again)
+      r = reserve_batch_need(W->ctx, need);
       for (size_t k = 0; k < in_flight.size() && r == BVCF_OK; k++) r = submit(in_flight[k]);
       if (r == BVCF_OK) {
         r = bvcf_collect(W->ctx, &res);

@@ -1185,14 +1185,6 @@ int write_mendel(Run &R, std::string *msg) {
   return BVCF_OK;
 }
 
-// --mendel / --mendelErrors, after a BVCF_E_CAPACITY: the events arena grown to what the batch reported
-int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c) {
-  if (!wants_mendel(c)) return BVCF_OK;
-  bvcf_trio_info t;
-  if (bvcf_trio_stats(ctx, &t) != BVCF_OK) return BVCF_OK;
-  return bvcf_reserve_trio_events(ctx, t.need_events + t.need_events / 4 + 1024);
-}
-
 int open_ld(Run &R, std::string *msg) {
   R.ld_on = wants_ld(R.cfg);
   if (!R.ld_on) return BVCF_OK;
@@ -1276,15 +1268,6 @@ int write_ld(Run &R, std::string *msg) {
   return BVCF_OK;
 }
 
-// --ld / --ldPrune, after a BVCF_E_CAPACITY: the events arena and the rows' arena grown to what the batch reported
-int reserve_ld_need(bvcf_ctx *ctx, const bvcf_config *c) {
-  if (!wants_ld(c)) return BVCF_OK;
-  bvcf_ld_info t;
-  if (bvcf_ld_stats(ctx, &t) != BVCF_OK) return BVCF_OK;
-  const int rc = bvcf_reserve_ld_events(ctx, t.need_events + t.need_events / 4 + 1024);
-  return rc ? rc : bvcf_reserve_bed_rows(ctx, t.need_row_bytes + t.need_row_bytes / 4 + 4096);
-}
-
 int close_dosage(Run &R) {
   if (!R.arrow) return BVCF_OK;
   const int rc = bvcf_arrow_close(R.arrow);
@@ -1292,12 +1275,30 @@ int close_dosage(Run &R) {
   return rc;
 }
 
-// --plinkOutput, after a BVCF_E_CAPACITY: the arena of the .bed rows grown to what the batch reported, like need_cmap_bytes
-int reserve_bed_need(bvcf_ctx *ctx, const bvcf_config *c) {
-  if (!wants_plink(c)) return BVCF_OK;
+// What a batch that came back BVCF_E_CAPACITY reported: the three needs of its bvcf_result and, of the analyses the run has
+// on, those of their arenas -- the .bed rows like need_cmap_bytes (--plinkOutput), the trios' events (--mendel /
+// --mendelErrors), the pairs' events and the rows the pairs read (--ld / --ldPrune).  The reports are the ctx's, of the batch
+// collected last: read right after the failed collect, before anything else is collected
+BatchNeed read_batch_need(bvcf_ctx *ctx, const bvcf_config *c, const bvcf_result &res) {
+  BatchNeed n{res.need_lines, res.need_alleles, res.need_cmap_bytes, 0, 0, 0, 0};
   bvcf_bed_rows_info b;
-  if (bvcf_bed_rows(ctx, &b) != BVCF_OK) return BVCF_OK;
-  return bvcf_reserve_bed_rows(ctx, b.need_bytes + b.need_bytes / 4 + 4096);
+  if (wants_plink(c) && bvcf_bed_rows(ctx, &b) == BVCF_OK) n.bed_bytes = b.need_bytes;
+  bvcf_trio_info t;
+  if (wants_mendel(c) && bvcf_trio_stats(ctx, &t) == BVCF_OK) n.trio_events = t.need_events;
+  bvcf_ld_info l;
+  if (wants_ld(c) && bvcf_ld_stats(ctx, &l) == BVCF_OK) n.ld_events = l.need_events, n.ld_row_bytes = l.need_row_bytes;
+  return n;
+}
+
+// ... and the reservations grown to it, with nothing in flight: a quarter more than asked, so that the next batches fit too
+int reserve_batch_need(bvcf_ctx *ctx, const BatchNeed &n) {
+  auto more = [](uint64_t need, uint64_t least) { return need + need / 4 + least; };
+  int rc = bvcf_reserve(ctx, more(n.lines, 64), more(n.alleles, 64), more(n.cmap_bytes, 4096));
+  if (rc == BVCF_OK && n.bed_bytes) rc = bvcf_reserve_bed_rows(ctx, more(n.bed_bytes, 4096));
+  if (rc == BVCF_OK && n.trio_events) rc = bvcf_reserve_trio_events(ctx, more(n.trio_events, 1024));
+  if (rc == BVCF_OK && n.ld_events) rc = bvcf_reserve_ld_events(ctx, more(n.ld_events, 1024));
+  if (rc == BVCF_OK && n.ld_row_bytes) rc = bvcf_reserve_bed_rows(ctx, more(n.ld_row_bytes, 4096));
+  return rc;
 }
 
 // submit one block and collect it, growing the result reservation when the batch asks for it
@@ -1314,11 +1315,7 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
       *msg = std::string("bvcf_collect: ") + bvcf_last_error(R.ctx);
       return rc;
     }
-    rc = bvcf_reserve(R.ctx, res->need_lines + res->need_lines / 4 + 64, res->need_alleles + res->need_alleles / 4 + 64,
-                      res->need_cmap_bytes + res->need_cmap_bytes / 4 + 4096);
-    if (rc == BVCF_OK) rc = reserve_bed_need(R.ctx, R.cfg);
-    if (rc == BVCF_OK) rc = reserve_trio_need(R.ctx, R.cfg);
-    if (rc == BVCF_OK) rc = reserve_ld_need(R.ctx, R.cfg);
+    rc = reserve_batch_need(R.ctx, read_batch_need(R.ctx, R.cfg, *res));
     if (rc) {
       *msg = std::string("bvcf_reserve: ") + bvcf_last_error(R.ctx);
       return rc;
@@ -1327,10 +1324,6 @@ int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_res
   *msg = "result reservation did not converge";
   return BVCF_E_CAPACITY;
 }
-
-
-
-
 
 int open_sample_stats(const bvcf_config *c, int *fd, std::string *msg) {
   *fd = -1;

@@ -282,7 +282,6 @@ int open_plink(Run &R, std::string *msg);
 int append_plink(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_bed_rows_info &bed);
 int close_plink(Run &R);
 int write_plink_heads(Run &R);  // (prepare_run: the .fam and the .bed magic)
-int reserve_bed_need(bvcf_ctx *ctx, const bvcf_config *c);
 // --mendel / --mendelErrors: the files opened (truncated) -- BVCF_E_IO with one message in *msg; the pedigree read and
 // matched against the (kept) names (prepare_run) -- BVCF_E_IO with one message; the counts and events of one collected batch
 // (ti = what bvcf_trio_stats gave for it) added to the run's -- BVCF_E_FATAL when the events name a row the batch does not
@@ -292,7 +291,6 @@ int load_pedigree(Run &R, std::string *msg);
 int append_mendel(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_trio_info &ti);
 int write_mendel(Run &R, std::string *msg);
 void close_mendel(Run &R);
-int reserve_trio_need(bvcf_ctx *ctx, const bvcf_config *c);
 // --ld / --ldPrune: the files opened (truncated) and the window and threshold checked -- BVCF_E_IO / BVCF_E_ARG with one
 // message in *msg; the events, edge rows and loci of one collected batch (li = what bvcf_ld_stats gave for it) pushed into
 // the run's seam -- BVCF_E_FATAL when they contradict the batch's rows; the files written and closed at the end of a
@@ -301,8 +299,15 @@ int open_ld(Run &R, std::string *msg);
 int append_ld(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_ld_info &li);
 int write_ld(Run &R, std::string *msg);
 void close_ld(Run &R);
-int reserve_ld_need(bvcf_ctx *ctx, const bvcf_config *c);
 int close_dosage(Run &R);
+// the grow path after a BVCF_E_CAPACITY, for bvcf_run_buffer and the driver alike: what the batch reported (read right after the
+// failed collect), and every reservation grown to it with its margin
+struct BatchNeed {
+  uint64_t lines, alleles, cmap_bytes;                        // bvcf_result.need_*
+  uint64_t bed_bytes, trio_events, ld_events, ld_row_bytes;  // bvcf_bed_rows / bvcf_trio_stats / bvcf_ld_stats
+};
+BatchNeed read_batch_need(bvcf_ctx *ctx, const bvcf_config *c, const bvcf_result &res);
+int reserve_batch_need(bvcf_ctx *ctx, const BatchNeed &n);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
 // --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
 // and, at the end of a successful run, the table of the summed per-sample counts t (bvcf_sample_stats layout) written
