@@ -34,6 +34,7 @@ NO_CMAP = 0xFFFFFFFF
 
 OK, E_ARG, E_HIP, E_NODEV, E_BUSY, E_EMPTY, E_TOO_BIG, E_CAPACITY, E_NOMEM, E_FATAL = 0, -1, -2, -3, -4, -5, -6, -7, -8, -9
 LINE_OK, LINE_FIELDS, LINE_FILTER, LINE_NOALLELE = 0, 1, 2, 3
+ALLELE_POS_TEXT = 1  # BVCF_ALLELE_POS_TEXT in bvcf_allele.flags: the output pos is the POS field verbatim, the record's pos is 0
 SITE_NAMES = ["SNP", "INS", "DEL", "MNP", "MULTIALLELIC"]
 ALT_BASE, ALT_INS, ALT_DEL = 0, 1, 2
 CLS_NONE, CLS_HET, CLS_HOM, CLS_MISSING = 0, 1, 2, 3
@@ -48,7 +49,8 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
                  "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
-                 "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride"]
+                 "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
+                 "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -71,6 +73,9 @@ EXPORTS = [
     "bvcf_locus_hash", "bvcf_variant_table_capacity", "bvcf_variant_table_build", "bvcf_variant_table_parse",
     "bvcf_variant_table_free", "bvcf_variant_table_has", "bvcf_set_variant_table", "bvcf_set_variant_list",
     "bvcf_variant_gate_count", "bvcf_config_variants_defaults",
+    "bvcf_region_table_parse_specs", "bvcf_region_table_parse_bed", "bvcf_region_table_build", "bvcf_region_table_free",
+    "bvcf_region_table_has", "bvcf_region_table_stays", "bvcf_set_region_table", "bvcf_region_gate_count",
+    "bvcf_config_regions_defaults",
 ]
 
 
@@ -267,6 +272,121 @@ class VariantTable:
             self.close()
         except Exception:
             pass
+
+
+CONFIG_MORE_REGIONS = 6  # BVCF_CONFIG_MORE_REGIONS in Config.reserved[1]: the ConfigVariants is the head of a ConfigRegions
+REGION_MAX_INTERVALS = 1 << 26  # BVCF_REGION_MAX_INTERVALS
+REGION_MAX_CHROMS = 1 << 20  # BVCF_REGION_MAX_CHROMS
+# the lines of the --regionFilterReport file; region_gate_count() gives the last three
+REGION_REPORT = ["keepIntervals", "excludeIntervals", "examined", "kept", "dropped"]
+REGION_CHROM_DTYPE = np.dtype([("tag", "<u4"), ("off", "<u4"), ("len", "<u4"), ("zero", "<u4"), ("first", "<u4", (2,)),
+                               ("n", "<u4", (2,))])
+REGION_INTERVAL_DTYPE = np.dtype([("beg", "<i8"), ("end", "<i8")])
+REGION_CONFIG_KEYS = (("regions", "regions"), ("regionsFile", "regions_path"), ("excludeRegions", "exclude_regions"),
+                      ("excludeRegionsFile", "exclude_regions_path"), ("regionFilterReport", "region_filter_path"))
+
+
+class ConfigRegions(C.Structure):
+    """bvcf_config_regions: a bvcf_config_variants and what came after it"""
+    _fields_ = [("variants", ConfigVariants), ("regions", C.c_char_p), ("regions_path", C.c_char_p),
+                ("exclude_regions", C.c_char_p), ("exclude_regions_path", C.c_char_p), ("region_filter_path", C.c_char_p)]
+
+
+class RegionTableStruct(C.Structure):
+    """bvcf_region_table"""
+    _fields_ = [("chroms", C.c_void_p), ("capacity", C.c_uint64), ("blob", C.c_void_p), ("blob_bytes", C.c_uint64),
+                ("intervals", C.c_void_p), ("n_intervals", C.c_uint64), ("n_chroms", C.c_uint64), ("n_keep", C.c_uint64),
+                ("n_exclude", C.c_uint64), ("keep_given", C.c_uint32), ("max_name", C.c_uint32), ("raw", C.c_void_p)]
+
+
+class RegionTable:
+    """a host table of regions: SPEC lists (keep= / exclude=, bytes) and BED texts (keep_bed= / exclude_bed=, bytes) go
+    through bvcf_region_table_parse_specs / _parse_bed, then bvcf_region_table_build.  A keep argument that is not None
+    gives a keep set, even an empty one (b"" as keep_bed; an empty SPEC list is an error).  A parse error raises
+    BvcfError with the library's message  (host code, no device)"""
+
+    def __init__(self, keep=None, keep_bed=None, exclude=None, exclude_bed=None):
+        self.t = RegionTableStruct()
+        err = C.create_string_buffer(256)
+        for fn in (lib.bvcf_region_table_parse_specs, lib.bvcf_region_table_parse_bed):
+            fn.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_int, C.c_char_p, C.c_size_t]
+        for text, fn, excl in ((keep, lib.bvcf_region_table_parse_specs, 0), (keep_bed, lib.bvcf_region_table_parse_bed, 0),
+                               (exclude, lib.bvcf_region_table_parse_specs, 1), (exclude_bed, lib.bvcf_region_table_parse_bed, 1)):
+            if text is None:
+                continue
+            rc = fn(C.byref(self.t), bytes(text), len(text), excl, err, len(err))
+            if rc:
+                self.close()
+                raise BvcfError(rc, err.value.decode(errors="replace"))
+        lib.bvcf_region_table_build.argtypes = [C.c_void_p]
+        rc = lib.bvcf_region_table_build(C.byref(self.t))
+        if rc:
+            self.close()
+            raise BvcfError(rc, "bvcf_region_table_build")
+
+    n_keep = property(lambda self: int(self.t.n_keep))
+    n_exclude = property(lambda self: int(self.t.n_exclude))
+    n_chroms = property(lambda self: int(self.t.n_chroms))
+    capacity = property(lambda self: int(self.t.capacity))
+    keep_given = property(lambda self: bool(self.t.keep_given))
+
+    @property
+    def blob(self):
+        return C.string_at(self.t.blob, self.t.blob_bytes) if self.t.blob_bytes else b""
+
+    @property
+    def chroms(self):
+        """the slots as a REGION_CHROM_DTYPE array (copied)"""
+        n = self.capacity * REGION_CHROM_DTYPE.itemsize
+        return np.frombuffer(C.string_at(self.t.chroms, n), dtype=REGION_CHROM_DTYPE).copy()
+
+    @property
+    def intervals(self):
+        """all intervals as a REGION_INTERVAL_DTYPE array (copied); a name's are [first[s], first[s] + n[s])"""
+        n = int(self.t.n_intervals) * REGION_INTERVAL_DTYPE.itemsize
+        return np.frombuffer(C.string_at(self.t.intervals, n) if n else b"", dtype=REGION_INTERVAL_DTYPE).copy()
+
+    def merged(self, exclude=False):
+        """{normalised name: [(beg, end), ...]} of one set, as the table holds it"""
+        iv, blob, s, out = self.intervals, self.blob, int(bool(exclude)), {}
+        for c in self.chroms:
+            if c["len"] and c["n"][s]:
+                f = int(c["first"][s])
+                out[blob[int(c["off"]):int(c["off"]) + int(c["len"])]] = [(int(x["beg"]), int(x["end"])) for x in iv[f:f + int(c["n"][s])]]
+        return out
+
+    def has(self, chrom, pos, alt):
+        """bvcf_region_table_has: the lookup the device runs, for a row's TSV columns (bytes) -> bit 0: overlaps the keep
+        set, bit 1: the exclude set"""
+        lib.bvcf_region_table_has.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        r = lib.bvcf_region_table_has(C.byref(self.t), bytes(chrom), len(chrom), bytes(pos), len(pos), bytes(alt), len(alt))
+        if r < 0:
+            raise ValueError("bvcf_region_table_has: bad arguments")
+        return int(r)
+
+    def stays(self, chrom, pos, alt):
+        """the rule of the flags on has()'s bits (bvcf_region_table_stays)"""
+        lib.bvcf_region_table_stays.argtypes = [C.c_void_p, C.c_int]
+        return bool(lib.bvcf_region_table_stays(C.byref(self.t), self.has(chrom, pos, alt)))
+
+    def close(self):
+        lib.bvcf_region_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_region_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def region_gate_count(result):
+    """bvcf_region_gate_count over a collected batch (a Result) -> [examined, kept, dropped]"""
+    out = (C.c_uint64 * 3)()
+    lib.bvcf_region_gate_count.restype = None
+    lib.bvcf_region_gate_count.argtypes = [C.c_void_p, C.c_void_p]
+    lib.bvcf_region_gate_count(C.byref(result), out)
+    return [int(x) for x in out]
 
 
 def variant_gate_count(result):
@@ -494,7 +614,10 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--mendel / --mendelErrors: the larger struct and its marker, only then; every other config is a ConfigMore as before)
     # (--ld / --ldPrune: the still larger struct and its marker, only then)
     # (--keepVariants / --excludeVariants / --variantFilterReport: the largest struct and its marker, only then)
-    vc = ConfigVariants() if any(cfg.get(k) for k in ("keepVariants", "excludeVariants", "variantFilterReport")) else None
+    # (--regions / --excludeRegions, their files, --regionFilterReport: the struct behind that one and its marker, only then)
+    rgc = ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
+    vc = (rgc.variants if rgc is not None else
+          ConfigVariants() if any(cfg.get(k) for k in ("keepVariants", "excludeVariants", "variantFilterReport")) else None)
     ldc = vc.ld if vc is not None else ConfigLd() if cfg.get("ld") or cfg.get("ldPrune") else None
     trios = ldc.trios if ldc is not None else ConfigTrios() if cfg.get("mendel") or cfg.get("mendelErrors") else None
     more = trios.more if trios is not None else ConfigMore()
@@ -580,6 +703,12 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 keep.append(str(cfg[key]).encode())
                 setattr(vc, field, keep[-1])
         c.reserved[1] = CONFIG_MORE_VARIANTS
+    if rgc is not None:  # the regions and their report
+        for key, field in REGION_CONFIG_KEYS:
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(rgc, field, keep[-1])
+        c.reserved[1] = CONFIG_MORE_REGIONS
     c._keep = keep
     return c
 
@@ -915,6 +1044,7 @@ class Batch:
         self._result = r
         self._gate_counts = None
         self._variant_counts = None  # bvcf_variant_gate_count, likewise
+        self._region_counts = None  # bvcf_region_gate_count, likewise
         self.n_samples = r.n_samples
         self.cmap_stride = r.cmap_stride
         self.kernel_ms = r.kernel_ms
@@ -1024,6 +1154,12 @@ class Batch:
             self._variant_counts = variant_gate_count(self._result)
         return self._variant_counts
 
+    @property
+    def region_counts(self):
+        if self._region_counts is None:
+            self._region_counts = region_gate_count(self._result)
+        return self._region_counts
+
     def record_slots(self, i):
         """indices into alleles[] (and dosage[]) of line i's output alleles, in order"""
         L = self.lines[i]
@@ -1066,7 +1202,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None):
+                 variants=None, regions=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1106,6 +1242,12 @@ class Ctx:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
                 raise BvcfError(rc, msg)
+        if regions is not None:  # bvcf_set_region_table: a built RegionTable
+            try:
+                self.set_region_table(regions)
+            except BvcfError:
+                self.close()
+                raise
         if variants is not None:  # bvcf_set_variant_list / bvcf_set_variant_table: (loci or a VariantTable, exclude)
             try:
                 self.set_variant_list(*variants)
@@ -1257,6 +1399,24 @@ class Ctx:
         lib.bvcf_set_variant_list.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
         self._check(lib.bvcf_set_variant_list(self.h, blob, offs.ctypes.data if len(loci) else None,
                                               lens.ctypes.data if len(loci) else None, len(loci), int(bool(exclude))))
+
+    def set_region_table(self, table):
+        """before the first submit: a built RegionTable (bvcf_set_region_table)"""
+        lib.bvcf_set_region_table.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_set_region_table(self.h, C.byref(table.t)))
+
+    def region_gate_stride(self):
+        """the alleles[] slots k_region_gate's grid covers in one step"""
+        lib.bvcf_bench_region_gate_stride.restype = C.c_uint32
+        lib.bvcf_bench_region_gate_stride.argtypes = [C.c_void_p]
+        return int(lib.bvcf_bench_region_gate_stride(self.h))
+
+    def bench_region_kernel(self):
+        """k_region_gate over the last bench block of the ctx -> ms"""
+        ms = C.c_float()
+        lib.bvcf_bench_region_kernel.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_bench_region_kernel(self.h, C.byref(ms)))
+        return float(ms.value)
 
     def variant_gate_stride(self):
         """the alleles[] slots k_variant_gate's grid covers in one step"""

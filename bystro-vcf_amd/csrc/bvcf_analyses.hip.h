@@ -1,4 +1,4 @@
-// bvcf_analyses.hip.h — the host half of the analyses behind k_finish: the site gate and the variant gate, the row index with
+// bvcf_analyses.hip.h — the host half of the analyses behind k_finish: the site gate, the variant gate and the region gate, the row index with
 // the .bed rows, the trios and the LD pairs on it, the per-sample and the pair counts.  Per analysis one struct of what a slot
 // owns and one of what the ctx owns, then its functions next to each other: allocate for the ctx's current capacities,
 // ready, kernel args, launch, its part of collect, its entries of the C-ABI, its bench hook.  The kernels are in the
@@ -57,6 +57,16 @@ struct VariantGateCtx {
   uint32_t exclude = 0, mask = 0;
   DevBuf<VariantEntry> entries;
   DevBuf<uint8_t> blob;
+};
+
+// bvcf_set_region_table on a file with samples: k_region_gate behind k_finish, in front of the variant gate; the table
+// (bvcf_regions.hip.h) is the ctx's, read by the batches of every slot
+struct RegionGateCtx {
+  bool on = false;
+  uint32_t mask = 0, max_name = 0, keep_on = 0, exclude_on = 0;
+  DevBuf<RegionChrom> chroms;
+  DevBuf<uint8_t> blob;
+  DevBuf<RegionInterval> intervals;
 };
 
 // the row index the .bed rows, the trios and the LD pairs share (bvcf_bedrows.hip.h), built once when any of them is on:
@@ -280,16 +290,18 @@ uint32_t bvcf_hwe_inline_terms(void) { return kHweInlineTerms; }
 
 // the chain of the last bench block once more with the variant gate (and the site gate) off: the records as k_finish
 // leaves them, for the gates' hooks
-static int launch_ungated(bvcf_ctx *c, Slot &s, KernelArgs *a, bool variants_too) {
+static int launch_ungated(bvcf_ctx *c, Slot &s, KernelArgs *a, bool variants_too, bool regions_too = false) {
   if (const int rc = alloc_results(c, s)) return rc;
   s.s2_parity ^= 1u;
   *a = make_args(c, s, (const uint8_t *)c->bench_src, c->bench_nbytes);
-  const bool gate_on = c->gate.on, variants_on = c->variants.on;
+  const bool gate_on = c->gate.on, variants_on = c->variants.on, regions_on = c->regions.on;
   c->gate.on = false;
   if (variants_too) c->variants.on = false;
+  if (regions_too) c->regions.on = false;
   launch_chain(c, *a, s.stream, nullptr, nullptr, &s);
   c->gate.on = gate_on;
   c->variants.on = variants_on;
+  c->regions.on = regions_on;
   return BVCF_OK;
 }
 
@@ -343,8 +355,30 @@ static void launch_variant_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st
   hipLaunchKernelGGL(k_variant_gate, dim3(variant_gate_grid(c)), dim3(kWgThreads), 0, st, a, make_variant_args(c));
 }
 
+static RegionGateArgs make_region_args(const bvcf_ctx *c) {
+  RegionGateArgs ra{};
+  ra.chroms = c->regions.chroms;
+  ra.blob = c->regions.blob;
+  ra.intervals = c->regions.intervals;
+  ra.mask = c->regions.mask;
+  ra.max_name = c->regions.max_name;
+  ra.keep_on = c->regions.keep_on;
+  ra.exclude_on = c->regions.exclude_on;
+  return ra;
+}
+
+static uint32_t region_gate_grid(const bvcf_ctx *c) { return (uint32_t)c->n_cu * kRegionGateWgs; }
+
+// bvcf_set_region_table: right behind k_finish and in front of the variant gate -- the rows the regions do not select are
+// taken out (bvcf_regions.hip.h) before anything examines them
+static void launch_region_gate(bvcf_ctx *c, const KernelArgs &a, hipStream_t st) {
+  if (!c->regions.on) return;
+  hipLaunchKernelGGL(k_region_gate, dim3(region_gate_grid(c)), dim3(kWgThreads), 0, st, a, make_region_args(c));
+}
+
 // right behind k_finish: the gates, in front of every kernel that reads a record's ac
 static void launch_gates(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
+  launch_region_gate(c, a, st);
   launch_variant_gate(c, a, st);
   launch_site_gate(c, a, st, slot);
 }
@@ -476,7 +510,8 @@ void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]) {
     if (L.status != BVCF_LINE_OK) continue;
     for (uint32_t j = 0; j < L.n_rec; j++) {
       const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
-      if (A.pad[1]) {
+      if (A.pad[1] & 2u) continue;  // (a row the regions took out before: not examined)
+      if (A.pad[1] & 1u) {
         out[2]++;
       } else if (A.ac || A.pad[0]) {  // (a row the site gate took out afterwards was kept here)
         out[1]++;
@@ -499,6 +534,405 @@ int bvcf_bench_variant_kernel(bvcf_ctx *c, float *ms) {
   if (const int rc = launch_ungated(c, s, &a, true)) return rc;
   HIP_TRY(c, hipEventRecord(ev[0], s.stream));
   launch_variant_gate(c, a, s.stream);
+  HIP_TRY(c, hipEventRecord(ev[1], s.stream));
+  return finish_hook(c, ev, s.stream, ms);
+}
+
+// ---- the regions (bvcf_regions.hip.h): the host's table, made with the device's own functions
+
+// a host text for the __host__ __device__ walks: bytes past the end read as 0, as BlockText's do
+struct HostText {
+  const uint8_t *s;
+  uint32_t n;
+  uint32_t operator()(uint32_t off) const { return off < n ? s[off] : 0u; }
+};
+
+struct NameAppender {
+  std::string *o;
+  bool operator()(uint32_t byte) {
+    o->push_back((char)byte);
+    return true;
+  }
+};
+
+// the regions as given: a set bit, a normalised name, 1-based inclusive coordinates
+struct RegionItem {
+  uint32_t name, set;
+  long long beg, end;
+};
+struct RegionRaw {
+  std::vector<std::string> names;
+  std::unordered_map<std::string, uint32_t> index;
+  std::vector<RegionItem> items;
+};
+struct RegionGiven {
+  std::string name;  // normalised
+  long long beg, end;
+};
+
+static std::string region_normalised(const char *s, size_t n) {
+  std::string o;
+  NameAppender f{&o};
+  region_chrom_bytes(HostText{(const uint8_t *)s, (uint32_t)n}, 0u, (uint32_t)n, f);
+  return o;
+}
+
+static void region_err(char *err, size_t cap, const std::string &msg) {
+  if (err && cap) snprintf(err, cap, "%s", msg.c_str());
+}
+
+// s[0, n) as 1 to 18 digits
+static bool region_digits(const char *s, size_t n, long long *out) {
+  if (n == 0 || n > kRegionPosDigits) return false;
+  long long v = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (s[i] < '0' || s[i] > '9') return false;
+    v = v * 10 + (s[i] - '0');
+  }
+  *out = v;
+  return true;
+}
+
+// the regions of one parse call join the table, or none of them does
+static int region_commit(bvcf_region_table *t, std::vector<RegionGiven> &given, int exclude, char *err, size_t err_cap) {
+  RegionRaw *raw = (RegionRaw *)t->raw;
+  const size_t have = raw ? raw->items.size() : 0;
+  if (have + given.size() > BVCF_REGION_MAX_INTERVALS) {
+    region_err(err, err_cap, "more than 67108864 intervals");
+    return BVCF_E_TOO_BIG;
+  }
+  {
+    std::unordered_set<std::string_view> fresh;
+    for (const RegionGiven &g : given)
+      if (!raw || !raw->index.count(g.name)) fresh.emplace(g.name);
+    if ((raw ? raw->names.size() : 0) + fresh.size() > BVCF_REGION_MAX_CHROMS) {
+      region_err(err, err_cap, "more than 1048576 distinct chromosome names");
+      return BVCF_E_TOO_BIG;
+    }
+  }
+  if (!raw) t->raw = raw = new RegionRaw;
+  for (RegionGiven &g : given) {
+    auto it = raw->index.find(g.name);
+    if (it == raw->index.end()) {
+      it = raw->index.emplace(g.name, (uint32_t)raw->names.size()).first;
+      raw->names.push_back(std::move(g.name));
+    }
+    raw->items.push_back(RegionItem{it->second, exclude ? 1u : 0u, g.beg, g.end});
+  }
+  if (!exclude) t->keep_given = 1;
+  return BVCF_OK;
+}
+
+int bvcf_region_table_parse_specs(bvcf_region_table *t, const char *text, size_t n, int exclude, char *err, size_t err_cap) {
+  if (!t || (!text && n)) return BVCF_E_ARG;
+  std::vector<RegionGiven> given;
+  for (size_t pos = 0; pos <= n;) {
+    const char *cm = pos < n ? (const char *)memchr(text + pos, ',', n - pos) : nullptr;
+    const size_t e = cm ? (size_t)(cm - text) : n;
+    const char *s = text + pos;
+    const size_t l = e - pos;
+    pos = e + 1;
+    if (!l) {
+      region_err(err, err_cap, "an empty region");
+      return BVCF_E_ARG;
+    }
+    // split at the last ':'; a tail that is not D, D- or D-D leaves the whole SPEC a chromosome name
+    size_t c_len = l;
+    long long beg = 1, end = kRegionMaxCoord;
+    size_t colon = l;
+    while (colon > 0 && s[colon - 1] != ':') colon--;
+    if (colon > 0) {
+      const char *tail = s + colon;
+      const size_t tl = l - colon;
+      const char *dash = (const char *)memchr(tail, '-', tl);
+      const size_t bl = dash ? (size_t)(dash - tail) : tl;
+      long long b = 0, en = 0;
+      bool is_range = region_digits(tail, bl, &b) && b >= 1;
+      if (is_range) {
+        if (!dash) {
+          en = b;
+        } else if (bl + 1 == tl) {
+          en = kRegionMaxCoord;
+        } else {
+          is_range = region_digits(dash + 1, tl - bl - 1, &en) && en >= 1;
+        }
+      }
+      if (is_range) {
+        c_len = colon - 1;
+        beg = b;
+        end = en;
+        if (beg > end) {
+          region_err(err, err_cap, "region \"" + std::string(s, l) + "\": BEG is greater than END");
+          return BVCF_E_ARG;
+        }
+      }
+    }
+    if (!c_len) {
+      region_err(err, err_cap, "region \"" + std::string(s, l) + "\": an empty chromosome name");
+      return BVCF_E_ARG;
+    }
+    if (c_len > 0xFFFFFFF0ull) return BVCF_E_TOO_BIG;
+    given.push_back(RegionGiven{region_normalised(s, c_len), beg, end});
+  }
+  return region_commit(t, given, exclude, err, err_cap);
+}
+
+int bvcf_region_table_parse_bed(bvcf_region_table *t, const char *text, size_t n, int exclude, char *err, size_t err_cap) {
+  if (!t || (!text && n)) return BVCF_E_ARG;
+  std::vector<RegionGiven> given;
+  uint64_t line_no = 0;
+  for (size_t pos = 0; pos < n;) {
+    const char *nl = (const char *)memchr(text + pos, '\n', n - pos);
+    const size_t e = nl ? (size_t)(nl - text) : n;
+    const char *s = text + pos;
+    size_t l = e - pos;
+    pos = e + 1;
+    line_no++;
+    if (l && s[l - 1] == '\r') l--;
+    if (!l || s[0] == '#' || (l >= 5 && !memcmp(s, "track", 5)) || (l >= 7 && !memcmp(s, "browser", 7))) continue;
+    const auto bad = [&](const char *what) {
+      region_err(err, err_cap, "line " + std::to_string(line_no) + ": " + what);
+      return BVCF_E_ARG;
+    };
+    const char *t1 = (const char *)memchr(s, '\t', l);
+    const char *t2 = t1 ? (const char *)memchr(t1 + 1, '\t', l - (size_t)(t1 + 1 - s)) : nullptr;
+    if (!t2) return bad("fewer than three columns");
+    const char *t3 = (const char *)memchr(t2 + 1, '\t', l - (size_t)(t2 + 1 - s));
+    const char *end_at = t3 ? t3 : s + l;
+    long long b0 = 0, e0 = 0;
+    if (!region_digits(t1 + 1, (size_t)(t2 - t1 - 1), &b0)) return bad("start is not 1 to 18 digits");
+    if (!region_digits(t2 + 1, (size_t)(end_at - t2 - 1), &e0)) return bad("end is not 1 to 18 digits");
+    if (b0 > e0) return bad("start is greater than end");
+    if (b0 == e0) continue;  // (names no base)
+    if ((size_t)(t1 - s) > 0xFFFFFFF0ull) return BVCF_E_TOO_BIG;
+    given.push_back(RegionGiven{region_normalised(s, (size_t)(t1 - s)), b0 + 1, e0});
+  }
+  return region_commit(t, given, exclude, err, err_cap);
+}
+
+static void region_free_built(bvcf_region_table *t) {
+  free((void *)t->chroms);
+  free((void *)t->blob);
+  free((void *)t->intervals);
+  t->chroms = nullptr;
+  t->blob = nullptr;
+  t->intervals = nullptr;
+  t->capacity = t->blob_bytes = t->n_intervals = t->n_chroms = t->n_keep = t->n_exclude = 0;
+  t->max_name = 0;
+}
+
+void bvcf_region_table_free(bvcf_region_table *t) {
+  if (!t) return;
+  region_free_built(t);
+  delete (RegionRaw *)t->raw;
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_region_table_build(bvcf_region_table *t) {
+  if (!t) return BVCF_E_ARG;
+  region_free_built(t);
+  static const RegionRaw kNone;
+  const RegionRaw &raw = t->raw ? *(const RegionRaw *)t->raw : kNone;
+  // sorted by name, set and beg, then merged: overlapping or abutting intervals become one
+  std::vector<RegionItem> v = raw.items;
+  std::sort(v.begin(), v.end(), [](const RegionItem &x, const RegionItem &y) {
+    if (x.name != y.name) return x.name < y.name;
+    if (x.set != y.set) return x.set < y.set;
+    return x.beg < y.beg;
+  });
+  size_t m = 0;
+  for (size_t i = 0; i < v.size(); i++) {
+    if (m && v[m - 1].name == v[i].name && v[m - 1].set == v[i].set && v[m - 1].end >= v[i].beg - 1) {  // (beg >= 1)
+      if (v[i].end > v[m - 1].end) v[m - 1].end = v[i].end;
+    } else {
+      v[m++] = v[i];
+    }
+  }
+  v.resize(m);
+  uint64_t n_chroms = 0, blob_bytes = 0;
+  for (size_t i = 0; i < v.size(); i++)
+    if (!i || v[i].name != v[i - 1].name) {
+      n_chroms++;
+      blob_bytes += raw.names[v[i].name].size();
+    }
+  if (blob_bytes >= (1ull << 32)) return BVCF_E_TOO_BIG;
+  const uint64_t cap = variant_capacity(n_chroms);
+  RegionChrom *chroms = (RegionChrom *)calloc((size_t)cap, sizeof(RegionChrom));
+  uint8_t *blob = (uint8_t *)malloc((size_t)blob_bytes + 1);
+  RegionInterval *iv = (RegionInterval *)malloc((v.size() + 1) * sizeof(RegionInterval));
+  if (!chroms || !blob || !iv) {
+    free(chroms);
+    free(blob);
+    free(iv);
+    return BVCF_E_NOMEM;
+  }
+  const uint32_t mask = (uint32_t)(cap - 1);
+  uint64_t at = 0;
+  uint32_t max_name = 0;
+  for (size_t i = 0; i < v.size();) {
+    const std::string &name = raw.names[v[i].name];
+    const unsigned long long h = fnv1a((const uint8_t *)name.data(), name.size());
+    uint32_t slot = (uint32_t)h & mask;
+    while (chroms[slot].len) slot = (slot + 1u) & mask;
+    RegionChrom &c = chroms[slot];
+    c.tag = (uint32_t)(h >> 32);
+    c.off = (uint32_t)at;
+    c.len = (uint32_t)name.size();
+    memcpy(blob + at, name.data(), name.size());
+    at += name.size();
+    max_name = std::max(max_name, c.len);
+    const uint32_t who = v[i].name;
+    for (; i < v.size() && v[i].name == who; i++) {
+      if (!c.n[v[i].set]++) c.first[v[i].set] = (uint32_t)i;
+      iv[i] = RegionInterval{v[i].beg, v[i].end};
+      (v[i].set ? t->n_exclude : t->n_keep)++;
+    }
+  }
+  t->chroms = (const uint32_t *)chroms;
+  t->capacity = cap;
+  t->blob = (const char *)blob;
+  t->blob_bytes = blob_bytes;
+  t->intervals = (const int64_t *)iv;
+  t->n_intervals = v.size();
+  t->n_chroms = n_chroms;
+  t->max_name = max_name;
+  return BVCF_OK;
+}
+
+// the table as the kernel's arguments, on whatever memory holds it
+static RegionGateArgs region_args_of(const bvcf_region_table *t, const RegionChrom *chroms, const uint8_t *blob, const RegionInterval *iv) {
+  RegionGateArgs ra{};
+  ra.chroms = chroms;
+  ra.blob = blob;
+  ra.intervals = iv;
+  ra.mask = (uint32_t)(t->capacity - 1);
+  ra.max_name = t->max_name;
+  ra.keep_on = t->keep_given ? 1u : 0u;
+  ra.exclude_on = t->n_exclude ? 1u : 0u;
+  return ra;
+}
+
+int bvcf_region_table_has(const bvcf_region_table *t, const char *chrom, size_t chrom_len, const char *pos, size_t pos_len,
+                          const char *alt, size_t alt_len) {
+  if (!t || !t->chroms || !t->capacity || (t->capacity & (t->capacity - 1)) || (!chrom && chrom_len) || (!pos && pos_len) ||
+      (!alt && alt_len) || chrom_len > 0xFFFFFFF0ull || pos_len > 0xFFFFFFF0ull)
+    return -1;
+  long long p = 0, lo = 0, hi = 0;
+  const bool has_pos = region_parse_pos(HostText{(const uint8_t *)pos, (uint32_t)pos_len}, 0u, (uint32_t)pos_len, &p);
+  if (has_pos) {
+    // an alt of "-N": a deletion of N bases (N beyond 32 bits: as long as a record can say)
+    uint32_t kind = BVCF_ALT_BASE, del = 1;
+    if (alt_len >= 2 && alt[0] == '-') {
+      unsigned long long v = 0;
+      bool digits = true;
+      for (size_t i = 1; i < alt_len && digits; i++) {
+        digits = alt[i] >= '0' && alt[i] <= '9';
+        if (digits && v <= 0xFFFFFFFFull) v = v * 10ull + (unsigned long long)(alt[i] - '0');
+      }
+      if (digits) {
+        kind = BVCF_ALT_DEL;
+        del = v > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)v;
+      }
+    }
+    region_span(p, kind, del, &lo, &hi);
+  }
+  const RegionGateArgs ra = region_args_of(t, (const RegionChrom *)t->chroms, (const uint8_t *)t->blob, (const RegionInterval *)t->intervals);
+  return (int)region_row_bits(ra, HostText{(const uint8_t *)chrom, (uint32_t)chrom_len}, 0u, (uint32_t)chrom_len, has_pos, lo, hi);
+}
+
+int bvcf_region_table_stays(const bvcf_region_table *t, int bits) {
+  if (!t || bits < 0) return -1;
+  return region_row_stays(t->keep_given ? 1u : 0u, (uint32_t)bits) ? 1 : 0;
+}
+
+// every name lies in the blob, every range in the intervals, every range ascends without touching; the capacity is a power
+// of two with an empty slot
+static bool region_table_sound(const bvcf_region_table *t) {
+  if (!t || !t->chroms || !t->intervals || t->capacity < 16 || t->capacity > (1ull << 31) || (t->capacity & (t->capacity - 1)) ||
+      t->blob_bytes >= (1ull << 32) || (t->blob_bytes && !t->blob) || t->n_intervals > (1ull << 27) ||
+      t->n_keep + t->n_exclude != t->n_intervals)
+    return false;
+  const RegionChrom *c = (const RegionChrom *)t->chroms;
+  const RegionInterval *iv = (const RegionInterval *)t->intervals;
+  uint64_t used = 0, n_set[2] = {0, 0};
+  for (uint64_t i = 0; i < t->capacity; i++) {
+    if (!c[i].len) continue;
+    used++;
+    if ((uint64_t)c[i].off + c[i].len > t->blob_bytes || c[i].len > t->max_name) return false;
+    for (int s = 0; s < 2; s++) {
+      if ((uint64_t)c[i].first[s] + c[i].n[s] > t->n_intervals) return false;
+      n_set[s] += c[i].n[s];
+      for (uint32_t j = 0; j < c[i].n[s]; j++) {
+        const RegionInterval &x = iv[c[i].first[s] + j];
+        if (x.beg > x.end || (j && iv[c[i].first[s] + j - 1].end >= x.beg)) return false;
+      }
+    }
+  }
+  return used == t->n_chroms && 2 * used <= t->capacity && n_set[0] == t->n_keep && n_set[1] == t->n_exclude;
+}
+
+int bvcf_set_region_table(bvcf_ctx *c, const bvcf_region_table *t) {
+  if (!c) return BVCF_E_ARG;
+  if (!region_table_sound(t)) {
+    c->err = "bvcf_set_region_table: want a table as bvcf_region_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_region_table")) return rc;
+  if (!c->n_samples) return BVCF_OK;  // (no sample columns: nothing is examined)
+  c->regions.on = false;
+  c->regions.chroms.reset();
+  c->regions.blob.reset();
+  c->regions.intervals.reset();
+  if (!t->keep_given && !t->n_exclude) return BVCF_OK;  // (every row stays: nothing is allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  HIP_TRY(c, c->regions.chroms.alloc((size_t)t->capacity));
+  HIP_TRY(c, c->regions.blob.alloc((size_t)t->blob_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, c->regions.intervals.alloc((size_t)t->n_intervals + 1));
+  HIP_TRY(c, hipMemcpy(c->regions.chroms, t->chroms, (size_t)t->capacity * sizeof(RegionChrom), hipMemcpyHostToDevice));
+  if (t->blob_bytes) HIP_TRY(c, hipMemcpy(c->regions.blob, t->blob, (size_t)t->blob_bytes, hipMemcpyHostToDevice));
+  if (t->n_intervals)
+    HIP_TRY(c, hipMemcpy(c->regions.intervals, t->intervals, (size_t)t->n_intervals * sizeof(RegionInterval), hipMemcpyHostToDevice));
+  const RegionGateArgs ra = region_args_of(t, c->regions.chroms, c->regions.blob, c->regions.intervals);
+  c->regions.mask = ra.mask;
+  c->regions.max_name = ra.max_name;
+  c->regions.keep_on = ra.keep_on;
+  c->regions.exclude_on = ra.exclude_on;
+  c->regions.on = true;
+  return BVCF_OK;
+}
+
+void bvcf_region_gate_count(const bvcf_result *r, uint64_t out[3]) {
+  if (!out) return;
+  out[0] = out[1] = out[2] = 0;
+  if (!r || r->status != BVCF_OK || !r->n_samples || r->sites || !r->lines || !r->alleles) return;
+  for (uint32_t i = 0; i < r->n_lines; i++) {
+    const bvcf_line &L = r->lines[i];
+    if (L.status != BVCF_LINE_OK) continue;
+    for (uint32_t j = 0; j < L.n_rec; j++) {
+      const bvcf_allele &A = r->alleles[j ? L.rec_first + j - 1 : i];
+      if (A.pad[1] & 2u) {
+        out[2]++;
+      } else if (A.ac || A.pad[0] || A.pad[1]) {  // (a row the list or the site gate took out afterwards was kept here)
+        out[1]++;
+      }
+    }
+  }
+  out[0] = out[1] + out[2];
+}
+
+uint32_t bvcf_bench_region_gate_stride(const bvcf_ctx *c) { return c ? region_gate_grid(c) * kWgThreads : 0u; }
+
+int bvcf_bench_region_kernel(bvcf_ctx *c, float *ms) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Event ev[2];
+  if (const int rc = start_hook(c, "bvcf_bench_region_kernel", c->regions.on && c->bench_src,
+                                "the ctx has no region table, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  Slot &s = c->slots[0];
+  KernelArgs a;
+  if (const int rc = launch_ungated(c, s, &a, true, true)) return rc;
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_region_gate(c, a, s.stream);
   HIP_TRY(c, hipEventRecord(ev[1], s.stream));
   return finish_hook(c, ev, s.stream, ms);
 }

@@ -21,6 +21,7 @@
 #include <string>
 #include <string_view>
 #include <thread>
+#include <unordered_map>
 #include <unordered_set>
 #include <vector>
 
@@ -169,6 +170,7 @@ struct bvcf_ctx : bvcf_ctx_plan {
   PairStatsCtx pr;
   SiteGateCtx gate;
   VariantGateCtx variants;
+  RegionGateCtx regions;
   BedCtx bed;
   TrioCtx trio;
   LdCtx ld;

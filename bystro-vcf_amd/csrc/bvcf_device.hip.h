@@ -54,6 +54,9 @@
 //   (bvcf_enable_pair_stats, behind them and from the same row lists: k_pr_planes / k_pr_gemm / k_pr_sparse count, per
 //    pair of samples, the rows that name both -- the bit-matrix product behind --relatedness, bvcf_pairstats.hip.h;
 //    k_pr_fold adds a collected batch's tables to the ctx's totals)
+//   (bvcf_set_region_table, right behind k_finish and in front of the variant gate: k_region_gate finds every row's
+//    chromosome in the hash set of --regions / --excludeRegions, binary-searches the row's span in the chromosome's merged
+//    intervals and takes the unselected rows out -- bvcf_regions.hip.h)
 //   (bvcf_set_variant_list, right behind k_finish and in front of the site gate: k_variant_gate walks the bytes of every
 //    row's locus string "chrom:pos:ref:alt", looks it up in the hash set of --keepVariants / --excludeVariants and takes
 //    the unselected rows out -- bvcf_variantlist.hip.h)
@@ -114,6 +117,7 @@
 #include "bvcf_names.hip.h"
 #include "bvcf_sitegate.hip.h"
 #include "bvcf_variantlist.hip.h"
+#include "bvcf_regions.hip.h"
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_bedrows.hip.h"

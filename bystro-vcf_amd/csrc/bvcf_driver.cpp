@@ -455,6 +455,11 @@ void Driver::device_main(DevWorker *W) {
       bvcf_variant_gate_count(&res, t);
       for (int q = 0; q < 3; q++) W->variant_counts[q] += t[q];
     }
+    if (R_.region_fd >= 0) {  // --regionFilterReport: likewise
+      uint64_t t[3];
+      bvcf_region_gate_count(&res, t);
+      for (int q = 0; q < 3; q++) W->region_counts[q] += t[q];
+    }
     FmtJob j;
     j.b = b;
     j.res = res;
@@ -631,6 +636,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return rc;
     }
     if (const int rc = open_variants(R_, &msg)) {  // --keepVariants / --excludeVariants / --variantFilterReport: the list read, the report opened
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
+    if (const int rc = open_regions(R_, &msg)) {  // --regions / --excludeRegions and their files, --regionFilterReport: likewise
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
@@ -858,6 +867,16 @@ int Driver::run(uint64_t *n_lines_in) {
         for (int q = 0; q < 3; q++) sum[q] += W->variant_counts[q];
       std::string msg;
       if (write_variant_report(R_, sum, &msg)) {
+        fail(msg, BVCF_E_IO);
+        write_all(fd_err_, log_.data(), log_.size());
+      }
+    }
+    if (R_.region_fd >= 0 && rc_ == BVCF_OK) {  // --regionFilterReport: likewise
+      uint64_t sum[3] = {0, 0, 0};
+      for (auto &W : workers_)
+        for (int q = 0; q < 3; q++) sum[q] += W->region_counts[q];
+      std::string msg;
+      if (write_region_report(R_, sum, &msg)) {
         fail(msg, BVCF_E_IO);
         write_all(fd_err_, log_.data(), log_.size());
       }

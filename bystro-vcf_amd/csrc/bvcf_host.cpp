@@ -61,6 +61,12 @@ void bvcf_config_variants_defaults(bvcf_config_variants *c) {
   c->ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_VARIANTS;
 }
 
+void bvcf_config_regions_defaults(bvcf_config_regions *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_variants_defaults(&c->variants);
+  c->variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_REGIONS;
+}
+
 int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out) {
   if (!out || (!text && n)) return BVCF_E_ARG;
   std::vector<uint64_t> off;
@@ -147,6 +153,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   int ss_fd = -1, pr_fd = -1, sg_fd = -1;
   uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};
   uint64_t variant_counts[3] = {0, 0, 0};
+  uint64_t region_counts[3] = {0, 0, 0};
   int rc = open_sample_stats(c, &ss_fd, &msg);
   if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
   if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
@@ -154,6 +161,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_mendel(R, &msg);
   if (rc == BVCF_OK) rc = open_ld(R, &msg);
   if (rc == BVCF_OK) rc = open_variants(R, &msg);
+  if (rc == BVCF_OK) rc = open_regions(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -197,6 +205,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         uint64_t t[3];
         bvcf_variant_gate_count(&res, t);
         for (int q = 0; q < 3; q++) variant_counts[q] += t[q];
+      }
+      if (R.region_fd >= 0) {  // --regionFilterReport: likewise
+        uint64_t t[3];
+        bvcf_region_gate_count(&res, t);
+        for (int q = 0; q < 3; q++) region_counts[q] += t[q];
       }
       if (R.want_rows) {
         format_batch(c, &res, vcf + pos, nm, R.ratios.get(), R.pool.get(), o, l);
@@ -300,6 +313,10 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
     }
   }
   if (R.variant_fd >= 0 && rc == BVCF_OK && write_variant_report(R, variant_counts, &msg)) {  // --variantFilterReport: likewise
+    l.append(msg + "\n");
+    rc = BVCF_E_IO;
+  }
+  if (R.region_fd >= 0 && rc == BVCF_OK && write_region_report(R, region_counts, &msg)) {  // --regionFilterReport: likewise
     l.append(msg + "\n");
     rc = BVCF_E_IO;
   }

@@ -862,6 +862,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.regions_on) {  // --regions / --excludeRegions: the run's table on every ctx of the run
+    rc = bvcf_set_region_table(*ctx, &R.region_table);
+    if (rc) {
+      *msg = std::string("bvcf_set_region_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (rc == BVCF_OK && R.variants_on) {  // --keepVariants / --excludeVariants: the run's table on every ctx of the run
     rc = bvcf_set_variant_table(*ctx, &R.variant_table, R.variants_exclude);
     if (rc) {
@@ -1475,6 +1483,92 @@ int write_variant_report(Run &R, const uint64_t counts[3], std::string *msg) {
   R.variant_fd = -1;
   if (bad || bad_close) {
     *msg = std::string("variantFilterReport: write failed: ") + strerror(bad ? saved : errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+// the whole file, or one message
+static int read_text_file(const char *path, std::string *text, std::string *msg) {
+  FILE *f = fopen(path, "rb");
+  if (!f) {
+    *msg = std::string("open ") + path + ": " + strerror(errno);
+    return BVCF_E_FATAL;
+  }
+  char buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, f)) > 0) text->append(buf, got);
+  const int err = ferror(f) ? errno : 0;
+  fclose(f);
+  if (err) {
+    *msg = std::string("read ") + path + ": " + strerror(err);
+    return BVCF_E_FATAL;
+  }
+  return BVCF_OK;
+}
+
+int open_regions(Run &R, std::string *msg) {
+  const bvcf_config_regions *g = regions_config(R.cfg);
+  if (!g) return BVCF_OK;
+  const char *rp = g->region_filter_path;
+  if (rp && *rp) {
+    R.region_fd = open(rp, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (R.region_fd < 0) {
+      *msg = std::string("open ") + rp + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  const struct {
+    const char *specs, *path, *flag, *file_flag;
+  } sets[2] = {{g->regions, g->regions_path, "regions", "regionsFile"},
+               {g->exclude_regions, g->exclude_regions_path, "excludeRegions", "excludeRegionsFile"}};
+  bool any = false;
+  char why[256];
+  for (int s = 0; s < 2; s++) {
+    if (sets[s].specs && *sets[s].specs) {
+      any = true;
+      why[0] = 0;
+      if (const int rc = bvcf_region_table_parse_specs(&R.region_table, sets[s].specs, strlen(sets[s].specs), s, why, sizeof why)) {
+        *msg = std::string(sets[s].flag) + ": " + why;
+        return rc == BVCF_E_ARG ? BVCF_E_ARG : BVCF_E_FATAL;
+      }
+    }
+    if (sets[s].path && *sets[s].path) {
+      any = true;
+      std::string text;
+      if (const int rc = read_text_file(sets[s].path, &text, msg)) return rc;
+      why[0] = 0;
+      if (bvcf_region_table_parse_bed(&R.region_table, text.data(), text.size(), s, why, sizeof why)) {
+        *msg = std::string(sets[s].file_flag) + ": " + sets[s].path + ": " + why;
+        return BVCF_E_FATAL;
+      }
+    }
+  }
+  if (bvcf_region_table_build(&R.region_table)) {
+    *msg = "regions: out of memory";
+    return BVCF_E_FATAL;
+  }
+  R.regions_on = any;
+  return BVCF_OK;
+}
+
+int write_region_report(Run &R, const uint64_t counts[3], std::string *msg) {
+  if (R.region_fd < 0) return BVCF_OK;
+  static const char *const kNames[5] = {"keepIntervals", "excludeIntervals", "examined", "kept", "dropped"};
+  const uint64_t v[5] = {R.region_table.n_keep, R.region_table.n_exclude, counts[0], counts[1], counts[2]};
+  std::string o;
+  for (int q = 0; q < 5; q++) {
+    o.append(kNames[q]);
+    o.push_back('\t');
+    append_ll(o, (long long)v[q]);
+    o.push_back('\n');
+  }
+  const bool bad = write_all(R.region_fd, o.data(), o.size()) != 0;
+  const int saved = errno;
+  const bool bad_close = close(R.region_fd) != 0;
+  R.region_fd = -1;
+  if (bad || bad_close) {
+    *msg = std::string("regionFilterReport: write failed: ") + strerror(bad ? saved : errno);
     return BVCF_E_IO;
   }
   return BVCF_OK;

@@ -255,11 +255,18 @@ struct Run {
   bool variants_on = false, variants_exclude = false;
   bvcf_variant_table variant_table{};
   int variant_fd = -1;
+  // --regions / --regionsFile / --excludeRegions / --excludeRegionsFile / --regionFilterReport: open_regions opens the report
+  // and parses the SPECs and BED files into the run's one table before any device work; create_ctx uploads it to every ctx;
+  // write_region_report writes the merged interval counts and the sum of bvcf_region_gate_count over the batches of the output
+  bool regions_on = false;
+  bvcf_region_table region_table{};
+  int region_fd = -1;
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd})
+    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
     bvcf_variant_table_free(&variant_table);
+    bvcf_region_table_free(&region_table);
   }
 };
 
@@ -373,6 +380,16 @@ inline const bvcf_config_variants *variants_config(const bvcf_config *c) {
 // (counts = the sum of bvcf_variant_gate_count over the batches of the output) and the file closed
 int open_variants(Run &R, std::string *msg);
 int write_variant_report(Run &R, const uint64_t counts[3], std::string *msg);
+// --regions / --excludeRegions and their files, --regionFilterReport: the config as a bvcf_config_regions (the seventh marker), or NULL
+inline const bvcf_config_regions *regions_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_REGIONS) ? reinterpret_cast<const bvcf_config_regions *>(c)
+                                                                                            : nullptr;
+}
+// the report opened (truncated) and the regions parsed into R.region_table -- BVCF_E_ARG for a bad SPEC, BVCF_E_IO for the
+// report, BVCF_E_FATAL for a BED file that cannot be read, has a bad line or is over the bounds, one message in *msg; the
+// five lines written (counts = the sum of bvcf_region_gate_count over the batches of the output) and the file closed
+int open_regions(Run &R, std::string *msg);
+int write_region_report(Run &R, const uint64_t counts[3], std::string *msg);
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

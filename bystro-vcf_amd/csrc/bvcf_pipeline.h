@@ -216,6 +216,7 @@ struct DevWorker {
   std::vector<uint64_t> pr_carry;  // --relatedness: the same for the pair tables
   uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};  // --siteFilterReport: bvcf_site_gate_count over the batches handed to the formatter
   uint64_t variant_counts[3] = {0, 0, 0};           // --variantFilterReport: bvcf_variant_gate_count over the same batches
+  uint64_t region_counts[3] = {0, 0, 0};            // --regionFilterReport: bvcf_region_gate_count over the same batches
 };
 
 enum Mode { kStream = BVCF_MODE_STREAM, kRangeText = BVCF_MODE_TEXT_RANGES, kRangeBgzf = BVCF_MODE_BGZF_RANGES };

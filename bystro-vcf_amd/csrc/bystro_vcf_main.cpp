@@ -57,6 +57,11 @@ struct Cli {
   // is in the list / all the others (looked up on the device, in front of the site gate); --variantFilterReport PATH, how
   // many rows the list examined, kept and dropped
   std::string keep_variants, exclude_variants, variant_report;
+  // extension: --regions SPEC[,SPEC...] / --regionsFile BED, the run keeps only the rows that overlap one of the regions (the
+  // union of both); --excludeRegions / --excludeRegionsFile, it drops the rows that overlap one; keep and exclude may be
+  // given together (decided on the device, in front of the variant list and the site gate); --regionFilterReport PATH, the
+  // merged intervals of each set and how many rows the regions examined, kept and dropped
+  std::string regions, regions_file, exclude_regions, exclude_regions_file, region_report;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -152,7 +157,8 @@ int parse(int argc, char **argv, Cli &c) {
         name == "minGQ" || name == "minDP" || name == "keepSamples" || name == "excludeSamples" || name == "relatedness" ||
         name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
         name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
-        name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport") {
+        name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
+        name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -223,6 +229,27 @@ int parse(int argc, char **argv, Cli &c) {
         (name == "keepVariants" ? c.keep_variants : c.exclude_variants) = val;
       } else if (name == "variantFilterReport") {
         c.variant_report = val;
+      } else if (name == "regions" || name == "excludeRegions") {
+        // (the SPECs are checked here, by the parser the run uses: a bad one is an argument error)
+        bvcf_region_table probe;
+        memset(&probe, 0, sizeof probe);
+        char why[256] = "";
+        const int bad = bvcf_region_table_parse_specs(&probe, val.data(), val.size(), name == "excludeRegions", why, sizeof why);
+        bvcf_region_table_free(&probe);
+        if (bad) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: %s\n", val.c_str(), name.c_str(), why);
+          return 2;
+        }
+        std::string &dst = name == "regions" ? c.regions : c.exclude_regions;
+        dst = dst.empty() ? val : dst + "," + val;  // (given twice: the union)
+      } else if (name == "regionsFile" || name == "excludeRegionsFile") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of a BED file\n", name.c_str());
+          return 2;
+        }
+        (name == "regionsFile" ? c.regions_file : c.exclude_regions_file) = val;
+      } else if (name == "regionFilterReport") {
+        c.region_report = val;
       } else if (name == "keepSamples" || name == "excludeSamples") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of a list of sample names\n", name.c_str());
@@ -278,10 +305,11 @@ int main(int argc, char **argv) {
     return 1;
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
-  // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so is --variantFilterReport alone)
+  // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so are --variantFilterReport and
+  // --regionFilterReport alone)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
       c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
-      c.variant_report.empty()) {
+      c.variant_report.empty() && c.region_report.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -295,9 +323,11 @@ int main(int argc, char **argv) {
 
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
-  // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report)
-  bvcf_config_variants vc;
-  bvcf_config_variants_defaults(&vc);
+  // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
+  // regions and their report)
+  bvcf_config_regions rc_cfg;
+  bvcf_config_regions_defaults(&rc_cfg);
+  bvcf_config_variants &vc = rc_cfg.variants;
   bvcf_config_ld &ldc = vc.ld;
   bvcf_config_trios &trios = ldc.trios;
   bvcf_config_more &more = trios.more;
@@ -368,6 +398,11 @@ int main(int argc, char **argv) {
   vc.keep_variants_path = c.keep_variants.c_str();
   vc.exclude_variants_path = c.exclude_variants.c_str();
   vc.variant_filter_path = c.variant_report.c_str();
+  rc_cfg.regions = c.regions.c_str();
+  rc_cfg.regions_path = c.regions_file.c_str();
+  rc_cfg.exclude_regions = c.exclude_regions.c_str();
+  rc_cfg.exclude_regions_path = c.exclude_regions_file.c_str();
+  rc_cfg.region_filter_path = c.region_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -225,7 +225,9 @@ typedef struct {
   uint8_t flags;
   uint8_t pad[2];      /* [0]: bvcf_set_site_gate, the BVCF_GATE_* bits of a row the gate took out (its ac is then 0); else 0
                           [1]: bvcf_set_variant_list, 1 for a row the list took out (its ac is then 0, and [0] is 0: the
-                          site gate never saw it); else 0 -- every kernel that writes a record writes 0 here */
+                          site gate never saw it); bvcf_set_region_table, 2 for a row the regions took out (its ac is
+                          then 0, and [0] is 0: neither the list nor the site gate saw it, so bit 0 is never set beside bit 1);
+                          else 0 -- every kernel that writes a record writes 0 here */
   uint32_t gt_task;    /* internal: genotype-scan task that produced ac..n_miss */
   uint32_t pad2;
 } bvcf_allele;
@@ -608,8 +610,80 @@ int bvcf_variant_table_has(const bvcf_variant_table *t, const char *s, size_t n)
 int bvcf_set_variant_table(bvcf_ctx *ctx, const bvcf_variant_table *t, int exclude);
 int bvcf_set_variant_list(bvcf_ctx *ctx, const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, int exclude);
 /* what the list did to a collected batch, from its records alone (host only; no ctx): out = {examined, kept, dropped}.  A
- * row the site gate took out afterwards counts as kept here.  All zero for a batch without sample columns. */
+ * row the site gate took out afterwards counts as kept here; a row the regions took out before (bit 1 of pad[1]) was not
+ * examined and is in no count; dropped tests bit 0 of pad[1] alone.  All zero for a batch without sample columns. */
 void bvcf_variant_gate_count(const bvcf_result *r, uint64_t out[3]);
+
+/* Row selection by genomic interval (--regions / --excludeRegions).  A region is a chromosome name and 1-based inclusive
+ * coordinates beg .. end.  A chromosome name is normalised as the TSV normalises CHROM -- "chr" is put in front unless the
+ * name has four bytes or more and starts with 'c' -- and then compared with the row's TSV chrom byte for byte: "1" and
+ * "chr1" name the same chromosome, and both match a file that writes "1" or "chr1".
+ * A row's SPAN is defined on its TSV columns pos and alt only: pos is a position iff the column is an optional '-' followed
+ * by 1 to 18 ASCII digits (leading zeros are fine; the POS bytes of a BVCF_ALLELE_POS_TEXT row are printed verbatim, so
+ * "1e5", "+7", "" or 19 digits are possible, and are no position); an alt of "-N" (a deletion) spans pos .. pos + N - 1,
+ * every other row -- a SNP, each row of an MNP at its own pos, an insertion at its anchor -- spans pos alone.  A row
+ * OVERLAPS a set iff its span shares at least one base with an interval of its chromosome; integers are compared as signed
+ * 64-bit.  A row without a position overlaps nothing.  A row STAYS iff (no keep set was given, or it overlaps the keep set)
+ * and it does not overlap the exclude set.  A keep set that was given and is empty leaves no row; an empty exclude set is off.
+ * The rows examined are the rows the site gate examines.  On the device, right behind the kernel that settles the counts
+ * and IN FRONT OF bvcf_set_variant_list and the site gate: a row the regions take out is examined by neither and is in
+ * none of bvcf_variant_gate_count's or bvcf_site_gate_count's counts.  The contract: such a row has ac == 0,
+ * bvcf_allele.pad[1] == 2 and pad[0] == 0; an, n_het, n_hom and n_miss stay as they were; every consumer written against
+ * this ABI drops it as it drops any row no sample carries (see bvcf_set_variant_list).
+ * The table: chroms[8 * i ..] = {tag, off, len, 0, keep_first, exclude_first, keep_n, exclude_n} for slot i < capacity, len
+ * == 0 = empty -- a hash set of the normalised names by the rules of bvcf_variant_table: bvcf_locus_hash of the normalised
+ * name, capacity = bvcf_variant_table_capacity(n_chroms), linear probing, and the bytes are compared before a name counts
+ * as found; a name's bytes are blob[off, off + len), its intervals of a set intervals[2 * (first + j) ..] = {beg, end} for
+ * j < n, sorted, overlapping and abutting intervals merged into one.  At most BVCF_REGION_MAX_INTERVALS intervals given
+ * per table and BVCF_REGION_MAX_CHROMS distinct names.
+ * A table is made in three steps on a zeroed struct: bvcf_region_table_parse_specs / _parse_bed add regions to the keep set
+ * (exclude == 0; the keep set then counts as given, even when nothing was added) or to the exclude set, any number of
+ * times -- the union is taken --; bvcf_region_table_build sorts, merges and builds the arrays (again after more parsing);
+ * bvcf_region_table_free releases everything.  A table built without any parse call is valid and selects every row.
+ *   SPECs, comma-separated: CHROM, CHROM:POS, CHROM:BEG-END or CHROM:BEG- .  A SPEC is split at its last ':'; if the tail is
+ *   not D, D- or D-D -- D = 1 to 18 ASCII digits with a value >= 1, no sign, space or separator -- the whole SPEC is a
+ *   chromosome name.  CHROM alone is CHROM:1- ; an open end means "to the largest coordinate" (2^63 - 1).  BEG > END, an
+ *   empty SPEC or an empty CHROM: BVCF_E_ARG.
+ *   BED text: chrom<TAB>start<TAB>end[<TAB>...], 0-based half-open, so a line is the bases start + 1 .. end.  Further columns
+ *   are ignored, a trailing '\r' is dropped, empty lines and lines beginning with '#', "track" or "browser" are ignored,
+ *   start == end names no base and is ignored.  Fewer than three columns, a start or end that is not 1 to
+ *   18 digits, start > end: BVCF_E_ARG.
+ *   Both: over the bounds BVCF_E_TOO_BIG.  On an error one message is written to err[0, err_cap) (NUL-terminated; a BED
+ *   message names the 1-based line) and the table stays as it was before the call.
+ * bvcf_region_table_has runs the device's lookup on the host's table for a row given by its TSV columns chrom (normalised
+ * or not: the rule is idempotent), pos and alt: bit 0 = the row overlaps the keep set, bit 1 = the exclude set; -1 for bad
+ * arguments or a table not built.  bvcf_region_table_stays applies the rule above to those bits (1 / 0).
+ * bvcf_set_region_table uploads a built table to a ctx (one table serves every ctx of a run).  Call once, before the first
+ * submit, like bvcf_set_site_gate; BVCF_E_BUSY with batches in flight.  A no-op returning BVCF_OK on a ctx without sample
+ * columns.  A table with no keep set given and an empty exclude set selects every row: the ctx then allocates and launches
+ * nothing for it, as a ctx on which it is never called.  bvcf_params and the ABI version do not change with it. */
+#define BVCF_REGION_MAX_INTERVALS (1ull << 26)
+#define BVCF_REGION_MAX_CHROMS (1ull << 20)
+typedef struct {
+  const uint32_t *chroms;   /* [8 * capacity] */
+  uint64_t capacity;
+  const char *blob;
+  uint64_t blob_bytes;
+  const int64_t *intervals; /* [2 * n_intervals] */
+  uint64_t n_intervals;     /* n_keep + n_exclude */
+  uint64_t n_chroms;        /* distinct names */
+  uint64_t n_keep;          /* the intervals of the keep set after merging */
+  uint64_t n_exclude;       /* ... of the exclude set */
+  uint32_t keep_given;      /* a keep set was given (it may be empty) */
+  uint32_t max_name;        /* the longest normalised name, bytes */
+  void *raw;                /* internal: the regions as given */
+} bvcf_region_table;
+int bvcf_region_table_parse_specs(bvcf_region_table *t, const char *text, size_t n, int exclude, char *err, size_t err_cap);
+int bvcf_region_table_parse_bed(bvcf_region_table *t, const char *text, size_t n, int exclude, char *err, size_t err_cap);
+int bvcf_region_table_build(bvcf_region_table *t);
+void bvcf_region_table_free(bvcf_region_table *t);
+int bvcf_region_table_has(const bvcf_region_table *t, const char *chrom, size_t chrom_len, const char *pos, size_t pos_len,
+                          const char *alt, size_t alt_len);
+int bvcf_region_table_stays(const bvcf_region_table *t, int bits);
+int bvcf_set_region_table(bvcf_ctx *ctx, const bvcf_region_table *t);
+/* what the regions did to a collected batch, from its records alone (host only; no ctx): out = {examined, kept, dropped}.
+ * A row the list or the site gate took out afterwards counts as kept here.  All zero for a batch without sample columns. */
+void bvcf_region_gate_count(const bvcf_result *r, uint64_t out[3]);
 
 /* running totals since bvcf_create: {lines_in, lines_ok, alleles_out, alleles_ac0, errs,
  * bytes_in, cmap_bytes, kernel_ns}; alleles_ac0 includes the rows bvcf_set_site_gate took out */
@@ -641,7 +715,7 @@ typedef struct {
   uint8_t normalize_header;     /* parse.NormalizeHeader restatement ('.' -> '_'), default 1 */
   uint8_t leave_teardown_to_exit; /* bvcf_run_fd: the process exits right after the call (the CLI): skip destroying the
                                    ctxs and unpinning the buffers, the OS reclaims them (~0.1 s of a 0.9 s run) */
-  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct; [1]: BVCF_CONFIG_MORE_GATE .. BVCF_CONFIG_MORE_VARIANTS */
+  uint8_t reserved[2];          /* [0]: BVCF_CONFIG_MORE when a bvcf_config_more starts with this struct; [1]: BVCF_CONFIG_MORE_GATE .. BVCF_CONFIG_MORE_REGIONS */
   int32_t device;               /* HIP device ordinal */
   uint32_t n_format_threads;    /* 0 = the CPUs the process may use (affinity, cgroup quota), at most 32 */
   uint64_t max_batch_bytes;     /* 0 = 64 MiB (256 MiB of text for a BGZF file inflated on the device) */
@@ -812,6 +886,34 @@ typedef struct {
 } bvcf_config_variants;
 /* the whole struct: bvcf_config_ld_defaults, base.reserved[1] = BVCF_CONFIG_MORE_VARIANTS, no paths */
 void bvcf_config_variants_defaults(bvcf_config_variants *c);
+/* Likewise what came after bvcf_config_variants: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_REGIONS.  bvcf_config_regions_defaults sets that; the six older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_REGIONS 6
+typedef struct {
+  bvcf_config_variants variants;
+  /* --regions / --regionsFile / --excludeRegions / --excludeRegionsFile: the bvcf_set_region_table of every ctx of the
+   * run.  regions is a comma-separated list of SPECs, regions_path a BED file; given together they are united; the same
+   * for the exclude pair; NULL or "" = not given.  Keep and exclude may be given together: a row stays iff (no keep field
+   * was given, or it overlaps the keep set) and it does not overlap the exclude set.  The rules of SPECs, BED lines,
+   * chromosome names and a row's span are bvcf_region_table's.  A bad SPEC: BVCF_E_ARG; an unreadable file, a bad BED line
+   * (named in the message) or a set over the bounds: BVCF_E_FATAL; one message, before any device work.  A region that
+   * matches no row is no error; a keep set that is empty leaves no rows, an empty exclude set changes nothing.
+   * The one rule: a run with regions produces, byte for byte, what the run without them produces with the unselected rows
+   * taken out -- every output bvcf_config_variants names.  The regions act first, the variant list next, the site gate
+   * last: a row the regions take out is not examined by the list or the gate and is in neither of their reports.  **Files
+   * without sample columns accept the fields and come out unchanged.**  The output does not depend on devices, batch size
+   * or input kind, and the chain a file runs on does not change with regions. */
+  const char *regions;
+  const char *regions_path;
+  const char *exclude_regions;
+  const char *exclude_regions_path;
+  /* --regionFilterReport: five lines "name\tcount" -- keepIntervals and excludeIntervals (the intervals of each set after
+   * merging), then examined, kept, dropped summed with bvcf_region_gate_count over the batches of the output.  Opened
+   * before any device work, written at the end of a successful run.  NULL or "" = no report */
+  const char *region_filter_path;
+} bvcf_config_regions;
+/* the whole struct: bvcf_config_variants_defaults, base.reserved[1] = BVCF_CONFIG_MORE_REGIONS, no regions, no paths */
+void bvcf_config_regions_defaults(bvcf_config_regions *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -70,6 +70,13 @@ int bvcf_bench_variant_kernel(bvcf_ctx *ctx, float *ms);
 /* the alleles[] slots k_variant_gate's grid covers in one step (its threads): a batch with more rows takes a second step */
 uint32_t bvcf_bench_variant_gate_stride(const bvcf_ctx *ctx);
 
+/* bvcf_set_region_table: k_region_gate on its own, as bvcf_bench_variant_kernel times the variant gate -- the chain of the
+ * last bench block once more on the first slot with all three gates off, then the kernel over those records between two
+ * HIP events: *ms.  BVCF_E_ARG on a ctx without a region table, or when no bvcf_bench_device* call went before */
+int bvcf_bench_region_kernel(bvcf_ctx *ctx, float *ms);
+/* the alleles[] slots k_region_gate's grid covers in one step (its threads): a batch with more rows takes a second step */
+uint32_t bvcf_bench_region_gate_stride(const bvcf_ctx *ctx);
+
 /* bvcf_enable_bed_rows: the .bed kernels over the records and class maps the first slot's last bench chain left, with HIP
  * events around them: ms = {k_bed_count + k_bed_scan + k_bed_index (the row index), k_bed_rows}; out[0] = the rows, out[1] = the bytes
  * k_bed_rows wrote (rows * row_bytes).  BVCF_E_ARG on a ctx without bed rows, BVCF_E_CAPACITY when the rows outrun the arena */
