@@ -50,7 +50,8 @@ BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_str
                  "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
-                 "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride"]
+                 "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
+                 "bvcf_bench_guard_check", "bvcf_bench_guarded_buffers"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -911,6 +912,23 @@ def bench_deflate_codes(cases, device=0):
     if rc:
         raise BvcfError(rc, "bvcf_bench_deflate_codes")
     return lens, rle, out
+
+
+def guard_check():
+    """bvcf_bench_guard_check (BVCF_POISON, tests only): the guard zones around every live device and pinned buffer, and
+    what the freed ones recorded -> (buffers damaged since the last call, the report of the first one or "")"""
+    msg = C.create_string_buffer(256)
+    lib.bvcf_bench_guard_check.restype = C.c_ulong
+    lib.bvcf_bench_guard_check.argtypes = [C.c_char_p, C.c_size_t]
+    n = lib.bvcf_bench_guard_check(msg, len(msg))
+    return int(n), msg.value.decode(errors="replace")
+
+
+def guarded_buffers():
+    """bvcf_bench_guarded_buffers: the buffers BVCF_POISON holds between guards at the moment (0 when the mode is off)"""
+    lib.bvcf_bench_guarded_buffers.restype = C.c_size_t
+    lib.bvcf_bench_guarded_buffers.argtypes = []
+    return int(lib.bvcf_bench_guarded_buffers())
 
 
 def string_header(cfg=None):

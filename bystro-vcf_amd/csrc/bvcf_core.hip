@@ -2046,6 +2046,9 @@ int bvcf_bench_stream_kernel(const bvcf_ctx *c) { return (c && is_stream(c)) ? (
 
 long bvcf_bench_head_left(const bvcf_ctx *c) { return (c && is_stream(c) && c->last_left != 0xFFFFFFFFu) ? (long)c->last_left : -1; }
 
+unsigned long bvcf_bench_guard_check(char *msg, size_t cap) { return bvcf_mem::guard_check(msg, cap); }
+size_t bvcf_bench_guarded_buffers(void) { return bvcf_mem::guarded_live(); }
+
 int bvcf_head_fast_line(const uint8_t *head, uint32_t head_bytes, uint32_t ls, uint32_t len_flags, const uint32_t counts[5],
                         uint32_t cmap_off, const uint32_t tab_bits[8], uint32_t line, uint32_t n_header, const char *allow_filter,
                         const char *exclude_filter, bvcf_line *out_line, bvcf_allele *out_allele) {

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/bvcf.h"
+#include "../../include/bvcf_bench.h"
 #include "../../include/bvcf_plan.h"
 
 namespace {
@@ -414,6 +415,14 @@ int main(int argc, char **argv) {
   if (fd_out != 1 && close(fd_out) != 0 && rc == BVCF_OK) {
     dprintf(fd_err, "close %s: %s\n", c.out.c_str(), strerror(errno));
     rc = BVCF_E_IO;
+  }
+  // BVCF_POISON (tests only): the guards around every buffer the run left alive, and what the freed ones recorded
+  if (const char *poison = getenv("BVCF_POISON"); poison && *poison) {
+    char msg[256];
+    if (bvcf_bench_guard_check(msg, sizeof msg)) {
+      fprintf(stderr, "BVCF_POISON: %s\n", msg);
+      rc = BVCF_E_FATAL;
+    }
   }
   fflush(nullptr);
   // (a profiler writes its results from exit handlers: leave normally under rocprofv3)

@@ -93,6 +93,17 @@ int bvcf_bench_trio_kernels(bvcf_ctx *ctx, float ms[4], uint64_t out[2]);
  * the events outrun their arena */
 int bvcf_bench_ld_kernels(bvcf_ctx *ctx, float ms[6], uint64_t out[2]);
 
+/* BVCF_POISON=XX (tests only; bvcf_devmem.h): every device and pinned buffer of a ctx created while it is set is filled
+ * with the byte XX and stands between two guard zones filled with ~XX.  Reads the guards of every live buffer and returns
+ * the number of buffers with a damaged guard since the last call -- live ones, and ones found damaged when they were freed;
+ * each buffer counts once.  msg (cap bytes, may be NULL) receives the report of the first one: the file and line of its
+ * allocation, its payload bytes, which guard, and the offset of the first damaged byte from the payload's start (negative:
+ * in front of it); an empty string when there is none.  The caller has collected every batch: a kernel still running
+ * would be read halfway.  0 when the mode is off.  Needs no ctx */
+unsigned long bvcf_bench_guard_check(char *msg, size_t cap);
+/* the buffers the mode holds alive at the moment (0 when it is off) */
+size_t bvcf_bench_guarded_buffers(void);
+
 #ifdef __cplusplus
 }
 #endif

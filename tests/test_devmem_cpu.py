@@ -38,4 +38,7 @@ def test_failed_allocations_leave_the_owners_empty(tmp_path):
 
 
 def test_owners_free_once_and_lose_nothing(tmp_path):
-    _build_and_run(tmp_path, "devmem_check_stand_ins", ["-DDEVMEM_STAND_INS"])
+    """... and the test mode (BVCF_POISON): the fills, the guards' reports by side, offset and allocation site, damage seen
+    only at reset(), the registry under moves and failed allocations, and the off mode asking for exactly today's bytes"""
+    out = _build_and_run(tmp_path, "devmem_check_stand_ins", ["-DDEVMEM_STAND_INS"])
+    assert "poison ok" in out
