@@ -47,7 +47,7 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
@@ -77,6 +77,7 @@ EXPORTS = [
     "bvcf_region_table_parse_specs", "bvcf_region_table_parse_bed", "bvcf_region_table_build", "bvcf_region_table_free",
     "bvcf_region_table_has", "bvcf_region_table_stays", "bvcf_set_region_table", "bvcf_region_gate_count",
     "bvcf_config_regions_defaults",
+    "bvcf_enable_grm", "bvcf_grm", "bvcf_config_grm_defaults",
 ]
 
 
@@ -291,6 +292,16 @@ class ConfigRegions(C.Structure):
     """bvcf_config_regions: a bvcf_config_variants and what came after it"""
     _fields_ = [("variants", ConfigVariants), ("regions", C.c_char_p), ("regions_path", C.c_char_p),
                 ("exclude_regions", C.c_char_p), ("exclude_regions_path", C.c_char_p), ("region_filter_path", C.c_char_p)]
+
+
+CONFIG_MORE_GRM = 7  # BVCF_CONFIG_MORE_GRM in Config.reserved[1]: the ConfigRegions is the head of a ConfigGrm
+GRM_MAX_BATCH_ROWS = 524288  # BVCF_GRM_MAX_BATCH_ROWS: most allele slots of a ctx with grm=True
+GRM_SHIFT = 14  # the GRM's scores are in units of 2^-14: A = T / (2^28 N)
+
+
+class ConfigGrm(C.Structure):
+    """bvcf_config_grm: a bvcf_config_regions and what came after it"""
+    _fields_ = [("regions", ConfigRegions), ("grm_prefix", C.c_char_p)]
 
 
 class RegionTableStruct(C.Structure):
@@ -616,7 +627,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--ld / --ldPrune: the still larger struct and its marker, only then)
     # (--keepVariants / --excludeVariants / --variantFilterReport: the largest struct and its marker, only then)
     # (--regions / --excludeRegions, their files, --regionFilterReport: the struct behind that one and its marker, only then)
-    rgc = ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
+    # (--grm: the struct behind that one and its marker, only then)
+    gc = ConfigGrm() if cfg.get("grm") else None
+    rgc = gc.regions if gc is not None else ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
     vc = (rgc.variants if rgc is not None else
           ConfigVariants() if any(cfg.get(k) for k in ("keepVariants", "excludeVariants", "variantFilterReport")) else None)
     ldc = vc.ld if vc is not None else ConfigLd() if cfg.get("ld") or cfg.get("ldPrune") else None
@@ -710,6 +723,10 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 keep.append(str(cfg[key]).encode())
                 setattr(rgc, field, keep[-1])
         c.reserved[1] = CONFIG_MORE_REGIONS
+    if gc is not None:  # PREFIX.grm.bin / .grm.N.bin / .grm.id of the run's rows
+        keep.append(str(cfg["grm"]).encode())
+        gc.grm_prefix = keep[-1]
+        c.reserved[1] = CONFIG_MORE_GRM
     c._keep = keep
     return c
 
@@ -1220,7 +1237,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None, regions=None):
+                 variants=None, regions=None, grm=False):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1234,6 +1251,13 @@ class Ctx:
         if pair_stats:  # bvcf_enable_pair_stats: the pair tables behind every chain (read with pair_stats())
             lib.bvcf_enable_pair_stats.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_pair_stats(self.h)
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+        if grm:  # bvcf_enable_grm: the GRM's integer tables behind every chain (read with grm() / grm_words())
+            lib.bvcf_enable_grm.argtypes = [C.c_void_p]
+            rc = lib.bvcf_enable_grm(self.h)
             if rc:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
@@ -1562,6 +1586,33 @@ class Ctx:
         lib.bvcf_bench_pair_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(lib.bvcf_bench_pair_kernels(self.h, ms))
         return list(ms)
+
+    def bench_grm_kernels(self):
+        """the GRM kernels over the first slot's last bench chain -> ms of [k_grm_list, k_grm_pack + k_grm_gemm, k_grm_sparse, k_grm_fold]"""
+        ms = (C.c_float * 4)()
+        lib.bvcf_bench_grm_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_grm_kernels(self.h, ms))
+        return list(ms)
+
+    def grm_words(self, reset=False):
+        """bvcf_enable_grm: the GRM's tables over the rows of the batches collected so far, as bvcf_grm gives them ->
+        (lo, hi, MM, N): the low and the high 64 bits of T (two's complement) and MM as uint64 arrays (n_samples,
+        n_samples), N the number of GRM rows (see include/bvcf.h)"""
+        ns = self.n_samples
+        n = ns * ns
+        out = np.zeros(3 * n + 1, dtype=np.uint64)
+        lib.bvcf_grm.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._check(lib.bvcf_grm(self.h, out.ctypes.data, int(reset)))
+        return out[:n].reshape(ns, ns), out[n:2 * n].reshape(ns, ns), out[2 * n:3 * n].reshape(ns, ns), int(out[3 * n])
+
+    def grm(self, reset=False):
+        """the same with T as an object array of Python integers -> (T, MM, N)"""
+        lo, hi, mm, n = self.grm_words(reset)
+        t = np.empty(lo.size, dtype=object)
+        for k, (l, h) in enumerate(zip(lo.ravel().tolist(), hi.ravel().tolist())):
+            v = (h << 64) | l
+            t[k] = v - (1 << 128) if v >> 127 else v
+        return t.reshape(lo.shape), mm, n
 
     def pair_stats(self, reset=False):
         """bvcf_enable_pair_stats: the pair tables over the rows of the batches collected so far -> uint64 array

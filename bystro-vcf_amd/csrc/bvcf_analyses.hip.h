@@ -149,6 +149,21 @@ struct PairStatsCtx {
   Event ev_fold;
 };
 
+// bvcf_enable_grm on a file with samples (bvcf_grm.hip.h): the GRM's integer tables behind every chain.  A slot holds its own
+// row lists (they follow max_alleles), the int8 operand of one chunk of dense rows and the batch's tables.  The totals are
+// the ctx's: the folds of the slots' batches follow one another through ev_fold
+struct GrmSlot {
+  DevBuf<GrmRow> dense, sparse;
+  DevBuf<uint32_t> ctr, bmm;
+  DevBuf<uint8_t> ops;
+  DevBuf<long long> bt, bv;
+};
+struct GrmCtx {
+  bool asked = false, on = false, folded = false;
+  DevBuf<unsigned long long> tot;
+  Event ev_fold;
+};
+
 }  // namespace
 
 #else  // ---- the functions, behind Slot, bvcf_ctx and HIP_TRY
@@ -159,9 +174,9 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes);
 int alloc_results(bvcf_ctx *c, Slot &s);
 void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot);
 
-// the per-sample, pair and trio counts, the .bed rows and the LD pairs are made from the class maps on the device: the
+// the per-sample, pair and trio counts, the GRM, the .bed rows and the LD pairs are made from the class maps on the device: the
 // maps are made whether or not the caller wants them on the host
-bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->bed.on || c->trio.on || c->ld.on; }
+bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->grm.on || c->bed.on || c->trio.on || c->ld.on; }
 
 // "<what> with batches in flight": what every call that changes what the slots hold says when it comes too early
 int refuse_in_flight(bvcf_ctx *c, const char *what) {
@@ -1467,6 +1482,20 @@ static int alloc_ss_tables(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
+// bvcf_enable_grm: the GRM's row lists (they follow max_alleles).  The batch's int64 tables hold kGrmMaxBatchRows rows
+// (bvcf_grm.hip.h): a ctx that may list more is refused, here and on the grow path
+static int alloc_grm_lists(bvcf_ctx *c, Slot &s) {
+  if (!c->grm.on) return BVCF_OK;
+  if (c->max_alleles > kGrmMaxBatchRows) {
+    c->err = "the GRM's batch tables hold " + std::to_string(kGrmMaxBatchRows) + " rows, the ctx reserves " +
+             std::to_string(c->max_alleles) + " allele slots: use smaller batches (max_batch_bytes / max_lines)";
+    return BVCF_E_TOO_BIG;
+  }
+  HIP_TRY(c, s.grm.dense.alloc(c->max_alleles));
+  HIP_TRY(c, s.grm.sparse.alloc(c->max_alleles));
+  return BVCF_OK;
+}
+
 // what follows max_lines / max_alleles or a bound of the ctx's, for the ctx's current capacities: the analyses' above, then
 // the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
 static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
@@ -1474,6 +1503,7 @@ static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_bed_rows(c, s)) return rc;
   if (const int rc = alloc_trios(c, s)) return rc;
   if (const int rc = alloc_ld(c, s)) return rc;
+  if (const int rc = alloc_grm_lists(c, s)) return rc;
   if (!c->ss_on && !c->pr.on) return BVCF_OK;
   s.pr.planes.reset();
   s.pr.cap_tiles = 0;
@@ -1549,9 +1579,48 @@ static void launch_sample_stats(bvcf_ctx *c, const KernelArgs &a, hipStream_t st
   if (c->pr.on && slot->pr.planes && slot->pr.bt) launch_pair_kernels(c, a, st, make_pr_args(c, *slot));
 }
 
+static GrmArgs make_grm_args(bvcf_ctx *c, Slot &s) {
+  GrmArgs ga{};
+  ga.dense = s.grm.dense;
+  ga.sparse = s.grm.sparse;
+  ga.ctr = s.grm.ctr;
+  ga.ops = s.grm.ops;
+  ga.bt = s.grm.bt;
+  ga.bmm = s.grm.bmm;
+  ga.bv = s.grm.bv;
+  ga.tot = c->grm.tot;
+  ga.list_cap = (uint32_t)s.grm.sparse.size();  // (the second of the two lists: there when both are)
+  ga.ns = c->n_samples;
+  ga.ns_pad = 4u * c->cmap_stride;
+  return ga;
+}
+
+// bvcf_enable_grm: the batch's integer tables (bvcf_grm.hip.h) -- the tables from zero, the row lists, the dense rows a chunk
+// at a time (a chunk past the list's end finds no tiles and returns: the list's length is the device's), the short lists
+static void launch_grm(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot, const Event *ev = nullptr) {
+  if (!c->grm.on || !slot || !slot->grm.dense || !slot->grm.bt) return;
+  const GrmArgs ga = make_grm_args(c, *slot);
+  const size_t n = (size_t)ga.ns * ga.ns;
+  hipMemsetAsync(ga.ctr, 0, 2 * sizeof(uint32_t), st);
+  hipMemsetAsync(ga.bt, 0, n * sizeof(long long), st);
+  hipMemsetAsync(ga.bmm, 0, n * sizeof(uint32_t), st);
+  hipMemsetAsync(ga.bv, 0, ((size_t)ga.ns + 1) * sizeof(long long), st);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_grm_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, ga);
+  mark(ev, st);
+  const uint32_t nb = ga.ns_pad / kGrmBlock;
+  for (uint64_t row0 = 0; row0 < ga.list_cap; row0 += kGrmChunkRows) {
+    hipLaunchKernelGGL(k_grm_pack, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, ga, (uint32_t)row0);
+    hipLaunchKernelGGL(k_grm_gemm, dim3(nb, nb), dim3(kWgThreads), 0, st, ga, (uint32_t)row0);
+  }
+  mark(ev, st);
+  hipLaunchKernelGGL(k_grm_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ga);
+}
+
 // the end of a chain with samples, behind the dosage rows: the counts, then the rows
 static void launch_analyses(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
   launch_sample_stats(c, a, st, slot);
+  launch_grm(c, a, st, slot);
   launch_rows(c, a, st, slot);
 }
 
@@ -1559,6 +1628,12 @@ static void launch_pr_fold(bvcf_ctx *c, hipStream_t st, const PairStatsArgs &pa)
   const size_t n = (size_t)kPrTables * pa.ns * pa.ns;
   const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
   hipLaunchKernelGGL(k_pr_fold, dim3(grid), dim3(kWgThreads), 0, st, pa);
+}
+
+static void launch_grm_fold(bvcf_ctx *c, hipStream_t st, const GrmArgs &ga) {
+  const size_t n = (size_t)ga.ns * ga.ns;
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
+  hipLaunchKernelGGL(k_grm_fold, dim3(grid), dim3(kWgThreads), 0, st, ga);
 }
 
 // the batch is in: its per-sample counts join the slot's totals and its pair tables the ctx's (ahead of the copies on the
@@ -1577,6 +1652,13 @@ static int launch_folds(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->pr.ev_fold, s.stream));
     c->pr.folded = true;
+  }
+  if (c->grm.on && s.grm.bt) {  // (likewise)
+    if (c->grm.folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->grm.ev_fold, 0));
+    launch_grm_fold(c, s.stream, make_grm_args(c, s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->grm.ev_fold, s.stream));
+    c->grm.folded = true;
   }
   return BVCF_OK;
 }
@@ -1667,6 +1749,76 @@ int bvcf_bench_pair_kernels(bvcf_ctx *c, float ms[4]) {
   launch_pair_kernels(c, a, s.stream, pa, ev);  // (ev[0] behind the memset, ev[1], ev[2])
   HIP_TRY(c, hipEventRecord(ev[3], s.stream));
   launch_pr_fold(c, s.stream, pa);
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  return finish_hook(c, ev, s.stream, ms);
+}
+
+int bvcf_enable_grm(bvcf_ctx *c) {
+  if (!c) return BVCF_E_ARG;
+  if (const int rc = refuse_in_flight(c, "bvcf_enable_grm")) return rc;
+  static_assert(BVCF_PAIR_MAX_SAMPLES <= BVCF_GRM_MAX_N, "the quantiser's bounds hold for every row of an accepted ctx");
+  if (c->n_samples > BVCF_PAIR_MAX_SAMPLES) {
+    c->err = "bvcf_enable_grm: " + std::to_string(c->n_samples) + " samples, the GRM's tables hold at most " +
+             std::to_string(BVCF_PAIR_MAX_SAMPLES);
+    return BVCF_E_ARG;
+  }
+  c->grm.asked = true;
+  if (!c->n_samples || c->grm.on) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t n = (size_t)c->n_samples * c->n_samples;
+  HIP_TRY(c, c->grm.tot.alloc(3 * n + 1));
+  HIP_TRY(c, hipMemset(c->grm.tot, 0, (3 * n + 1) * sizeof(unsigned long long)));
+  HIP_TRY(c, c->grm.ev_fold.create(hipEventDisableTiming));
+  c->grm.on = true;
+  for (auto &s : c->slots) {
+    HIP_TRY(c, s.grm.ctr.alloc(2));
+    HIP_TRY(c, s.grm.ops.alloc((size_t)kGrmChunkTiles * kGrmMats * 4u * c->cmap_stride * kGrmTile));
+    HIP_TRY(c, s.grm.bt.alloc(n));
+    HIP_TRY(c, s.grm.bmm.alloc(n));
+    HIP_TRY(c, s.grm.bv.alloc((size_t)c->n_samples + 1));
+    HIP_TRY(c, hipMemset(s.grm.ctr, 0, 2 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(s.grm.bt, 0, n * sizeof(long long)));
+    HIP_TRY(c, hipMemset(s.grm.bmm, 0, n * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(s.grm.bv, 0, ((size_t)c->n_samples + 1) * sizeof(long long)));
+    if (const int rc = alloc_grm_lists(c, s)) {
+      c->grm.on = false;
+      return rc;
+    }
+  }
+  return BVCF_OK;
+}
+
+int bvcf_grm(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->grm.asked) {
+    c->err = "bvcf_grm: bvcf_enable_grm was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (!c->grm.on) {  // (no sample columns: an empty table, no rows)
+    if (out) out[0] = 0;
+    return BVCF_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+  const size_t bytes = (3 * (size_t)c->n_samples * c->n_samples + 1) * sizeof(unsigned long long);
+  hipStream_t st = c->slots[0].stream;
+  if (out) HIP_TRY(c, hipMemcpyAsync(out, c->grm.tot, bytes, hipMemcpyDeviceToHost, st));
+  if (reset) HIP_TRY(c, hipMemsetAsync(c->grm.tot, 0, bytes, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BVCF_OK;
+}
+
+// (the last interval is k_grm_fold, which the product runs at collect -- launch_folds --: the hook's own step; the totals
+// take the block once more, as bvcf_bench_pair_kernels' do)
+int bvcf_bench_grm_kernels(bvcf_ctx *c, float ms[4]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[5];
+  if (const int rc = start_hook(c, "bvcf_bench_grm_kernels", c->grm.on && s.grm.dense && s.grm.bt, "the ctx has no GRM tables", ev)) return rc;
+  const KernelArgs a = make_args(c, s, nullptr, 0);  // (the kernels read the records, the counters and a.cmap only)
+  launch_grm(c, a, s.stream, &s, ev);  // (ev[0] behind the memsets, ev[1] behind k_grm_list, ev[2] behind the product)
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  launch_grm_fold(c, s.stream, make_grm_args(c, s));
   HIP_TRY(c, hipEventRecord(ev[4], s.stream));
   return finish_hook(c, ev, s.stream, ms);
 }

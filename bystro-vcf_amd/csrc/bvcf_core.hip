@@ -119,6 +119,7 @@ struct Slot {
   // the analyses behind k_finish (bvcf_analyses.hip.h)
   SampleStatsSlot ss;
   PairStatsSlot pr;
+  GrmSlot grm;
   SiteGateSlot gate;
   RowIndexSlot idx;
   BedSlot bed;
@@ -168,6 +169,7 @@ struct bvcf_ctx : bvcf_ctx_plan {
   uint32_t row_tail_len = 0, row_keep_pos = 0, row_keep_id = 0, row_keep_info = 0;
   // the analyses behind k_finish (bvcf_analyses.hip.h)
   PairStatsCtx pr;
+  GrmCtx grm;
   SiteGateCtx gate;
   VariantGateCtx variants;
   RegionGateCtx regions;

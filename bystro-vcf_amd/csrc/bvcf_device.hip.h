@@ -54,6 +54,9 @@
 //   (bvcf_enable_pair_stats, behind them and from the same row lists: k_pr_planes / k_pr_gemm / k_pr_sparse count, per
 //    pair of samples, the rows that name both -- the bit-matrix product behind --relatedness, bvcf_pairstats.hip.h;
 //    k_pr_fold adds a collected batch's tables to the ctx's totals)
+//   (bvcf_enable_grm, behind them: k_grm_list lists the polymorphic rows with their quantised standard scores, k_grm_pack /
+//    k_grm_gemm multiply the dense rows' int8 limbs on the matrix cores, k_grm_sparse adds the short lists' pairs -- the exact
+//    integer tables behind --grm, bvcf_grm.hip.h; k_grm_fold adds a collected batch's tables to the ctx's 128-bit totals)
 //   (bvcf_set_region_table, right behind k_finish and in front of the variant gate: k_region_gate finds every row's
 //    chromosome in the hash set of --regions / --excludeRegions, binary-searches the row's span in the chromosome's merged
 //    intervals and takes the unselected rows out -- bvcf_regions.hip.h)
@@ -120,6 +123,7 @@
 #include "bvcf_regions.hip.h"
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
+#include "bvcf_grm.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
 #include "bvcf_ld.hip.h"

@@ -417,10 +417,25 @@ void Driver::device_main(DevWorker *W) {
         }
         for (size_t k = 0; k < n; k++) W->pr_carry[k] += t[k];
       }
+      // (--grm: the same for the GRM's tables)
+      const bool grm = wants_grm(c_) && R_.pre.header.size() > 9;
+      if (grm) {
+        const size_t ns = R_.pre.header.size() - 9;
+        std::vector<uint64_t> t(grm_table_words(ns), 0);
+        if (bvcf_grm(W->ctx, t.data(), 1) != BVCF_OK) {
+          fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          return;
+        }
+        add_grm_table(W->grm_carry, t.data(), ns);
+      }
       for (size_t k = 1; k < in_flight.size(); k++) {
         bvcf_result tmp;
         bvcf_collect(W->ctx, &tmp);
         n_collects++;
+      }
+      if (grm && bvcf_grm(W->ctx, nullptr, 1) != BVCF_OK) {
+        fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+        return;
       }
       if (pr && bvcf_pair_stats(W->ctx, nullptr, 1) != BVCF_OK) {
         fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
@@ -643,6 +658,10 @@ int Driver::run(uint64_t *n_lines_in) {
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
+    if (const int rc = open_grm(R_, &msg)) {  // --grm: likewise, all three files
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
   }
   sniff_input();
   // --compressOutput bgzf: one compressed stream for the header and the rows, on the run's first device
@@ -843,6 +862,24 @@ int Driver::run(uint64_t *n_lines_in) {
       }
       if (rc_ != BVCF_OK) close(pr_fd_);  // (write_pair_stats closed it)
       pr_fd_ = -1;
+    }
+    if (R_.grm_fd >= 0 && rc_ == BVCF_OK) {
+      // --grm: the workers' tables added one after another into one host table (a failed run leaves the files empty)
+      const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0;
+      std::vector<uint64_t> sum(grm_table_words(ns), 0), t;
+      for (auto &W : workers_) {
+        if (!W->ctx) continue;
+        t.assign(grm_table_words(ns), 0);
+        if (bvcf_grm(W->ctx, t.data(), 0) != BVCF_OK) {
+          fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          break;
+        }
+        add_grm_table(sum, t.data(), ns);
+        if (!W->grm_carry.empty()) add_grm_table(sum, W->grm_carry.data(), ns);
+      }
+      std::string msg;
+      if (rc_ == BVCF_OK && write_grm(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+      if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
     }
     if (sg_fd_ >= 0) {
       // --siteFilterReport: the workers' counts of the batches they handed on

@@ -710,6 +710,11 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
            std::to_string(BVCF_PAIR_MAX_SAMPLES) + " (select fewer with --keepSamples / --excludeSamples)";
     return BVCF_E_ARG;
   }
+  if (wants_grm(R.cfg) && R.pre.header.size() > 9 + (size_t)BVCF_PAIR_MAX_SAMPLES) {  // (likewise)
+    *msg = "grm: " + std::to_string(R.pre.header.size() - 9) + " samples, the matrix holds at most " +
+           std::to_string(BVCF_PAIR_MAX_SAMPLES) + " (select fewer with --keepSamples / --excludeSamples)";
+    return BVCF_E_ARG;
+  }
   if (write_sample_list(R)) {  // main.go:298-304
     *msg = "Couldn't write sample list file";
     return BVCF_E_FATAL;
@@ -784,6 +789,13 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
       p.max_lines = (uint32_t)std::min<uint64_t>(R.max_batch / per_line + slack, 0x7FFFFFFFu);
     }
   }
+  // --grm: a ctx with the GRM on reserves at most BVCF_GRM_MAX_BATCH_ROWS allele slots (2 * max_lines + 1024 of them).  A
+  // batch of more lines grows the reservation as far as that; one that needs more fails with bvcf_reserve's message
+  if (wants_grm(R.cfg) && R.pre.header.size() > 9) {
+    const uint64_t floor_len = std::max<uint64_t>(48, 2ull * R.n_header_full);
+    const uint64_t derived = p.max_lines ? p.max_lines : std::min<uint64_t>(R.max_batch / floor_len + 4096, 0x7FFFFFFFu);
+    p.max_lines = (uint32_t)std::min<uint64_t>(derived, (BVCF_GRM_MAX_BATCH_ROWS - 1024u) / 2u);
+  }
   p.path = data ? choose_path(R, data, n_data) : 0;
   for (size_t i = 9; i < R.pre.header.size(); i++) {
     R.name_ptr.push_back(R.pre.header[i].data());
@@ -834,6 +846,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
     rc = bvcf_enable_pair_stats(*ctx);
     if (rc) {
       *msg = std::string("bvcf_enable_pair_stats: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
+  if (rc == BVCF_OK && wants_grm(R.cfg)) {  // --grm: the GRM's tables of every ctx of the run
+    rc = bvcf_enable_grm(*ctx);
+    if (rc) {
+      *msg = std::string("bvcf_enable_grm: ") + bvcf_last_error(*ctx);
       bvcf_destroy(*ctx);
       *ctx = nullptr;
     }
@@ -1627,6 +1647,74 @@ int write_pair_stats(int fd, const bvcf_config *c, const Preamble &pre, const ui
   const int saved = errno;
   if (close(fd) || bad) {
     *msg = std::string("relatedness: write failed: ") + strerror(bad ? saved : errno);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_grm(Run &R, std::string *msg) {
+  if (!wants_grm(R.cfg)) return BVCF_OK;
+  const std::string prefix = grm_prefix(R.cfg);
+  const std::pair<int *, const char *> files[3] = {{&R.grm_fd, ".grm.bin"}, {&R.grm_n_fd, ".grm.N.bin"}, {&R.grm_id_fd, ".grm.id"}};
+  for (const auto &f : files) {
+    const std::string path = prefix + f.second;
+    *f.first = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.first < 0) {
+      *msg = "open " + path + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  return BVCF_OK;
+}
+
+void add_grm_table(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns) {
+  const size_t n = ns * ns;
+  sum.resize(grm_table_words(ns), 0);
+  for (size_t k = 0; k < n; k++) grm_add128w(&sum[k], &sum[n + k], t[k], t[n + k]);
+  for (size_t k = 2 * n; k < 3 * n + 1; k++) sum[k] += t[k];
+}
+
+// A(i,j) = T(i,j) / (2^28 N(i,j)) with N(i,j) = N - miss_i - miss_j + MM(i,j), miss_i = MM(i,i): the correctly rounded double of
+// the integer T (what the conversion of a 128-bit integer gives) over the double 2^28 N(i,j) (exact), rounded to float32; 0
+// when no row has both samples called.  The diagonal by the same formula: PLINK's convention
+int write_grm(Run &R, const uint64_t *sum, std::string *msg) {
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0, n = ns * ns;
+  const uint64_t *lo = sum, *hi = sum + n, *mm = sum + 2 * n;
+  const uint64_t rows = ns ? sum[3 * n] : 0;
+  std::vector<float> a, cnt;
+  a.reserve(64 + ns);
+  cnt.reserve(64 + ns);
+  bool bad = false;
+  for (size_t i = 0; i < ns && !bad; i++) {
+    a.clear();
+    cnt.clear();
+    for (size_t j = 0; j <= i; j++) {
+      const uint64_t nij = rows - mm[i * ns + i] - mm[j * ns + j] + mm[i * ns + j];
+      const __int128 t = (__int128)(((unsigned __int128)hi[i * ns + j] << 64) | lo[i * ns + j]);
+      a.push_back(nij ? (float)((double)t / ((double)nij * 268435456.0)) : 0.0f);
+      cnt.push_back((float)nij);
+    }
+    bad = write_all(R.grm_fd, (const char *)a.data(), a.size() * sizeof(float)) != 0 ||
+          write_all(R.grm_n_fd, (const char *)cnt.data(), cnt.size() * sizeof(float)) != 0;
+  }
+  std::string ids;
+  for (size_t i = 0; i < ns; i++) {
+    ids.append(R.pre.header[9 + i]);
+    ids.push_back('\t');
+    ids.append(R.pre.header[9 + i]);
+    ids.push_back('\n');
+  }
+  if (!bad) bad = write_all(R.grm_id_fd, ids.data(), ids.size()) != 0;
+  int saved = errno;
+  for (int *fd : {&R.grm_fd, &R.grm_n_fd, &R.grm_id_fd}) {
+    if (close(*fd) && !bad) {
+      bad = true;
+      saved = errno;
+    }
+    *fd = -1;
+  }
+  if (bad) {
+    *msg = std::string("grm: write failed: ") + strerror(saved);
     return BVCF_E_IO;
   }
   return BVCF_OK;

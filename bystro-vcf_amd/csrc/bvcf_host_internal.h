@@ -8,6 +8,7 @@
 #include "../../include/bvcf_plan.h"
 #include "bvcf_input.h"
 #include "bvcf_bgzf.h"
+#include "bvcf_grm_q.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -261,8 +262,12 @@ struct Run {
   bool regions_on = false;
   bvcf_region_table region_table{};
   int region_fd = -1;
+  // --grm: PREFIX.grm.bin / .grm.N.bin / .grm.id, opened by open_grm before any device work; write_grm writes all three from
+  // the sum of the run's bvcf_grm tables at the end of a successful run and closes them
+  int grm_fd = -1, grm_n_fd = -1, grm_id_fd = -1;
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd})
+    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
+                   grm_n_fd, grm_id_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
     bvcf_variant_table_free(&variant_table);
@@ -390,6 +395,23 @@ inline const bvcf_config_regions *regions_config(const bvcf_config *c) {
 // five lines written (counts = the sum of bvcf_region_gate_count over the batches of the output) and the file closed
 int open_regions(Run &R, std::string *msg);
 int write_region_report(Run &R, const uint64_t counts[3], std::string *msg);
+// --grm: bvcf_config_grm.grm_prefix of a config that reaches up to it (the eighth marker); NULL otherwise
+inline const char *grm_prefix(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_GRM) ? reinterpret_cast<const bvcf_config_grm *>(c)->grm_prefix
+                                                                                        : nullptr;
+}
+// true when the run writes the matrix (every ctx of the run then gets bvcf_enable_grm)
+inline bool wants_grm(const bvcf_config *c) {
+  const char *p = grm_prefix(c);
+  return p && *p;
+}
+// the three files opened (truncated) -- BVCF_E_IO with one message in *msg; one ctx's bvcf_grm table t ([3 S S + 1]) added into
+// the run's sum (T in 128 bits); the three files written from the sum and closed
+int open_grm(Run &R, std::string *msg);
+void add_grm_table(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns);
+int write_grm(Run &R, const uint64_t *sum, std::string *msg);
+// the words of a bvcf_grm table over ns samples
+inline size_t grm_table_words(size_t ns) { return 3 * ns * ns + 1; }
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

@@ -63,6 +63,9 @@ struct Cli {
   // given together (decided on the device, in front of the variant list and the site gate); --regionFilterReport PATH, the
   // merged intervals of each set and how many rows the regions examined, kept and dropped
   std::string regions, regions_file, exclude_regions, exclude_regions_file, region_report;
+  // extension: --grm PREFIX, the genomic relationship matrix of the run's rows in GCTA's binary format, PREFIX.grm.bin /
+  // .grm.N.bin / .grm.id (exact integer tables, multiplied on the device's matrix cores)
+  std::string grm;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -159,7 +162,8 @@ int parse(int argc, char **argv, Cli &c) {
         name == "minMaf" || name == "maxMaf" || name == "minMac" || name == "maxMissing" || name == "hwe" || name == "siteFilterReport" ||
         name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
-        name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport") {
+        name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
+        name == "grm") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -183,6 +187,8 @@ int parse(int argc, char **argv, Cli &c) {
         c.site_report = val;
       } else if (name == "plinkOutput") {
         c.plink = val;
+      } else if (name == "grm") {
+        c.grm = val;
       } else if (name == "mendel" || name == "mendelErrors") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to write\n", name.c_str());
@@ -307,10 +313,10 @@ int main(int argc, char **argv) {
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
   // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so are --variantFilterReport and
-  // --regionFilterReport alone)
+  // --regionFilterReport alone; --grm alone: a GRM-only pass)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
       c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
-      c.variant_report.empty() && c.region_report.empty()) {
+      c.variant_report.empty() && c.region_report.empty() && c.grm.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -325,9 +331,10 @@ int main(int argc, char **argv) {
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
-  // regions and their report)
-  bvcf_config_regions rc_cfg;
-  bvcf_config_regions_defaults(&rc_cfg);
+  // regions and their report; behind those the --grm prefix)
+  bvcf_config_grm grm_cfg;
+  bvcf_config_grm_defaults(&grm_cfg);
+  bvcf_config_regions &rc_cfg = grm_cfg.regions;
   bvcf_config_variants &vc = rc_cfg.variants;
   bvcf_config_ld &ldc = vc.ld;
   bvcf_config_trios &trios = ldc.trios;
@@ -404,6 +411,7 @@ int main(int argc, char **argv) {
   rc_cfg.exclude_regions = c.exclude_regions.c_str();
   rc_cfg.exclude_regions_path = c.exclude_regions_file.c_str();
   rc_cfg.region_filter_path = c.region_report.c_str();
+  grm_cfg.grm_prefix = c.grm.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -96,6 +96,8 @@ enum {
 #define BVCF_NO_CMAP 0xFFFFFFFFu
 #define BVCF_DEVICE_PAD 64      /* bytes a device-resident block must own past nbytes */
 #define BVCF_PAIR_MAX_SAMPLES 8192u /* most samples bvcf_enable_pair_stats accepts: the tables grow with their square */
+#define BVCF_GRM_MAX_BATCH_ROWS 524288u /* most allele slots (bvcf_params.max_alleles, bvcf_reserve) of a ctx with bvcf_enable_grm:
+                                          a batch's int64 tables hold the sums of that many rows */
 #define BVCF_MAX_THRESHOLD 999999999u /* largest bvcf_params.min_gq / min_dp (a value of 10 digits or more is no number) */
 /* bvcf_set_site_gate: the fail bits of a gated record, in bvcf_allele.pad[0] */
 #define BVCF_GATE_MIN_MAF 1u
@@ -419,6 +421,28 @@ int bvcf_enable_pair_stats(bvcf_ctx *ctx);
  * for the ctx's slots; reset: zero the totals after reading them (out may then be NULL).  BVCF_E_ARG on a ctx on which
  * bvcf_enable_pair_stats was not called. */
 int bvcf_pair_stats(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S: [t][i][j] */, int reset);
+/* The genomic relationship matrix over the same rows, in integers, made on the device from the class maps (which the ctx then
+ * makes even when want_class_maps is 0, without copying them to the host).  A sample's dosage g in a row is 0 (no list names
+ * it), 1 (het), 2 (hom; a haploid call counts as hom) or missing.  From the record's own counts n = S - n_miss,
+ * a = n_het + 2 n_hom and D = 2 a (2n - a); a row with D == 0 is monomorphic and skipped, the others are the GRM rows.  q(g) is
+ * the integer nearest to (2n g - 2a) 2^14 / sqrt(D) -- the standard score (g - 2p) / sqrt(2p (1 - p)), p = a / 2n, in units of
+ * 2^-14 --, ties away from zero, decided by integer compares alone (bvcf_grm_q.h); q(missing) = 0.  Over the GRM rows:
+ *   T(i,j) = sum q(g_i) q(g_j)   (symmetric, 128 bits)     MM(i,j) = sum M_i M_j, M = 1 for a missing call     N = their number
+ * so that N(i,j) = N - MM(i,i) - MM(j,j) + MM(i,j) rows have both samples called and A(i,j) = T(i,j) / (2^28 N(i,j)).  A
+ * multiallelic line gives one row per output allele, "this ALT against the rest".  The dense rows are multiplied on the
+ * matrix cores (int8 limbs, int32 sums), the short lists added with integer atomics: the tables are a property of the data.
+ * bvcf_enable_grm: call once, before the first submit, as bvcf_enable_pair_stats is called; BVCF_E_ARG for a ctx of more than
+ * BVCF_PAIR_MAX_SAMPLES samples (after bvcf_params.sample_keep; the totals take 24 bytes per ordered pair, a slot's batch
+ * tables 12); BVCF_E_TOO_BIG -- here and from bvcf_reserve -- for a ctx that reserves more than BVCF_GRM_MAX_BATCH_ROWS allele slots
+ * (use smaller batches, or a smaller bvcf_params.max_lines); a no-op returning BVCF_OK on a ctx without sample columns.
+ * bvcf_params and the ABI version do not change with it.
+ * bvcf_grm: out[0 .. S*S) the low and out[S*S .. 2*S*S) the high 64 bits of T(i,j) in two's complement, at i * S + j;
+ * out[2*S*S .. 3*S*S) MM; out[3*S*S] N -- over the batches collected so far.  The contract of bvcf_pair_stats: a batch counts
+ * once it is collected with BVCF_OK, one that came back BVCF_E_CAPACITY does not; waits for the ctx's slots; reset: zero the
+ * totals after reading them (out may then be NULL).  A ctx without sample columns writes out[0] = 0 alone.  BVCF_E_ARG on a
+ * ctx on which bvcf_enable_grm was not called. */
+int bvcf_enable_grm(bvcf_ctx *ctx);
+int bvcf_grm(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S + 1 */, int reset);
 /* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
  * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
  * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
@@ -914,6 +938,25 @@ typedef struct {
 } bvcf_config_regions;
 /* the whole struct: bvcf_config_variants_defaults, base.reserved[1] = BVCF_CONFIG_MORE_REGIONS, no regions, no paths */
 void bvcf_config_regions_defaults(bvcf_config_regions *c);
+/* Likewise what came after bvcf_config_regions: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_GRM.  bvcf_config_grm_defaults sets that; the seven older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_GRM 7
+typedef struct {
+  bvcf_config_regions regions;
+  /* --grm PREFIX: the run's genomic relationship matrix in GCTA's binary format, from the bvcf_grm tables of the run's ctxs.
+   * PREFIX.grm.bin: float32 little-endian A(i,j), the lower triangle with the diagonal, i = 0 .. S-1 and j = 0 .. i within
+   * it; A = (float)((double)T / (double)(2^28 N(i,j))), the double of the integer T correctly rounded, 0 when N(i,j) = 0; the
+   * diagonal by the same formula (PLINK's convention, not GCTA's inbreeding diagonal).  PREFIX.grm.N.bin: N(i,j) as float32
+   * in the same order.  PREFIX.grm.id: "name \t name \n" per (kept) sample in header order.  All three are opened before
+   * any device work and written at the end of a successful run; BVCF_E_ARG with one message when more than
+   * BVCF_PAIR_MAX_SAMPLES samples are left after the sample selection.  The rows are the rows sample_stats_path counts: after
+   * min_gq / min_dp, the sample selection, the regions, the variant list and the site gate.  A file without sample columns
+   * gives three empty files.  The bytes do not depend on devices, batch size or input kind, and no other output changes
+   * with them.  NULL or "" = no matrix */
+  const char *grm_prefix;
+} bvcf_config_grm;
+/* the whole struct: bvcf_config_regions_defaults, base.reserved[1] = BVCF_CONFIG_MORE_GRM, no matrix */
+void bvcf_config_grm_defaults(bvcf_config_grm *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -40,6 +40,12 @@ long bvcf_bench_head_left(const bvcf_ctx *ctx);
  * BVCF_E_ARG on a ctx without pair tables */
 int bvcf_bench_pair_kernels(bvcf_ctx *ctx, float ms[4]);
 
+/* bvcf_enable_grm: the GRM kernels once more over what the last bvcf_bench_device* chain of the ctx's first slot left (its
+ * records and class maps), with HIP events around each step: ms = {k_grm_list, k_grm_pack + k_grm_gemm over every chunk,
+ * k_grm_sparse, k_grm_fold}.  The fold adds the batch to the ctx's totals like a collect would: for a ctx that only measures.
+ * BVCF_E_ARG on a ctx without GRM tables */
+int bvcf_bench_grm_kernels(bvcf_ctx *ctx, float ms[4]);
+
 /* The exact Hardy-Weinberg test as the site gate runs it on the device: triples = n x {het, hom, other}, p[j] the p value of
  * triple j -- by the thread-per-row recurrence or by a wave (k_site_hwe's code), chosen by the length of the support as
  * k_site_gate chooses.  Needs no ctx */
