@@ -47,7 +47,7 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
@@ -59,7 +59,8 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
                 "bvcf_site_gate_verdict", "bvcf_hwe_exact", "bvcf_hwe_inline_terms", "bvcf_bed_row",
                 "bvcf_trio_verdict", "bvcf_parse_fam",
                 "bvcf_ld_counts", "bvcf_ld_in_ld", "bvcf_parse_ld_r2", "bvcf_ld_seam_create", "bvcf_ld_seam_push",
-                "bvcf_ld_seam_read", "bvcf_ld_seam_rows", "bvcf_ld_seam_pairs", "bvcf_ld_seam_destroy"]
+                "bvcf_ld_seam_read", "bvcf_ld_seam_rows", "bvcf_ld_seam_pairs", "bvcf_ld_seam_destroy",
+                "bvcf_score_weight", "bvcf_score_limbs", "bvcf_score_decimal"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -78,6 +79,8 @@ EXPORTS = [
     "bvcf_region_table_has", "bvcf_region_table_stays", "bvcf_set_region_table", "bvcf_region_gate_count",
     "bvcf_config_regions_defaults",
     "bvcf_enable_grm", "bvcf_grm", "bvcf_config_grm_defaults",
+    "bvcf_score_table_build", "bvcf_score_table_parse", "bvcf_score_table_free", "bvcf_score_table_find", "bvcf_set_score_table",
+    "bvcf_score", "bvcf_config_score_defaults",
 ]
 
 
@@ -302,6 +305,140 @@ GRM_SHIFT = 14  # the GRM's scores are in units of 2^-14: A = T / (2^28 N)
 class ConfigGrm(C.Structure):
     """bvcf_config_grm: a bvcf_config_regions and what came after it"""
     _fields_ = [("regions", ConfigRegions), ("grm_prefix", C.c_char_p)]
+
+
+CONFIG_MORE_SCORE = 8  # BVCF_CONFIG_MORE_SCORE in Config.reserved[1]: the ConfigGrm is the head of a ConfigScore
+SCORE_ONE = 10 ** 12  # a weight's integer W is in units of 10^-12
+SCORE_MAX_W = 10 ** 18
+SCORE_MAX_COLUMNS = 64
+
+
+class ConfigScore(C.Structure):
+    """bvcf_config_score: a bvcf_config_grm and what came after it"""
+    _fields_ = [("grm", ConfigGrm), ("score_path", C.c_char_p), ("score_output_path", C.c_char_p),
+                ("score_report_path", C.c_char_p)]
+
+
+class ScoreTableStruct(C.Structure):
+    """bvcf_score_table"""
+    _fields_ = [("entries", C.c_void_p), ("capacity", C.c_uint64), ("blob", C.c_void_p), ("blob_bytes", C.c_uint64),
+                ("n", C.c_uint64), ("weights", C.c_void_p), ("n_columns", C.c_uint32), ("n_limbs", C.c_uint32),
+                ("names", C.c_void_p), ("names_bytes", C.c_uint64)]
+
+
+def score_weight(text):
+    """bvcf_score_weight: a weight's text (bytes) -> the integer nearest to w 10^12, ties away from zero; ValueError for text
+    that is no weight, OverflowError above 10^18  (host code, no device)"""
+    out = C.c_int64(0)
+    lib.bvcf_score_weight.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+    rc = lib.bvcf_score_weight(bytes(text), len(text), C.byref(out))
+    if rc == -2:
+        raise OverflowError("weight above 10^6 in size")
+    if rc:
+        raise ValueError("not a weight")
+    return int(out.value)
+
+
+def score_limbs(w):
+    """bvcf_score_limbs: W -> (its eight balanced base-256 digits, the smallest count that holds it)"""
+    out = (C.c_int8 * 8)()
+    lib.bvcf_score_limbs.argtypes = [C.c_int64, C.c_void_p]
+    n = lib.bvcf_score_limbs(w, out)
+    return [int(x) for x in out], int(n)
+
+
+def score_decimal(t):
+    """bvcf_score_decimal: the integer t (128 bits, two's complement) over 10^12 as exact decimal text"""
+    v = t & ((1 << 128) - 1)
+    out = C.create_string_buffer(48)
+    lib.bvcf_score_decimal.restype = C.c_size_t
+    lib.bvcf_score_decimal.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+    n = lib.bvcf_score_decimal(v & ((1 << 64) - 1), v >> 64, out)
+    return out.raw[:n]
+
+
+class ScoreTable:
+    """a host score table: bvcf_score_table_build over loci (bytes) and their integer weights W (a list of K per locus), or
+    -- text= -- bvcf_score_table_parse over the bytes of a score file  (host code, no device)"""
+
+    def __init__(self, loci=None, weights=None, names=None, text=None):
+        self.t = ScoreTableStruct()
+        if text is not None:
+            err = C.create_string_buffer(512)
+            lib.bvcf_score_table_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t]
+            rc = lib.bvcf_score_table_parse(bytes(text), len(text), C.byref(self.t), err, len(err))
+            if rc:
+                raise BvcfError(rc, err.value.decode())
+            return
+        loci = [bytes(x) for x in loci]
+        w = np.ascontiguousarray(np.array(weights, dtype=np.int64).reshape(len(loci), -1) if len(loci) else
+                                 np.zeros((0, len(names or [b"SCORE1"])), dtype=np.int64))
+        k = w.shape[1]
+        nm = b"".join(bytes(x) + b"\0" for x in (names or [b"SCORE%d" % (i + 1) for i in range(k)]))
+        blob = b"".join(loci)
+        lens = np.array([len(x) for x in loci], dtype=np.uint32)
+        offs = np.zeros(len(loci), dtype=np.uint64)
+        if len(loci) > 1:
+            offs[1:] = np.cumsum(lens[:-1], dtype=np.uint64)
+        lib.bvcf_score_table_build.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                               C.c_char_p, C.c_size_t, C.c_void_p]
+        rc = lib.bvcf_score_table_build(blob, offs.ctypes.data if len(loci) else None, lens.ctypes.data if len(loci) else None,
+                                        len(loci), w.ctypes.data if len(loci) else None, k, nm, len(nm), C.byref(self.t))
+        if rc:
+            raise BvcfError(rc, "bvcf_score_table_build")
+
+    @property
+    def n(self):
+        return int(self.t.n)
+
+    @property
+    def capacity(self):
+        return int(self.t.capacity)
+
+    @property
+    def n_columns(self):
+        return int(self.t.n_columns)
+
+    @property
+    def n_limbs(self):
+        return int(self.t.n_limbs)
+
+    @property
+    def names(self):
+        return C.string_at(self.t.names, self.t.names_bytes).split(b"\0")[:-1] if self.t.names_bytes else []
+
+    @property
+    def weights(self):
+        """the int8 weight rows [n][n_columns * n_limbs + 1] (copied)"""
+        cols = self.n_columns * self.n_limbs + 1
+        if not self.n:
+            return np.zeros((0, cols), dtype=np.int8)
+        return np.frombuffer(C.string_at(self.t.weights, self.n * cols), dtype=np.int8).reshape(self.n, cols).copy()
+
+    @property
+    def entries(self):
+        """the slots as a VARIANT_ENTRY_DTYPE array (copied); the fourth word is the entry's weight row"""
+        n = self.capacity * VARIANT_ENTRY_DTYPE.itemsize
+        return np.frombuffer(C.string_at(self.t.entries, n), dtype=VARIANT_ENTRY_DTYPE).copy()
+
+    def find(self, s):
+        """bvcf_score_table_find: the entry's weight row by the probe the device runs, or -1"""
+        lib.bvcf_score_table_find.restype = C.c_int64
+        lib.bvcf_score_table_find.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+        r = int(lib.bvcf_score_table_find(C.byref(self.t), bytes(s), len(s)))
+        if r < -1:
+            raise ValueError("bvcf_score_table_find: bad arguments")
+        return r
+
+    def close(self):
+        lib.bvcf_score_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_score_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class RegionTableStruct(C.Structure):
@@ -628,7 +765,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--keepVariants / --excludeVariants / --variantFilterReport: the largest struct and its marker, only then)
     # (--regions / --excludeRegions, their files, --regionFilterReport: the struct behind that one and its marker, only then)
     # (--grm: the struct behind that one and its marker, only then)
-    gc = ConfigGrm() if cfg.get("grm") else None
+    # (--score / --scoreOutput / --scoreReport: the struct behind that one and its marker, only then)
+    sc = ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
+    gc = sc.grm if sc is not None else ConfigGrm() if cfg.get("grm") else None
     rgc = gc.regions if gc is not None else ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
     vc = (rgc.variants if rgc is not None else
           ConfigVariants() if any(cfg.get(k) for k in ("keepVariants", "excludeVariants", "variantFilterReport")) else None)
@@ -724,9 +863,16 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 setattr(rgc, field, keep[-1])
         c.reserved[1] = CONFIG_MORE_REGIONS
     if gc is not None:  # PREFIX.grm.bin / .grm.N.bin / .grm.id of the run's rows
-        keep.append(str(cfg["grm"]).encode())
-        gc.grm_prefix = keep[-1]
+        if cfg.get("grm"):
+            keep.append(str(cfg["grm"]).encode())
+            gc.grm_prefix = keep[-1]
         c.reserved[1] = CONFIG_MORE_GRM
+    if sc is not None:  # the score file, the table of per-sample scores and the report
+        for key, field in (("score", "score_path"), ("scoreOutput", "score_output_path"), ("scoreReport", "score_report_path")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(sc, field, keep[-1])
+        c.reserved[1] = CONFIG_MORE_SCORE
     c._keep = keep
     return c
 
@@ -1237,7 +1383,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None, regions=None, grm=False):
+                 variants=None, regions=None, grm=False, score=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1255,6 +1401,15 @@ class Ctx:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
                 raise BvcfError(rc, msg)
+        self.score_columns = 0
+        if score is not None:  # bvcf_set_score_table: a built ScoreTable; the scores' words behind every chain (score_words())
+            lib.bvcf_set_score_table.argtypes = [C.c_void_p, C.c_void_p]
+            rc = lib.bvcf_set_score_table(self.h, C.byref(score.t))
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+            self.score_columns = score.n_columns
         if grm:  # bvcf_enable_grm: the GRM's integer tables behind every chain (read with grm() / grm_words())
             lib.bvcf_enable_grm.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_grm(self.h)
@@ -1593,6 +1748,37 @@ class Ctx:
         lib.bvcf_bench_grm_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(lib.bvcf_bench_grm_kernels(self.h, ms))
         return list(ms)
+
+    def bench_score_kernels(self):
+        """the score kernels over the first slot's last bench chain -> ms of [k_score_list, k_score_gemm, k_score_sparse, k_score_fold]"""
+        ms = (C.c_float * 4)()
+        lib.bvcf_bench_score_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_score_kernels(self.h, ms))
+        return list(ms)
+
+    def score_words(self, reset=False):
+        """bvcf_set_score_table: the scores over the rows of the batches collected so far, as bvcf_score gives them ->
+        (lo, hi, G, X, R): the low and the high 64 bits of T (two's complement) as uint64 arrays (n_samples, K), G and X as
+        uint64 arrays (n_samples), R the number of matched rows (see include/bvcf.h)"""
+        ns, k = self.n_samples, self.score_columns
+        n = ns * k
+        out = np.zeros(2 * n + 2 * ns + 1, dtype=np.uint64)
+        lib.bvcf_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        self._check(lib.bvcf_score(self.h, out.ctypes.data, int(reset)))
+        return (out[:n].reshape(ns, k), out[n:2 * n].reshape(ns, k), out[2 * n:2 * n + ns].copy(),
+                out[2 * n + ns:2 * n + 2 * ns].copy(), int(out[2 * n + 2 * ns]))
+
+    def scores(self, reset=False):
+        """the same with T as a list of rows of Python integers -> (T, G, X, R)"""
+        lo, hi, g, x, r = self.score_words(reset)
+        t = []
+        for lrow, hrow in zip(lo.tolist(), hi.tolist()):
+            row = []
+            for l, h in zip(lrow, hrow):
+                v = (h << 64) | l
+                row.append(v - (1 << 128) if v >> 127 else v)
+            t.append(row)
+        return t, g.tolist(), x.tolist(), r
 
     def grm_words(self, reset=False):
         """bvcf_enable_grm: the GRM's tables over the rows of the batches collected so far, as bvcf_grm gives them ->

@@ -164,6 +164,25 @@ struct GrmCtx {
   Event ev_fold;
 };
 
+// bvcf_set_score_table on a file with samples (bvcf_score.hip.h): the scores' integer tables behind every chain.  A slot
+// holds its own row lists (they follow max_alleles) and the batch's tables.  The score table -- hash set, blob and weight
+// rows -- and the totals are the ctx's: the folds of the slots' batches follow one another through ev_fold
+struct ScoreSlot {
+  DevBuf<uint2> dense, sparse;
+  DevBuf<uint32_t> ctr;
+  DevBuf<long long> bt, shi;
+  DevBuf<unsigned long long> slo;
+};
+struct ScoreCtx {
+  bool asked = false, on = false, folded = false;
+  uint32_t mask = 0, n_entries = 0, K = 0, L = 0, wstride = 0;
+  DevBuf<VariantEntry> entries;
+  DevBuf<uint8_t> blob;
+  DevBuf<int8_t> weights;
+  DevBuf<unsigned long long> tot;
+  Event ev_fold;
+};
+
 }  // namespace
 
 #else  // ---- the functions, behind Slot, bvcf_ctx and HIP_TRY
@@ -174,9 +193,9 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes);
 int alloc_results(bvcf_ctx *c, Slot &s);
 void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot);
 
-// the per-sample, pair and trio counts, the GRM, the .bed rows and the LD pairs are made from the class maps on the device: the
+// the per-sample, pair and trio counts, the GRM, the scores, the .bed rows and the LD pairs are made from the class maps on the device: the
 // maps are made whether or not the caller wants them on the host
-bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->grm.on || c->bed.on || c->trio.on || c->ld.on; }
+bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->grm.on || c->score.on || c->bed.on || c->trio.on || c->ld.on; }
 
 // "<what> with batches in flight": what every call that changes what the slots hold says when it comes too early
 int refuse_in_flight(bvcf_ctx *c, const char *what) {
@@ -1496,6 +1515,14 @@ static int alloc_grm_lists(bvcf_ctx *c, Slot &s) {
   return BVCF_OK;
 }
 
+// bvcf_set_score_table: the scores' row lists (they follow max_alleles)
+static int alloc_score_lists(bvcf_ctx *c, Slot &s) {
+  if (!c->score.on) return BVCF_OK;
+  HIP_TRY(c, s.score.dense.alloc(c->max_alleles));
+  HIP_TRY(c, s.score.sparse.alloc(c->max_alleles));
+  return BVCF_OK;
+}
+
 // what follows max_lines / max_alleles or a bound of the ctx's, for the ctx's current capacities: the analyses' above, then
 // the row lists of the per-sample and the pair counts (they follow max_alleles), and the pair counts' bit planes
 static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
@@ -1504,6 +1531,7 @@ static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_trios(c, s)) return rc;
   if (const int rc = alloc_ld(c, s)) return rc;
   if (const int rc = alloc_grm_lists(c, s)) return rc;
+  if (const int rc = alloc_score_lists(c, s)) return rc;
   if (!c->ss_on && !c->pr.on) return BVCF_OK;
   s.pr.planes.reset();
   s.pr.cap_tiles = 0;
@@ -1617,10 +1645,54 @@ static void launch_grm(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *s
   hipLaunchKernelGGL(k_grm_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, ga);
 }
 
+static ScoreArgs make_score_args(bvcf_ctx *c, Slot &s) {
+  ScoreArgs sa{};
+  sa.entries = c->score.entries;
+  sa.blob = c->score.blob;
+  sa.weights = c->score.weights;
+  sa.dense = s.score.dense;
+  sa.sparse = s.score.sparse;
+  sa.ctr = s.score.ctr;
+  sa.bt = s.score.bt;
+  sa.slo = s.score.slo;
+  sa.shi = s.score.shi;
+  sa.tot = c->score.tot;
+  sa.mask = c->score.mask;
+  sa.n_entries = c->score.n_entries;
+  sa.K = c->score.K;
+  sa.L = c->score.L;
+  sa.n_cols = c->score.K * c->score.L + 1u;
+  sa.wstride = c->score.wstride;
+  sa.list_cap = (uint32_t)s.score.sparse.size();  // (the second of the two lists: there when both are)
+  sa.ns = c->n_samples;
+  return sa;
+}
+
+// bvcf_set_score_table: the batch's integer tables (bvcf_score.hip.h) -- the tables from zero, the row lists, the dense
+// rows' product (the tiles of a (sample block, column group) dealt among `split` workgroups: the list's length is the
+// device's), the short lists
+static void launch_score(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot, const Event *ev = nullptr) {
+  if (!c->score.on || !slot || !slot->score.dense || !slot->score.bt) return;
+  const ScoreArgs sa = make_score_args(c, *slot);
+  hipMemsetAsync(sa.ctr, 0, 3 * sizeof(uint32_t), st);
+  hipMemsetAsync(sa.bt, 0, (size_t)sa.ns * (sa.n_cols + 1u) * sizeof(long long), st);
+  hipMemsetAsync(sa.slo, 0, (size_t)sa.ns * sa.K * sizeof(unsigned long long), st);
+  hipMemsetAsync(sa.shi, 0, (size_t)sa.ns * sa.K * sizeof(long long), st);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_score_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, a, sa);
+  mark(ev, st);
+  const uint32_t nb = 4u * c->cmap_stride / kScoreBlock, ng = (sa.wstride + kScoreGroupCols - 1u) / kScoreGroupCols;
+  const uint32_t split = std::min<uint32_t>(kScoreMaxSplit, std::max<uint32_t>(1u, 2u * (uint32_t)c->n_cu / (nb * ng)));
+  hipLaunchKernelGGL(k_score_gemm, dim3(nb, ng, split), dim3(kWgThreads), 0, st, a, sa);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_score_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);
+}
+
 // the end of a chain with samples, behind the dosage rows: the counts, then the rows
 static void launch_analyses(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
   launch_sample_stats(c, a, st, slot);
   launch_grm(c, a, st, slot);
+  launch_score(c, a, st, slot);
   launch_rows(c, a, st, slot);
 }
 
@@ -1634,6 +1706,12 @@ static void launch_grm_fold(bvcf_ctx *c, hipStream_t st, const GrmArgs &ga) {
   const size_t n = (size_t)ga.ns * ga.ns;
   const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
   hipLaunchKernelGGL(k_grm_fold, dim3(grid), dim3(kWgThreads), 0, st, ga);
+}
+
+static void launch_score_fold(bvcf_ctx *c, hipStream_t st, const ScoreArgs &sa) {
+  const size_t n = (size_t)sa.ns * (sa.K + 1u);
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + kWgThreads - 1) / kWgThreads, (size_t)c->n_cu * 16);
+  hipLaunchKernelGGL(k_score_fold, dim3(grid), dim3(kWgThreads), 0, st, sa);
 }
 
 // the batch is in: its per-sample counts join the slot's totals and its pair tables the ctx's (ahead of the copies on the
@@ -1659,6 +1737,13 @@ static int launch_folds(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->grm.ev_fold, s.stream));
     c->grm.folded = true;
+  }
+  if (c->score.on && s.score.bt) {  // (likewise)
+    if (c->score.folded) HIP_TRY(c, hipStreamWaitEvent(s.stream, c->score.ev_fold, 0));
+    launch_score_fold(c, s.stream, make_score_args(c, s));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->score.ev_fold, s.stream));
+    c->score.folded = true;
   }
   return BVCF_OK;
 }
@@ -1819,6 +1904,311 @@ int bvcf_bench_grm_kernels(bvcf_ctx *c, float ms[4]) {
   launch_grm(c, a, s.stream, &s, ev);  // (ev[0] behind the memsets, ev[1] behind k_grm_list, ev[2] behind the product)
   HIP_TRY(c, hipEventRecord(ev[3], s.stream));
   launch_grm_fold(c, s.stream, make_grm_args(c, s));
+  HIP_TRY(c, hipEventRecord(ev[4], s.stream));
+  return finish_hook(c, ev, s.stream, ms);
+}
+
+// ---- scores
+
+int bvcf_score_weight(const char *text, size_t n, int64_t *out) { return score_weight(text, n, out); }
+int bvcf_score_limbs(int64_t w, int8_t out[8]) { return out ? score_limbs(w, out) : -1; }
+size_t bvcf_score_decimal(uint64_t lo, uint64_t hi, char out[48]) { return out ? score_decimal(lo, hi, out) : 0; }
+
+void bvcf_score_table_free(bvcf_score_table *t) {
+  if (!t) return;
+  free((void *)t->entries);
+  free((void *)t->blob);
+  free((void *)t->weights);
+  free((void *)t->names);
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_score_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, const int64_t *w, uint32_t k,
+                           const char *names, size_t names_bytes, bvcf_score_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (k < 1 || k > BVCF_SCORE_MAX_COLUMNS || (n && (!bytes || !off || !len || !w))) return BVCF_E_ARG;
+  if (n > BVCF_VARIANT_MAX_ENTRIES) return BVCF_E_TOO_BIG;
+  uint64_t blob_bytes = 0;
+  uint32_t limbs = 1;
+  for (uint64_t i = 0; i < n; i++) {
+    if (!len[i]) return BVCF_E_ARG;  // (len == 0 marks an empty slot)
+    blob_bytes += len[i];
+    if (blob_bytes >= (1ull << 32)) return BVCF_E_TOO_BIG;
+    for (uint32_t c = 0; c < k; c++) {
+      const int64_t v = w[i * k + c];
+      if (v > BVCF_SCORE_MAX_W || v < -BVCF_SCORE_MAX_W) return BVCF_E_ARG;
+      int8_t l[BVCF_SCORE_MAX_LIMBS];
+      limbs = std::max(limbs, (uint32_t)score_limbs(v, l));
+    }
+  }
+  const uint64_t cols = (uint64_t)k * limbs + 1;
+  if (n * cols > BVCF_SCORE_MAX_WEIGHT_BYTES) return BVCF_E_TOO_BIG;
+  const uint64_t cap = variant_capacity(n);
+  VariantEntry *entries = (VariantEntry *)calloc((size_t)cap, sizeof(VariantEntry));
+  uint8_t *blob = (uint8_t *)malloc((size_t)blob_bytes + 1);
+  int8_t *weights = (int8_t *)calloc((size_t)(n * cols) + 1, 1);
+  char *nm = (char *)malloc(names_bytes + 1);
+  if (!entries || !blob || !weights || !nm) {
+    free(entries);
+    free(blob);
+    free(weights);
+    free(nm);
+    return BVCF_E_NOMEM;
+  }
+  if (names_bytes) memcpy(nm, names, names_bytes);
+  const uint32_t mask = (uint32_t)(cap - 1);
+  uint64_t at = 0;
+  int rc = BVCF_OK;
+  for (uint64_t i = 0; i < n && rc == BVCF_OK; i++) {
+    const uint8_t *s = (const uint8_t *)bytes + off[i];
+    const unsigned long long h = fnv1a(s, len[i]);
+    // (a locus is an entry once: the probe the device runs finds an earlier one)
+    if (score_find(entries, blob, mask, h, len[i], [&](LocusComparer &cmp) {
+          for (uint32_t q = 0; q < len[i]; q++)
+            if (!cmp(s[q])) return false;
+          return true;
+        }) != kScoreNoEntry) {
+      rc = BVCF_E_ARG;
+      break;
+    }
+    uint32_t slot = (uint32_t)h & mask;
+    while (entries[slot].len) slot = (slot + 1u) & mask;
+    entries[slot] = VariantEntry{(uint32_t)(h >> 32), (uint32_t)at, len[i], (uint32_t)i};
+    memcpy(blob + at, s, len[i]);
+    at += len[i];
+    int8_t *row = weights + i * cols;
+    for (uint32_t c = 0; c < k; c++) {
+      int8_t l[BVCF_SCORE_MAX_LIMBS];
+      score_limbs(w[i * k + c], l);
+      memcpy(row + (size_t)c * limbs, l, limbs);
+    }
+    row[cols - 1] = 1;
+  }
+  if (rc) {
+    free(entries);
+    free(blob);
+    free(weights);
+    free(nm);
+    return rc;
+  }
+  out->entries = (const uint32_t *)entries;
+  out->capacity = cap;
+  out->blob = (const char *)blob;
+  out->blob_bytes = blob_bytes;
+  out->n = n;
+  out->weights = weights;
+  out->n_columns = k;
+  out->n_limbs = limbs;
+  out->names = nm;
+  out->names_bytes = names_bytes;
+  return BVCF_OK;
+}
+
+// the file's rules (bvcf_config_score.score_path); every refusal names its line in err
+int bvcf_score_table_parse(const char *text, size_t n, bvcf_score_table *out, char *err, size_t err_cap) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  std::string msg;
+  const auto fail = [&](uint64_t line, const std::string &what, int rc) {
+    msg = line ? "line " + std::to_string(line) + ": " + what : what;
+    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
+    return rc;
+  };
+  if (n && !text) return BVCF_E_ARG;
+  std::vector<uint64_t> off;
+  std::vector<uint32_t> len;
+  std::vector<int64_t> w;
+  std::string names;
+  std::unordered_map<std::string_view, uint64_t> seen;
+  uint32_t k = 0;
+  uint64_t line_no = 0;
+  bool first = true;
+  std::vector<std::string_view> f;
+  for (size_t at = 0; at < n;) {
+    const char *nl = (const char *)memchr(text + at, '\n', n - at);
+    size_t end = nl ? (size_t)(nl - text) : n;
+    const size_t next = nl ? end + 1 : n;
+    line_no++;
+    if (end > at && text[end - 1] == '\r') end--;
+    const std::string_view line(text + at, end - at);
+    at = next;
+    if (line.empty()) continue;
+    f.clear();
+    for (size_t p = 0;;) {
+      const size_t t = line.find('\t', p);
+      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
+      if (t == std::string_view::npos) break;
+      p = t + 1;
+    }
+    const bool header = line[0] == '#';
+    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
+    if (first) {
+      if (f.size() < 2 || f.size() - 1 > BVCF_SCORE_MAX_COLUMNS)
+        return fail(line_no, "want a locus and 1 to " + std::to_string(BVCF_SCORE_MAX_COLUMNS) + " columns, tab-separated", BVCF_E_ARG);
+      k = (uint32_t)(f.size() - 1);
+      first = false;
+      if (header) {
+        if (f[0] != "#locus") return fail(line_no, "a header starts with \"#locus\"", BVCF_E_ARG);
+        for (uint32_t c = 0; c < k; c++) {
+          if (f[1 + c].empty()) return fail(line_no, "an empty column name", BVCF_E_ARG);
+          for (uint32_t d = 0; d < c; d++)
+            if (f[1 + d] == f[1 + c]) return fail(line_no, "the column name " + std::string(f[1 + c]) + " twice", BVCF_E_ARG);
+          names.append(f[1 + c]);
+          names.push_back('\0');
+        }
+        continue;
+      }
+      for (uint32_t c = 0; c < k; c++) {
+        names.append("SCORE" + std::to_string(c + 1));
+        names.push_back('\0');
+      }
+    }
+    if (f.size() != (size_t)k + 1)
+      return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(k + 1), BVCF_E_ARG);
+    if (f[0].empty()) return fail(line_no, "an empty locus", BVCF_E_ARG);
+    if (f[0].size() >= (1ull << 32)) return fail(line_no, "a locus of 4 GiB", BVCF_E_TOO_BIG);
+    const auto ins = seen.emplace(f[0], line_no);
+    if (!ins.second)
+      return fail(line_no, "the locus " + std::string(f[0]) + " is on line " + std::to_string(ins.first->second) + " already", BVCF_E_ARG);
+    for (uint32_t c = 0; c < k; c++) {
+      int64_t v = 0;
+      const int rc = score_weight(f[1 + c].data(), f[1 + c].size(), &v);
+      if (rc == -2) return fail(line_no, "the weight " + std::string(f[1 + c]) + " is above 10^6 in size", BVCF_E_ARG);
+      if (rc) return fail(line_no, "bad weight \"" + std::string(f[1 + c].substr(0, 80)) + "\"", BVCF_E_ARG);
+      w.push_back(v);
+    }
+    off.push_back((uint64_t)(f[0].data() - text));
+    len.push_back((uint32_t)f[0].size());
+    if (off.size() > BVCF_VARIANT_MAX_ENTRIES) return fail(line_no, "more than 2^27 entries", BVCF_E_TOO_BIG);
+  }
+  if (first) return fail(0, "no line", BVCF_E_ARG);
+  const int rc = bvcf_score_table_build(text, off.data(), len.data(), off.size(), w.data(), k, names.data(), names.size(), out);
+  if (rc == BVCF_E_TOO_BIG) return fail(0, "the weight table passes 2 GiB, or the loci 4 GiB", rc);
+  if (rc) return fail(0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
+  return BVCF_OK;
+}
+
+// every entry lies in the blob and names a weight row, the capacity is a power of two with an empty slot
+static bool score_table_sound(const bvcf_score_table *t) {
+  if (!t || !t->entries || t->capacity < 16 || t->capacity > (1ull << 31) || (t->capacity & (t->capacity - 1)) ||
+      t->blob_bytes >= (1ull << 32) || (t->blob_bytes && !t->blob) || t->n_columns < 1 || t->n_columns > BVCF_SCORE_MAX_COLUMNS ||
+      t->n_limbs < 1 || t->n_limbs > BVCF_SCORE_MAX_LIMBS || (t->n && !t->weights) ||
+      t->n * ((uint64_t)t->n_columns * t->n_limbs + 1) > BVCF_SCORE_MAX_WEIGHT_BYTES)
+    return false;
+  const VariantEntry *e = (const VariantEntry *)t->entries;
+  uint64_t used = 0;
+  for (uint64_t i = 0; i < t->capacity; i++) {
+    if (!e[i].len) continue;
+    used++;
+    if ((uint64_t)e[i].off + e[i].len > t->blob_bytes || e[i].zero >= t->n) return false;
+  }
+  return used == t->n && 2 * used <= t->capacity;
+}
+
+int64_t bvcf_score_table_find(const bvcf_score_table *t, const char *s, size_t n) {
+  if (!t || !t->entries || !t->capacity || (t->capacity & (t->capacity - 1)) || (!s && n) || n > 0xFFFFFFFFull) return -2;
+  const uint32_t e = score_find((const VariantEntry *)t->entries, (const uint8_t *)t->blob, (uint32_t)(t->capacity - 1),
+                                fnv1a((const uint8_t *)s, n), (uint32_t)n, [&](LocusComparer &cmp) {
+                                  for (size_t i = 0; i < n; i++)
+                                    if (!cmp((uint8_t)s[i])) return false;
+                                  return true;
+                                });
+  return e == kScoreNoEntry ? -1 : (int64_t)e;
+}
+
+static size_t score_words(const bvcf_ctx *c) { return 2 * (size_t)c->n_samples * c->score.K + 2 * (size_t)c->n_samples + 1; }
+
+int bvcf_set_score_table(bvcf_ctx *c, const bvcf_score_table *t) {
+  if (!c) return BVCF_E_ARG;
+  if (!score_table_sound(t)) {
+    c->err = "bvcf_set_score_table: want a table as bvcf_score_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_score_table")) return rc;
+  if (c->score.asked) {
+    c->err = "bvcf_set_score_table: the ctx has a score table";
+    return BVCF_E_ARG;
+  }
+  const uint64_t K = t->n_columns, L = t->n_limbs, cols = K * L + 1, ns = c->n_samples;
+  // a slot's tables: the limb columns with G and X, and the short lists' two halves
+  const uint64_t slot_bytes = 8ull * ns * (cols + 1 + 2 * K);
+  if (slot_bytes > (1ull << 30)) {
+    c->err = "bvcf_set_score_table: " + std::to_string(ns) + " samples x " + std::to_string(K) + " columns of " + std::to_string(L) +
+             " limbs: a slot's tables would take " + std::to_string(slot_bytes) + " bytes, more than 1 GiB";
+    return BVCF_E_TOO_BIG;
+  }
+  c->score.asked = true;
+  c->score.K = (uint32_t)K;
+  c->score.L = (uint32_t)L;
+  if (!ns) return BVCF_OK;  // (no sample columns: an empty table)
+  HIP_TRY(c, hipSetDevice(c->device));
+  const uint32_t wstride = (uint32_t)((cols + 15) & ~15ull);
+  HIP_TRY(c, c->score.entries.alloc((size_t)t->capacity));
+  HIP_TRY(c, c->score.blob.alloc((size_t)t->blob_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, c->score.weights.alloc((size_t)t->n * wstride + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->score.entries, t->entries, (size_t)t->capacity * sizeof(VariantEntry), hipMemcpyHostToDevice));
+  if (t->blob_bytes) HIP_TRY(c, hipMemcpy(c->score.blob, t->blob, (size_t)t->blob_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemset(c->score.weights, 0, (size_t)t->n * wstride + BVCF_DEVICE_PAD));
+  if (t->n) HIP_TRY(c, hipMemcpy2D(c->score.weights, wstride, t->weights, (size_t)cols, (size_t)cols, (size_t)t->n, hipMemcpyHostToDevice));
+  c->score.mask = (uint32_t)(t->capacity - 1);
+  c->score.n_entries = (uint32_t)t->n;
+  c->score.wstride = wstride;
+  HIP_TRY(c, c->score.tot.alloc(score_words(c)));
+  HIP_TRY(c, hipMemset(c->score.tot, 0, score_words(c) * sizeof(unsigned long long)));
+  HIP_TRY(c, c->score.ev_fold.create(hipEventDisableTiming));
+  c->score.on = true;
+  for (auto &s : c->slots) {
+    HIP_TRY(c, s.score.ctr.alloc(3));
+    HIP_TRY(c, s.score.bt.alloc((size_t)ns * (cols + 1)));
+    HIP_TRY(c, s.score.slo.alloc((size_t)ns * K));
+    HIP_TRY(c, s.score.shi.alloc((size_t)ns * K));
+    HIP_TRY(c, hipMemset(s.score.ctr, 0, 3 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemset(s.score.bt, 0, (size_t)ns * (cols + 1) * sizeof(long long)));
+    HIP_TRY(c, hipMemset(s.score.slo, 0, (size_t)ns * K * sizeof(unsigned long long)));
+    HIP_TRY(c, hipMemset(s.score.shi, 0, (size_t)ns * K * sizeof(long long)));
+    if (const int rc = alloc_score_lists(c, s)) {
+      c->score.on = false;
+      return rc;
+    }
+  }
+  return BVCF_OK;
+}
+
+int bvcf_score(bvcf_ctx *c, uint64_t *out, int reset) {
+  if (!c) return BVCF_E_ARG;
+  if (!c->score.asked) {
+    c->err = "bvcf_score: bvcf_set_score_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (!c->score.on) {  // (no sample columns: no sample's words, no rows)
+    if (out) out[0] = 0;
+    return BVCF_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  for (auto &s : c->slots) HIP_TRY(c, hipStreamSynchronize(s.stream));  // (the folds of the batches collected so far)
+  const size_t bytes = score_words(c) * sizeof(unsigned long long);
+  hipStream_t st = c->slots[0].stream;
+  if (out) HIP_TRY(c, hipMemcpyAsync(out, c->score.tot, bytes, hipMemcpyDeviceToHost, st));
+  if (reset) HIP_TRY(c, hipMemsetAsync(c->score.tot, 0, bytes, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  return BVCF_OK;
+}
+
+// (the last interval is k_score_fold, which the product runs at collect -- launch_folds --: the hook's own step; the totals
+// take the block once more, as bvcf_bench_grm_kernels' do)
+int bvcf_bench_score_kernels(bvcf_ctx *c, float ms[4]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[5];
+  if (const int rc = start_hook(c, "bvcf_bench_score_kernels", c->score.on && s.score.dense && s.score.bt && c->bench_src,
+                                "the ctx has no score tables, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  // (k_score_list walks the rows' loci: the block of the last bench call, which is still on the device)
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  launch_score(c, a, s.stream, &s, ev);  // (ev[0] behind the memsets, ev[1] behind k_score_list, ev[2] behind the product)
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  launch_score_fold(c, s.stream, make_score_args(c, s));
   HIP_TRY(c, hipEventRecord(ev[4], s.stream));
   return finish_hook(c, ev, s.stream, ms);
 }

@@ -120,6 +120,7 @@ struct Slot {
   SampleStatsSlot ss;
   PairStatsSlot pr;
   GrmSlot grm;
+  ScoreSlot score;
   SiteGateSlot gate;
   RowIndexSlot idx;
   BedSlot bed;
@@ -170,6 +171,7 @@ struct bvcf_ctx : bvcf_ctx_plan {
   // the analyses behind k_finish (bvcf_analyses.hip.h)
   PairStatsCtx pr;
   GrmCtx grm;
+  ScoreCtx score;
   SiteGateCtx gate;
   VariantGateCtx variants;
   RegionGateCtx regions;

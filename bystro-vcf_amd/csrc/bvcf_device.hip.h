@@ -57,6 +57,11 @@
 //   (bvcf_enable_grm, behind them: k_grm_list lists the polymorphic rows with their quantised standard scores, k_grm_pack /
 //    k_grm_gemm multiply the dense rows' int8 limbs on the matrix cores, k_grm_sparse adds the short lists' pairs -- the exact
 //    integer tables behind --grm, bvcf_grm.hip.h; k_grm_fold adds a collected batch's tables to the ctx's 128-bit totals)
+//   (bvcf_set_score_table, behind them: k_score_list finds every row's locus in the hash set of --score and lists the matched
+//    rows with their entry, k_score_gemm multiplies the dense rows' dosages with the entries' int8 weight limbs on the matrix
+//    cores -- classes expanded in registers, the tile's weights staged in LDS --, k_score_sparse adds the short lists with
+//    integer atomics -- the exact fixed-point sums behind --score, bvcf_score.hip.h; k_score_fold recombines a collected
+//    batch's limbs into the ctx's 128-bit totals)
 //   (bvcf_set_region_table, right behind k_finish and in front of the variant gate: k_region_gate finds every row's
 //    chromosome in the hash set of --regions / --excludeRegions, binary-searches the row's span in the chromosome's merged
 //    intervals and takes the unselected rows out -- bvcf_regions.hip.h)
@@ -124,6 +129,7 @@
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_grm.hip.h"
+#include "bvcf_score.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
 #include "bvcf_ld.hip.h"

@@ -428,10 +428,25 @@ void Driver::device_main(DevWorker *W) {
         }
         add_grm_table(W->grm_carry, t.data(), ns);
       }
+      // (--score: the same for the scores' words)
+      const bool score = R_.score_on && R_.pre.header.size() > 9;
+      if (score) {
+        const size_t ns = R_.pre.header.size() - 9, k = R_.score_table.n_columns;
+        std::vector<uint64_t> t(score_table_words(ns, k), 0);
+        if (bvcf_score(W->ctx, t.data(), 1) != BVCF_OK) {
+          fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          return;
+        }
+        add_score_words(W->score_carry, t.data(), ns, k);
+      }
       for (size_t k = 1; k < in_flight.size(); k++) {
         bvcf_result tmp;
         bvcf_collect(W->ctx, &tmp);
         n_collects++;
+      }
+      if (score && bvcf_score(W->ctx, nullptr, 1) != BVCF_OK) {
+        fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+        return;
       }
       if (grm && bvcf_grm(W->ctx, nullptr, 1) != BVCF_OK) {
         fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
@@ -662,6 +677,10 @@ int Driver::run(uint64_t *n_lines_in) {
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
+    if (const int rc = open_score(R_, &msg)) {  // --score: the outputs opened, the score file read
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
   }
   sniff_input();
   // --compressOutput bgzf: one compressed stream for the header and the rows, on the run's first device
@@ -879,6 +898,24 @@ int Driver::run(uint64_t *n_lines_in) {
       }
       std::string msg;
       if (rc_ == BVCF_OK && write_grm(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+      if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
+    }
+    if (R_.score_fd >= 0 && rc_ == BVCF_OK) {
+      // --score: the workers' words added one after another into one host table (a failed run leaves the files empty)
+      const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0, k = R_.score_table.n_columns;
+      std::vector<uint64_t> sum(score_table_words(ns, k), 0), t;
+      for (auto &W : workers_) {
+        if (!W->ctx) continue;
+        t.assign(score_table_words(ns, k), 0);
+        if (bvcf_score(W->ctx, t.data(), 0) != BVCF_OK) {
+          fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+          break;
+        }
+        if (ns) add_score_words(sum, t.data(), ns, k);
+        if (!W->score_carry.empty()) add_score_words(sum, W->score_carry.data(), ns, k);
+      }
+      std::string msg;
+      if (rc_ == BVCF_OK && write_score(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
       if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
     }
     if (sg_fd_ >= 0) {

@@ -73,6 +73,12 @@ void bvcf_config_grm_defaults(bvcf_config_grm *c) {
   c->regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_GRM;
 }
 
+void bvcf_config_score_defaults(bvcf_config_score *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_grm_defaults(&c->grm);
+  c->grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_SCORE;
+}
+
 int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out) {
   if (!out || (!text && n)) return BVCF_E_ARG;
   std::vector<uint64_t> off;
@@ -169,6 +175,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_variants(R, &msg);
   if (rc == BVCF_OK) rc = open_regions(R, &msg);
   if (rc == BVCF_OK) rc = open_grm(R, &msg);
+  if (rc == BVCF_OK) rc = open_score(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -318,6 +325,17 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       l.append(std::string("bvcf_grm: ") + bvcf_last_error(R.ctx) + "\n");
       rc = BVCF_E_HIP;
     } else if (write_grm(R, t.data(), &msg)) {
+      l.append(msg + "\n");
+      rc = BVCF_E_IO;
+    }
+  }
+  if (R.score_fd >= 0 && rc == BVCF_OK) {  // --score: the run's scores, after a successful run only
+    const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+    std::vector<uint64_t> t(score_table_words(ns, R.score_table.n_columns), 0);
+    if (R.ctx && bvcf_score(R.ctx, t.data(), 0) != BVCF_OK) {
+      l.append(std::string("bvcf_score: ") + bvcf_last_error(R.ctx) + "\n");
+      rc = BVCF_E_HIP;
+    } else if (write_score(R, t.data(), &msg)) {
       l.append(msg + "\n");
       rc = BVCF_E_IO;
     }

@@ -858,6 +858,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.score_on) {  // --score: the run's table and the score tables of every ctx of the run
+    rc = bvcf_set_score_table(*ctx, &R.score_table);
+    if (rc) {
+      *msg = std::string("bvcf_set_score_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (rc == BVCF_OK && wants_plink(R.cfg)) {  // --plinkOutput: the .bed rows of every ctx of the run
     rc = bvcf_enable_bed_rows(*ctx);
     if (rc) {
@@ -1715,6 +1723,124 @@ int write_grm(Run &R, const uint64_t *sum, std::string *msg) {
   }
   if (bad) {
     *msg = std::string("grm: write failed: ") + strerror(saved);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_score(Run &R, std::string *msg) {
+  const bvcf_config_score *sc = score_config(R.cfg);
+  if (!sc) return BVCF_OK;
+  const char *sp = sc->score_path, *op = sc->score_output_path, *rp = sc->score_report_path;
+  const bool have_s = sp && *sp, have_o = op && *op, have_r = rp && *rp;
+  if (have_s != have_o) {
+    *msg = have_s ? "score_path without score_output_path" : "score_output_path without score_path";
+    return BVCF_E_ARG;
+  }
+  if (have_r && !have_s) {
+    *msg = "score_report_path without score_path";
+    return BVCF_E_ARG;
+  }
+  if (!have_s) return BVCF_OK;
+  for (const auto &f : {std::pair<int *, const char *>{&R.score_fd, op}, std::pair<int *, const char *>{&R.score_report_fd, have_r ? rp : nullptr}}) {
+    if (!f.second) continue;
+    *f.first = open(f.second, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.first < 0) {
+      *msg = std::string("open ") + f.second + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  std::string text;
+  {
+    FILE *f = fopen(sp, "rb");
+    if (!f) {
+      *msg = std::string("open ") + sp + ": " + strerror(errno);
+      return BVCF_E_FATAL;
+    }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const int err = ferror(f) ? errno : 0;
+    fclose(f);
+    if (err) {
+      *msg = std::string("read ") + sp + ": " + strerror(err);
+      return BVCF_E_FATAL;
+    }
+  }
+  char err[512] = "";
+  if (bvcf_score_table_parse(text.data(), text.size(), &R.score_table, err, sizeof err)) {
+    *msg = std::string("score: ") + sp + ": " + err;
+    return BVCF_E_FATAL;
+  }
+  R.score_on = true;
+  return BVCF_OK;
+}
+
+void add_score_words(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns, size_t k) {
+  const size_t n = ns * k;
+  sum.resize(score_table_words(ns, k), 0);
+  for (size_t q = 0; q < n; q++) score_add128w(&sum[q], &sum[n + q], t[q], t[n + q]);
+  for (size_t q = 2 * n; q < 2 * n + 2 * ns + 1; q++) sum[q] += t[q];
+}
+
+// name_SUM exactly from the 128-bit integer; name_AVG = the correctly rounded double of T over the correctly rounded double
+// of 10^12 * 2 * called, "%.6G"
+int write_score(Run &R, const uint64_t *sum, std::string *msg) {
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0, K = R.score_table.n_columns, n = ns * K;
+  const uint64_t *lo = sum, *hi = sum + n, *G = sum + 2 * n, *X = G + ns;
+  const uint64_t rows = ns ? sum[2 * n + 2 * ns] : 0;
+  const char *empty = or_default(R.cfg->empty_field, "!");
+  std::string o = "sample\tmatched\tcalled\tdosageSum";
+  for (const char *nm = R.score_table.names, *e = nm + R.score_table.names_bytes; nm < e; nm += strlen(nm) + 1) {
+    o.append("\t").append(nm).append("_SUM\t").append(nm).append("_AVG");
+  }
+  o.push_back('\n');
+  bool bad = false;
+  for (size_t i = 0; i < ns && !bad; i++) {
+    const uint64_t called = rows - X[i];
+    o.append(R.pre.header[9 + i]);
+    for (uint64_t v : {rows, called, G[i]}) {
+      o.push_back('\t');
+      append_ll(o, (long long)v);
+    }
+    for (size_t k = 0; k < K; k++) {
+      char buf[64];
+      o.push_back('\t');
+      o.append(buf, score_decimal(lo[i * K + k], hi[i * K + k], buf));
+      o.push_back('\t');
+      const __int128 t = (__int128)(((unsigned __int128)hi[i * K + k] << 64) | lo[i * K + k]);
+      if (!called) {
+        o.append(empty);
+      } else if (t == 0) {
+        o.push_back('0');
+      } else {
+        const double den = (double)((unsigned __int128)called * 2u * (unsigned __int128)BVCF_SCORE_ONE);
+        snprintf(buf, sizeof buf, "%.6G", (double)t / den);
+        o.append(buf);
+      }
+    }
+    o.push_back('\n');
+    if (o.size() >= (4u << 20)) {
+      bad = write_all(R.score_fd, o.data(), o.size()) != 0;
+      o.clear();
+    }
+  }
+  if (!bad) bad = write_all(R.score_fd, o.data(), o.size()) != 0;
+  if (!bad && R.score_report_fd >= 0) {
+    std::string r = "listed\t" + std::to_string(R.score_table.n) + "\ncolumns\t" + std::to_string(K) + "\nmatchedRows\t" +
+                    std::to_string(rows) + "\n";
+    bad = write_all(R.score_report_fd, r.data(), r.size()) != 0;
+  }
+  int saved = errno;
+  for (int *fd : {&R.score_fd, &R.score_report_fd}) {
+    if (*fd >= 0 && close(*fd) && !bad) {
+      bad = true;
+      saved = errno;
+    }
+    *fd = -1;
+  }
+  if (bad) {
+    *msg = std::string("score: write failed: ") + strerror(saved);
     return BVCF_E_IO;
   }
   return BVCF_OK;

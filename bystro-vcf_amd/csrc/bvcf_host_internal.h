@@ -9,6 +9,7 @@
 #include "bvcf_input.h"
 #include "bvcf_bgzf.h"
 #include "bvcf_grm_q.h"
+#include "bvcf_score_q.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -265,11 +266,18 @@ struct Run {
   // --grm: PREFIX.grm.bin / .grm.N.bin / .grm.id, opened by open_grm before any device work; write_grm writes all three from
   // the sum of the run's bvcf_grm tables at the end of a successful run and closes them
   int grm_fd = -1, grm_n_fd = -1, grm_id_fd = -1;
+  // --score / --scoreOutput / --scoreReport: open_score opens the outputs and reads the score file into the run's one table
+  // before any device work; create_ctx uploads it to every ctx; write_score writes the table (and the report) from the sum of
+  // the run's bvcf_score words at the end of a successful run and closes them
+  bool score_on = false;
+  bvcf_score_table score_table{};
+  int score_fd = -1, score_report_fd = -1;
   ~Run() {
     for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
-                   grm_n_fd, grm_id_fd})
+                   grm_n_fd, grm_id_fd, score_fd, score_report_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
+    bvcf_score_table_free(&score_table);
     bvcf_variant_table_free(&variant_table);
     bvcf_region_table_free(&region_table);
   }
@@ -412,6 +420,19 @@ void add_grm_table(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns);
 int write_grm(Run &R, const uint64_t *sum, std::string *msg);
 // the words of a bvcf_grm table over ns samples
 inline size_t grm_table_words(size_t ns) { return 3 * ns * ns + 1; }
+// --score: the bvcf_config_score of a config that reaches up to it (the ninth marker); NULL otherwise
+inline const bvcf_config_score *score_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_SCORE) ? reinterpret_cast<const bvcf_config_score *>(c)
+                                                                                           : nullptr;
+}
+// the outputs opened (truncated) and the score file read into R.score_table -- BVCF_E_ARG for a path without its partner,
+// BVCF_E_IO for an output, BVCF_E_FATAL for the score file, each with one message in *msg; one ctx's bvcf_score words t added into
+// `sum` (T in 128 bits); the table and the report written from the run's sum and the files closed
+int open_score(Run &R, std::string *msg);
+void add_score_words(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns, size_t k);
+int write_score(Run &R, const uint64_t *sum, std::string *msg);
+// the words of a bvcf_score table over ns samples and k columns
+inline size_t score_table_words(size_t ns, size_t k) { return 2 * ns * k + 2 * ns + 1; }
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

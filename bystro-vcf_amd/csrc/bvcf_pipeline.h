@@ -214,6 +214,7 @@ struct DevWorker {
   // batches in flight are collected, dropped and submitted again)
   std::vector<uint64_t> ss_carry;
   std::vector<uint64_t> pr_carry;  // --relatedness: the same for the pair tables
+  std::vector<uint64_t> score_carry;  // --score: the same for the scores' words (added with add_score_words: T is 128 bits)
   std::vector<uint64_t> grm_carry;  // --grm: the same for the GRM's tables (added with add_grm_table: T is 128 bits)
   uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};  // --siteFilterReport: bvcf_site_gate_count over the batches handed to the formatter
   uint64_t variant_counts[3] = {0, 0, 0};           // --variantFilterReport: bvcf_variant_gate_count over the same batches

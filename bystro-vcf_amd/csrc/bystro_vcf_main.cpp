@@ -66,6 +66,9 @@ struct Cli {
   // extension: --grm PREFIX, the genomic relationship matrix of the run's rows in GCTA's binary format, PREFIX.grm.bin /
   // .grm.N.bin / .grm.id (exact integer tables, multiplied on the device's matrix cores)
   std::string grm;
+  // extension: --score FILE --scoreOutput PATH [--scoreReport PATH], per-sample scores of the run's rows from a table of
+  // locus weights -- a polygenic score, PC loadings -- in exact fixed point (the dense rows on the device's matrix cores)
+  std::string score, score_output, score_report;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -163,7 +166,7 @@ int parse(int argc, char **argv, Cli &c) {
         name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
         name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
-        name == "grm") {
+        name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -189,6 +192,12 @@ int parse(int argc, char **argv, Cli &c) {
         c.plink = val;
       } else if (name == "grm") {
         c.grm = val;
+      } else if (name == "score" || name == "scoreOutput" || name == "scoreReport") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to %s\n", name.c_str(), name == "score" ? "read" : "write");
+          return 2;
+        }
+        (name == "score" ? c.score : name == "scoreOutput" ? c.score_output : c.score_report) = val;
       } else if (name == "mendel" || name == "mendelErrors") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to write\n", name.c_str());
@@ -278,6 +287,14 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-keepVariants and -excludeVariants cannot both be given\n");
     return 2;
   }
+  if (c.score.empty() != c.score_output.empty()) {
+    fprintf(stderr, "-score and -scoreOutput come together\n");
+    return 2;
+  }
+  if (!c.score_report.empty() && c.score.empty()) {
+    fprintf(stderr, "-scoreReport needs -score and -scoreOutput\n");
+    return 2;
+  }
   if ((!c.mendel.empty() || !c.mendel_errors.empty()) && c.fam.empty()) {
     fprintf(stderr, "-mendel and -mendelErrors need the pedigree: -fam PATH\n");
     return 2;
@@ -313,10 +330,10 @@ int main(int argc, char **argv) {
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
   // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so are --variantFilterReport and
-  // --regionFilterReport alone; --grm alone: a GRM-only pass)
+  // --regionFilterReport alone; --grm alone: a GRM-only pass; --score with --scoreOutput alone: a scoring-only pass)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
       c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
-      c.variant_report.empty() && c.region_report.empty() && c.grm.empty()) {
+      c.variant_report.empty() && c.region_report.empty() && c.grm.empty() && c.score.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -331,9 +348,10 @@ int main(int argc, char **argv) {
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
-  // regions and their report; behind those the --grm prefix)
-  bvcf_config_grm grm_cfg;
-  bvcf_config_grm_defaults(&grm_cfg);
+  // regions and their report; behind those the --grm prefix; behind that the --score paths)
+  bvcf_config_score score_cfg;
+  bvcf_config_score_defaults(&score_cfg);
+  bvcf_config_grm &grm_cfg = score_cfg.grm;
   bvcf_config_regions &rc_cfg = grm_cfg.regions;
   bvcf_config_variants &vc = rc_cfg.variants;
   bvcf_config_ld &ldc = vc.ld;
@@ -412,6 +430,9 @@ int main(int argc, char **argv) {
   rc_cfg.exclude_regions_path = c.exclude_regions_file.c_str();
   rc_cfg.region_filter_path = c.region_report.c_str();
   grm_cfg.grm_prefix = c.grm.c_str();
+  score_cfg.score_path = c.score.c_str();
+  score_cfg.score_output_path = c.score_output.c_str();
+  score_cfg.score_report_path = c.score_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -443,6 +443,53 @@ int bvcf_pair_stats(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S: [t][i][j] */, int
  * ctx on which bvcf_enable_grm was not called. */
 int bvcf_enable_grm(bvcf_ctx *ctx);
 int bvcf_grm(bvcf_ctx *ctx, uint64_t *out /* 3 * S * S + 1 */, int reset);
+/* Per-sample scores over the same rows -- a polygenic score's weights, or PC loadings -- summed on the device from the class
+ * maps (which the ctx then makes even when want_class_maps is 0, without copying them to the host), in fixed point.
+ * The score table is a bvcf_variant_table of locus strings (the rules and the probe of bvcf_set_variant_table: a row is
+ * matched when the bytes of its TSV locus "chrom:pos:ref:alt" are an entry's) whose entries each stand once and carry, in
+ * their fourth word, the index of their row of weights: K = n_columns integers W_k, |W_k| <= 10^18, the weight in units of
+ * 10^-12.  weights[entry][K * n_limbs + 1] holds them as n_limbs (1 .. 8) balanced base-256 digits each, W = sum l_a 256^a
+ * with l_a in [-128, 127], least significant first -- n_limbs the smallest count that holds every W of the table -- and the
+ * constant 1 in the last column.  A sample's dosage g in a row is 0, 1 (het), 2 (hom; a haploid call counts as hom) or
+ * missing; the effect allele is the row's ALT.  Over the matched rows -- monomorphic ones included:
+ *   T(i,k) = sum W_k g_i (128 bits; a missing call adds nothing)   G(i) = sum g_i   X(i) = sum M_i, M = 1 for a missing call
+ *   R = their number
+ * A matched row whose record has no class map (cmap_off == BVCF_NO_CMAP) counts as bvcf_bed_rows packs it: every sample
+ * missing -- it is in R and in every X.  The dense rows are multiplied on the matrix cores (int8 limbs, int32 sums), the
+ * short lists added with integer atomics: the words are a property of the data.
+ * bvcf_score_table_build: n loci bytes[off[i], off[i] + len[i]) with weights w[i * k + c]; names = k NUL-terminated column
+ * names back to back (kept for the caller, may be NULL with names_bytes 0).  BVCF_E_ARG for an empty locus, a locus given
+ * twice, k outside 1 .. 64 or |W| > 10^18; BVCF_E_TOO_BIG over BVCF_VARIANT_MAX_ENTRIES entries, 4 GiB of loci or
+ * BVCF_SCORE_MAX_WEIGHT_BYTES of weights.  bvcf_score_table_parse: the table of a score file's text by the file's rules
+ * (bvcf_config_score.score_path); a refusal leaves one message that names the line in err.  bvcf_score_table_find: the
+ * entry's weight row by the probe the device runs, -1 when the string is no entry (-2 for bad arguments).
+ * bvcf_set_score_table uploads a built table to a ctx (one table serves every ctx of a run) and allocates the tables:
+ * about 8 S (K L + 2 + 2 K) bytes per slot -- BVCF_E_TOO_BIG with a message, before anything is allocated, when that passes
+ * 1 GiB.  Call once, before the first submit; BVCF_E_BUSY with batches in flight; on a ctx without sample columns nothing is
+ * allocated or launched.  bvcf_params and the ABI version do not change with it.
+ * bvcf_score: out[0 .. S*K) the low and out[S*K .. 2*S*K) the high 64 bits of T(i,k) in two's complement, at i * K + k;
+ * out[2*S*K .. + S) G; the next S words X; the last word R -- over the batches collected so far.  The contract of bvcf_grm:
+ * a batch counts once it is collected with BVCF_OK, one that came back BVCF_E_CAPACITY does not; waits for the ctx's slots;
+ * reset: zero the totals after reading them (out may then be NULL).  A ctx without sample columns writes out[0] = 0 alone. */
+#define BVCF_SCORE_MAX_WEIGHT_BYTES (1ull << 31)
+typedef struct {
+  const uint32_t *entries; /* [4 * capacity]: {tag, off, len, weight row} */
+  uint64_t capacity;
+  const char *blob;
+  uint64_t blob_bytes;
+  uint64_t n;              /* entries */
+  const int8_t *weights;   /* [n][n_columns * n_limbs + 1] */
+  uint32_t n_columns, n_limbs;
+  const char *names;       /* n_columns NUL-terminated names */
+  uint64_t names_bytes;
+} bvcf_score_table;
+int bvcf_score_table_build(const char *bytes, const uint64_t *off, const uint32_t *len, uint64_t n, const int64_t *w, uint32_t k,
+                           const char *names, size_t names_bytes, bvcf_score_table *out);
+int bvcf_score_table_parse(const char *text, size_t n, bvcf_score_table *out, char *err, size_t err_cap);
+void bvcf_score_table_free(bvcf_score_table *t);
+int64_t bvcf_score_table_find(const bvcf_score_table *t, const char *s, size_t n);
+int bvcf_set_score_table(bvcf_ctx *ctx, const bvcf_score_table *t);
+int bvcf_score(bvcf_ctx *ctx, uint64_t *out /* 2 * S * K + 2 * S + 1 */, int reset);
 /* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
  * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
  * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
@@ -957,6 +1004,36 @@ typedef struct {
 } bvcf_config_grm;
 /* the whole struct: bvcf_config_regions_defaults, base.reserved[1] = BVCF_CONFIG_MORE_GRM, no matrix */
 void bvcf_config_grm_defaults(bvcf_config_grm *c);
+/* Likewise what came after bvcf_config_grm: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_SCORE.  bvcf_config_score_defaults sets that; the eight older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_SCORE 8
+typedef struct {
+  bvcf_config_grm grm;
+  /* --score FILE with --scoreOutput PATH: per-sample scores of the run's rows from the bvcf_score words of the run's ctxs.
+   * The score file: lines end in '\n', a trailing '\r' is dropped, empty lines are ignored.  The first non-empty line may be
+   * a header "#locus \t name1 \t ... \t nameK" (names non-empty and distinct; without one the names are SCORE1 .. SCOREK);
+   * every other line is "locus \t w1 \t ... \t wK" with the K of the first non-empty line, 1 <= K <= 64.  locus is taken
+   * whole and compared byte for byte with a row's TSV locus "chrom:pos:ref:alt" as keep_variants_path's entries are; a locus
+   * stands on one line.  A weight is at most 64 bytes of [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D{1,3})?; its value is the rational
+   * the text denotes, W the integer nearest to w 10^12 (ties away from zero, decided on the digits), |W| <= 10^18.  A '#'
+   * line behind the first, a wrong field count, an empty locus, a locus on two lines, a bad weight, an unreadable file, no
+   * non-empty line, more than 2^27 entries or 2 GiB of weights: BVCF_E_ARG / BVCF_E_IO / BVCF_E_TOO_BIG with one message that
+   * names the line, before any device work.  A header alone is valid: nothing matches.
+   * score_output_path: "sample matched called dosageSum" and per column "name_SUM name_AVG", tab-separated, then a line per
+   * (kept) sample in header order: R, R - X(i), G(i); name_SUM = T(i,k) / 10^12 printed exactly from the 128-bit integer ("-"?,
+   * the integer part, "." and the 12 fraction digits less trailing zeros when any remain; zero is "0"); name_AVG = the
+   * correctly rounded double of T(i,k) over the double 10^12 * 2 * called(i), "%.6G" ("0" for T = 0, empty_field when no row is
+   * called).  A file without sample columns gives the header line alone.
+   * score_report_path (only with the other two): "listed", "columns", "matchedRows", each "name \t count \n".
+   * The outputs are opened before any device work and written at the end of a successful run.  The rows are the rows
+   * sample_stats_path counts; the bytes do not depend on devices, batch size or input kind, and no other output changes
+   * with them.  score_path and score_output_path come together (BVCF_E_ARG otherwise).  NULL or "" = off */
+  const char *score_path;
+  const char *score_output_path;
+  const char *score_report_path;
+} bvcf_config_score;
+/* the whole struct: bvcf_config_grm_defaults, base.reserved[1] = BVCF_CONFIG_MORE_SCORE, no scores */
+void bvcf_config_score_defaults(bvcf_config_score *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

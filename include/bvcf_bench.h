@@ -46,6 +46,12 @@ int bvcf_bench_pair_kernels(bvcf_ctx *ctx, float ms[4]);
  * BVCF_E_ARG on a ctx without GRM tables */
 int bvcf_bench_grm_kernels(bvcf_ctx *ctx, float ms[4]);
 
+/* bvcf_set_score_table: the score kernels once more over what the last bvcf_bench_device* chain of the ctx's first slot left
+ * (its block, records and class maps), with HIP events around each step: ms = {k_score_list, k_score_gemm, k_score_sparse,
+ * k_score_fold}.  The fold adds the batch to the ctx's totals like a collect would: for a ctx that only measures.
+ * BVCF_E_ARG on a ctx without score tables or without a bench call before */
+int bvcf_bench_score_kernels(bvcf_ctx *ctx, float ms[4]);
+
 /* The exact Hardy-Weinberg test as the site gate runs it on the device: triples = n x {het, hom, other}, p[j] the p value of
  * triple j -- by the thread-per-row recurrence or by a wave (k_site_hwe's code), chosen by the length of the support as
  * k_site_gate chooses.  Needs no ctx */

@@ -187,6 +187,16 @@ uint64_t bvcf_ld_seam_rows(const bvcf_ld_seam *s);
 uint64_t bvcf_ld_seam_pairs(const bvcf_ld_seam *s);
 void bvcf_ld_seam_destroy(bvcf_ld_seam *s);
 
+/* The fixed-point arithmetic behind bvcf_set_score_table -- csrc/bvcf_score_q.h -- run on the host: the functions the
+ * table builder, the kernels and the writer share.  bvcf_score_weight: text[0, n) by the weight grammar of
+ * bvcf_config_score -> *out = W, the integer nearest to w 10^12, ties away from zero; 0, -1 for text that is no weight, -2 for
+ * |W| > 10^18.  bvcf_score_limbs: W as eight balanced base-256 digits (W = sum out[a] 256^a, out[a] in [-128, 127]);
+ * returns the smallest count that holds W (1 for 0).  bvcf_score_decimal: the 128-bit two's complement integer (hi, lo)
+ * over 10^12 as exact decimal text (at most 48 bytes, no NUL) -> the length. */
+int bvcf_score_weight(const char *text, size_t n, int64_t *out);
+int bvcf_score_limbs(int64_t w, int8_t out[8]);
+size_t bvcf_score_decimal(uint64_t lo, uint64_t hi, char out[48]);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
