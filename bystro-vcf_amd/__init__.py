@@ -47,7 +47,7 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_assoc_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
@@ -60,7 +60,8 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
                 "bvcf_trio_verdict", "bvcf_parse_fam",
                 "bvcf_ld_counts", "bvcf_ld_in_ld", "bvcf_parse_ld_r2", "bvcf_ld_seam_create", "bvcf_ld_seam_push",
                 "bvcf_ld_seam_read", "bvcf_ld_seam_rows", "bvcf_ld_seam_pairs", "bvcf_ld_seam_destroy",
-                "bvcf_score_weight", "bvcf_score_limbs", "bvcf_score_decimal"]
+                "bvcf_score_weight", "bvcf_score_limbs", "bvcf_score_decimal",
+                "bvcf_assoc_value", "bvcf_assoc_limbs", "bvcf_assoc_ints"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -81,6 +82,8 @@ EXPORTS = [
     "bvcf_enable_grm", "bvcf_grm", "bvcf_config_grm_defaults",
     "bvcf_score_table_build", "bvcf_score_table_parse", "bvcf_score_table_free", "bvcf_score_table_find", "bvcf_set_score_table",
     "bvcf_score", "bvcf_config_score_defaults",
+    "bvcf_pheno_table_build", "bvcf_pheno_table_parse", "bvcf_pheno_table_free", "bvcf_set_pheno_table",
+    "bvcf_reserve_assoc_rows", "bvcf_assoc", "bvcf_assoc_stat", "bvcf_config_assoc_defaults",
 ]
 
 
@@ -441,6 +444,165 @@ class ScoreTable:
             pass
 
 
+CONFIG_MORE_ASSOC = 9  # BVCF_CONFIG_MORE_ASSOC in Config.reserved[1]: the ConfigScore is the head of a ConfigAssoc
+ASSOC_ONE = 10 ** 6  # a phenotype's integer Y is in units of 10^-6
+ASSOC_MAX_Y = 10 ** 12
+ASSOC_MAX_COLUMNS = 16
+ASSOC_COLUMNS = ["chrom", "pos", "ref", "alt", "pheno", "n", "altFreq", "beta", "se", "chisq", "p"]
+ASSOC_REC_DTYPE = np.dtype([("n_het", "<u4"), ("n_hom", "<u4"), ("n_mis", "<u4"), ("pad", "<u4"), ("a_het", "<i8"), ("a_hom", "<i8"),
+                            ("a_mis", "<i8"), ("b_mis_lo", "<u8"), ("b_mis_hi", "<u8")])  # bvcf_assoc_rec
+PHENO_TOTALS_DTYPE = np.dtype([("np", "<u8"), ("ay", "<i8"), ("by_lo", "<u8"), ("by_hi", "<u8")])  # bvcf_pheno_totals
+
+
+class ConfigAssoc(C.Structure):
+    """bvcf_config_assoc: a bvcf_config_score and what came after it"""
+    _fields_ = [("score", ConfigScore), ("pheno_path", C.c_char_p), ("assoc_path", C.c_char_p), ("assoc_report_path", C.c_char_p)]
+
+
+class PhenoTableStruct(C.Structure):
+    """bvcf_pheno_table"""
+    _fields_ = [("n_columns", C.c_uint32), ("n_samples", C.c_uint32), ("s64", C.c_uint32), ("l1", C.c_uint32), ("l2", C.c_uint32),
+                ("n_cols", C.c_uint32), ("n_named", C.c_uint64), ("b", C.c_void_p), ("y", C.c_void_p), ("present", C.c_void_p),
+                ("totals", C.c_void_p), ("names", C.c_void_p), ("names_bytes", C.c_uint64)]
+
+
+class AssocInfo(C.Structure):
+    """bvcf_assoc_info"""
+    _fields_ = [("recs", C.c_void_p), ("n_rows", C.c_uint64), ("need_rows", C.c_uint64), ("n_columns", C.c_uint32)]
+
+
+class PhenoTable:
+    """a host phenotype table: bvcf_pheno_table_build over y / present (K lists of S integers Y and of S flags), or -- text=
+    with sample_names= -- bvcf_pheno_table_parse over the bytes of a phenotype file  (host code, no device)"""
+
+    def __init__(self, y=None, present=None, names=None, text=None, sample_names=None, n_named=0):
+        self.t = PhenoTableStruct()
+        if text is not None:
+            sn = [bytes(x) for x in (sample_names or [])]
+            ptrs = (C.c_char_p * max(len(sn), 1))(*sn)
+            lens = (C.c_uint32 * max(len(sn), 1))(*[len(x) for x in sn])
+            err = C.create_string_buffer(512)
+            lib.bvcf_pheno_table_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t]
+            rc = lib.bvcf_pheno_table_parse(bytes(text), len(text), ptrs, lens, len(sn), C.byref(self.t), err, len(err))
+            if rc:
+                raise BvcfError(rc, err.value.decode(errors="replace"))
+            return
+        yy = np.ascontiguousarray(np.array(y, dtype=np.int64))
+        k, s = yy.shape
+        pp = np.ascontiguousarray(np.array(present, dtype=np.uint8).reshape(k, s))
+        nm = b"".join(bytes(x) + b"\0" for x in (names or [b"PHENO%d" % (i + 1) for i in range(k)]))
+        lib.bvcf_pheno_table_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint64,
+                                               C.c_void_p]
+        rc = lib.bvcf_pheno_table_build(yy.ctypes.data if s else None, pp.ctypes.data if s else None, k, s, nm, len(nm), int(n_named),
+                                        C.byref(self.t))
+        if rc:
+            raise BvcfError(rc, "bvcf_pheno_table_build")
+
+    n_columns = property(lambda self: int(self.t.n_columns))
+    n_samples = property(lambda self: int(self.t.n_samples))
+    s64 = property(lambda self: int(self.t.s64))
+    l1 = property(lambda self: int(self.t.l1))
+    l2 = property(lambda self: int(self.t.l2))
+    n_cols = property(lambda self: int(self.t.n_cols))
+    n_named = property(lambda self: int(self.t.n_named))
+
+    @property
+    def names(self):
+        return C.string_at(self.t.names, self.t.names_bytes).split(b"\0")[:-1] if self.t.names_bytes else []
+
+    @property
+    def b(self):
+        """operand B, int8 [n_cols][s64] (copied)"""
+        n = self.n_cols * self.s64
+        return (np.frombuffer(C.string_at(self.t.b, n), dtype=np.int8).reshape(self.n_cols, self.s64).copy() if n else
+                np.zeros((self.n_cols, 0), dtype=np.int8))
+
+    @property
+    def y(self):
+        n = self.n_columns * self.n_samples
+        return (np.frombuffer(C.string_at(self.t.y, 8 * n), dtype=np.int64).reshape(self.n_columns, self.n_samples).copy() if n else
+                np.zeros((self.n_columns, 0), dtype=np.int64))
+
+    @property
+    def present(self):
+        n = self.n_columns * self.n_samples
+        return (np.frombuffer(C.string_at(self.t.present, n), dtype=np.uint8).reshape(self.n_columns, self.n_samples).copy() if n else
+                np.zeros((self.n_columns, 0), dtype=np.uint8))
+
+    @property
+    def totals(self):
+        """[(NP, AY, BY)] per column, Python integers"""
+        t = np.frombuffer(C.string_at(self.t.totals, PHENO_TOTALS_DTYPE.itemsize * self.n_columns), dtype=PHENO_TOTALS_DTYPE)
+        return [(int(x["np"]), int(x["ay"]), (int(x["by_hi"]) << 64) | int(x["by_lo"])) for x in t]
+
+    def close(self):
+        lib.bvcf_pheno_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_pheno_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def assoc_value(text):
+    """bvcf_assoc_value: a value's text (bytes) -> the integer nearest to y 10^6, ties away from zero; ValueError for text that
+    is no value, OverflowError above 10^6  (host code, no device)"""
+    out = C.c_int64(0)
+    lib.bvcf_assoc_value.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+    rc = lib.bvcf_assoc_value(bytes(text), len(text), C.byref(out))
+    if rc == -2:
+        raise OverflowError("value above 10^6 in size")
+    if rc:
+        raise ValueError("not a value")
+    return int(out.value)
+
+
+def assoc_limbs(v):
+    """bvcf_assoc_limbs: v (128 bits) -> (its sixteen balanced base-256 digits, the smallest count that holds it)"""
+    out = (C.c_int8 * 16)()
+    u = v & ((1 << 128) - 1)
+    lib.bvcf_assoc_limbs.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
+    n = lib.bvcf_assoc_limbs(u & ((1 << 64) - 1), u >> 64, out)
+    return [int(x) for x in out], int(n)
+
+
+def _assoc_structs(rec, totals):
+    r = np.zeros(1, dtype=ASSOC_REC_DTYPE)
+    m64 = (1 << 64) - 1
+    r[0] = (rec[0], rec[1], rec[2], 0, rec[3], rec[4], rec[5], rec[6] & m64, rec[6] >> 64)
+    t = np.zeros(1, dtype=PHENO_TOTALS_DTYPE)
+    t[0] = (totals[0], totals[1], totals[2] & m64, totals[2] >> 64)
+    return r, t
+
+
+def assoc_ints(rec, totals):
+    """bvcf_assoc_ints: (n, Sg, c, va, vb) as Python integers, rec and totals as for assoc_stat"""
+    r, t = _assoc_structs(rec, totals)
+    out = (C.c_uint64 * 8)()
+    lib.bvcf_assoc_ints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if lib.bvcf_assoc_ints(r.ctypes.data, t.ctypes.data, out):
+        raise ValueError("bvcf_assoc_ints")
+    def s64(x):
+        return x - (1 << 64) if x >> 63 else x
+    def s128(lo, hi):
+        v = (hi << 64) | lo
+        return v - (1 << 128) if v >> 127 else v
+    return s64(out[0]), s64(out[1]), s128(out[2], out[3]), s128(out[4], out[5]), s128(out[6], out[7])
+
+
+def assoc_stat(rec, totals):
+    """bvcf_assoc_stat: rec = (n_het, n_hom, n_mis, a_het, a_hom, a_mis, b_mis), totals = (NP, AY, BY), Python integers ->
+    (flags, [n, altFreq, beta, se, chisq, p])  (host code, no device)"""
+    r, t = _assoc_structs(rec, totals)
+    out = (C.c_double * 6)()
+    lib.bvcf_assoc_stat.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    flags = lib.bvcf_assoc_stat(r.ctypes.data, t.ctypes.data, out)
+    return int(flags), list(out)
+
+
 class RegionTableStruct(C.Structure):
     """bvcf_region_table"""
     _fields_ = [("chroms", C.c_void_p), ("capacity", C.c_uint64), ("blob", C.c_void_p), ("blob_bytes", C.c_uint64),
@@ -766,7 +928,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--regions / --excludeRegions, their files, --regionFilterReport: the struct behind that one and its marker, only then)
     # (--grm: the struct behind that one and its marker, only then)
     # (--score / --scoreOutput / --scoreReport: the struct behind that one and its marker, only then)
-    sc = ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
+    # (--pheno / --assoc / --assocReport: the struct behind that one and its marker, only then)
+    ac = ConfigAssoc() if any(cfg.get(k) for k in ("pheno", "assoc", "assocReport")) else None
+    sc = ac.score if ac is not None else ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
     gc = sc.grm if sc is not None else ConfigGrm() if cfg.get("grm") else None
     rgc = gc.regions if gc is not None else ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
     vc = (rgc.variants if rgc is not None else
@@ -873,6 +1037,12 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 keep.append(str(cfg[key]).encode())
                 setattr(sc, field, keep[-1])
         c.reserved[1] = CONFIG_MORE_SCORE
+    if ac is not None:  # the phenotype file, the scan's table and the report
+        for key, field in (("pheno", "pheno_path"), ("assoc", "assoc_path"), ("assocReport", "assoc_report_path")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(ac, field, keep[-1])
+        c.reserved[1] = CONFIG_MORE_ASSOC
     c._keep = keep
     return c
 
@@ -1383,7 +1553,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None, regions=None, grm=False, score=None):
+                 variants=None, regions=None, grm=False, score=None, pheno=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1410,6 +1580,15 @@ class Ctx:
                 self.close()
                 raise BvcfError(rc, msg)
             self.score_columns = score.n_columns
+        self.assoc_columns = 0
+        if pheno is not None:  # bvcf_set_pheno_table: a built PhenoTable; the scan's records behind every chain (assoc())
+            lib.bvcf_set_pheno_table.argtypes = [C.c_void_p, C.c_void_p]
+            rc = lib.bvcf_set_pheno_table(self.h, C.byref(pheno.t))
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+            self.assoc_columns = pheno.n_columns
         if grm:  # bvcf_enable_grm: the GRM's integer tables behind every chain (read with grm() / grm_words())
             lib.bvcf_enable_grm.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_grm(self.h)
@@ -1748,6 +1927,34 @@ class Ctx:
         lib.bvcf_bench_grm_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         self._check(lib.bvcf_bench_grm_kernels(self.h, ms))
         return list(ms)
+
+    def bench_assoc_kernels(self):
+        """the scan's kernels over the first slot's last bench chain -> ms of [k_assoc_list, k_assoc_gemm, k_assoc_sparse]"""
+        ms = (C.c_float * 3)()
+        lib.bvcf_bench_assoc_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_assoc_kernels(self.h, ms))
+        return list(ms)
+
+    def assoc_info(self):
+        """bvcf_assoc: the AssocInfo of the batch collected last (need_rows is set after BVCF_E_CAPACITY too)"""
+        info = AssocInfo()
+        lib.bvcf_assoc.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_assoc(self.h, C.byref(info)))
+        return info
+
+    def assoc(self):
+        """the batch collected last -> its records, an ASSOC_REC_DTYPE array (n_rows, K), copied out of the slot"""
+        info = self.assoc_info()
+        n, k = int(info.n_rows), int(info.n_columns)
+        if not n or not info.recs:
+            return np.zeros((0, k), dtype=ASSOC_REC_DTYPE)
+        raw = (C.c_uint8 * (n * k * ASSOC_REC_DTYPE.itemsize)).from_address(info.recs)
+        return np.frombuffer(raw, dtype=ASSOC_REC_DTYPE).reshape(n, k).copy()
+
+    def reserve_assoc_rows(self, n):
+        """bvcf_reserve_assoc_rows: grow the arena of the records (no batch in flight)"""
+        lib.bvcf_reserve_assoc_rows.argtypes = [C.c_void_p, C.c_uint64]
+        self._check(lib.bvcf_reserve_assoc_rows(self.h, int(n)))
 
     def bench_score_kernels(self):
         """the score kernels over the first slot's last bench chain -> ms of [k_score_list, k_score_gemm, k_score_sparse, k_score_fold]"""

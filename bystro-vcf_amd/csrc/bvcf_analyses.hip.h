@@ -69,7 +69,7 @@ struct RegionGateCtx {
   DevBuf<RegionInterval> intervals;
 };
 
-// the row index the .bed rows, the trios and the LD pairs share (bvcf_bedrows.hip.h), built once when any of them is on:
+// the row index the .bed rows, the trios, the LD pairs and the association scan share (bvcf_bedrows.hip.h), built once when any of them is on:
 // the first row of every line (follows max_lines) and a row's map (follows max_alleles); the batch's row count is the
 // counter of the .bed arena
 struct RowIndexSlot {
@@ -183,9 +183,29 @@ struct ScoreCtx {
   Event ev_fold;
 };
 
+// bvcf_set_pheno_table on a file with samples (bvcf_assoc.hip.h): k_assoc_list / k_assoc_gemm / k_assoc_sparse at the end of
+// every chain, behind the row index.  A slot holds its own row lists (they follow max_alleles) and the arena of the batch's
+// records [rows][K] with its pinned copy; the batch's row count is the row index's.  Operand B, the Y table and the totals are
+// the ctx's.  cap is what a slot's arena holds, in rows (bvcf_reserve_assoc_rows grows it), last the batch collected last
+// (bvcf_assoc)
+struct AssocSlot {
+  DevBuf<uint2> dense, sparse;
+  DevBuf<uint32_t> ctr;
+  Arena<bvcf_assoc_rec> rec;
+};
+struct AssocCtx {
+  bool asked = false, on = false;
+  uint32_t K = 0, L1 = 0, L2 = 0, nb_py = 0, nb_q = 0, s64 = 0;
+  DevBuf<int8_t> b;
+  DevBuf<long long> y;
+  DevBuf<bvcf_pheno_totals> tot;
+  uint64_t cap = 0;
+  bvcf_assoc_info last{};
+};
+
 }  // namespace
 
-#else  // ---- the functions, behind Slot, bvcf_ctx and HIP_TRY
+#else // ---- the functions, behind Slot, bvcf_ctx and HIP_TRY
 
 namespace {
 
@@ -193,9 +213,11 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes);
 int alloc_results(bvcf_ctx *c, Slot &s);
 void launch_chain(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, hipEvent_t ev_gt0, hipEvent_t ev_gt1, Slot *slot);
 
-// the per-sample, pair and trio counts, the GRM, the scores, the .bed rows and the LD pairs are made from the class maps on the device: the
-// maps are made whether or not the caller wants them on the host
-bool analyses_read_maps(const bvcf_ctx *c) { return c->ss_on || c->pr.on || c->grm.on || c->score.on || c->bed.on || c->trio.on || c->ld.on; }
+// the per-sample, pair and trio counts, the GRM, the scores, the association scan, the .bed rows and the LD pairs are made from the
+// class maps on the device: the maps are made whether or not the caller wants them on the host
+bool analyses_read_maps(const bvcf_ctx *c) {
+  return c->ss_on || c->pr.on || c->grm.on || c->score.on || c->assoc.on || c->bed.on || c->trio.on || c->ld.on;
+}
 
 // "<what> with batches in flight": what every call that changes what the slots hold says when it comes too early
 int refuse_in_flight(bvcf_ctx *c, const char *what) {
@@ -996,11 +1018,11 @@ static int reserve_arena(bvcf_ctx *c, const char *what, const char *enable, bool
 
 // ---- the row index and the .bed rows
 
-// bvcf_enable_bed_rows / bvcf_enable_trios / bvcf_enable_ld: the row index all three read -- the lines' first rows (follow
+// bvcf_enable_bed_rows / bvcf_enable_trios / bvcf_enable_ld / bvcf_set_pheno_table: the row index all four read -- the lines' first rows (follow
 // max_lines), a row's map (follows max_alleles) and the counter; the .bed arena and its pinned copy when the ctx's bound
 // has grown past what the slot holds
 static int alloc_bed_rows(bvcf_ctx *c, Slot &s) {
-  if (!c->bed.on && !c->trio.on && !c->ld.on) return BVCF_OK;
+  if (!c->bed.on && !c->trio.on && !c->ld.on && !c->assoc.on) return BVCF_OK;
   if (s.idx.base.size() < c->max_lines) {
     HIP_TRY(c, s.idx.base.alloc(c->max_lines));
     HIP_TRY(c, s.idx.tile.alloc(c->max_lines / kBedTile + 2));
@@ -1383,18 +1405,420 @@ int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
   return bvcf_ld::in_ld(counts, t6) ? 1 : 0;
 }
 
+// ---- the association scan
+
+// a slot's arena holds at most 1 GiB of records
+static uint64_t assoc_max_rows(const bvcf_ctx *c) { return (1ull << 30) / (sizeof(bvcf_assoc_rec) * std::max<uint32_t>(c->assoc.K, 1u)); }
+
+// bvcf_set_pheno_table: the row lists (they follow max_alleles) and the cursors; the records' arena and its pinned copy when
+// the ctx's bound has grown past what the slot holds
+static int alloc_assoc(bvcf_ctx *c, Slot &s) {
+  if (!c->assoc.on) return BVCF_OK;
+  if (!s.assoc.ctr) HIP_TRY(c, s.assoc.ctr.alloc(2));
+  if (s.assoc.dense.size() < c->max_alleles) {
+    HIP_TRY(c, s.assoc.dense.alloc(c->max_alleles));
+    HIP_TRY(c, s.assoc.sparse.alloc(c->max_alleles));
+  }
+  HIP_TRY(c, s.assoc.rec.grow_to(c->assoc.cap * c->assoc.K));
+  return BVCF_OK;
+}
+
+// the slot holds the row index and everything the scan's kernels write
+static bool assoc_ready(const bvcf_ctx *c, const Slot &s) {
+  return s.assoc.rec.d && s.assoc.ctr && s.assoc.dense.size() >= c->max_alleles && s.assoc.sparse.size() >= c->max_alleles &&
+         index_ready(c, s);
+}
+
+static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
+  AssocArgs sa{};
+  sa.b = c->assoc.b;
+  sa.y = c->assoc.y;
+  sa.tot = c->assoc.tot;
+  sa.row_src = s.idx.src;
+  sa.total = s.bed.rows.d_total;
+  sa.dense = s.assoc.dense;
+  sa.sparse = s.assoc.sparse;
+  sa.ctr = s.assoc.ctr;
+  sa.rec = s.assoc.rec.d;
+  sa.cap_rows = s.assoc.rec.cap / c->assoc.K;
+  sa.row_cap = (uint32_t)s.idx.src.size();
+  sa.list_cap = (uint32_t)s.assoc.sparse.size();  // (the second of the two lists: there when both are)
+  sa.K = c->assoc.K;
+  sa.L1 = c->assoc.L1;
+  sa.L2 = c->assoc.L2;
+  sa.nb_py = c->assoc.nb_py;
+  sa.nb_q = c->assoc.nb_q;
+  sa.s64 = c->assoc.s64;
+  sa.ns = c->n_samples;
+  return sa;
+}
+
+// bvcf_set_pheno_table: behind the row index, the cursors from zero and the three kernels (bvcf_assoc.hip.h; bvcf_collect
+// copies the used part of the records)
+static void launch_assoc(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const AssocArgs &sa, const Event *ev = nullptr) {
+  hipMemsetAsync(sa.ctr, 0, 2 * sizeof(uint32_t), st);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_assoc_list, dim3(c->n_cu * kSsListWgs), dim3(kWgThreads), 0, st, sa);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_assoc_gemm, dim3(c->n_cu * 4), dim3(kWgThreads), 0, st, a, sa);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_assoc_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa);
+}
+
+// collect, as for the .bed rows: the batch's rows against the slot's arena
+static bvcf_assoc_info assoc_need(bvcf_ctx *c, const Slot &s) {
+  bvcf_assoc_info t{};
+  t.n_columns = c->assoc.K;
+  if (c->assoc.on && assoc_ready(c, s)) {
+    t.recs = s.assoc.rec.h;
+    t.n_rows = *s.bed.rows.h_total;
+  }
+  t.need_rows = t.n_rows;
+  c->assoc.last = bvcf_assoc_info{};
+  c->assoc.last.n_columns = t.n_columns;
+  c->assoc.last.need_rows = t.need_rows;
+  return t;
+}
+static int assoc_copy(bvcf_ctx *c, Slot &s, const bvcf_assoc_info &t) {
+  if (t.n_rows)
+    HIP_TRY(c, hipMemcpyAsync(s.assoc.rec.h, s.assoc.rec.d, t.n_rows * t.n_columns * sizeof(bvcf_assoc_rec), hipMemcpyDeviceToHost, s.stream));
+  return BVCF_OK;
+}
+
+void bvcf_pheno_table_free(bvcf_pheno_table *t) {
+  if (!t) return;
+  free((void *)t->b);
+  free((void *)t->y);
+  free((void *)t->present);
+  free((void *)t->totals);
+  free((void *)t->names);
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_pheno_table_build(const int64_t *y, const uint8_t *present, uint32_t k, uint32_t s, const char *names, size_t names_bytes,
+                           uint64_t n_named, bvcf_pheno_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (k < 1 || k > BVCF_ASSOC_MAX_COLUMNS || (s && (!y || !present)) || (names_bytes && !names)) return BVCF_E_ARG;
+  if (s > BVCF_ASSOC_MAX_SAMPLES) return BVCF_E_TOO_BIG;
+  const size_t n = (size_t)k * s;
+  uint32_t l1 = 1, l2 = 1;
+  int8_t l[16];
+  for (size_t q = 0; q < n; q++) {
+    if (!present[q]) continue;
+    if (y[q] > BVCF_ASSOC_MAX_Y || y[q] < -BVCF_ASSOC_MAX_Y) return BVCF_E_ARG;
+    l1 = std::max(l1, (uint32_t)assoc_limbs(y[q], l));
+    uint64_t lo, hi;
+    assoc_square(y[q], &lo, &hi);
+    l2 = std::max(l2, (uint32_t)assoc_limbs128(lo, hi, l));
+  }
+  const uint32_t s64 = (s + 63u) & ~63u, n_cols = k * (1u + l1 + l2);
+  int8_t *b = (int8_t *)calloc((size_t)n_cols * s64 + 1, 1);
+  int64_t *yy = (int64_t *)calloc(n + 1, sizeof(int64_t));
+  uint8_t *pp = (uint8_t *)calloc(n + 1, 1);
+  bvcf_pheno_totals *tot = (bvcf_pheno_totals *)calloc(k, sizeof(bvcf_pheno_totals));
+  char *nm = (char *)malloc(names_bytes + 1);
+  if (!b || !yy || !pp || !tot || !nm) {
+    free(b);
+    free(yy);
+    free(pp);
+    free(tot);
+    free(nm);
+    return BVCF_E_NOMEM;
+  }
+  if (names_bytes) memcpy(nm, names, names_bytes);
+  // the columns: per phenotype P and the limbs of Y, then per phenotype the limbs of Y^2
+  for (uint32_t c = 0; c < k; c++) {
+    int8_t *py = b + (size_t)c * (1u + l1) * s64, *q2 = b + ((size_t)k * (1u + l1) + (size_t)c * l2) * s64;
+    for (uint32_t i = 0; i < s; i++) {
+      const size_t at = (size_t)c * s + i;
+      if (!present[at]) continue;
+      pp[at] = 1;
+      yy[at] = y[at];
+      py[i] = 1;
+      assoc_limbs(y[at], l);
+      for (uint32_t a = 0; a < l1; a++) py[(size_t)(1u + a) * s64 + i] = l[a];
+      uint64_t lo, hi;
+      assoc_square(y[at], &lo, &hi);
+      assoc_limbs128(lo, hi, l);
+      for (uint32_t a = 0; a < l2; a++) q2[(size_t)a * s64 + i] = l[a];
+      tot[c].np++;
+      tot[c].ay += y[at];
+      assoc_add128w(&tot[c].by_lo, &tot[c].by_hi, lo, hi);
+    }
+  }
+  out->n_columns = k;
+  out->n_samples = s;
+  out->s64 = s64;
+  out->l1 = l1;
+  out->l2 = l2;
+  out->n_cols = n_cols;
+  out->n_named = n_named;
+  out->b = b;
+  out->y = yy;
+  out->present = pp;
+  out->totals = tot;
+  out->names = nm;
+  out->names_bytes = names_bytes;
+  return BVCF_OK;
+}
+
+// the file's rules (bvcf_config_assoc.pheno_path); every refusal names its line in err
+int bvcf_pheno_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
+                           bvcf_pheno_table *out, char *err, size_t err_cap) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  std::string msg;
+  const auto fail = [&](uint64_t line, const std::string &what, int rc) {
+    msg = line ? "line " + std::to_string(line) + ": " + what : what;
+    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
+    return rc;
+  };
+  if ((n && !text) || (s && (!sample_names || !sample_lens))) return BVCF_E_ARG;
+  if (s > BVCF_ASSOC_MAX_SAMPLES) return fail(0, std::to_string(s) + " samples, more than 2^22", BVCF_E_TOO_BIG);
+  // a name -> its first sample column and how many columns carry it
+  std::unordered_map<std::string_view, std::pair<uint32_t, uint32_t>> cols;
+  for (uint32_t i = 0; i < s; i++) {
+    auto ins = cols.emplace(std::string_view(sample_names[i], sample_lens[i]), std::make_pair(i, 0u));
+    ins.first->second.second++;
+  }
+  std::vector<int64_t> y;
+  std::vector<uint8_t> present;
+  std::vector<uint64_t> line_of(s, 0);
+  std::string names;
+  uint32_t k = 0;
+  uint64_t line_no = 0, n_named = 0;
+  bool first = true;
+  std::vector<std::string_view> f;
+  std::vector<int64_t> vals;
+  std::vector<uint8_t> have;
+  for (size_t at = 0; at < n;) {
+    const char *nl = (const char *)memchr(text + at, '\n', n - at);
+    size_t end = nl ? (size_t)(nl - text) : n;
+    const size_t next = nl ? end + 1 : n;
+    line_no++;
+    if (end > at && text[end - 1] == '\r') end--;
+    const std::string_view line(text + at, end - at);
+    at = next;
+    if (line.empty()) continue;
+    f.clear();
+    for (size_t p = 0;;) {
+      const size_t t = line.find('\t', p);
+      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
+      if (t == std::string_view::npos) break;
+      p = t + 1;
+    }
+    const bool header = line[0] == '#';
+    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
+    if (first) {
+      if (f.size() < 2 || f.size() - 1 > BVCF_ASSOC_MAX_COLUMNS)
+        return fail(line_no, "want a sample and 1 to " + std::to_string(BVCF_ASSOC_MAX_COLUMNS) + " columns, tab-separated", BVCF_E_ARG);
+      k = (uint32_t)(f.size() - 1);
+      first = false;
+      y.assign((size_t)k * s, 0);
+      present.assign((size_t)k * s, 0);
+      if (header) {
+        if (f[0] != "#sample") return fail(line_no, "a header starts with \"#sample\"", BVCF_E_ARG);
+        for (uint32_t c = 0; c < k; c++) {
+          if (f[1 + c].empty()) return fail(line_no, "an empty column name", BVCF_E_ARG);
+          for (uint32_t d = 0; d < c; d++)
+            if (f[1 + d] == f[1 + c]) return fail(line_no, "the column name " + std::string(f[1 + c]) + " twice", BVCF_E_ARG);
+          names.append(f[1 + c]);
+          names.push_back('\0');
+        }
+        continue;
+      }
+      for (uint32_t c = 0; c < k; c++) {
+        names.append("PHENO" + std::to_string(c + 1));
+        names.push_back('\0');
+      }
+    }
+    if (f.size() != (size_t)k + 1)
+      return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(k + 1), BVCF_E_ARG);
+    if (f[0].empty()) return fail(line_no, "an empty sample name", BVCF_E_ARG);
+    vals.assign(k, 0);
+    have.assign(k, 0);
+    for (uint32_t c = 0; c < k; c++) {
+      if (f[1 + c] == "NA") continue;
+      const int rc = assoc_value(f[1 + c].data(), f[1 + c].size(), &vals[c]);
+      if (rc == -2) return fail(line_no, "the value " + std::string(f[1 + c]) + " is above 10^6 in size", BVCF_E_ARG);
+      if (rc) return fail(line_no, "bad value \"" + std::string(f[1 + c].substr(0, 80)) + "\"", BVCF_E_ARG);
+      have[c] = 1;
+    }
+    const auto it = cols.find(f[0]);
+    if (it == cols.end()) continue;  // (no (kept) sample: ignored)
+    if (it->second.second > 1) return fail(line_no, "the name " + std::string(f[0]) + " matches more than one sample column", BVCF_E_ARG);
+    const uint32_t i = it->second.first;
+    if (line_of[i]) return fail(line_no, "the sample " + std::string(f[0]) + " is on line " + std::to_string(line_of[i]) + " already", BVCF_E_ARG);
+    line_of[i] = line_no;
+    n_named++;
+    for (uint32_t c = 0; c < k; c++) {
+      y[(size_t)c * s + i] = vals[c];
+      present[(size_t)c * s + i] = have[c];
+    }
+  }
+  if (first) return fail(0, "no line", BVCF_E_ARG);
+  const int rc = bvcf_pheno_table_build(y.data(), present.data(), k, s, names.data(), names.size(), n_named, out);
+  if (rc) return fail(0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
+  return BVCF_OK;
+}
+
+// the table is one bvcf_pheno_table_build made: its counts agree with one another
+static bool pheno_table_sound(const bvcf_pheno_table *t) {
+  return t && t->n_columns >= 1 && t->n_columns <= BVCF_ASSOC_MAX_COLUMNS && t->n_samples <= BVCF_ASSOC_MAX_SAMPLES &&
+         t->s64 == ((t->n_samples + 63u) & ~63u) && t->l1 >= 1 && t->l1 <= BVCF_ASSOC_MAX_LIMBS1 && t->l2 >= 1 &&
+         t->l2 <= BVCF_ASSOC_MAX_LIMBS2 && t->n_cols == t->n_columns * (1u + t->l1 + t->l2) && t->b && t->y && t->present && t->totals;
+}
+
+int bvcf_set_pheno_table(bvcf_ctx *c, const bvcf_pheno_table *t) {
+  if (!c) return BVCF_E_ARG;
+  if (!pheno_table_sound(t)) {
+    c->err = "bvcf_set_pheno_table: want a table as bvcf_pheno_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_pheno_table")) return rc;
+  if (c->assoc.asked) {
+    c->err = "bvcf_set_pheno_table: the ctx has a phenotype table";
+    return BVCF_E_ARG;
+  }
+  if (t->n_samples != c->n_samples) {
+    c->err = "bvcf_set_pheno_table: the table has " + std::to_string(t->n_samples) + " samples, the ctx " + std::to_string(c->n_samples);
+    return BVCF_E_ARG;
+  }
+  const uint32_t K = t->n_columns, ns = c->n_samples;
+  // a line of text gives a row and has two bytes per sample at least; lines with many ALTs outrun this and grow the arena
+  // (BVCF_E_CAPACITY, bvcf_reserve_assoc_rows)
+  const uint64_t cap = (c->p.max_batch_bytes / std::max<uint64_t>(2ull * ns, 256) + 256 + 63) & ~63ull;
+  const uint64_t max_rows = (1ull << 30) / (sizeof(bvcf_assoc_rec) * K);
+  if (ns && cap > max_rows) {
+    c->err = "bvcf_set_pheno_table: " + std::to_string(cap) + " rows x " + std::to_string(K) + " columns: a slot's records would take " +
+             std::to_string(cap * K * sizeof(bvcf_assoc_rec)) + " bytes, more than 1 GiB: use fewer columns or smaller batches (max_batch_bytes)";
+    return BVCF_E_TOO_BIG;
+  }
+  c->assoc.asked = true;
+  c->assoc.K = K;
+  c->assoc.last = bvcf_assoc_info{};
+  c->assoc.last.n_columns = K;
+  if (!ns) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  // B on the device: the PY columns from column 0, the Q columns from the next whole block of 16, zero columns between
+  const uint32_t n_py = K * (1u + t->l1), n_q = K * t->l2, nb_py = (n_py + 15u) / 16u, nb_q = (n_q + 15u) / 16u;
+  const size_t b_bytes = (size_t)16u * (nb_py + nb_q) * t->s64;
+  HIP_TRY(c, c->assoc.b.alloc(b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemset(c->assoc.b, 0, b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->assoc.b, t->b, (size_t)n_py * t->s64, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(c->assoc.b + (size_t)16u * nb_py * t->s64, t->b + (size_t)n_py * t->s64, (size_t)n_q * t->s64, hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.y.alloc((size_t)K * ns));
+  HIP_TRY(c, hipMemcpy(c->assoc.y, t->y, (size_t)K * ns * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.tot.alloc(K));
+  HIP_TRY(c, hipMemcpy(c->assoc.tot, t->totals, (size_t)K * sizeof(bvcf_pheno_totals), hipMemcpyHostToDevice));
+  c->assoc.L1 = t->l1;
+  c->assoc.L2 = t->l2;
+  c->assoc.nb_py = nb_py;
+  c->assoc.nb_q = nb_q;
+  c->assoc.s64 = t->s64;
+  c->assoc.cap = std::max<uint64_t>(c->assoc.cap, cap);
+  c->assoc.on = true;
+  for (auto &s : c->slots) {
+    if (const int rc = alloc_bed_rows(c, s)) return rc;
+    if (const int rc = alloc_assoc(c, s)) return rc;
+  }
+  return BVCF_OK;
+}
+
+int bvcf_reserve_assoc_rows(bvcf_ctx *c, uint64_t rows) {
+  if (!c) return BVCF_E_ARG;
+  if (c->assoc.on && !c->in_flight && rows > assoc_max_rows(c)) {
+    c->err = "bvcf_reserve_assoc_rows: " + std::to_string(rows) + " rows x " + std::to_string(c->assoc.K) +
+             " columns: a slot's records would pass 1 GiB: use fewer columns or smaller batches (max_batch_bytes)";
+    return BVCF_E_TOO_BIG;
+  }
+  return reserve_arena(c, "bvcf_reserve_assoc_rows", "bvcf_set_pheno_table", c->assoc.asked, c->assoc.on, rows, assoc_max_rows(c),
+                       ": a slot's records would pass 1 GiB", &c->assoc.cap, alloc_assoc);
+}
+
+int bvcf_assoc(bvcf_ctx *c, bvcf_assoc_info *out) {
+  if (!c || !out) return BVCF_E_ARG;
+  if (!c->assoc.asked) {
+    c->err = "bvcf_assoc: bvcf_set_pheno_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  *out = c->assoc.last;
+  return BVCF_OK;
+}
+
+int bvcf_assoc_value(const char *text, size_t n, int64_t *out) { return assoc_value(text, n, out); }
+int bvcf_assoc_limbs(uint64_t lo, uint64_t hi, int8_t out[16]) { return out ? assoc_limbs128(lo, hi, out) : -1; }
+
+static AssocSums assoc_sums_of(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals) {
+  AssocSums s{};
+  s.n_het = rec->n_het;
+  s.n_hom = rec->n_hom;
+  s.n_mis = rec->n_mis;
+  s.a_het = rec->a_het;
+  s.a_hom = rec->a_hom;
+  s.a_mis = rec->a_mis;
+  s.b_mis = ((unsigned __int128)rec->b_mis_hi << 64) | rec->b_mis_lo;
+  s.np = totals->np;
+  s.ay = totals->ay;
+  s.by = ((unsigned __int128)totals->by_hi << 64) | totals->by_lo;
+  return s;
+}
+
+int bvcf_assoc_ints(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, uint64_t out[8]) {
+  if (!rec || !totals || !out) return -1;
+  const AssocInts q = assoc_ints(assoc_sums_of(rec, totals));
+  out[0] = (uint64_t)q.n;
+  out[1] = (uint64_t)q.sg;
+  const __int128 v[3] = {q.c, q.va, q.vb};
+  for (int k = 0; k < 3; k++) {
+    out[2 + 2 * k] = (uint64_t)(unsigned __int128)v[k];
+    out[3 + 2 * k] = (uint64_t)((unsigned __int128)v[k] >> 64);
+  }
+  return 0;
+}
+
+int bvcf_assoc_stat(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, double out[6]) {
+  if (!rec || !totals || !out) return -1;
+  return assoc_stat(assoc_ints(assoc_sums_of(rec, totals)), out);
+}
+
+// (k_assoc_list reads the row index of the slot's last chain: the hook builds it once more first)
+int bvcf_bench_assoc_kernels(bvcf_ctx *c, float ms[3]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[4];
+  if (const int rc = start_hook(c, "bvcf_bench_assoc_kernels", c->assoc.on && assoc_ready(c, s) && c->bench_src,
+                                "the ctx has no phenotype table, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  launch_row_index(c, a, s.stream, make_bed_args(c, s));
+  launch_assoc(c, a, s.stream, make_assoc_args(c, s), ev);  // (ev[0] behind the memset, ev[1] behind k_assoc_list, ev[2] behind the product)
+  HIP_TRY(c, hipEventRecord(ev[3], s.stream));
+  if (const int rc = finish_hook(c, ev, s.stream, ms)) return rc;
+  HIP_TRY(c, s.bed.rows.copy_total(s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  if (*s.bed.rows.h_total * c->assoc.K > s.assoc.rec.cap) {
+    c->err = "bvcf_bench_assoc_kernels: the rows outrun the arena (bvcf_reserve_assoc_rows): " + std::to_string(*s.bed.rows.h_total) + " rows";
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
 // ---- the rows' kernels together: the end of a chain, the counters' way to the host, the bench hooks
 
-// the end of a chain with samples, with bvcf_enable_bed_rows, bvcf_enable_ld and / or bvcf_enable_trios: every row's place
-// in output order -- once --, then the .bed rows into the slot's arena, the pairs' events and the trios' counts and events
-// into theirs
+// the end of a chain with samples, with bvcf_enable_bed_rows, bvcf_enable_ld, bvcf_enable_trios and / or bvcf_set_pheno_table:
+// every row's place in output order -- once --, then the scan's records, the .bed rows into the slot's arena, the pairs'
+// events and the trios' counts and events into theirs
 static void launch_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *slot) {
   if (!slot) return;
   const bool ld = c->ld.on && ld_ready(c, *slot);
   const bool bed = (c->bed.on && bed_ready(c, *slot)) || ld, trios = c->trio.on && trios_ready(c, *slot);
-  if (!bed && !trios) return;
+  const bool assoc = c->assoc.on && assoc_ready(c, *slot);
+  if (!bed && !trios && !assoc) return;
   const BedArgs ba = make_bed_args(c, *slot);
   launch_row_index(c, a, st, ba);
+  if (assoc) launch_assoc(c, a, st, make_assoc_args(c, *slot));
   if (bed) launch_bed_rows(c, a, st, ba);
   if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
   if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)
@@ -1402,7 +1826,7 @@ static void launch_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *
 
 // the arenas' counters on their way to the host, behind the batch's own (launch_batch)
 static int copy_arena_totals(bvcf_ctx *c, Slot &s) {
-  if ((c->bed.on || c->trio.on || c->ld.on) && s.bed.rows.d_total) HIP_TRY(c, s.bed.rows.copy_total(s.stream));
+  if ((c->bed.on || c->trio.on || c->ld.on || c->assoc.on) && s.bed.rows.d_total) HIP_TRY(c, s.bed.rows.copy_total(s.stream));
   if (c->ld.on && ld_ready(c, s)) HIP_TRY(c, s.ld.ev.copy_total(s.stream));
   if (c->trio.on && trios_ready(c, s)) HIP_TRY(c, s.trio.ev.copy_total(s.stream));
   return BVCF_OK;
@@ -1532,6 +1956,7 @@ static int alloc_row_lists(bvcf_ctx *c, Slot &s) {
   if (const int rc = alloc_ld(c, s)) return rc;
   if (const int rc = alloc_grm_lists(c, s)) return rc;
   if (const int rc = alloc_score_lists(c, s)) return rc;
+  if (const int rc = alloc_assoc(c, s)) return rc;
   if (!c->ss_on && !c->pr.on) return BVCF_OK;
   s.pr.planes.reset();
   s.pr.cap_tiles = 0;

@@ -121,6 +121,7 @@ struct Slot {
   PairStatsSlot pr;
   GrmSlot grm;
   ScoreSlot score;
+  AssocSlot assoc;
   SiteGateSlot gate;
   RowIndexSlot idx;
   BedSlot bed;
@@ -172,6 +173,7 @@ struct bvcf_ctx : bvcf_ctx_plan {
   PairStatsCtx pr;
   GrmCtx grm;
   ScoreCtx score;
+  AssocCtx assoc;
   SiteGateCtx gate;
   VariantGateCtx variants;
   RegionGateCtx regions;
@@ -1985,7 +1987,8 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   const bvcf_bed_rows_info bed = bed_need(c, s);
   const bvcf_ld_info ld = ld_need(c, s);
   const bvcf_trio_info trio = trio_need(c, s);
-  if (!k.need.fits || !s.bed.rows.fits(bed.need_bytes) || !s.trio.ev.fits(trio.need_events) || !s.bed.rows.fits(ld.need_row_bytes) ||
+  const bvcf_assoc_info assoc = assoc_need(c, s);
+  if (!k.need.fits || !s.assoc.rec.fits(assoc.need_rows * assoc.n_columns) || !s.bed.rows.fits(bed.need_bytes) || !s.trio.ev.fits(trio.need_events) || !s.bed.rows.fits(ld.need_row_bytes) ||
       !s.ld.ev.fits(ld.need_events)) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
@@ -2012,6 +2015,7 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   if (!rc) rc = bed_copy(c, s, bed);
   if (!rc) rc = trio_copy(c, s, trio);
   if (!rc) rc = ld_copy(c, s, ld);
+  if (!rc) rc = assoc_copy(c, s, assoc);
   if (rc) return rc;
   e = hipStreamSynchronize(s.stream);
   if (e != hipSuccess) {
@@ -2022,6 +2026,7 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   c->bed.last = bed;  // (published: until here the reports held the needs alone)
   c->trio.last = trio;
   c->ld.last = ld;
+  c->assoc.last = assoc;
   add_totals(c, s, k, r);
   return BVCF_OK;
 }

@@ -62,6 +62,10 @@
 //    cores -- classes expanded in registers, the tile's weights staged in LDS --, k_score_sparse adds the short lists with
 //    integer atomics -- the exact fixed-point sums behind --score, bvcf_score.hip.h; k_score_fold recombines a collected
 //    batch's limbs into the ctx's 128-bit totals)
+//   (bvcf_set_pheno_table, behind the row index: k_assoc_list deals the rows by the form of their map, k_assoc_gemm multiplies
+//    the dense rows' classes -- the map is the A operand, expanded in registers -- with the phenotypes' int8 limbs on the
+//    matrix cores, reducing over the samples into one record per (row, phenotype), k_assoc_sparse does the short lists --
+//    the exact integer sums behind --pheno / --assoc, bvcf_assoc.hip.h)
 //   (bvcf_set_region_table, right behind k_finish and in front of the variant gate: k_region_gate finds every row's
 //    chromosome in the hash set of --regions / --excludeRegions, binary-searches the row's span in the chromosome's merged
 //    intervals and takes the unselected rows out -- bvcf_regions.hip.h)
@@ -130,6 +134,7 @@
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_grm.hip.h"
 #include "bvcf_score.hip.h"
+#include "bvcf_assoc.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
 #include "bvcf_ld.hip.h"

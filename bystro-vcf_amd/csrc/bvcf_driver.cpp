@@ -506,6 +506,10 @@ void Driver::device_main(DevWorker *W) {
       fail(std::string("bvcf_ld_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
       return;
     }
+    if (R_.assoc_on && bvcf_assoc(W->ctx, &j.assoc) != BVCF_OK) {  // --pheno / --assoc: likewise
+      fail(std::string("bvcf_assoc: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      return;
+    }
     j.job = n_jobs;
     outstanding.emplace_back(n_jobs, n_collects - 1);
     n_jobs++;
@@ -603,11 +607,12 @@ void Driver::formatter_main(DevWorker *W) {
       const bool plink = R_.bed_fd >= 0;
       const bool mendel = R_.mendel_on && !R_.trios.empty();  // (the tables are summed in input order too: one thread)
       const bool ld = R_.ld_on;  // (the seam is a state machine over the batches in input order: one thread)
-      if ((R_.arrow && j.res.dosage) || plink || mendel || ld) {
+      const bool assoc = R_.assoc_fd >= 0;  // (the lines go into the file in input order: one thread)
+      if ((R_.arrow && j.res.dosage) || plink || mendel || ld || assoc) {
         // the dosage rows go into the file in input order (main.go:576-584): the sink runs this when it is the block's
         // turn; the result slot and the text stay on loan until then -- and so do the batch's .bed rows and .bim lines
         auto keep = std::make_shared<FmtJob>(std::move(j));
-        it.in_order = [this, keep, text, release, plink, mendel, ld]() {
+        it.in_order = [this, keep, text, release, plink, mendel, ld, assoc]() {
           if (!dosage_failed_.load() && append_dosage(R_, &keep->res, text)) {
             dosage_failed_.store(true);
             fail("dosage matrix: write failed", BVCF_E_FATAL);
@@ -623,6 +628,12 @@ void Driver::formatter_main(DevWorker *W) {
           if (ld && !ld_failed_.load() && append_ld(R_, &keep->res, text, keep->ld)) {
             ld_failed_.store(true);
             fail("ld: the device's events do not match the batch's rows", BVCF_E_FATAL);
+          }
+          if (assoc && !assoc_failed_.load()) {
+            if (const int arc = append_assoc(R_, &keep->res, text, keep->assoc)) {
+              assoc_failed_.store(true);
+              fail(arc == BVCF_E_IO ? "assoc: write failed" : "assoc: the device's rows do not match the batch's rows", BVCF_E_FATAL);
+            }
           }
           release();
         };
@@ -678,6 +689,10 @@ int Driver::run(uint64_t *n_lines_in) {
       return rc;
     }
     if (const int rc = open_score(R_, &msg)) {  // --score: the outputs opened, the score file read
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
+    if (const int rc = open_assoc(R_, &msg)) {  // --pheno / --assoc: the outputs opened
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
@@ -917,6 +932,14 @@ int Driver::run(uint64_t *n_lines_in) {
       std::string msg;
       if (rc_ == BVCF_OK && write_score(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
       if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
+    }
+    if (R_.assoc_fd >= 0) {
+      // --pheno / --assoc: the sink wrote the batches it was handed, in input order; the last lines and the report
+      std::string msg;
+      if (close_assoc(R_, rc_ == BVCF_OK, &msg)) {
+        fail(msg, BVCF_E_IO);
+        write_all(fd_err_, log_.data(), log_.size());
+      }
     }
     if (sg_fd_ >= 0) {
       // --siteFilterReport: the workers' counts of the batches they handed on

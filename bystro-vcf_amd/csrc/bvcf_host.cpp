@@ -79,6 +79,12 @@ void bvcf_config_score_defaults(bvcf_config_score *c) {
   c->grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_SCORE;
 }
 
+void bvcf_config_assoc_defaults(bvcf_config_assoc *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_score_defaults(&c->score);
+  c->score.grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_ASSOC;
+}
+
 int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out) {
   if (!out || (!text && n)) return BVCF_E_ARG;
   std::vector<uint64_t> off;
@@ -176,6 +182,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_regions(R, &msg);
   if (rc == BVCF_OK) rc = open_grm(R, &msg);
   if (rc == BVCF_OK) rc = open_score(R, &msg);
+  if (rc == BVCF_OK) rc = open_assoc(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -255,6 +262,15 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         bvcf_ld_info li;
         if (bvcf_ld_stats(R.ctx, &li) != BVCF_OK || append_ld(R, &res, vcf + pos, li)) {
           l.append("ld: the device's events do not match the batch's rows\n");
+          rc = BVCF_E_FATAL;
+          break;
+        }
+      }
+      if (R.assoc_on) {  // --pheno / --assoc: the batch's records, a line per (row, phenotype)
+        bvcf_assoc_info ai;
+        const int arc = bvcf_assoc(R.ctx, &ai) != BVCF_OK ? BVCF_E_FATAL : append_assoc(R, &res, vcf + pos, ai);
+        if (arc) {
+          l.append(arc == BVCF_E_IO ? "assoc: write failed\n" : "assoc: the device's rows do not match the batch's rows\n");
           rc = BVCF_E_FATAL;
           break;
         }
@@ -339,6 +355,10 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       l.append(msg + "\n");
       rc = BVCF_E_IO;
     }
+  }
+  if (R.assoc_fd >= 0 && close_assoc(R, rc == BVCF_OK, &msg)) {  // --pheno / --assoc: the last lines and the report
+    l.append(msg + "\n");
+    rc = BVCF_E_IO;
   }
   if (sg_fd >= 0) {  // --siteFilterReport: after a successful run only
     if (rc != BVCF_OK) {

@@ -724,6 +724,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
     return BVCF_E_IO;
   }
   if (const int rc = load_pedigree(R, msg)) return rc;  // --mendel / --mendelErrors: the trios among the (kept) names
+  if (const int rc = load_pheno(R, msg)) return rc;     // --pheno / --assoc: the phenotypes of the (kept) names
   bvcf_params &p = R.params;
   memset(&p, 0, sizeof p);
   p.abi_version = BVCF_ABI_VERSION;
@@ -862,6 +863,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
     rc = bvcf_set_score_table(*ctx, &R.score_table);
     if (rc) {
       *msg = std::string("bvcf_set_score_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
+  if (rc == BVCF_OK && R.assoc_on) {  // --pheno / --assoc: the run's table and the record arenas of every ctx of the run
+    rc = bvcf_set_pheno_table(*ctx, &R.pheno_table);
+    if (rc) {
+      *msg = std::string("bvcf_set_pheno_table: ") + bvcf_last_error(*ctx);
       bvcf_destroy(*ctx);
       *ctx = nullptr;
     }
@@ -1316,13 +1325,15 @@ int close_dosage(Run &R) {
 // --mendelErrors), the pairs' events and the rows the pairs read (--ld / --ldPrune).  The reports are the ctx's, of the batch
 // collected last: read right after the failed collect, before anything else is collected
 BatchNeed read_batch_need(bvcf_ctx *ctx, const bvcf_config *c, const bvcf_result &res) {
-  BatchNeed n{res.need_lines, res.need_alleles, res.need_cmap_bytes, 0, 0, 0, 0};
+  BatchNeed n{res.need_lines, res.need_alleles, res.need_cmap_bytes, 0, 0, 0, 0, 0};
   bvcf_bed_rows_info b;
   if (wants_plink(c) && bvcf_bed_rows(ctx, &b) == BVCF_OK) n.bed_bytes = b.need_bytes;
   bvcf_trio_info t;
   if (wants_mendel(c) && bvcf_trio_stats(ctx, &t) == BVCF_OK) n.trio_events = t.need_events;
   bvcf_ld_info l;
   if (wants_ld(c) && bvcf_ld_stats(ctx, &l) == BVCF_OK) n.ld_events = l.need_events, n.ld_row_bytes = l.need_row_bytes;
+  bvcf_assoc_info ai;
+  if (wants_assoc(c) && bvcf_assoc(ctx, &ai) == BVCF_OK) n.assoc_rows = ai.need_rows;
   return n;
 }
 
@@ -1334,6 +1345,7 @@ int reserve_batch_need(bvcf_ctx *ctx, const BatchNeed &n) {
   if (rc == BVCF_OK && n.trio_events) rc = bvcf_reserve_trio_events(ctx, more(n.trio_events, 1024));
   if (rc == BVCF_OK && n.ld_events) rc = bvcf_reserve_ld_events(ctx, more(n.ld_events, 1024));
   if (rc == BVCF_OK && n.ld_row_bytes) rc = bvcf_reserve_bed_rows(ctx, more(n.ld_row_bytes, 4096));
+  if (rc == BVCF_OK && n.assoc_rows) rc = bvcf_reserve_assoc_rows(ctx, more(n.assoc_rows, 256));
   return rc;
 }
 
@@ -1841,6 +1853,170 @@ int write_score(Run &R, const uint64_t *sum, std::string *msg) {
   }
   if (bad) {
     *msg = std::string("score: write failed: ") + strerror(saved);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_assoc(Run &R, std::string *msg) {
+  const bvcf_config_assoc *ac = assoc_config(R.cfg);
+  if (!ac) return BVCF_OK;
+  const char *pp = ac->pheno_path, *op = ac->assoc_path, *rp = ac->assoc_report_path;
+  const bool have_p = pp && *pp, have_o = op && *op, have_r = rp && *rp;
+  if (have_p != have_o) {
+    *msg = have_p ? "pheno_path without assoc_path" : "assoc_path without pheno_path";
+    return BVCF_E_ARG;
+  }
+  if (have_r && !have_p) {
+    *msg = "assoc_report_path without pheno_path";
+    return BVCF_E_ARG;
+  }
+  if (!have_p) return BVCF_OK;
+  for (const auto &f : {std::pair<int *, const char *>{&R.assoc_fd, op}, std::pair<int *, const char *>{&R.assoc_report_fd, have_r ? rp : nullptr}}) {
+    if (!f.second) continue;
+    *f.first = open(f.second, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.first < 0) {
+      *msg = std::string("open ") + f.second + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  R.assoc_on = true;
+  return BVCF_OK;
+}
+
+// the phenotype file against the (kept) names, once the header is known; the output's header line
+int load_pheno(Run &R, std::string *msg) {
+  if (!R.assoc_on) return BVCF_OK;
+  const char *path = assoc_config(R.cfg)->pheno_path;
+  std::string text;
+  {
+    FILE *f = fopen(path, "rb");
+    if (!f) {
+      *msg = std::string("open ") + path + ": " + strerror(errno);
+      return BVCF_E_FATAL;
+    }
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, f)) > 0) text.append(buf, got);
+    const int err = ferror(f) ? errno : 0;
+    fclose(f);
+    if (err) {
+      *msg = std::string("read ") + path + ": " + strerror(err);
+      return BVCF_E_FATAL;
+    }
+  }
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+  if (ns > BVCF_ASSOC_MAX_SAMPLES) {
+    *msg = "assoc: " + std::to_string(ns) + " samples, the scan holds at most 2^22 (select fewer with --keepSamples / --excludeSamples)";
+    return BVCF_E_FATAL;
+  }
+  std::vector<const char *> names(ns);
+  std::vector<uint32_t> lens(ns);
+  for (size_t s = 0; s < ns; s++) {
+    names[s] = R.pre.header[9 + s].data();
+    lens[s] = (uint32_t)R.pre.header[9 + s].size();
+  }
+  char err[512] = "";
+  bvcf_pheno_table_free(&R.pheno_table);
+  if (bvcf_pheno_table_parse(text.data(), text.size(), names.data(), lens.data(), (uint32_t)ns, &R.pheno_table, err, sizeof err)) {
+    *msg = std::string("pheno: ") + path + ": " + err;
+    return BVCF_E_FATAL;
+  }
+  static const char kHead[] = "chrom\tpos\tref\talt\tpheno\tn\taltFreq\tbeta\tse\tchisq\tp\n";
+  R.assoc_buf.assign(kHead, sizeof kHead - 1);
+  R.assoc_rows = R.assoc_tested = 0;
+  return BVCF_OK;
+}
+
+// a line per (row, phenotype): the rows bvcf_assoc numbers are the rows this loop visits, in this order, as for append_plink
+int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai) {
+  if (R.assoc_fd < 0 || !r->n_samples) return BVCF_OK;
+  const uint32_t K = R.pheno_table.n_columns;
+  if (ai.n_columns != K || (ai.n_rows && !ai.recs)) return BVCF_E_FATAL;
+  const char *empty = or_default(R.cfg->empty_field, "!");
+  std::vector<std::string_view> names;
+  for (const char *nm = R.pheno_table.names, *e = nm + R.pheno_table.names_bytes; nm < e; nm += strlen(nm) + 1) names.emplace_back(nm);
+  if (names.size() != K) return BVCF_E_FATAL;
+  std::string &o = R.assoc_buf;
+  std::string locus;
+  size_t at[5];
+  uint64_t n_rows = 0;
+  const auto put = [&](double v) {
+    if (v == 0.0)
+      o.push_back('0');
+    else
+      append_g3(o, v);
+  };
+  for (uint32_t li = 0; li < r->n_lines; li++) {
+    const bvcf_line &L = r->lines[li];
+    if (L.status != BVCF_LINE_OK) continue;
+    const char *row = row_of(r, block, li, L);
+    for (uint32_t k = 0; k < L.n_rec; k++) {
+      const bvcf_allele &A = r->alleles[k ? L.rec_first + k - 1 : li];
+      if (A.ac == 0) continue;  // main.go:558-560
+      if (n_rows >= ai.n_rows) return BVCF_E_FATAL;
+      locus.clear();
+      append_locus(locus, L, A, row, '\t', at);
+      for (uint32_t c = 0; c < K; c++) {
+        double st[6];
+        const int have = bvcf_assoc_stat(ai.recs + n_rows * K + c, R.pheno_table.totals + c, st);
+        if (have < 0) return BVCF_E_FATAL;
+        o.append(locus);
+        o.push_back('\t');
+        o.append(names[c]);
+        o.push_back('\t');
+        append_ll(o, (long long)st[0]);
+        o.push_back('\t');
+        if (have & 1)
+          put(st[1]);
+        else
+          o.append(empty);
+        for (int q = 2; q < 6; q++) {
+          o.push_back('\t');
+          if (have & 2)
+            put(st[q]);
+          else
+            o.append(empty);
+        }
+        o.push_back('\n');
+        if (have & 2) R.assoc_tested++;
+      }
+      n_rows++;
+    }
+    if (o.size() >= (4u << 20)) {
+      if (write_all(R.assoc_fd, o.data(), o.size())) return BVCF_E_IO;
+      o.clear();
+    }
+  }
+  if (n_rows != ai.n_rows) return BVCF_E_FATAL;  // (the device's rows are the batch's)
+  R.assoc_rows += n_rows;
+  return BVCF_OK;
+}
+
+int close_assoc(Run &R, bool ok, std::string *msg) {
+  if (R.assoc_fd < 0) return BVCF_OK;
+  bool bad = false;
+  if (ok) {
+    bad = write_all(R.assoc_fd, R.assoc_buf.data(), R.assoc_buf.size()) != 0;
+    if (!bad && R.assoc_report_fd >= 0) {
+      const std::string rep = "columns\t" + std::to_string(R.pheno_table.n_columns) + "\nsamples\t" + std::to_string(R.pheno_table.n_named) +
+                              "\nrows\t" + std::to_string(R.assoc_rows) + "\ntested\t" + std::to_string(R.assoc_tested) + "\n";
+      bad = write_all(R.assoc_report_fd, rep.data(), rep.size()) != 0;
+    }
+  } else {
+    (void)ftruncate(R.assoc_fd, 0);  // (outputs are a successful run's only)
+  }
+  R.assoc_buf.clear();
+  int saved = errno;
+  for (int *fd : {&R.assoc_fd, &R.assoc_report_fd}) {
+    if (*fd >= 0 && close(*fd) && !bad) {
+      bad = true;
+      saved = errno;
+    }
+    *fd = -1;
+  }
+  if (bad && ok) {
+    *msg = std::string("assoc: write failed: ") + strerror(saved);
     return BVCF_E_IO;
   }
   return BVCF_OK;

@@ -10,6 +10,7 @@
 #include "bvcf_bgzf.h"
 #include "bvcf_grm_q.h"
 #include "bvcf_score_q.h"
+#include "bvcf_assoc_q.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -272,12 +273,21 @@ struct Run {
   bool score_on = false;
   bvcf_score_table score_table{};
   int score_fd = -1, score_report_fd = -1;
+  // --pheno / --assoc / --assocReport: open_assoc opens the outputs before any device work; prepare_run reads the phenotype
+  // file against the (kept) names into the run's one table (load_pheno); create_ctx uploads it to every ctx; append_assoc
+  // writes a batch's lines in input order; close_assoc writes the report -- or, after a failed run, empties the files
+  bool assoc_on = false;
+  bvcf_pheno_table pheno_table{};
+  int assoc_fd = -1, assoc_report_fd = -1;
+  uint64_t assoc_rows = 0, assoc_tested = 0;
+  std::string assoc_buf;
   ~Run() {
     for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
-                   grm_n_fd, grm_id_fd, score_fd, score_report_fd})
+                   grm_n_fd, grm_id_fd, score_fd, score_report_fd, assoc_fd, assoc_report_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
     bvcf_score_table_free(&score_table);
+    bvcf_pheno_table_free(&pheno_table);
     bvcf_variant_table_free(&variant_table);
     bvcf_region_table_free(&region_table);
   }
@@ -325,6 +335,7 @@ int close_dosage(Run &R);
 struct BatchNeed {
   uint64_t lines, alleles, cmap_bytes;                        // bvcf_result.need_*
   uint64_t bed_bytes, trio_events, ld_events, ld_row_bytes;  // bvcf_bed_rows / bvcf_trio_stats / bvcf_ld_stats
+  uint64_t assoc_rows;                                        // bvcf_assoc
 };
 BatchNeed read_batch_need(bvcf_ctx *ctx, const bvcf_config *c, const bvcf_result &res);
 int reserve_batch_need(bvcf_ctx *ctx, const BatchNeed &n);
@@ -433,6 +444,25 @@ void add_score_words(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns, s
 int write_score(Run &R, const uint64_t *sum, std::string *msg);
 // the words of a bvcf_score table over ns samples and k columns
 inline size_t score_table_words(size_t ns, size_t k) { return 2 * ns * k + 2 * ns + 1; }
+// --pheno / --assoc / --assocReport: the bvcf_config_assoc of a config that reaches up to it (the tenth marker); NULL otherwise
+inline const bvcf_config_assoc *assoc_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_ASSOC) ? reinterpret_cast<const bvcf_config_assoc *>(c)
+                                                                                           : nullptr;
+}
+// true when the run scans (every ctx of the run then gets bvcf_set_pheno_table)
+inline bool wants_assoc(const bvcf_config *c) {
+  const bvcf_config_assoc *a = assoc_config(c);
+  return a && a->pheno_path && *a->pheno_path && a->assoc_path && *a->assoc_path;
+}
+// the outputs opened (truncated) -- BVCF_E_ARG for a path without its partner, BVCF_E_IO for an output, one message in *msg;
+// the phenotype file read and matched against the (kept) names (prepare_run) -- BVCF_E_FATAL with one message that names the
+// line; the lines of one collected batch (ai = what bvcf_assoc gave for it) written -- BVCF_E_FATAL when the device's row
+// count is not the batch's, BVCF_E_IO when the write fails; the report written and the files closed (ok: the run succeeded;
+// otherwise both files are left empty)
+int open_assoc(Run &R, std::string *msg);
+int load_pheno(Run &R, std::string *msg);
+int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai);
+int close_assoc(Run &R, bool ok, std::string *msg);
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

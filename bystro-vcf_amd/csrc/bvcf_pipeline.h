@@ -184,6 +184,7 @@ struct FmtJob {
   bvcf_bed_rows_info bed{};  // --plinkOutput: bvcf_bed_rows of the batch (valid as long as res)
   bvcf_trio_info trio{};     // --mendel / --mendelErrors: bvcf_trio_stats of the batch (likewise)
   bvcf_ld_info ld{};         // --ld / --ldPrune: bvcf_ld_stats of the batch (likewise)
+  bvcf_assoc_info assoc{};   // --pheno / --assoc: bvcf_assoc of the batch (likewise)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };
@@ -305,6 +306,7 @@ class Driver {
   std::atomic<bool> plink_failed_{false};  // --plinkOutput: likewise
   std::atomic<bool> mendel_failed_{false};  // --mendel / --mendelErrors: likewise
   std::atomic<bool> ld_failed_{false};      // --ld / --ldPrune: likewise
+  std::atomic<bool> assoc_failed_{false};   // --pheno / --assoc: likewise
   // stream mode
   std::string source_err_;
   std::unique_ptr<Channel<Block>> ready_q_;

@@ -69,6 +69,9 @@ struct Cli {
   // extension: --score FILE --scoreOutput PATH [--scoreReport PATH], per-sample scores of the run's rows from a table of
   // locus weights -- a polygenic score, PC loadings -- in exact fixed point (the dense rows on the device's matrix cores)
   std::string score, score_output, score_report;
+  // extension: --pheno FILE --assoc PATH [--assocReport PATH], every row of the run against the file's phenotypes: the
+  // additive score test / Cochran-Armitage trend test from exact integer sums (the dense rows on the device's matrix cores)
+  std::string pheno, assoc, assoc_report;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -166,7 +169,8 @@ int parse(int argc, char **argv, Cli &c) {
         name == "plinkOutput" || name == "mendel" || name == "mendelErrors" || name == "ld" || name == "ldPrune" || name == "ldWindow" ||
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
         name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
-        name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport") {
+        name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport" || name == "pheno" || name == "assoc" ||
+        name == "assocReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -198,6 +202,12 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         (name == "score" ? c.score : name == "scoreOutput" ? c.score_output : c.score_report) = val;
+      } else if (name == "pheno" || name == "assoc" || name == "assocReport") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to %s\n", name.c_str(), name == "pheno" ? "read" : "write");
+          return 2;
+        }
+        (name == "pheno" ? c.pheno : name == "assoc" ? c.assoc : c.assoc_report) = val;
       } else if (name == "mendel" || name == "mendelErrors") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to write\n", name.c_str());
@@ -295,6 +305,14 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-scoreReport needs -score and -scoreOutput\n");
     return 2;
   }
+  if (c.pheno.empty() != c.assoc.empty()) {
+    fprintf(stderr, "-pheno and -assoc come together\n");
+    return 2;
+  }
+  if (!c.assoc_report.empty() && c.pheno.empty()) {
+    fprintf(stderr, "-assocReport needs -pheno and -assoc\n");
+    return 2;
+  }
   if ((!c.mendel.empty() || !c.mendel_errors.empty()) && c.fam.empty()) {
     fprintf(stderr, "-mendel and -mendelErrors need the pedigree: -fam PATH\n");
     return 2;
@@ -330,10 +348,11 @@ int main(int argc, char **argv) {
   }
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
   // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so are --variantFilterReport and
-  // --regionFilterReport alone; --grm alone: a GRM-only pass; --score with --scoreOutput alone: a scoring-only pass)
+  // --regionFilterReport alone; --grm alone: a GRM-only pass; --score with --scoreOutput alone: a scoring-only pass;
+  // --pheno with --assoc alone: a scan-only pass)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
       c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
-      c.variant_report.empty() && c.region_report.empty() && c.grm.empty() && c.score.empty()) {
+      c.variant_report.empty() && c.region_report.empty() && c.grm.empty() && c.score.empty() && c.pheno.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -348,9 +367,11 @@ int main(int argc, char **argv) {
   // (bvcf_config and, behind it, the --relatedness path, the site gate and its report, the PLINK prefix; behind those the
   // pedigree and the two --mendel paths)
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
-  // regions and their report; behind those the --grm prefix; behind that the --score paths)
-  bvcf_config_score score_cfg;
-  bvcf_config_score_defaults(&score_cfg);
+  // regions and their report; behind those the --grm prefix; behind that the --score paths; behind those the --pheno / --assoc
+  // paths)
+  bvcf_config_assoc assoc_cfg;
+  bvcf_config_assoc_defaults(&assoc_cfg);
+  bvcf_config_score &score_cfg = assoc_cfg.score;
   bvcf_config_grm &grm_cfg = score_cfg.grm;
   bvcf_config_regions &rc_cfg = grm_cfg.regions;
   bvcf_config_variants &vc = rc_cfg.variants;
@@ -433,6 +454,9 @@ int main(int argc, char **argv) {
   score_cfg.score_path = c.score.c_str();
   score_cfg.score_output_path = c.score_output.c_str();
   score_cfg.score_report_path = c.score_report.c_str();
+  assoc_cfg.pheno_path = c.pheno.c_str();
+  assoc_cfg.assoc_path = c.assoc.c_str();
+  assoc_cfg.assoc_report_path = c.assoc_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

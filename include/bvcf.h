@@ -490,6 +490,79 @@ void bvcf_score_table_free(bvcf_score_table *t);
 int64_t bvcf_score_table_find(const bvcf_score_table *t, const char *s, size_t n);
 int bvcf_set_score_table(bvcf_ctx *ctx, const bvcf_score_table *t);
 int bvcf_score(bvcf_ctx *ctx, uint64_t *out /* 2 * S * K + 2 * S + 1 */, int reset);
+/* A per-row association scan over the same rows: every row against up to 16 phenotypes, summed on the device from the
+ * class maps (which the ctx then makes even when want_class_maps is 0, without copying them to the host).  A phenotype k
+ * gives sample i a flag P_i (1: present) and an integer Y_i, the value in units of 10^-6, |Y| <= 10^12 (Y = 0 where P = 0).
+ * A sample's class in a row is ref, het, hom (a haploid call included) or missing; g = 0, 1, 2.  Per (row, phenotype) the
+ * device sums, exactly, over the samples of class c in {het, hom, missing}:
+ *   N_c = sum P_i     A_c = sum Y_i     and B_mis = sum Y_i^2 over the missing ones (128 bits)
+ * -- a bvcf_assoc_rec, 56 bytes.  A row whose record has no usable class map (cmap_off == BVCF_NO_CMAP) counts as bvcf_bed_rows
+ * packs it: every sample missing.  The dense rows are multiplied on the matrix cores (int8 limbs, int32 sums), the short
+ * lists added per list; every record has one writer: the words are a property of the data.
+ * With the phenotype's totals NP = sum P, AY = sum Y, BY = sum Y^2 (bvcf_pheno_totals) the host derives
+ *   n = NP - N_mis   Sy = AY - A_mis   Syy = BY - B_mis   Sg = N_het + 2 N_hom   Sgg = N_het + 4 N_hom   Sgy = A_het + 2 A_hom
+ *   c = n Sgy - Sg Sy   va = n Sgg - Sg^2   vb = n Syy - Sy^2          (exact, 128 bits)
+ * and, with dc, dva, dvb the correctly rounded doubles of the three, by this sequence of IEEE double operations and nothing
+ * else (no multiply-add contracted):
+ *   r2 = min(1.0, (dc / dva) * (dc / dvb))   chisq = (double)n * r2   beta = dc / dva / 1e6
+ *   se = sqrt((dvb / dva) * (1.0 - r2) / (double)(n - 2)) / 1e6   p = erfc(sqrt(chisq / 2.0)), libm's erfc
+ * For a 0/1 trait chisq is the Cochran-Armitage trend test, for a quantitative one the score test of the additive model;
+ * beta is per ALT allele in the phenotype's units.
+ * bvcf_pheno_table_build: k columns over s samples from y[c * s + i] and present[c * s + i] (0 / 1; y is taken as 0 where
+ * present is 0); names = k NUL-terminated column names back to back (kept for the caller, may be NULL with names_bytes 0);
+ * n_named is kept for the caller.  BVCF_E_ARG for k outside 1 .. 16 or |Y| > 10^12, BVCF_E_TOO_BIG for s > 2^22.  The table
+ * holds operand B of the product: int8 b[n_cols][s64], s64 = s rounded up to 64, zero past s and wherever P = 0 -- per
+ * column P and the l1 (1 .. 6) balanced base-256 digits of Y, least significant first, then per column the l2 (1 .. 11) digits
+ * of Y^2; l1 and l2 are the smallest counts that hold the table's values; n_cols = k (1 + l1 + l2).
+ * bvcf_pheno_table_parse: the table of a phenotype file's text by the file's rules (bvcf_config_assoc.pheno_path) against
+ * the s sample names (bytes, compared whole); a refusal leaves one message that names the line in err.
+ * bvcf_set_pheno_table uploads a built table to a ctx (one table serves every ctx of a run) and allocates a record arena
+ * [rows][k] per slot with its pinned copy: BVCF_E_ARG when the table's samples are not the ctx's, BVCF_E_TOO_BIG with a message,
+ * before anything is allocated, when a slot's arena would pass 1 GiB (fewer columns, or smaller batches: max_batch_bytes).
+ * Call once, before the first submit; BVCF_E_BUSY with batches in flight; on a ctx without sample columns nothing is
+ * allocated or launched.  bvcf_params and the ABI version do not change with it.
+ * A batch whose rows outrun the arena comes back BVCF_E_CAPACITY with nothing written and need_rows reported;
+ * bvcf_reserve_assoc_rows grows the arena to `rows` rows with nothing in flight (BVCF_E_TOO_BIG past 1 GiB), and the batch
+ * is submitted again.  bvcf_assoc: the batch collected last -- recs[r * n_columns + k] for row r in output order, valid
+ * until that slot's next collect as bvcf_result's arrays are.
+ * bvcf_assoc_stat: pure host code; out = {n, altFreq = Sg / (2 n), beta, se, chisq, p}.  Returns bit 0: altFreq is there
+ * (n > 0); bit 1: beta, se, chisq and p are there (n >= 3, va != 0, vb != 0); what is not there is 0.  -1 for NULL. */
+typedef struct {
+  uint64_t np;            /* samples with the phenotype */
+  int64_t ay;             /* sum Y */
+  uint64_t by_lo, by_hi;  /* sum Y^2 */
+} bvcf_pheno_totals;
+typedef struct {
+  uint32_t n_columns, n_samples, s64;
+  uint32_t l1, l2, n_cols;
+  uint64_t n_named;                /* the (kept) samples the file names */
+  const int8_t *b;                 /* [n_cols][s64] */
+  const int64_t *y;                /* [n_columns][n_samples] */
+  const uint8_t *present;          /* [n_columns][n_samples] */
+  const bvcf_pheno_totals *totals; /* [n_columns] */
+  const char *names;               /* n_columns NUL-terminated names */
+  uint64_t names_bytes;
+} bvcf_pheno_table;
+typedef struct {
+  uint32_t n_het, n_hom, n_mis, pad;
+  int64_t a_het, a_hom, a_mis;
+  uint64_t b_mis_lo, b_mis_hi;
+} bvcf_assoc_rec;
+typedef struct {
+  const bvcf_assoc_rec *recs; /* [n_rows][n_columns] */
+  uint64_t n_rows;
+  uint64_t need_rows;
+  uint32_t n_columns;
+} bvcf_assoc_info;
+int bvcf_pheno_table_build(const int64_t *y, const uint8_t *present, uint32_t k, uint32_t s, const char *names, size_t names_bytes,
+                           uint64_t n_named, bvcf_pheno_table *out);
+int bvcf_pheno_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
+                           bvcf_pheno_table *out, char *err, size_t err_cap);
+void bvcf_pheno_table_free(bvcf_pheno_table *t);
+int bvcf_set_pheno_table(bvcf_ctx *ctx, const bvcf_pheno_table *t);
+int bvcf_reserve_assoc_rows(bvcf_ctx *ctx, uint64_t rows);
+int bvcf_assoc(bvcf_ctx *ctx, bvcf_assoc_info *out);
+int bvcf_assoc_stat(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, double out[6]);
 /* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
  * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
  * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
@@ -1034,6 +1107,39 @@ typedef struct {
 } bvcf_config_score;
 /* the whole struct: bvcf_config_grm_defaults, base.reserved[1] = BVCF_CONFIG_MORE_SCORE, no scores */
 void bvcf_config_score_defaults(bvcf_config_score *c);
+/* Likewise what came after bvcf_config_score: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_ASSOC.  bvcf_config_assoc_defaults sets that; the nine older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_ASSOC 9
+typedef struct {
+  bvcf_config_score score;
+  /* --pheno FILE with --assoc PATH: every row of the run against the file's phenotypes, from the bvcf_assoc records of the
+   * run's batches.  The phenotype file: lines end in '\n', a trailing '\r' is dropped, empty lines are ignored.  The first
+   * non-empty line may be a header "#sample \t name1 \t ... \t nameK" (names non-empty and distinct; without one the names
+   * are PHENO1 .. PHENOK); every other line is "sample \t v1 \t ... \t vK" with the K of the first non-empty line, 1 <= K <=
+   * 16.  sample is compared byte for byte with the (kept) sample names as sample_list_path writes them, as fam_path's are: a
+   * line whose name is no (kept) sample is ignored, a (kept) sample the file does not name has every phenotype missing.  A
+   * value is the two bytes NA (missing) or at most 64 bytes of [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D{1,3})?; its value is the
+   * rational the text denotes, |y| <= 10^6, Y the integer nearest to y 10^6 (ties away from zero, decided on the digits).  A
+   * binary trait is the numbers 0 and 1.  A '#' line behind the first, a wrong field count, an empty name, a name that is a
+   * (kept) sample on two lines, a name that matches more than one sample column, a bad value, an unreadable file, no non-empty
+   * line, K > 16, more than 2^22 (kept) samples: BVCF_E_FATAL with one message that names the line, before any device work.  A
+   * header alone is valid: nobody has a phenotype.
+   * assoc_path: "chrom pos ref alt pheno n altFreq beta se chisq p", tab-separated, then a line per (row, phenotype) -- rows in
+   * TSV order, phenotypes in column order within a row: the row's four TSV columns byte for byte, the phenotype's name, n in
+   * decimal, altFreq = Sg / (2 n) and the four statistics as the TSV's ratios are printed ("%.3G"; a zero prints "0").
+   * altFreq is empty_field when n = 0; beta, se, chisq and p are empty_field when n < 3, va = 0 or vb = 0.  A file without
+   * sample columns gives the header line alone.
+   * assoc_report_path (only with the other two): "columns", "samples" (the kept samples the file names), "rows", "tested" (the
+   * lines with a statistic), each "name \t count \n".
+   * The outputs are opened before any device work and hold a successful run's lines only (a failed run leaves them empty).
+   * The rows are the rows sample_stats_path counts; the bytes do not depend on devices, batch size or input kind, and no
+   * other output changes with them.  pheno_path and assoc_path come together (BVCF_E_ARG otherwise).  NULL or "" = off */
+  const char *pheno_path;
+  const char *assoc_path;
+  const char *assoc_report_path;
+} bvcf_config_assoc;
+/* the whole struct: bvcf_config_score_defaults, base.reserved[1] = BVCF_CONFIG_MORE_ASSOC, no scan */
+void bvcf_config_assoc_defaults(bvcf_config_assoc *c);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

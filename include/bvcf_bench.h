@@ -52,6 +52,12 @@ int bvcf_bench_grm_kernels(bvcf_ctx *ctx, float ms[4]);
  * BVCF_E_ARG on a ctx without score tables or without a bench call before */
 int bvcf_bench_score_kernels(bvcf_ctx *ctx, float ms[4]);
 
+/* bvcf_set_pheno_table: the row index and the scan's kernels once more over what the last bvcf_bench_device* chain of the
+ * ctx's first slot left (its records and class maps), with HIP events around each step: ms = {k_assoc_list, k_assoc_gemm,
+ * k_assoc_sparse}.  BVCF_E_ARG on a ctx without a phenotype table or without a bench call before; BVCF_E_CAPACITY when the
+ * block's rows outrun the arena (bvcf_reserve_assoc_rows) */
+int bvcf_bench_assoc_kernels(bvcf_ctx *ctx, float ms[3]);
+
 /* The exact Hardy-Weinberg test as the site gate runs it on the device: triples = n x {het, hom, other}, p[j] the p value of
  * triple j -- by the thread-per-row recurrence or by a wave (k_site_hwe's code), chosen by the length of the support as
  * k_site_gate chooses.  Needs no ctx */

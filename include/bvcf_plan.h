@@ -197,6 +197,16 @@ int bvcf_score_weight(const char *text, size_t n, int64_t *out);
 int bvcf_score_limbs(int64_t w, int8_t out[8]);
 size_t bvcf_score_decimal(uint64_t lo, uint64_t hi, char out[48]);
 
+/* The arithmetic behind bvcf_set_pheno_table -- csrc/bvcf_assoc_q.h -- run on the host.  bvcf_assoc_value: text[0, n) by the
+ * value grammar of bvcf_config_assoc -> *out = Y, the integer nearest to y 10^6, ties away from zero; 0, -1 for text that is
+ * no value, -2 for |y| > 10^6.  bvcf_assoc_limbs: the 128-bit two's complement integer (hi, lo) as sixteen balanced base-256
+ * digits (v = sum out[a] 256^a, out[a] in [-128, 127]); returns the smallest count that holds v (1 for 0).  bvcf_assoc_ints:
+ * the integers of a record against its phenotype's totals, out = {n, Sg, c lo, c hi, va lo, va hi, vb lo, vb hi} (two's
+ * complement words); 0, -1 for NULL. */
+int bvcf_assoc_value(const char *text, size_t n, int64_t *out);
+int bvcf_assoc_limbs(uint64_t lo, uint64_t hi, int8_t out[16]);
+int bvcf_assoc_ints(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, uint64_t out[8]);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */

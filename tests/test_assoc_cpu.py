@@ -1,0 +1,422 @@
+"""--pheno / --assoc without a device: the value grammar and its rounding, the limbs of Y and Y^2, the phenotype file's rules,
+the integers c / va / vb and the statistic agree with the definition written in Python (assoc.py); the structs match the
+header; the CLI refuses what it must; the GPU tests' inputs reach every case; and bvcf_assoc_q.h -- the arithmetic the kernels,
+the table builder and the writer share -- runs clean in a stand-alone program under the address and undefined-behaviour
+sanitizers."""
+import ctypes as C
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import assoc
+import grm
+import oracle_lib as orc
+import pairtable as pt
+import variantlist as vl
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "bystro-vcf_amd", "csrc")
+EXE = os.path.join(ROOT, "bystro-vcf_amd", "bystro-vcf")
+HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+
+
+@pytest.fixture(scope="module")
+def bv():
+    import bystro_vcf_amd as b
+    return b
+
+
+def both(bv, text):
+    """(reference, library): ("ok", Y) / ("bad",) / ("big",)"""
+    out = []
+    for fn in (assoc.value, bv.assoc_value):
+        try:
+            out.append(("ok", fn(text)))
+        except ValueError:
+            out.append(("bad",))
+        except OverflowError:
+            out.append(("big",))
+    return tuple(out)
+
+
+# ---- a value
+
+WORKED = [(b"0.0000005", 1), (b"-0.0000005", -1), (b"4.9999e-7", 0), (b"1e6", 10 ** 12), (b"-1E+6", -10 ** 12), (b"0", 0), (b"-0", 0),
+          (b"+.5", 5 * 10 ** 5), (b"5.", 5 * 10 ** 6), (b"1.5e-6", 2), (b"2.5e-6", 3), (b"-2.5e-6", -3), (b"0.4999995", 5 * 10 ** 5),
+          (b"0.49999949999", 499999), (b"1e-999", 0), (b"0e999", 0), (b"1", 10 ** 6), (b"0001.50", 15 * 10 ** 5),
+          (b"999999.9999995", 10 ** 12), (b"1000000.000000", 10 ** 12), (b"1e-6", 1), (b"12345678.9e-2", 123456789000),
+          (b"000000000000000000000000000000000000000000000000000000000001.5", 15 * 10 ** 5)]
+REFUSED_BIG = [b"1000000.0000001", b"1000000.000000000000000001", b"1000000.5", b"1e7", b"1e999", b"-1000001", b"9" * 64, b"-1000000.1"]
+REFUSED_BAD = [b"", b".", b"+", b"-", b"e5", b"1e", b"1e+", b"1e1234", b" 1", b"1 ", b"nan", b"inf", b"-inf", b"0x10", b"1,5", b"1..5",
+               b"1e5.0", b"--1", b"1_0", b"1" * 65, b"0." + b"0" * 63, b"\t1", b"na", b"NaN"]
+
+
+def seeded_texts(n, seed):
+    rng = random.Random(seed)
+    out = []
+    for _ in range(n):
+        ip = "".join(rng.choice("0123456789") for _ in range(rng.randint(0, 8)))
+        fp = "".join(rng.choice("0123456789") for _ in range(rng.randint(0, 10)))
+        t = rng.choice(["", "+", "-"]) + ip + (("." + fp) if fp or rng.random() < 0.2 else "")
+        if rng.random() < 0.4:
+            t += rng.choice("eE") + rng.choice(["", "+", "-"]) + str(rng.randint(0, 9))
+        if rng.random() < 0.1:  # near a tie at the last kept digit
+            t = "%d.%06d5" % (rng.randint(0, 999), rng.randint(0, 999999)) + rng.choice(["", "0", "00001"])
+        out.append(t.encode())
+    return out
+
+
+def test_worked_cases_ties_and_bounds(bv):
+    for text, want in WORKED:
+        assert both(bv, text) == (("ok", want), ("ok", want)), text
+    for text in REFUSED_BIG:
+        assert both(bv, text) == (("big",), ("big",)), text
+    for text in REFUSED_BAD:
+        assert both(bv, text) == (("bad",), ("bad",)), text
+
+
+def test_parser_against_fractions(bv):
+    kinds = set()
+    for text in seeded_texts(4000, seed=3):
+        a, b = both(bv, text)
+        assert a == b, (text, a, b)
+        kinds.add(a[0])
+    assert kinds == {"ok", "bad", "big"}
+
+
+def test_limbs_of_y_and_y_squared_at_every_length(bv):
+    seen1, seen2 = set(), set()
+    rng = random.Random(8)
+    ys = [0, 1, -1, 127, 128, -128, -129, assoc.MAX_Y, -assoc.MAX_Y, assoc.MAX_Y - 1]
+    for bits in range(1, 41):
+        ys += [min(assoc.MAX_Y, (1 << bits) - 1), -min(assoc.MAX_Y, 1 << bits), rng.randint(0, min(assoc.MAX_Y, 1 << bits))]
+    for y in ys:
+        for v, seen in ((y, seen1), (y * y, seen2)):
+            got, n = bv.assoc_limbs(v)
+            assert got == assoc.limbs(v) and n == assoc.n_limbs(v), v
+            assert sum(d << (8 * a) for a, d in enumerate(got)) == v and all(-128 <= d <= 127 for d in got)
+            seen.add(n)
+    assert seen1 == set(range(1, 7)) and seen2 == set(range(1, 12))
+
+
+# ---- the file
+
+NAMES = [b"s1", b"s2", b"s3", b"dup", b"dup", b"s 6"]
+GOOD = b"#sample\tbmi\tcase\r\ns2\t21.5\t1\n\nstranger\t1\t1\ns1\tNA\t0\r\ns 6\t-3e2\tNA\n"
+BAD_FILES = [(b"", 0), (b"\n\r\n", 0), (b"s1\t1\n#sample\ta\n", 2), (b"#sample\ta\n#x\t1\n", 2), (b"s1\t1\t2\ns2\t1\n", 2), (b"s1\t1\ns2\t1\t2\n", 2),
+             (b"s1\n", 1), (b"#sample\ta\n\t1\n", 2), (b"s1\t1\ns2\t2\ns1\t3\n", 3), (b"s1\t1\ndup\t2\n", 2), (b"s1\t1\ns2\tx\n", 2),
+             (b"s1\t1\nstranger\t1e7\n", 2), (b"s1\t1000000.0000001\n", 1), (b"s1\tna\n", 1), (b"s1\t\n", 1), (b"#sample\ta\ta\n", 1),
+             (b"#sample\t\n", 1), (b"#locus\ta\n", 1), (b"s1" + b"\t1" * 17 + b"\n", 1), (b"#sample" + b"".join(b"\tc%d" % i for i in range(17)) + b"\n", 1)]
+
+
+def test_file_rules(bv):
+    for text in (GOOD, b"s3\t0.5\n", b"#sample\tx\n", b"stranger\t1\tNA\n", b"s1" + b"\t1" * 16 + b"\n"):
+        names, Y, P, n_named = assoc.parse_file(text, NAMES)
+        t = bv.PhenoTable(text=text, sample_names=NAMES)
+        assert t.names == names and t.n_named == n_named and (t.n_columns, t.n_samples, t.s64) == (len(names), 6, 64)
+        assert t.y.tolist() == Y and t.present.tolist() == P
+        assert t.totals == assoc.totals(Y, P)
+        t.close()
+    names, Y, P, n_named = assoc.parse_file(GOOD, NAMES)
+    assert names == [b"bmi", b"case"] and n_named == 3
+    assert Y == [[0, 21500000, 0, 0, 0, -300000000], [0, 10 ** 6, 0, 0, 0, 0]] and P == [[0, 1, 0, 0, 0, 1], [1, 1, 0, 0, 0, 0]]
+    names, Y, P, n_named = assoc.parse_file(b"#sample\tx\n", NAMES)  # a header alone: nobody has a phenotype
+    assert n_named == 0 and not any(P[0])
+
+
+@pytest.mark.parametrize("text,line", BAD_FILES)
+def test_file_errors_name_their_line(bv, text, line):
+    with pytest.raises(assoc.PhenoFileError) as ei:
+        assoc.parse_file(text, NAMES)
+    assert ei.value.line == line
+    with pytest.raises(bv.BvcfError) as ei:
+        bv.PhenoTable(text=text, sample_names=NAMES)
+    assert ("line %d:" % line in str(ei.value)) == bool(line), str(ei.value)
+
+
+def test_operand_b(bv):
+    """int8 [n_cols][S64]: per column P and the limbs of Y, then per column the limbs of Y^2; zero past S and where P = 0;
+    L1 and L2 the smallest counts that hold the file's values"""
+    rng = random.Random(21)
+    for S, big, want in ((70, False, None), (130, True, (6, 11)), (1, False, None), (64, True, (6, 11))):
+        K = 3
+        Y = [[rng.randint(-assoc.MAX_Y, assoc.MAX_Y) if big else rng.randint(-300, 300) for _ in range(S)] for _ in range(K)]
+        if big:
+            Y[1][0] = assoc.MAX_Y
+        P = [[int(rng.random() < 0.8) for _ in range(S)] for _ in range(K)]
+        P[1][0] = 1
+        t = bv.PhenoTable(Y, P)
+        l1 = max([1] + [assoc.n_limbs(y) for ys, ps in zip(Y, P) for y, p in zip(ys, ps) if p])
+        l2 = max([1] + [assoc.n_limbs(y * y) for ys, ps in zip(Y, P) for y, p in zip(ys, ps) if p])
+        assert (t.l1, t.l2) == (l1, l2) and (want is None or (l1, l2) == want)
+        assert t.n_cols == K * (1 + l1 + l2) and t.s64 == (S + 63) // 64 * 64
+        b = t.b
+        assert not b[:, S:].any()
+        for k in range(K):
+            for i in range(S):
+                col = b[:, i].tolist()
+                py = col[k * (1 + l1):(k + 1) * (1 + l1)]
+                q = col[K * (1 + l1) + k * l2:K * (1 + l1) + (k + 1) * l2]
+                if P[k][i]:
+                    assert py == [1] + assoc.limbs(Y[k][i], l1) and q == assoc.limbs(Y[k][i] ** 2, l2)
+                else:
+                    assert not any(py) and not any(q)
+        assert t.y.tolist() == [[y if p else 0 for y, p in zip(ys, ps)] for ys, ps in zip(Y, P)]
+        t.close()
+    with pytest.raises(bv.BvcfError):
+        bv.PhenoTable([[assoc.MAX_Y + 1]], [[1]])
+    with pytest.raises(bv.BvcfError):
+        bv.PhenoTable([[0]] * 17, [[1]] * 17)
+    t = bv.PhenoTable([[1]] * 16, [[1]] * 16)
+    t.close()
+
+
+# ---- the integers and the statistic
+
+def seeded_records(n, seed):
+    """(record, totals) pairs that a cohort could give: classes dealt to S samples with phenotypes of mixed size"""
+    rng = random.Random(seed)
+    out = []
+    for q in range(n):
+        S = rng.choice([3, 4, 10, 100, 1000])
+        scale = rng.choice([1, 10 ** 3, 10 ** 6, assoc.MAX_Y])
+        binary = rng.random() < 0.3
+        ys = [rng.choice([0, assoc.ONE]) if binary else rng.randint(-scale, scale) for _ in range(S)]
+        ps = [int(rng.random() < 0.9) for _ in range(S)]
+        ys = [y if p else 0 for y, p in zip(ys, ps)]
+        w = rng.choice([(6, 3, 1, 0), (1, 1, 1, 1), (0, 0, 1, 0), (1, 0, 0, 0), (5, 1, 0, 4)])
+        cls = rng.choices([0, 1, 2, 3], weights=w, k=S)
+        if q % 7 == 0:  # g a linear function of y: r2 = 1 up to rounding
+            order = sorted(range(S), key=lambda i: ys[i])
+            for rank, i in enumerate(order):
+                cls[i] = 0 if rank < S // 2 else 2
+            ys = [0 if c == 0 else assoc.ONE for c in cls]
+            ps = [1] * S
+        rec = [0] * 7
+        for c, y, p in zip(cls, ys, ps):
+            if c and p:
+                rec[c - 1] += 1
+                rec[c + 2] += y
+                if c == 3:
+                    rec[6] += y * y
+        out.append((tuple(rec), (sum(ps), sum(ys), sum(y * y for y in ys))))
+    return out
+
+
+def bound_records():
+    """S = 2^22 samples at |Y| = 10^12: the largest c and vb"""
+    S, Ymax = assoc.MAX_SAMPLES, assoc.MAX_Y
+    h = S // 2
+    return [((0, h, 0, 0, h * Ymax, 0, 0), (S, h * Ymax - h * Ymax, S * Ymax * Ymax)),     # hom carry +Y, the rest -Y
+            ((0, h, 0, 0, -h * Ymax, 0, 0), (S, 0, S * Ymax * Ymax)),
+            ((h, 0, 0, h * Ymax, 0, 0, 0), (S, S * Ymax, S * Ymax * Ymax)),                # a constant column: vb = 0
+            ((1, 1, S - 3, Ymax, -Ymax, 0, (S - 3) * Ymax * Ymax), (S, 0, (S - 1) * Ymax * Ymax)),
+            ((0, 0, S, 0, 0, S * Ymax, S * Ymax * Ymax), (S, S * Ymax, S * Ymax * Ymax))]  # everybody missing: n = 0
+
+
+def test_integers_against_python_at_the_bounds(bv):
+    big_c = big_vb = 0
+    for rec, tot in bound_records() + seeded_records(300, seed=31):
+        want = assoc.ints(rec, tot)
+        assert bv.assoc_ints(rec, tot) == want, (rec, tot)
+        big_c, big_vb = max(big_c, abs(want[2])), max(big_vb, want[4])
+        assert abs(want[2]) < 1 << 86 and 0 <= want[4] < 1 << 125
+    # (half the cohort hom with +Y against the rest with -Y: c = S^2 Y, a little under 2^84; vb = S^2 Y^2 > 2^123)
+    assert big_c > 1 << 83 and big_vb > 1 << 123
+
+
+def fmt(x):
+    return float(x).hex()
+
+
+def test_statistic_against_the_model(bv):
+    clamped = underflow = tested = untested = 0
+    cases = bound_records() + seeded_records(600, seed=32)
+    # n = 1000, g = 2 * y exactly: p underflows to 0
+    cases.append(((0, 500, 0, 0, 500 * assoc.ONE, 0, 0), (1000, 500 * assoc.ONE, 500 * assoc.ONE ** 2)))
+    for rec, tot in cases:
+        n, freq, st = assoc.stat(rec, tot)
+        flags, out = bv.assoc_stat(rec, tot)
+        assert out[0] == n and bool(flags & 1) == (freq is not None) and bool(flags & 2) == (st is not None)
+        if freq is not None:
+            assert fmt(out[1]) == fmt(freq)
+        if st is None:
+            untested += 1
+            assert out[2:] == [0.0] * 4
+            continue
+        tested += 1
+        assert [fmt(x) for x in out[2:]] == [fmt(x) for x in st], (rec, tot)
+        _, _, c, va, vb = assoc.ints(rec, tot)
+        clamped += (float(c) / float(va)) * (float(c) / float(vb)) > 1.0 or st[2] == float(n)
+        underflow += st[3] == 0.0
+    assert tested > 300 and untested > 20 and clamped > 0 and underflow > 0
+
+
+# ---- the header, the structs, the config
+
+def test_header_and_exports(bv):
+    hdr = open(os.path.join(ROOT, "include", "bvcf.h")).read()
+    for name in ("bvcf_pheno_table_build", "bvcf_pheno_table_parse", "bvcf_pheno_table_free", "bvcf_set_pheno_table",
+                 "bvcf_reserve_assoc_rows", "bvcf_assoc", "bvcf_assoc_stat", "bvcf_config_assoc_defaults"):
+        assert name + "(" in hdr and name in bv.EXPORTS
+        getattr(bv.lib, name)
+    assert "bvcf_bench_assoc_kernels" in bv.BENCH_EXPORTS
+    assert "#define BVCF_CONFIG_MORE_ASSOC 9" in hdr and bv.CONFIG_MORE_ASSOC == 9
+
+
+def test_layout_matches_header(bv, tmp_path):
+    src = tmp_path / "sizes.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "bvcf.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu\\n",'
+                   "sizeof(bvcf_assoc_rec),sizeof(bvcf_pheno_totals),sizeof(bvcf_pheno_table),sizeof(bvcf_assoc_info),"
+                   "sizeof(bvcf_config_assoc),offsetof(bvcf_config_assoc,pheno_path),offsetof(bvcf_assoc_rec,b_mis_lo));return 0;}\n")
+    exe = tmp_path / "sizes"
+    subprocess.check_call(["cc", "-o", str(exe), str(src), "-I", os.path.join(ROOT, "include")])
+    out = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
+    assert out == [bv.ASSOC_REC_DTYPE.itemsize, bv.PHENO_TOTALS_DTYPE.itemsize, C.sizeof(bv.PhenoTableStruct), C.sizeof(bv.AssocInfo),
+                   C.sizeof(bv.ConfigAssoc), bv.ConfigAssoc.pheno_path.offset, 40]
+    assert out[0] == 56
+
+
+def test_config_markers(bv):
+    c = bv.make_config({"score": "/w", "scoreOutput": "/o"})
+    assert list(c.reserved) == [bv.CONFIG_MORE, bv.CONFIG_MORE_SCORE]  # (the flags off: what the ninth marker wrote)
+    c = bv.make_config({"pheno": "/p", "assoc": "/a", "grm": "/g", "minMac": 3})
+    assert list(c.reserved) == [bv.CONFIG_MORE, bv.CONFIG_MORE_ASSOC]
+    a = C.cast(C.byref(c), C.POINTER(bv.ConfigAssoc)).contents
+    assert (a.pheno_path, a.assoc_path, a.assoc_report_path, a.score.score_path, a.score.grm.grm_prefix) == (b"/p", b"/a", None, None, b"/g")
+    d = bv.ConfigAssoc()
+    bv.lib.bvcf_config_assoc_defaults(C.byref(d))
+    base = d.score.grm.regions.variants.ld.trios.more.base
+    assert list(base.reserved) == [bv.CONFIG_MORE, bv.CONFIG_MORE_ASSOC] and d.pheno_path is None and d.assoc_path is None
+    s = bv.ConfigScore()
+    bv.lib.bvcf_config_score_defaults(C.byref(s))
+    assert list(s.grm.regions.variants.ld.trios.more.base.reserved) == [bv.CONFIG_MORE, bv.CONFIG_MORE_SCORE]
+
+
+# ---- the CLI, as far as it gets without a device
+
+def cli(args, stdin_bytes=b""):
+    return subprocess.run([EXE] + args, input=stdin_bytes, capture_output=True, timeout=60)
+
+
+@pytest.mark.parametrize("flag", ["pheno", "assoc", "assocReport"])
+def test_cli_flag_without_a_value(flag):
+    p = cli(["--" + flag])
+    assert p.returncode == 2 and p.stdout == b""
+    assert p.stderr == ("flag needs an argument: -%s\n" % flag).encode()
+    p = cli(["--%s=" % flag])
+    assert p.returncode == 2 and p.stdout == b"" and p.stderr.count(b"\n") == 1
+
+
+@pytest.mark.parametrize("args", [["--pheno", "f"], ["--assoc", "o"], ["--assocReport", "r"], ["--assocReport", "r", "--pheno", "f"]])
+def test_cli_flags_come_together(args):
+    p = cli(args, vl.rows_vcf(5))
+    assert p.returncode == 2 and p.stdout == b"" and p.stderr.count(b"\n") == 1
+
+
+def test_cli_unwritable_outputs(tmp_path):
+    """one message and exit code 1, before the input is looked at or a device asked for"""
+    f = tmp_path / "p.tsv"
+    f.write_bytes(b"s0\t1\n")
+    bad = tmp_path / "no_such_dir" / "x"
+    for extra in (["--assoc", str(bad)], ["--assoc", str(tmp_path / "o"), "--assocReport", str(bad)]):
+        p = cli(["--pheno", str(f)] + extra, vl.rows_vcf(5))
+        assert p.returncode == 1 and p.stdout == b""
+        assert p.stderr.count(b"\n") == 1 and str(bad).encode() in p.stderr
+
+
+# ---- the GPU tests' inputs, with the oracle alone
+
+def coverage(vcf, text, cfg=None):
+    """what an input's rows do against a phenotype file: (rows with many carriers, rows with few, rows with a missing call,
+    lines with a statistic, lines without, records)"""
+    recs, tots, out, rep, body, _ = assoc.expected(orc.run, vcf, text, cfg)
+    H, O, M = pt.matrices(body, pt.sample_names(vcf), cfg)
+    car = H + O + M
+    nbytes = np.array([len({i // 4 for i in np.flatnonzero(r)}) for r in car])
+    tested = int(rep.split(b"tested\t")[1])
+    return int((nbytes > 15).sum()), int((nbytes <= 15).sum()), int((M.sum(axis=1) > 0).sum()), tested, len(recs) * len(tots) - tested, recs
+
+
+def test_inputs_reach_every_case():
+    for seed, *_ in pt.FUZZ:
+        cfg = {"allow": ""} if seed % 2 else {"keepId": True, "keepInfo": True, "keepPos": True, "fieldDelimiter": ",", "emptyField": "NA"}
+        vcf = pt.fuzz_vcf(seed)
+        dense, short, miss, tested, untested, recs = coverage(vcf, assoc.pheno_for(vcf, 3, seed, big=bool(seed & 2)), cfg)
+        assert dense + short > 50 and miss > 0 and tested > 100, (seed, dense, short, miss, tested)
+        # every row and column gets different data
+        assert len({r for row in recs for r in row}) > len(recs)
+    vcf = pt.rare_vcf(300)
+    dense, short, miss, tested, untested, recs = coverage(vcf, assoc.pheno_for(vcf, 3, 610, big=True))
+    assert dense > 20 and short > 50 and miss > 0
+    vcf = pt.short_list_limit_vcf()
+    dense, short, miss, tested, untested, recs = coverage(vcf, assoc.pheno_for(vcf, 2, 620, big=True))
+    assert short >= 15 and miss >= 3
+    for n in assoc.DENSE_ROWS:
+        vcf = assoc.dense_vcf(n)
+        assert coverage(vcf, assoc.pheno_for(vcf, 2, n))[:2] == (n, 1)
+    # the special rows: va = 0, everybody missing, n = 2, a sample never called
+    vcf = assoc.special_vcf()
+    text = assoc.pheno_for(vcf, 2, 640, na=0, absent=0)
+    recs, tots, out, rep, body, _ = assoc.expected(orc.run, vcf, text)
+    st = [[assoc.stat(r, t) for r, t in zip(row, tots)] for row in recs]
+    ints = [[assoc.ints(r, t) for r, t in zip(row, tots)] for row in recs]
+    assert ints[0][0][3] == 0 and ints[0][0][0] > 3 and st[0][0][2] is None       # all hom: va = 0
+    assert ints[1][0][0] == 1 and st[1][0][2] is None                              # one called sample
+    assert ints[2][0][0] == 2 and st[2][0][1] is not None and st[2][0][2] is None  # n = 2
+    assert st[4][0][2] is not None
+    # B_mis passes 2^64
+    vcf = assoc.big_missing_vcf()
+    rows = [(nm.encode(), [assoc.MAX_Y]) for nm in pt.sample_names(vcf)]
+    recs = assoc.expected(orc.run, vcf, assoc.file_text(rows))[0]
+    assert recs[0][0][6] == 299 * 10 ** 24 and recs[0][0][6] >= 1 << 64
+    # 288 columns
+    assert 16 * (1 + assoc.n_limbs(assoc.MAX_Y) + assoc.n_limbs(assoc.MAX_Y ** 2)) == 288
+
+
+# ---- the shared header under sanitizers
+
+def test_arithmetic_header_alone_under_sanitizers(tmp_path):
+    """bvcf_assoc_q.h in a program of its own: every seeded value text against Python's exact definition, the limbs of Y and
+    Y^2, the integers at the bounds, the doubles and the statistic bit for bit"""
+    if os.path.exists("/dev/kfd"):
+        pytest.skip("GPU present: sanitized programs run on the build machine")
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not found")
+    exe = str(tmp_path / "assoc_check")
+    subprocess.check_call([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
+                           "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC, os.path.join(ROOT, "tests", "assoc_check.cpp"),
+                           "-o", exe], timeout=120)
+    texts = [t for t in seeded_texts(3000, seed=5) + [w for w, _ in WORKED] + REFUSED_BIG + REFUSED_BAD if b"\n" not in t]
+    (tmp_path / "v.txt").write_bytes(b"".join(t + b"\n" for t in texts))
+    cases = bound_records() + seeded_records(400, seed=33)
+    m64 = (1 << 64) - 1
+    (tmp_path / "r.txt").write_text("".join(" ".join(str(x) for x in list(rec[:6]) + [rec[6] & m64, rec[6] >> 64, tot[0], tot[1], tot[2] & m64,
+                                                                                      tot[2] >> 64]) + "\n" for rec, tot in cases))
+    p = subprocess.run([exe, str(tmp_path / "v.txt"), str(tmp_path / "r.txt")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    out = p.stdout.decode()
+    assert p.returncode == 0 and out.endswith("assoc_q ok\n"), out[-2000:]
+    assert "ERROR" not in out and "runtime error" not in out, out[-2000:]
+    lines = out.split("\n")[:-2]
+    want = []
+    for t in texts:
+        try:
+            y, rc = assoc.value(t), 0
+        except ValueError:
+            y, rc = 0, -1
+        except OverflowError:
+            y, rc = 0, -2
+        want.append(" ".join(str(x) for x in [rc, y, assoc.n_limbs(y), assoc.n_limbs(y * y)] + assoc.limbs(y, 6) + assoc.limbs(y * y, 11)))
+    for rec, tot in cases:
+        n, sg, c, va, vb = assoc.ints(rec, tot)
+        _, freq, st = assoc.stat(rec, tot)
+        have = (freq is not None) + 2 * (st is not None)
+        six = [float(n), freq or 0.0] + (list(st) if st else [0.0] * 4)
+        want.append(" ".join([str(n), str(sg), str(c), str(va), str(vb), str(have)] + [fmt(x) for x in six + [float(c), float(va), float(vb)]]))
+
+    def canon(line):  # (C's %a and float.hex() spell the same double differently)
+        return " ".join(fmt(float.fromhex(x)) if "x" in x or x in ("inf", "-inf") else x for x in line.split(" "))
+    assert [canon(x) for x in lines] == [canon(x) for x in want]
