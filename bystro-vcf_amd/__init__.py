@@ -51,7 +51,7 @@ BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_str
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
-                 "bvcf_bench_guard_check", "bvcf_bench_guarded_buffers"]
+                 "bvcf_bench_pca_eigen", "bvcf_bench_guard_check", "bvcf_bench_guarded_buffers"]
 
 # the partition logic of bvcf_run_fd, exported for host-only tests (include/bvcf_plan.h; not part of the drop-in ABI)
 PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text_range", "bvcf_find_bgzf_chain",
@@ -61,7 +61,7 @@ PLAN_EXPORTS = ["bvcf_plan_text_ranges", "bvcf_plan_bgzf_ranges", "bvcf_cut_text
                 "bvcf_ld_counts", "bvcf_ld_in_ld", "bvcf_parse_ld_r2", "bvcf_ld_seam_create", "bvcf_ld_seam_push",
                 "bvcf_ld_seam_read", "bvcf_ld_seam_rows", "bvcf_ld_seam_pairs", "bvcf_ld_seam_destroy",
                 "bvcf_score_weight", "bvcf_score_limbs", "bvcf_score_decimal",
-                "bvcf_assoc_value", "bvcf_assoc_limbs", "bvcf_assoc_ints"]
+                "bvcf_assoc_value", "bvcf_assoc_limbs", "bvcf_assoc_ints", "bvcf_pca_tridiag"]
 
 # every symbol include/bvcf.h declares
 EXPORTS = [
@@ -84,6 +84,7 @@ EXPORTS = [
     "bvcf_score", "bvcf_config_score_defaults",
     "bvcf_pheno_table_build", "bvcf_pheno_table_parse", "bvcf_pheno_table_free", "bvcf_set_pheno_table",
     "bvcf_reserve_assoc_rows", "bvcf_assoc", "bvcf_assoc_stat", "bvcf_config_assoc_defaults",
+    "bvcf_grm_matrix", "bvcf_pca_eigen", "bvcf_config_pca_defaults",
 ]
 
 
@@ -464,6 +465,17 @@ class PhenoTableStruct(C.Structure):
     _fields_ = [("n_columns", C.c_uint32), ("n_samples", C.c_uint32), ("s64", C.c_uint32), ("l1", C.c_uint32), ("l2", C.c_uint32),
                 ("n_cols", C.c_uint32), ("n_named", C.c_uint64), ("b", C.c_void_p), ("y", C.c_void_p), ("present", C.c_void_p),
                 ("totals", C.c_void_p), ("names", C.c_void_p), ("names_bytes", C.c_uint64)]
+
+
+CONFIG_MORE_PCA = 10  # BVCF_CONFIG_MORE_PCA in Config.reserved[1]: the ConfigAssoc is the head of a ConfigPca
+PCA_MAX_COMPONENTS = 64  # BVCF_PCA_MAX_COMPONENTS
+PCA_DEFAULT_COMPONENTS = 10  # BVCF_PCA_DEFAULT_COMPONENTS
+
+
+class ConfigPca(C.Structure):
+    """bvcf_config_pca: a bvcf_config_assoc and what came after it"""
+    _fields_ = [("assoc", ConfigAssoc), ("pca_prefix", C.c_char_p), ("pca_count", C.c_uint32), ("pca_reserved", C.c_uint32),
+                ("pca_report_path", C.c_char_p)]
 
 
 class AssocInfo(C.Structure):
@@ -929,7 +941,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--grm: the struct behind that one and its marker, only then)
     # (--score / --scoreOutput / --scoreReport: the struct behind that one and its marker, only then)
     # (--pheno / --assoc / --assocReport: the struct behind that one and its marker, only then)
-    ac = ConfigAssoc() if any(cfg.get(k) for k in ("pheno", "assoc", "assocReport")) else None
+    # (--pca / --pcaCount / --pcaReport: the struct behind that one and its marker, only then)
+    pc = ConfigPca() if any(cfg.get(k) for k in ("pca", "pcaCount", "pcaReport")) else None
+    ac = pc.assoc if pc is not None else ConfigAssoc() if any(cfg.get(k) for k in ("pheno", "assoc", "assocReport")) else None
     sc = ac.score if ac is not None else ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
     gc = sc.grm if sc is not None else ConfigGrm() if cfg.get("grm") else None
     rgc = gc.regions if gc is not None else ConfigRegions() if any(cfg.get(k) for k, _ in REGION_CONFIG_KEYS) else None
@@ -1043,8 +1057,70 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 keep.append(str(cfg[key]).encode())
                 setattr(ac, field, keep[-1])
         c.reserved[1] = CONFIG_MORE_ASSOC
+    if pc is not None:  # PREFIX.eigenvec / .eigenval of the run's relationship matrix, how many components, the report
+        for key, field in (("pca", "pca_prefix"), ("pcaReport", "pca_report_path")):
+            if cfg.get(key):
+                keep.append(str(cfg[key]).encode())
+                setattr(pc, field, keep[-1])
+        pc.pca_count = int(cfg.get("pcaCount") or PCA_DEFAULT_COMPONENTS)
+        c.reserved[1] = CONFIG_MORE_PCA
     c._keep = keep
     return c
+
+
+def grm_matrix(tables, n_samples):
+    """bvcf_grm_matrix: the uint64 words bvcf_grm gives (3 S S + 1 of them) -> (lower, counts), the float32 lower triangles
+    of PREFIX.grm.bin and PREFIX.grm.N.bin  (host code, no device)"""
+    t = np.ascontiguousarray(tables, dtype=np.uint64).ravel()
+    s = int(n_samples)
+    assert t.size == 3 * s * s + 1
+    lower = np.zeros(s * (s + 1) // 2, dtype=np.float32)
+    counts = np.zeros(s * (s + 1) // 2, dtype=np.float32)
+    lib.bvcf_grm_matrix.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    rc = lib.bvcf_grm_matrix(t.ctypes.data, s, lower.ctypes.data, counts.ctypes.data)
+    if rc:
+        raise BvcfError(rc, "bvcf_grm_matrix")
+    return lower, counts
+
+
+def pca_tridiag(d, e, k):
+    """bvcf_pca_tridiag: the k largest eigenvalues, descending, of the symmetric tridiagonal matrix (d, e) and a unit vector
+    for each -> (values (k,), vectors (k, n))  (host code, no device)"""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    n = d.size
+    assert e.size == max(n - 1, 0)
+    values = np.zeros(max(int(k), 0), dtype=np.float64)
+    z = np.zeros((max(int(k), 0), n), dtype=np.float64)
+    lib.bvcf_pca_tridiag.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    rc = lib.bvcf_pca_tridiag(d.ctypes.data, e.ctypes.data if e.size else None, n, int(k), values.ctypes.data, z.ctypes.data)
+    if rc:
+        raise BvcfError(rc, "bvcf_pca_tridiag")
+    return values, z
+
+
+def pca_eigen(lower, n_samples, k, device=0, timings=None):
+    """bvcf_pca_eigen: the packed float32 lower triangle of a symmetric matrix (S (S + 1) / 2 values, row by row) -> (values (k,),
+    vectors (k, S)): the k largest eigenvalues, descending, and unit eigenvectors, largest component positive.  timings: a
+    list that receives the five phase times in ms (bvcf_bench_pca_eigen)"""
+    a = np.ascontiguousarray(lower, dtype=np.float32).ravel()
+    s, k = int(n_samples), int(k)
+    assert a.size == s * (s + 1) // 2
+    values = np.zeros(max(k, 0), dtype=np.float64)
+    vectors = np.zeros((max(k, 0), s), dtype=np.float64)
+    if timings is not None:
+        ms = (C.c_float * 5)()
+        lib.bvcf_bench_pca_eigen.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        rc, msg = lib.bvcf_bench_pca_eigen(device, a.ctypes.data, s, k, values.ctypes.data, vectors.ctypes.data, ms), "bvcf_bench_pca_eigen"
+        timings[:] = list(ms)
+    else:
+        err = C.create_string_buffer(256)
+        lib.bvcf_pca_eigen.argtypes = [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        rc = lib.bvcf_pca_eigen(device, a.ctypes.data, s, k, values.ctypes.data, vectors.ctypes.data, err, len(err))
+        msg = err.value.decode()
+    if rc:
+        raise BvcfError(rc, msg)
+    return values, vectors
 
 
 def ld_counts(row_a, row_b, n_samples):

@@ -11,12 +11,16 @@
 #include "bvcf_devmem.h"
 
 #include <dlfcn.h>
+#include <math.h>
+#include <stdarg.h>
 #include <rccl/rccl.h>  // types and prototypes only: librccl.so.1 is dlopen'ed by bvcf_allreduce_counters
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
+#include <cmath>
 #include <mutex>
 #include <string>
 #include <string_view>
@@ -2140,6 +2144,114 @@ int bvcf_bgzf_inflate_device(int device, const uint8_t *comp, size_t n_comp, uin
   for (size_t i = 0; i < nb; i++)
     if (status[i] != kInfOk || crc[i] != blocks[i].crc) return BVCF_E_FATAL;  // corrupt block (inflate or CRC mismatch)
   return BVCF_OK;
+}
+
+namespace {
+
+// bvcf_pca_eigen and its measuring twin: ms (may be NULL) = {upload + k_pca_expand, the tridiagonalisation's 4 (n - 1) launches,
+// the host's tridiagonal solve, upload + k_pca_back + download, everything}.  The phases end at stream waits that are there
+// anyway: measuring changes nothing about the run
+struct PcaSay {
+  char *err;
+  size_t cap;
+  __attribute__((format(printf, 2, 3))) void operator()(const char *fmt, ...) const {
+    if (!err || !cap) return;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(err, cap, fmt, ap);
+    va_end(ap);
+  }
+};
+
+int pca_eigen(int device, const float *lower, uint32_t s, uint32_t k, double *values, double *vectors, char *err, size_t err_cap, float *ms) {
+  const PcaSay say{err, err_cap};
+  if (err && err_cap) err[0] = 0;
+  if (ms) memset(ms, 0, 5 * sizeof(float));
+  if (s == 0) return BVCF_OK;
+  if (!lower || !values || !vectors) return say("pca: a NULL argument"), BVCF_E_ARG;
+  if (s > BVCF_PAIR_MAX_SAMPLES) return say("pca: %u samples, the solver takes at most %u", s, BVCF_PAIR_MAX_SAMPLES), BVCF_E_ARG;
+  if (k == 0 || k > s || k > BVCF_PCA_MAX_COMPONENTS)
+    return say("pca: %u components of a matrix of %u samples: want 1 to %u", k, s, std::min<uint32_t>(s, BVCF_PCA_MAX_COMPONENTS)), BVCF_E_ARG;
+  const uint64_t n_lower = (uint64_t)s * (s + 1) / 2;
+  for (uint64_t i = 0; i < n_lower; i++)
+    if (!std::isfinite(lower[i])) return say("pca: entry %llu of the matrix is not finite", (unsigned long long)i), BVCF_E_ARG;
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) return say("pca: no device %d", device), BVCF_E_NODEV;
+  if (hipSetDevice(device) != hipSuccess) return say("pca: hipSetDevice(%d) failed", device), BVCF_E_HIP;
+
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  auto since = [](clk::time_point a) { return std::chrono::duration<float, std::milli>(clk::now() - a).count(); };
+  const uint32_t n = s, ld = (n + 15u) & ~15u;
+  // the packed triangle goes up a run of whole rows at a time, through at most 64 MB
+  const uint64_t stage_cap = std::min<uint64_t>(n_lower, std::max<uint64_t>(16u << 20, n));
+  Stream st;
+  DevBuf<double> d_a, d_d, d_e, d_tau, d_p, d_w, d_z, d_u;
+  DevBuf<float> d_stage;
+  if (st.create(hipStreamNonBlocking) != hipSuccess) return say("pca: no stream"), BVCF_E_HIP;
+  if (d_a.alloc((size_t)n * ld) != hipSuccess || d_stage.alloc(stage_cap) != hipSuccess || d_d.alloc(n) != hipSuccess ||
+      d_e.alloc(n) != hipSuccess || d_tau.alloc(n) != hipSuccess || d_p.alloc(n) != hipSuccess || d_w.alloc(n) != hipSuccess ||
+      d_z.alloc((size_t)k * n) != hipSuccess || d_u.alloc((size_t)k * n) != hipSuccess)
+    return say("pca: out of device memory for a matrix of %u samples", n), BVCF_E_NOMEM;
+  bool ok = true;
+  for (uint32_t row0 = 0; ok && row0 < n;) {
+    uint32_t rows = 0;
+    uint64_t elems = 0;
+    while (row0 + rows < n && elems + row0 + rows + 1 <= stage_cap) elems += row0 + rows++ + 1;
+    ok = hipMemcpyAsync(d_stage, lower + (uint64_t)row0 * (row0 + 1) / 2, elems * sizeof(float), hipMemcpyHostToDevice, st) == hipSuccess;
+    hipLaunchKernelGGL(k_pca_expand, dim3((n + kWgThreads - 1) / kWgThreads, rows), dim3(kWgThreads), 0, st, d_stage.get(), row0, rows,
+                       d_a.get(), ld, n);
+    // (the next run overwrites the staging buffer, and `lower` is pageable: the copy has left it when the call returns)
+    ok = ok && hipStreamSynchronize(st) == hipSuccess;
+    row0 += rows;
+  }
+  if (!ok) return say("pca: upload failed: %s", hipGetErrorString(hipGetLastError())), BVCF_E_HIP;
+  d_stage.reset();
+  const auto t1 = clk::now();
+  if (ms) ms[0] = since(t0);
+
+  for (uint32_t j = 0; j < n; j++) {
+    const uint32_t m = n - j - 1;
+    hipLaunchKernelGGL(k_pca_house, dim3(1), dim3(kPcaWgThreads), 0, st, d_a.get(), ld, n, j, d_d.get(), d_e.get(), d_tau.get());
+    if (m < 2) continue;  // (m = 1: nothing behind x_0, tau = 0 and A22 stays; m = 0: the last diagonal entry)
+    hipLaunchKernelGGL(k_pca_symv, dim3((m + kWavesPerWg - 1) / kWavesPerWg), dim3(kWgThreads), 0, st, d_a.get(), ld, n, j, d_tau.get(), d_p.get());
+    hipLaunchKernelGGL(k_pca_w, dim3(1), dim3(kPcaWgThreads), 0, st, d_a.get(), ld, n, j, d_tau.get(), d_p.get(), d_w.get());
+    hipLaunchKernelGGL(k_pca_rank2, dim3((m + kWgThreads - 1) / kWgThreads, (m + kPcaRank2Rows - 1) / kPcaRank2Rows), dim3(kWgThreads), 0, st,
+                       d_a.get(), ld, n, j, d_tau.get(), d_w.get());
+  }
+  std::vector<double> d(n), e(n), tau(n), z((size_t)k * n);
+  ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(d.data(), d_d, n * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+       (n < 2 || (hipMemcpyAsync(e.data(), d_e, (n - 1) * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess &&
+                  hipMemcpyAsync(tau.data(), d_tau, (n - 1) * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess)) &&
+       hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return say("pca: the tridiagonalisation failed: %s", hipGetErrorString(hipGetLastError())), BVCF_E_HIP;
+  const auto t2 = clk::now();
+  if (ms) ms[1] = since(t1);
+
+  if (bvcf_pca_tridiag(d.data(), e.data(), n, k, values, z.data()) != BVCF_OK) return say("pca: the tridiagonal matrix is not finite"), BVCF_E_FATAL;
+  const auto t3 = clk::now();
+  if (ms) ms[2] = since(t2);
+
+  ok = hipMemcpyAsync(d_z, z.data(), (size_t)k * n * sizeof(double), hipMemcpyHostToDevice, st) == hipSuccess;
+  hipLaunchKernelGGL(k_pca_back, dim3(k), dim3(kPcaWgThreads), 0, st, d_a.get(), ld, n, d_tau.get(), d_z.get(), d_u.get());
+  ok = ok && hipGetLastError() == hipSuccess &&
+       hipMemcpyAsync(vectors, d_u, (size_t)k * n * sizeof(double), hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+  if (!ok) return say("pca: the back-transformation failed: %s", hipGetErrorString(hipGetLastError())), BVCF_E_HIP;
+  if (ms) {
+    ms[3] = since(t3);
+    ms[4] = since(t0);
+  }
+  return BVCF_OK;
+}
+
+}  // namespace
+
+int bvcf_pca_eigen(int device, const float *lower, uint32_t s, uint32_t k, double *values, double *vectors, char *err, size_t err_cap) {
+  return pca_eigen(device, lower, s, k, values, vectors, err, err_cap, nullptr);
+}
+
+int bvcf_bench_pca_eigen(int device, const float *lower, uint32_t s, uint32_t k, double *values, double *vectors, float ms[5]) {
+  return pca_eigen(device, lower, s, k, values, vectors, nullptr, 0, ms);
 }
 
 int bvcf_bgzf_deflate_device(int device, const uint8_t *text, size_t n, int add_eof, uint8_t *out, size_t cap, size_t *n_out) {

@@ -66,6 +66,9 @@
 //    the dense rows' classes -- the map is the A operand, expanded in registers -- with the phenotypes' int8 limbs on the
 //    matrix cores, reducing over the samples into one record per (row, phenotype), k_assoc_sparse does the short lists --
 //    the exact integer sums behind --pheno / --assoc, bvcf_assoc.hip.h)
+//   (bvcf_pca_eigen, outside every chain and without a ctx: k_pca_expand, then per step k_pca_house / k_pca_symv / k_pca_w /
+//    k_pca_rank2 -- Householder tridiagonalisation of the relationship matrix in double --, and k_pca_back, the reflectors applied
+//    to the eigenvectors the host found for the tridiagonal matrix -- the solver behind --pca, bvcf_pca.hip.h)
 //   (bvcf_set_region_table, right behind k_finish and in front of the variant gate: k_region_gate finds every row's
 //    chromosome in the hash set of --regions / --excludeRegions, binary-searches the row's span in the chromosome's merged
 //    intervals and takes the unselected rows out -- bvcf_regions.hip.h)
@@ -133,6 +136,7 @@
 #include "bvcf_samplestats.hip.h"
 #include "bvcf_pairstats.hip.h"
 #include "bvcf_grm.hip.h"
+#include "bvcf_pca.hip.h"
 #include "bvcf_score.hip.h"
 #include "bvcf_assoc.hip.h"
 #include "bvcf_bedrows.hip.h"

@@ -418,7 +418,7 @@ void Driver::device_main(DevWorker *W) {
         for (size_t k = 0; k < n; k++) W->pr_carry[k] += t[k];
       }
       // (--grm: the same for the GRM's tables)
-      const bool grm = wants_grm(c_) && R_.pre.header.size() > 9;
+      const bool grm = wants_grm_tables(c_) && R_.pre.header.size() > 9;
       if (grm) {
         const size_t ns = R_.pre.header.size() - 9;
         std::vector<uint64_t> t(grm_table_words(ns), 0);
@@ -696,6 +696,10 @@ int Driver::run(uint64_t *n_lines_in) {
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
+    if (const int rc = open_pca(R_, &msg)) {  // --pca / --pcaReport: the outputs opened
+      dprintf(fd_err_, "%s\n", msg.c_str());
+      return rc;
+    }
   }
   sniff_input();
   // --compressOutput bgzf: one compressed stream for the header and the rows, on the run's first device
@@ -897,8 +901,8 @@ int Driver::run(uint64_t *n_lines_in) {
       if (rc_ != BVCF_OK) close(pr_fd_);  // (write_pair_stats closed it)
       pr_fd_ = -1;
     }
-    if (R_.grm_fd >= 0 && rc_ == BVCF_OK) {
-      // --grm: the workers' tables added one after another into one host table (a failed run leaves the files empty)
+    if ((R_.grm_fd >= 0 || R_.pca_vec_fd >= 0) && rc_ == BVCF_OK) {
+      // --grm / --pca: the workers' tables added one after another into one host table (a failed run leaves the files empty)
       const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0;
       std::vector<uint64_t> sum(grm_table_words(ns), 0), t;
       for (auto &W : workers_) {
@@ -912,7 +916,11 @@ int Driver::run(uint64_t *n_lines_in) {
         if (!W->grm_carry.empty()) add_grm_table(sum, W->grm_carry.data(), ns);
       }
       std::string msg;
-      if (rc_ == BVCF_OK && write_grm(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+      if (rc_ == BVCF_OK && R_.grm_fd >= 0 && write_grm(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
+      // (the components of the same matrix, solved on the run's first device)
+      if (rc_ == BVCF_OK && R_.pca_vec_fd >= 0) {
+        if (const int prc = write_pca(R_, sum.data(), dev_list_[0] >= 0 ? dev_list_[0] : c_->device, &msg)) fail(msg, prc);
+      }
       if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
     }
     if (R_.score_fd >= 0 && rc_ == BVCF_OK) {

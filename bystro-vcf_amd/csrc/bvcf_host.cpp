@@ -85,6 +85,33 @@ void bvcf_config_assoc_defaults(bvcf_config_assoc *c) {
   c->score.grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_ASSOC;
 }
 
+void bvcf_config_pca_defaults(bvcf_config_pca *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_assoc_defaults(&c->assoc);
+  c->assoc.score.grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_PCA;
+  c->pca_count = BVCF_PCA_DEFAULT_COMPONENTS;
+}
+
+// A(i,j) = T(i,j) / (2^28 N(i,j)) with N(i,j) = N - miss_i - miss_j + MM(i,j), miss_i = MM(i,i): the correctly rounded double of
+// the integer T (what the conversion of a 128-bit integer gives) over the double 2^28 N(i,j) (exact), rounded to float32; 0
+// when no row has both samples called.  The diagonal by the same formula: PLINK's convention
+int bvcf_grm_matrix(const uint64_t *tables, uint32_t s, float *lower, float *counts) {
+  if (s > BVCF_PAIR_MAX_SAMPLES || (!tables && s)) return BVCF_E_ARG;
+  const size_t ns = s, n = ns * ns;
+  const uint64_t *lo = tables, *hi = tables + n, *mm = tables + 2 * n;
+  const uint64_t rows = ns ? tables[3 * n] : 0;
+  size_t at = 0;
+  for (size_t i = 0; i < ns; i++) {
+    for (size_t j = 0; j <= i; j++, at++) {
+      const uint64_t nij = rows - mm[i * ns + i] - mm[j * ns + j] + mm[i * ns + j];
+      const __int128 t = (__int128)(((unsigned __int128)hi[i * ns + j] << 64) | lo[i * ns + j]);
+      if (lower) lower[at] = nij ? (float)((double)t / ((double)nij * 268435456.0)) : 0.0f;
+      if (counts) counts[at] = (float)nij;
+    }
+  }
+  return BVCF_OK;
+}
+
 int bvcf_variant_table_parse(const char *text, size_t n, bvcf_variant_table *out) {
   if (!out || (!text && n)) return BVCF_E_ARG;
   std::vector<uint64_t> off;
@@ -183,6 +210,7 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   if (rc == BVCF_OK) rc = open_grm(R, &msg);
   if (rc == BVCF_OK) rc = open_score(R, &msg);
   if (rc == BVCF_OK) rc = open_assoc(R, &msg);
+  if (rc == BVCF_OK) rc = open_pca(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -334,15 +362,20 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       close(pr_fd);
     }
   }
-  if (R.grm_fd >= 0 && rc == BVCF_OK) {  // --grm: the run's matrix, after a successful run only
+  if ((R.grm_fd >= 0 || R.pca_vec_fd >= 0) && rc == BVCF_OK) {  // --grm / --pca: the run's matrix, after a successful run only
     const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
     std::vector<uint64_t> t(grm_table_words(ns), 0);
     if (R.ctx && bvcf_grm(R.ctx, t.data(), 0) != BVCF_OK) {
       l.append(std::string("bvcf_grm: ") + bvcf_last_error(R.ctx) + "\n");
       rc = BVCF_E_HIP;
-    } else if (write_grm(R, t.data(), &msg)) {
+    } else if (R.grm_fd >= 0 && write_grm(R, t.data(), &msg)) {
       l.append(msg + "\n");
       rc = BVCF_E_IO;
+    } else if (R.pca_vec_fd >= 0) {  // (the components of the same matrix, solved on the ctx's device)
+      if (const int prc = write_pca(R, t.data(), c->device, &msg)) {
+        l.append(msg + "\n");
+        rc = prc;
+      }
     }
   }
   if (R.score_fd >= 0 && rc == BVCF_OK) {  // --score: the run's scores, after a successful run only

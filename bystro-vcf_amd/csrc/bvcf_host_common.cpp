@@ -710,8 +710,8 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
            std::to_string(BVCF_PAIR_MAX_SAMPLES) + " (select fewer with --keepSamples / --excludeSamples)";
     return BVCF_E_ARG;
   }
-  if (wants_grm(R.cfg) && R.pre.header.size() > 9 + (size_t)BVCF_PAIR_MAX_SAMPLES) {  // (likewise)
-    *msg = "grm: " + std::to_string(R.pre.header.size() - 9) + " samples, the matrix holds at most " +
+  if (wants_grm_tables(R.cfg) && R.pre.header.size() > 9 + (size_t)BVCF_PAIR_MAX_SAMPLES) {  // (likewise; --pca alone: its own prefix)
+    *msg = std::string(wants_grm(R.cfg) ? "grm: " : "pca: ") + std::to_string(R.pre.header.size() - 9) + " samples, the matrix holds at most " +
            std::to_string(BVCF_PAIR_MAX_SAMPLES) + " (select fewer with --keepSamples / --excludeSamples)";
     return BVCF_E_ARG;
   }
@@ -792,7 +792,7 @@ int prepare_run(Run &R, std::string *msg, const uint8_t *data, size_t n_data, bo
   }
   // --grm: a ctx with the GRM on reserves at most BVCF_GRM_MAX_BATCH_ROWS allele slots (2 * max_lines + 1024 of them).  A
   // batch of more lines grows the reservation as far as that; one that needs more fails with bvcf_reserve's message
-  if (wants_grm(R.cfg) && R.pre.header.size() > 9) {
+  if (wants_grm_tables(R.cfg) && R.pre.header.size() > 9) {
     const uint64_t floor_len = std::max<uint64_t>(48, 2ull * R.n_header_full);
     const uint64_t derived = p.max_lines ? p.max_lines : std::min<uint64_t>(R.max_batch / floor_len + 4096, 0x7FFFFFFFu);
     p.max_lines = (uint32_t)std::min<uint64_t>(derived, (BVCF_GRM_MAX_BATCH_ROWS - 1024u) / 2u);
@@ -851,10 +851,10 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
-  if (rc == BVCF_OK && wants_grm(R.cfg)) {  // --grm: the GRM's tables of every ctx of the run
+  if (rc == BVCF_OK && wants_grm_tables(R.cfg)) {  // --grm / --pca: the GRM's tables of every ctx of the run
     rc = bvcf_enable_grm(*ctx);
     if (rc) {
-      *msg = std::string("bvcf_enable_grm: ") + bvcf_last_error(*ctx);
+      *msg = std::string(wants_grm(R.cfg) ? "bvcf_enable_grm: " : "pca: bvcf_enable_grm: ") + bvcf_last_error(*ctx);
       bvcf_destroy(*ctx);
       *ctx = nullptr;
     }
@@ -1694,29 +1694,13 @@ void add_grm_table(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns) {
   for (size_t k = 2 * n; k < 3 * n + 1; k++) sum[k] += t[k];
 }
 
-// A(i,j) = T(i,j) / (2^28 N(i,j)) with N(i,j) = N - miss_i - miss_j + MM(i,j), miss_i = MM(i,i): the correctly rounded double of
-// the integer T (what the conversion of a 128-bit integer gives) over the double 2^28 N(i,j) (exact), rounded to float32; 0
-// when no row has both samples called.  The diagonal by the same formula: PLINK's convention
+// (the arithmetic is bvcf_grm_matrix's, bvcf_host.cpp)
 int write_grm(Run &R, const uint64_t *sum, std::string *msg) {
-  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0, n = ns * ns;
-  const uint64_t *lo = sum, *hi = sum + n, *mm = sum + 2 * n;
-  const uint64_t rows = ns ? sum[3 * n] : 0;
-  std::vector<float> a, cnt;
-  a.reserve(64 + ns);
-  cnt.reserve(64 + ns);
-  bool bad = false;
-  for (size_t i = 0; i < ns && !bad; i++) {
-    a.clear();
-    cnt.clear();
-    for (size_t j = 0; j <= i; j++) {
-      const uint64_t nij = rows - mm[i * ns + i] - mm[j * ns + j] + mm[i * ns + j];
-      const __int128 t = (__int128)(((unsigned __int128)hi[i * ns + j] << 64) | lo[i * ns + j]);
-      a.push_back(nij ? (float)((double)t / ((double)nij * 268435456.0)) : 0.0f);
-      cnt.push_back((float)nij);
-    }
-    bad = write_all(R.grm_fd, (const char *)a.data(), a.size() * sizeof(float)) != 0 ||
-          write_all(R.grm_n_fd, (const char *)cnt.data(), cnt.size() * sizeof(float)) != 0;
-  }
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+  std::vector<float> a(ns * (ns + 1) / 2), cnt(ns * (ns + 1) / 2);
+  bool bad = bvcf_grm_matrix(sum, (uint32_t)ns, a.data(), cnt.data()) != BVCF_OK ||
+             write_all(R.grm_fd, (const char *)a.data(), a.size() * sizeof(float)) != 0 ||
+             write_all(R.grm_n_fd, (const char *)cnt.data(), cnt.size() * sizeof(float)) != 0;
   std::string ids;
   for (size_t i = 0; i < ns; i++) {
     ids.append(R.pre.header[9 + i]);
@@ -1735,6 +1719,106 @@ int write_grm(Run &R, const uint64_t *sum, std::string *msg) {
   }
   if (bad) {
     *msg = std::string("grm: write failed: ") + strerror(saved);
+    return BVCF_E_IO;
+  }
+  return BVCF_OK;
+}
+
+int open_pca(Run &R, std::string *msg) {
+  const bvcf_config_pca *pc = pca_config(R.cfg);
+  if (!pc) return BVCF_OK;
+  const bool have_r = pc->pca_report_path && *pc->pca_report_path;
+  if (!wants_pca(R.cfg)) {
+    if (have_r) {
+      *msg = "pca_report_path without pca_prefix";
+      return BVCF_E_ARG;
+    }
+    return BVCF_OK;
+  }
+  if (pc->pca_count > BVCF_PCA_MAX_COMPONENTS) {
+    *msg = "pca: " + std::to_string(pc->pca_count) + " components, at most " + std::to_string(BVCF_PCA_MAX_COMPONENTS);
+    return BVCF_E_ARG;
+  }
+  const std::string prefix = pc->pca_prefix;
+  const std::pair<int *, std::string> files[3] = {{&R.pca_vec_fd, prefix + ".eigenvec"}, {&R.pca_val_fd, prefix + ".eigenval"},
+                                                  {&R.pca_report_fd, have_r ? std::string(pc->pca_report_path) : std::string()}};
+  for (const auto &f : files) {
+    if (f.second.empty()) continue;
+    *f.first = open(f.second.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (*f.first < 0) {
+      *msg = "open " + f.second + ": " + strerror(errno);
+      return BVCF_E_IO;
+    }
+  }
+  return BVCF_OK;
+}
+
+namespace {
+// "%.6G"; a zero, -0 included, prints "0"
+void append_g6(std::string &o, double v) {
+  if (v == 0.0) {
+    o.push_back('0');
+    return;
+  }
+  char b[40];
+  o.append(b, (size_t)snprintf(b, sizeof b, "%.6G", v));
+}
+}  // namespace
+
+int write_pca(Run &R, const uint64_t *sum, int device, std::string *msg) {
+  const bvcf_config_pca *pc = pca_config(R.cfg);
+  const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
+  const uint32_t want = pc->pca_count ? pc->pca_count : BVCF_PCA_DEFAULT_COMPONENTS;
+  const uint32_t k = (uint32_t)std::min<size_t>(want, ns);
+  std::vector<float> a(ns * (ns + 1) / 2);
+  std::vector<double> values(k), vectors((size_t)k * ns);
+  int rc = bvcf_grm_matrix(sum, (uint32_t)ns, a.data(), nullptr);
+  if (rc == BVCF_OK && ns) {
+    char err[256] = "";
+    rc = bvcf_pca_eigen(device, a.data(), (uint32_t)ns, k, values.data(), vectors.data(), err, sizeof err);
+    if (rc) *msg = err[0] ? std::string(err) : std::string("pca: the solver failed");
+  } else if (rc) {
+    *msg = "pca: bad tables";
+  }
+  bool bad = false;
+  int saved = 0;
+  if (rc == BVCF_OK) {
+    std::string vec = "#FID\tIID", val, rep;
+    for (uint32_t c = 0; c < k; c++) vec += "\tPC" + std::to_string(c + 1);
+    vec.push_back('\n');
+    for (size_t i = 0; i < ns; i++) {
+      vec.append(R.pre.header[9 + i]);
+      vec.push_back('\t');
+      vec.append(R.pre.header[9 + i]);
+      for (uint32_t c = 0; c < k; c++) {
+        vec.push_back('\t');
+        append_g6(vec, vectors[(size_t)c * ns + i]);
+      }
+      vec.push_back('\n');
+    }
+    for (uint32_t c = 0; c < k; c++) {
+      append_g6(val, values[c]);
+      val.push_back('\n');
+    }
+    double trace = 0.0;
+    for (size_t i = 0; i < ns; i++) trace += (double)a[i * (i + 1) / 2 + i];
+    rep = "samples\t" + std::to_string(ns) + "\nrows\t" + std::to_string(ns ? sum[3 * ns * ns] : 0) + "\ncomponents\t" + std::to_string(k) + "\ntrace\t";
+    append_g6(rep, trace);
+    rep.push_back('\n');
+    bad = write_all(R.pca_vec_fd, vec.data(), vec.size()) != 0 || write_all(R.pca_val_fd, val.data(), val.size()) != 0 ||
+          (R.pca_report_fd >= 0 && write_all(R.pca_report_fd, rep.data(), rep.size()) != 0);
+    saved = errno;
+  }
+  for (int *fd : {&R.pca_vec_fd, &R.pca_val_fd, &R.pca_report_fd}) {
+    if (*fd >= 0 && close(*fd) && !bad) {
+      bad = true;
+      saved = errno;
+    }
+    *fd = -1;
+  }
+  if (rc) return rc;
+  if (bad) {
+    *msg = std::string("pca: write failed: ") + strerror(saved);
     return BVCF_E_IO;
   }
   return BVCF_OK;

@@ -267,6 +267,9 @@ struct Run {
   // --grm: PREFIX.grm.bin / .grm.N.bin / .grm.id, opened by open_grm before any device work; write_grm writes all three from
   // the sum of the run's bvcf_grm tables at the end of a successful run and closes them
   int grm_fd = -1, grm_n_fd = -1, grm_id_fd = -1;
+  // --pca: PREFIX.eigenvec / .eigenval and the report, opened by open_pca before any device work; write_pca solves the matrix
+  // of the same summed tables at the end of a successful run, writes the files and closes them
+  int pca_vec_fd = -1, pca_val_fd = -1, pca_report_fd = -1;
   // --score / --scoreOutput / --scoreReport: open_score opens the outputs and reads the score file into the run's one table
   // before any device work; create_ctx uploads it to every ctx; write_score writes the table (and the report) from the sum of
   // the run's bvcf_score words at the end of a successful run and closes them
@@ -283,7 +286,7 @@ struct Run {
   std::string assoc_buf;
   ~Run() {
     for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
-                   grm_n_fd, grm_id_fd, score_fd, score_report_fd, assoc_fd, assoc_report_fd})
+                   grm_n_fd, grm_id_fd, score_fd, score_report_fd, assoc_fd, assoc_report_fd, pca_vec_fd, pca_val_fd, pca_report_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
     bvcf_score_table_free(&score_table);
@@ -419,7 +422,7 @@ inline const char *grm_prefix(const bvcf_config *c) {
   return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_GRM) ? reinterpret_cast<const bvcf_config_grm *>(c)->grm_prefix
                                                                                         : nullptr;
 }
-// true when the run writes the matrix (every ctx of the run then gets bvcf_enable_grm)
+// true when the run writes the matrix
 inline bool wants_grm(const bvcf_config *c) {
   const char *p = grm_prefix(c);
   return p && *p;
@@ -463,6 +466,23 @@ int open_assoc(Run &R, std::string *msg);
 int load_pheno(Run &R, std::string *msg);
 int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai);
 int close_assoc(Run &R, bool ok, std::string *msg);
+// --pca / --pcaCount / --pcaReport: the bvcf_config_pca of a config that reaches up to it (the eleventh marker); NULL otherwise
+inline const bvcf_config_pca *pca_config(const bvcf_config *c) {
+  return (c->reserved[0] == BVCF_CONFIG_MORE && c->reserved[1] >= BVCF_CONFIG_MORE_PCA) ? reinterpret_cast<const bvcf_config_pca *>(c) : nullptr;
+}
+// true when the run writes components
+inline bool wants_pca(const bvcf_config *c) {
+  const bvcf_config_pca *p = pca_config(c);
+  return p && p->pca_prefix && *p->pca_prefix;
+}
+// true when the run sums the GRM's tables: for the matrix, for the components or for both (every ctx of the run then gets
+// bvcf_enable_grm)
+inline bool wants_grm_tables(const bvcf_config *c) { return wants_grm(c) || wants_pca(c); }
+// the files opened (truncated) -- BVCF_E_ARG for a report without a prefix or a count above BVCF_PCA_MAX_COMPONENTS, BVCF_E_IO for a
+// file, one message in *msg; the run's summed tables turned into the float32 triangle, solved on `device`, the files written
+// and closed
+int open_pca(Run &R, std::string *msg);
+int write_pca(Run &R, const uint64_t *sum, int device, std::string *msg);
 inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;

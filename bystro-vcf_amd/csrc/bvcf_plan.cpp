@@ -4,6 +4,7 @@
 // work items (main.go:345-380).
 #include "bvcf_pipeline.h"
 #include "bvcf_ld_counts.h"
+#include "bvcf_pca_tri.h"
 
 #include <algorithm>
 #include <array>
@@ -498,6 +499,10 @@ int bvcf_ld_seam_push(bvcf_ld_seam *s, uint64_t n_rows, uint32_t n_edge, const u
   while (s->carry.size() > N) s->carry.pop_front();
   s->n_rows += n_rows;
   return 0;
+}
+
+int bvcf_pca_tridiag(const double *d, const double *e, uint32_t n, uint32_t k, double *values, double *z) {
+  return pca_tri::solve(d, e, n, k, values, z) ? BVCF_E_ARG : BVCF_OK;
 }
 
 }  // extern "C"

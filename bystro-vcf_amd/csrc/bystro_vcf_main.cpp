@@ -72,6 +72,11 @@ struct Cli {
   // extension: --pheno FILE --assoc PATH [--assocReport PATH], every row of the run against the file's phenotypes: the
   // additive score test / Cochran-Armitage trend test from exact integer sums (the dense rows on the device's matrix cores)
   std::string pheno, assoc, assoc_report;
+  // extension: --pca PREFIX [--pcaCount K] [--pcaReport PATH], the top K principal components of the run's relationship
+  // matrix as PREFIX.eigenvec / .eigenval (a dense symmetric eigensolver on the run's first device); --pcaCount alone is
+  // accepted and does nothing
+  std::string pca, pca_report;
+  uint32_t pca_count = BVCF_PCA_DEFAULT_COMPONENTS;
 };
 
 // a decimal in [0, hi]: strtod over the whole text, which starts with a digit or the point (no space, no sign), and
@@ -170,7 +175,7 @@ int parse(int argc, char **argv, Cli &c) {
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
         name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
         name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport" || name == "pheno" || name == "assoc" ||
-        name == "assocReport") {
+        name == "assocReport" || name == "pca" || name == "pcaCount" || name == "pcaReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -208,6 +213,17 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         (name == "pheno" ? c.pheno : name == "assoc" ? c.assoc : c.assoc_report) = val;
+      } else if (name == "pca" || name == "pcaReport") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -%s: want the %s to write\n", name.c_str(), name == "pca" ? "prefix of the two files" : "path of the file");
+          return 2;
+        }
+        (name == "pca" ? c.pca : c.pca_report) = val;
+      } else if (name == "pcaCount") {
+        if (!parse_threshold(val, &c.pca_count) || c.pca_count < 1 || c.pca_count > BVCF_PCA_MAX_COMPONENTS) {
+          fprintf(stderr, "invalid value \"%s\" for flag -%s: want an integer from 1 to %u\n", val.c_str(), name.c_str(), BVCF_PCA_MAX_COMPONENTS);
+          return 2;
+        }
       } else if (name == "mendel" || name == "mendelErrors") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to write\n", name.c_str());
@@ -313,6 +329,10 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-assocReport needs -pheno and -assoc\n");
     return 2;
   }
+  if (!c.pca_report.empty() && c.pca.empty()) {
+    fprintf(stderr, "-pcaReport needs -pca\n");
+    return 2;
+  }
   if ((!c.mendel.empty() || !c.mendel_errors.empty()) && c.fam.empty()) {
     fprintf(stderr, "-mendel and -mendelErrors need the pedigree: -fam PATH\n");
     return 2;
@@ -349,10 +369,10 @@ int main(int argc, char **argv) {
   // main.go:164-166 (--sampleStats, --relatedness or --siteFilterReport alone: a QC-only pass; --plinkOutput alone: a
   // conversion-only pass; --mendel / --mendelErrors alone: QC-only again; so are --variantFilterReport and
   // --regionFilterReport alone; --grm alone: a GRM-only pass; --score with --scoreOutput alone: a scoring-only pass;
-  // --pheno with --assoc alone: a scan-only pass)
+  // --pheno with --assoc alone: a scan-only pass; --pca alone: a PCA-only pass)
   if (c.no_out && c.dosage.empty() && c.sample_stats.empty() && c.relatedness.empty() && c.site_report.empty() && c.plink.empty() &&
       c.mendel.empty() && c.mendel_errors.empty() && c.ld.empty() && c.ld_prune.empty() &&
-      c.variant_report.empty() && c.region_report.empty() && c.grm.empty() && c.score.empty() && c.pheno.empty()) {
+      c.variant_report.empty() && c.region_report.empty() && c.grm.empty() && c.score.empty() && c.pheno.empty() && c.pca.empty()) {
     dprintf(fd_err, "When specifying --noOut, must specify --dosageOutput\n");
     return 1;
   }
@@ -368,9 +388,10 @@ int main(int argc, char **argv) {
   // pedigree and the two --mendel paths)
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
   // regions and their report; behind those the --grm prefix; behind that the --score paths; behind those the --pheno / --assoc
-  // paths)
-  bvcf_config_assoc assoc_cfg;
-  bvcf_config_assoc_defaults(&assoc_cfg);
+  // paths; behind those the --pca prefix, count and report)
+  bvcf_config_pca pca_cfg;
+  bvcf_config_pca_defaults(&pca_cfg);
+  bvcf_config_assoc &assoc_cfg = pca_cfg.assoc;
   bvcf_config_score &score_cfg = assoc_cfg.score;
   bvcf_config_grm &grm_cfg = score_cfg.grm;
   bvcf_config_regions &rc_cfg = grm_cfg.regions;
@@ -457,6 +478,9 @@ int main(int argc, char **argv) {
   assoc_cfg.pheno_path = c.pheno.c_str();
   assoc_cfg.assoc_path = c.assoc.c_str();
   assoc_cfg.assoc_report_path = c.assoc_report.c_str();
+  pca_cfg.pca_prefix = c.pca.c_str();
+  pca_cfg.pca_count = c.pca_count;
+  pca_cfg.pca_report_path = c.pca_report.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -1140,6 +1140,59 @@ typedef struct {
 } bvcf_config_assoc;
 /* the whole struct: bvcf_config_score_defaults, base.reserved[1] = BVCF_CONFIG_MORE_ASSOC, no scan */
 void bvcf_config_assoc_defaults(bvcf_config_assoc *c);
+/* Likewise what came after bvcf_config_assoc: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_PCA.  bvcf_config_pca_defaults sets that; the ten older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_PCA 10
+#define BVCF_PCA_MAX_COMPONENTS 64u  /* most eigenpairs bvcf_pca_eigen gives; pca_count's largest value */
+#define BVCF_PCA_DEFAULT_COMPONENTS 10u
+typedef struct {
+  bvcf_config_assoc assoc;
+  /* --pca PREFIX: the top principal components of the run's relationship matrix.  The run sums the bvcf_grm tables as for
+   * grm_prefix (which need not be given; with both, the .grm.* bytes are what grm_prefix alone writes), the host forms the
+   * float32 lower triangle with bvcf_grm_matrix -- the content of PREFIX.grm.bin -- and bvcf_pca_eigen solves it on the run's
+   * first device (bvcf_run_buffer: the config's device).  K = min(pca_count, S); pca_count 0 = BVCF_PCA_DEFAULT_COMPONENTS,
+   * above BVCF_PCA_MAX_COMPONENTS: BVCF_E_ARG.
+   * PREFIX.eigenvec: "#FID \t IID \t PC1 .. \t PCK", then per (kept) sample in header order "name \t name" as .grm.id has it and
+   * the sample's K components as "%.6G" (a zero, -0 included, prints "0").  PREFIX.eigenval: the K eigenvalues, descending,
+   * one "%.6G" per line.  The vectors have unit norm, as PLINK's have; their signs follow bvcf_pca_eigen's rule.
+   * pca_report_path (only with pca_prefix, BVCF_E_ARG otherwise): "samples" S, "rows" N (the GRM rows), "components" K and
+   * "trace" -- the sum of the float32 diagonal in double, in index order, "%.6G": what an eigenvalue is a proportion of --
+   * each "name \t value \n".
+   * All files are opened before any device work and written at the end of a successful run; BVCF_E_ARG with one message
+   * ("pca: ...") when more than BVCF_PAIR_MAX_SAMPLES samples are left after the sample selection; the batch-row rule of
+   * bvcf_enable_grm holds.  A file without sample columns gives "#FID \t IID" alone and an empty .eigenval.  The bytes do not
+   * depend on devices, batch size or input kind (one fixed sequence of operations on one device; the same build on the same
+   * GPU model gives the same bytes), and no other output changes with them.  NULL or "" = no components */
+  const char *pca_prefix;
+  uint32_t pca_count;
+  uint32_t pca_reserved;
+  const char *pca_report_path;
+} bvcf_config_pca;
+/* the whole struct: bvcf_config_assoc_defaults, base.reserved[1] = BVCF_CONFIG_MORE_PCA, no components, pca_count the default */
+void bvcf_config_pca_defaults(bvcf_config_pca *c);
+
+/* write_grm's arithmetic on its own: tables as bvcf_grm gives them (summed over a run's ctxs: [3 s s + 1]) -> the lower
+ * triangle with the diagonal, row by row (s (s + 1) / 2 floats each): lower = A(i,j) = (float)((double)T / (2^28 N(i,j))), 0 when
+ * N(i,j) = 0 -- the content of PREFIX.grm.bin -- and counts = N(i,j) as float32 -- that of PREFIX.grm.N.bin.  Either output may be
+ * NULL.  Host-only.  BVCF_E_ARG for NULL tables with s > 0 or s > BVCF_PAIR_MAX_SAMPLES */
+int bvcf_grm_matrix(const uint64_t *tables, uint32_t s, float *lower, float *counts);
+/* The k algebraically largest eigenvalues, descending, and unit eigenvectors of the symmetric s x s matrix whose lower triangle
+ * is `lower` (as bvcf_grm_matrix gives it), every float32 promoted to double (exact).  vectors[a * s + i] = component i of
+ * vector a.  Sign rule: in each vector the component of largest magnitude is positive, ties to the lowest index.  For a
+ * repeated eigenvalue the vectors are some orthonormal basis of its eigenspace; every output is finite for every finite input,
+ * the zero matrix included.
+ * A direct method, so nothing depends on gaps in the spectrum: Householder tridiagonalisation on the device (dsytd2's
+ * formulas, one launch per phase and step), Sturm-count bisection and inverse iteration for the tridiagonal matrix on the
+ * host (csrc/bvcf_pca_tri.h), the reflectors applied to the k vectors on the device (csrc/bvcf_pca.hip.h).  Every sum has a
+ * fixed order and there are no atomics: the same build on the same GPU model returns the same bytes for the same input.
+ * Promised, with u = s 2^-52 ||A||_F: max |A U - U diag(values)| and max |values - true| within a small multiple of u,
+ * max |U^T U - I| within a small multiple of s 2^-52 (tests/pca.py has the numbers); bit-equality with LAPACK is not.
+ * Needs no ctx.  Device memory: the s x ld matrix of doubles (ld = s rounded up to 16; 512 MB at the cap), at most 64 MB to
+ * stage the triangle, the vectors; all freed before return on every path.  s = 0: BVCF_OK, nothing done.  BVCF_E_ARG -- checked on
+ * the host before any device work -- for k = 0, k > s, k > BVCF_PCA_MAX_COMPONENTS, s > BVCF_PAIR_MAX_SAMPLES or an entry that is
+ * not finite; err (may be NULL) receives one line of message */
+int bvcf_pca_eigen(int device, const float *lower, uint32_t s, uint32_t k, double *values /* k */, double *vectors /* k * s */,
+                   char *err, size_t err_cap);
 
 /* stringHeader(config), main.go:219-239: writes the tab-joined header (no newline), returns its
  * length (or the length needed if cap is too small) */

@@ -111,6 +111,11 @@ int bvcf_bench_trio_kernels(bvcf_ctx *ctx, float ms[4], uint64_t out[2]);
  * the events outrun their arena */
 int bvcf_bench_ld_kernels(bvcf_ctx *ctx, float ms[6], uint64_t out[2]);
 
+/* bvcf_pca_eigen, timed on the host between the stream waits it makes anyway: ms = {upload + k_pca_expand, the tridiagonalisation
+ * (k_pca_house / k_pca_symv / k_pca_w / k_pca_rank2 over every step), the host's tridiagonal solve, upload + k_pca_back +
+ * download, the whole call}.  The per-kernel split of the second entry: a kernel trace of the same call.  Needs no ctx */
+int bvcf_bench_pca_eigen(int device, const float *lower, uint32_t s, uint32_t k, double *values, double *vectors, float ms[5]);
+
 /* BVCF_POISON=XX (tests only; bvcf_devmem.h): every device and pinned buffer of a ctx created while it is set is filled
  * with the byte XX and stands between two guard zones filled with ~XX.  Reads the guards of every live buffer and returns
  * the number of buffers with a damaged guard since the last call -- live ones, and ones found damaged when they were freed;

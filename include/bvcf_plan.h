@@ -207,6 +207,12 @@ int bvcf_assoc_value(const char *text, size_t n, int64_t *out);
 int bvcf_assoc_limbs(uint64_t lo, uint64_t hi, int8_t out[16]);
 int bvcf_assoc_ints(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, uint64_t out[8]);
 
+/* The host step of bvcf_pca_eigen -- csrc/bvcf_pca_tri.h -- on its own: the k algebraically largest eigenvalues, descending, of
+ * the symmetric tridiagonal matrix with the diagonal d[0, n) and the off-diagonal e[0, n - 1) by Sturm-count bisection, and a
+ * unit vector for each by inverse iteration, z[a * n + i] = component i of vector a.  BVCF_OK; BVCF_E_ARG for n = 0, k = 0, k > n,
+ * a NULL argument or an entry that is not finite */
+int bvcf_pca_tridiag(const double *d, const double *e, uint32_t n, uint32_t k, double *values, double *z /* k * n */);
+
 /* What bvcf_create decides before it touches the device: pure arithmetic on bvcf_params and the BVCF_* environment
  * variables.  A ctx runs on exactly this struct (bvcf_reserve grows max_*; the streaming path's adaptive kernel choice
  * moves gen_mode and shape_seen). */
