@@ -47,7 +47,7 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_assoc_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_assoc_kernels", "bvcf_bench_assoc_cov_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
@@ -85,6 +85,8 @@ EXPORTS = [
     "bvcf_pheno_table_build", "bvcf_pheno_table_parse", "bvcf_pheno_table_free", "bvcf_set_pheno_table",
     "bvcf_reserve_assoc_rows", "bvcf_assoc", "bvcf_assoc_stat", "bvcf_config_assoc_defaults",
     "bvcf_grm_matrix", "bvcf_pca_eigen", "bvcf_config_pca_defaults",
+    "bvcf_covar_table_parse", "bvcf_covar_table_build", "bvcf_covar_table_free", "bvcf_pheno_table_mask", "bvcf_set_covar_table",
+    "bvcf_assoc_cov", "bvcf_assoc_cov_stat", "bvcf_config_covar_defaults",
 ]
 
 
@@ -483,6 +485,29 @@ class AssocInfo(C.Structure):
     _fields_ = [("recs", C.c_void_p), ("n_rows", C.c_uint64), ("need_rows", C.c_uint64), ("n_columns", C.c_uint32)]
 
 
+CONFIG_MORE_COVAR = 11  # BVCF_CONFIG_MORE_COVAR in Config.reserved[1]: the ConfigPca is the head of a ConfigCovar
+COVAR_MAX = 16  # BVCF_COVAR_MAX
+
+
+class ConfigCovar(C.Structure):
+    """bvcf_config_covar: a bvcf_config_pca and what came after it"""
+    _fields_ = [("pca", ConfigPca), ("covar_path", C.c_char_p)]
+
+
+class CovarTableStruct(C.Structure):
+    """bvcf_covar_table"""
+    _fields_ = [("n_covars", C.c_uint32), ("n_samples", C.c_uint32), ("s64", C.c_uint32), ("n_columns", C.c_uint32),
+                ("n_groups", C.c_uint32), ("lc", C.c_uint32), ("lcc", C.c_uint32), ("lcy", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("row_words", C.c_uint32), ("n_named", C.c_uint64), ("n_incomplete", C.c_uint64), ("b", C.c_void_p), ("c", C.c_void_p),
+                ("complete", C.c_void_p), ("group_of", C.c_void_p), ("group_first", C.c_void_p), ("pheno_np", C.c_void_p),
+                ("totals", C.c_void_p), ("names", C.c_void_p), ("names_bytes", C.c_uint64)]
+
+
+class AssocCovInfo(C.Structure):
+    """bvcf_assoc_cov_info"""
+    _fields_ = [("words", C.c_void_p), ("n_rows", C.c_uint64), ("row_words", C.c_uint32)]
+
+
 class PhenoTable:
     """a host phenotype table: bvcf_pheno_table_build over y / present (K lists of S integers Y and of S flags), or -- text=
     with sample_names= -- bvcf_pheno_table_parse over the bytes of a phenotype file  (host code, no device)"""
@@ -548,6 +573,18 @@ class PhenoTable:
         t = np.frombuffer(C.string_at(self.t.totals, PHENO_TOTALS_DTYPE.itemsize * self.n_columns), dtype=PHENO_TOTALS_DTYPE)
         return [(int(x["np"]), int(x["ay"]), (int(x["by_hi"]) << 64) | int(x["by_lo"])) for x in t]
 
+    def masked(self, complete):
+        """bvcf_pheno_table_mask: a new PhenoTable with P = 0 wherever complete (S flags) is 0"""
+        out = PhenoTable.__new__(PhenoTable)
+        out.t = PhenoTableStruct()
+        cp = np.ascontiguousarray(np.array(complete, dtype=np.uint8).reshape(self.n_samples))
+        keep = cp if cp.size else np.zeros(1, dtype=np.uint8)
+        lib.bvcf_pheno_table_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = lib.bvcf_pheno_table_mask(C.byref(self.t), keep.ctypes.data, C.byref(out.t))
+        if rc:
+            raise BvcfError(rc, "bvcf_pheno_table_mask")
+        return out
+
     def close(self):
         lib.bvcf_pheno_table_free.argtypes = [C.c_void_p]
         lib.bvcf_pheno_table_free(C.byref(self.t))
@@ -557,6 +594,94 @@ class PhenoTable:
             self.close()
         except Exception:
             pass
+
+
+class CovarTable:
+    """a host covariate table: bvcf_covar_table_build over c / complete (J lists of S integers C and S flags), or -- text= with
+    sample_names= -- bvcf_covar_table_parse over the bytes of a covariate file, which leaves an unbound table.  pheno= a MASKED
+    PhenoTable (PhenoTable.masked(table.complete)) binds the table to it: groups, totals and operand B  (host code, no device)"""
+
+    def __init__(self, c=None, complete=None, names=None, text=None, sample_names=None, n_named=0, pheno=None):
+        self.t = CovarTableStruct()
+        if text is not None:
+            sn = [bytes(x) for x in (sample_names or [])]
+            ptrs = (C.c_char_p * max(len(sn), 1))(*sn)
+            lens = (C.c_uint32 * max(len(sn), 1))(*[len(x) for x in sn])
+            err = C.create_string_buffer(512)
+            lib.bvcf_covar_table_parse.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_size_t]
+            rc = lib.bvcf_covar_table_parse(bytes(text), len(text), ptrs, lens, len(sn), C.byref(self.t), err, len(err))
+            if rc:
+                raise BvcfError(rc, err.value.decode(errors="replace"))
+            return
+        cc = np.ascontiguousarray(np.array(c, dtype=np.int64))
+        j, s = cc.shape
+        cp = np.ascontiguousarray(np.array(complete, dtype=np.uint8).reshape(s))
+        nm = b"".join(bytes(x) + b"\0" for x in (names or [b"COV%d" % (i + 1) for i in range(j)]))
+        lib.bvcf_covar_table_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_size_t, C.c_uint64,
+                                               C.c_void_p, C.c_void_p]
+        rc = lib.bvcf_covar_table_build(cc.ctypes.data if s else None, cp.ctypes.data if s else None, j, s, nm, len(nm), int(n_named),
+                                        C.byref(pheno.t) if pheno is not None else None, C.byref(self.t))
+        if rc:
+            raise BvcfError(rc, "bvcf_covar_table_build")
+
+    def bound(self, pheno):
+        """the same covariates bound to a masked PhenoTable"""
+        return CovarTable(self.c if self.n_samples else np.zeros((self.n_covars, 0), dtype=np.int64), self.complete, self.names,
+                          n_named=self.n_named, pheno=pheno)
+
+    n_covars = property(lambda self: int(self.t.n_covars))
+    n_samples = property(lambda self: int(self.t.n_samples))
+    s64 = property(lambda self: int(self.t.s64))
+    n_columns = property(lambda self: int(self.t.n_columns))
+    n_groups = property(lambda self: int(self.t.n_groups))
+    lc = property(lambda self: int(self.t.lc))
+    lcc = property(lambda self: int(self.t.lcc))
+    lcy = property(lambda self: int(self.t.lcy))
+    n_blocks = property(lambda self: int(self.t.n_blocks))
+    row_words = property(lambda self: int(self.t.row_words))
+    n_named = property(lambda self: int(self.t.n_named))
+    n_incomplete = property(lambda self: int(self.t.n_incomplete))
+
+    def _array(self, ptr, dtype, shape):
+        n = int(np.prod(shape))
+        if not n:
+            return np.zeros(shape, dtype=dtype)
+        return np.frombuffer(C.string_at(ptr, n * np.dtype(dtype).itemsize), dtype=dtype).reshape(shape).copy()
+
+    @property
+    def names(self):
+        return C.string_at(self.t.names, self.t.names_bytes).split(b"\0")[:-1] if self.t.names_bytes else []
+
+    b = property(lambda self: self._array(self.t.b, np.int8, (16 * self.n_blocks, self.s64)))
+    c = property(lambda self: self._array(self.t.c, np.int64, (self.n_covars, self.n_samples)))
+    complete = property(lambda self: self._array(self.t.complete, np.uint8, (self.n_samples,)))
+    group_of = property(lambda self: [int(x) for x in self._array(self.t.group_of, np.uint32, (self.n_columns,))])
+    group_first = property(lambda self: [int(x) for x in self._array(self.t.group_first, np.uint32, (self.n_groups,))])
+    totals = property(lambda self: self._array(self.t.totals, np.uint64, (self.row_words,)))
+
+    def close(self):
+        lib.bvcf_covar_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_covar_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def assoc_cov_stat(table, k, rec, totals, cov_row):
+    """bvcf_assoc_cov_stat: phenotype k of a row from its record (as assoc_stat's), the phenotype's totals and the row's
+    covariate record (row_words uint64) against a bound CovarTable -> (flags, [n, altFreq, beta, se, chisq, p]); flags bit 2:
+    collinear  (host code, no device)"""
+    r, t = _assoc_structs(rec, totals)
+    w = np.ascontiguousarray(cov_row, dtype=np.uint64)
+    assert w.size == table.row_words
+    out = (C.c_double * 6)()
+    lib.bvcf_assoc_cov_stat.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    flags = lib.bvcf_assoc_cov_stat(C.byref(table.t), int(k), r.ctypes.data, t.ctypes.data, w.ctypes.data, out)
+    return int(flags), list(out)
 
 
 def assoc_value(text):
@@ -942,7 +1067,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--score / --scoreOutput / --scoreReport: the struct behind that one and its marker, only then)
     # (--pheno / --assoc / --assocReport: the struct behind that one and its marker, only then)
     # (--pca / --pcaCount / --pcaReport: the struct behind that one and its marker, only then)
-    pc = ConfigPca() if any(cfg.get(k) for k in ("pca", "pcaCount", "pcaReport")) else None
+    # (--covar: the struct behind that one and its marker, only then)
+    cvc = ConfigCovar() if cfg.get("covar") else None
+    pc = cvc.pca if cvc is not None else ConfigPca() if any(cfg.get(k) for k in ("pca", "pcaCount", "pcaReport")) else None
     ac = pc.assoc if pc is not None else ConfigAssoc() if any(cfg.get(k) for k in ("pheno", "assoc", "assocReport")) else None
     sc = ac.score if ac is not None else ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
     gc = sc.grm if sc is not None else ConfigGrm() if cfg.get("grm") else None
@@ -1064,6 +1191,10 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
                 setattr(pc, field, keep[-1])
         pc.pca_count = int(cfg.get("pcaCount") or PCA_DEFAULT_COMPONENTS)
         c.reserved[1] = CONFIG_MORE_PCA
+    if cvc is not None:  # the covariate file of the scan
+        keep.append(str(cfg["covar"]).encode())
+        cvc.covar_path = keep[-1]
+        c.reserved[1] = CONFIG_MORE_COVAR
     c._keep = keep
     return c
 
@@ -1629,7 +1760,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None, regions=None, grm=False, score=None, pheno=None):
+                 variants=None, regions=None, grm=False, score=None, pheno=None, covar=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1665,6 +1796,13 @@ class Ctx:
                 self.close()
                 raise BvcfError(rc, msg)
             self.assoc_columns = pheno.n_columns
+        if covar is not None:  # bvcf_set_covar_table: a CovarTable bound to pheno; the covariate records beside (assoc_cov())
+            lib.bvcf_set_covar_table.argtypes = [C.c_void_p, C.c_void_p]
+            rc = lib.bvcf_set_covar_table(self.h, C.byref(covar.t))
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
         if grm:  # bvcf_enable_grm: the GRM's integer tables behind every chain (read with grm() / grm_words())
             lib.bvcf_enable_grm.argtypes = [C.c_void_p]
             rc = lib.bvcf_enable_grm(self.h)
@@ -2026,6 +2164,24 @@ class Ctx:
             return np.zeros((0, k), dtype=ASSOC_REC_DTYPE)
         raw = (C.c_uint8 * (n * k * ASSOC_REC_DTYPE.itemsize)).from_address(info.recs)
         return np.frombuffer(raw, dtype=ASSOC_REC_DTYPE).reshape(n, k).copy()
+
+    def assoc_cov(self):
+        """bvcf_assoc_cov: the batch collected last -> its covariate records, uint64 (n_rows, row_words), copied out of the slot"""
+        info = AssocCovInfo()
+        lib.bvcf_assoc_cov.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_assoc_cov(self.h, C.byref(info)))
+        n, w = int(info.n_rows), int(info.row_words)
+        if not n or not info.words:
+            return np.zeros((0, w), dtype=np.uint64)
+        raw = (C.c_uint8 * (n * w * 8)).from_address(info.words)
+        return np.frombuffer(raw, dtype=np.uint64).reshape(n, w).copy()
+
+    def bench_assoc_cov_kernels(self):
+        """the covariate kernels over the first slot's last bench chain -> ms of [k_assoc_cov_gemm, k_assoc_cov_sparse]"""
+        ms = (C.c_float * 2)()
+        lib.bvcf_bench_assoc_cov_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_assoc_cov_kernels(self.h, ms))
+        return list(ms)
 
     def reserve_assoc_rows(self, n):
         """bvcf_reserve_assoc_rows: grow the arena of the records (no batch in flight)"""

@@ -192,6 +192,18 @@ struct AssocSlot {
   DevBuf<uint2> dense, sparse;
   DevBuf<uint32_t> ctr;
   Arena<bvcf_assoc_rec> rec;
+  Arena<unsigned long long> cov;  // bvcf_set_covar_table: the covariate records [rows][cov.l.w], in words
+};
+// bvcf_set_covar_table (bvcf_assoc_cov.hip.h): k_assoc_cov_gemm / k_assoc_cov_sparse behind the scan's own kernels.  The
+// layout, operand B, the int64 table, the groups' phenotypes and the totals row are the ctx's
+struct AssocCovCtx {
+  bool on = false;
+  AssocCovLayout l{};
+  DevBuf<int8_t> b;
+  DevBuf<long long> c;
+  DevBuf<uint32_t> rep;
+  DevBuf<unsigned long long> tot;
+  bvcf_assoc_cov_info last{};
 };
 struct AssocCtx {
   bool asked = false, on = false;
@@ -201,6 +213,9 @@ struct AssocCtx {
   DevBuf<bvcf_pheno_totals> tot;
   uint64_t cap = 0;
   bvcf_assoc_info last{};
+  std::vector<uint64_t> np;  // NP per phenotype: what a covariate table must be bound to
+  bool cov_asked = false;
+  AssocCovCtx cov;
 };
 
 }  // namespace
@@ -1408,7 +1423,11 @@ int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
 // ---- the association scan
 
 // a slot's arena holds at most 1 GiB of records
-static uint64_t assoc_max_rows(const bvcf_ctx *c) { return (1ull << 30) / (sizeof(bvcf_assoc_rec) * std::max<uint32_t>(c->assoc.K, 1u)); }
+// a row's bytes in a slot's two arenas: the phenotypes' records and -- with a covariate table -- the covariate record
+static uint64_t assoc_row_bytes(const bvcf_ctx *c) {
+  return sizeof(bvcf_assoc_rec) * std::max<uint32_t>(c->assoc.K, 1u) + (c->assoc.cov.on ? 8ull * c->assoc.cov.l.w : 0ull);
+}
+static uint64_t assoc_max_rows(const bvcf_ctx *c) { return (1ull << 30) / assoc_row_bytes(c); }
 
 // bvcf_set_pheno_table: the row lists (they follow max_alleles) and the cursors; the records' arena and its pinned copy when
 // the ctx's bound has grown past what the slot holds
@@ -1420,13 +1439,14 @@ static int alloc_assoc(bvcf_ctx *c, Slot &s) {
     HIP_TRY(c, s.assoc.sparse.alloc(c->max_alleles));
   }
   HIP_TRY(c, s.assoc.rec.grow_to(c->assoc.cap * c->assoc.K));
+  if (c->assoc.cov.on) HIP_TRY(c, s.assoc.cov.grow_to(c->assoc.cap * c->assoc.cov.l.w));
   return BVCF_OK;
 }
 
 // the slot holds the row index and everything the scan's kernels write
 static bool assoc_ready(const bvcf_ctx *c, const Slot &s) {
   return s.assoc.rec.d && s.assoc.ctr && s.assoc.dense.size() >= c->max_alleles && s.assoc.sparse.size() >= c->max_alleles &&
-         index_ready(c, s);
+         (!c->assoc.cov.on || s.assoc.cov.d) && index_ready(c, s);
 }
 
 static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
@@ -1441,6 +1461,12 @@ static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
   sa.ctr = s.assoc.ctr;
   sa.rec = s.assoc.rec.d;
   sa.cap_rows = s.assoc.rec.cap / c->assoc.K;
+  if (c->assoc.cov.on) {  // (a batch whose rows outrun either arena writes nothing)
+    sa.cap_rows = std::min<unsigned long long>(sa.cap_rows, s.assoc.cov.cap / c->assoc.cov.l.w);
+    sa.cov = s.assoc.cov.d;
+    sa.cov_tot = c->assoc.cov.tot;
+    sa.cov_w = c->assoc.cov.l.w;
+  }
   sa.row_cap = (uint32_t)s.idx.src.size();
   sa.list_cap = (uint32_t)s.assoc.sparse.size();  // (the second of the two lists: there when both are)
   sa.K = c->assoc.K;
@@ -1451,6 +1477,26 @@ static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
   sa.s64 = c->assoc.s64;
   sa.ns = c->n_samples;
   return sa;
+}
+
+static AssocCovArgs make_assoc_cov_args(bvcf_ctx *c, Slot &s) {
+  AssocCovArgs ca{};
+  ca.l = c->assoc.cov.l;
+  ca.b = c->assoc.cov.b;
+  ca.c = c->assoc.cov.c;
+  ca.rep = c->assoc.cov.rep;
+  ca.cov = s.assoc.cov.d;
+  return ca;
+}
+
+// bvcf_set_covar_table: behind k_assoc_list's lists, the two kernels of bvcf_assoc_cov.hip.h -- the dense rows' tiles dealt
+// over blockIdx.x, the column slices over blockIdx.y
+static void launch_assoc_cov(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const AssocArgs &sa, const AssocCovArgs &ca,
+                             const Event *ev = nullptr) {
+  const uint32_t gx = std::max<uint32_t>(16u, (uint32_t)c->n_cu * 4u / ca.l.n_slices);
+  hipLaunchKernelGGL(k_assoc_cov_gemm, dim3(gx, ca.l.n_slices), dim3(kWgThreads), 0, st, a, sa, ca);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_assoc_cov_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa, ca);
 }
 
 // bvcf_set_pheno_table: behind the row index, the cursors from zero and the three kernels (bvcf_assoc.hip.h; bvcf_collect
@@ -1477,12 +1523,27 @@ static bvcf_assoc_info assoc_need(bvcf_ctx *c, const Slot &s) {
   c->assoc.last = bvcf_assoc_info{};
   c->assoc.last.n_columns = t.n_columns;
   c->assoc.last.need_rows = t.need_rows;
+  c->assoc.cov.last = bvcf_assoc_cov_info{};
+  c->assoc.cov.last.row_words = c->assoc.cov.l.w;
   return t;
+}
+// the batch's rows fit both arenas
+static bool assoc_fits(const bvcf_ctx *c, const Slot &s, const bvcf_assoc_info &t) {
+  return s.assoc.rec.fits(t.need_rows * t.n_columns) && (!c->assoc.cov.on || s.assoc.cov.fits(t.need_rows * c->assoc.cov.l.w));
 }
 static int assoc_copy(bvcf_ctx *c, Slot &s, const bvcf_assoc_info &t) {
   if (t.n_rows)
     HIP_TRY(c, hipMemcpyAsync(s.assoc.rec.h, s.assoc.rec.d, t.n_rows * t.n_columns * sizeof(bvcf_assoc_rec), hipMemcpyDeviceToHost, s.stream));
+  if (t.n_rows && c->assoc.cov.on)
+    HIP_TRY(c, hipMemcpyAsync(s.assoc.cov.h, s.assoc.cov.d, t.n_rows * c->assoc.cov.l.w * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   return BVCF_OK;
+}
+// published with the records: the covariate records of the same batch
+static void assoc_publish(bvcf_ctx *c, const Slot &s, const bvcf_assoc_info &t) {
+  c->assoc.last = t;
+  if (!c->assoc.cov.on) return;
+  c->assoc.cov.last.words = reinterpret_cast<const uint64_t *>(s.assoc.cov.h.get());
+  c->assoc.cov.last.n_rows = t.n_rows;
 }
 
 void bvcf_pheno_table_free(bvcf_pheno_table *t) {
@@ -1699,6 +1760,8 @@ int bvcf_set_pheno_table(bvcf_ctx *c, const bvcf_pheno_table *t) {
   c->assoc.K = K;
   c->assoc.last = bvcf_assoc_info{};
   c->assoc.last.n_columns = K;
+  c->assoc.np.resize(K);
+  for (uint32_t k = 0; k < K; k++) c->assoc.np[k] = t->totals[k].np;
   if (!ns) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
   HIP_TRY(c, hipSetDevice(c->device));
   // B on the device: the PY columns from column 0, the Q columns from the next whole block of 16, zero columns between
@@ -1729,8 +1792,10 @@ int bvcf_set_pheno_table(bvcf_ctx *c, const bvcf_pheno_table *t) {
 int bvcf_reserve_assoc_rows(bvcf_ctx *c, uint64_t rows) {
   if (!c) return BVCF_E_ARG;
   if (c->assoc.on && !c->in_flight && rows > assoc_max_rows(c)) {
-    c->err = "bvcf_reserve_assoc_rows: " + std::to_string(rows) + " rows x " + std::to_string(c->assoc.K) +
-             " columns: a slot's records would pass 1 GiB: use fewer columns or smaller batches (max_batch_bytes)";
+    c->err = "bvcf_reserve_assoc_rows: " + std::to_string(rows) + " rows x " + std::to_string(c->assoc.K) + " columns" +
+             (c->assoc.cov.on ? " and " + std::to_string(c->assoc.cov.l.J) + " covariates" : std::string()) +
+             ": a slot's records would pass 1 GiB: use fewer columns" + (c->assoc.cov.on ? ", fewer covariates" : "") +
+             " or smaller batches (max_batch_bytes)";
     return BVCF_E_TOO_BIG;
   }
   return reserve_arena(c, "bvcf_reserve_assoc_rows", "bvcf_set_pheno_table", c->assoc.asked, c->assoc.on, rows, assoc_max_rows(c),
@@ -1783,6 +1848,363 @@ int bvcf_assoc_stat(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, 
   return assoc_stat(assoc_ints(assoc_sums_of(rec, totals)), out);
 }
 
+// ---- the scan's covariates
+
+void bvcf_covar_table_free(bvcf_covar_table *t) {
+  if (!t) return;
+  free((void *)t->b);
+  free((void *)t->c);
+  free((void *)t->complete);
+  free((void *)t->group_of);
+  free((void *)t->group_first);
+  free((void *)t->pheno_np);
+  free((void *)t->totals);
+  free((void *)t->names);
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_pheno_table_mask(const bvcf_pheno_table *t, const uint8_t *complete, bvcf_pheno_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (!pheno_table_sound(t) || (t->n_samples && !complete)) return BVCF_E_ARG;
+  const uint32_t k = t->n_columns, s = t->n_samples;
+  std::vector<uint8_t> p((size_t)k * s);
+  for (uint32_t c = 0; c < k; c++)
+    for (uint32_t i = 0; i < s; i++) p[(size_t)c * s + i] = t->present[(size_t)c * s + i] && complete[i];
+  return bvcf_pheno_table_build(t->y, p.data(), k, s, t->names, t->names_bytes, t->n_named, out);
+}
+
+int bvcf_covar_table_build(const int64_t *c, const uint8_t *complete, uint32_t j, uint32_t s, const char *names, size_t names_bytes,
+                           uint64_t n_named, const bvcf_pheno_table *pheno, bvcf_covar_table *out) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  if (j < 1 || j > BVCF_COVAR_MAX || (s && (!c || !complete)) || (names_bytes && !names)) return BVCF_E_ARG;
+  if (s > BVCF_ASSOC_MAX_SAMPLES) return BVCF_E_TOO_BIG;
+  if (pheno && (!pheno_table_sound(pheno) || pheno->n_samples != s)) return BVCF_E_ARG;
+  const uint32_t K = pheno ? pheno->n_columns : 0u, s64 = (s + 63u) & ~63u;
+  uint64_t n_incomplete = 0;
+  for (uint32_t i = 0; i < s; i++) {
+    n_incomplete += complete[i] ? 0u : 1u;
+    for (uint32_t q = 0; q < j && complete[i]; q++)
+      if (c[(size_t)q * s + i] > BVCF_ASSOC_MAX_Y || c[(size_t)q * s + i] < -BVCF_ASSOC_MAX_Y) return BVCF_E_ARG;
+    for (uint32_t k = 0; k < K && !complete[i]; k++)
+      if (pheno->present[(size_t)k * s + i]) return BVCF_E_ARG;  // (the table is not the masked one)
+  }
+  // the mask groups, in order of their first phenotype
+  std::vector<uint32_t> group_of(K), first;
+  for (uint32_t k = 0; k < K; k++) {
+    uint32_t g = 0;
+    for (; g < first.size(); g++)
+      if (!s || !memcmp(pheno->present + (size_t)first[g] * s, pheno->present + (size_t)k * s, s)) break;
+    if (g == first.size()) first.push_back(k);
+    group_of[k] = g;
+  }
+  const uint32_t G = (uint32_t)first.size();
+  // the limb counts: the smallest that hold the values a column can get
+  uint32_t lc = 1, lcc = 1, lcy = 1;
+  int8_t lim[16];
+  uint64_t lo, hi;
+  for (uint32_t i = 0; i < s && K; i++) {
+    if (!complete[i]) continue;
+    for (uint32_t q = 0; q < j; q++) {
+      const int64_t x = c[(size_t)q * s + i];
+      lc = std::max(lc, (uint32_t)assoc_limbs(x, lim));
+      for (uint32_t p = 0; p <= q; p++) {
+        assoc_mul128(c[(size_t)p * s + i], x, &lo, &hi);
+        lcc = std::max(lcc, (uint32_t)assoc_limbs128(lo, hi, lim));
+      }
+      for (uint32_t k = 0; k < K; k++) {
+        if (!pheno->present[(size_t)k * s + i]) continue;
+        assoc_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
+        lcy = std::max(lcy, (uint32_t)assoc_limbs128(lo, hi, lim));
+      }
+    }
+  }
+  const AssocCovLayout l = assoc_cov_layout(j, K, G, lc, lcc, lcy);
+  const size_t n_b = pheno ? (size_t)16u * l.n_blocks * s64 : 0;
+  int8_t *b = (int8_t *)calloc(n_b + 1, 1);
+  int64_t *cc = (int64_t *)calloc((size_t)j * s + 1, sizeof(int64_t));
+  uint8_t *cp = (uint8_t *)calloc((size_t)s + 1, 1);
+  uint32_t *go = (uint32_t *)calloc(K + 1, sizeof(uint32_t)), *gf = (uint32_t *)calloc(G + 1, sizeof(uint32_t));
+  uint64_t *np = (uint64_t *)calloc(K + 1, sizeof(uint64_t)), *tot = (uint64_t *)calloc((pheno ? l.w : 0u) + 1, sizeof(uint64_t));
+  char *nm = (char *)malloc(names_bytes + 1);
+  if (!b || !cc || !cp || !go || !gf || !np || !tot || !nm) {
+    for (void *p : {(void *)b, (void *)cc, (void *)cp, (void *)go, (void *)gf, (void *)np, (void *)tot, (void *)nm}) free(p);
+    return BVCF_E_NOMEM;
+  }
+  if (names_bytes) memcpy(nm, names, names_bytes);
+  for (uint32_t i = 0; i < s; i++) {
+    cp[i] = complete[i] ? 1 : 0;
+    for (uint32_t q = 0; q < j && cp[i]; q++) cc[(size_t)q * s + i] = c[(size_t)q * s + i];
+  }
+  for (uint32_t k = 0; k < K; k++) go[k] = group_of[k], np[k] = pheno->totals[k].np;
+  for (uint32_t g = 0; g < G; g++) gf[g] = first[g];
+  // the columns and the totals row: per group C_j and C_p C_j over the group's samples, per phenotype C_j Y_k over its own
+  const auto put = [&](uint32_t col, uint32_t limbs, uint32_t i) {
+    for (uint32_t a = 0; a < limbs; a++) b[(size_t)(col + a) * s64 + i] = lim[a];
+  };
+  for (uint32_t i = 0; i < s && K; i++) {
+    if (!cp[i]) continue;
+    for (uint32_t q = 0; q < j; q++) {
+      const int64_t x = cc[(size_t)q * s + i];
+      for (uint32_t g = 0; g < G; g++) {
+        if (!pheno->present[(size_t)first[g] * s + i]) continue;
+        const uint32_t v = g * j + q;
+        assoc_limbs(x, lim);
+        put(assoc_cov_column(0, l.vc, lc, v), lc, i);
+        tot[assoc_cov_word_c(l, v, 2)] += (uint64_t)x;
+        for (uint32_t p = 0; p <= q; p++) {
+          const uint32_t vv = g * l.np2 + q * (q + 1u) / 2u + p;
+          assoc_mul128(cc[(size_t)p * s + i], x, &lo, &hi);
+          assoc_limbs128(lo, hi, lim);
+          put(assoc_cov_column(l.bc, l.vcc, lcc, vv), lcc, i);
+          uint64_t *w = tot + assoc_cov_word_cc(l, vv);
+          assoc_add128w(w, w + 1, lo, hi);
+        }
+      }
+      for (uint32_t k = 0; k < K; k++) {
+        if (!pheno->present[(size_t)k * s + i]) continue;
+        const uint32_t v = k * j + q;
+        assoc_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
+        assoc_limbs128(lo, hi, lim);
+        put(assoc_cov_column(l.bc + l.bcc, l.vcy, lcy, v), lcy, i);
+        uint64_t *w = tot + assoc_cov_word_cy(l, v);
+        assoc_add128w(w, w + 1, lo, hi);
+      }
+    }
+  }
+  out->n_covars = j;
+  out->n_samples = s;
+  out->s64 = s64;
+  out->n_columns = K;
+  out->n_groups = G;
+  out->lc = lc, out->lcc = lcc, out->lcy = lcy;
+  out->n_blocks = pheno ? l.n_blocks : 0u;
+  out->row_words = pheno ? l.w : 0u;
+  out->n_named = n_named;
+  out->n_incomplete = n_incomplete;
+  out->b = b;
+  out->c = cc;
+  out->complete = cp;
+  out->group_of = go;
+  out->group_first = gf;
+  out->pheno_np = np;
+  out->totals = tot;
+  out->names = nm;
+  out->names_bytes = names_bytes;
+  return BVCF_OK;
+}
+
+// the file's rules (bvcf_config_covar.covar_path); every refusal names its line in err
+int bvcf_covar_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
+                           bvcf_covar_table *out, char *err, size_t err_cap) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  std::string msg;
+  const auto fail = [&](uint64_t line, const std::string &what, int rc) {
+    msg = line ? "line " + std::to_string(line) + ": " + what : what;
+    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
+    return rc;
+  };
+  if ((n && !text) || (s && (!sample_names || !sample_lens))) return BVCF_E_ARG;
+  if (s > BVCF_ASSOC_MAX_SAMPLES) return fail(0, std::to_string(s) + " samples, more than 2^22", BVCF_E_TOO_BIG);
+  std::unordered_map<std::string_view, std::pair<uint32_t, uint32_t>> cols;
+  for (uint32_t i = 0; i < s; i++) {
+    auto ins = cols.emplace(std::string_view(sample_names[i], sample_lens[i]), std::make_pair(i, 0u));
+    ins.first->second.second++;
+  }
+  std::vector<int64_t> c;
+  std::vector<uint8_t> complete(s, 0);
+  std::vector<uint64_t> line_of(s, 0);
+  std::string names;
+  uint32_t j = 0, lead = 1;  // lead: the name fields of a line -- two behind a "#FID \t IID" header
+  uint64_t line_no = 0, n_named = 0;
+  bool first = true;
+  std::vector<std::string_view> f;
+  std::vector<int64_t> vals;
+  for (size_t at = 0; at < n;) {
+    const char *nl = (const char *)memchr(text + at, '\n', n - at);
+    size_t end = nl ? (size_t)(nl - text) : n;
+    const size_t next = nl ? end + 1 : n;
+    line_no++;
+    if (end > at && text[end - 1] == '\r') end--;
+    const std::string_view line(text + at, end - at);
+    at = next;
+    if (line.empty()) continue;
+    f.clear();
+    for (size_t p = 0;;) {
+      const size_t t = line.find('\t', p);
+      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
+      if (t == std::string_view::npos) break;
+      p = t + 1;
+    }
+    const bool header = line[0] == '#';
+    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
+    if (first) {
+      if (header && f.size() >= 2 && f[0] == "#FID" && f[1] == "IID") lead = 2;
+      if (f.size() < lead + 1u || f.size() - lead > BVCF_COVAR_MAX)
+        return fail(line_no, "want a sample and 1 to " + std::to_string(BVCF_COVAR_MAX) + " covariates, tab-separated", BVCF_E_ARG);
+      j = (uint32_t)(f.size() - lead);
+      first = false;
+      c.assign((size_t)j * s, 0);
+      if (header) {
+        if (lead == 1 && f[0] != "#sample") return fail(line_no, "a header starts with \"#sample\", or with \"#FID\" and \"IID\"", BVCF_E_ARG);
+        for (uint32_t q = 0; q < j; q++) {
+          if (f[lead + q].empty()) return fail(line_no, "an empty covariate name", BVCF_E_ARG);
+          for (uint32_t d = 0; d < q; d++)
+            if (f[lead + d] == f[lead + q]) return fail(line_no, "the covariate name " + std::string(f[lead + q]) + " twice", BVCF_E_ARG);
+          names.append(f[lead + q]);
+          names.push_back('\0');
+        }
+        continue;
+      }
+      for (uint32_t q = 0; q < j; q++) {
+        names.append("COV" + std::to_string(q + 1));
+        names.push_back('\0');
+      }
+    }
+    if (f.size() != (size_t)j + lead) return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(j + lead), BVCF_E_ARG);
+    const std::string_view name = f[lead - 1u];
+    if (name.empty()) return fail(line_no, "an empty sample name", BVCF_E_ARG);
+    vals.assign(j, 0);
+    bool whole = true;
+    for (uint32_t q = 0; q < j; q++) {
+      const std::string_view x = f[lead + q];
+      if (x == "NA") {
+        whole = false;
+        continue;
+      }
+      const int rc = assoc_value(x.data(), x.size(), &vals[q]);
+      if (rc == -2) return fail(line_no, "the value " + std::string(x) + " is above 10^6 in size", BVCF_E_ARG);
+      if (rc) return fail(line_no, "bad value \"" + std::string(x.substr(0, 80)) + "\"", BVCF_E_ARG);
+    }
+    const auto it = cols.find(name);
+    if (it == cols.end()) continue;  // (no (kept) sample: ignored)
+    if (it->second.second > 1) return fail(line_no, "the name " + std::string(name) + " matches more than one sample column", BVCF_E_ARG);
+    const uint32_t i = it->second.first;
+    if (line_of[i]) return fail(line_no, "the sample " + std::string(name) + " is on line " + std::to_string(line_of[i]) + " already", BVCF_E_ARG);
+    line_of[i] = line_no;
+    n_named++;
+    complete[i] = whole ? 1 : 0;
+    for (uint32_t q = 0; q < j && whole; q++) c[(size_t)q * s + i] = vals[q];
+  }
+  if (first) return fail(0, "no line", BVCF_E_ARG);
+  const int rc = bvcf_covar_table_build(c.data(), complete.data(), j, s, names.data(), names.size(), n_named, nullptr, out);
+  if (rc) return fail(0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
+  return BVCF_OK;
+}
+
+// the table is a bound one bvcf_covar_table_build made: its counts agree with one another
+static bool covar_table_sound(const bvcf_covar_table *t) {
+  if (!t || t->n_covars < 1 || t->n_covars > BVCF_COVAR_MAX || t->n_columns < 1 || t->n_columns > BVCF_ASSOC_MAX_COLUMNS ||
+      t->n_groups < 1 || t->n_groups > t->n_columns || t->n_samples > BVCF_ASSOC_MAX_SAMPLES || t->s64 != ((t->n_samples + 63u) & ~63u) ||
+      t->lc < 1 || t->lc > BVCF_ASSOC_MAX_LIMBS1 || t->lcc < 1 || t->lcc > BVCF_ASSOC_MAX_LIMBS2 || t->lcy < 1 || t->lcy > BVCF_ASSOC_MAX_LIMBS2 ||
+      !t->b || !t->c || !t->complete || !t->group_of || !t->group_first || !t->pheno_np || !t->totals)
+    return false;
+  const AssocCovLayout l = assoc_cov_layout(t->n_covars, t->n_columns, t->n_groups, t->lc, t->lcc, t->lcy);
+  if (t->n_blocks != l.n_blocks || t->row_words != l.w) return false;
+  for (uint32_t k = 0; k < t->n_columns; k++)
+    if (t->group_of[k] >= t->n_groups) return false;
+  for (uint32_t g = 0; g < t->n_groups; g++)
+    if (t->group_first[g] >= t->n_columns || t->group_of[t->group_first[g]] != g) return false;
+  return true;
+}
+
+int bvcf_set_covar_table(bvcf_ctx *c, const bvcf_covar_table *t) {
+  if (!c) return BVCF_E_ARG;
+  if (!covar_table_sound(t)) {
+    c->err = "bvcf_set_covar_table: want a table as bvcf_covar_table_build makes it, bound to a phenotype table";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_covar_table")) return rc;
+  if (!c->assoc.asked) {
+    c->err = "bvcf_set_covar_table: bvcf_set_pheno_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (c->assoc.cov_asked) {
+    c->err = "bvcf_set_covar_table: the ctx has a covariate table";
+    return BVCF_E_ARG;
+  }
+  bool same = t->n_samples == c->n_samples && t->n_columns == c->assoc.K;
+  for (uint32_t k = 0; same && k < t->n_columns; k++) same = t->pheno_np[k] == c->assoc.np[k];
+  if (!same) {
+    c->err = "bvcf_set_covar_table: the table is not bound to the ctx's phenotype table (samples, columns or NP differ)";
+    return BVCF_E_ARG;
+  }
+  const AssocCovLayout l = assoc_cov_layout(t->n_covars, t->n_columns, t->n_groups, t->lc, t->lcc, t->lcy);
+  const uint64_t row_bytes = sizeof(bvcf_assoc_rec) * c->assoc.K + 8ull * l.w;
+  if (c->assoc.on && c->assoc.cap * row_bytes > (1ull << 30)) {
+    c->err = "bvcf_set_covar_table: " + std::to_string(c->assoc.cap) + " rows x " + std::to_string(c->assoc.K) + " columns and " +
+             std::to_string(l.J) + " covariates: a slot's records would take " + std::to_string(c->assoc.cap * row_bytes) +
+             " bytes, more than 1 GiB: use fewer columns, fewer covariates or smaller batches (max_batch_bytes)";
+    return BVCF_E_TOO_BIG;
+  }
+  c->assoc.cov_asked = true;
+  c->assoc.cov.l = l;
+  c->assoc.cov.last = bvcf_assoc_cov_info{};
+  c->assoc.cov.last.row_words = l.w;
+  if (!c->assoc.on) return BVCF_OK;  // (no sample columns: no rows, nothing allocated or launched)
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t b_bytes = (size_t)16u * l.n_blocks * t->s64, ns = c->n_samples;
+  HIP_TRY(c, c->assoc.cov.b.alloc(b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemset(c->assoc.cov.b, 0, b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->assoc.cov.b, t->b, b_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.cov.c.alloc((size_t)l.J * ns));
+  HIP_TRY(c, hipMemcpy(c->assoc.cov.c, t->c, (size_t)l.J * ns * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.cov.rep.alloc(l.G));
+  HIP_TRY(c, hipMemcpy(c->assoc.cov.rep, t->group_first, (size_t)l.G * sizeof(uint32_t), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.cov.tot.alloc(l.w));
+  HIP_TRY(c, hipMemcpy(c->assoc.cov.tot, t->totals, (size_t)l.w * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  c->assoc.cov.on = true;
+  for (auto &s : c->slots)
+    if (const int rc = alloc_assoc(c, s)) return rc;
+  return BVCF_OK;
+}
+
+int bvcf_assoc_cov(bvcf_ctx *c, bvcf_assoc_cov_info *out) {
+  if (!c || !out) return BVCF_E_ARG;
+  if (!c->assoc.cov_asked) {
+    c->err = "bvcf_assoc_cov: bvcf_set_covar_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  *out = c->assoc.cov.last;
+  return BVCF_OK;
+}
+
+int bvcf_assoc_cov_stat(const bvcf_covar_table *t, uint32_t k, const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals,
+                        const uint64_t *cov_row, double out[6]) {
+  if (!rec || !totals || !cov_row || !out || !covar_table_sound(t) || k >= t->n_columns) return -1;
+  const AssocCovLayout l = assoc_cov_layout(t->n_covars, t->n_columns, t->n_groups, t->lc, t->lcc, t->lcy);
+  AssocCovGram q;
+  assoc_cov_gram(l, k, t->group_of[k], assoc_sums_of(rec, totals), cov_row, t->totals, &q);
+  return assoc_cov_stat(q, out);
+}
+
+// (as bvcf_bench_assoc_kernels, the lists made once more first: ms = {k_assoc_cov_gemm, k_assoc_cov_sparse})
+int bvcf_bench_assoc_cov_kernels(bvcf_ctx *c, float ms[2]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[3];
+  if (const int rc = start_hook(c, "bvcf_bench_assoc_cov_kernels", c->assoc.on && c->assoc.cov.on && assoc_ready(c, s) && c->bench_src,
+                                "the ctx has no covariate table, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  launch_row_index(c, a, s.stream, make_bed_args(c, s));
+  const AssocArgs sa = make_assoc_args(c, s);
+  launch_assoc(c, a, s.stream, sa);
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_assoc_cov(c, a, s.stream, sa, make_assoc_cov_args(c, s), ev + 1);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  if (const int rc = finish_hook(c, ev, s.stream, ms)) return rc;
+  HIP_TRY(c, s.bed.rows.copy_total(s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  if (*s.bed.rows.h_total > sa.cap_rows) {
+    c->err = "bvcf_bench_assoc_cov_kernels: the rows outrun the arena (bvcf_reserve_assoc_rows): " + std::to_string(*s.bed.rows.h_total) + " rows";
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
 // (k_assoc_list reads the row index of the slot's last chain: the hook builds it once more first)
 int bvcf_bench_assoc_kernels(bvcf_ctx *c, float ms[3]) {
   if (!c || !ms) return BVCF_E_ARG;
@@ -1819,6 +2241,7 @@ static void launch_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *
   const BedArgs ba = make_bed_args(c, *slot);
   launch_row_index(c, a, st, ba);
   if (assoc) launch_assoc(c, a, st, make_assoc_args(c, *slot));
+  if (assoc && c->assoc.cov.on) launch_assoc_cov(c, a, st, make_assoc_args(c, *slot), make_assoc_cov_args(c, *slot));
   if (bed) launch_bed_rows(c, a, st, ba);
   if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
   if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)

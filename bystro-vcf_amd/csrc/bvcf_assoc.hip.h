@@ -70,6 +70,10 @@ struct AssocArgs {
   uint32_t row_cap, list_cap;
   uint32_t K, L1, L2, nb_py, nb_q;
   uint32_t s64, ns;
+  // bvcf_set_covar_table (bvcf_assoc_cov.hip.h): the rows' covariate records [cap_rows][cov_w] and the totals row; NULL / 0 without
+  unsigned long long *cov;
+  const unsigned long long *cov_tot;
+  uint32_t cov_w;
 };
 
 // the batch's rows, or 0 when they outrun the arena: nothing is written then
@@ -101,6 +105,8 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_list(AssocArgs sa) {
           o.b_mis_hi = t.by_hi;
           sa.rec[(size_t)r * sa.K + k] = o;
         }
+        // (and its covariate record: the missing-class sums are the totals, het / hom are zero -- the totals row)
+        for (uint32_t q = 0; q < sa.cov_w; q++) sa.cov[(size_t)r * sa.cov_w + q] = sa.cov_tot[q];
       } else {
         sparse = src.y != 0u;
         dense = !sparse;

@@ -1992,7 +1992,7 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   const bvcf_ld_info ld = ld_need(c, s);
   const bvcf_trio_info trio = trio_need(c, s);
   const bvcf_assoc_info assoc = assoc_need(c, s);
-  if (!k.need.fits || !s.assoc.rec.fits(assoc.need_rows * assoc.n_columns) || !s.bed.rows.fits(bed.need_bytes) || !s.trio.ev.fits(trio.need_events) || !s.bed.rows.fits(ld.need_row_bytes) ||
+  if (!k.need.fits || !assoc_fits(c, s, assoc) || !s.bed.rows.fits(bed.need_bytes) || !s.trio.ev.fits(trio.need_events) || !s.bed.rows.fits(ld.need_row_bytes) ||
       !s.ld.ev.fits(ld.need_events)) {
     r->status = BVCF_E_CAPACITY;
     r->need_lines = ctr.n_lines;
@@ -2030,7 +2030,7 @@ static int collect_slot(bvcf_ctx *c, Slot &s, bvcf_result *r) {
   c->bed.last = bed;  // (published: until here the reports held the needs alone)
   c->trio.last = trio;
   c->ld.last = ld;
-  c->assoc.last = assoc;
+  assoc_publish(c, s, assoc);
   add_totals(c, s, k, r);
   return BVCF_OK;
 }

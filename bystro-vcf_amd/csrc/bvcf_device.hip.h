@@ -66,6 +66,9 @@
 //    the dense rows' classes -- the map is the A operand, expanded in registers -- with the phenotypes' int8 limbs on the
 //    matrix cores, reducing over the samples into one record per (row, phenotype), k_assoc_sparse does the short lists --
 //    the exact integer sums behind --pheno / --assoc, bvcf_assoc.hip.h)
+//   (bvcf_set_covar_table, behind those: k_assoc_cov_gemm multiplies the same classes with the int8 limbs of the covariates and
+//    of their products, the column blocks dealt to workgroups as (tile, slice), k_assoc_cov_sparse does the short lists per
+//    (list, family) -- the exact Gram sums behind --covar, bvcf_assoc_cov.hip.h)
 //   (bvcf_pca_eigen, outside every chain and without a ctx: k_pca_expand, then per step k_pca_house / k_pca_symv / k_pca_w /
 //    k_pca_rank2 -- Householder tridiagonalisation of the relationship matrix in double --, and k_pca_back, the reflectors applied
 //    to the eigenvectors the host found for the tridiagonal matrix -- the solver behind --pca, bvcf_pca.hip.h)
@@ -139,6 +142,7 @@
 #include "bvcf_pca.hip.h"
 #include "bvcf_score.hip.h"
 #include "bvcf_assoc.hip.h"
+#include "bvcf_assoc_cov.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
 #include "bvcf_ld.hip.h"

@@ -875,6 +875,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.covar_on) {  // --covar: the covariate table bound to that one, and the second arena
+    rc = bvcf_set_covar_table(*ctx, &R.covar_table);
+    if (rc) {
+      *msg = std::string("bvcf_set_covar_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (rc == BVCF_OK && wants_plink(R.cfg)) {  // --plinkOutput: the .bed rows of every ctx of the run
     rc = bvcf_enable_bed_rows(*ctx);
     if (rc) {
@@ -1955,6 +1963,10 @@ int open_assoc(Run &R, std::string *msg) {
     *msg = "assoc_report_path without pheno_path";
     return BVCF_E_ARG;
   }
+  if (covar_path(R.cfg) && !have_p) {
+    *msg = "covar_path without pheno_path and assoc_path";
+    return BVCF_E_ARG;
+  }
   if (!have_p) return BVCF_OK;
   for (const auto &f : {std::pair<int *, const char *>{&R.assoc_fd, op}, std::pair<int *, const char *>{&R.assoc_report_fd, have_r ? rp : nullptr}}) {
     if (!f.second) continue;
@@ -1965,6 +1977,26 @@ int open_assoc(Run &R, std::string *msg) {
     }
   }
   R.assoc_on = true;
+  R.covar_on = covar_path(R.cfg) != nullptr;
+  return BVCF_OK;
+}
+
+// a whole file's bytes
+static int read_whole(const char *path, std::string *text, std::string *msg) {
+  FILE *f = fopen(path, "rb");
+  if (!f) {
+    *msg = std::string("open ") + path + ": " + strerror(errno);
+    return BVCF_E_FATAL;
+  }
+  char buf[1 << 16];
+  size_t got;
+  while ((got = fread(buf, 1, sizeof buf, f)) > 0) text->append(buf, got);
+  const int err = ferror(f) ? errno : 0;
+  fclose(f);
+  if (err) {
+    *msg = std::string("read ") + path + ": " + strerror(err);
+    return BVCF_E_FATAL;
+  }
   return BVCF_OK;
 }
 
@@ -2006,6 +2038,30 @@ int load_pheno(Run &R, std::string *msg) {
     *msg = std::string("pheno: ") + path + ": " + err;
     return BVCF_E_FATAL;
   }
+  if (R.covar_on) {
+    // --covar: the covariates of the same names; the phenotypes of the incomplete samples go; the table bound to what is left
+    const char *cpath = covar_path(R.cfg);
+    std::string ctext;
+    if (const int rc = read_whole(cpath, &ctext, msg)) return rc;
+    bvcf_covar_table raw{};
+    if (bvcf_covar_table_parse(ctext.data(), ctext.size(), names.data(), lens.data(), (uint32_t)ns, &raw, err, sizeof err)) {
+      *msg = std::string("covar: ") + cpath + ": " + err;
+      return BVCF_E_FATAL;
+    }
+    bvcf_pheno_table masked{};
+    int rc = bvcf_pheno_table_mask(&R.pheno_table, raw.complete, &masked);
+    bvcf_covar_table_free(&R.covar_table);
+    if (!rc) rc = bvcf_covar_table_build(raw.c, raw.complete, raw.n_covars, (uint32_t)ns, raw.names, raw.names_bytes, raw.n_named, &masked, &R.covar_table);
+    bvcf_covar_table_free(&raw);
+    if (rc) {
+      bvcf_pheno_table_free(&masked);
+      *msg = std::string("covar: ") + cpath + (rc == BVCF_E_NOMEM ? ": no memory" : ": bad table");
+      return BVCF_E_FATAL;
+    }
+    bvcf_pheno_table_free(&R.pheno_table);
+    R.pheno_table = masked;
+    R.assoc_collinear = 0;
+  }
   static const char kHead[] = "chrom\tpos\tref\talt\tpheno\tn\taltFreq\tbeta\tse\tchisq\tp\n";
   R.assoc_buf.assign(kHead, sizeof kHead - 1);
   R.assoc_rows = R.assoc_tested = 0;
@@ -2013,10 +2069,11 @@ int load_pheno(Run &R, std::string *msg) {
 }
 
 // a line per (row, phenotype): the rows bvcf_assoc numbers are the rows this loop visits, in this order, as for append_plink
-int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai) {
+int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai, const bvcf_assoc_cov_info *ci) {
   if (R.assoc_fd < 0 || !r->n_samples) return BVCF_OK;
   const uint32_t K = R.pheno_table.n_columns;
   if (ai.n_columns != K || (ai.n_rows && !ai.recs)) return BVCF_E_FATAL;
+  if (R.covar_on && (!ci || ci->n_rows != ai.n_rows || ci->row_words != R.covar_table.row_words || (ci->n_rows && !ci->words))) return BVCF_E_FATAL;
   const char *empty = or_default(R.cfg->empty_field, "!");
   std::vector<std::string_view> names;
   for (const char *nm = R.pheno_table.names, *e = nm + R.pheno_table.names_bytes; nm < e; nm += strlen(nm) + 1) names.emplace_back(nm);
@@ -2043,7 +2100,9 @@ int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_
       append_locus(locus, L, A, row, '\t', at);
       for (uint32_t c = 0; c < K; c++) {
         double st[6];
-        const int have = bvcf_assoc_stat(ai.recs + n_rows * K + c, R.pheno_table.totals + c, st);
+        const int have = R.covar_on ? bvcf_assoc_cov_stat(&R.covar_table, c, ai.recs + n_rows * K + c, R.pheno_table.totals + c,
+                                                          ci->words + n_rows * ci->row_words, st)
+                                    : bvcf_assoc_stat(ai.recs + n_rows * K + c, R.pheno_table.totals + c, st);
         if (have < 0) return BVCF_E_FATAL;
         o.append(locus);
         o.push_back('\t');
@@ -2064,6 +2123,7 @@ int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_
         }
         o.push_back('\n');
         if (have & 2) R.assoc_tested++;
+        if (have & 4) R.assoc_collinear++;
       }
       n_rows++;
     }
@@ -2083,8 +2143,11 @@ int close_assoc(Run &R, bool ok, std::string *msg) {
   if (ok) {
     bad = write_all(R.assoc_fd, R.assoc_buf.data(), R.assoc_buf.size()) != 0;
     if (!bad && R.assoc_report_fd >= 0) {
-      const std::string rep = "columns\t" + std::to_string(R.pheno_table.n_columns) + "\nsamples\t" + std::to_string(R.pheno_table.n_named) +
-                              "\nrows\t" + std::to_string(R.assoc_rows) + "\ntested\t" + std::to_string(R.assoc_tested) + "\n";
+      std::string rep = "columns\t" + std::to_string(R.pheno_table.n_columns) + "\nsamples\t" + std::to_string(R.pheno_table.n_named) +
+                        "\nrows\t" + std::to_string(R.assoc_rows) + "\ntested\t" + std::to_string(R.assoc_tested) + "\n";
+      if (R.covar_on)
+        rep += "covariates\t" + std::to_string(R.covar_table.n_covars) + "\nincomplete\t" + std::to_string(R.covar_table.n_incomplete) +
+               "\ncollinear\t" + std::to_string(R.assoc_collinear) + "\n";
       bad = write_all(R.assoc_report_fd, rep.data(), rep.size()) != 0;
     }
   } else {

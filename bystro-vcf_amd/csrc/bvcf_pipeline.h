@@ -185,6 +185,7 @@ struct FmtJob {
   bvcf_trio_info trio{};     // --mendel / --mendelErrors: bvcf_trio_stats of the batch (likewise)
   bvcf_ld_info ld{};         // --ld / --ldPrune: bvcf_ld_stats of the batch (likewise)
   bvcf_assoc_info assoc{};   // --pheno / --assoc: bvcf_assoc of the batch (likewise)
+  bvcf_assoc_cov_info assoc_cov{};  // --covar: bvcf_assoc_cov of the batch (likewise)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };

@@ -72,6 +72,8 @@ struct Cli {
   // extension: --pheno FILE --assoc PATH [--assocReport PATH], every row of the run against the file's phenotypes: the
   // additive score test / Cochran-Armitage trend test from exact integer sums (the dense rows on the device's matrix cores)
   std::string pheno, assoc, assoc_report;
+  // extension: --covar FILE (with --pheno and --assoc), the scan adjusted for the file's covariates: y ~ g + C_1 .. C_J
+  std::string covar;
   // extension: --pca PREFIX [--pcaCount K] [--pcaReport PATH], the top K principal components of the run's relationship
   // matrix as PREFIX.eigenvec / .eigenval (a dense symmetric eigensolver on the run's first device); --pcaCount alone is
   // accepted and does nothing
@@ -175,7 +177,7 @@ int parse(int argc, char **argv, Cli &c) {
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
         name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
         name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport" || name == "pheno" || name == "assoc" ||
-        name == "assocReport" || name == "pca" || name == "pcaCount" || name == "pcaReport") {
+        name == "assocReport" || name == "covar" || name == "pca" || name == "pcaCount" || name == "pcaReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -207,6 +209,12 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         (name == "score" ? c.score : name == "scoreOutput" ? c.score_output : c.score_report) = val;
+      } else if (name == "covar") {
+        if (val.empty()) {
+          fprintf(stderr, "invalid value \"\" for flag -covar: want the path of the file to read\n");
+          return 2;
+        }
+        c.covar = val;
       } else if (name == "pheno" || name == "assoc" || name == "assocReport") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -%s: want the path of the file to %s\n", name.c_str(), name == "pheno" ? "read" : "write");
@@ -329,6 +337,10 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-assocReport needs -pheno and -assoc\n");
     return 2;
   }
+  if (!c.covar.empty() && c.pheno.empty()) {
+    fprintf(stderr, "-covar needs -pheno and -assoc\n");
+    return 2;
+  }
   if (!c.pca_report.empty() && c.pca.empty()) {
     fprintf(stderr, "-pcaReport needs -pca\n");
     return 2;
@@ -389,8 +401,9 @@ int main(int argc, char **argv) {
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
   // regions and their report; behind those the --grm prefix; behind that the --score paths; behind those the --pheno / --assoc
   // paths; behind those the --pca prefix, count and report)
-  bvcf_config_pca pca_cfg;
-  bvcf_config_pca_defaults(&pca_cfg);
+  bvcf_config_covar covar_cfg;
+  bvcf_config_covar_defaults(&covar_cfg);
+  bvcf_config_pca &pca_cfg = covar_cfg.pca;
   bvcf_config_assoc &assoc_cfg = pca_cfg.assoc;
   bvcf_config_score &score_cfg = assoc_cfg.score;
   bvcf_config_grm &grm_cfg = score_cfg.grm;
@@ -481,6 +494,7 @@ int main(int argc, char **argv) {
   pca_cfg.pca_prefix = c.pca.c_str();
   pca_cfg.pca_count = c.pca_count;
   pca_cfg.pca_report_path = c.pca_report.c_str();
+  covar_cfg.covar_path = c.covar.c_str();
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -563,6 +563,85 @@ int bvcf_set_pheno_table(bvcf_ctx *ctx, const bvcf_pheno_table *t);
 int bvcf_reserve_assoc_rows(bvcf_ctx *ctx, uint64_t rows);
 int bvcf_assoc(bvcf_ctx *ctx, bvcf_assoc_info *out);
 int bvcf_assoc_stat(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals, double out[6]);
+/* Covariates for the scan: y ~ g + C_1 .. C_J.  J (1 .. 16) covariates give sample i integers C_j,i by the value rules of a
+ * phenotype (units of 10^-6, |C| <= 10^12).  A sample is INCOMPLETE when it has no value for some covariate; an incomplete
+ * sample has every phenotype missing, so the phenotype table a ctx gets is the masked one (bvcf_pheno_table_mask: P = 0,
+ * Y = 0 there; NP, AY, BY and operand B follow).  Two phenotypes with the same presence vector after that form one MASK
+ * GROUP (G <= K groups, numbered in order of their first phenotype).
+ * For a row and phenotype k the sample set is {P_k = 1 and the genotype called}, n its size.  With v_0 = 1, v_1 .. v_J = C_j,
+ * v_{J+1} = g (0 / 1 / 2) and v_{J+2} = Y_k the Gram matrix G[a][b] = sum v_a v_b over the set is exact: every entry is an
+ * integer below 2^103, and is a host total minus what the device summed over the row's missing samples, or a device sum
+ * over het / hom.  Per row the device writes a covariate record of row_words 64-bit words beside the bvcf_assoc_rec's:
+ *   per group g at g GW, GW = 3 J + J (J + 1):  C_het[J], C_hom[J], C_mis[J] (int64: sum C_j over the group's samples of the
+ *     class), then CC_mis[J (J + 1) / 2] as (lo, hi) pairs: sum C_i C_j over the missing ones, pair (i <= j) at j (j + 1) / 2 + i
+ *   per phenotype k at G GW + 2 J k:  CY_mis[J] as (lo, hi) pairs: sum C_j Y_k over the phenotype's missing samples
+ * and bvcf_covar_table.totals is the same layout summed over all samples of the group / phenotype in the missing-class
+ * places (zero in the het / hom places).  The dense rows are multiplied on the matrix cores (int8 limbs, int32 sums), the
+ * short lists added per list; every word has one writer.
+ * D[a][b] is the correctly rounded double of G[a][b]; then an unpivoted LDL^T in the order 0 .. J + 2, by exactly these IEEE
+ * double operations (no multiply-add contracted):
+ *   for a = 0 .. J+2:
+ *     for b = 0 .. a-1: s = D[a][b]; for t = 0 .. b-1: s = s - u[a][t] * L[b][t];  u[a][b] = s; L[a][b] = s / d[b]
+ *     s = D[a][a];      for t = 0 .. a-1: s = s - u[a][t] * L[a][t];               d[a] = s
+ * rss0 is s of the last row (a = J + 2) behind the term t = J: before the g term is subtracted.  A pivot d[a], a <= J + 1, is
+ * USABLE iff d[a] > D[a][a] 2^-30 -- the factor is part of the definition: collinear is a property of the data, not of
+ * rounding luck --, rss0 by the same rule against D[J+2][J+2].  The statistics exist iff n >= J + 3, every pivot is usable and
+ * rss0 is; with bg = L[J+2][J+1], ug = u[J+2][J+1]:
+ *   r2 = (ug * bg) / rss0 clamped into [0, 1]   chisq = (double)n * r2   beta = bg / 1e6
+ *   se = sqrt((rss0 / d[J+1]) * (1.0 - r2) / (double)(n - J - 2)) / 1e6   p = erfc(sqrt(chisq / 2.0))
+ * chisq is the score test of g given the covariates; for a 0/1 trait that is the linear-probability trend test, not logistic
+ * regression.  A (row, phenotype) with n >= J + 3 whose first unusable pivot is one of a <= J counts as COLLINEAR (the
+ * factorisation stops at the first unusable pivot).
+ * bvcf_covar_table_parse: the values of a covariate file's text by the file's rules (bvcf_config_covar.covar_path) against
+ * the s sample names; the table it leaves is UNBOUND: values, complete, names and counts, no columns.  bvcf_pheno_table_mask:
+ * the phenotype table with P = 0 wherever complete is 0, built anew.  bvcf_covar_table_build: j covariates over s samples
+ * from c[q * s + i] and complete[i] (c is taken as 0 where complete is 0), bound to a MASKED phenotype table (BVCF_E_ARG when
+ * it has a phenotype on an incomplete sample, or other samples); pheno NULL gives an unbound table.  A bound table holds the
+ * groups, the totals row and operand B: int8 b[16 n_blocks][s64], zero past s and wherever the group's / phenotype's P = 0,
+ * in blocks of 16 columns -- first the "C" blocks (per group the lc balanced base-256 digits of each C_j), then "CC" (per
+ * group the lcc digits of each C_i C_j), then "CY" (per phenotype the lcy digits of each C_j Y_k); a block holds 16 / digits
+ * whole values and zero columns behind them, so no value straddles a block.  lc (1 .. 6), lcc and lcy (1 .. 11) are the
+ * smallest counts that hold the table's values.
+ * bvcf_set_covar_table: a bound table to a ctx that has the phenotype table it is bound to (BVCF_E_ARG otherwise, also for an
+ * unbound table, a ctx without a phenotype table or a second call), before the first submit.  The slots get a second arena
+ * [rows][row_words]; the 1 GiB cap of a slot applies to the two arenas' sum (BVCF_E_TOO_BIG with a message: fewer columns,
+ * fewer covariates or smaller batches), bvcf_reserve_assoc_rows grows both, and a batch whose rows outrun either writes
+ * nothing (BVCF_E_CAPACITY).  Without it nothing new is allocated or launched.  bvcf_assoc_cov: the covariate records of
+ * the batch bvcf_assoc describes, words[r * row_words ..].
+ * bvcf_assoc_cov_stat: pure host code, phenotype k of a row from its two records; out as bvcf_assoc_stat's.  Returns bit 0:
+ * altFreq is there; bit 1: beta, se, chisq and p are there; bit 2: collinear.  -1 for NULL, an unbound table or k >= K. */
+typedef struct {
+  uint32_t n_covars, n_samples, s64;
+  uint32_t n_columns, n_groups;      /* K and G of the phenotype table it is bound to; 0: unbound */
+  uint32_t lc, lcc, lcy;
+  uint32_t n_blocks, row_words;
+  uint64_t n_named;                  /* the (kept) samples the file names */
+  uint64_t n_incomplete;             /* the (kept) samples without a value for some covariate */
+  const int8_t *b;                   /* [16 n_blocks][s64] */
+  const int64_t *c;                  /* [n_covars][n_samples] */
+  const uint8_t *complete;           /* [n_samples] */
+  const uint32_t *group_of;          /* [n_columns] */
+  const uint32_t *group_first;       /* [n_groups] the group's first phenotype */
+  const uint64_t *pheno_np;          /* [n_columns] NP of the phenotype table */
+  const uint64_t *totals;            /* [row_words] */
+  const char *names;                 /* n_covars NUL-terminated names */
+  uint64_t names_bytes;
+} bvcf_covar_table;
+typedef struct {
+  const uint64_t *words; /* [n_rows][row_words] */
+  uint64_t n_rows;
+  uint32_t row_words;
+} bvcf_assoc_cov_info;
+int bvcf_covar_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
+                           bvcf_covar_table *out, char *err, size_t err_cap);
+int bvcf_covar_table_build(const int64_t *c, const uint8_t *complete, uint32_t j, uint32_t s, const char *names, size_t names_bytes,
+                           uint64_t n_named, const bvcf_pheno_table *pheno, bvcf_covar_table *out);
+void bvcf_covar_table_free(bvcf_covar_table *t);
+int bvcf_pheno_table_mask(const bvcf_pheno_table *t, const uint8_t *complete, bvcf_pheno_table *out);
+int bvcf_set_covar_table(bvcf_ctx *ctx, const bvcf_covar_table *t);
+int bvcf_assoc_cov(bvcf_ctx *ctx, bvcf_assoc_cov_info *out);
+int bvcf_assoc_cov_stat(const bvcf_covar_table *t, uint32_t k, const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals,
+                        const uint64_t *cov_row, double out[6]);
 /* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
  * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
  * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
@@ -1170,6 +1249,29 @@ typedef struct {
 } bvcf_config_pca;
 /* the whole struct: bvcf_config_assoc_defaults, base.reserved[1] = BVCF_CONFIG_MORE_PCA, no components, pca_count the default */
 void bvcf_config_pca_defaults(bvcf_config_pca *c);
+/* Likewise what came after bvcf_config_pca: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_COVAR.  bvcf_config_covar_defaults sets that; the eleven older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_COVAR 11
+typedef struct {
+  bvcf_config_pca pca;
+  /* --covar FILE (only with pheno_path and assoc_path, BVCF_E_ARG otherwise): the scan of assoc_path adjusted for the file's
+   * covariates, y ~ g + C_1 .. C_J (bvcf_assoc_cov_stat has the definition).  The file follows pheno_path's rules -- lines,
+   * '\r', empty lines, the optional header "#sample \t name1 \t ... \t nameJ" (without one the names are COV1 .. COVJ), values
+   * and NA by the same grammar, names matched against the (kept) samples the same way, 1 <= J <= 16 -- with one addition: a
+   * header whose first two fields are exactly "#FID" and "IID" gives every line two name fields, the sample's name being
+   * the second, so pca_prefix's .eigenvec can be fed as it stands.  A (kept) sample the file does not name, or with NA for
+   * any covariate, is incomplete: it has every phenotype missing (the "samples" of the report do not change, NP does).
+   * A '#' line behind the first, a wrong field count, an empty name, a name that is a (kept) sample on two lines or matches
+   * more than one sample column, a bad value, an unreadable file, no non-empty line, J = 0 or J > 16: BVCF_E_FATAL with one
+   * message that names the line, before any device work.
+   * assoc_path keeps its columns and header; beta, se, chisq and p are empty_field when n < J + 3, a pivot is not usable or
+   * rss0 is not.  assoc_report_path gets three more lines behind its four: "covariates" (J), "incomplete" (the kept samples
+   * that are) and "collinear" (the (row, phenotype) lines that are).  The bytes do not depend on devices, batch size or
+   * input kind, and no other output changes.  NULL or "" = off: every byte is what the run writes without the field */
+  const char *covar_path;
+} bvcf_config_covar;
+/* the whole struct: bvcf_config_pca_defaults, base.reserved[1] = BVCF_CONFIG_MORE_COVAR, no covariates */
+void bvcf_config_covar_defaults(bvcf_config_covar *c);
 
 /* write_grm's arithmetic on its own: tables as bvcf_grm gives them (summed over a run's ctxs: [3 s s + 1]) -> the lower
  * triangle with the diagonal, row by row (s (s + 1) / 2 floats each): lower = A(i,j) = (float)((double)T / (2^28 N(i,j))), 0 when
