@@ -266,6 +266,120 @@ int finish_hook(bvcf_ctx *c, Event (&ev)[N], hipStream_t st, float *ms) {
   return BVCF_OK;
 }
 
+// A refusal of a table file: "line N: what" (what alone when no line is to blame) into err; rc is handed through
+int table_file_fail(char *err, size_t err_cap, uint64_t line, const std::string &what, int rc) {
+  const std::string msg = line ? "line " + std::to_string(line) + ": " + what : what;
+  if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
+  return rc;
+}
+
+// ---- the sample-keyed value files (--pheno, --covar): bvcf_pheno_table_parse and bvcf_covar_table_parse are its callers
+
+// What tells the two apart
+struct SampleFileRules {
+  uint32_t max_columns;
+  const char *word;    // a value column in the messages: "column", "covariate"
+  const char *prefix;  // the columns' names without a header: prefix1, prefix2 ..
+  bool fid_lead;       // a "#FID \t IID" header is allowed: two name fields per line, the second the sample's
+};
+
+// The rules of a sample-keyed value file, once: lines end with LF or CR LF and empty ones are skipped; the fields are
+// tab-separated, a name and 1 to max_columns values; the first line may be a "#sample" header with the columns' names, none
+// empty and none twice, and no other line starts with '#'; a value is "NA" or assoc_value's; a line whose name no sample
+// column carries is ignored -- after its values were looked at --, one whose name several carry is refused, and so is a sample's
+// second line.  on_columns(k) is called behind the first line, on_line(i, vals, have) per accepted line of sample column i
+// (have[c] = 0: column c was "NA").  Every refusal names its line in err
+template <class C, class L>
+int sample_file_read(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
+                            const SampleFileRules &r, std::string *names, uint64_t *n_named, const C &on_columns, const L &on_line,
+                            char *err, size_t err_cap) {
+  const auto fail = [&](uint64_t line, const std::string &what, int rc) { return table_file_fail(err, err_cap, line, what, rc); };
+  if ((n && !text) || (s && (!sample_names || !sample_lens))) return BVCF_E_ARG;
+  if (s > BVCF_ASSOC_MAX_SAMPLES) return fail(0, std::to_string(s) + " samples, more than 2^22", BVCF_E_TOO_BIG);
+  // a name -> its first sample column and how many columns carry it
+  std::unordered_map<std::string_view, std::pair<uint32_t, uint32_t>> cols;
+  for (uint32_t i = 0; i < s; i++) {
+    auto ins = cols.emplace(std::string_view(sample_names[i], sample_lens[i]), std::make_pair(i, 0u));
+    ins.first->second.second++;
+  }
+  const std::string word = r.word;
+  std::vector<uint64_t> line_of(s, 0);
+  uint32_t k = 0, lead = 1;  // lead: the name fields of a line -- two behind a "#FID \t IID" header
+  uint64_t line_no = 0;
+  bool first = true;
+  std::vector<std::string_view> f;
+  std::vector<int64_t> vals;
+  std::vector<uint8_t> have;
+  *n_named = 0;
+  for (size_t at = 0; at < n;) {
+    const char *nl = (const char *)memchr(text + at, '\n', n - at);
+    size_t end = nl ? (size_t)(nl - text) : n;
+    const size_t next = nl ? end + 1 : n;
+    line_no++;
+    if (end > at && text[end - 1] == '\r') end--;
+    const std::string_view line(text + at, end - at);
+    at = next;
+    if (line.empty()) continue;
+    f.clear();
+    for (size_t p = 0;;) {
+      const size_t t = line.find('\t', p);
+      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
+      if (t == std::string_view::npos) break;
+      p = t + 1;
+    }
+    const bool header = line[0] == '#';
+    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
+    if (first) {
+      if (r.fid_lead && header && f.size() >= 2 && f[0] == "#FID" && f[1] == "IID") lead = 2;
+      if (f.size() < lead + 1u || f.size() - lead > r.max_columns)
+        return fail(line_no, "want a sample and 1 to " + std::to_string(r.max_columns) + " " + word + "s, tab-separated", BVCF_E_ARG);
+      k = (uint32_t)(f.size() - lead);
+      first = false;
+      on_columns(k);
+      if (header) {
+        if (lead == 1 && f[0] != "#sample")
+          return fail(line_no, r.fid_lead ? "a header starts with \"#sample\", or with \"#FID\" and \"IID\"" : "a header starts with \"#sample\"",
+                      BVCF_E_ARG);
+        for (uint32_t c = 0; c < k; c++) {
+          if (f[lead + c].empty()) return fail(line_no, "an empty " + word + " name", BVCF_E_ARG);
+          for (uint32_t d = 0; d < c; d++)
+            if (f[lead + d] == f[lead + c]) return fail(line_no, "the " + word + " name " + std::string(f[lead + c]) + " twice", BVCF_E_ARG);
+          names->append(f[lead + c]);
+          names->push_back('\0');
+        }
+        continue;
+      }
+      for (uint32_t c = 0; c < k; c++) {
+        names->append(r.prefix + std::to_string(c + 1));
+        names->push_back('\0');
+      }
+    }
+    if (f.size() != (size_t)k + lead) return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(k + lead), BVCF_E_ARG);
+    const std::string_view name = f[lead - 1u];
+    if (name.empty()) return fail(line_no, "an empty sample name", BVCF_E_ARG);
+    vals.assign(k, 0);
+    have.assign(k, 0);
+    for (uint32_t c = 0; c < k; c++) {
+      const std::string_view x = f[lead + c];
+      if (x == "NA") continue;
+      const int rc = assoc_value(x.data(), x.size(), &vals[c]);
+      if (rc == -2) return fail(line_no, "the value " + std::string(x) + " is above 10^6 in size", BVCF_E_ARG);
+      if (rc) return fail(line_no, "bad value \"" + std::string(x.substr(0, 80)) + "\"", BVCF_E_ARG);
+      have[c] = 1;
+    }
+    const auto it = cols.find(name);
+    if (it == cols.end()) continue;  // (no (kept) sample: ignored)
+    if (it->second.second > 1) return fail(line_no, "the name " + std::string(name) + " matches more than one sample column", BVCF_E_ARG);
+    const uint32_t i = it->second.first;
+    if (line_of[i]) return fail(line_no, "the sample " + std::string(name) + " is on line " + std::to_string(line_of[i]) + " already", BVCF_E_ARG);
+    line_of[i] = line_no;
+    (*n_named)++;
+    on_line(i, vals.data(), have.data());
+  }
+  if (first) return fail(0, "no line", BVCF_E_ARG);
+  return BVCF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1568,10 +1682,10 @@ int bvcf_pheno_table_build(const int64_t *y, const uint8_t *present, uint32_t k,
   for (size_t q = 0; q < n; q++) {
     if (!present[q]) continue;
     if (y[q] > BVCF_ASSOC_MAX_Y || y[q] < -BVCF_ASSOC_MAX_Y) return BVCF_E_ARG;
-    l1 = std::max(l1, (uint32_t)assoc_limbs(y[q], l));
+    l1 = std::max(l1, (uint32_t)exact_limbs(y[q], l, 16));
     uint64_t lo, hi;
-    assoc_square(y[q], &lo, &hi);
-    l2 = std::max(l2, (uint32_t)assoc_limbs128(lo, hi, l));
+    exact_square(y[q], &lo, &hi);
+    l2 = std::max(l2, (uint32_t)exact_limbs128(lo, hi, l, 16));
   }
   const uint32_t s64 = (s + 63u) & ~63u, n_cols = k * (1u + l1 + l2);
   int8_t *b = (int8_t *)calloc((size_t)n_cols * s64 + 1, 1);
@@ -1597,15 +1711,15 @@ int bvcf_pheno_table_build(const int64_t *y, const uint8_t *present, uint32_t k,
       pp[at] = 1;
       yy[at] = y[at];
       py[i] = 1;
-      assoc_limbs(y[at], l);
+      exact_limbs(y[at], l, 16);
       for (uint32_t a = 0; a < l1; a++) py[(size_t)(1u + a) * s64 + i] = l[a];
       uint64_t lo, hi;
-      assoc_square(y[at], &lo, &hi);
-      assoc_limbs128(lo, hi, l);
+      exact_square(y[at], &lo, &hi);
+      exact_limbs128(lo, hi, l, 16);
       for (uint32_t a = 0; a < l2; a++) q2[(size_t)a * s64 + i] = l[a];
       tot[c].np++;
       tot[c].ay += y[at];
-      assoc_add128w(&tot[c].by_lo, &tot[c].by_hi, lo, hi);
+      exact_add128(&tot[c].by_lo, &tot[c].by_hi, lo, hi);
     }
   }
   out->n_columns = k;
@@ -1624,103 +1738,33 @@ int bvcf_pheno_table_build(const int64_t *y, const uint8_t *present, uint32_t k,
   return BVCF_OK;
 }
 
-// the file's rules (bvcf_config_assoc.pheno_path); every refusal names its line in err
+// the phenotype file (bvcf_config_assoc.pheno_path): per column, who has a value
 int bvcf_pheno_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
                            bvcf_pheno_table *out, char *err, size_t err_cap) {
   if (!out) return BVCF_E_ARG;
   memset(out, 0, sizeof *out);
-  std::string msg;
-  const auto fail = [&](uint64_t line, const std::string &what, int rc) {
-    msg = line ? "line " + std::to_string(line) + ": " + what : what;
-    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
-    return rc;
-  };
-  if ((n && !text) || (s && (!sample_names || !sample_lens))) return BVCF_E_ARG;
-  if (s > BVCF_ASSOC_MAX_SAMPLES) return fail(0, std::to_string(s) + " samples, more than 2^22", BVCF_E_TOO_BIG);
-  // a name -> its first sample column and how many columns carry it
-  std::unordered_map<std::string_view, std::pair<uint32_t, uint32_t>> cols;
-  for (uint32_t i = 0; i < s; i++) {
-    auto ins = cols.emplace(std::string_view(sample_names[i], sample_lens[i]), std::make_pair(i, 0u));
-    ins.first->second.second++;
-  }
   std::vector<int64_t> y;
   std::vector<uint8_t> present;
-  std::vector<uint64_t> line_of(s, 0);
   std::string names;
   uint32_t k = 0;
-  uint64_t line_no = 0, n_named = 0;
-  bool first = true;
-  std::vector<std::string_view> f;
-  std::vector<int64_t> vals;
-  std::vector<uint8_t> have;
-  for (size_t at = 0; at < n;) {
-    const char *nl = (const char *)memchr(text + at, '\n', n - at);
-    size_t end = nl ? (size_t)(nl - text) : n;
-    const size_t next = nl ? end + 1 : n;
-    line_no++;
-    if (end > at && text[end - 1] == '\r') end--;
-    const std::string_view line(text + at, end - at);
-    at = next;
-    if (line.empty()) continue;
-    f.clear();
-    for (size_t p = 0;;) {
-      const size_t t = line.find('\t', p);
-      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
-      if (t == std::string_view::npos) break;
-      p = t + 1;
-    }
-    const bool header = line[0] == '#';
-    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
-    if (first) {
-      if (f.size() < 2 || f.size() - 1 > BVCF_ASSOC_MAX_COLUMNS)
-        return fail(line_no, "want a sample and 1 to " + std::to_string(BVCF_ASSOC_MAX_COLUMNS) + " columns, tab-separated", BVCF_E_ARG);
-      k = (uint32_t)(f.size() - 1);
-      first = false;
-      y.assign((size_t)k * s, 0);
-      present.assign((size_t)k * s, 0);
-      if (header) {
-        if (f[0] != "#sample") return fail(line_no, "a header starts with \"#sample\"", BVCF_E_ARG);
+  uint64_t n_named = 0;
+  int rc = sample_file_read(
+      text, n, sample_names, sample_lens, s, SampleFileRules{BVCF_ASSOC_MAX_COLUMNS, "column", "PHENO", false}, &names, &n_named,
+      [&](uint32_t n_columns) {
+        k = n_columns;
+        y.assign((size_t)k * s, 0);
+        present.assign((size_t)k * s, 0);
+      },
+      [&](uint32_t i, const int64_t *vals, const uint8_t *have) {
         for (uint32_t c = 0; c < k; c++) {
-          if (f[1 + c].empty()) return fail(line_no, "an empty column name", BVCF_E_ARG);
-          for (uint32_t d = 0; d < c; d++)
-            if (f[1 + d] == f[1 + c]) return fail(line_no, "the column name " + std::string(f[1 + c]) + " twice", BVCF_E_ARG);
-          names.append(f[1 + c]);
-          names.push_back('\0');
+          y[(size_t)c * s + i] = vals[c];
+          present[(size_t)c * s + i] = have[c];
         }
-        continue;
-      }
-      for (uint32_t c = 0; c < k; c++) {
-        names.append("PHENO" + std::to_string(c + 1));
-        names.push_back('\0');
-      }
-    }
-    if (f.size() != (size_t)k + 1)
-      return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(k + 1), BVCF_E_ARG);
-    if (f[0].empty()) return fail(line_no, "an empty sample name", BVCF_E_ARG);
-    vals.assign(k, 0);
-    have.assign(k, 0);
-    for (uint32_t c = 0; c < k; c++) {
-      if (f[1 + c] == "NA") continue;
-      const int rc = assoc_value(f[1 + c].data(), f[1 + c].size(), &vals[c]);
-      if (rc == -2) return fail(line_no, "the value " + std::string(f[1 + c]) + " is above 10^6 in size", BVCF_E_ARG);
-      if (rc) return fail(line_no, "bad value \"" + std::string(f[1 + c].substr(0, 80)) + "\"", BVCF_E_ARG);
-      have[c] = 1;
-    }
-    const auto it = cols.find(f[0]);
-    if (it == cols.end()) continue;  // (no (kept) sample: ignored)
-    if (it->second.second > 1) return fail(line_no, "the name " + std::string(f[0]) + " matches more than one sample column", BVCF_E_ARG);
-    const uint32_t i = it->second.first;
-    if (line_of[i]) return fail(line_no, "the sample " + std::string(f[0]) + " is on line " + std::to_string(line_of[i]) + " already", BVCF_E_ARG);
-    line_of[i] = line_no;
-    n_named++;
-    for (uint32_t c = 0; c < k; c++) {
-      y[(size_t)c * s + i] = vals[c];
-      present[(size_t)c * s + i] = have[c];
-    }
-  }
-  if (first) return fail(0, "no line", BVCF_E_ARG);
-  const int rc = bvcf_pheno_table_build(y.data(), present.data(), k, s, names.data(), names.size(), n_named, out);
-  if (rc) return fail(0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
+      },
+      err, err_cap);
+  if (rc) return rc;
+  rc = bvcf_pheno_table_build(y.data(), present.data(), k, s, names.data(), names.size(), n_named, out);
+  if (rc) return table_file_fail(err, err_cap, 0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
   return BVCF_OK;
 }
 
@@ -1813,7 +1857,7 @@ int bvcf_assoc(bvcf_ctx *c, bvcf_assoc_info *out) {
 }
 
 int bvcf_assoc_value(const char *text, size_t n, int64_t *out) { return assoc_value(text, n, out); }
-int bvcf_assoc_limbs(uint64_t lo, uint64_t hi, int8_t out[16]) { return out ? assoc_limbs128(lo, hi, out) : -1; }
+int bvcf_assoc_limbs(uint64_t lo, uint64_t hi, int8_t out[16]) { return out ? exact_limbs128(lo, hi, out, 16) : -1; }
 
 static AssocSums assoc_sums_of(const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals) {
   AssocSums s{};
@@ -1908,15 +1952,15 @@ int bvcf_covar_table_build(const int64_t *c, const uint8_t *complete, uint32_t j
     if (!complete[i]) continue;
     for (uint32_t q = 0; q < j; q++) {
       const int64_t x = c[(size_t)q * s + i];
-      lc = std::max(lc, (uint32_t)assoc_limbs(x, lim));
+      lc = std::max(lc, (uint32_t)exact_limbs(x, lim, 16));
       for (uint32_t p = 0; p <= q; p++) {
-        assoc_mul128(c[(size_t)p * s + i], x, &lo, &hi);
-        lcc = std::max(lcc, (uint32_t)assoc_limbs128(lo, hi, lim));
+        exact_mul128(c[(size_t)p * s + i], x, &lo, &hi);
+        lcc = std::max(lcc, (uint32_t)exact_limbs128(lo, hi, lim, 16));
       }
       for (uint32_t k = 0; k < K; k++) {
         if (!pheno->present[(size_t)k * s + i]) continue;
-        assoc_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
-        lcy = std::max(lcy, (uint32_t)assoc_limbs128(lo, hi, lim));
+        exact_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
+        lcy = std::max(lcy, (uint32_t)exact_limbs128(lo, hi, lim, 16));
       }
     }
   }
@@ -1950,26 +1994,26 @@ int bvcf_covar_table_build(const int64_t *c, const uint8_t *complete, uint32_t j
       for (uint32_t g = 0; g < G; g++) {
         if (!pheno->present[(size_t)first[g] * s + i]) continue;
         const uint32_t v = g * j + q;
-        assoc_limbs(x, lim);
+        exact_limbs(x, lim, 16);
         put(assoc_cov_column(0, l.vc, lc, v), lc, i);
         tot[assoc_cov_word_c(l, v, 2)] += (uint64_t)x;
         for (uint32_t p = 0; p <= q; p++) {
           const uint32_t vv = g * l.np2 + q * (q + 1u) / 2u + p;
-          assoc_mul128(cc[(size_t)p * s + i], x, &lo, &hi);
-          assoc_limbs128(lo, hi, lim);
+          exact_mul128(cc[(size_t)p * s + i], x, &lo, &hi);
+          exact_limbs128(lo, hi, lim, 16);
           put(assoc_cov_column(l.bc, l.vcc, lcc, vv), lcc, i);
           uint64_t *w = tot + assoc_cov_word_cc(l, vv);
-          assoc_add128w(w, w + 1, lo, hi);
+          exact_add128(w, w + 1, lo, hi);
         }
       }
       for (uint32_t k = 0; k < K; k++) {
         if (!pheno->present[(size_t)k * s + i]) continue;
         const uint32_t v = k * j + q;
-        assoc_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
-        assoc_limbs128(lo, hi, lim);
+        exact_mul128(x, pheno->y[(size_t)k * s + i], &lo, &hi);
+        exact_limbs128(lo, hi, lim, 16);
         put(assoc_cov_column(l.bc + l.bcc, l.vcy, lcy, v), lcy, i);
         uint64_t *w = tot + assoc_cov_word_cy(l, v);
-        assoc_add128w(w, w + 1, lo, hi);
+        exact_add128(w, w + 1, lo, hi);
       }
     }
   }
@@ -1995,102 +2039,34 @@ int bvcf_covar_table_build(const int64_t *c, const uint8_t *complete, uint32_t j
   return BVCF_OK;
 }
 
-// the file's rules (bvcf_config_covar.covar_path); every refusal names its line in err
+// the covariate file (bvcf_config_covar.covar_path), sample_file_read's rules with the "#FID \t IID" header: a sample counts
+// when its line is complete, and only then are its values kept
 int bvcf_covar_table_parse(const char *text, size_t n, const char *const *sample_names, const uint32_t *sample_lens, uint32_t s,
                            bvcf_covar_table *out, char *err, size_t err_cap) {
   if (!out) return BVCF_E_ARG;
   memset(out, 0, sizeof *out);
-  std::string msg;
-  const auto fail = [&](uint64_t line, const std::string &what, int rc) {
-    msg = line ? "line " + std::to_string(line) + ": " + what : what;
-    if (err && err_cap) snprintf(err, err_cap, "%s", msg.c_str());
-    return rc;
-  };
-  if ((n && !text) || (s && (!sample_names || !sample_lens))) return BVCF_E_ARG;
-  if (s > BVCF_ASSOC_MAX_SAMPLES) return fail(0, std::to_string(s) + " samples, more than 2^22", BVCF_E_TOO_BIG);
-  std::unordered_map<std::string_view, std::pair<uint32_t, uint32_t>> cols;
-  for (uint32_t i = 0; i < s; i++) {
-    auto ins = cols.emplace(std::string_view(sample_names[i], sample_lens[i]), std::make_pair(i, 0u));
-    ins.first->second.second++;
-  }
   std::vector<int64_t> c;
-  std::vector<uint8_t> complete(s, 0);
-  std::vector<uint64_t> line_of(s, 0);
+  std::vector<uint8_t> complete;
   std::string names;
-  uint32_t j = 0, lead = 1;  // lead: the name fields of a line -- two behind a "#FID \t IID" header
-  uint64_t line_no = 0, n_named = 0;
-  bool first = true;
-  std::vector<std::string_view> f;
-  std::vector<int64_t> vals;
-  for (size_t at = 0; at < n;) {
-    const char *nl = (const char *)memchr(text + at, '\n', n - at);
-    size_t end = nl ? (size_t)(nl - text) : n;
-    const size_t next = nl ? end + 1 : n;
-    line_no++;
-    if (end > at && text[end - 1] == '\r') end--;
-    const std::string_view line(text + at, end - at);
-    at = next;
-    if (line.empty()) continue;
-    f.clear();
-    for (size_t p = 0;;) {
-      const size_t t = line.find('\t', p);
-      f.push_back(line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p));
-      if (t == std::string_view::npos) break;
-      p = t + 1;
-    }
-    const bool header = line[0] == '#';
-    if (header && !first) return fail(line_no, "a '#' line behind the first line", BVCF_E_ARG);
-    if (first) {
-      if (header && f.size() >= 2 && f[0] == "#FID" && f[1] == "IID") lead = 2;
-      if (f.size() < lead + 1u || f.size() - lead > BVCF_COVAR_MAX)
-        return fail(line_no, "want a sample and 1 to " + std::to_string(BVCF_COVAR_MAX) + " covariates, tab-separated", BVCF_E_ARG);
-      j = (uint32_t)(f.size() - lead);
-      first = false;
-      c.assign((size_t)j * s, 0);
-      if (header) {
-        if (lead == 1 && f[0] != "#sample") return fail(line_no, "a header starts with \"#sample\", or with \"#FID\" and \"IID\"", BVCF_E_ARG);
-        for (uint32_t q = 0; q < j; q++) {
-          if (f[lead + q].empty()) return fail(line_no, "an empty covariate name", BVCF_E_ARG);
-          for (uint32_t d = 0; d < q; d++)
-            if (f[lead + d] == f[lead + q]) return fail(line_no, "the covariate name " + std::string(f[lead + q]) + " twice", BVCF_E_ARG);
-          names.append(f[lead + q]);
-          names.push_back('\0');
-        }
-        continue;
-      }
-      for (uint32_t q = 0; q < j; q++) {
-        names.append("COV" + std::to_string(q + 1));
-        names.push_back('\0');
-      }
-    }
-    if (f.size() != (size_t)j + lead) return fail(line_no, std::to_string(f.size()) + " fields, want " + std::to_string(j + lead), BVCF_E_ARG);
-    const std::string_view name = f[lead - 1u];
-    if (name.empty()) return fail(line_no, "an empty sample name", BVCF_E_ARG);
-    vals.assign(j, 0);
-    bool whole = true;
-    for (uint32_t q = 0; q < j; q++) {
-      const std::string_view x = f[lead + q];
-      if (x == "NA") {
-        whole = false;
-        continue;
-      }
-      const int rc = assoc_value(x.data(), x.size(), &vals[q]);
-      if (rc == -2) return fail(line_no, "the value " + std::string(x) + " is above 10^6 in size", BVCF_E_ARG);
-      if (rc) return fail(line_no, "bad value \"" + std::string(x.substr(0, 80)) + "\"", BVCF_E_ARG);
-    }
-    const auto it = cols.find(name);
-    if (it == cols.end()) continue;  // (no (kept) sample: ignored)
-    if (it->second.second > 1) return fail(line_no, "the name " + std::string(name) + " matches more than one sample column", BVCF_E_ARG);
-    const uint32_t i = it->second.first;
-    if (line_of[i]) return fail(line_no, "the sample " + std::string(name) + " is on line " + std::to_string(line_of[i]) + " already", BVCF_E_ARG);
-    line_of[i] = line_no;
-    n_named++;
-    complete[i] = whole ? 1 : 0;
-    for (uint32_t q = 0; q < j && whole; q++) c[(size_t)q * s + i] = vals[q];
-  }
-  if (first) return fail(0, "no line", BVCF_E_ARG);
-  const int rc = bvcf_covar_table_build(c.data(), complete.data(), j, s, names.data(), names.size(), n_named, nullptr, out);
-  if (rc) return fail(0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
+  uint32_t j = 0;
+  uint64_t n_named = 0;
+  int rc = sample_file_read(
+      text, n, sample_names, sample_lens, s, SampleFileRules{BVCF_COVAR_MAX, "covariate", "COV", true}, &names, &n_named,
+      [&](uint32_t n_covars) {
+        j = n_covars;
+        c.assign((size_t)j * s, 0);
+        complete.assign(s, 0);
+      },
+      [&](uint32_t i, const int64_t *vals, const uint8_t *have) {
+        bool whole = true;
+        for (uint32_t q = 0; q < j; q++) whole = whole && have[q];
+        complete[i] = whole ? 1 : 0;
+        for (uint32_t q = 0; q < j && whole; q++) c[(size_t)q * s + i] = vals[q];
+      },
+      err, err_cap);
+  if (rc) return rc;
+  rc = bvcf_covar_table_build(c.data(), complete.data(), j, s, names.data(), names.size(), n_named, nullptr, out);
+  if (rc) return table_file_fail(err, err_cap, 0, rc == BVCF_E_NOMEM ? "no memory" : "bad table", rc);
   return BVCF_OK;
 }
 
@@ -2759,7 +2735,7 @@ int bvcf_bench_grm_kernels(bvcf_ctx *c, float ms[4]) {
 // ---- scores
 
 int bvcf_score_weight(const char *text, size_t n, int64_t *out) { return score_weight(text, n, out); }
-int bvcf_score_limbs(int64_t w, int8_t out[8]) { return out ? score_limbs(w, out) : -1; }
+int bvcf_score_limbs(int64_t w, int8_t out[8]) { return out ? exact_limbs(w, out, BVCF_SCORE_MAX_LIMBS) : -1; }
 size_t bvcf_score_decimal(uint64_t lo, uint64_t hi, char out[48]) { return out ? score_decimal(lo, hi, out) : 0; }
 
 void bvcf_score_table_free(bvcf_score_table *t) {
@@ -2787,7 +2763,7 @@ int bvcf_score_table_build(const char *bytes, const uint64_t *off, const uint32_
       const int64_t v = w[i * k + c];
       if (v > BVCF_SCORE_MAX_W || v < -BVCF_SCORE_MAX_W) return BVCF_E_ARG;
       int8_t l[BVCF_SCORE_MAX_LIMBS];
-      limbs = std::max(limbs, (uint32_t)score_limbs(v, l));
+      limbs = std::max(limbs, (uint32_t)exact_limbs(v, l, BVCF_SCORE_MAX_LIMBS));
     }
   }
   const uint64_t cols = (uint64_t)k * limbs + 1;
@@ -2828,7 +2804,7 @@ int bvcf_score_table_build(const char *bytes, const uint64_t *off, const uint32_
     int8_t *row = weights + i * cols;
     for (uint32_t c = 0; c < k; c++) {
       int8_t l[BVCF_SCORE_MAX_LIMBS];
-      score_limbs(w[i * k + c], l);
+      exact_limbs(w[i * k + c], l, BVCF_SCORE_MAX_LIMBS);
       memcpy(row + (size_t)c * limbs, l, limbs);
     }
     row[cols - 1] = 1;

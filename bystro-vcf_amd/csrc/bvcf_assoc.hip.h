@@ -38,6 +38,7 @@
 
 #include "bvcf_assoc_q.h"
 #include "bvcf_bedrows.hip.h"
+#include "bvcf_rows.hip.h"
 
 namespace bvcf_dev {
 
@@ -54,8 +55,6 @@ static_assert(kAssocLds + kAssocTile * kAssocChunk * 16 <= 64 * 1024, "static LD
 // a product of a 0/1 class byte and a limb is at most 128 in size: an int32 accumulator takes 2^22 samples
 static_assert(128ull * BVCF_ASSOC_MAX_SAMPLES <= (1ull << 30), "int32 accumulators hold a row of 2^22 samples");
 static_assert(sizeof(bvcf_assoc_rec) == 56, "the record is 56 bytes");
-
-typedef int assoc_i32x4 __attribute__((ext_vector_type(4)));
 
 struct AssocArgs {
   const int8_t *b;                    // [16 (nb_py + nb_q)][s64]
@@ -138,12 +137,8 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_list(AssocArgs sa) {
   }
 }
 
-__device__ __forceinline__ assoc_i32x4 assoc_mfma(assoc_i32x4 a, assoc_i32x4 b, assoc_i32x4 c) {
-  return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
-
 // 16 classes (2 bits each) -> the 0/1 bytes of het, hom and missing, class j in byte j of the 16
-__device__ __forceinline__ void assoc_expand(uint32_t x, assoc_i32x4 &fh, assoc_i32x4 &fo, assoc_i32x4 &fm) {
+__device__ __forceinline__ void assoc_expand(uint32_t x, i32x4 &fh, i32x4 &fo, i32x4 &fm) {
 #pragma unroll
   for (uint32_t q = 0; q < 4; q++) {
     const uint32_t b = (x >> (8u * q)) & 0xFFu;
@@ -159,20 +154,13 @@ static_assert(BVCF_CLS_HET == 1 && BVCF_CLS_HOM == 2 && BVCF_CLS_MISSING == 3, "
 // a wave's accumulator blocks into its epilogue image [16 rows][kAssocEStride]: C/D has column lane & 15 of each block and
 // rows 4 (lane >> 4) + reg
 template <uint32_t N>
-__device__ __forceinline__ void assoc_spill(int *e, const assoc_i32x4 (&acc)[N], uint32_t nb, uint32_t lane) {
+__device__ __forceinline__ void assoc_spill(int *e, const i32x4 (&acc)[N], uint32_t nb, uint32_t lane) {
   const uint32_t r = lane & 15u, h = lane >> 4;
 #pragma unroll
   for (uint32_t b = 0; b < N; b++)
     if (b < nb)
 #pragma unroll
       for (uint32_t reg = 0; reg < 4; reg++) e[(4u * h + reg) * kAssocEStride + 16u * b + r] = acc[b][reg];
-}
-
-// sum 256^a limb sum over the n limb columns at e (modulo 2^64: the total fits, the terms need not)
-__device__ __forceinline__ long long assoc_recombine(const int *e, uint32_t n) {
-  unsigned long long v = 0;
-  for (uint32_t a = 0; a < n; a++) v += (unsigned long long)(long long)e[a] << (8u * a);
-  return (long long)v;
 }
 
 __global__ __launch_bounds__(kWgThreads) void k_assoc_gemm(KernelArgs a, AssocArgs sa) {
@@ -192,15 +180,16 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_gemm(KernelArgs a, AssocAr
     const uint32_t li = tile * kAssocTile + trow;
     const bool valid = li < n_dense;  // (a row past the list's end: class NONE everywhere, and no record)
     const uint32_t cmap_off = valid ? sa.dense[li].y : 0u;
-    assoc_i32x4 acc_h[kAssocMaxPY], acc_o[kAssocMaxPY], acc_m[kAssocMaxPY], acc_q[kAssocMaxQ];
+    i32x4 acc_h[kAssocMaxPY], acc_o[kAssocMaxPY], acc_m[kAssocMaxPY], acc_q[kAssocMaxQ];
 #pragma unroll
-    for (uint32_t b = 0; b < kAssocMaxPY; b++) acc_h[b] = acc_o[b] = acc_m[b] = assoc_i32x4{0, 0, 0, 0};
+    for (uint32_t b = 0; b < kAssocMaxPY; b++) acc_h[b] = acc_o[b] = acc_m[b] = i32x4{0, 0, 0, 0};
 #pragma unroll
-    for (uint32_t b = 0; b < kAssocMaxQ; b++) acc_q[b] = assoc_i32x4{0, 0, 0, 0};
+    for (uint32_t b = 0; b < kAssocMaxQ; b++) acc_q[b] = i32x4{0, 0, 0, 0};
     for (uint32_t step0 = 0; step0 < n_steps; step0 += kAssocChunk) {
       __syncthreads();  // (the chunk before, or the tile's epilogue before, has been read)
       {
         // thread (trow, piece): the 16 map bytes of row trow at step step0 + piece (a padded map is 16 n_steps bytes)
+        // (this fetch, the staging below and the barriers around them stand again in k_assoc_cov_gemm: change both)
         const uint32_t st = step0 + piece;
         const u32x4 m = (valid && st < n_steps) ? *reinterpret_cast<const u32x4 *>(a.cmap + cmap_off + 16u * st) : u32x4{0u, 0u, 0u, 0u};
         *reinterpret_cast<u32x4 *>(&s_map[trow][piece][0]) = m;
@@ -215,23 +204,23 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_gemm(KernelArgs a, AssocAr
           *reinterpret_cast<u32x4 *>(s_mem + c * kAssocBStride + 16u * piece) =
               *reinterpret_cast<const u32x4 *>(sa.b + (size_t)c * sa.s64 + 64u * step + 16u * piece);
         __syncthreads();
-        assoc_i32x4 fh, fo, fm;
+        i32x4 fh, fo, fm;
         assoc_expand(s_map[16u * w + r][j][h], fh, fo, fm);
 #pragma unroll
         for (uint32_t b = 0; b < kAssocMaxPY; b++) {
           if (b < sa.nb_py) {
-            const assoc_i32x4 fb = *reinterpret_cast<const assoc_i32x4 *>(s_mem + (16u * b + r) * kAssocBStride + 16u * h);
-            acc_h[b] = assoc_mfma(fh, fb, acc_h[b]);
-            acc_o[b] = assoc_mfma(fo, fb, acc_o[b]);
-            acc_m[b] = assoc_mfma(fm, fb, acc_m[b]);
+            const i32x4 fb = *reinterpret_cast<const i32x4 *>(s_mem + (16u * b + r) * kAssocBStride + 16u * h);
+            acc_h[b] = mfma_i8(fh, fb, acc_h[b]);
+            acc_o[b] = mfma_i8(fo, fb, acc_o[b]);
+            acc_m[b] = mfma_i8(fm, fb, acc_m[b]);
           }
         }
 #pragma unroll
         for (uint32_t b = 0; b < kAssocMaxQ; b++) {
           if (b < sa.nb_q) {
-            const assoc_i32x4 fb =
-                *reinterpret_cast<const assoc_i32x4 *>(s_mem + (16u * (sa.nb_py + b) + r) * kAssocBStride + 16u * h);
-            acc_q[b] = assoc_mfma(fm, fb, acc_q[b]);
+            const i32x4 fb =
+                *reinterpret_cast<const i32x4 *>(s_mem + (16u * (sa.nb_py + b) + r) * kAssocBStride + 16u * h);
+            acc_q[b] = mfma_i8(fm, fb, acc_q[b]);
           }
         }
       }
@@ -257,13 +246,13 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_gemm(KernelArgs a, AssocAr
         const int *e = epi + (p & 15u) * kAssocEStride;
         if (phase < 3) {
           const uint32_t n = (uint32_t)e[k * py];
-          const long long s = assoc_recombine(e + k * py + 1u, sa.L1);
+          const long long s = exact_unlimbs(e + k * py + 1u, sa.L1);
           if (phase == 0) rec[i].n_het = n, rec[i].a_het = s;
           if (phase == 1) rec[i].n_hom = n, rec[i].a_hom = s;
           if (phase == 2) rec[i].n_mis = n, rec[i].a_mis = s;
         } else {
           uint64_t lo = 0, hi = 0;
-          for (uint32_t q = 0; q < sa.L2; q++) assoc_add128s(&lo, &hi, (int64_t)e[k * sa.L2 + q], 8u * q);
+          for (uint32_t q = 0; q < sa.L2; q++) exact_add128s(&lo, &hi, (int64_t)e[k * sa.L2 + q], 8u * q);
           rec[i].b_mis_lo = lo;
           rec[i].b_mis_hi = hi;
         }
@@ -287,10 +276,8 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_sparse(KernelArgs a, Assoc
   const uint32_t py = 1u + sa.L1;
   for (uint32_t j = g >> 4; j < n_sparse; j += (gridDim.x * kWgThreads) >> 4) {
     const uint2 ent = sa.sparse[j];
-    const uint32_t *cm = reinterpret_cast<const uint32_t *>(a.cmap + ent.y);
-    const uint32_t n = min(cm[0], (uint32_t)BVCF_CMAP_SPARSE_MAX);
-    const uint32_t v = e < n ? cm[1u + e] : 0u;
-    const uint32_t byte = v & 0xFFu, s_base = (v >> 8) * 4u;
+    uint32_t byte, s_base;
+    ShortList(a.cmap, ent.y).entry(e, &byte, &s_base);  // (a lane past the list's end goes along with no class: the reductions below)
     for (uint32_t k = 0; k < sa.K; k++) {
       // what the entry's up to four samples add per class; Y^2 < 2^80 in two pieces of 40 bits: 60 of them add up in uint64
       unsigned long long cnt = 0;  // N_het, N_hom, N_mis: 21 bits each
@@ -308,7 +295,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_sparse(KernelArgs a, Assoc
         if (cls == BVCF_CLS_MISSING) {
           a_mis += y;
           uint64_t lo, hi;
-          assoc_square(y, &lo, &hi);
+          exact_square(y, &lo, &hi);
           q0 += lo & ((1ull << 40) - 1ull);
           q1 += (lo >> 40) | (hi << 24);
         }
@@ -331,7 +318,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_sparse(KernelArgs a, Assoc
         o.a_hom = a_hom;
         o.a_mis = a_mis;
         uint64_t lo = q0, hi = 0;
-        assoc_add128w(&lo, &hi, q1 << 40, q1 >> 24);
+        exact_add128(&lo, &hi, q1 << 40, q1 >> 24);
         o.b_mis_lo = lo;
         o.b_mis_hi = hi;
         sa.rec[(size_t)ent.x * sa.K + k] = o;

@@ -75,12 +75,13 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_gemm(KernelArgs a, Ass
     const uint32_t li = tile * kAssocTile + trow;
     const bool valid = li < n_dense;  // (a row past the list's end: class NONE everywhere, and no record)
     const uint32_t cmap_off = valid ? sa.dense[li].y : 0u;
-    assoc_i32x4 acc[kCovAcc];
+    i32x4 acc[kCovAcc];
 #pragma unroll
-    for (uint32_t b = 0; b < kCovAcc; b++) acc[b] = assoc_i32x4{0, 0, 0, 0};
+    for (uint32_t b = 0; b < kCovAcc; b++) acc[b] = i32x4{0, 0, 0, 0};
     for (uint32_t step0 = 0; step0 < n_steps; step0 += kAssocChunk) {
       __syncthreads();  // (the chunk before, or the tile's epilogue before, has been read)
       {
+        // (this fetch, the staging below and the barriers around them are k_assoc_gemm's, bvcf_assoc.hip.h: change both)
         const uint32_t st = step0 + piece;
         const u32x4 m = (valid && st < n_steps) ? *reinterpret_cast<const u32x4 *>(a.cmap + cmap_off + 16u * st) : u32x4{0u, 0u, 0u, 0u};
         *reinterpret_cast<u32x4 *>(&s_map[trow][piece][0]) = m;
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_gemm(KernelArgs a, Ass
           *reinterpret_cast<u32x4 *>(s_mem + c * kAssocBStride + 16u * piece) =
               *reinterpret_cast<const u32x4 *>(bs + (size_t)c * sa.s64 + 64u * step + 16u * piece);
         __syncthreads();
-        assoc_i32x4 fh, fo, fm;
+        i32x4 fh, fo, fm;
         assoc_expand(s_map[16u * w + r][j][h], fh, fo, fm);
         // accumulator ai of a C slice is (block ai / 3, class ai % 3), of a CC / CY slice (block ai, missing): one unrolled
         // loop for both kinds, so that a wave holds one set of 16 accumulators
@@ -103,9 +104,9 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_gemm(KernelArgs a, Ass
         for (uint32_t ai = 0; ai < kCovAcc; ai++) {
           const uint32_t b = kind_c ? ai / 3u : ai;
           if (b < n_blk) {
-            const assoc_i32x4 fb = *reinterpret_cast<const assoc_i32x4 *>(s_mem + (16u * b + r) * kAssocBStride + 16u * h);
-            const assoc_i32x4 fa = !kind_c ? fm : ai % 3u == 0u ? fh : ai % 3u == 1u ? fo : fm;
-            acc[ai] = assoc_mfma(fa, fb, acc[ai]);
+            const i32x4 fb = *reinterpret_cast<const i32x4 *>(s_mem + (16u * b + r) * kAssocBStride + 16u * h);
+            const i32x4 fa = !kind_c ? fm : ai % 3u == 0u ? fh : ai % 3u == 1u ? fo : fm;
+            acc[ai] = mfma_i8(fa, fb, acc[ai]);
           }
         }
       }
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_gemm(KernelArgs a, Ass
         if (kind_c) {
           const uint32_t b = ai / 3u, cls = ai % 3u, v = (blk0 + b) * l.vc + vi;
           if (b >= n_blk || v >= l.nc) continue;
-          out[assoc_cov_word_c(l, v, cls)] = (unsigned long long)assoc_recombine(e + vi * l.lc, l.lc);
+          out[assoc_cov_word_c(l, v, cls)] = (unsigned long long)exact_unlimbs(e + vi * l.lc, l.lc);
         } else {
           if (ai >= n_blk) continue;
           const uint32_t blk = blk0 + ai;
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_gemm(KernelArgs a, Ass
           const uint32_t v = (blk - (cc ? l.bc : l.bc + l.bcc)) * vper + vi;
           if (v >= (cc ? l.ncc : l.ncy)) continue;
           uint64_t lo = 0, hi = 0;
-          for (uint32_t q = 0; q < limbs; q++) assoc_add128s(&lo, &hi, (int64_t)e[vi * limbs + q], 8u * q);
+          for (uint32_t q = 0; q < limbs; q++) exact_add128s(&lo, &hi, (int64_t)e[vi * limbs + q], 8u * q);
           const uint32_t at = cc ? assoc_cov_word_cc(l, v) : assoc_cov_word_cy(l, v);
           out[at] = lo;
           out[at + 1u] = hi;
@@ -170,10 +171,8 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_sparse(KernelArgs a, A
   for (unsigned long long it = g >> 4; it < n_items; it += (gridDim.x * kWgThreads) >> 4) {
     const uint32_t jl = (uint32_t)(it / n_fam), fam = (uint32_t)(it % n_fam);
     const uint2 ent = sa.sparse[jl];
-    const uint32_t *cm = reinterpret_cast<const uint32_t *>(a.cmap + ent.y);
-    const uint32_t n = min(cm[0], (uint32_t)BVCF_CMAP_SPARSE_MAX);
-    const uint32_t v = e < n ? cm[1u + e] : 0u;
-    const uint32_t byte = v & 0xFFu, s_base = (v >> 8) * 4u;
+    uint32_t byte, s_base;
+    ShortList(a.cmap, ent.y).entry(e, &byte, &s_base);  // (a lane past the list's end goes along with no class: the reductions below)
     const uint32_t pk = fam < l.G ? ca.rep[fam] : fam < 2u * l.G ? ca.rep[fam - l.G] : fam - 2u * l.G;
     // the classes of the entry's up to four samples: NONE where the sample is outside the group / has no phenotype
     uint32_t cls[4];
@@ -241,7 +240,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_cov_sparse(KernelArgs a, A
         }
         if (writer) {
           uint64_t lo = q0, hi = 0;
-          assoc_add128s(&lo, &hi, q1, 40u);
+          exact_add128s(&lo, &hi, q1, 40u);
           const uint32_t at = cc ? assoc_cov_word_cc(l, (fam - l.G) * l.np2 + p) : assoc_cov_word_cy(l, pk * J + p);
           out[at] = lo;
           out[at + 1u] = hi;

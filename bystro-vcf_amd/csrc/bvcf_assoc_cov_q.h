@@ -35,7 +35,7 @@ struct AssocCovLayout {
   uint32_t n_blocks, n_slices_c, n_slices;
 };
 
-BVCF_ASSOC_HD AssocCovLayout assoc_cov_layout(uint32_t J, uint32_t K, uint32_t G, uint32_t lc, uint32_t lcc, uint32_t lcy) {
+BVCF_HD AssocCovLayout assoc_cov_layout(uint32_t J, uint32_t K, uint32_t G, uint32_t lc, uint32_t lcc, uint32_t lcy) {
   AssocCovLayout l;
   l.J = J, l.K = K, l.G = G, l.lc = lc, l.lcc = lcc, l.lcy = lcy;
   l.np2 = J * (J + 1u) / 2u;
@@ -53,22 +53,15 @@ BVCF_ASSOC_HD AssocCovLayout assoc_cov_layout(uint32_t J, uint32_t K, uint32_t G
 }
 
 // the first column of value v of a family whose first block is `first`
-BVCF_ASSOC_HD uint32_t assoc_cov_column(uint32_t first, uint32_t per, uint32_t limbs, uint32_t v) {
+BVCF_HD uint32_t assoc_cov_column(uint32_t first, uint32_t per, uint32_t limbs, uint32_t v) {
   return 16u * (first + v / per) + (v % per) * limbs;
 }
 // a record's words
-BVCF_ASSOC_HD uint32_t assoc_cov_word_c(const AssocCovLayout &l, uint32_t v, uint32_t cls /* 0 het, 1 hom, 2 missing */) {
+BVCF_HD uint32_t assoc_cov_word_c(const AssocCovLayout &l, uint32_t v, uint32_t cls /* 0 het, 1 hom, 2 missing */) {
   return (v / l.J) * l.gw + cls * l.J + v % l.J;
 }
-BVCF_ASSOC_HD uint32_t assoc_cov_word_cc(const AssocCovLayout &l, uint32_t v) { return (v / l.np2) * l.gw + 3u * l.J + 2u * (v % l.np2); }
-BVCF_ASSOC_HD uint32_t assoc_cov_word_cy(const AssocCovLayout &l, uint32_t v) { return l.G * l.gw + 2u * v; }
-
-// a * b of |a|, |b| < 2^63 as a 128-bit two's complement integer in two words
-BVCF_ASSOC_HD void assoc_mul128(int64_t a, int64_t b, uint64_t *lo, uint64_t *hi) {
-  const __int128 p = (__int128)a * b;
-  *lo = (uint64_t)(unsigned __int128)p;
-  *hi = (uint64_t)((unsigned __int128)p >> 64);
-}
+BVCF_HD uint32_t assoc_cov_word_cc(const AssocCovLayout &l, uint32_t v) { return (v / l.np2) * l.gw + 3u * l.J + 2u * (v % l.np2); }
+BVCF_HD uint32_t assoc_cov_word_cy(const AssocCovLayout &l, uint32_t v) { return l.G * l.gw + 2u * v; }
 
 // The Gram matrix of a (row, phenotype): v_0 = 1, v_1 .. v_J = C_j, v_{J+1} = g, v_{J+2} = Y over the samples with the
 // phenotype and a called genotype; the lower triangle, exact.  With S <= 2^22 and |C|, |Y| < 2^40 every entry is below 2^103
@@ -78,28 +71,6 @@ struct AssocCovGram {
   __int128 g[BVCF_COVAR_DIM][BVCF_COVAR_DIM];
 };
 static_assert(BVCF_ASSOC_MAX_SAMPLES == (1u << 22) && BVCF_ASSOC_MAX_Y < (1ll << 40), "a Gram entry is below 2^103");
-
-// assoc_double's value -- the correctly rounded double, ties to even, by the bits -- with the top bit found by a count of
-// leading zeros: a Gram matrix has up to 190 entries per (row, phenotype)
-inline double assoc_cov_double(__int128 v) {
-  const bool neg = v < 0;
-  unsigned __int128 m = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
-  if (m == 0) return 0.0;
-  const uint64_t hi = (uint64_t)(m >> 64), lo = (uint64_t)m;
-  const int top = hi ? 127 - __builtin_clzll(hi) : 63 - __builtin_clzll(lo);
-  int e = 0;
-  if (top > 52) {  // keep 53 bits: the first bit dropped decides, a tie goes to the even neighbour
-    const int drop = top - 52;
-    const unsigned __int128 half = (unsigned __int128)1 << (drop - 1), rem = m & (((unsigned __int128)1 << drop) - 1);
-    m >>= drop;
-    if (rem > half || (rem == half && (m & 1))) m++;
-    e = drop;
-  }
-  const double d = ldexp((double)(uint64_t)m, e);  // (m <= 2^53: exact, and so is the scaling)
-  return neg ? -d : d;
-}
-
-inline __int128 assoc_cov_i128(const uint64_t *w) { return (__int128)(((unsigned __int128)w[1] << 64) | w[0]); }
 
 // s: the phenotype's class sums and totals (AssocSums); row / tot: the row's covariate record and the totals row; k the
 // phenotype, grp its group.  A total minus what the device summed over the row's missing samples, or a device sum over
@@ -121,10 +92,10 @@ inline void assoc_cov_gram(const AssocCovLayout &l, uint32_t k, uint32_t grp, co
     q.g[ig][1 + j] = (__int128)c_het + 2 * (__int128)c_hom;
     for (uint32_t i = 0; i <= j; i++) {
       const uint32_t at = assoc_cov_word_cc(l, grp * l.np2 + j * (j + 1u) / 2u + i);
-      q.g[1 + j][1 + i] = assoc_cov_i128(tot + at) - assoc_cov_i128(row + at);
+      q.g[1 + j][1 + i] = exact_i128(tot + at) - exact_i128(row + at);
     }
     const uint32_t at = assoc_cov_word_cy(l, k * J + j);
-    q.g[iy][1 + j] = assoc_cov_i128(tot + at) - assoc_cov_i128(row + at);
+    q.g[iy][1 + j] = exact_i128(tot + at) - exact_i128(row + at);
   }
   q.g[ig][0] = q.sg;
   q.g[ig][ig] = (int64_t)s.n_het + 4 * (int64_t)s.n_hom;
@@ -161,7 +132,7 @@ inline int assoc_cov_stat(const AssocCovGram &q, double out[6]) {
   const double tiny = 9.313225746154785e-10;  // 2^-30
   double D[BVCF_COVAR_DIM][BVCF_COVAR_DIM], u[BVCF_COVAR_DIM][BVCF_COVAR_DIM], L[BVCF_COVAR_DIM][BVCF_COVAR_DIM], d[BVCF_COVAR_DIM];
   for (uint32_t a = 0; a < m; a++)
-    for (uint32_t b = 0; b <= a; b++) D[a][b] = assoc_cov_double(q.g[a][b]);
+    for (uint32_t b = 0; b <= a; b++) D[a][b] = exact_double(q.g[a][b]);
   double rss0 = 0.0;
   for (uint32_t a = 0; a < m; a++) {
     for (uint32_t b = 0; b < a; b++) {

@@ -8,8 +8,8 @@
 // the short lists (BVCF_ALLELE_CMAP_SPARSE) as dense rows, and the rows back to back in output order: a .bed row is
 // ceil(S / 4) bytes without padding, a map is padded to 16.  Behind each batch's chain:
 //   k_bed_count  one thread per line, a workgroup per tile of 256 lines: how many of the line's records are rows (the slot
-//                rules of bvcf_result.alleles, as k_ss_list reads them from the record's side), the rows in front of the
-//                line within its tile (wave scans), the tile's rows
+//                rules of bvcf_result.alleles, as is_row -- bvcf_rows.hip.h -- reads them from the record's side), the
+//                rows in front of the line within its tile (wave scans), the tile's rows
 //   k_bed_scan   exclusive prefix over the tiles in input order (one workgroup: a block has some 1 200 tiles) -> the rows
 //                in front of every tile, the batch's row count
 //   k_bed_index  one thread per line again: row r of the batch is record ... -> row_src[r] = {its map's offset, its form}:

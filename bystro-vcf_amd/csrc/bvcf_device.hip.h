@@ -51,6 +51,8 @@
 //   (bvcf_params.want_sample_stats, at the end of the chain of a file with samples: k_ss_list / k_ss_dense / k_ss_sparse
 //    count, per sample, the rows whose class maps name it -- bvcf_samplestats.hip.h; k_ss_fold adds a collected batch's
 //    counts to the slot's totals)
+//   (bvcf_rows.hip.h holds what these and the kernels below share: which alleles[] slots are rows, reading a short list and
+//    the int8 matrix-core step; bvcf_exact.h the exact-integer arithmetic)
 //   (bvcf_enable_pair_stats, behind them and from the same row lists: k_pr_planes / k_pr_gemm / k_pr_sparse count, per
 //    pair of samples, the rows that name both -- the bit-matrix product behind --relatedness, bvcf_pairstats.hip.h;
 //    k_pr_fold adds a collected batch's tables to the ctx's totals)
@@ -122,6 +124,7 @@
 
 
 #include "bvcf_common.hip.h"
+#include "bvcf_rows.hip.h"
 #include "bvcf_index.hip.h"
 #include "bvcf_alleles.hip.h"
 #include "bvcf_gtscan.hip.h"

@@ -6,7 +6,7 @@
 // standard score of dosage g (bvcf_grm_q.h; q(missing) = 0) and M = 1 for a missing call.  Summed over the GRM rows:
 //   T(i,j) = sum q(g_i) q(g_j)     MM(i,j) = sum M_i M_j     N = their number
 // all exact: the host divides (bvcf_host_common.cpp).  Behind each batch's chain, where the k_pr_* kernels sit:
-//   k_grm_list    one thread per alleles[] slot, k_ss_list's slot rules: the GRM rows with a dense map and those with a
+//   k_grm_list    one thread per alleles[] slot, is_row's slot rules: the GRM rows with a dense map and those with a
 //                 short list, each with its own entry -- the map and the three scores as three balanced base-256 int8
 //                 limbs (k_ss_list's entries carry no counts and stay as they are).  A monomorphic row is in neither list.
 //   k_grm_pack    a chunk of kGrmChunkRows dense rows becomes the int8 operand of the product: per tile of 64 rows four
@@ -31,8 +31,8 @@
 // is submitted again) never counts.
 #pragma once
 
-#include "bvcf_common.hip.h"
 #include "bvcf_grm_q.h"
+#include "bvcf_rows.hip.h"
 
 namespace bvcf_dev {
 
@@ -55,8 +55,6 @@ static_assert(kGrmChunkRows <= kGrmFlushRows && 3ull * (1ull << 14) * kGrmFlushR
 constexpr uint64_t kGrmMaxBatchRows = BVCF_GRM_MAX_BATCH_ROWS;
 static_assert((kGrmMaxBatchRows << 44) <= (1ull << 63), "the batch's int64 tables cannot overflow");
 static_assert(16ull * BVCF_GRM_MAX_N * BVCF_GRM_MAX_N < 182ull * 182ull * 2ull * (2ull * BVCF_GRM_MAX_N - 1ull), "z(2) - z(0) < 182");
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // a GRM row: its map and q(0), q(1), q(2) as limbs (grm_limbs)
 struct GrmRow {
@@ -93,7 +91,7 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_list(KernelArgs a, GrmArgs g
     GrmRow ent{0u, {0u, 0u, 0u}};
     if (k < n_alleles) {
       const bvcf_allele r = a.alleles[k];
-      // (k_ss_list's slot rules: slot k < n_lines is line k's first allele, the others belong to r.line's run)
+      // (is_row's slot rules, bvcf_rows.hip.h: slot k < n_lines is line k's first allele, the others belong to r.line's run)
       const uint32_t li = k < n_lines ? k : r.line;
       bool row = false;
       if (li < n_lines) {
@@ -198,8 +196,6 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_pack(KernelArgs a, GrmArgs g
   }
 }
 
-__device__ __forceinline__ i32x4 grm_mfma(i32x4 a, i32x4 b, i32x4 c) { return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0); }
-
 // blockIdx.x = j-block, blockIdx.y = i-block; the chunk that starts at dense row row0
 __global__ __launch_bounds__(kWgThreads) void k_grm_gemm(GrmArgs ga, uint32_t row0) {
   const uint32_t jb = blockIdx.x, ib = blockIdx.y;
@@ -231,8 +227,8 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_gemm(GrmArgs ga, uint32_t ro
 #pragma unroll
       for (uint32_t la = 0; la < 3; la++)
 #pragma unroll
-        for (uint32_t lb = 0; lb < 3; lb++) acc[js][la + lb] = grm_mfma(fa[la], fb[lb], acc[js][la + lb]);
-      acc[js][5] = grm_mfma(fa[3], fb[3], acc[js][5]);
+        for (uint32_t lb = 0; lb < 3; lb++) acc[js][la + lb] = mfma_i8(fa[la], fb[lb], acc[js][la + lb]);
+      acc[js][5] = mfma_i8(fa[3], fb[3], acc[js][5]);
     }
   }
   // C/D: the lane holds column j = lane & 15 and rows i = 4 (lane >> 4) + reg of each 16 x 16 block
@@ -272,11 +268,9 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_sparse(KernelArgs a, GrmArgs
     const long long d_het = grm_unlimbs(row.tab[1]) - q0, d_hom = grm_unlimbs(row.tab[2]) - q0;
     const auto d = [&](uint32_t cls) { return cls == BVCF_CLS_HET ? d_het : cls == BVCF_CLS_HOM ? d_hom : -q0; };
     if (e == 0u) c_sum += q0 * q0;
-    const uint32_t *cm = reinterpret_cast<const uint32_t *>(a.cmap + row.cmap_off);
-    const uint32_t n = min(cm[0], (uint32_t)BVCF_CMAP_SPARSE_MAX);
-    if (e >= n) continue;
-    const uint32_t v = cm[1u + e];
-    const uint32_t byte_e = v & 0xFFu, s_e = (v >> 8) * 4u;
+    const ShortList list(a.cmap, row.cmap_off);
+    uint32_t byte_e, s_e;
+    if (!list.entry(e, &byte_e, &s_e)) continue;
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++) {
       const uint32_t ci = (byte_e >> (2u * q)) & 3u;
@@ -284,9 +278,9 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_sparse(KernelArgs a, GrmArgs
       if (ci == BVCF_CLS_NONE || i >= ns) continue;
       // (a sample is in one entry of its list: once per row)
       atomicAdd(reinterpret_cast<unsigned long long *>(ga.bv + i), (unsigned long long)(q0 * d(ci)));
-      for (uint32_t f = 0; f < n; f++) {
-        const uint32_t vf = cm[1u + f];
-        const uint32_t byte_f = vf & 0xFFu, s_f = (vf >> 8) * 4u;
+      for (uint32_t f = 0; f < list.n; f++) {
+        uint32_t byte_f, s_f;
+        list.entry(f, &byte_f, &s_f);
 #pragma unroll
         for (uint32_t q2 = 0; q2 < 4; q2++) {
           const uint32_t cj = (byte_f >> (2u * q2)) & 3u;
@@ -310,10 +304,10 @@ __global__ __launch_bounds__(kWgThreads) void k_grm_fold(GrmArgs ga) {
   for (size_t t = (size_t)blockIdx.x * kWgThreads + threadIdx.x; t < n; t += (size_t)gridDim.x * kWgThreads) {
     const size_t i = t / ns, j = t % ns;
     uint64_t lo = ga.tot[t], hi = ga.tot[n + t];
-    grm_add128(&lo, &hi, ga.bt[t]);
-    grm_add128(&lo, &hi, c);
-    grm_add128(&lo, &hi, ga.bv[i]);
-    grm_add128(&lo, &hi, ga.bv[j]);
+    exact_add128s(&lo, &hi, ga.bt[t], 0u);
+    exact_add128s(&lo, &hi, c, 0u);
+    exact_add128s(&lo, &hi, ga.bv[i], 0u);
+    exact_add128s(&lo, &hi, ga.bv[j], 0u);
     ga.tot[t] = lo;
     ga.tot[n + t] = hi;
     const uint32_t mm = ga.bmm[t];

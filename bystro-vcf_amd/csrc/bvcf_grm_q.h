@@ -1,4 +1,4 @@
-// bvcf_grm_q.h — the exact quantiser of the GRM (--grm) and a 128-bit add, for the kernels (bvcf_grm.hip.h), the host
+// bvcf_grm_q.h — the exact quantiser of the GRM (--grm) and its packed limbs, for the kernels (bvcf_grm.hip.h), the host
 // writer (bvcf_host_common.cpp) and a stand-alone CPU test alike.  Nothing else lives here.
 //
 // A row with n called samples and a = n_het + 2 n_hom ALT alleles has D = 2 a (2n - a); the standard score of dosage g is
@@ -8,14 +8,7 @@
 #ifndef BVCF_GRM_Q_H
 #define BVCF_GRM_Q_H
 
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define BVCF_GRM_HD __host__ __device__ inline
-#else
-#define BVCF_GRM_HD inline
-#endif
+#include "bvcf_exact.h"
 
 // most called samples of a row the bounds below are derived for (BVCF_PAIR_MAX_SAMPLES)
 #define BVCF_GRM_MAX_N 8192u
@@ -33,14 +26,14 @@ static_assert(2ull * (2ull * BVCF_GRM_MAX_N - 1ull) < 182ull * 182ull, "|z| < 18
 static_assert((1ll << 22) < 127ll + 127ll * 256 + 127ll * 65536, "|q| < 2^22 fits three balanced int8 limbs");
 
 // is (2m - 1)^2 D <= 4 num^2 2^28 ?  (m >= 1, num = |2n g - 2a| <= 4n, D <= 2 n^2: the left side needs more than 64 bits)
-BVCF_GRM_HD bool grm_q_fits(uint64_t m, uint64_t num, uint64_t D) {
+BVCF_HD bool grm_q_fits(uint64_t m, uint64_t num, uint64_t D) {
   const unsigned __int128 l = (unsigned __int128)((2 * m - 1) * (2 * m - 1)) * D;
   const unsigned __int128 r = (unsigned __int128)(num * num) << (2 * BVCF_GRM_SHIFT + 2);
   return l <= r;
 }
 
 // q(g) of a row with n called samples (1 <= n <= BVCF_GRM_MAX_N) and a ALT alleles (0 < a < 2n), g in {0, 1, 2}
-BVCF_GRM_HD int32_t grm_q(uint32_t n, uint32_t a, uint32_t g) {
+BVCF_HD int32_t grm_q(uint32_t n, uint32_t a, uint32_t g) {
   const int64_t snum = 2ll * (int64_t)n * (int64_t)g - 2ll * (int64_t)a;
   if (snum == 0) return 0;
   const uint64_t num = (uint64_t)(snum < 0 ? -snum : snum);
@@ -52,28 +45,15 @@ BVCF_GRM_HD int32_t grm_q(uint32_t n, uint32_t a, uint32_t g) {
 }
 
 // q as three balanced base-256 digits, q = l0 + 256 l1 + 65536 l2 with every l in [-128, 127], packed as bytes 0..2
-BVCF_GRM_HD uint32_t grm_limbs(int32_t q) {
+BVCF_HD uint32_t grm_limbs(int32_t q) {
   const int32_t l0 = ((q + 128) & 255) - 128;
   q = (q - l0) >> 8;  // (exact: q - l0 is a multiple of 256)
   const int32_t l1 = ((q + 128) & 255) - 128;
   const int32_t l2 = (q - l1) >> 8;
   return (uint32_t)(l0 & 255) | (uint32_t)(l1 & 255) << 8 | (uint32_t)(l2 & 255) << 16;
 }
-BVCF_GRM_HD int32_t grm_unlimbs(uint32_t w) {
+BVCF_HD int32_t grm_unlimbs(uint32_t w) {
   return (int32_t)(int8_t)(w & 255u) + 256 * (int32_t)(int8_t)((w >> 8) & 255u) + 65536 * (int32_t)(int8_t)((w >> 16) & 255u);
-}
-
-// (lo, hi) += the sign-extended v: a 128-bit two's complement sum as two 64-bit words with carry
-BVCF_GRM_HD void grm_add128(uint64_t *lo, uint64_t *hi, int64_t v) {
-  const uint64_t old = *lo;
-  *lo = old + (uint64_t)v;
-  *hi += (v < 0 ? ~0ull : 0ull) + (*lo < old ? 1ull : 0ull);
-}
-// (lo, hi) += (vlo, vhi)
-BVCF_GRM_HD void grm_add128w(uint64_t *lo, uint64_t *hi, uint64_t vlo, uint64_t vhi) {
-  const uint64_t old = *lo;
-  *lo = old + vlo;
-  *hi += vhi + (*lo < old ? 1ull : 0ull);
 }
 
 #endif /* BVCF_GRM_Q_H */

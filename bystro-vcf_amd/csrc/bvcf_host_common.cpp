@@ -1698,7 +1698,7 @@ int open_grm(Run &R, std::string *msg) {
 void add_grm_table(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns) {
   const size_t n = ns * ns;
   sum.resize(grm_table_words(ns), 0);
-  for (size_t k = 0; k < n; k++) grm_add128w(&sum[k], &sum[n + k], t[k], t[n + k]);
+  for (size_t k = 0; k < n; k++) exact_add128(&sum[k], &sum[n + k], t[k], t[n + k]);
   for (size_t k = 2 * n; k < 3 * n + 1; k++) sum[k] += t[k];
 }
 
@@ -1883,7 +1883,7 @@ int open_score(Run &R, std::string *msg) {
 void add_score_words(std::vector<uint64_t> &sum, const uint64_t *t, size_t ns, size_t k) {
   const size_t n = ns * k;
   sum.resize(score_table_words(ns, k), 0);
-  for (size_t q = 0; q < n; q++) score_add128w(&sum[q], &sum[n + q], t[q], t[n + q]);
+  for (size_t q = 0; q < n; q++) exact_add128(&sum[q], &sum[n + q], t[q], t[n + q]);
   for (size_t q = 2 * n; q < 2 * n + 2 * ns + 1; q++) sum[q] += t[q];
 }
 

@@ -12,7 +12,7 @@
 //   intervals  {beg, end}, 1-based inclusive; per name and set sorted, overlapping and abutting ones merged, so both beg
 //              and end ascend and the first interval with end >= lo is the only one that has to be tested against hi
 // Right behind k_finish and IN FRONT OF the variant gate and the site gate
-//   k_region_gate  one thread per alleles[] slot, the slot rules of k_site_gate.  The thread hashes the CHROM bytes of its
+//   k_region_gate  one thread per alleles[] slot, the rows by is_row (bvcf_rows.hip.h).  The thread hashes the CHROM bytes of its
 //                  line under the "chr" rule, probes, confirms a tag hit on the bytes, takes pos from the record or -- a
 //                  BVCF_ALLELE_POS_TEXT row, whose record holds pos = 0 -- parses the POS bytes of the block, forms the span
 //                  and binary-searches the name's intervals once per set that is on.  A row taken out gets ac = 0, which
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(kWgThreads) void k_region_gate(KernelArgs a, Region
   const BlockText text{a.buf, a.buf ? a.cap : 0u};
   for (uint32_t k = blockIdx.x * kWgThreads + threadIdx.x; k < n_alleles; k += gridDim.x * kWgThreads) {
     const bvcf_allele r = a.alleles[k];
-    if (!gate_is_row(a, k, n_lines, r)) continue;
+    if (!is_row(a, k, n_lines, r)) continue;
     const bvcf_line L = a.lines[k < n_lines ? k : r.line];
     long long pos = r.pos;
     bool has_pos;

@@ -17,7 +17,7 @@
 // BVCF_E_CAPACITY (and is submitted again) never counts.
 #pragma once
 
-#include "bvcf_common.hip.h"
+#include "bvcf_rows.hip.h"
 
 namespace bvcf_dev {
 
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kWgThreads) void k_ss_list(KernelArgs a, SampleStat
     uint2 ent = make_uint2(0u, 0u);
     if (k < n_alleles) {
       const bvcf_allele r = a.alleles[k];
-      // (the slot rules of bvcf_result.alleles: slot k < n_lines is line k's first allele, the others belong to
+      // (is_row's slot rules, bvcf_rows.hip.h: slot k < n_lines is line k's first allele, the others belong to
       // r.line's run [rec_first, rec_first + n_rec - 1))
       const uint32_t li = k < n_lines ? k : r.line;
       if (li < n_lines) {
@@ -199,11 +199,8 @@ __global__ __launch_bounds__(kWgThreads) void k_ss_sparse(KernelArgs a, SampleSt
   const uint32_t e = g & 15u;  // the lane's entry of the list
   for (uint32_t j = g >> 4; j < n_sparse; j += (gridDim.x * kWgThreads) >> 4) {
     const uint2 ent = sa.sparse[j];
-    const uint32_t *cm = reinterpret_cast<const uint32_t *>(a.cmap + ent.x);
-    const uint32_t n = min(cm[0], (uint32_t)BVCF_CMAP_SPARSE_MAX);
-    if (e >= n) continue;
-    const uint32_t v = cm[1u + e];
-    const uint32_t byte = v & 0xFFu, s_base = (v >> 8) * 4u;
+    uint32_t byte, s_base;
+    if (!ShortList(a.cmap, ent.x).entry(e, &byte, &s_base)) continue;
 #pragma unroll
     for (uint32_t q = 0; q < 4; q++) {
       const uint32_t cls = (byte >> (2u * q)) & 3u, s = s_base + q;

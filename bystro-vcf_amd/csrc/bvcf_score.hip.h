@@ -8,7 +8,7 @@
 // 1 (het), 2 (hom) or missing (adds nothing), M = 1 for a missing call, summed over the matched rows -- monomorphic ones too:
 //   T(i,k) = sum W_k g_i     G(i) = sum g_i     X(i) = sum M_i     R = their number
 // all exact.  Behind each batch's chain:
-//   k_score_list    one thread per alleles[] slot, k_ss_list's slot rules; the thread walks the row's locus as
+//   k_score_list    one thread per alleles[] slot, is_row's slot rules; the thread walks the row's locus as
 //                   k_variant_gate does and probes.  Matched rows go to a list of {cmap_off, entry} by the form of their
 //                   map (wave ballots, one atomic per workgroup and list); one without a map is counted: every sample is
 //                   missing in it, as k_bed_rows has it.
@@ -49,8 +49,6 @@ static_assert(256ull * kScoreFlushTiles * kScoreTile <= (1ull << 30), "int32 acc
 // an unsigned word, g hi to less than 2^62.
 static_assert(2ull * ((1ull << 31) - 1ull) <= ~0ull / ((1ull << 32) - 1ull), "the lo halves of a batch fit uint64");
 static_assert(BVCF_SCORE_MAX_W / (1ll << 31) + 1 < (1ll << 29), "the hi halves of a batch fit int64");
-
-typedef int score_i32x4 __attribute__((ext_vector_type(4)));
 
 struct ScoreArgs {
   const VariantEntry *entries;  // the score table: {tag, off, len, weight row}
@@ -103,7 +101,7 @@ __global__ __launch_bounds__(kWgThreads) void k_score_list(KernelArgs a, ScoreAr
     uint2 ent = make_uint2(0u, 0u);
     if (k < n_alleles) {
       const bvcf_allele r = a.alleles[k];
-      // (k_ss_list's slot rules: slot k < n_lines is line k's first allele, the others belong to r.line's run)
+      // (is_row's slot rules, bvcf_rows.hip.h: slot k < n_lines is line k's first allele, the others belong to r.line's run)
       const uint32_t li = k < n_lines ? k : r.line;
       bool row = false;
       bvcf_line L{};
@@ -158,13 +156,9 @@ __global__ __launch_bounds__(kWgThreads) void k_score_list(KernelArgs a, ScoreAr
   }
 }
 
-__device__ __forceinline__ score_i32x4 score_mfma(score_i32x4 a, score_i32x4 b, score_i32x4 c) {
-  return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-}
-
 // the wave's sums into the batch's table and back to zero.  C/D: the lane holds weight column lane & 15 of each block and
 // samples 4 (lane >> 4) + reg of the wave's 16
-__device__ __forceinline__ void score_flush(const ScoreArgs &sa, score_i32x4 (&acc)[kScoreGroupBlocks], score_i32x4 &accm, uint32_t i0,
+__device__ __forceinline__ void score_flush(const ScoreArgs &sa, i32x4 (&acc)[kScoreGroupBlocks], i32x4 &accm, uint32_t i0,
                                             uint32_t col0, uint32_t n_blk, bool with_m, uint32_t lane) {
   const uint32_t s = lane & 15u, h = lane >> 4;
   const size_t row = (size_t)sa.n_cols + 1u;
@@ -183,8 +177,8 @@ __device__ __forceinline__ void score_flush(const ScoreArgs &sa, score_i32x4 (&a
     }
   }
 #pragma unroll
-  for (uint32_t b = 0; b < kScoreGroupBlocks; b++) acc[b] = score_i32x4{0, 0, 0, 0};
-  accm = score_i32x4{0, 0, 0, 0};
+  for (uint32_t b = 0; b < kScoreGroupBlocks; b++) acc[b] = i32x4{0, 0, 0, 0};
+  accm = i32x4{0, 0, 0, 0};
 }
 
 // blockIdx.x = block of 64 samples, blockIdx.y = group of kScoreGroupCols weight columns, blockIdx.z = the run of tiles
@@ -200,9 +194,9 @@ __global__ __launch_bounds__(kWgThreads) void k_score_gemm(KernelArgs a, ScoreAr
   const uint32_t s = lane & 15u, h = lane >> 4;
   const uint32_t i0 = blockIdx.x * kScoreBlock + w * 16u;  // the wave's samples: map bytes 16 blockIdx.x + 4 w .. + 3
   const uint32_t r = threadIdx.x & 63u, part = threadIdx.x >> 6;
-  score_i32x4 acc[kScoreGroupBlocks], accm = score_i32x4{0, 0, 0, 0};
+  i32x4 acc[kScoreGroupBlocks], accm = i32x4{0, 0, 0, 0};
 #pragma unroll
-  for (uint32_t b = 0; b < kScoreGroupBlocks; b++) acc[b] = score_i32x4{0, 0, 0, 0};
+  for (uint32_t b = 0; b < kScoreGroupBlocks; b++) acc[b] = i32x4{0, 0, 0, 0};
   uint32_t pending = 0;
   for (uint32_t tile = blockIdx.z; tile < n_tiles; tile += gridDim.z) {
     __syncthreads();  // (the tile before has been read)
@@ -224,7 +218,7 @@ __global__ __launch_bounds__(kWgThreads) void k_score_gemm(KernelArgs a, ScoreAr
     }
     __syncthreads();
     // the A side: sample 16 w + s is bits 2 s of dword w of a row's 16 map bytes; rows 16 h .. 16 h + 15 of the tile
-    score_i32x4 fa = score_i32x4{0, 0, 0, 0}, fm = score_i32x4{0, 0, 0, 0};
+    i32x4 fa = i32x4{0, 0, 0, 0}, fm = i32x4{0, 0, 0, 0};
 #pragma unroll
     for (uint32_t j = 0; j < 16; j++) {
       const uint32_t cls = (s_map[16u * h + j][w] >> (2u * s)) & 3u;
@@ -236,13 +230,13 @@ __global__ __launch_bounds__(kWgThreads) void k_score_gemm(KernelArgs a, ScoreAr
 #pragma unroll
     for (uint32_t b = 0; b < kScoreGroupBlocks; b++) {
       if (b < n_blk) {
-        const score_i32x4 fb = *reinterpret_cast<const score_i32x4 *>(s_b + (16u * b + s) * kScoreBStride + 16u * h);
-        acc[b] = score_mfma(fa, fb, acc[b]);
+        const i32x4 fb = *reinterpret_cast<const i32x4 *>(s_b + (16u * b + s) * kScoreBStride + 16u * h);
+        acc[b] = mfma_i8(fa, fb, acc[b]);
       }
     }
     if (with_m) {
       const int ones = s == 0u ? 0x01010101 : 0;  // (column 0 of the B side: the constant 1)
-      accm = score_mfma(fm, score_i32x4{ones, ones, ones, ones}, accm);
+      accm = mfma_i8(fm, i32x4{ones, ones, ones, ones}, accm);
     }
     if (++pending == kScoreFlushTiles) {
       score_flush(sa, acc, accm, i0, col0, n_blk, with_m, lane);
@@ -282,7 +276,9 @@ __global__ __launch_bounds__(kWgThreads) void k_score_sparse(KernelArgs a, Score
     if (!(dos[0] | dos[1] | dos[2] | dos[3])) continue;
     const int8_t *wr = sa.weights + (size_t)ent.y * sa.wstride;
     for (uint32_t k = 0; k < sa.K; k++) {
-      const long long W = score_unlimbs(wr + k * sa.L, (int)sa.L);
+      long long W = 0;  // (exact_unlimbs' value, from the top limb down)
+      const int8_t *limb = wr + k * sa.L;
+      for (int l = (int)sa.L; l-- > 0;) W = W * 256 + limb[l];
       if (!W) continue;
       const unsigned long long lo = (unsigned long long)W & 0x7FFFFFFFull;
       const long long hi = W >> 31;  // (floor: W = lo + 2^31 hi)
@@ -297,6 +293,13 @@ __global__ __launch_bounds__(kWgThreads) void k_score_sparse(KernelArgs a, Score
   }
 }
 
+// exact_add128s for 0 <= sh < 64, which is all k_score_fold shifts by: with the general form the kernel takes two more
+// registers and measured 2 % slower
+__device__ __forceinline__ void score_fold_add(uint64_t *lo, uint64_t *hi, int64_t v, unsigned sh) {
+  const uint64_t vhi = sh ? (uint64_t)(v >> (64u - sh)) : (v < 0 ? ~0ull : 0ull);
+  exact_add128(lo, hi, (uint64_t)v << sh, vhi);
+}
+
 // bvcf_collect, batch OK: its tables into the totals (one thread per (sample, column) and one more per sample: a single
 // writer each)
 __global__ __launch_bounds__(kWgThreads) void k_score_fold(ScoreArgs sa) {
@@ -308,9 +311,9 @@ __global__ __launch_bounds__(kWgThreads) void k_score_fold(ScoreArgs sa) {
     if (k < K) {
       const size_t at = i * K + k;
       uint64_t lo = sa.tot[at], hi = sa.tot[ns * K + at];
-      for (uint32_t l = 0; l < sa.L; l++) score_add128s(&lo, &hi, sa.bt[i * row + k * sa.L + l], 8u * l);
-      score_add128w(&lo, &hi, sa.slo[at], 0ull);
-      score_add128s(&lo, &hi, sa.shi[at], 31u);
+      for (uint32_t l = 0; l < sa.L; l++) score_fold_add(&lo, &hi, sa.bt[i * row + k * sa.L + l], 8u * l);
+      exact_add128(&lo, &hi, sa.slo[at], 0ull);
+      score_fold_add(&lo, &hi, sa.shi[at], 31u);
       sa.tot[at] = lo;
       sa.tot[ns * K + at] = hi;
     } else {

@@ -5,7 +5,7 @@
 // record's counts are final, the gate examines every such row and takes the failing ones out by setting ac = 0 -- which is
 // what every consumer behind it (k_dosage*, the name lists, k_ss_list and through it the pair kernels, the host formatter
 // and the dosage writer) already drops -- and leaves the reasons in bvcf_allele.pad[0] (BVCF_GATE_*).
-//   k_site_gate  one thread per alleles[] slot, the slot rules of k_ss_list.  The cheap criteria, and the exact HWE test of
+//   k_site_gate  one thread per alleles[] slot, the rows by is_row (bvcf_rows.hip.h).  The cheap criteria, and the exact HWE test of
 //                rows whose support has at most kHweInlineTerms terms (every short-list row; most rows of a cohort file),
 //                by the sequential recurrence from the mode.  Longer rows are listed (wave ballots + one atomic per
 //                workgroup, as k_ss_list compacts) for
@@ -19,7 +19,7 @@
 
 #include <math.h>
 
-#include "bvcf_common.hip.h"
+#include "bvcf_rows.hip.h"
 
 namespace bvcf_dev {
 
@@ -229,15 +229,6 @@ __device__ inline double hwe_exact_wave(uint32_t het, uint32_t hom, uint32_t oth
   return p > 1.0 ? 1.0 : p;
 }
 
-// is slot k of alleles[] a row the TSV would print?  (the slot rules of bvcf_result.alleles, as in k_ss_list)
-__device__ __forceinline__ bool gate_is_row(const KernelArgs &a, uint32_t k, uint32_t n_lines, const bvcf_allele &r) {
-  const uint32_t li = k < n_lines ? k : r.line;
-  if (li >= n_lines) return false;
-  const bvcf_line L = a.lines[li];
-  return L.status == BVCF_LINE_OK && L.n_rec > 0 && r.ac != 0 &&
-         (k < n_lines || (k >= L.rec_first && k - L.rec_first + 1u < L.n_rec));
-}
-
 __global__ __launch_bounds__(kWgThreads) void k_site_gate(KernelArgs a, SiteGateArgs ga) {
   __shared__ uint32_t s_wave[kWavesPerWg];
   __shared__ uint32_t s_base;
@@ -251,7 +242,7 @@ __global__ __launch_bounds__(kWgThreads) void k_site_gate(KernelArgs a, SiteGate
     bool listed = false;
     if (k < n_alleles) {
       const bvcf_allele r = a.alleles[k];
-      if (gate_is_row(a, k, n_lines, r)) {
+      if (is_row(a, k, n_lines, r)) {
         uint32_t bits = site_gate_cheap(ga.g, a.n_samples, r.ac, r.an, r.n_miss);
         if (hwe_on) {
           uint32_t het, hom, other;

@@ -8,7 +8,7 @@
 //            h = FNV-1a 64 of the locus bytes, the home slot is h & (capacity - 1), tag = h >> 32, linear probing
 //   blob     the entries' bytes, entry e at blob[e.off, e.off + e.len)
 // Right behind k_finish and IN FRONT OF the site gate
-//   k_variant_gate  one thread per alleles[] slot, the slot rules of k_site_gate.  The thread walks the bytes of the row's
+//   k_variant_gate  one thread per alleles[] slot, the rows by is_row (bvcf_rows.hip.h).  The thread walks the bytes of the row's
 //                   locus piecewise -- nothing is materialised: the CHROM bytes of the block with the "chr" rule, the
 //                   digits of pos (or the POS bytes), ref, and the base / '+' and the inserted bases of the block / '-'
 //                   and the digits of the length -- once to hash them; it then probes, and on an entry of its tag and
@@ -162,7 +162,7 @@ __global__ __launch_bounds__(kWgThreads) void k_variant_gate(KernelArgs a, Varia
   const BlockText text{a.buf, a.buf ? a.cap : 0u};
   for (uint32_t k = blockIdx.x * kWgThreads + threadIdx.x; k < n_alleles; k += gridDim.x * kWgThreads) {
     const bvcf_allele r = a.alleles[k];
-    if (!gate_is_row(a, k, n_lines, r)) continue;
+    if (!is_row(a, k, n_lines, r)) continue;
     const bvcf_line L = a.lines[k < n_lines ? k : r.line];
     LocusHasher hs;
     locus_bytes(text, L, r, hs);

@@ -40,10 +40,10 @@ int main(int argc, char **argv) {
     free(exact);
     if (rc) y = 0;
     int8_t l1[16], l2[16];
-    const int n1 = assoc_limbs(y, l1);
+    const int n1 = exact_limbs(y, l1, 16);
     uint64_t lo, hi;
-    assoc_square(y, &lo, &hi);
-    const int n2 = assoc_limbs128(lo, hi, l2);
+    exact_square(y, &lo, &hi);
+    const int n2 = exact_limbs128(lo, hi, l2, 16);
     printf("%d %" PRId64 " %d %d", rc, y, n1, n2);
     for (int a = 0; a < BVCF_ASSOC_MAX_LIMBS1; a++) printf(" %d", l1[a]);
     for (int a = 0; a < BVCF_ASSOC_MAX_LIMBS2; a++) printf(" %d", l2[a]);
@@ -53,7 +53,7 @@ int main(int argc, char **argv) {
       if (l2[a]) return 3;
     // the limbs put together again with the adds the kernels use
     uint64_t rl = 0, rh = 0;
-    for (int a = 0; a < 16; a++) assoc_add128s(&rl, &rh, l2[a], 8u * (unsigned)a);
+    for (int a = 0; a < 16; a++) exact_add128s(&rl, &rh, l2[a], 8u * (unsigned)a);
     if (rl != lo || rh != hi) return 4;
     printf("\n");
   }
@@ -82,22 +82,22 @@ int main(int argc, char **argv) {
     const int have = assoc_stat(q, out);
     printf("%" PRId64 " %" PRId64 " %s %s %s %d", q.n, q.sg, dec128(q.c).c_str(), dec128(q.va).c_str(), dec128(q.vb).c_str(), have);
     for (int k = 0; k < 6; k++) printf(" %a", out[k]);
-    printf(" %a %a %a\n", assoc_double(q.c), assoc_double(q.va), assoc_double(q.vb));
+    printf(" %a %a %a\n", exact_double(q.c), exact_double(q.va), exact_double(q.vb));
   }
   fclose(f);
   // carries: (2^64 - 1) + 1, a negative term across the words, shifts on both sides of 64
   uint64_t lo = ~0ull, hi = 0;
-  assoc_add128w(&lo, &hi, 1, 0);
+  exact_add128(&lo, &hi, 1, 0);
   if (lo != 0 || hi != 1) return 6;
-  assoc_add128s(&lo, &hi, -1, 0);
+  exact_add128s(&lo, &hi, -1, 0);
   if (lo != ~0ull || hi != 0) return 6;
   lo = hi = 0;
-  assoc_add128s(&lo, &hi, -3, 63);
-  assoc_add128s(&lo, &hi, 3, 63);
-  assoc_add128s(&lo, &hi, -5, 64);
-  assoc_add128s(&lo, &hi, 5, 64);
-  assoc_add128s(&lo, &hi, -7, 100);
-  assoc_add128s(&lo, &hi, 7, 100);
+  exact_add128s(&lo, &hi, -3, 63);
+  exact_add128s(&lo, &hi, 3, 63);
+  exact_add128s(&lo, &hi, -5, 64);
+  exact_add128s(&lo, &hi, 5, 64);
+  exact_add128s(&lo, &hi, -7, 100);
+  exact_add128s(&lo, &hi, 7, 100);
   if (lo || hi) return 6;
   printf("assoc_q ok\n");
   return 0;

@@ -48,25 +48,25 @@ int main(int argc, char **argv) {
 
   // 128-bit sums: a carry out of the low word, a borrow back, the sign extension of a negative addend, two full words
   uint64_t lo = ~0ull - 1, hi = 0;
-  grm_add128(&lo, &hi, 5);
+  exact_add128s(&lo, &hi, 5, 0u);
   CHECK(lo == 3 && hi == 1, "carry: %llx %llx", (unsigned long long)hi, (unsigned long long)lo);
-  grm_add128(&lo, &hi, -4);
+  exact_add128s(&lo, &hi, -4, 0u);
   CHECK(lo == ~0ull && hi == 0, "borrow: %llx %llx", (unsigned long long)hi, (unsigned long long)lo);
   lo = 0, hi = 0;
-  grm_add128(&lo, &hi, -1);
+  exact_add128s(&lo, &hi, -1, 0u);
   CHECK(lo == ~0ull && hi == ~0ull, "minus one: %llx %llx", (unsigned long long)hi, (unsigned long long)lo);
-  grm_add128(&lo, &hi, 1);
+  exact_add128s(&lo, &hi, 1, 0u);
   CHECK(lo == 0 && hi == 0, "back to zero: %llx %llx", (unsigned long long)hi, (unsigned long long)lo);
   __int128 want = 0;
   lo = hi = 0;
   for (int k = 0; k < 1000; k++) {  // 2^62-sized terms of both signs: the sum leaves 64 bits and comes back
     const int64_t v = (k % 3 == 2 ? -1 : 1) * ((1ll << 62) - k);
-    grm_add128(&lo, &hi, v);
+    exact_add128s(&lo, &hi, v, 0u);
     want += v;
     CHECK((uint64_t)want == lo && (uint64_t)((unsigned __int128)want >> 64) == hi, "running sum at %d", k);
   }
   uint64_t lo2 = ~0ull, hi2 = 7;
-  grm_add128w(&lo2, &hi2, lo, hi);
+  exact_add128(&lo2, &hi2, lo, hi);
   const unsigned __int128 w2 = (((unsigned __int128)7 << 64) | ~0ull) + (unsigned __int128)want;
   CHECK((uint64_t)w2 == lo2 && (uint64_t)(w2 >> 64) == hi2, "word sum");
   if (fails) return 1;

@@ -47,8 +47,8 @@ int main(int argc, char **argv) {
     const int rc = score_weight(w, n, &W);
     free(w);
     int8_t l[BVCF_SCORE_MAX_LIMBS];
-    const int nl = score_limbs(rc ? 0 : W, l);
-    CHECK(score_unlimbs(l, BVCF_SCORE_MAX_LIMBS) == (rc ? 0 : W) && score_unlimbs(l, nl) == (rc ? 0 : W), "limbs of %lld", (long long)W);
+    const int nl = exact_limbs(rc ? 0 : W, l, BVCF_SCORE_MAX_LIMBS);
+    CHECK(exact_unlimbs(l, BVCF_SCORE_MAX_LIMBS) == (rc ? 0 : W) && exact_unlimbs(l, nl) == (rc ? 0 : W), "limbs of %lld", (long long)W);
     printf("%d %lld", rc, (long long)(rc ? 0 : W));
     for (int a = 0; a < BVCF_SCORE_MAX_LIMBS; a++) printf(" %d", (int)l[a]);
     printf(" %d\n", nl);
@@ -56,8 +56,8 @@ int main(int argc, char **argv) {
   }
   for (int64_t W : {(int64_t)BVCF_SCORE_MAX_W, -(int64_t)BVCF_SCORE_MAX_W, (int64_t)127, (int64_t)128, (int64_t)-128, (int64_t)-129}) {
     int8_t l[BVCF_SCORE_MAX_LIMBS];
-    const int nl = score_limbs(W, l);
-    CHECK(score_unlimbs(l, nl) == W, "limbs of %lld", (long long)W);
+    const int nl = exact_limbs(W, l, BVCF_SCORE_MAX_LIMBS);
+    CHECK(exact_unlimbs(l, nl) == W, "limbs of %lld", (long long)W);
   }
   // the adds against the compiler's 128-bit integers
   const int64_t vals[] = {0, 1, -1, 255, -256, INT64_MAX, INT64_MIN, (int64_t)BVCF_SCORE_MAX_W, -(int64_t)BVCF_SCORE_MAX_W};
@@ -67,10 +67,10 @@ int main(int argc, char **argv) {
         __int128 want = (__int128)a * 1000003 + (__int128)b * (__int128)(1ull << sh);
         unsigned __int128 start = (unsigned __int128)((__int128)a * 1000003);
         uint64_t lo = (uint64_t)start, hi = (uint64_t)(start >> 64);
-        score_add128s(&lo, &hi, b, sh);
+        exact_add128s(&lo, &hi, b, sh);
         CHECK(lo == (uint64_t)(unsigned __int128)want && hi == (uint64_t)((unsigned __int128)want >> 64), "add128s %lld %lld %u",
               (long long)a, (long long)b, sh);
-        score_add128w(&lo, &hi, (uint64_t)a, a < 0 ? ~0ull : 0ull);
+        exact_add128(&lo, &hi, (uint64_t)a, a < 0 ? ~0ull : 0ull);
         want += a;
         CHECK(lo == (uint64_t)(unsigned __int128)want && hi == (uint64_t)((unsigned __int128)want >> 64), "add128w %lld", (long long)a);
       }

@@ -78,6 +78,21 @@ def test_worked_cases_ties_and_bounds(bv):
         assert both(bv, text) == (("bad",), ("bad",)), text
 
 
+def other_texts():
+    """the texts of the --score weight tests: the two parsers are one function with two range rules"""
+    import test_score_cpu as other
+    return [t for t, _ in other.WORKED] + other.REFUSED_BIG + other.REFUSED_BAD
+
+
+def test_the_weight_tests_texts_by_the_value_rule(bv):
+    """a text a hair above 10^6 is no value -- the bound is on the exact y -- though it is a weight"""
+    verdicts = {t: both(bv, t) for t in other_texts()}
+    for t, (a, b) in verdicts.items():
+        assert a == b, t
+    assert verdicts[b"1000000.0000000000004999"][0] == ("big",) and verdicts[b"1000000.000000000001"][0] == ("big",)
+    assert verdicts[b"999999.9999999999995"][0] == ("ok", 10 ** 12) and verdicts[b"0.0000000000005"][0] == ("ok", 0)
+
+
 def test_parser_against_fractions(bv):
     kinds = set()
     for text in seeded_texts(4000, seed=3):
@@ -390,7 +405,7 @@ def test_arithmetic_header_alone_under_sanitizers(tmp_path):
     subprocess.check_call([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC, os.path.join(ROOT, "tests", "assoc_check.cpp"),
                            "-o", exe], timeout=120)
-    texts = [t for t in seeded_texts(3000, seed=5) + [w for w, _ in WORKED] + REFUSED_BIG + REFUSED_BAD if b"\n" not in t]
+    texts = [t for t in seeded_texts(3000, seed=5) + [w for w, _ in WORKED] + REFUSED_BIG + REFUSED_BAD + other_texts() if b"\n" not in t]
     (tmp_path / "v.txt").write_bytes(b"".join(t + b"\n" for t in texts))
     cases = bound_records() + seeded_records(400, seed=33)
     m64 = (1 << 64) - 1

@@ -62,6 +62,21 @@ def test_worked_cases_ties_and_bounds(bv):
         assert both(bv, text) == (("bad",), ("bad",)), text
 
 
+def other_texts():
+    """the texts of the --pheno value tests: the two parsers are one function with two range rules"""
+    import test_assoc_cpu as other
+    return [t for t, _ in other.WORKED] + other.REFUSED_BIG + other.REFUSED_BAD
+
+
+def test_the_value_tests_texts_by_the_weight_rule(bv):
+    """a text a hair above 10^6 is a weight -- the bound is on the rounded W -- though it is no phenotype value"""
+    verdicts = {t: both(bv, t) for t in other_texts()}
+    for t, (a, b) in verdicts.items():
+        assert a == b, t
+    assert verdicts[b"1000000.000000000000000001"][0] == ("ok", 10 ** 18) and verdicts[b"1000000.0000001"][0] == ("big",)
+    assert verdicts[b"999999.9999995"][0] == ("ok", 9999999999995 * 10 ** 5) and verdicts[b"0.0000005"][0] == ("ok", 500000)
+
+
 def seeded_texts(n, seed=1):
     rng = random.Random(seed)
     out = []
@@ -374,7 +389,7 @@ def test_arithmetic_header_alone_under_sanitizers(tmp_path):
     subprocess.check_call([HIPCC, "-x", "c++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Xarch_host", "-fsanitize=address,undefined",
                            "-Xarch_host", "-fno-sanitize-recover=undefined", "-I", CSRC, os.path.join(ROOT, "tests", "score_check.cpp"),
                            "-o", exe], timeout=120)
-    texts = [t for t in seeded_texts(3000, seed=5) + [w for w, _ in WORKED] + REFUSED_BIG + REFUSED_BAD if b"\n" not in t]
+    texts = [t for t in seeded_texts(3000, seed=5) + [w for w, _ in WORKED] + REFUSED_BIG + REFUSED_BAD + other_texts() if b"\n" not in t]
     (tmp_path / "w.txt").write_bytes(b"".join(t + b"\n" for t in texts))
     p = subprocess.run([exe, str(tmp_path / "w.txt")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
     out = p.stdout.decode()
