@@ -47,7 +47,7 @@ PAIR_MAX_SAMPLES = 8192  # BVCF_PAIR_MAX_SAMPLES
 
 # the measurement hooks of include/bvcf_bench.h (not part of the drop-in ABI)
 BENCH_EXPORTS = ["bvcf_bench_device", "bvcf_bench_device_slots", "bvcf_bench_stream_kernel", "bvcf_bench_head_left",
-                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_assoc_kernels", "bvcf_bench_assoc_cov_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
+                 "bvcf_bench_pair_kernels", "bvcf_bench_grm_kernels", "bvcf_bench_score_kernels", "bvcf_bench_assoc_kernels", "bvcf_bench_assoc_cov_kernels", "bvcf_bench_assoc_logit_kernels", "bvcf_bench_hwe", "bvcf_bench_gate_kernels", "bvcf_bench_bed_kernels",
                  "bvcf_bench_deflate_codes", "bvcf_bench_trio_kernels", "bvcf_bench_ld_kernels",
                  "bvcf_bench_variant_kernel", "bvcf_bench_variant_gate_stride",
                  "bvcf_bench_region_kernel", "bvcf_bench_region_gate_stride",
@@ -87,6 +87,8 @@ EXPORTS = [
     "bvcf_grm_matrix", "bvcf_pca_eigen", "bvcf_config_pca_defaults",
     "bvcf_covar_table_parse", "bvcf_covar_table_build", "bvcf_covar_table_free", "bvcf_pheno_table_mask", "bvcf_set_covar_table",
     "bvcf_assoc_cov", "bvcf_assoc_cov_stat", "bvcf_config_covar_defaults",
+    "bvcf_logit_table_build", "bvcf_logit_table_free", "bvcf_set_logit_table", "bvcf_assoc_logit", "bvcf_assoc_logit_stat",
+    "bvcf_config_logit_defaults",
 ]
 
 
@@ -508,6 +510,30 @@ class AssocCovInfo(C.Structure):
     _fields_ = [("words", C.c_void_p), ("n_rows", C.c_uint64), ("row_words", C.c_uint32)]
 
 
+CONFIG_MORE_LOGIT = 12  # BVCF_CONFIG_MORE_LOGIT in Config.reserved[1]: the ConfigCovar is the head of a ConfigLogit
+ASSOC_MODELS = {"linear": 0, "logistic": 1}  # BVCF_ASSOC_MODEL_*
+LOGIT_ONE = 1 << 24  # BVCF_LOGIT_ONE
+
+
+class ConfigLogit(C.Structure):
+    """bvcf_config_logit: a bvcf_config_covar and what came after it"""
+    _fields_ = [("covar", ConfigCovar), ("assoc_model", C.c_uint32), ("reserved_logit", C.c_uint32)]
+
+
+class LogitTableStruct(C.Structure):
+    """bvcf_logit_table"""
+    _fields_ = [("n_covars", C.c_uint32), ("n_samples", C.c_uint32), ("s64", C.c_uint32), ("n_columns", C.c_uint32),
+                ("lwc", C.c_uint32), ("lr", C.c_uint32), ("lrc", C.c_uint32), ("lwcc", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("row_words", C.c_uint32), ("n_unfitted", C.c_uint32), ("pad", C.c_uint32), ("b", C.c_void_p), ("c", C.c_void_p),
+                ("m", C.c_void_p), ("r", C.c_void_p), ("w", C.c_void_p), ("fitted", C.c_void_p), ("rounds", C.c_void_p),
+                ("beta", C.c_void_p), ("pheno_np", C.c_void_p), ("totals", C.c_void_p)]
+
+
+class AssocLogitInfo(C.Structure):
+    """bvcf_assoc_logit_info"""
+    _fields_ = [("words", C.c_void_p), ("n_rows", C.c_uint64), ("row_words", C.c_uint32)]
+
+
 class PhenoTable:
     """a host phenotype table: bvcf_pheno_table_build over y / present (K lists of S integers Y and of S flags), or -- text=
     with sample_names= -- bvcf_pheno_table_parse over the bytes of a phenotype file  (host code, no device)"""
@@ -669,6 +695,71 @@ class CovarTable:
             self.close()
         except Exception:
             pass
+
+
+class LogitTable:
+    """bvcf_logit_table_build: the null fits, the fixed-point vectors M / R / W, the totals row and operand B from a PhenoTable
+    (the masked one with covariates) and a CovarTable or None; BvcfError with the message for a value that is not 0 / 1
+    (host code, no device)"""
+
+    def __init__(self, pheno, covar=None):
+        self.t = LogitTableStruct()
+        err = C.create_string_buffer(512)
+        lib.bvcf_logit_table_build.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        rc = lib.bvcf_logit_table_build(C.byref(pheno.t), C.byref(covar.t) if covar is not None else None, C.byref(self.t), err, len(err))
+        if rc:
+            raise BvcfError(rc, err.value.decode(errors="replace"))
+
+    n_covars = property(lambda self: int(self.t.n_covars))
+    n_samples = property(lambda self: int(self.t.n_samples))
+    s64 = property(lambda self: int(self.t.s64))
+    n_columns = property(lambda self: int(self.t.n_columns))
+    lwc = property(lambda self: int(self.t.lwc))
+    lr = property(lambda self: int(self.t.lr))
+    lrc = property(lambda self: int(self.t.lrc))
+    lwcc = property(lambda self: int(self.t.lwcc))
+    n_blocks = property(lambda self: int(self.t.n_blocks))
+    row_words = property(lambda self: int(self.t.row_words))
+    n_unfitted = property(lambda self: int(self.t.n_unfitted))
+
+    def _array(self, ptr, dtype, shape):
+        n = int(np.prod(shape))
+        if not n:
+            return np.zeros(shape, dtype=dtype)
+        return np.frombuffer(C.string_at(ptr, n * np.dtype(dtype).itemsize), dtype=dtype).reshape(shape).copy()
+
+    b = property(lambda self: self._array(self.t.b, np.int8, (16 * self.n_blocks, self.s64)))
+    c = property(lambda self: self._array(self.t.c, np.int64, (self.n_covars, self.n_samples)))
+    m = property(lambda self: self._array(self.t.m, np.int64, (self.n_columns, self.n_samples)))
+    r = property(lambda self: self._array(self.t.r, np.int64, (self.n_columns, self.n_samples)))
+    w = property(lambda self: self._array(self.t.w, np.int64, (self.n_columns, self.n_samples)))
+    fitted = property(lambda self: [int(x) for x in self._array(self.t.fitted, np.uint8, (self.n_columns,))])
+    rounds = property(lambda self: [int(x) for x in self._array(self.t.rounds, np.uint32, (self.n_columns,))])
+    beta = property(lambda self: self._array(self.t.beta, np.float64, (self.n_columns, self.n_covars + 1)))
+    totals = property(lambda self: self._array(self.t.totals, np.uint64, (self.row_words,)))
+
+    def close(self):
+        lib.bvcf_logit_table_free.argtypes = [C.c_void_p]
+        lib.bvcf_logit_table_free(C.byref(self.t))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def assoc_logit_stat(table, k, rec, totals, logit_row):
+    """bvcf_assoc_logit_stat: phenotype k of a row from its record (as assoc_stat's), the phenotype's totals and the row's
+    logistic record (row_words uint64) against a LogitTable -> (flags, [n, altFreq, beta, se, chisq, p]); flags bit 2:
+    collinear  (host code, no device)"""
+    r, t = _assoc_structs(rec, totals)
+    w = np.ascontiguousarray(logit_row, dtype=np.uint64)
+    assert w.size == table.row_words
+    out = (C.c_double * 6)()
+    lib.bvcf_assoc_logit_stat.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    flags = lib.bvcf_assoc_logit_stat(C.byref(table.t), int(k), r.ctypes.data, t.ctypes.data, w.ctypes.data, out)
+    return int(flags), list(out)
 
 
 def assoc_cov_stat(table, k, rec, totals, cov_row):
@@ -1068,7 +1159,9 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
     # (--pheno / --assoc / --assocReport: the struct behind that one and its marker, only then)
     # (--pca / --pcaCount / --pcaReport: the struct behind that one and its marker, only then)
     # (--covar: the struct behind that one and its marker, only then)
-    cvc = ConfigCovar() if cfg.get("covar") else None
+    # (--assocModel: the struct behind that one and its marker, only then)
+    lgc = ConfigLogit() if cfg.get("assocModel") is not None else None
+    cvc = lgc.covar if lgc is not None else ConfigCovar() if cfg.get("covar") else None
     pc = cvc.pca if cvc is not None else ConfigPca() if any(cfg.get(k) for k in ("pca", "pcaCount", "pcaReport")) else None
     ac = pc.assoc if pc is not None else ConfigAssoc() if any(cfg.get(k) for k in ("pheno", "assoc", "assocReport")) else None
     sc = ac.score if ac is not None else ConfigScore() if any(cfg.get(k) for k in ("score", "scoreOutput", "scoreReport")) else None
@@ -1192,9 +1285,14 @@ def make_config(cfg=None, device=0, max_batch_bytes=0, n_format_threads=0):
         pc.pca_count = int(cfg.get("pcaCount") or PCA_DEFAULT_COMPONENTS)
         c.reserved[1] = CONFIG_MORE_PCA
     if cvc is not None:  # the covariate file of the scan
-        keep.append(str(cfg["covar"]).encode())
-        cvc.covar_path = keep[-1]
+        if cfg.get("covar"):
+            keep.append(str(cfg["covar"]).encode())
+            cvc.covar_path = keep[-1]
         c.reserved[1] = CONFIG_MORE_COVAR
+    if lgc is not None:  # the scan's model: "linear" / "logistic", or the number itself
+        m = cfg["assocModel"]
+        lgc.assoc_model = ASSOC_MODELS[m] if m in ASSOC_MODELS else int(m)
+        c.reserved[1] = CONFIG_MORE_LOGIT
     c._keep = keep
     return c
 
@@ -1760,7 +1858,7 @@ class Ctx:
                  path=0, want_dosage=False, sample_names=None, delimiter=";", packed_sites=False, render_sites=False,
                  empty_field="!", keep_pos=False, keep_id=False, keep_info=False, sample_stats=False,
                  min_gq=0, min_dp=0, sample_keep=None, pair_stats=False, site_gate=None, bed_rows=False, trios=None, ld=None,
-                 variants=None, regions=None, grm=False, score=None, pheno=None, covar=None):
+                 variants=None, regions=None, grm=False, score=None, pheno=None, covar=None, logit=None):
         p = make_params(n_header_fields, allow, exclude, device, eol_chars, eol_byte, max_batch_bytes, max_lines, max_alleles,
                         cmap_bytes, n_slots, want_class_maps, path, want_dosage, sample_names is not None, packed_sites,
                         render_sites, sample_stats, min_gq, min_dp, sample_keep)
@@ -1799,6 +1897,13 @@ class Ctx:
         if covar is not None:  # bvcf_set_covar_table: a CovarTable bound to pheno; the covariate records beside (assoc_cov())
             lib.bvcf_set_covar_table.argtypes = [C.c_void_p, C.c_void_p]
             rc = lib.bvcf_set_covar_table(self.h, C.byref(covar.t))
+            if rc:
+                msg = lib.bvcf_last_error(self.h).decode()
+                self.close()
+                raise BvcfError(rc, msg)
+        if logit is not None:  # bvcf_set_logit_table: a LogitTable built from pheno; the logistic records beside (assoc_logit())
+            lib.bvcf_set_logit_table.argtypes = [C.c_void_p, C.c_void_p]
+            rc = lib.bvcf_set_logit_table(self.h, C.byref(logit.t))
             if rc:
                 msg = lib.bvcf_last_error(self.h).decode()
                 self.close()
@@ -2175,6 +2280,24 @@ class Ctx:
             return np.zeros((0, w), dtype=np.uint64)
         raw = (C.c_uint8 * (n * w * 8)).from_address(info.words)
         return np.frombuffer(raw, dtype=np.uint64).reshape(n, w).copy()
+
+    def assoc_logit(self):
+        """bvcf_assoc_logit: the batch collected last -> its logistic records, uint64 (n_rows, row_words), copied out of the slot"""
+        info = AssocLogitInfo()
+        lib.bvcf_assoc_logit.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(lib.bvcf_assoc_logit(self.h, C.byref(info)))
+        n, w = int(info.n_rows), int(info.row_words)
+        if not n or not info.words:
+            return np.zeros((0, w), dtype=np.uint64)
+        raw = (C.c_uint8 * (n * w * 8)).from_address(info.words)
+        return np.frombuffer(raw, dtype=np.uint64).reshape(n, w).copy()
+
+    def bench_assoc_logit_kernels(self):
+        """the logistic kernels over the first slot's last bench chain -> ms of [k_assoc_logit_gemm, k_assoc_logit_sparse]"""
+        ms = (C.c_float * 2)()
+        lib.bvcf_bench_assoc_logit_kernels.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(lib.bvcf_bench_assoc_logit_kernels(self.h, ms))
+        return list(ms)
 
     def bench_assoc_cov_kernels(self):
         """the covariate kernels over the first slot's last bench chain -> ms of [k_assoc_cov_gemm, k_assoc_cov_sparse]"""

@@ -193,6 +193,17 @@ struct AssocSlot {
   DevBuf<uint32_t> ctr;
   Arena<bvcf_assoc_rec> rec;
   Arena<unsigned long long> cov;  // bvcf_set_covar_table: the covariate records [rows][cov.l.w], in words
+  Arena<unsigned long long> logit;  // bvcf_set_logit_table: the logistic records [rows][logit.l.w], in words
+};
+// bvcf_set_logit_table (bvcf_assoc_logit.hip.h): k_assoc_logit_gemm / k_assoc_logit_sparse behind the scan's own kernels.  The
+// layout, operand B, the int64 tables C, R and W and the totals row are the ctx's
+struct AssocLogitCtx {
+  bool on = false;
+  AssocLogitLayout l{};
+  DevBuf<int8_t> b;
+  DevBuf<long long> c, r, w;
+  DevBuf<unsigned long long> tot;
+  bvcf_assoc_logit_info last{};
 };
 // bvcf_set_covar_table (bvcf_assoc_cov.hip.h): k_assoc_cov_gemm / k_assoc_cov_sparse behind the scan's own kernels.  The
 // layout, operand B, the int64 table, the groups' phenotypes and the totals row are the ctx's
@@ -216,6 +227,8 @@ struct AssocCtx {
   std::vector<uint64_t> np;  // NP per phenotype: what a covariate table must be bound to
   bool cov_asked = false;
   AssocCovCtx cov;
+  bool logit_asked = false;
+  AssocLogitCtx logit;
 };
 
 }  // namespace
@@ -1537,9 +1550,11 @@ int bvcf_ld_in_ld(const uint32_t counts[6], uint32_t t6) {
 // ---- the association scan
 
 // a slot's arena holds at most 1 GiB of records
-// a row's bytes in a slot's two arenas: the phenotypes' records and -- with a covariate table -- the covariate record
+// a row's bytes in a slot's arenas: the phenotypes' records and -- with a covariate table -- the covariate record or -- with a
+// logistic table -- the logistic record
 static uint64_t assoc_row_bytes(const bvcf_ctx *c) {
-  return sizeof(bvcf_assoc_rec) * std::max<uint32_t>(c->assoc.K, 1u) + (c->assoc.cov.on ? 8ull * c->assoc.cov.l.w : 0ull);
+  return sizeof(bvcf_assoc_rec) * std::max<uint32_t>(c->assoc.K, 1u) + (c->assoc.cov.on ? 8ull * c->assoc.cov.l.w : 0ull) +
+         (c->assoc.logit.on ? 8ull * c->assoc.logit.l.w : 0ull);
 }
 static uint64_t assoc_max_rows(const bvcf_ctx *c) { return (1ull << 30) / assoc_row_bytes(c); }
 
@@ -1554,13 +1569,14 @@ static int alloc_assoc(bvcf_ctx *c, Slot &s) {
   }
   HIP_TRY(c, s.assoc.rec.grow_to(c->assoc.cap * c->assoc.K));
   if (c->assoc.cov.on) HIP_TRY(c, s.assoc.cov.grow_to(c->assoc.cap * c->assoc.cov.l.w));
+  if (c->assoc.logit.on) HIP_TRY(c, s.assoc.logit.grow_to(c->assoc.cap * c->assoc.logit.l.w));
   return BVCF_OK;
 }
 
 // the slot holds the row index and everything the scan's kernels write
 static bool assoc_ready(const bvcf_ctx *c, const Slot &s) {
   return s.assoc.rec.d && s.assoc.ctr && s.assoc.dense.size() >= c->max_alleles && s.assoc.sparse.size() >= c->max_alleles &&
-         (!c->assoc.cov.on || s.assoc.cov.d) && index_ready(c, s);
+         (!c->assoc.cov.on || s.assoc.cov.d) && (!c->assoc.logit.on || s.assoc.logit.d) && index_ready(c, s);
 }
 
 static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
@@ -1580,6 +1596,12 @@ static AssocArgs make_assoc_args(bvcf_ctx *c, Slot &s) {
     sa.cov = s.assoc.cov.d;
     sa.cov_tot = c->assoc.cov.tot;
     sa.cov_w = c->assoc.cov.l.w;
+  }
+  if (c->assoc.logit.on) {  // (likewise: assoc_rows takes the smallest capacity)
+    sa.cap_rows = std::min<unsigned long long>(sa.cap_rows, s.assoc.logit.cap / c->assoc.logit.l.w);
+    sa.logit = s.assoc.logit.d;
+    sa.logit_tot = c->assoc.logit.tot;
+    sa.logit_w = c->assoc.logit.l.w;
   }
   sa.row_cap = (uint32_t)s.idx.src.size();
   sa.list_cap = (uint32_t)s.assoc.sparse.size();  // (the second of the two lists: there when both are)
@@ -1613,6 +1635,27 @@ static void launch_assoc_cov(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, c
   hipLaunchKernelGGL(k_assoc_cov_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa, ca);
 }
 
+static AssocLogitArgs make_assoc_logit_args(bvcf_ctx *c, Slot &s) {
+  AssocLogitArgs la{};
+  la.l = c->assoc.logit.l;
+  la.b = c->assoc.logit.b;
+  la.c = c->assoc.logit.c;
+  la.r = c->assoc.logit.r;
+  la.w = c->assoc.logit.w;
+  la.out = s.assoc.logit.d;
+  return la;
+}
+
+// bvcf_set_logit_table: behind k_assoc_list's lists, the two kernels of bvcf_assoc_logit.hip.h -- the dense rows' tiles dealt
+// over blockIdx.x, the column slices over blockIdx.y
+static void launch_assoc_logit(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const AssocArgs &sa, const AssocLogitArgs &la,
+                               const Event *ev = nullptr) {
+  const uint32_t gx = std::max<uint32_t>(16u, (uint32_t)c->n_cu * 4u / la.l.n_slices);
+  hipLaunchKernelGGL(k_assoc_logit_gemm, dim3(gx, la.l.n_slices), dim3(kWgThreads), 0, st, a, sa, la);
+  mark(ev, st);
+  hipLaunchKernelGGL(k_assoc_logit_sparse, dim3(c->n_cu * 8), dim3(kWgThreads), 0, st, a, sa, la);
+}
+
 // bvcf_set_pheno_table: behind the row index, the cursors from zero and the three kernels (bvcf_assoc.hip.h; bvcf_collect
 // copies the used part of the records)
 static void launch_assoc(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, const AssocArgs &sa, const Event *ev = nullptr) {
@@ -1639,25 +1682,35 @@ static bvcf_assoc_info assoc_need(bvcf_ctx *c, const Slot &s) {
   c->assoc.last.need_rows = t.need_rows;
   c->assoc.cov.last = bvcf_assoc_cov_info{};
   c->assoc.cov.last.row_words = c->assoc.cov.l.w;
+  c->assoc.logit.last = bvcf_assoc_logit_info{};
+  c->assoc.logit.last.row_words = c->assoc.logit.l.w;
   return t;
 }
-// the batch's rows fit both arenas
+// the batch's rows fit every arena
 static bool assoc_fits(const bvcf_ctx *c, const Slot &s, const bvcf_assoc_info &t) {
-  return s.assoc.rec.fits(t.need_rows * t.n_columns) && (!c->assoc.cov.on || s.assoc.cov.fits(t.need_rows * c->assoc.cov.l.w));
+  return s.assoc.rec.fits(t.need_rows * t.n_columns) && (!c->assoc.cov.on || s.assoc.cov.fits(t.need_rows * c->assoc.cov.l.w)) &&
+         (!c->assoc.logit.on || s.assoc.logit.fits(t.need_rows * c->assoc.logit.l.w));
 }
 static int assoc_copy(bvcf_ctx *c, Slot &s, const bvcf_assoc_info &t) {
   if (t.n_rows)
     HIP_TRY(c, hipMemcpyAsync(s.assoc.rec.h, s.assoc.rec.d, t.n_rows * t.n_columns * sizeof(bvcf_assoc_rec), hipMemcpyDeviceToHost, s.stream));
   if (t.n_rows && c->assoc.cov.on)
     HIP_TRY(c, hipMemcpyAsync(s.assoc.cov.h, s.assoc.cov.d, t.n_rows * c->assoc.cov.l.w * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
+  if (t.n_rows && c->assoc.logit.on)
+    HIP_TRY(c, hipMemcpyAsync(s.assoc.logit.h, s.assoc.logit.d, t.n_rows * c->assoc.logit.l.w * sizeof(unsigned long long), hipMemcpyDeviceToHost, s.stream));
   return BVCF_OK;
 }
-// published with the records: the covariate records of the same batch
+// published with the records: the covariate / logistic records of the same batch
 static void assoc_publish(bvcf_ctx *c, const Slot &s, const bvcf_assoc_info &t) {
   c->assoc.last = t;
-  if (!c->assoc.cov.on) return;
-  c->assoc.cov.last.words = reinterpret_cast<const uint64_t *>(s.assoc.cov.h.get());
-  c->assoc.cov.last.n_rows = t.n_rows;
+  if (c->assoc.cov.on) {
+    c->assoc.cov.last.words = reinterpret_cast<const uint64_t *>(s.assoc.cov.h.get());
+    c->assoc.cov.last.n_rows = t.n_rows;
+  }
+  if (c->assoc.logit.on) {
+    c->assoc.logit.last.words = reinterpret_cast<const uint64_t *>(s.assoc.logit.h.get());
+    c->assoc.logit.last.n_rows = t.n_rows;
+  }
 }
 
 void bvcf_pheno_table_free(bvcf_pheno_table *t) {
@@ -1837,8 +1890,10 @@ int bvcf_reserve_assoc_rows(bvcf_ctx *c, uint64_t rows) {
   if (!c) return BVCF_E_ARG;
   if (c->assoc.on && !c->in_flight && rows > assoc_max_rows(c)) {
     c->err = "bvcf_reserve_assoc_rows: " + std::to_string(rows) + " rows x " + std::to_string(c->assoc.K) + " columns" +
-             (c->assoc.cov.on ? " and " + std::to_string(c->assoc.cov.l.J) + " covariates" : std::string()) +
-             ": a slot's records would pass 1 GiB: use fewer columns" + (c->assoc.cov.on ? ", fewer covariates" : "") +
+             (c->assoc.cov.on     ? " and " + std::to_string(c->assoc.cov.l.J) + " covariates"
+              : c->assoc.logit.on ? " and " + std::to_string(c->assoc.logit.l.J) + " covariates (logistic)"
+                                  : std::string()) +
+             ": a slot's records would pass 1 GiB: use fewer columns" + (c->assoc.cov.on || c->assoc.logit.on ? ", fewer covariates" : "") +
              " or smaller batches (max_batch_bytes)";
     return BVCF_E_TOO_BIG;
   }
@@ -2097,8 +2152,8 @@ int bvcf_set_covar_table(bvcf_ctx *c, const bvcf_covar_table *t) {
     c->err = "bvcf_set_covar_table: bvcf_set_pheno_table was not called on the ctx";
     return BVCF_E_ARG;
   }
-  if (c->assoc.cov_asked) {
-    c->err = "bvcf_set_covar_table: the ctx has a covariate table";
+  if (c->assoc.cov_asked || c->assoc.logit_asked) {
+    c->err = c->assoc.cov_asked ? "bvcf_set_covar_table: the ctx has a covariate table" : "bvcf_set_covar_table: the ctx has a logistic table";
     return BVCF_E_ARG;
   }
   bool same = t->n_samples == c->n_samples && t->n_columns == c->assoc.K;
@@ -2181,6 +2236,284 @@ int bvcf_bench_assoc_cov_kernels(bvcf_ctx *c, float ms[2]) {
   return BVCF_OK;
 }
 
+// ---- the scan's logistic model
+
+void bvcf_logit_table_free(bvcf_logit_table *t) {
+  if (!t) return;
+  for (const void *p : {(const void *)t->b, (const void *)t->c, (const void *)t->m, (const void *)t->r, (const void *)t->w,
+                        (const void *)t->fitted, (const void *)t->rounds, (const void *)t->beta, (const void *)t->pheno_np,
+                        (const void *)t->totals})
+    free(const_cast<void *>(p));
+  memset(t, 0, sizeof *t);
+}
+
+int bvcf_logit_table_build(const bvcf_pheno_table *pheno, const bvcf_covar_table *covar, bvcf_logit_table *out, char *err, size_t err_cap) {
+  if (!out) return BVCF_E_ARG;
+  memset(out, 0, sizeof *out);
+  const auto fail = [&](const std::string &what, int rc) {
+    if (err && err_cap) snprintf(err, err_cap, "%s", what.c_str());
+    return rc;
+  };
+  if (!pheno_table_sound(pheno)) return fail("want a phenotype table as bvcf_pheno_table_build makes it", BVCF_E_ARG);
+  const uint32_t K = pheno->n_columns, s = pheno->n_samples, s64 = (s + 63u) & ~63u;
+  const uint32_t J = covar ? covar->n_covars : 0u, j1 = J + 1u;
+  if (covar && (J < 1 || J > BVCF_COVAR_MAX || covar->n_samples != s || (s && (!covar->c || !covar->complete))))
+    return fail("the covariate table is not one of the phenotype table's samples", BVCF_E_ARG);
+  std::vector<std::string_view> names;
+  for (const char *nm = pheno->names, *e = nm + pheno->names_bytes; nm && nm < e; nm += strlen(nm) + 1) names.emplace_back(nm);
+  for (uint32_t k = 0; k < K && covar; k++)
+    for (uint32_t i = 0; i < s; i++)
+      if (pheno->present[(size_t)k * s + i] && !covar->complete[i])
+        return fail("a phenotype on a sample without covariates: the table is not the masked one", BVCF_E_ARG);
+  uint32_t bad_k, bad_i;
+  if (assoc_logit_first_non_binary(pheno->y, pheno->present, K, s, &bad_k, &bad_i))
+    return fail("the phenotype " + (bad_k < names.size() ? std::string(names[bad_k]) : std::to_string(bad_k + 1)) + " is not 0 or 1 on sample " +
+                    std::to_string(bad_i + 1) + " (column " + std::to_string(bad_i + 1) + " of the kept samples): the logistic model wants 0 / 1",
+                BVCF_E_ARG);
+  int64_t *cc = (int64_t *)calloc((size_t)J * s + 1, sizeof(int64_t));
+  int64_t *mm = (int64_t *)calloc((size_t)K * s + 1, sizeof(int64_t)), *rr = (int64_t *)calloc((size_t)K * s + 1, sizeof(int64_t));
+  int64_t *ww = (int64_t *)calloc((size_t)K * s + 1, sizeof(int64_t));
+  uint8_t *fitted = (uint8_t *)calloc(K + 1, 1);
+  uint32_t *rounds = (uint32_t *)calloc(K + 1, sizeof(uint32_t));
+  double *beta = (double *)calloc((size_t)K * j1 + 1, sizeof(double));
+  uint64_t *np = (uint64_t *)calloc(K + 1, sizeof(uint64_t));
+  int8_t *b = nullptr;
+  uint64_t *tot = nullptr;
+  const auto release = [&] {
+    for (void *p : {(void *)cc, (void *)mm, (void *)rr, (void *)ww, (void *)fitted, (void *)rounds, (void *)beta, (void *)np, (void *)b, (void *)tot}) free(p);
+  };
+  if (!cc || !mm || !rr || !ww || !fitted || !rounds || !beta || !np) {
+    release();
+    return fail("no memory", BVCF_E_NOMEM);
+  }
+  for (uint32_t q = 0; q < J; q++)
+    for (uint32_t i = 0; i < s; i++)
+      if (covar->complete[i]) cc[(size_t)q * s + i] = covar->c[(size_t)q * s + i];
+  // the fits, and what they leave in fixed point
+  uint32_t n_unfitted = 0;
+  std::vector<double> x, y;
+  std::vector<uint32_t> omega;
+  for (uint32_t k = 0; k < K; k++) {
+    np[k] = pheno->totals[k].np;
+    omega.clear(), x.clear(), y.clear();
+    for (uint32_t i = 0; i < s; i++) {
+      if (!pheno->present[(size_t)k * s + i]) continue;
+      omega.push_back(i);
+      x.push_back(1.0);
+      for (uint32_t q = 0; q < J; q++) x.push_back((double)cc[(size_t)q * s + i] / 1e6);
+      y.push_back(pheno->y[(size_t)k * s + i] ? 1.0 : 0.0);
+    }
+    fitted[k] = (uint8_t)assoc_logit_fit(J, omega.size(), x.data(), y.data(), beta + (size_t)k * j1, rounds + k);
+    if (!fitted[k]) {
+      n_unfitted++;
+      continue;
+    }
+    for (size_t o = 0; o < omega.size(); o++) {
+      const size_t at = (size_t)k * s + omega[o];
+      mm[at] = assoc_logit_m(assoc_logit_mu(beta + (size_t)k * j1, x.data() + (size_t)j1 * o, J));
+      rr[at] = (y[o] != 0.0 ? BVCF_LOGIT_ONE : 0) - mm[at];
+      ww[at] = assoc_logit_w(mm[at]);
+    }
+  }
+  // the limb counts: the smallest that hold the values a column can get
+  uint32_t lwc = 1, lr = 1, lrc = 1, lwcc = 1;
+  int8_t lim[16];
+  uint64_t lo, hi;
+  const auto cval = [&](uint32_t a, uint32_t i) -> int64_t { return a ? cc[(size_t)(a - 1u) * s + i] : 1; };
+  for (uint32_t k = 0; k < K; k++)
+    for (uint32_t i = 0; i < s; i++) {
+      const int64_t w = ww[(size_t)k * s + i], r = rr[(size_t)k * s + i];
+      if (!pheno->present[(size_t)k * s + i]) continue;
+      lr = std::max(lr, (uint32_t)exact_limbs(r, lim, 16));
+      for (uint32_t a = 0; a <= J; a++) {
+        const int64_t wc = w * cval(a, i);  // (below 2^63 in size)
+        lwc = std::max(lwc, (uint32_t)exact_limbs(wc, lim, 16));
+        exact_mul128(r, cval(a, i), &lo, &hi);
+        lrc = std::max(lrc, (uint32_t)exact_limbs128(lo, hi, lim, 16));
+        for (uint32_t bb = std::max(a, 1u); bb <= J && a; bb++) {
+          exact_mul128(wc, cval(bb, i), &lo, &hi);
+          lwcc = std::max(lwcc, (uint32_t)exact_limbs128(lo, hi, lim, 16));
+        }
+      }
+    }
+  const AssocLogitLayout l = assoc_logit_layout(J, K, lwc, lr, lrc, lwcc);
+  const size_t n_b = (size_t)16u * l.n_blocks * s64;
+  b = (int8_t *)calloc(n_b + 1, 1);
+  tot = (uint64_t *)calloc((size_t)l.w + 1, sizeof(uint64_t));
+  if (!b || !tot) {
+    release();
+    return fail("no memory", BVCF_E_NOMEM);
+  }
+  const auto put = [&](uint32_t col, uint32_t limbs, uint32_t i) {
+    for (uint32_t q = 0; q < limbs; q++) b[(size_t)(col + q) * s64 + i] = lim[q];
+  };
+  const uint32_t first_r = l.bwc, first_rc = l.bwc + l.br, first_wcc = l.bwc + l.br + l.brc;
+  for (uint32_t k = 0; k < K; k++)
+    for (uint32_t i = 0; i < s; i++) {
+      if (!pheno->present[(size_t)k * s + i]) continue;
+      const int64_t w = ww[(size_t)k * s + i], r = rr[(size_t)k * s + i];
+      exact_limbs(r, lim, 16);
+      put(assoc_cov_column(first_r, l.vr, lr, k), lr, i);  // (R over all of Omega has no place in the totals row: het / hom alone)
+      for (uint32_t a = 0; a <= J; a++) {
+        const uint32_t v = k * j1 + a;
+        const int64_t wc = w * cval(a, i);
+        exact_limbs(wc, lim, 16);
+        put(assoc_cov_column(0, l.vwc, lwc, v), lwc, i);
+        uint64_t *t = tot + assoc_logit_word_wc(l, v, 2);
+        exact_add128s(t, t + 1, wc, 0u);
+        exact_mul128(r, cval(a, i), &lo, &hi);
+        exact_limbs128(lo, hi, lim, 16);
+        put(assoc_cov_column(first_rc, l.vrc, lrc, v), lrc, i);
+        t = tot + assoc_logit_word_rc(l, v);
+        exact_add128(t, t + 1, lo, hi);
+        for (uint32_t bb = std::max(a, 1u); bb <= J && a; bb++) {
+          const uint32_t vv = k * l.np2 + (bb - 1u) * bb / 2u + (a - 1u);
+          exact_mul128(wc, cval(bb, i), &lo, &hi);
+          exact_limbs128(lo, hi, lim, 16);
+          put(assoc_cov_column(first_wcc, l.vwcc, lwcc, vv), lwcc, i);
+          t = tot + assoc_logit_word_wcc(l, vv);
+          exact_add128(t, t + 1, lo, hi);
+        }
+      }
+    }
+  out->n_covars = J;
+  out->n_samples = s;
+  out->s64 = s64;
+  out->n_columns = K;
+  out->lwc = lwc, out->lr = lr, out->lrc = lrc, out->lwcc = lwcc;
+  out->n_blocks = l.n_blocks;
+  out->row_words = l.w;
+  out->n_unfitted = n_unfitted;
+  out->b = b;
+  out->c = cc;
+  out->m = mm, out->r = rr, out->w = ww;
+  out->fitted = fitted;
+  out->rounds = rounds;
+  out->beta = beta;
+  out->pheno_np = np;
+  out->totals = tot;
+  return BVCF_OK;
+}
+
+// the table is one bvcf_logit_table_build made: its counts agree with one another
+static bool logit_table_sound(const bvcf_logit_table *t) {
+  if (!t || t->n_covars > BVCF_COVAR_MAX || t->n_columns < 1 || t->n_columns > BVCF_ASSOC_MAX_COLUMNS || t->n_samples > BVCF_ASSOC_MAX_SAMPLES ||
+      t->s64 != ((t->n_samples + 63u) & ~63u) || t->lwc < 1 || t->lwc > BVCF_LOGIT_MAX_LIMBS || t->lr < 1 || t->lr > BVCF_LOGIT_MAX_LIMBS ||
+      t->lrc < 1 || t->lrc > BVCF_LOGIT_MAX_LIMBS || t->lwcc < 1 || t->lwcc > BVCF_LOGIT_MAX_LIMBS || !t->b || !t->c || !t->m || !t->r || !t->w ||
+      !t->fitted || !t->pheno_np || !t->totals)
+    return false;
+  const AssocLogitLayout l = assoc_logit_layout(t->n_covars, t->n_columns, t->lwc, t->lr, t->lrc, t->lwcc);
+  return t->n_blocks == l.n_blocks && t->row_words == l.w;
+}
+
+int bvcf_set_logit_table(bvcf_ctx *c, const bvcf_logit_table *t) {
+  if (!c) return BVCF_E_ARG;
+  if (!logit_table_sound(t)) {
+    c->err = "bvcf_set_logit_table: want a table as bvcf_logit_table_build makes it";
+    return BVCF_E_ARG;
+  }
+  if (const int rc = refuse_in_flight(c, "bvcf_set_logit_table")) return rc;
+  if (!c->assoc.asked) {
+    c->err = "bvcf_set_logit_table: bvcf_set_pheno_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  if (c->assoc.cov_asked || c->assoc.logit_asked) {
+    c->err = c->assoc.cov_asked ? "bvcf_set_logit_table: the ctx has a covariate table (the logistic table holds the covariates)"
+                                : "bvcf_set_logit_table: the ctx has a logistic table";
+    return BVCF_E_ARG;
+  }
+  bool same = t->n_samples == c->n_samples && t->n_columns == c->assoc.K;
+  for (uint32_t k = 0; same && k < t->n_columns; k++) same = t->pheno_np[k] == c->assoc.np[k];
+  if (!same) {
+    c->err = "bvcf_set_logit_table: the table was not built from the ctx's phenotype table (samples, columns or NP differ)";
+    return BVCF_E_ARG;
+  }
+  const AssocLogitLayout l = assoc_logit_layout(t->n_covars, t->n_columns, t->lwc, t->lr, t->lrc, t->lwcc);
+  const uint64_t row_bytes = sizeof(bvcf_assoc_rec) * c->assoc.K + 8ull * l.w;
+  if (c->assoc.on && c->assoc.cap * row_bytes > (1ull << 30)) {
+    c->err = "bvcf_set_logit_table: " + std::to_string(c->assoc.cap) + " rows x " + std::to_string(c->assoc.K) + " columns and " +
+             std::to_string(l.J) + " covariates: a slot's records would take " + std::to_string(c->assoc.cap * row_bytes) +
+             " bytes, more than 1 GiB: use fewer columns, fewer covariates or smaller batches (max_batch_bytes)";
+    return BVCF_E_TOO_BIG;
+  }
+  // (asked, the layout and on are set behind the uploads: a call that fails midway leaves a ctx that can be asked again)
+  const auto asked = [&] {
+    c->assoc.logit_asked = true;
+    c->assoc.logit.l = l;
+    c->assoc.logit.last = bvcf_assoc_logit_info{};
+    c->assoc.logit.last.row_words = l.w;
+  };
+  if (!c->assoc.on) {  // (no sample columns: no rows, nothing allocated or launched)
+    asked();
+    return BVCF_OK;
+  }
+  HIP_TRY(c, hipSetDevice(c->device));
+  const size_t b_bytes = (size_t)16u * l.n_blocks * t->s64, ns = c->n_samples, kn = (size_t)l.K * ns;
+  HIP_TRY(c, c->assoc.logit.b.alloc(b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemset(c->assoc.logit.b, 0, b_bytes + BVCF_DEVICE_PAD));
+  HIP_TRY(c, hipMemcpy(c->assoc.logit.b, t->b, b_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.logit.c.alloc((size_t)l.J * ns + 1));
+  if (l.J) HIP_TRY(c, hipMemcpy(c->assoc.logit.c, t->c, (size_t)l.J * ns * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.logit.r.alloc(kn));
+  HIP_TRY(c, hipMemcpy(c->assoc.logit.r, t->r, kn * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.logit.w.alloc(kn));
+  HIP_TRY(c, hipMemcpy(c->assoc.logit.w, t->w, kn * sizeof(long long), hipMemcpyHostToDevice));
+  HIP_TRY(c, c->assoc.logit.tot.alloc(l.w));
+  HIP_TRY(c, hipMemcpy(c->assoc.logit.tot, t->totals, (size_t)l.w * sizeof(unsigned long long), hipMemcpyHostToDevice));
+  asked();
+  c->assoc.logit.on = true;
+  for (auto &s : c->slots)
+    if (const int rc = alloc_assoc(c, s)) {  // (a slot's arena did not grow: the table is off again)
+      c->assoc.logit.on = c->assoc.logit_asked = false;
+      return rc;
+    }
+  return BVCF_OK;
+}
+
+int bvcf_assoc_logit(bvcf_ctx *c, bvcf_assoc_logit_info *out) {
+  if (!c || !out) return BVCF_E_ARG;
+  if (!c->assoc.logit_asked) {
+    c->err = "bvcf_assoc_logit: bvcf_set_logit_table was not called on the ctx";
+    return BVCF_E_ARG;
+  }
+  *out = c->assoc.logit.last;
+  return BVCF_OK;
+}
+
+int bvcf_assoc_logit_stat(const bvcf_logit_table *t, uint32_t k, const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals,
+                          const uint64_t *logit_row, double out[6]) {
+  if (!rec || !totals || !logit_row || !out || !logit_table_sound(t) || k >= t->n_columns) return -1;
+  const AssocLogitLayout l = assoc_logit_layout(t->n_covars, t->n_columns, t->lwc, t->lr, t->lrc, t->lwcc);
+  AssocLogitGram q;
+  assoc_logit_gram(l, k, t->fitted[k], assoc_sums_of(rec, totals), logit_row, t->totals, &q);
+  return assoc_logit_stat(q, out);
+}
+
+// (as bvcf_bench_assoc_cov_kernels: ms = {k_assoc_logit_gemm, k_assoc_logit_sparse})
+int bvcf_bench_assoc_logit_kernels(bvcf_ctx *c, float ms[2]) {
+  if (!c || !ms) return BVCF_E_ARG;
+  Slot &s = c->slots[0];
+  Event ev[3];
+  if (const int rc = start_hook(c, "bvcf_bench_assoc_logit_kernels", c->assoc.on && c->assoc.logit.on && assoc_ready(c, s) && c->bench_src,
+                                "the ctx has no logistic table, or no bvcf_bench_device* call went before", ev))
+    return rc;
+  const KernelArgs a = make_args(c, s, static_cast<const uint8_t *>(c->bench_src), c->bench_nbytes);
+  launch_row_index(c, a, s.stream, make_bed_args(c, s));
+  const AssocArgs sa = make_assoc_args(c, s);
+  launch_assoc(c, a, s.stream, sa);
+  HIP_TRY(c, hipEventRecord(ev[0], s.stream));
+  launch_assoc_logit(c, a, s.stream, sa, make_assoc_logit_args(c, s), ev + 1);
+  HIP_TRY(c, hipEventRecord(ev[2], s.stream));
+  if (const int rc = finish_hook(c, ev, s.stream, ms)) return rc;
+  HIP_TRY(c, s.bed.rows.copy_total(s.stream));
+  HIP_TRY(c, hipStreamSynchronize(s.stream));
+  if (*s.bed.rows.h_total > sa.cap_rows) {
+    c->err = "bvcf_bench_assoc_logit_kernels: the rows outrun the arena (bvcf_reserve_assoc_rows): " + std::to_string(*s.bed.rows.h_total) + " rows";
+    return BVCF_E_CAPACITY;
+  }
+  return BVCF_OK;
+}
+
 // (k_assoc_list reads the row index of the slot's last chain: the hook builds it once more first)
 int bvcf_bench_assoc_kernels(bvcf_ctx *c, float ms[3]) {
   if (!c || !ms) return BVCF_E_ARG;
@@ -2218,6 +2551,7 @@ static void launch_rows(bvcf_ctx *c, const KernelArgs &a, hipStream_t st, Slot *
   launch_row_index(c, a, st, ba);
   if (assoc) launch_assoc(c, a, st, make_assoc_args(c, *slot));
   if (assoc && c->assoc.cov.on) launch_assoc_cov(c, a, st, make_assoc_args(c, *slot), make_assoc_cov_args(c, *slot));
+  if (assoc && c->assoc.logit.on) launch_assoc_logit(c, a, st, make_assoc_args(c, *slot), make_assoc_logit_args(c, *slot));
   if (bed) launch_bed_rows(c, a, st, ba);
   if (ld) launch_ld_kernels(c, a, st, ba, make_ld_args(c, *slot));
   if (trios) (void)launch_trio_kernels(c, a, st, ba, make_trio_args(c, *slot));  // (a failed memset shows at the stream's next call)

@@ -73,6 +73,10 @@ struct AssocArgs {
   unsigned long long *cov;
   const unsigned long long *cov_tot;
   uint32_t cov_w;
+  // bvcf_set_logit_table (bvcf_assoc_logit.hip.h): likewise the rows' logistic records [cap_rows][logit_w] and their totals row
+  unsigned long long *logit;
+  const unsigned long long *logit_tot;
+  uint32_t logit_w;
 };
 
 // the batch's rows, or 0 when they outrun the arena: nothing is written then
@@ -106,6 +110,7 @@ __global__ __launch_bounds__(kWgThreads) void k_assoc_list(AssocArgs sa) {
         }
         // (and its covariate record: the missing-class sums are the totals, het / hom are zero -- the totals row)
         for (uint32_t q = 0; q < sa.cov_w; q++) sa.cov[(size_t)r * sa.cov_w + q] = sa.cov_tot[q];
+        for (uint32_t q = 0; q < sa.logit_w; q++) sa.logit[(size_t)r * sa.logit_w + q] = sa.logit_tot[q];
       } else {
         sparse = src.y != 0u;
         dense = !sparse;

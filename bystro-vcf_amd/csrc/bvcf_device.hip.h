@@ -71,6 +71,9 @@
 //   (bvcf_set_covar_table, behind those: k_assoc_cov_gemm multiplies the same classes with the int8 limbs of the covariates and
 //    of their products, the column blocks dealt to workgroups as (tile, slice), k_assoc_cov_sparse does the short lists per
 //    (list, family) -- the exact Gram sums behind --covar, bvcf_assoc_cov.hip.h)
+//   (bvcf_set_logit_table, in their place: k_assoc_logit_gemm multiplies the classes with the int8 limbs of W C, R, R C and
+//    W C C of a null model fitted on the host, an accumulator per (block, class), k_assoc_logit_sparse does the short lists per
+//    (list, phenotype, family) -- the exact 128-bit sums behind --assocModel logistic, bvcf_assoc_logit.hip.h)
 //   (bvcf_pca_eigen, outside every chain and without a ctx: k_pca_expand, then per step k_pca_house / k_pca_symv / k_pca_w /
 //    k_pca_rank2 -- Householder tridiagonalisation of the relationship matrix in double --, and k_pca_back, the reflectors applied
 //    to the eigenvectors the host found for the tridiagonal matrix -- the solver behind --pca, bvcf_pca.hip.h)
@@ -146,6 +149,7 @@
 #include "bvcf_score.hip.h"
 #include "bvcf_assoc.hip.h"
 #include "bvcf_assoc_cov.hip.h"
+#include "bvcf_assoc_logit.hip.h"
 #include "bvcf_bedrows.hip.h"
 #include "bvcf_mendel.hip.h"
 #include "bvcf_ld.hip.h"

@@ -514,6 +514,10 @@ void Driver::device_main(DevWorker *W) {
       fail(std::string("bvcf_assoc_cov: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
       return;
     }
+    if (R_.logit_on && bvcf_assoc_logit(W->ctx, &j.assoc_logit) != BVCF_OK) {  // --assocModel logistic: likewise
+      fail(std::string("bvcf_assoc_logit: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      return;
+    }
     j.job = n_jobs;
     outstanding.emplace_back(n_jobs, n_collects - 1);
     n_jobs++;
@@ -634,7 +638,8 @@ void Driver::formatter_main(DevWorker *W) {
             fail("ld: the device's events do not match the batch's rows", BVCF_E_FATAL);
           }
           if (assoc && !assoc_failed_.load()) {
-            if (const int arc = append_assoc(R_, &keep->res, text, keep->assoc, R_.covar_on ? &keep->assoc_cov : nullptr)) {
+            if (const int arc = append_assoc(R_, &keep->res, text, keep->assoc, R_.covar_on ? &keep->assoc_cov : nullptr,
+                                               R_.logit_on ? &keep->assoc_logit : nullptr)) {
               assoc_failed_.store(true);
               fail(arc == BVCF_E_IO ? "assoc: write failed" : "assoc: the device's rows do not match the batch's rows", BVCF_E_FATAL);
             }

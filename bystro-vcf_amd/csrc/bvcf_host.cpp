@@ -98,6 +98,12 @@ void bvcf_config_covar_defaults(bvcf_config_covar *c) {
   c->pca.assoc.score.grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_COVAR;
 }
 
+void bvcf_config_logit_defaults(bvcf_config_logit *c) {
+  memset(c, 0, sizeof *c);
+  bvcf_config_covar_defaults(&c->covar);
+  c->covar.pca.assoc.score.grm.regions.variants.ld.trios.more.base.reserved[1] = BVCF_CONFIG_MORE_LOGIT;
+}
+
 // A(i,j) = T(i,j) / (2^28 N(i,j)) with N(i,j) = N - miss_i - miss_j + MM(i,j), miss_i = MM(i,i): the correctly rounded double of
 // the integer T (what the conversion of a 128-bit integer gives) over the double 2^28 N(i,j) (exact), rounded to float32; 0
 // when no row has both samples called.  The diagonal by the same formula: PLINK's convention
@@ -303,9 +309,11 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
       if (R.assoc_on) {  // --pheno / --assoc: the batch's records, a line per (row, phenotype)
         bvcf_assoc_info ai;
         bvcf_assoc_cov_info ci;
-        const int arc = bvcf_assoc(R.ctx, &ai) != BVCF_OK || (R.covar_on && bvcf_assoc_cov(R.ctx, &ci) != BVCF_OK)
+        bvcf_assoc_logit_info li;
+        const int arc = bvcf_assoc(R.ctx, &ai) != BVCF_OK || (R.covar_on && bvcf_assoc_cov(R.ctx, &ci) != BVCF_OK) ||
+                                (R.logit_on && bvcf_assoc_logit(R.ctx, &li) != BVCF_OK)
                             ? BVCF_E_FATAL
-                            : append_assoc(R, &res, vcf + pos, ai, R.covar_on ? &ci : nullptr);
+                            : append_assoc(R, &res, vcf + pos, ai, R.covar_on ? &ci : nullptr, R.logit_on ? &li : nullptr);
         if (arc) {
           l.append(arc == BVCF_E_IO ? "assoc: write failed\n" : "assoc: the device's rows do not match the batch's rows\n");
           rc = BVCF_E_FATAL;

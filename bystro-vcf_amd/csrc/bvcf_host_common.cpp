@@ -883,6 +883,14 @@ int create_ctx(const Run &R, int device, bvcf_ctx **ctx, std::string *msg) {
       *ctx = nullptr;
     }
   }
+  if (rc == BVCF_OK && R.logit_on) {  // --assocModel logistic: the logistic table built from that one, and its arena
+    rc = bvcf_set_logit_table(*ctx, &R.logit_table);
+    if (rc) {
+      *msg = std::string("bvcf_set_logit_table: ") + bvcf_last_error(*ctx);
+      bvcf_destroy(*ctx);
+      *ctx = nullptr;
+    }
+  }
   if (rc == BVCF_OK && wants_plink(R.cfg)) {  // --plinkOutput: the .bed rows of every ctx of the run
     rc = bvcf_enable_bed_rows(*ctx);
     if (rc) {
@@ -1967,6 +1975,10 @@ int open_assoc(Run &R, std::string *msg) {
     *msg = "covar_path without pheno_path and assoc_path";
     return BVCF_E_ARG;
   }
+  if (assoc_model(R.cfg) != BVCF_ASSOC_MODEL_LINEAR && (!have_p || assoc_model(R.cfg) != BVCF_ASSOC_MODEL_LOGISTIC)) {
+    *msg = have_p ? "assoc_model is neither linear nor logistic" : "assoc_model without pheno_path and assoc_path";
+    return BVCF_E_ARG;
+  }
   if (!have_p) return BVCF_OK;
   for (const auto &f : {std::pair<int *, const char *>{&R.assoc_fd, op}, std::pair<int *, const char *>{&R.assoc_report_fd, have_r ? rp : nullptr}}) {
     if (!f.second) continue;
@@ -1977,7 +1989,9 @@ int open_assoc(Run &R, std::string *msg) {
     }
   }
   R.assoc_on = true;
-  R.covar_on = covar_path(R.cfg) != nullptr;
+  R.logit_on = assoc_model(R.cfg) == BVCF_ASSOC_MODEL_LOGISTIC;
+  R.logit_covar = R.logit_on && covar_path(R.cfg) != nullptr;
+  R.covar_on = covar_path(R.cfg) != nullptr && !R.logit_on;
   return BVCF_OK;
 }
 
@@ -2038,7 +2052,7 @@ int load_pheno(Run &R, std::string *msg) {
     *msg = std::string("pheno: ") + path + ": " + err;
     return BVCF_E_FATAL;
   }
-  if (R.covar_on) {
+  if (R.covar_on || R.logit_covar) {
     // --covar: the covariates of the same names; the phenotypes of the incomplete samples go; the table bound to what is left
     const char *cpath = covar_path(R.cfg);
     std::string ctext;
@@ -2051,7 +2065,10 @@ int load_pheno(Run &R, std::string *msg) {
     bvcf_pheno_table masked{};
     int rc = bvcf_pheno_table_mask(&R.pheno_table, raw.complete, &masked);
     bvcf_covar_table_free(&R.covar_table);
-    if (!rc) rc = bvcf_covar_table_build(raw.c, raw.complete, raw.n_covars, (uint32_t)ns, raw.names, raw.names_bytes, raw.n_named, &masked, &R.covar_table);
+    // (--assocModel logistic keeps the table unbound: no mask groups, no operand B of --covar's)
+    if (!rc)
+      rc = bvcf_covar_table_build(raw.c, raw.complete, raw.n_covars, (uint32_t)ns, raw.names, raw.names_bytes, raw.n_named,
+                                  R.logit_on ? nullptr : &masked, &R.covar_table);
     bvcf_covar_table_free(&raw);
     if (rc) {
       bvcf_pheno_table_free(&masked);
@@ -2062,6 +2079,25 @@ int load_pheno(Run &R, std::string *msg) {
     R.pheno_table = masked;
     R.assoc_collinear = 0;
   }
+  if (R.logit_on) {
+    // --assocModel logistic: every present value 0 or 1; then the null fits, the fixed-point vectors and operand B
+    const bvcf_pheno_table &pt = R.pheno_table;
+    uint32_t bad_k, bad_i;
+    if (assoc_logit_first_non_binary(pt.y, pt.present, pt.n_columns, (uint32_t)ns, &bad_k, &bad_i)) {
+      const char *nm = pt.names;
+      for (uint32_t k = 0; k < bad_k; k++) nm += strlen(nm) + 1;
+      *msg = std::string("pheno: ") + path + ": the phenotype " + nm + " of the sample " + std::string(names[bad_i], lens[bad_i]) +
+             " is neither 0 nor 1: --assocModel logistic wants a 0/1 trait";
+      return BVCF_E_FATAL;
+    }
+    bvcf_logit_table_free(&R.logit_table);
+    const int rc = bvcf_logit_table_build(&R.pheno_table, R.logit_covar ? &R.covar_table : nullptr, &R.logit_table, err, sizeof err);
+    if (rc) {
+      *msg = std::string("assocModel: ") + err;
+      return BVCF_E_FATAL;
+    }
+    R.assoc_collinear = 0;
+  }
   static const char kHead[] = "chrom\tpos\tref\talt\tpheno\tn\taltFreq\tbeta\tse\tchisq\tp\n";
   R.assoc_buf.assign(kHead, sizeof kHead - 1);
   R.assoc_rows = R.assoc_tested = 0;
@@ -2069,11 +2105,13 @@ int load_pheno(Run &R, std::string *msg) {
 }
 
 // a line per (row, phenotype): the rows bvcf_assoc numbers are the rows this loop visits, in this order, as for append_plink
-int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai, const bvcf_assoc_cov_info *ci) {
+int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai, const bvcf_assoc_cov_info *ci,
+                 const bvcf_assoc_logit_info *lg) {
   if (R.assoc_fd < 0 || !r->n_samples) return BVCF_OK;
   const uint32_t K = R.pheno_table.n_columns;
   if (ai.n_columns != K || (ai.n_rows && !ai.recs)) return BVCF_E_FATAL;
   if (R.covar_on && (!ci || ci->n_rows != ai.n_rows || ci->row_words != R.covar_table.row_words || (ci->n_rows && !ci->words))) return BVCF_E_FATAL;
+  if (R.logit_on && (!lg || lg->n_rows != ai.n_rows || lg->row_words != R.logit_table.row_words || (lg->n_rows && !lg->words))) return BVCF_E_FATAL;
   const char *empty = or_default(R.cfg->empty_field, "!");
   std::vector<std::string_view> names;
   for (const char *nm = R.pheno_table.names, *e = nm + R.pheno_table.names_bytes; nm < e; nm += strlen(nm) + 1) names.emplace_back(nm);
@@ -2100,7 +2138,9 @@ int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_
       append_locus(locus, L, A, row, '\t', at);
       for (uint32_t c = 0; c < K; c++) {
         double st[6];
-        const int have = R.covar_on ? bvcf_assoc_cov_stat(&R.covar_table, c, ai.recs + n_rows * K + c, R.pheno_table.totals + c,
+        const int have = R.logit_on ? bvcf_assoc_logit_stat(&R.logit_table, c, ai.recs + n_rows * K + c, R.pheno_table.totals + c,
+                                                            lg->words + n_rows * lg->row_words, st)
+                         : R.covar_on ? bvcf_assoc_cov_stat(&R.covar_table, c, ai.recs + n_rows * K + c, R.pheno_table.totals + c,
                                                           ci->words + n_rows * ci->row_words, st)
                                     : bvcf_assoc_stat(ai.recs + n_rows * K + c, R.pheno_table.totals + c, st);
         if (have < 0) return BVCF_E_FATAL;
@@ -2145,9 +2185,10 @@ int close_assoc(Run &R, bool ok, std::string *msg) {
     if (!bad && R.assoc_report_fd >= 0) {
       std::string rep = "columns\t" + std::to_string(R.pheno_table.n_columns) + "\nsamples\t" + std::to_string(R.pheno_table.n_named) +
                         "\nrows\t" + std::to_string(R.assoc_rows) + "\ntested\t" + std::to_string(R.assoc_tested) + "\n";
-      if (R.covar_on)
+      if (R.covar_on || R.logit_on)
         rep += "covariates\t" + std::to_string(R.covar_table.n_covars) + "\nincomplete\t" + std::to_string(R.covar_table.n_incomplete) +
                "\ncollinear\t" + std::to_string(R.assoc_collinear) + "\n";
+      if (R.logit_on) rep += "unfitted\t" + std::to_string(R.logit_table.n_unfitted) + "\n";
       bad = write_all(R.assoc_report_fd, rep.data(), rep.size()) != 0;
     }
   } else {

@@ -12,6 +12,7 @@
 #include "bvcf_score_q.h"
 #include "bvcf_assoc_q.h"
 #include "bvcf_assoc_cov_q.h"
+#include "bvcf_assoc_logit_q.h"
 
 #include <errno.h>
 #include <fcntl.h>
@@ -290,6 +291,11 @@ struct Run {
   bool covar_on = false;
   bvcf_covar_table covar_table{};
   uint64_t assoc_collinear = 0;
+  // --assocModel logistic: load_pheno checks the phenotypes for 0 / 1, fits the null models and builds the logistic table
+  // (with --covar from the covariate table, which then stays unbound: covar_on is false, no covariate kernels run);
+  // create_ctx uploads it; append_assoc takes the statistic from the record and the logistic record of a row
+  bool logit_on = false, logit_covar = false;
+  bvcf_logit_table logit_table{};
   ~Run() {
     for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
                    grm_n_fd, grm_id_fd, score_fd, score_report_fd, assoc_fd, assoc_report_fd, pca_vec_fd, pca_val_fd, pca_report_fd})
@@ -298,6 +304,7 @@ struct Run {
     bvcf_score_table_free(&score_table);
     bvcf_pheno_table_free(&pheno_table);
     bvcf_covar_table_free(&covar_table);
+    bvcf_logit_table_free(&logit_table);
     bvcf_variant_table_free(&variant_table);
     bvcf_region_table_free(&region_table);
   }
@@ -471,13 +478,19 @@ inline bool wants_assoc(const bvcf_config *c) {
 // otherwise both files are left empty)
 int open_assoc(Run &R, std::string *msg);
 int load_pheno(Run &R, std::string *msg);
-int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai, const bvcf_assoc_cov_info *ci = nullptr);
+int append_assoc(Run &R, const bvcf_result *r, const uint8_t *block, const bvcf_assoc_info &ai, const bvcf_assoc_cov_info *ci = nullptr,
+                 const bvcf_assoc_logit_info *li = nullptr);
 int close_assoc(Run &R, bool ok, std::string *msg);
 // --covar: the path of a config that reaches up to bvcf_config_covar (the twelfth marker) and names one; NULL otherwise
 inline const char *covar_path(const bvcf_config *c) {
   if (c->reserved[0] != BVCF_CONFIG_MORE || c->reserved[1] < BVCF_CONFIG_MORE_COVAR) return nullptr;
   const char *p = reinterpret_cast<const bvcf_config_covar *>(c)->covar_path;
   return p && *p ? p : nullptr;
+}
+// --assocModel: the model of a config that reaches up to bvcf_config_logit (the thirteenth marker); linear otherwise
+inline uint32_t assoc_model(const bvcf_config *c) {
+  if (c->reserved[0] != BVCF_CONFIG_MORE || c->reserved[1] < BVCF_CONFIG_MORE_LOGIT) return BVCF_ASSOC_MODEL_LINEAR;
+  return reinterpret_cast<const bvcf_config_logit *>(c)->assoc_model;
 }
 // --pca / --pcaCount / --pcaReport: the bvcf_config_pca of a config that reaches up to it (the eleventh marker); NULL otherwise
 inline const bvcf_config_pca *pca_config(const bvcf_config *c) {

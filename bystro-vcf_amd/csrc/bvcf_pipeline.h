@@ -186,6 +186,7 @@ struct FmtJob {
   bvcf_ld_info ld{};         // --ld / --ldPrune: bvcf_ld_stats of the batch (likewise)
   bvcf_assoc_info assoc{};   // --pheno / --assoc: bvcf_assoc of the batch (likewise)
   bvcf_assoc_cov_info assoc_cov{};  // --covar: bvcf_assoc_cov of the batch (likewise)
+  bvcf_assoc_logit_info assoc_logit{};  // --assocModel logistic: bvcf_assoc_logit of the batch (likewise)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };

@@ -74,6 +74,10 @@ struct Cli {
   std::string pheno, assoc, assoc_report;
   // extension: --covar FILE (with --pheno and --assoc), the scan adjusted for the file's covariates: y ~ g + C_1 .. C_J
   std::string covar;
+  // extension: --assocModel linear|logistic (with --pheno and --assoc): logistic is the covariate-adjusted logistic score test
+  // against a null model fitted once per phenotype; linear, the default, is the scan as it is without the flag
+  bool assoc_model_set = false;
+  uint32_t assoc_model = BVCF_ASSOC_MODEL_LINEAR;
   // extension: --pca PREFIX [--pcaCount K] [--pcaReport PATH], the top K principal components of the run's relationship
   // matrix as PREFIX.eigenvec / .eigenval (a dense symmetric eigensolver on the run's first device); --pcaCount alone is
   // accepted and does nothing
@@ -177,7 +181,7 @@ int parse(int argc, char **argv, Cli &c) {
         name == "ldR2" || name == "keepVariants" || name == "excludeVariants" || name == "variantFilterReport" ||
         name == "regions" || name == "regionsFile" || name == "excludeRegions" || name == "excludeRegionsFile" || name == "regionFilterReport" ||
         name == "grm" || name == "score" || name == "scoreOutput" || name == "scoreReport" || name == "pheno" || name == "assoc" ||
-        name == "assocReport" || name == "covar" || name == "pca" || name == "pcaCount" || name == "pcaReport") {
+        name == "assocReport" || name == "covar" || name == "assocModel" || name == "pca" || name == "pcaCount" || name == "pcaReport") {
       if (!has_val) {
         if (i + 1 >= argc) {
           fprintf(stderr, "flag needs an argument: -%s\n", name.c_str());
@@ -209,6 +213,13 @@ int parse(int argc, char **argv, Cli &c) {
           return 2;
         }
         (name == "score" ? c.score : name == "scoreOutput" ? c.score_output : c.score_report) = val;
+      } else if (name == "assocModel") {
+        if (val != "linear" && val != "logistic") {
+          fprintf(stderr, "invalid value \"%s\" for flag -assocModel: want linear or logistic\n", val.c_str());
+          return 2;
+        }
+        c.assoc_model_set = true;
+        c.assoc_model = val == "logistic" ? BVCF_ASSOC_MODEL_LOGISTIC : BVCF_ASSOC_MODEL_LINEAR;
       } else if (name == "covar") {
         if (val.empty()) {
           fprintf(stderr, "invalid value \"\" for flag -covar: want the path of the file to read\n");
@@ -341,6 +352,10 @@ int parse(int argc, char **argv, Cli &c) {
     fprintf(stderr, "-covar needs -pheno and -assoc\n");
     return 2;
   }
+  if (c.assoc_model_set && c.pheno.empty()) {
+    fprintf(stderr, "-assocModel needs -pheno and -assoc\n");
+    return 2;
+  }
   if (!c.pca_report.empty() && c.pca.empty()) {
     fprintf(stderr, "-pcaReport needs -pca\n");
     return 2;
@@ -401,8 +416,9 @@ int main(int argc, char **argv) {
   // (... and behind those the --ld paths, window and threshold; behind those the variant list and its report; behind those the
   // regions and their report; behind those the --grm prefix; behind that the --score paths; behind those the --pheno / --assoc
   // paths; behind those the --pca prefix, count and report)
-  bvcf_config_covar covar_cfg;
-  bvcf_config_covar_defaults(&covar_cfg);
+  bvcf_config_logit logit_cfg;
+  bvcf_config_logit_defaults(&logit_cfg);
+  bvcf_config_covar &covar_cfg = logit_cfg.covar;
   bvcf_config_pca &pca_cfg = covar_cfg.pca;
   bvcf_config_assoc &assoc_cfg = pca_cfg.assoc;
   bvcf_config_score &score_cfg = assoc_cfg.score;
@@ -495,6 +511,7 @@ int main(int argc, char **argv) {
   pca_cfg.pca_count = c.pca_count;
   pca_cfg.pca_report_path = c.pca_report.c_str();
   covar_cfg.covar_path = c.covar.c_str();
+  logit_cfg.assoc_model = c.assoc_model;
   const char *raw = getenv("BVCF_RAW_SAMPLE_NAMES");
   if (raw && *raw == '1') cfg.normalize_header = 0;
 

@@ -642,6 +642,86 @@ int bvcf_set_covar_table(bvcf_ctx *ctx, const bvcf_covar_table *t);
 int bvcf_assoc_cov(bvcf_ctx *ctx, bvcf_assoc_cov_info *out);
 int bvcf_assoc_cov_stat(const bvcf_covar_table *t, uint32_t k, const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals,
                         const uint64_t *cov_row, double out[6]);
+/* The logistic score test of the scan (--assocModel logistic): per phenotype a NULL MODEL logit P(y = 1) = beta . (1, C_1 ..
+ * C_J) is fitted once on the host, and every row is tested against it -- the score test of SAIGE / REGENIE / BOLT's binary
+ * modes, without their corrections.  J = 0 .. 16 (no covariate table: an intercept).  Every present value of every phenotype
+ * must be exactly 0 or 1 (Y = 0 or 10^6) after the masking of incomplete samples.
+ * THE NULL FIT of phenotype k over Omega = {i : P_k(i) = 1} in ascending sample index, one fixed sequence of IEEE double
+ * operations (none contracted into a multiply-add; exp is libm's): x_i0 = 1.0, x_ij = (double)C_j,i / 1e6, y_i = 1.0 or 0.0,
+ * beta = 0; then at most 25 rounds of
+ *   1. per sample: eta = beta_0; for j = 1 .. J: eta = eta + beta_j * x_ij;  mu_i = 1.0 / (1.0 + exp(-eta));
+ *      w_i = mu_i * (1.0 - mu_i);  r_i = y_i - mu_i
+ *   2. H[a][b] = sum_i (w_i * x_ia) * x_ib for b <= a, s[a] = sum_i x_ia * r_i; every sum starts at 0.0, ascending i
+ *   3. the unpivoted LDL^T of bvcf_assoc_cov_stat's sequence on H in the order 0 .. J with s carried as one more row:
+ *      q_b = u[J+1][b], z_b = q_b / d[b]
+ *   4. a pivot is usable iff d[a] > H[a][a] 2^-30; an unusable pivot ends the fit: UNFITTED
+ *   5. for b = J down to 0: delta_b = z_b; for t = b+1 .. J ascending: delta_b = delta_b - L[t][b] * delta_t
+ *   6. beta_a = beta_a + delta_a; a beta that is not finite: unfitted
+ *   7. converged iff max |delta_a| <= 1e-10
+ * No convergence after 25 rounds: unfitted (separation, an all-0 or all-1 trait and an empty Omega all end one of these
+ * ways).  For a fitted phenotype mu_i is computed once more from the final beta by step 1.
+ * FIXED POINT: M_i = the integer nearest to mu_i 2^24, ties to even (0 <= M <= 2^24); R_i = y_i 2^24 - M_i;
+ * W_i = floor(M_i (2^24 - M_i) / 2^24) (at most 2^22); outside Omega, and everywhere for an unfitted phenotype, all three
+ * are 0.  With C_0 = 1 and |C_j| <= 10^12 every sum below is an exact integer below 2^127 in size at S <= 2^22.
+ * THE LOGISTIC RECORD of a row: row_words = 2 K PV 64-bit words, PV = 4 (J + 1) + 2 + J (J + 1) / 2; per phenotype k at
+ * 2 k PV, every value a (lo, hi) pair of words, two's complement:
+ *   WC_het[J+1], WC_hom[J+1], WC_mis[J+1]   sum W C_a over the phenotype's samples of the class, a = 0 .. J
+ *   R_het, R_hom                            sum R over the class
+ *   RC_mis[J+1]                             sum R C_a over the missing class
+ *   WCC_mis[J (J + 1) / 2]                  sum W C_a C_b over the missing class, pair (1 <= a <= b <= J) at (b-1) b / 2 + (a-1)
+ * and bvcf_logit_table.totals is the same layout summed over all of Omega in the missing-class places (zero in the het / hom
+ * places); a row without a usable class map gets that row.  The counts n and altFreq come from the bvcf_assoc_rec.
+ * THE STATISTIC: the exact integer matrix G, indices 0 .. J + 2: G[a][b] = totals - mis for b <= a <= J (column 0 from WC_mis,
+ * the rest from WCC_mis); G[J+1][b] = WC_het[b] + 2 WC_hom[b]; G[J+1][J+1] = WC_het[0] + 4 WC_hom[0]; G[J+2][b] = totals -
+ * RC_mis[b] for b <= J; G[J+2][J+1] = R_het + 2 R_hom; G[J+2][J+2] is not used.  D is the correctly rounded double of G; the
+ * elimination sequence of bvcf_assoc_cov_stat runs on the rows 0 .. J + 1 and on the off-diagonal part of the row J + 2;
+ * V = d[J+1], ug = u[J+2][J+1].  The statistics exist iff the phenotype is fitted, n >= J + 3 and every d[a], a <= J + 1, is
+ * usable by the 2^-30 rule; then
+ *   beta = ug / V (the one-step log odds per ALT allele)   chisq = (ug / V) * (ug / 16777216.0)
+ *   se = sqrt(16777216.0 / V)                              p = erfc(sqrt(chisq / 2.0))
+ * A (row, phenotype) of a fitted phenotype with n >= J + 3 whose first unusable pivot is one of a <= J counts as COLLINEAR.
+ * OPERAND B: int8 b[16 n_blocks][s64], zero past s and outside Omega, balanced base-256 digits in blocks of 16 columns, in
+ * this order: the "WC" blocks (value k (J + 1) + a: the lwc digits of W_k C_a), the "R" blocks (value k: the lr digits of R_k),
+ * the "RC" blocks (value k (J + 1) + a: the lrc digits of R_k C_a), the "WCC" blocks (value k J (J + 1) / 2 + pair: the lwcc
+ * digits of W_k C_a C_b).  A block holds 16 / digits whole values of its family and zero columns behind them, so no value
+ * straddles a block; value v of a family is in the family's block v / (16 / digits) at column (v % (16 / digits)) digits.
+ * lwc (1 .. 8), lr (1 .. 4), lrc (1 .. 9) and lwcc (1 .. 13) are the smallest counts that hold the table's values.
+ * bvcf_logit_table_build: the fit, the fixed-point vectors, the totals and operand B from a phenotype table -- the masked one
+ * when there are covariates -- and a covariate table (bound or not; its samples must be the phenotype table's and no
+ * phenotype may be present on an incomplete sample) or NULL.  BVCF_E_ARG with a message in err that names the phenotype and
+ * the first sample whose present value is neither 0 nor 1.  Pure host code.
+ * bvcf_set_logit_table: to a ctx that has the phenotype table it was built from and no covariate table (BVCF_E_ARG
+ * otherwise), before the first submit.  The slots get one more arena [rows][row_words]; the 1 GiB cap of a slot applies to
+ * the arenas' sum (BVCF_E_TOO_BIG with a message: fewer columns, fewer covariates or smaller batches),
+ * bvcf_reserve_assoc_rows grows all of them, and a batch whose rows outrun any writes nothing (BVCF_E_CAPACITY).  Without it
+ * nothing new is allocated or launched.  bvcf_assoc_logit: the logistic records of the batch bvcf_assoc describes.
+ * bvcf_assoc_logit_stat: pure host code, phenotype k of a row from its two records; out as bvcf_assoc_stat's.  Returns bit 0:
+ * altFreq is there; bit 1: beta, se, chisq and p are there; bit 2: collinear.  -1 for NULL or k >= K. */
+typedef struct {
+  uint32_t n_covars, n_samples, s64, n_columns;
+  uint32_t lwc, lr, lrc, lwcc;
+  uint32_t n_blocks, row_words;
+  uint32_t n_unfitted, pad;
+  const int8_t *b;          /* [16 n_blocks][s64] */
+  const int64_t *c;         /* [n_covars][n_samples] */
+  const int64_t *m, *r, *w; /* [n_columns][n_samples] each */
+  const uint8_t *fitted;    /* [n_columns] */
+  const uint32_t *rounds;   /* [n_columns] the rounds the fit took */
+  const double *beta;       /* [n_columns][n_covars + 1] (what the last round left when unfitted) */
+  const uint64_t *pheno_np; /* [n_columns] NP of the phenotype table */
+  const uint64_t *totals;   /* [row_words] */
+} bvcf_logit_table;
+typedef struct {
+  const uint64_t *words; /* [n_rows][row_words] */
+  uint64_t n_rows;
+  uint32_t row_words;
+} bvcf_assoc_logit_info;
+int bvcf_logit_table_build(const bvcf_pheno_table *pheno, const bvcf_covar_table *covar, bvcf_logit_table *out, char *err, size_t err_cap);
+void bvcf_logit_table_free(bvcf_logit_table *t);
+int bvcf_set_logit_table(bvcf_ctx *ctx, const bvcf_logit_table *t);
+int bvcf_assoc_logit(bvcf_ctx *ctx, bvcf_assoc_logit_info *out);
+int bvcf_assoc_logit_stat(const bvcf_logit_table *t, uint32_t k, const bvcf_assoc_rec *rec, const bvcf_pheno_totals *totals,
+                          const uint64_t *logit_row, double out[6]);
 /* The same rows as the rows of a PLINK 1 .bed file (variant-major), packed on the device from the class maps (which the
  * ctx then makes even when want_class_maps is 0, without copying them to the host).  A row is row_bytes = ceil(S / 4) bytes,
  * S = bvcf_result.n_samples, sample s in byte s / 4 at bits 2 (s % 4), A1 = the row's ALT and A2 = its REF:
@@ -1272,6 +1352,30 @@ typedef struct {
 } bvcf_config_covar;
 /* the whole struct: bvcf_config_pca_defaults, base.reserved[1] = BVCF_CONFIG_MORE_COVAR, no covariates */
 void bvcf_config_covar_defaults(bvcf_config_covar *c);
+/* Likewise what came after bvcf_config_covar: read only when base.reserved[0] = BVCF_CONFIG_MORE and base.reserved[1] >=
+ * BVCF_CONFIG_MORE_LOGIT.  bvcf_config_logit_defaults sets that; the twelve older *_defaults write what they wrote. */
+#define BVCF_CONFIG_MORE_LOGIT 12
+#define BVCF_ASSOC_MODEL_LINEAR 0
+#define BVCF_ASSOC_MODEL_LOGISTIC 1
+typedef struct {
+  bvcf_config_covar covar;
+  /* --assocModel linear|logistic (only with pheno_path and assoc_path, BVCF_E_ARG otherwise; another value: BVCF_E_ARG).
+   * BVCF_ASSOC_MODEL_LINEAR = 0: every byte is what the run writes without the field.  BVCF_ASSOC_MODEL_LOGISTIC: the scan of
+   * assoc_path is the logistic score test against a null model fitted once per phenotype (bvcf_assoc_logit_stat has the
+   * definition), with covar_path's covariates or, without one, an intercept alone.  The files' rules do not change; one
+   * more: after the masking of incomplete samples every present value of every phenotype must be exactly 0 or 1, otherwise
+   * BVCF_E_FATAL with one message that names the phenotype and the first such sample, before any device work.
+   * assoc_path keeps its columns and header: beta is the one-step log odds per ALT allele; beta, se, chisq and p are
+   * empty_field for an unfitted phenotype, when n < J + 3 or when a pivot is not usable.  assoc_report_path holds its four
+   * lines, then "covariates", "incomplete" and "collinear" (zeros without covar_path), then "unfitted": the phenotypes
+   * whose null model did not fit.  The bytes do not depend on devices, batch size or input kind, and no other output
+   * changes.  Not done here: Firth's correction, the saddle-point approximation for unbalanced traits, refitting the null
+   * model per row, odds-ratio and confidence columns, mixed models */
+  uint32_t assoc_model;
+  uint32_t reserved_logit;
+} bvcf_config_logit;
+/* the whole struct: bvcf_config_covar_defaults, base.reserved[1] = BVCF_CONFIG_MORE_LOGIT, the linear model */
+void bvcf_config_logit_defaults(bvcf_config_logit *c);
 
 /* write_grm's arithmetic on its own: tables as bvcf_grm gives them (summed over a run's ctxs: [3 s s + 1]) -> the lower
  * triangle with the diagonal, row by row (s (s + 1) / 2 floats each): lower = A(i,j) = (float)((double)T / (2^28 N(i,j))), 0 when

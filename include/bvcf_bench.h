@@ -61,6 +61,10 @@ int bvcf_bench_assoc_kernels(bvcf_ctx *ctx, float ms[3]);
  * first: ms = {k_assoc_cov_gemm, k_assoc_cov_sparse}.  BVCF_E_ARG on a ctx without a covariate table or without a bench call
  * before; BVCF_E_CAPACITY when the block's rows outrun the arenas (bvcf_reserve_assoc_rows) */
 int bvcf_bench_assoc_cov_kernels(bvcf_ctx *ctx, float ms[2]);
+/* bvcf_set_logit_table: likewise the two kernels of the logistic model: ms = {k_assoc_logit_gemm, k_assoc_logit_sparse}.
+ * BVCF_E_ARG on a ctx without a logistic table or without a bench call before; BVCF_E_CAPACITY when the block's rows outrun
+ * the arenas (bvcf_reserve_assoc_rows) */
+int bvcf_bench_assoc_logit_kernels(bvcf_ctx *ctx, float ms[2]);
 
 /* The exact Hardy-Weinberg test as the site gate runs it on the device: triples = n x {het, hom, other}, p[j] the p value of
  * triple j -- by the thread-per-row recurrence or by a wave (k_site_hwe's code), chosen by the length of the support as
