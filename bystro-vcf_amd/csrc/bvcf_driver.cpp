@@ -393,71 +393,18 @@ void Driver::device_main(DevWorker *W) {
       // (what the batch that asked reported, for its result arrays and for the analyses' arenas: read before the collects
       // below replace the ctx's reports)
       const BatchNeed need = read_batch_need(W->ctx, c_, res);
-      // (--sampleStats: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
-      const bool ss = R_.params.want_sample_stats && R_.pre.header.size() > 9;
-      if (ss) {
-        const size_t n = 6 * (R_.pre.header.size() - 9);
-        std::vector<uint64_t> t(n, 0);
-        W->ss_carry.resize(n, 0);
-        if (bvcf_sample_stats(W->ctx, t.data(), 1) != BVCF_OK) {
-          fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          return;
-        }
-        for (size_t k = 0; k < n; k++) W->ss_carry[k] += t[k];
-      }
-      // (--relatedness: the same for the pair tables)
-      const bool pr = wants_pair_stats(c_) && R_.pre.header.size() > 9;
-      if (pr) {
-        const size_t ns = R_.pre.header.size() - 9, n = 3 * ns * ns;
-        std::vector<uint64_t> t(n, 0);
-        W->pr_carry.resize(n, 0);
-        if (bvcf_pair_stats(W->ctx, t.data(), 1) != BVCF_OK) {
-          fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          return;
-        }
-        for (size_t k = 0; k < n; k++) W->pr_carry[k] += t[k];
-      }
-      // (--grm: the same for the GRM's tables)
-      const bool grm = wants_grm_tables(c_) && R_.pre.header.size() > 9;
-      if (grm) {
-        const size_t ns = R_.pre.header.size() - 9;
-        std::vector<uint64_t> t(grm_table_words(ns), 0);
-        if (bvcf_grm(W->ctx, t.data(), 1) != BVCF_OK) {
-          fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          return;
-        }
-        add_grm_table(W->grm_carry, t.data(), ns);
-      }
-      // (--score: the same for the scores' words)
-      const bool score = R_.score_on && R_.pre.header.size() > 9;
-      if (score) {
-        const size_t ns = R_.pre.header.size() - 9, k = R_.score_table.n_columns;
-        std::vector<uint64_t> t(score_table_words(ns, k), 0);
-        if (bvcf_score(W->ctx, t.data(), 1) != BVCF_OK) {
-          fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          return;
-        }
-        add_score_words(W->score_carry, t.data(), ns, k);
+      // (the run tables: the ctx's totals hold the batches handed on so far -- kept here -- and then those dropped below)
+      if (const int crc = carry_run_tables(R_, W->ctx, &W->carry, false, &wmsg)) {
+        fail(wmsg, crc);
+        return;
       }
       for (size_t k = 1; k < in_flight.size(); k++) {
         bvcf_result tmp;
         bvcf_collect(W->ctx, &tmp);
         n_collects++;
       }
-      if (score && bvcf_score(W->ctx, nullptr, 1) != BVCF_OK) {
-        fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-        return;
-      }
-      if (grm && bvcf_grm(W->ctx, nullptr, 1) != BVCF_OK) {
-        fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-        return;
-      }
-      if (pr && bvcf_pair_stats(W->ctx, nullptr, 1) != BVCF_OK) {
-        fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-        return;
-      }
-      if (ss && bvcf_sample_stats(W->ctx, nullptr, 1) != BVCF_OK) {
-        fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+      if (const int crc = carry_run_tables(R_, W->ctx, &W->carry, true, &wmsg)) {
+        fail(wmsg, crc);
         return;
       }
       // (grown with nothing in flight, before the batches are submitted again)
@@ -475,47 +422,13 @@ void Driver::device_main(DevWorker *W) {
     }
     in_flight.pop_front();
     lines_in_.fetch_add(res.n_lines_seen);
-    if (sg_fd_ >= 0) {  // --siteFilterReport: exactly the batches of the output -- nothing to reset when a reservation grows
-      uint64_t t[7];
-      bvcf_site_gate_count(&res, t);
-      for (int q = 0; q < 7; q++) W->gate_counts[q] += t[q];
-    }
-    if (R_.variant_fd >= 0) {  // --variantFilterReport: likewise
-      uint64_t t[3];
-      bvcf_variant_gate_count(&res, t);
-      for (int q = 0; q < 3; q++) W->variant_counts[q] += t[q];
-    }
-    if (R_.region_fd >= 0) {  // --regionFilterReport: likewise
-      uint64_t t[3];
-      bvcf_region_gate_count(&res, t);
-      for (int q = 0; q < 3; q++) W->region_counts[q] += t[q];
-    }
+    W->gates.add(R_, res);  // (exactly the batches of the output: nothing to reset when a reservation grows)
     FmtJob j;
     j.b = b;
     j.res = res;
     j.has_res = true;
-    if (wants_plink(c_) && bvcf_bed_rows(W->ctx, &j.bed) != BVCF_OK) {  // --plinkOutput: the rows collected with this batch
-      fail(std::string("bvcf_bed_rows: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-      return;
-    }
-    if (R_.mendel_on && bvcf_trio_stats(W->ctx, &j.trio) != BVCF_OK) {  // --mendel / --mendelErrors: likewise
-      fail(std::string("bvcf_trio_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-      return;
-    }
-    if (R_.ld_on && bvcf_ld_stats(W->ctx, &j.ld) != BVCF_OK) {  // --ld / --ldPrune: likewise
-      fail(std::string("bvcf_ld_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-      return;
-    }
-    if (R_.assoc_on && bvcf_assoc(W->ctx, &j.assoc) != BVCF_OK) {  // --pheno / --assoc: likewise
-      fail(std::string("bvcf_assoc: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-      return;
-    }
-    if (R_.covar_on && bvcf_assoc_cov(W->ctx, &j.assoc_cov) != BVCF_OK) {  // --covar: likewise
-      fail(std::string("bvcf_assoc_cov: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-      return;
-    }
-    if (R_.logit_on && bvcf_assoc_logit(W->ctx, &j.assoc_logit) != BVCF_OK) {  // --assocModel logistic: likewise
-      fail(std::string("bvcf_assoc_logit: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
+    if (const int frc = fetch_batch_outputs(R_, W->ctx, &j.outputs, &wmsg)) {  // (what was collected with this batch)
+      fail(wmsg, frc);
       return;
     }
     j.job = n_jobs;
@@ -612,38 +525,14 @@ void Driver::formatter_main(DevWorker *W) {
         format_parts(c_, &j.res, text, *R_.names, R_.ratios.get(), W->fmt_pool.get(), *it.parts);
       else
         for (auto &q : *it.parts) q.clear();
-      const bool plink = R_.bed_fd >= 0;
-      const bool mendel = R_.mendel_on && !R_.trios.empty();  // (the tables are summed in input order too: one thread)
-      const bool ld = R_.ld_on;  // (the seam is a state machine over the batches in input order: one thread)
-      const bool assoc = R_.assoc_fd >= 0;  // (the lines go into the file in input order: one thread)
-      if ((R_.arrow && j.res.dosage) || plink || mendel || ld || assoc) {
-        // the dosage rows go into the file in input order (main.go:576-584): the sink runs this when it is the block's
-        // turn; the result slot and the text stay on loan until then -- and so do the batch's .bed rows and .bim lines
+      if (has_batch_outputs(R_, j.res)) {
+        // the dosage rows go into the file in input order (main.go:576-584), and so do the other per-batch outputs (the trio
+        // tables are summed, the LD seam is fed, the scan's lines are written in that order: one thread): the sink runs this
+        // when it is the block's turn; the result slot, the text and the ctx's reports stay on loan until then
         auto keep = std::make_shared<FmtJob>(std::move(j));
-        it.in_order = [this, keep, text, release, plink, mendel, ld, assoc]() {
-          if (!dosage_failed_.load() && append_dosage(R_, &keep->res, text)) {
-            dosage_failed_.store(true);
-            fail("dosage matrix: write failed", BVCF_E_FATAL);
-          }
-          if (plink && !plink_failed_.load() && append_plink(R_, &keep->res, text, keep->bed)) {
-            plink_failed_.store(true);
-            fail("plinkOutput: write failed", BVCF_E_FATAL);
-          }
-          if (mendel && !mendel_failed_.load() && append_mendel(R_, &keep->res, text, keep->trio)) {
-            mendel_failed_.store(true);
-            fail("mendel: the device's events do not match the batch's rows", BVCF_E_FATAL);
-          }
-          if (ld && !ld_failed_.load() && append_ld(R_, &keep->res, text, keep->ld)) {
-            ld_failed_.store(true);
-            fail("ld: the device's events do not match the batch's rows", BVCF_E_FATAL);
-          }
-          if (assoc && !assoc_failed_.load()) {
-            if (const int arc = append_assoc(R_, &keep->res, text, keep->assoc, R_.covar_on ? &keep->assoc_cov : nullptr,
-                                               R_.logit_on ? &keep->assoc_logit : nullptr)) {
-              assoc_failed_.store(true);
-              fail(arc == BVCF_E_IO ? "assoc: write failed" : "assoc: the device's rows do not match the batch's rows", BVCF_E_FATAL);
-            }
-          }
+        it.in_order = [this, keep, text, release]() {
+          std::string msg;
+          if (const int arc = append_batch_outputs(R_, &keep->res, text, keep->outputs, &msg)) fail(msg, arc);
           release();
         };
       } else {
@@ -659,53 +548,9 @@ void Driver::formatter_main(DevWorker *W) {
 }
 
 int Driver::run(uint64_t *n_lines_in) {
-  if (!dry_) {  // --sampleStats: opened before any device work, as --sample's file is written before it
+  if (!dry_) {  // every side output is opened before any device work, as --sample's file is written before it
     std::string msg;
-    if (open_sample_stats(c_, &ss_fd_, &msg)) {
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return BVCF_E_IO;
-    }
-    if (open_pair_stats(c_, &pr_fd_, &msg)) {  // --relatedness: likewise
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return BVCF_E_IO;
-    }
-    if (open_site_report(c_, &sg_fd_, &msg)) {  // --siteFilterReport: likewise
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return BVCF_E_IO;
-    }
-    if (open_plink(R_, &msg)) {  // --plinkOutput: likewise, all three files
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return BVCF_E_IO;
-    }
-    if (const int rc = open_mendel(R_, &msg)) {  // --mendel / --mendelErrors: likewise
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_ld(R_, &msg)) {  // --ld / --ldPrune: likewise
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_variants(R_, &msg)) {  // --keepVariants / --excludeVariants / --variantFilterReport: the list read, the report opened
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_regions(R_, &msg)) {  // --regions / --excludeRegions and their files, --regionFilterReport: likewise
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_grm(R_, &msg)) {  // --grm: likewise, all three files
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_score(R_, &msg)) {  // --score: the outputs opened, the score file read
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_assoc(R_, &msg)) {  // --pheno / --assoc: the outputs opened
-      dprintf(fd_err_, "%s\n", msg.c_str());
-      return rc;
-    }
-    if (const int rc = open_pca(R_, &msg)) {  // --pca / --pcaReport: the outputs opened
+    if (const int rc = open_outputs(R_, &msg)) {
       dprintf(fd_err_, "%s\n", msg.c_str());
       return rc;
     }
@@ -824,6 +669,8 @@ int Driver::run(uint64_t *n_lines_in) {
   sink_->close();
   sink_->join();
   if (sink_->write_failed()) fail("write failed", BVCF_E_FATAL);
+  // (finish_outputs' first two steps, taken here already: a failure keeps the compressed stream's end-of-file block back
+  // and is in the log below)
   if (close_dosage(R_)) fail("dosage matrix: write failed", BVCF_E_FATAL);
   if (close_plink(R_)) fail("plinkOutput: write failed", BVCF_E_FATAL);
   if (bgzf_) {
@@ -867,151 +714,22 @@ int Driver::run(uint64_t *n_lines_in) {
       }
     }
     t_gather = now_s() - tg;
-    if (ss_fd_ >= 0) {
-      // --sampleStats: every ctx's table (and what its worker kept across a reservation) summed on the host -- integer sums,
-      // so the table does not depend on how the blocks were dealt
-      if (rc_ == BVCF_OK) {
-        const size_t n = R_.pre.header.size() > 9 ? 6 * (R_.pre.header.size() - 9) : 0;
-        std::vector<uint64_t> sum(n, 0), t(n, 0);
-        for (auto &W : workers_) {
-          if (!W->ctx) continue;
-          if (bvcf_sample_stats(W->ctx, t.data(), 0) != BVCF_OK) {
-            fail(std::string("bvcf_sample_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-            break;
-          }
-          for (size_t k = 0; k < n; k++) sum[k] += t[k] + (k < W->ss_carry.size() ? W->ss_carry[k] : 0);
-        }
-        std::string msg;
-        if (rc_ == BVCF_OK && write_sample_stats(ss_fd_, c_, R_.pre, sum.data(), &msg)) fail(msg, BVCF_E_IO);
-        if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
-      }
-      if (rc_ != BVCF_OK) close(ss_fd_);  // (write_sample_stats closed it)
-      ss_fd_ = -1;
-    }
-    if (pr_fd_ >= 0) {
-      // --relatedness: the workers' pair tables added one after another into one host table
-      if (rc_ == BVCF_OK) {
-        const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0, n = 3 * ns * ns;
-        std::vector<uint64_t> sum(n, 0), t;
-        for (auto &W : workers_) {
-          if (!W->ctx) continue;
-          t.assign(n, 0);
-          if (bvcf_pair_stats(W->ctx, t.data(), 0) != BVCF_OK) {
-            fail(std::string("bvcf_pair_stats: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-            break;
-          }
-          for (size_t k = 0; k < n; k++) sum[k] += t[k];
-          for (size_t k = 0; k < n && k < W->pr_carry.size(); k++) sum[k] += W->pr_carry[k];
-        }
-        std::string msg;
-        if (rc_ == BVCF_OK && write_pair_stats(pr_fd_, c_, R_.pre, sum.data(), &msg)) fail(msg, BVCF_E_IO);
-        if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
-      }
-      if (rc_ != BVCF_OK) close(pr_fd_);  // (write_pair_stats closed it)
-      pr_fd_ = -1;
-    }
-    if ((R_.grm_fd >= 0 || R_.pca_vec_fd >= 0) && rc_ == BVCF_OK) {
-      // --grm / --pca: the workers' tables added one after another into one host table (a failed run leaves the files empty)
-      const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0;
-      std::vector<uint64_t> sum(grm_table_words(ns), 0), t;
+    // the end of the side outputs: every ctx's tables (and what its worker kept across a reservation) and the workers' gate
+    // counts summed on the host -- integer sums, so they do not depend on how the blocks were dealt --, then every output
+    // written, or after a failed run left empty (--pca solves on the run's first device)
+    {
+      const bool ran = rc_ == BVCF_OK;
+      RunSums sums;
+      GateCounts gates;
+      std::string msg;
+      int frc = rc_;
       for (auto &W : workers_) {
-        if (!W->ctx) continue;
-        t.assign(grm_table_words(ns), 0);
-        if (bvcf_grm(W->ctx, t.data(), 0) != BVCF_OK) {
-          fail(std::string("bvcf_grm: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          break;
-        }
-        add_grm_table(sum, t.data(), ns);
-        if (!W->grm_carry.empty()) add_grm_table(sum, W->grm_carry.data(), ns);
+        gates += W->gates;
+        if (W->ctx && frc == BVCF_OK) frc = sum_run_tables(R_, W->ctx, W->carry, &sums, &msg);
       }
-      std::string msg;
-      if (rc_ == BVCF_OK && R_.grm_fd >= 0 && write_grm(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
-      // (the components of the same matrix, solved on the run's first device)
-      if (rc_ == BVCF_OK && R_.pca_vec_fd >= 0) {
-        if (const int prc = write_pca(R_, sum.data(), dev_list_[0] >= 0 ? dev_list_[0] : c_->device, &msg)) fail(msg, prc);
-      }
-      if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
-    }
-    if (R_.score_fd >= 0 && rc_ == BVCF_OK) {
-      // --score: the workers' words added one after another into one host table (a failed run leaves the files empty)
-      const size_t ns = R_.pre.header.size() > 9 ? R_.pre.header.size() - 9 : 0, k = R_.score_table.n_columns;
-      std::vector<uint64_t> sum(score_table_words(ns, k), 0), t;
-      for (auto &W : workers_) {
-        if (!W->ctx) continue;
-        t.assign(score_table_words(ns, k), 0);
-        if (bvcf_score(W->ctx, t.data(), 0) != BVCF_OK) {
-          fail(std::string("bvcf_score: ") + bvcf_last_error(W->ctx), BVCF_E_HIP);
-          break;
-        }
-        if (ns) add_score_words(sum, t.data(), ns, k);
-        if (!W->score_carry.empty()) add_score_words(sum, W->score_carry.data(), ns, k);
-      }
-      std::string msg;
-      if (rc_ == BVCF_OK && write_score(R_, sum.data(), &msg)) fail(msg, BVCF_E_IO);
-      if (rc_ != BVCF_OK) write_all(fd_err_, log_.data(), log_.size());
-    }
-    if (R_.assoc_fd >= 0) {
-      // --pheno / --assoc: the sink wrote the batches it was handed, in input order; the last lines and the report
-      std::string msg;
-      if (close_assoc(R_, rc_ == BVCF_OK, &msg)) {
-        fail(msg, BVCF_E_IO);
-        write_all(fd_err_, log_.data(), log_.size());
-      }
-    }
-    if (sg_fd_ >= 0) {
-      // --siteFilterReport: the workers' counts of the batches they handed on
-      if (rc_ == BVCF_OK) {
-        uint64_t sum[7] = {0, 0, 0, 0, 0, 0, 0};
-        for (auto &W : workers_)
-          for (int q = 0; q < 7; q++) sum[q] += W->gate_counts[q];
-        std::string msg;
-        if (write_site_report(sg_fd_, sum, &msg)) {
-          fail(msg, BVCF_E_IO);
-          write_all(fd_err_, log_.data(), log_.size());
-        }
-      } else {
-        close(sg_fd_);
-      }
-      sg_fd_ = -1;
-    }
-    if (R_.variant_fd >= 0 && rc_ == BVCF_OK) {
-      // --variantFilterReport: the workers' counts of the batches they handed on (a failed run leaves the file empty)
-      uint64_t sum[3] = {0, 0, 0};
-      for (auto &W : workers_)
-        for (int q = 0; q < 3; q++) sum[q] += W->variant_counts[q];
-      std::string msg;
-      if (write_variant_report(R_, sum, &msg)) {
-        fail(msg, BVCF_E_IO);
-        write_all(fd_err_, log_.data(), log_.size());
-      }
-    }
-    if (R_.region_fd >= 0 && rc_ == BVCF_OK) {  // --regionFilterReport: likewise
-      uint64_t sum[3] = {0, 0, 0};
-      for (auto &W : workers_)
-        for (int q = 0; q < 3; q++) sum[q] += W->region_counts[q];
-      std::string msg;
-      if (write_region_report(R_, sum, &msg)) {
-        fail(msg, BVCF_E_IO);
-        write_all(fd_err_, log_.data(), log_.size());
-      }
-    }
-    if (R_.mendel_fd >= 0 || R_.mendel_errors_fd >= 0) {
-      // --mendel / --mendelErrors: the sink added up the batches it was handed, in input order
-      std::string msg;
-      if (rc_ != BVCF_OK) {
-        close_mendel(R_);
-      } else if (write_mendel(R_, &msg)) {
-        fail(msg, BVCF_E_IO);
-        write_all(fd_err_, log_.data(), log_.size());
-      }
-    }
-    if (R_.ld_fd >= 0 || R_.ld_in_fd >= 0 || R_.ld_out_fd >= 0) {
-      // --ld / --ldPrune: the seam saw the batches the sink was handed, in input order
-      std::string msg;
-      if (rc_ != BVCF_OK) {
-        close_ld(R_);
-      } else if (write_ld(R_, &msg)) {
-        fail(msg, BVCF_E_IO);
+      frc = finish_outputs(R_, frc, &sums, gates, dev_list_[0] >= 0 ? dev_list_[0] : c_->device, &msg);
+      if (ran && frc != BVCF_OK) {
+        fail(msg, frc);
         write_all(fd_err_, log_.data(), log_.size());
       }
     }

@@ -207,22 +207,8 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
   R.cfg = c;
   R.max_batch = c->max_batch_bytes ? c->max_batch_bytes : (64ull << 20);
   uint64_t lines_in = 0;
-  int ss_fd = -1, pr_fd = -1, sg_fd = -1;
-  uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};
-  uint64_t variant_counts[3] = {0, 0, 0};
-  uint64_t region_counts[3] = {0, 0, 0};
-  int rc = open_sample_stats(c, &ss_fd, &msg);
-  if (rc == BVCF_OK) rc = open_pair_stats(c, &pr_fd, &msg);
-  if (rc == BVCF_OK) rc = open_site_report(c, &sg_fd, &msg);
-  if (rc == BVCF_OK) rc = open_plink(R, &msg);
-  if (rc == BVCF_OK) rc = open_mendel(R, &msg);
-  if (rc == BVCF_OK) rc = open_ld(R, &msg);
-  if (rc == BVCF_OK) rc = open_variants(R, &msg);
-  if (rc == BVCF_OK) rc = open_regions(R, &msg);
-  if (rc == BVCF_OK) rc = open_grm(R, &msg);
-  if (rc == BVCF_OK) rc = open_score(R, &msg);
-  if (rc == BVCF_OK) rc = open_assoc(R, &msg);
-  if (rc == BVCF_OK) rc = open_pca(R, &msg);
+  GateCounts gates;
+  int rc = open_outputs(R, &msg);
   if (rc) {
     l = msg + "\n";
   } else if ((rc = parse_preamble(vcf, n, true, c->normalize_header, &R.pre, &msg)) < 0) {
@@ -257,175 +243,28 @@ int bvcf_run_buffer(const bvcf_config *c, const uint8_t *vcf, size_t n, char **o
         break;
       }
       lines_in += res.n_lines_seen;
-      if (sg_fd >= 0) {  // --siteFilterReport: what the gate did to the batches of the output
-        uint64_t t[7];
-        bvcf_site_gate_count(&res, t);
-        for (int q = 0; q < 7; q++) gate_counts[q] += t[q];
-      }
-      if (R.variant_fd >= 0) {  // --variantFilterReport: likewise
-        uint64_t t[3];
-        bvcf_variant_gate_count(&res, t);
-        for (int q = 0; q < 3; q++) variant_counts[q] += t[q];
-      }
-      if (R.region_fd >= 0) {  // --regionFilterReport: likewise
-        uint64_t t[3];
-        bvcf_region_gate_count(&res, t);
-        for (int q = 0; q < 3; q++) region_counts[q] += t[q];
-      }
+      gates.add(R, res);  // --siteFilterReport & co.: what the gates did to the batches of the output
       if (R.want_rows) {
         format_batch(c, &res, vcf + pos, nm, R.ratios.get(), R.pool.get(), o, l);
       } else {
         format_log(&res, vcf + pos, l);
       }
-      if (append_dosage(R, &res, vcf + pos)) {
-        l.append("dosage matrix: write failed\n");
-        rc = BVCF_E_FATAL;
+      BatchOutputs bo;  // the outputs written batch by batch
+      rc = fetch_batch_outputs(R, R.ctx, &bo, &msg);
+      if (rc == BVCF_OK) rc = append_batch_outputs(R, &res, vcf + pos, bo, &msg);
+      if (rc) {
+        l.append(msg + "\n");
         break;
-      }
-      if (wants_plink(c)) {  // --plinkOutput: the batch's .bed rows and .bim lines
-        bvcf_bed_rows_info bed;
-        if (bvcf_bed_rows(R.ctx, &bed) != BVCF_OK || append_plink(R, &res, vcf + pos, bed)) {
-          l.append("plinkOutput: write failed\n");
-          rc = BVCF_E_FATAL;
-          break;
-        }
-      }
-      if (R.mendel_on) {  // --mendel / --mendelErrors: the batch's counts and events
-        bvcf_trio_info ti;
-        if (bvcf_trio_stats(R.ctx, &ti) != BVCF_OK || append_mendel(R, &res, vcf + pos, ti)) {
-          l.append("mendel: the device's events do not match the batch's rows\n");
-          rc = BVCF_E_FATAL;
-          break;
-        }
-      }
-      if (R.ld_on) {  // --ld / --ldPrune: the batch's events and edge rows
-        bvcf_ld_info li;
-        if (bvcf_ld_stats(R.ctx, &li) != BVCF_OK || append_ld(R, &res, vcf + pos, li)) {
-          l.append("ld: the device's events do not match the batch's rows\n");
-          rc = BVCF_E_FATAL;
-          break;
-        }
-      }
-      if (R.assoc_on) {  // --pheno / --assoc: the batch's records, a line per (row, phenotype)
-        bvcf_assoc_info ai;
-        bvcf_assoc_cov_info ci;
-        bvcf_assoc_logit_info li;
-        const int arc = bvcf_assoc(R.ctx, &ai) != BVCF_OK || (R.covar_on && bvcf_assoc_cov(R.ctx, &ci) != BVCF_OK) ||
-                                (R.logit_on && bvcf_assoc_logit(R.ctx, &li) != BVCF_OK)
-                            ? BVCF_E_FATAL
-                            : append_assoc(R, &res, vcf + pos, ai, R.covar_on ? &ci : nullptr, R.logit_on ? &li : nullptr);
-        if (arc) {
-          l.append(arc == BVCF_E_IO ? "assoc: write failed\n" : "assoc: the device's rows do not match the batch's rows\n");
-          rc = BVCF_E_FATAL;
-          break;
-        }
       }
       pos += nb;
     }
   }
-  if (close_dosage(R) && rc == BVCF_OK) {
-    l.append("dosage matrix: write failed\n");
-    rc = BVCF_E_FATAL;
-  }
-  if (close_plink(R) && rc == BVCF_OK) {
-    l.append("plinkOutput: write failed\n");
-    rc = BVCF_E_FATAL;
-  }
-  if (R.mendel_fd >= 0 || R.mendel_errors_fd >= 0) {  // --mendel / --mendelErrors: after a successful run only
-    if (rc != BVCF_OK) {
-      close_mendel(R);
-    } else if (write_mendel(R, &msg)) {
-      l.append(msg + "\n");
-      rc = BVCF_E_IO;
-    }
-  }
-  if (R.ld_fd >= 0 || R.ld_in_fd >= 0 || R.ld_out_fd >= 0) {  // --ld / --ldPrune: after a successful run only
-    if (rc != BVCF_OK) {
-      close_ld(R);
-    } else if (write_ld(R, &msg)) {
-      l.append(msg + "\n");
-      rc = BVCF_E_IO;
-    }
-  }
-  if (ss_fd >= 0) {  // --sampleStats: the run's table, after a successful run only
-    if (rc == BVCF_OK) {
-      const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
-      std::vector<uint64_t> t(6 * ns, 0);
-      if (R.ctx && bvcf_sample_stats(R.ctx, t.data(), 0) != BVCF_OK) {
-        l.append(std::string("bvcf_sample_stats: ") + bvcf_last_error(R.ctx) + "\n");
-        rc = BVCF_E_HIP;
-        close(ss_fd);
-      } else if (write_sample_stats(ss_fd, c, R.pre, t.data(), &msg)) {
-        l.append(msg + "\n");
-        rc = BVCF_E_IO;
-      }
-    } else {
-      close(ss_fd);
-    }
-  }
-  if (pr_fd >= 0) {  // --relatedness: the run's pairwise table, after a successful run only
-    if (rc == BVCF_OK) {
-      const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
-      std::vector<uint64_t> t(3 * ns * ns, 0);
-      if (R.ctx && bvcf_pair_stats(R.ctx, t.data(), 0) != BVCF_OK) {
-        l.append(std::string("bvcf_pair_stats: ") + bvcf_last_error(R.ctx) + "\n");
-        rc = BVCF_E_HIP;
-        close(pr_fd);
-      } else if (write_pair_stats(pr_fd, c, R.pre, t.data(), &msg)) {
-        l.append(msg + "\n");
-        rc = BVCF_E_IO;
-      }
-    } else {
-      close(pr_fd);
-    }
-  }
-  if ((R.grm_fd >= 0 || R.pca_vec_fd >= 0) && rc == BVCF_OK) {  // --grm / --pca: the run's matrix, after a successful run only
-    const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
-    std::vector<uint64_t> t(grm_table_words(ns), 0);
-    if (R.ctx && bvcf_grm(R.ctx, t.data(), 0) != BVCF_OK) {
-      l.append(std::string("bvcf_grm: ") + bvcf_last_error(R.ctx) + "\n");
-      rc = BVCF_E_HIP;
-    } else if (R.grm_fd >= 0 && write_grm(R, t.data(), &msg)) {
-      l.append(msg + "\n");
-      rc = BVCF_E_IO;
-    } else if (R.pca_vec_fd >= 0) {  // (the components of the same matrix, solved on the ctx's device)
-      if (const int prc = write_pca(R, t.data(), c->device, &msg)) {
-        l.append(msg + "\n");
-        rc = prc;
-      }
-    }
-  }
-  if (R.score_fd >= 0 && rc == BVCF_OK) {  // --score: the run's scores, after a successful run only
-    const size_t ns = R.pre.header.size() > 9 ? R.pre.header.size() - 9 : 0;
-    std::vector<uint64_t> t(score_table_words(ns, R.score_table.n_columns), 0);
-    if (R.ctx && bvcf_score(R.ctx, t.data(), 0) != BVCF_OK) {
-      l.append(std::string("bvcf_score: ") + bvcf_last_error(R.ctx) + "\n");
-      rc = BVCF_E_HIP;
-    } else if (write_score(R, t.data(), &msg)) {
-      l.append(msg + "\n");
-      rc = BVCF_E_IO;
-    }
-  }
-  if (R.assoc_fd >= 0 && close_assoc(R, rc == BVCF_OK, &msg)) {  // --pheno / --assoc: the last lines and the report
-    l.append(msg + "\n");
-    rc = BVCF_E_IO;
-  }
-  if (sg_fd >= 0) {  // --siteFilterReport: after a successful run only
-    if (rc != BVCF_OK) {
-      close(sg_fd);
-    } else if (write_site_report(sg_fd, gate_counts, &msg)) {
-      l.append(msg + "\n");
-      rc = BVCF_E_IO;
-    }
-  }
-  if (R.variant_fd >= 0 && rc == BVCF_OK && write_variant_report(R, variant_counts, &msg)) {  // --variantFilterReport: likewise
-    l.append(msg + "\n");
-    rc = BVCF_E_IO;
-  }
-  if (R.region_fd >= 0 && rc == BVCF_OK && write_region_report(R, region_counts, &msg)) {  // --regionFilterReport: likewise
-    l.append(msg + "\n");
-    rc = BVCF_E_IO;
-  }
+  // the end of the outputs: the one ctx's tables are the run's sums (--pca solves on the ctx's device)
+  RunSums sums;
+  const bool ran = rc == BVCF_OK;
+  if (ran) rc = sum_run_tables(R, R.ctx, RunSums(), &sums, &msg);
+  rc = finish_outputs(R, rc, &sums, gates, c->device, &msg);
+  if (ran && rc != BVCF_OK) l.append(msg + "\n");  // (a run that had failed has its message in the log already)
   if (R.ctx) bvcf_destroy(R.ctx);
   if (n_lines_in) *n_lines_in = lines_in;
   *out = dup_out(o, n_out);

@@ -1,7 +1,8 @@
 #pragma once
 // bvcf_host_internal.h — declarations shared by the host half of the path: bvcf_host.cpp (TSV assembly entry points, the
-// in-memory driver), bvcf_driver.cpp / bvcf_readers.cpp (the stream driver).  Definitions: bvcf_host_common.cpp.  The
-// counterpart of readVcf's preamble (main.go:241-304) and of processLines' TSV assembly (main.go:566-695).
+// in-memory driver), bvcf_driver.cpp / bvcf_readers.cpp (the stream driver).  Definitions: bvcf_host_common.cpp and, for the
+// side outputs, bvcf_outputs.cpp.  The counterpart of readVcf's preamble (main.go:241-304) and of processLines' TSV assembly
+// (main.go:566-695).
 //
 // Nothing here computes what the kernels compute: rows are assembled from bvcf_result only.
 #include "../../include/bvcf.h"
@@ -23,6 +24,7 @@
 #include <zlib.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -237,6 +239,11 @@ struct Run {
   // then the header with the unselected names cut out, which is what every consumer of the names is to see
   uint32_t n_header_full = 0;
   std::vector<uint32_t> keep_mask;
+  // --sampleStats, --relatedness, --siteFilterReport: opened by open_outputs before any device work, written by finish_outputs
+  int ss_fd = -1, pr_fd = -1, sg_fd = -1;
+  // the per-batch appends that failed: such an output is not appended to again (append_batch_outputs; touched only by the one
+  // thread that appends in input order)
+  bool dosage_failed = false, plink_failed = false, mendel_failed = false, ld_failed = false, assoc_failed = false;
   // --plinkOutput: PREFIX.bed / .bim / .fam, opened by open_plink before any device work; prepare_run writes the .fam and
   // the .bed magic, append_plink a batch's rows and .bim lines in input order, close_plink closes what is open
   int bed_fd = -1, bim_fd = -1, fam_fd = -1;
@@ -297,7 +304,7 @@ struct Run {
   bool logit_on = false, logit_covar = false;
   bvcf_logit_table logit_table{};
   ~Run() {
-    for (int fd : {bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
+    for (int fd : {ss_fd, pr_fd, sg_fd, bed_fd, bim_fd, fam_fd, mendel_fd, mendel_errors_fd, ld_fd, ld_in_fd, ld_out_fd, variant_fd, region_fd, grm_fd,
                    grm_n_fd, grm_id_fd, score_fd, score_report_fd, assoc_fd, assoc_report_fd, pca_vec_fd, pca_val_fd, pca_report_fd})
       if (fd >= 0) close(fd);
     bvcf_ld_seam_destroy(ld_seam);
@@ -357,15 +364,16 @@ struct BatchNeed {
 BatchNeed read_batch_need(bvcf_ctx *ctx, const bvcf_config *c, const bvcf_result &res);
 int reserve_batch_need(bvcf_ctx *ctx, const BatchNeed &n);
 int process_block(Run &R, const uint8_t *block, size_t n, uint64_t seq, bvcf_result *res, std::string *msg);
-// --sampleStats (bvcf_config.sample_stats_path): opened (truncated) before any device work -- *fd = -1 without a path --,
-// and, at the end of a successful run, the table of the summed per-sample counts t (bvcf_sample_stats layout) written
-int open_sample_stats(const bvcf_config *c, int *fd, std::string *msg);
+// --sampleStats (bvcf_config.sample_stats_path): R.ss_fd opened (truncated) before any device work -- left at -1 without a
+// path --, and, at the end of a successful run, the table of the summed per-sample counts t (bvcf_sample_stats layout)
+// written and the file closed
+int open_sample_stats(Run &R, std::string *msg);
 void format_sample_stats(const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string &out);
-int write_sample_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg);
-// --relatedness (bvcf_config_more.pair_stats_path): the same for the pairwise table -- t is the sum of the run's bvcf_pair_stats
-// tables, [3][S][S] over the header's samples; one line per unordered pair, i the outer loop
-int open_pair_stats(const bvcf_config *c, int *fd, std::string *msg);
-int write_pair_stats(int fd, const bvcf_config *c, const Preamble &pre, const uint64_t *t, std::string *msg);
+int write_sample_stats(Run &R, const uint64_t *t, std::string *msg);
+// --relatedness (bvcf_config_more.pair_stats_path): the same for R.pr_fd and the pairwise table -- t is the sum of the run's
+// bvcf_pair_stats tables, [3][S][S] over the header's samples; one line per unordered pair, i the outer loop
+int open_pair_stats(Run &R, std::string *msg);
+int write_pair_stats(Run &R, const uint64_t *t, std::string *msg);
 // bvcf_config_more.pair_stats_path of a config that is the head of one; NULL otherwise
 inline const char *pair_stats_path(const bvcf_config *c) {
   return c->reserved[0] == BVCF_CONFIG_MORE ? reinterpret_cast<const bvcf_config_more *>(c)->pair_stats_path : nullptr;
@@ -513,9 +521,67 @@ inline bool wants_site_report(const bvcf_config *c) {
   const bvcf_config_more *m = gate_config(c);
   return m && m->site_filter_path && *m->site_filter_path;
 }
-// the report file: opened before any device work; counts = the sum of bvcf_site_gate_count over the batches of the output
-int open_site_report(const bvcf_config *c, int *fd, std::string *msg);
-int write_site_report(int fd, const uint64_t counts[7], std::string *msg);
+// the report file (R.sg_fd): opened before any device work; counts = the sum of bvcf_site_gate_count over the batches of the output
+int open_site_report(Run &R, std::string *msg);
+int write_site_report(Run &R, const uint64_t counts[7], std::string *msg);
+
+// ---- the one path of bvcf_run_buffer and of the stream driver through the outputs above (bvcf_outputs.cpp)
+
+// the whole file appended to *text, or one message ("open PATH: ..." / "read PATH: ...") and rc_on_failure
+int read_file(const char *path, std::string *text, std::string *msg, int rc_on_failure);
+// an output file created or emptied: BVCF_E_IO with the message "open PATH: ..."
+int open_truncated(const std::string &path, int *fd, std::string *msg);
+// every output of the run opened and every list they come with read, before any device work, in the order sample stats, pair
+// stats, site report, plink, mendel, ld, variants, regions, grm, score, assoc, pca: the first failing step's code and message
+int open_outputs(Run &R, std::string *msg);
+
+// what the three gates did to the batches of the output (bvcf_site_gate_count / bvcf_variant_gate_count /
+// bvcf_region_gate_count), each counted only when its report is open
+struct GateCounts {
+  uint64_t site[7] = {0, 0, 0, 0, 0, 0, 0}, variant[3] = {0, 0, 0}, region[3] = {0, 0, 0};
+  void add(const Run &R, const bvcf_result &res);
+  GateCounts &operator+=(const GateCounts &o);
+};
+
+// what the ctx reports for the batch collected last, for the outputs written batch by batch (valid as long as its result slot)
+struct BatchOutputs {
+  bvcf_bed_rows_info bed{};             // --plinkOutput
+  bvcf_trio_info trio{};                // --mendel / --mendelErrors
+  bvcf_ld_info ld{};                    // --ld / --ldPrune
+  bvcf_assoc_info assoc{};              // --pheno / --assoc
+  bvcf_assoc_cov_info assoc_cov{};      // --covar
+  bvcf_assoc_logit_info assoc_logit{};  // --assocModel logistic
+};
+// right after the collect: BVCF_E_HIP with "bvcf_X: <the ctx's last error>" for the first getter that fails
+int fetch_batch_outputs(Run &R, bvcf_ctx *ctx, BatchOutputs *b, std::string *msg);
+// true when the batch has something to append in input order
+bool has_batch_outputs(const Run &R, const bvcf_result &res);
+// in input order, on one thread: the batch's dosage rows, .bed rows and .bim lines, trio counts and events, LD events, scan
+// lines.  An output whose append failed is latched in R and left alone from then on; the others are still appended to.
+// BVCF_E_FATAL with the message of the first output that failed in this call
+int append_batch_outputs(Run &R, const bvcf_result *res, const uint8_t *text, const BatchOutputs &b, std::string *msg);
+
+// The tables a run sums over its ctxs and writes at the end: what each needs in one place
+struct RunTable {
+  const char *getter;                                                               // its name, for messages
+  int (*get)(bvcf_ctx *, uint64_t *out, int reset);                                 // bvcf_sample_stats, ...
+  bool (*on)(const Run &);                                                          // the run writes it
+  size_t (*words)(const Run &);                                                     // of one table
+  void (*add)(const Run &, std::vector<uint64_t> &sum, const uint64_t *t);          // sum += t (sum sized on the way)
+  int (*write)(Run &, const uint64_t *sum, int pca_device, std::string *msg);       // the output(s) written and closed
+};
+enum { kRunTableCount = 4 };
+const RunTable *run_tables();  // kRunTableCount of them
+typedef std::array<std::vector<uint64_t>, kRunTableCount> RunSums;
+// A ctx is about to drop the batches in flight and take them again (a reservation grows): before the drain its tables are
+// added to *carry and reset; after it (drained) they are reset again, so that the dropped batches count once
+int carry_run_tables(const Run &R, bvcf_ctx *ctx, RunSums *carry, bool drained, std::string *msg);
+// a ctx's tables and what was carried for it added into the run's sums
+int sum_run_tables(const Run &R, bvcf_ctx *ctx, const RunSums &carry, RunSums *sums, std::string *msg);
+// Every end-of-run step, once: dosage and plink closed; the run tables, the scan's last lines and report, the three gate
+// reports, the mendel and ld files written when the run succeeded (rc == BVCF_OK) and nothing before failed -- otherwise the
+// files stay empty.  Needs no device but for --pca.  Returns the run's code: rc, or the failing step's with its message
+int finish_outputs(Run &R, int rc, RunSums *sums, const GateCounts &gates, int pca_device, std::string *msg);
 
 // a bounded FIFO between pipeline stages
 template <class T>

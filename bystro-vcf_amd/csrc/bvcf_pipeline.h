@@ -181,12 +181,7 @@ struct FmtJob {
   Block b;
   bvcf_result res;
   bool has_res = false;
-  bvcf_bed_rows_info bed{};  // --plinkOutput: bvcf_bed_rows of the batch (valid as long as res)
-  bvcf_trio_info trio{};     // --mendel / --mendelErrors: bvcf_trio_stats of the batch (likewise)
-  bvcf_ld_info ld{};         // --ld / --ldPrune: bvcf_ld_stats of the batch (likewise)
-  bvcf_assoc_info assoc{};   // --pheno / --assoc: bvcf_assoc of the batch (likewise)
-  bvcf_assoc_cov_info assoc_cov{};  // --covar: bvcf_assoc_cov of the batch (likewise)
-  bvcf_assoc_logit_info assoc_logit{};  // --assocModel logistic: bvcf_assoc_logit of the batch (likewise)
+  BatchOutputs outputs;  // what the ctx reported with the batch for the outputs appended in input order (valid as long as res)
   uint64_t job = 0;  // its number among the worker's collected batches
   bool end = false;
 };
@@ -213,15 +208,10 @@ struct DevWorker {
   // timing
   double t_warm = 0, t_ctx = 0, t_submit = 0, t_gpu = 0, t_fmt_wait = 0, t_first_submit = 0, t_starved = 0, t_fmt = 0, t_read = 0;
   uint64_t n_blocks = 0, n_bytes = 0;
-  // --sampleStats: the counts of batches collected before a reservation grew (the ctx's totals are reset then, because the
-  // batches in flight are collected, dropped and submitted again)
-  std::vector<uint64_t> ss_carry;
-  std::vector<uint64_t> pr_carry;  // --relatedness: the same for the pair tables
-  std::vector<uint64_t> score_carry;  // --score: the same for the scores' words (added with add_score_words: T is 128 bits)
-  std::vector<uint64_t> grm_carry;  // --grm: the same for the GRM's tables (added with add_grm_table: T is 128 bits)
-  uint64_t gate_counts[7] = {0, 0, 0, 0, 0, 0, 0};  // --siteFilterReport: bvcf_site_gate_count over the batches handed to the formatter
-  uint64_t variant_counts[3] = {0, 0, 0};           // --variantFilterReport: bvcf_variant_gate_count over the same batches
-  uint64_t region_counts[3] = {0, 0, 0};            // --regionFilterReport: bvcf_region_gate_count over the same batches
+  // the run tables (run_tables()) of the batches collected before a reservation grew: the ctx's totals are reset then, because
+  // the batches in flight are collected, dropped and submitted again
+  RunSums carry;
+  GateCounts gates;  // the three gate reports: over the batches handed to the formatter
 };
 
 enum Mode { kStream = BVCF_MODE_STREAM, kRangeText = BVCF_MODE_TEXT_RANGES, kRangeBgzf = BVCF_MODE_BGZF_RANGES };
@@ -231,11 +221,6 @@ class Driver {
  public:
   Driver(const bvcf_config *c, int fd_in, int fd_out, int fd_err, bool dry = false, unsigned dry_workers = 1,
          int dry_device_inflate = 1);
-  ~Driver() {
-    if (ss_fd_ >= 0) close(ss_fd_);  // (a run that ended before its table was written)
-    if (pr_fd_ >= 0) close(pr_fd_);
-    if (sg_fd_ >= 0) close(sg_fd_);
-  }
   int run(uint64_t *n_lines_in);
   // bvcf_plan_fd: the blocks the workers received, in (range, piece) order
   std::vector<bvcf_plan_block> dry_blocks;
@@ -287,9 +272,6 @@ class Driver {
   std::mutex fail_mu_;
   int rc_ = BVCF_OK;
   std::string log_;
-  int ss_fd_ = -1;  // --sampleStats
-  int pr_fd_ = -1;  // --relatedness
-  int sg_fd_ = -1;  // --siteFilterReport
   std::atomic<bool> failed_{false};
   // what the workers wait for: the header is known, the ctx parameters are set, the ranges are laid out
   struct {
@@ -304,11 +286,6 @@ class Driver {
   size_t text_in_flight_ = 2, bgzf_in_flight_ = 3;
   std::atomic<bool> input_is_bgzf_device_{false};
   std::atomic<uint8_t> eol_byte_{'\n'};
-  std::atomic<bool> dosage_failed_{false};
-  std::atomic<bool> plink_failed_{false};  // --plinkOutput: likewise
-  std::atomic<bool> mendel_failed_{false};  // --mendel / --mendelErrors: likewise
-  std::atomic<bool> ld_failed_{false};      // --ld / --ldPrune: likewise
-  std::atomic<bool> assoc_failed_{false};   // --pheno / --assoc: likewise
   // stream mode
   std::string source_err_;
   std::unique_ptr<Channel<Block>> ready_q_;
