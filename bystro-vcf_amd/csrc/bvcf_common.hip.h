@@ -123,6 +123,8 @@ struct KernelArgs {
   uint32_t *real_tasks;  // [max_tasks] streaming path: the task slots past n_lines that hold a scan (or kNoTask), see k_head
   uint32_t *left_lines;  // [max_lines] streaming path: the lines k_order left to k_head, in no particular order (counters->n_left)
   uint32_t head_fast;    // 1: k_order settles plain SNP lines itself (bvcf_headfast.hip.h); 0: it lists every line for k_head
+  uint32_t pend_epoch_ticks;  // k_stream: its pending result stores leave when the 100 MHz wall clock crosses a multiple of this
+                              // (0: no clock; 1: at every look, see bvcf_stream.hip.h)
   // k_sites1: the FILTER gate of the common lines as dwords (see bvcf_sites1.hip.h; 0 = no such table, 1 = keys, 2 = no test)
   uint32_t s1_fmode;
   uint32_t s1_fkey[4], s1_flen[4];

@@ -154,6 +154,10 @@ struct bvcf_ctx : bvcf_ctx_plan {
   int gt_subset_grid = 0;  // k_gt_subset / k_dosage_subset
   Stream scan_stream;  // see launch_stream
   uint32_t stream_lds_pad = 0;  // dynamic LDS asked for with k_stream (it uses none): caps the k_stream workgroups of ALL batches per CU
+  // k_stream's pending result stores leave at multiples of this many ticks of the 100 MHz wall clock (KernelArgs.pend_epoch_ticks;
+  // 32 us, which the log of 256 pieces reaches: profiles/k_stream_store_windows.txt).  BVCF_PEND_EPOCH_TICKS (test / tuning):
+  // 0 = no clock, 1 = at every look
+  uint32_t pend_epoch_ticks = 3200u;
   // streaming path: which kernel walks the next batch (gen_mode) -- k_stream (made for the 4-byte sample grid; other lines
   // are left to k_gt) or k_stream_gen (any fields, one pass).  Adaptive: a batch whose lines were mostly of the other
   // kernel's shape switches (the results are the same either way); BVCF_GEN_STREAM=0 / 1 pins it.
@@ -604,6 +608,7 @@ KernelArgs make_args(bvcf_ctx *c, Slot &s, const uint8_t *d_src, size_t nbytes) 
   a.real_tasks = s.d_finish_items ? s.d_finish_items + c->max_lines : nullptr;  // (one allocation: [max_lines] + [max_alleles])
   a.left_lines = s.d_left_lines;
   a.head_fast = c->head_fast ? 1u : 0u;
+  a.pend_epoch_ticks = c->pend_epoch_ticks;
   a.s1_fmode = c->s1_fmode;
   for (int i = 0; i < 4; i++) {
     a.s1_fkey[i] = c->s1_fkey[i];
@@ -1344,6 +1349,8 @@ int open_device(bvcf_ctx *c) {
   c->stream_lds_pad = (uint32_t)env_int("BVCF_EXP_STREAM_LDS", 0);
 #endif
   c->stream_grid = c->n_cu * per_cu;
+  const int pend_epoch = env_int("BVCF_PEND_EPOCH_TICKS", -1);
+  if (pend_epoch >= 0) c->pend_epoch_ticks = (uint32_t)pend_epoch;
   per_cu = std::min(wgs_per_cu(k_stream_gen, kWgThreads, gen_lds_bytes(c->n_samples), 2), 6);  // (7 fit a cohort of a few thousand samples; 6 measured best)
 #ifdef BVCF_EXPERIMENTS
   const int gen_wgs = env_int("BVCF_GEN_WGS", 0);  // experiment: workgroups per CU
@@ -2482,6 +2489,22 @@ extern "C" int bvcf_debug_gt_kinds(unsigned int out[4]) {
   const unsigned int z[4] = {0, 0, 0, 0};
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(bvcf_dev::g_gt_kinds), sizeof(z), 0, hipMemcpyDeviceToHost) != hipSuccess) return BVCF_E_HIP;
   return hipMemcpyToSymbol(HIP_SYMBOL(bvcf_dev::g_gt_kinds), z, sizeof(z), 0, hipMemcpyHostToDevice) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
+}
+#endif
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_COUNTS)
+// k_stream's log flushes since the last call: [0..3] flushes by cause, [4..7] the pieces they stored (see g_pend_counts)
+extern "C" int bvcf_debug_pend_counts(unsigned long long out[8]) {
+  const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(bvcf_dev::g_pend_counts), sizeof(z), 0, hipMemcpyDeviceToHost) != hipSuccess) return BVCF_E_HIP;
+  return hipMemcpyToSymbol(HIP_SYMBOL(bvcf_dev::g_pend_counts), z, sizeof(z), 0, hipMemcpyHostToDevice) == hipSuccess ? BVCF_OK : BVCF_E_HIP;
+}
+// resident workgroups per CU of the kernels that share a CU with blocks in flight, as the runtime counts them
+extern "C" int bvcf_debug_occupancy(int out[3]) {
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[0], bvcf_dev::k_stream, kWgThreads, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[1], bvcf_dev::k_head_lean, kWgThreads, 0) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[2], bvcf_dev::k_gt, kWgThreads, 0) != hipSuccess)
+    return BVCF_E_HIP;
+  return BVCF_OK;
 }
 #endif
 #ifdef BVCF_EXP_TIMES

@@ -190,14 +190,29 @@ __device__ __forceinline__ void flush_stage(const uint8_t *stage, uint8_t *cmap,
 // ---- k_stream's pending-store log (the pipelined path, bvcf_stream.hip.h)
 // A pipelined line leaves four kinds of result stores: its entry, its head TAB bitmap, ALT #1's class list or dense map.
 // They are not issued per line: they are appended, as 16-byte pieces with a 4-byte tag each (destination array and the
-// offset in it, in pieces), to a log in the part of the wave's stage that lines of <= 16 chunks never touch (zero_stage
-// and flush_stage stay within its first 1 KiB), and k_stream stores the whole log at once (pend_flush, see there).
-constexpr uint32_t kPendBase = 1024u;   // the log's pieces: stage bytes [1024, 3424)
-constexpr uint32_t kPendPieces = 150u;  // an average cohort line leaves 18, a dense-map line of 2 504 samples 44
-constexpr uint32_t kPendTags = kPendBase + 16u * kPendPieces;  // their tags: [3424, 4024)
+// offset in it, in pieces), to a log in the wave's LDS, and k_stream stores the whole log at once (pend_flush, see there).
+// The log starts in the part of the wave's stage that lines of <= 16 chunks never touch (zero_stage and flush_stage stay
+// within its first 1 KiB) and runs on into LDS of its own behind the stage: k_stream gives every wave kPendLdsBytes,
+// the other kernels' stage stays kStageBytes.
+// Capacity: the log is meant to reach the next epoch boundary (32 us, bvcf_stream.hip.h), not to fill.  An average cohort
+// line leaves 18 pieces and a dense-map line of 2 504 samples 44; with three blocks in flight a wave collects about 50
+// pieces per 16 us.  Counted on configs[2] (profiles/k_stream_store_windows.txt): at 16 us the 150 pieces that the stage's
+// spare 3 KiB hold were enough (0.4 % of the flushes came from the capacity rule); at 32 us they are not (21.7 % of the
+// flushes, 34.8 % of the pieces), and 256 are (0.5 % / 1.2 %).  256 pieces are 5 KiB, 2 KiB per wave more than the stage:
+// k_stream's workgroup has 29 KiB and stays below 32 KiB (three of them and two of k_head_lean on a CU; 384 pieces would
+// need 39 KiB).  Experiment builds choose with -DBVCF_EXP_PEND_PIECES=n.
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_PIECES)
+constexpr uint32_t kPendPieces = BVCF_EXP_PEND_PIECES;
+#else
+constexpr uint32_t kPendPieces = 256u;
+#endif
+constexpr uint32_t kPendBase = 1024u;                          // the log's pieces: bytes [1024, 1024 + 16 kPendPieces) of the wave's LDS
+constexpr uint32_t kPendTags = kPendBase + 16u * kPendPieces;  // their tags, 4 bytes each, behind them
+constexpr uint32_t kPendEnd = kPendTags + 4u * kPendPieces;
+constexpr uint32_t kPendLdsBytes = kPendEnd > kStageBytes ? (kPendEnd + 15u) & ~15u : kStageBytes;  // k_stream's stage + log, per wave
 constexpr uint32_t kPendEntries = 0u << 30, kPendHeadBits = 1u << 30, kPendCmap = 2u << 30;  // tag: array | piece offset
 constexpr uint32_t kPendOffMask = (1u << 30) - 1u;
-static_assert(kPendTags + 4u * kPendPieces <= kStageBytes, "the log lives in the stage");
+static_assert(kWavesPerWg * (kPendLdsBytes + sizeof(RawList)) <= 32768u, "k_stream: at most 32 KiB of LDS per workgroup (stage + log, raw list)");
 struct PendLog {
   u32x4 *data;     // the pieces
   uint32_t *tag;   // ... and their tags

@@ -121,20 +121,34 @@ constexpr int kPipeChunks = 10;  // chunk registers of the cross-line pipeline: 
 //   * at the end of a line after which the largest line of the geometry would no longer fit,
 //   * on every exit from the pipeline, and ahead of every store the pipeline still makes directly (further alleles'
 //     lists, raw_save), so that the log never outlives the order the stores had,
-//   * when the 100 MHz wall clock, which all waves of the chip read alike, has crossed a multiple of the epoch since
-//     the wave last looked: all waves then write within the same few microseconds, and between epochs the memory
-//     controllers see reads only.
+//   * when the 100 MHz wall clock, which all waves of the chip read alike, has crossed a multiple of the epoch
+//     (KernelArgs.pend_epoch_ticks, absolute ticks) since the wave last looked: all waves then write within the same
+//     window, and between epochs the memory controllers see reads only.  The wave looks after
+//     every line (experiment builds: also after every kPendLook-th chunk inside it; the window is as wide as the time
+//     between two looks, and narrowing it below a line's 3 us measured nothing).
 // Off the per-line path the stores also leave the vmcnt queue the chunk loads wait on.
 constexpr uint32_t kPendRounds = (kPendPieces + kWave - 1u) / kWave;
 static_assert(kPipeChunks <= 16, "pipelined lines keep to the stage's first 1 KiB");
 static_assert(sizeof(StreamEntry) == 32, "an entry is two pieces");
-// epoch in ticks of the wall clock (100 MHz); 0 = no clock: flush when full and at exits only.  Measured at 8, 16 and 32 us
-// and without the clock (profiles/k_stream_pending_stores.txt); experiment builds choose with -DBVCF_EXP_PEND_EPOCH_US=n
-#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_EPOCH_US)
-constexpr uint32_t kPendEpochTicks = 100u * (BVCF_EXP_PEND_EPOCH_US);
+// the largest line the pipeline admits: entry, head bitmap and a dense map of kPipeChunks chunks (pend_line_max below).
+// The log is emptied at a line's end when another such line would not fit: capacity must hold at least one.
+constexpr uint32_t kPendLineMax = 4u + kPipeChunks * 64u / 16u;
+static_assert(kPendLineMax <= kPendPieces, "the log holds the largest pipelined line");
+// chunks between two looks at the clock inside a line; 0 = only at the line's end.  Swept over 0, 1, 2 and 5 at epochs of
+// 16, 32 and 64 us: level with each other within the run-to-run spread at every epoch (profiles/k_stream_store_windows.txt),
+// so the product looks once per line and carries no flush inside the chunk loop.  Experiment builds choose with
+// -DBVCF_EXP_PEND_LOOK=n
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_LOOK)
+constexpr int kPendLook = BVCF_EXP_PEND_LOOK;
 #else
-constexpr uint32_t kPendEpochTicks = 1600u;
+constexpr int kPendLook = 0;
 #endif
+// -DBVCF_EXPERIMENTS -DBVCF_EXP_PEND_COUNTS: flushes that stored something, by cause (epoch, capacity, exit, ahead of a
+// direct store), and the pieces they stored; read and zeroed by bvcf_debug_pend_counts (tools/pend_counts.py)
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_COUNTS)
+__device__ unsigned long long g_pend_counts[8];
+#endif
+enum PendCause { kPendByEpoch = 0, kPendByCapacity = 1, kPendByExit = 2, kPendByDirect = 3 };
 
 // -DBVCF_EXP_TIMES: per-wave start/end wall clock, hardware placement and time per pipeline phase
 // (s_memtime stamps), read back through bvcf_debug_* by tools/wave_times.py.  Not part of the product.
@@ -166,7 +180,8 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
   }
   unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_readcyclecounter();
 #endif
-  __shared__ __attribute__((aligned(16))) uint8_t s_stage[kWavesPerWg][kStageBytes];
+  // (the stage proper is the first kStageBytes; the pending-store log starts in its spare part and runs on behind it)
+  __shared__ __attribute__((aligned(16))) uint8_t s_stage[kWavesPerWg][kPendLdsBytes];
   __shared__ __attribute__((aligned(16))) RawList s_sparse[kWavesPerWg];
   uint8_t *stage = s_stage[wave_in_wg()];
   RawList *sparse = &s_sparse[wave_in_wg()];
@@ -237,12 +252,20 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
   };
   // the pending-store log
   PendLog pl = {reinterpret_cast<u32x4 *>(stage + kPendBase), reinterpret_cast<uint32_t *>(stage + kPendTags), 0u, 0u};
-  uint32_t pend_epoch = 0;
   // pieces of the largest line of the pipeline: entry, bitmap, and a map (a list is four pieces at most)
-  const uint32_t pend_line_max = 4u + max(4u, min(n_chunks * 64u, a.cmap_stride) / 16u);
-  // Lane i stores pieces i, i + 64 and i + 128.  A fixed number of masked rounds, not a loop over the count: the stores of a
+  const uint32_t pend_line_max = 4u + max(4u, min(n_chunks * 64u, a.cmap_stride) / 16u);  // (<= kPendLineMax)
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_COUNTS)
+  uint32_t pend_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+  // Lane i stores pieces i, i + 64, i + 128, ...  A fixed number of masked rounds, not a loop over the count: the stores of a
   // flush are then a count hipcc's s_waitcnt insertion knows (see run_pipeline on the unconditional chunk loads).
-  auto pend_flush = [&]() {
+  auto pend_flush = [&](PendCause cause) {
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_COUNTS)
+    if (pl.n) {
+      pend_cnt[cause]++;
+      pend_cnt[4 + cause] += pl.n;
+    }
+#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -259,6 +282,25 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     pl.n = 0;
+  };
+  // The clock.  pend_next is the absolute tick of the next epoch boundary: boundaries are multiples of the epoch in ticks of
+  // the wall clock, which is what makes all waves of all blocks in flight agree on them without talking.  A look is a clock
+  // read, a subtract and a compare on scalars; the division is done here and once per boundary crossed.  (The low 32 bits
+  // of the clock: only differences are compared.)  Epoch 0: no clock, the log leaves when full and at exits only; epoch 1:
+  // every look finds a boundary (the tests place flushes with it).
+  const uint32_t epoch = a.pend_epoch_ticks;
+  auto pend_boundary = [&](uint32_t now) -> uint32_t { return epoch <= 1u ? now : now - now % epoch + epoch; };
+  uint32_t pend_next = (pipelined && epoch) ? pend_boundary((uint32_t)wall_clock64()) : 0u;
+  // A look may come anywhere before a line's last chunk: pend_map and pend_list append at the last chunk or behind it, so
+  // until then everything in the log belongs to lines already committed.
+  auto pend_look = [&]() {
+    if (epoch) {
+      const uint32_t now = (uint32_t)wall_clock64();
+      if ((int32_t)(now - pend_next) >= 0) {
+        pend_flush(kPendByEpoch);
+        pend_next = pend_boundary(now);
+      }
+    }
   };
   // list a line (in input order) in the tile it starts in
   // bits_ok: `bits` is the TAB mask of the line's head window (head_window16), one 16-bit piece per lane 0..15
@@ -416,6 +458,9 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
                          &pl);
             }
             va[g] = chunk_at(s_next, g);
+            // (the flush is conditional work younger than every load waited for below: the waits keep their counts)
+            if constexpr (kPendLook > 0)
+              if ((g + 1) % (kPendLook > 0 ? kPendLook : 1) == 0 && g + 1 < kLoads) pend_look();
           }
           STAMP(3);
           // a line that ends in list mode: its entries classified now, for ALT #1 and -- while ALT #1's list fits -- every
@@ -431,7 +476,7 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
             if (cm_next + 1u + raw_slots + reserve > cm_end || cmap_of(a, cm_next + raw_slots, true) == BVCF_NO_CMAP) return nullptr;
             return cm + a.cmap_stride;
           };
-          auto before_direct = [&]() { pend_flush(); };
+          auto before_direct = [&]() { pend_flush(kPendByDirect); };
           if (sparse_ok && acc.n_sp < kDenseMode) {
             enc = finish_list(sparse, acc, cm, min(kListAlleles, a.cmap_stride / (4u * kSparseWords)), stage, nc, a.cmap_stride,
                               acc.n_sp > BVCF_CMAP_SPARSE_MAX ? raw_area() : nullptr, &pl, before_direct);
@@ -454,13 +499,8 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
           // (offsets are multiples of 16: the low bits tell k_head what finish_list left in the slot, see there)
           commit(pA, peA, st, false, cmA == BVCF_NO_CMAP ? cmA : cmA | enc, bitsA, mtA, n_slots, true);
           // the log leaves at the epoch, or when the largest line there can be would not fit behind this one
-          bool leave = pl.n + pend_line_max > kPendPieces;
-          if constexpr (kPendEpochTicks != 0u) {
-            const uint32_t ep = (uint32_t)wall_clock64() / kPendEpochTicks;
-            leave |= ep != pend_epoch;
-            pend_epoch = ep;
-          }
-          if (leave) pend_flush();
+          pend_look();
+          if (pl.n + pend_line_max > kPendPieces) pend_flush(kPendByCapacity);
           p = peA + 1u;
           if (!b_ok) {
             s_begin = kNone;  // nothing pending: rediscover from p
@@ -492,7 +532,7 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
         default: run_pipeline(std::integral_constant<int, 10>{}); break;
       }
       static_assert(kPipeChunks == 10, "the dispatch above covers 1..10 chunks");
-      pend_flush();  // every exit: a line that was not regular after all, no B, the run's end
+      pend_flush(kPendByExit);  // every exit: a line that was not regular after all, no B, the run's end
       if (s_begin == kNone) continue;
       // fall through with (p, s_begin) of the line that failed the regular scan
     } else if (pred + a.eol_chars <= nb) {
@@ -543,6 +583,11 @@ __global__ __launch_bounds__(kWgThreads) void k_stream(KernelArgs a) {
   if (lane == 0) a.run_lines[wave] = n_listed;  // (every wave of the grid, with or without tiles: k_order adds them up)
   if (lane == 0 && seen) atomicAdd(&a.counters->lines_seen, seen);
   if (lane == 0 && n_other) atomicAdd(&a.counters->n_other_shape, n_other);
+#if defined(BVCF_EXPERIMENTS) && defined(BVCF_EXP_PEND_COUNTS)
+#pragma unroll
+  for (int k = 0; k < 8; k++)
+    if (lane == 0 && pend_cnt[k]) atomicAdd(&g_pend_counts[k], (unsigned long long)pend_cnt[k]);
+#endif
 #ifdef BVCF_EXP_TIMES
   if (lane == 0) {
     g_wave_t[1][wave] = wall_clock64();
